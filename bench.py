@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the ray-transport hot path on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR] [--full]
 
 N = 1 (default)  BASELINE config 2, the headline metric: Msamples/s on the Cornell box (scenes/cbox.xml geometry),
                  512 x 512, 256 spp, path max_depth 6, tent filter.  One step = one full render, scene and all path
@@ -19,11 +19,19 @@ N > 1            BASELINE config 5: the same scene at 4096 x 4096, 1024 spp (17.
                  reduce(sum)) | testring (config 4: TestRing/TestRing.obj, 1024 x 1024, 512 spp, LDS-resident BVH;
                  N > 1: bands + gather).  Default: cbox at N = 1, cbox4k at N > 1.
 
-With no --config at N = 1 the line also carries `also`: the other named scenes of BASELINE.json (us_sphere_box = config 3,
-testring = config 4, cbox4k = config 5 on one GPU), 3 steps each after the headline steps, each with its own roofline and its L2
-against the CPU port on a bounded sample; `seeds`: the headline render at seeds 1 and 2; and `scale_ref`: the
-N = 1 value of the workload `--gpus N > 1` runs (cbox4k), so that a scaling curve has its own one-GPU point on the line.  At N > 1
-the line carries `speedup_vs_scale_ref` when PBRT_SCALE_REF_MSAMPLES hands that value over.
+A plain run sets up, warms up, times the K steps and prints its line; everything else is behind --full.
+--full           also measure what the headline does not need: `cpu_baseline` / `l2_vs_cpu_ref` (the CPU port on a bounded
+                 sample, rank 0, N = 1 only), and with no --config at N = 1 `also`: the other named scenes of BASELINE.json
+                 (us_sphere_box = config 3, testring = config 4, cbox4k = config 5 on one GPU), 3 steps each after the headline
+                 steps, each with its own roofline and its L2 against the CPU port on a bounded sample; `seeds`: the headline
+                 render at seeds 1 and 2; and `scale_ref`: the N = 1 value of the workload `--gpus N > 1`
+                 runs (cbox4k), so that a scaling curve has its own one-GPU point on the line.  --no-cpu-baseline and
+                 --no-also leave parts of it out again.
+--dump-outputs DIR  after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
+                 (float32): film.npy (radiance, [H, W, 3]), channel_buffer.npy (ultrasound, [angles, elements, T]) or
+                 image.npy (usmain_loop, the display image of the headline size).  An array above 64 MB is written as a
+                 fixed, seeded sample of its elements, <name>_sample.npy, with their flat indices in <name>_sample_index.npy.
+At N > 1 the line carries `speedup_vs_scale_ref` when PBRT_SCALE_REF_MSAMPLES hands that value over.
 
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   roofline     -- the dominant kernels (k_bounce / k_us_bounce / k_trace_primary + k_trace + k_shade), bound = "hbm" as the contract
@@ -36,8 +44,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                   valu_issue_busy x lane_active, the share of the chip's 78.6 T f32 lane-slots per second that did work; same
                   file, same hash guard, null when not recorded).
   per_rank_ms  -- N > 1: every rank's render / acquisition time per step and (collective_ms) its time in the gather / reduce.
-  cpu_baseline -- the CPU oracle (C++ port of the same algorithm, same RNG: the reference's Python / Mitsuba path
-                  cannot run on this box) on the host cores, on a bounded sample of the same workload (~15 s), rank 0,
+  cpu_baseline -- --full only: the CPU oracle (C++ port of the same algorithm, same RNG: the reference's Python / Mitsuba
+                  path cannot run on this box) on the host cores, on a bounded sample of the same workload (~15 s), rank 0,
                   N = 1 only; the same run gives the per-pixel L2 between the HIP result and the CPU result.
 """
 from __future__ import annotations
@@ -111,6 +119,25 @@ def kernel_source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as float32 DIR/<name>.npy; one above DUMP_MAX_BYTES as a fixed, seeded sample of
+    DUMP_SAMPLE elements (<name>_sample.npy) and their flat indices (<name>_sample_index.npy, float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes <= DUMP_MAX_BYTES:
+            np.save(os.path.join(dirname, name + ".npy"), a)
+            continue
+        idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(dirname, name + "_sample.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(dirname, name + "_sample_index.npy"), idx.astype(np.float64))
+
+
 def visible_gpu_count():
     """GPUs this process would see, counted WITHOUT loading a GPU runtime: the KFD topology in sysfs (a node with
     simd_count > 0 is a GPU; CPUs are nodes too), narrowed by HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES when they are
@@ -167,11 +194,14 @@ def launch_ranks(args, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=0, help="0: 10 for cbox / us_sphere_box, 3 for the larger workloads")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 10 for cbox / us_sphere_box, 3 for the larger workloads, "
+                                                                "20 for usmain_loop)")
     ap.add_argument("--warmup", type=int, default=-1, help="-1: 2 for cbox / us_sphere_box, 1 for the larger workloads")
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="N = 1 default run: only the headline, not the other named scenes / seeds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and, N = 1 default run, the other named scenes / seeds")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full, N = 1 default run: only the headline, not the other named scenes / seeds")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU work of the cpu_baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: min(visible cores, 64)")
     ap.add_argument("--res", type=int, default=0, help="override the film size (rehearsals only: not the named workload)")
@@ -183,6 +213,8 @@ def main():
                     help="multi-rank rehearsal on a 1-GPU box: every rank uses device 0 and the collective runs over gloo "
                          "(host staging); exercises sharding + stitching, NOT RCCL -- numbers are not benchmark numbers")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -203,7 +235,7 @@ def main():
     if args.spp:
         cfg["spp" if cfg["kind"] == "radiance" else "ppr"] = args.spp
     big = name in ("cbox4k", "testring")
-    steps = args.steps or (3 if big else 10)
+    steps = args.steps if args.steps is not None else (3 if big else 10)
     warmup = args.warmup if args.warmup >= 0 else (1 if big else 2)
 
     import numpy as np
@@ -228,14 +260,16 @@ def main():
     if cfg["kind"] == "usmain_loop":
         if world > 1:
             sys.exit("bench.py --config usmain_loop: the reference's optimisation loop is one serial chain of renders (replicas only)")
-        out = measure_usmain_loop(env, cfg, args.steps or 20, args.warmup if args.warmup >= 0 else 3, with_cpu=not args.no_cpu_baseline)
+        out = measure_usmain_loop(env, cfg, args.steps if args.steps is not None else 20, args.warmup if args.warmup >= 0 else 3,
+                                  with_cpu=args.full and not args.no_cpu_baseline, dump_dir=args.dump_outputs)
         print(json.dumps(out), flush=True)
         if force:
             dist.barrier()
             dist.destroy_process_group()
         return out
-    out = measure(env, name, cfg, steps, warmup, seed=0, overridden=overridden, with_cpu=(world == 1 and not args.no_cpu_baseline))
-    if rank == 0 and world == 1 and args.config is None and not overridden and not args.no_also:
+    out = measure(env, name, cfg, steps, warmup, seed=0, overridden=overridden,
+                  with_cpu=(world == 1 and args.full and not args.no_cpu_baseline), dump_dir=args.dump_outputs)
+    if rank == 0 and world == 1 and args.config is None and not overridden and args.full and not args.no_also:
         # the driver runs this command once: the other named scenes of BASELINE.json ride on the same line (three timed steps after
         # TWO warm-up steps: after the CPU legs of the entry before, the first acquisition or two run ~10 % slow -- clocks,
         # tools/idle_gap_probe.py)
@@ -282,8 +316,9 @@ def main():
     return out
 
 
-def measure(env, name, cfg, steps, warmup, seed, overridden, with_cpu, cpu_seconds=None):
-    """W untimed + K timed steps of one named workload; rank 0 gets the result record (others None)."""
+def measure(env, name, cfg, steps, warmup, seed, overridden, with_cpu, cpu_seconds=None, dump_dir=None):
+    """W untimed + K timed steps of one named workload; rank 0 gets the result record (others None) and writes the last
+    step's result to dump_dir when it is given."""
     mi, par, np, torch, dist = env["mi"], env["par"], env["np"], env["torch"], env["dist"]
     device, rank, world, args = env["device"], env["rank"], env["world"], env["args"]
     radiance = cfg["kind"] == "radiance"
@@ -410,6 +445,8 @@ def measure(env, name, cfg, steps, warmup, seed, overridden, with_cpu, cpu_secon
 
     out = None
     if rank == 0:
+        if dump_dir:
+            dump_outputs(dump_dir, {"film" if radiance else "channel_buffer": result.detach().cpu().numpy()})
         ms = dt / steps * 1e3
         value = total_units / (dt / steps) / 1e6
         achieved = (acc["bounce_bytes"] / 1e9) / (acc["bounce_ms"] / 1e3) if acc["bounce_ms"] > 0 else 0.0
@@ -506,7 +543,7 @@ def measure(env, name, cfg, steps, warmup, seed, overridden, with_cpu, cpu_secon
     return out
 
 
-def measure_usmain_loop(env, cfg, steps, warmup, with_cpu):
+def measure_usmain_loop(env, cfg, steps, warmup, with_cpu, dump_dir=None):
     """One step = one iteration of the reference's finite-difference loop (USMain.py:279-283): forward(rough) and
     forward(rough + eps), each params.update() + us_render (acquisition -> DAS -> envelope -> log compression -> the display image
     on the host).  Timed at paths_per_ray 1 (the reference's own: one ray per (angle, element)), 64 and 4096; the value of the line is
@@ -551,6 +588,8 @@ def measure_usmain_loop(env, cfg, steps, warmup, with_cpu):
             img = iteration(ppr, 0.1 + 0.01 * i, acc)
         ctx.synchronize()
         dt = time.perf_counter() - t0
+        if dump_dir and not sizes:  # the headline size (the value of the line)
+            dump_outputs(dump_dir, {"image": np.asarray(img)})
         # the same loop with every call of the chain queued one by one (no recording): the before / after of the hipGraph replay
         t0 = time.perf_counter()
         for i in range(steps):

@@ -48,3 +48,26 @@ def test_tool_scripts_compile():
     assert len(scripts) >= 20
     for f in scripts:
         compile(open(f).read(), f, "exec")      # (syntax only: nothing is imported, nothing is written)
+
+
+def test_steps_below_one_are_refused():
+    """--steps is the number of timed steps: 0 is an error, not a default"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_writes_float32_and_a_seeded_sample_of_a_large_array(tmp_path):
+    import numpy as np
+    import bench
+    small = np.arange(12, dtype=np.float64).reshape(2, 2, 3)
+    big = np.arange(bench.DUMP_MAX_BYTES // 4 + 1, dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"film": small, "channel_buffer": big})
+    film = np.load(tmp_path / "a" / "film.npy")
+    assert film.dtype == np.float32 and np.array_equal(film, small)
+    assert not (tmp_path / "a" / "channel_buffer.npy").exists()
+    s, i = np.load(tmp_path / "a" / "channel_buffer_sample.npy"), np.load(tmp_path / "a" / "channel_buffer_sample_index.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and len(s) == len(i) == bench.DUMP_SAMPLE
+    assert np.all(np.diff(i) > 0) and np.array_equal(s, big[i.astype(np.int64)])
+    assert np.array_equal(i, np.load(tmp_path / "b" / "channel_buffer_sample_index.npy"))        # the same sample every run
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES

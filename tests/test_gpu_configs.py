@@ -156,3 +156,22 @@ def test_rccl_path_runs_beside_the_library_at_world_size_one(tmp_path):
         out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
         assert out["collective"]["backend"] == "nccl" and out["collective"]["world_size"] == 1
         assert out["n_gpus"] == 1 and out["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(mi, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: K timed steps, the headline line without what --full adds, and
+    --dump-outputs writes the film the last timed step returned (bit-identical to the same render through the package)"""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "Msamples/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert not {"also", "seeds", "scale_ref", "cpu_baseline", "l2_vs_cpu_ref"} & set(out)
+    film = np.load(tmp_path / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (512, 512, 3)
+    sc = mi.load_file(scene_path("cbox.xml"), res=512, spp=256, max_depth=6)
+    assert np.array_equal(film, mi.render(sc, seed=0))
