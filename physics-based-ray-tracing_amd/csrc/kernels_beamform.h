@@ -52,11 +52,6 @@ struct DasGrid {
 };
 DEV uint32_t das_band_lo(uint32_t band, uint32_t ntz) { return (band * ntz + DAS_BANDS - 1u) / DAS_BANDS; }
 DEV bool das_tile_of(const DasGrid g, uint32_t b, uint32_t *tx, uint32_t *tz) {
-#ifdef DAS_NO_XCD_BANDS
-    *tx = b / g.ntz;
-    *tz = b - *tx * g.ntz;
-    return *tx < g.ntx;
-#else
     const uint32_t xcd = b % DAS_XCDS, i = b / DAS_XCDS;
     const uint32_t lo1 = das_band_lo(xcd, g.ntz), n1 = das_band_lo(xcd + 1u, g.ntz) - lo1;
     const uint32_t lo2 = das_band_lo(DAS_BANDS - 1u - xcd, g.ntz), n2 = das_band_lo(DAS_BANDS - xcd, g.ntz) - lo2;
@@ -64,35 +59,12 @@ DEV bool das_tile_of(const DasGrid g, uint32_t b, uint32_t *tx, uint32_t *tz) {
     *tx = t;
     *tz = r < n1 ? lo1 + r : lo2 + (r - n1);
     return t < g.ntx && r < n1 + n2;
-#endif
-}
-
-// |(dx, z)|.  DAS_SQRT_NR: f32 v_rsq seed + two Goldschmidt steps + one Heron correction in f64 (< 1 ulp) instead of the compiler's
-// correctly rounded expansion around v_rsq_f64; arguments outside the f32 range (or 0) take the library routine.
-DEV double das_dist(double r) {
-#ifdef DAS_SQRT_NR
-    if (r > 1e-30 && r < 1e30) {
-        const double y = (double)__frsqrt_rn((float)r);
-        double g = r * y, h = 0.5 * y;
-        double e = __builtin_fma(-g, h, 0.5);
-        g = __builtin_fma(g, e, g);
-        h = __builtin_fma(h, e, h);
-        e = __builtin_fma(-g, h, 0.5);
-        g = __builtin_fma(g, e, g);
-        h = __builtin_fma(h, e, h);
-        return __builtin_fma(__builtin_fma(-g, g, r), h, g);
-    }
-#endif
-    return sqrt(r);
 }
 
 // A sample position as whole samples + a fraction in [0, 1): the sum of two positions is an integer add, an f32 add and the carry
 // (v_fract / v_floor) -- 2-cycle instructions -- where the f64 form needs add, multiply, floor / convert, subtract, convert at 4
 // cycles each per (element, angle).  The fraction keeps 24 bits (1.2e-7 samples; the f64 form rounds the interpolation weight
 // to f32 as well), the whole part is exact.
-#ifndef DAS_PAIR
-#define DAS_PAIR 0   // A/B (round 5): linear interpolation with two elements per trip of a wave, their gathers in flight together.  Same
-#endif               // bits, 74.6 -> 107.5 us: 81 VGPRs (5 waves per SIMD instead of 7) and every lane loads (profiles/r05_das_variants.txt)
 struct DasPos {
     int32_t i;
     float f;
@@ -135,7 +107,7 @@ __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, co
         for (uint32_t j = 0; j < DAS_ANG; ++j) tmin[j] = 1e300;
         for (uint32_t e = 0; e < E; ++e) {
             const double dx = x - (double)elem_x[e];
-            const double d = das_dist(dx * dx + zz) * inv_c;
+            const double d = sqrt(dx * dx + zz) * inv_c;
 #pragma unroll
             for (uint32_t j = 0; j < DAS_ANG; ++j)
                 if (j < na) tmin[j] = fmin(tmin[j], (double)tx[(size_t)(a0 + j) * E + e] + d);
@@ -215,7 +187,7 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
             for (uint32_t j = 0; j < DAS_ANG; ++j) tx_l[j] = j < na ? (double)tx[(size_t)(a0 + j) * E + eb + le] : 0.0;
             for (uint32_t e = wave; e < ne; e += DAS_SPLIT) {
                 const double dx = x - das_lane_f64(ex_l, e);
-                const double d = das_dist(dx * dx + zz) * inv_c;
+                const double d = sqrt(dx * dx + zz) * inv_c;
 #pragma unroll
                 for (uint32_t j = 0; j < DAS_ANG; ++j)
                     if (j < na) tmin[j] = fmin(tmin[j], das_lane_f64(tx_l[j], e) + d);
@@ -245,59 +217,12 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
         for (uint32_t eb = 0; eb < E; eb += 64u) {
             const uint32_t ne = min(64u, E - eb);
             const double ex_l = (double)elem_x[eb + min(lane, ne - 1u)];
-#if DAS_PAIR
-            // Linear interpolation, TWO elements of this wave's share per trip: the 4 x DAS_ANG samples of both are requested before
-            // the first is used (one element per trip leaves a wave waiting for its ten gathers 63 % of its life: SQ_WAIT_ANY /
-            // SQ_WAVE_CYCLES at five resident waves per SIMD).  Same sums in the same order, same bits -- and slower: see DAS_PAIR.
-            for (uint32_t el = wave; INTERP == PBRT_DAS_LINEAR && el < ne; el += 2u * DAS_SPLIT) {
-                float v0[2][DAS_ANG], v1[2][DAS_ANG], ww[2][DAS_ANG];
-                uint32_t kind[2] = {0u, 0u};  // per angle two bits: 1 interpolate, 2 exactly the last sample
-#pragma unroll
-                for (uint32_t u = 0; u < 2u; ++u) {
-                    const uint32_t elu = el + u * DAS_SPLIT;
-                    const bool have = elu < ne;  // (wave-uniform)
-                    const uint32_t e = eb + min(elu, ne - 1u);
-                    const double dx = x - das_lane_f64(ex_l, min(elu, ne - 1u));
-                    const bool in_ap = have && any && fabs(dx) <= half_ap;
-#pragma unroll
-                    for (uint32_t j = 0; j < DAS_ANG; ++j) v0[u][j] = v1[u][j] = ww[u][j] = 0.0f;
-                    if (__ballot(in_ap) == 0ull) continue;
-                    const DasPos dp = das_split(das_dist(dx * dx + zz) * inv_c * fs);
-#pragma unroll
-                    for (uint32_t j = 0; j < DAS_ANG; ++j) {
-                        if (j >= na) break;
-                        const float *trace = data + ((size_t)(a0 + j) * E + e) * T;
-                        const float fr = tp[j].f + dp.f;  // [0, 2)
-                        const float fl = floorf(fr);
-                        const float w = fr - fl;
-                        const uint32_t i0 = (uint32_t)(tp[j].i + dp.i + (int32_t)fl);
-                        const bool ok = in_ap && i0 < T - 1u, lastok = in_ap && i0 == T - 1u && w == 0.0f;
-                        const uint32_t ic = ok ? i0 : (T - 2u);  // (every lane loads: 94 % of the lanes of a trip are in the aperture)
-                        v0[u][j] = trace[ic];
-                        v1[u][j] = trace[ic + 1u];
-                        ww[u][j] = w;
-                        kind[u] |= (ok ? 1u : lastok ? 2u : 0u) << (2u * j);
-                    }
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < 2u; ++u) {
-#pragma unroll
-                    for (uint32_t j = 0; j < DAS_ANG; ++j) {
-                        const uint32_t k = (kind[u] >> (2u * j)) & 3u;
-                        const float val = k == 1u ? fma_(ww[u][j], v1[u][j] - v0[u][j], v0[u][j]) : v1[u][j];  // (k == 2: trace[T - 1])
-                        acc = k ? acc + val : acc;
-                    }
-                }
-            }
-            for (uint32_t el = wave; INTERP != PBRT_DAS_LINEAR && el < ne; el += DAS_SPLIT) {
-#else
             for (uint32_t el = wave; el < ne; el += DAS_SPLIT) {
-#endif
                 const uint32_t e = eb + el;
                 const double dx = x - das_lane_f64(ex_l, el);
                 const bool in_ap = any && fabs(dx) <= half_ap;
                 if (__ballot(in_ap) == 0ull) continue;
-                const double d = das_dist(dx * dx + zz) * inv_c;
+                const double d = sqrt(dx * dx + zz) * inv_c;
                 if (INTERP == PBRT_DAS_NEAREST) {
 #pragma unroll
                     for (uint32_t j = 0; j < DAS_ANG; ++j) {

@@ -81,13 +81,7 @@ __host__ __device__ constexpr uint32_t seg_waves_per_eu(int accel) {
 // per-chunk workgroup barrier), so the 16 waves of a workgroup must not wait for each other.  (The brute-force
 // kernels keep the workgroup scan: there the barrier is cheap and private regions cost registers, DESIGN.md.)
 __host__ __device__ constexpr bool rad_wave_private(int accel) {
-#ifdef PBRT_BVH_WG_COMPACT  // diagnostic builds only (A/B against the workgroup-level scan)
-    return false && accel;
-#elif defined(PBRT_BRUTE_DYN)  // diagnostic builds only: chunk queue for the brute-force kernels as well
-    return accel >= 0;
-#else
     return accel == ACCEL_K_BVH_GLOBAL || accel == ACCEL_K_BVH_LDS;
-#endif
 }
 // Radiance BVH kernels go one step further: the waves of a workgroup take their 64-path chunks from a queue in LDS
 // (one returning ds_add per chunk) and reserve the slots of their survivors with another, so the region is one
@@ -95,15 +89,11 @@ __host__ __device__ constexpr bool rad_wave_private(int accel) {
 // expensive rays kept its workgroup (and the 114 KB LDS image) alive while the other 15 had long left
 // (measured: 2.3 of 4 possible waves per SIMD).
 __host__ __device__ constexpr bool rad_dynamic(int accel) {
-#ifdef PBRT_BVH_STATIC_WAVES  // diagnostic builds only (A/B against fixed per-wave shares)
-    return false && accel;
-#else
     return rad_wave_private(accel);
-#endif
 }
-// live-path counters per region of the radiance kernels (one per workgroup, or one per wave with fixed shares)
-__host__ __device__ constexpr uint32_t rad_owners_per_region(int accel) {
-    return (rad_wave_private(accel) && !rad_dynamic(accel)) ? seg_threads(accel) / 64 : 1;
+// live-path counters per region of the radiance kernels (one per region: the waves of a BVH workgroup share theirs)
+__host__ __device__ constexpr uint32_t rad_owners_per_region(int) {
+    return 1;
 }
 // statistics rows per region (per workgroup, or per wave)
 __host__ __device__ constexpr uint32_t rad_rows_per_region(int accel) {
@@ -127,7 +117,7 @@ struct RadArgs {
     uint32_t n_paths;  // paths generated by the first bounce of this pass
     uint32_t depth, max_depth, rr_depth, seed;
     uint32_t nb;  // bounces this launch walks (the multi-bounce variants k_bounce<.., 2>; 2 .. MAX_CHAIN)
-    uint32_t repack_mask;  // chain launches: bit b = after the launch's b-th bounce the workgroup packs its live paths to its first lanes (k_bounce)
+    uint32_t repack_mask;  // unused; kept so that the kernel-argument layout stays unchanged
     uint32_t merge_at;  // k_chain_pair: the bounce from which a wave walks the survivors of its two tiles together (1 .. max_depth - 1)
     // key mode 0 (render): home -> (region pixel, local sample)
     uint32_t key_mode;
@@ -174,9 +164,6 @@ DEV uint32_t region_index(uint32_t xx, uint32_t yy, uint32_t rw, uint32_t tile_r
 // inside every aligned group of 8 by the sum of the base-8 digits of the group index deals every stripe to every XCD in turn.
 // A permutation of [0, n): the last, partial group is left alone.
 DEV uint32_t xcd_swizzle(uint32_t b, uint32_t n) {
-#ifdef PBRT_NO_XCD_SWIZZLE
-    return b;
-#else
     if ((b | 7u) >= n) return b;
     uint32_t g = b >> 3, rot = 0;
     while (g) {
@@ -184,7 +171,6 @@ DEV uint32_t xcd_swizzle(uint32_t b, uint32_t n) {
         g >>= 3;
     }
     return (b & ~7u) | ((b + rot) & 7u);
-#endif
 }
 
 template <bool TILED>
@@ -236,9 +222,6 @@ __host__ __device__ constexpr uint32_t ilog2_c(uint32_t v) { return v <= 1u ? 0u
 // scenes then only walk the primitives that can occlude such a segment (DevScene::occ_prims).
 template <int ACCEL, bool ANY, bool SEGMENT = false>
 DEV bool scene_intersect(const DevScene &sc, const LdsScene &ls, V3 o, V3 d, float tmax, Hit *h) {
-#ifdef PBRT_BRUTE_PAIRS
-    if (ACCEL == ACCEL_K_BRUTE && !ANY) return brute_closest_pairs(sc, o, d, tmax, h);
-#endif
     if (ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG)
         return brute_intersect<ANY, SEGMENT, ACCEL != ACCEL_K_BRUTE>(sc, o, d, tmax, h);
     if (ACCEL == ACCEL_K_BVH_GLOBAL) return bvh_intersect<ANY>(TreeGlobal{sc.nodes, sc.lprims}, sc.prims, ls.stk, o, d, tmax, h);
@@ -424,7 +407,7 @@ template <bool FIRST, int ACCEL, int NB = 1>
 __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUTE ? FUSED_WAVES_PER_EU : BIG_WAVES_PER_EU) : seg_waves_per_eu(ACCEL)) void k_bounce(const RadArgs a) {
     static_assert(NB == 1 || ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG, "fused bounces: brute-force kernels only");
     // the per-bounce survivor counts of a chain are packed 10 bits each per WORKGROUP and summed by thread 0: one segment per region,
-    // workgroup-level compaction (a -DREGION_SEGS_BRUTE / -DPBRT_BRUTE_DYN build would silently lose them)
+    // workgroup-level compaction (a -DREGION_SEGS_BRUTE build would silently lose them)
     static_assert(NB == 1 || (rad_region_segs(ACCEL) == 1 && !rad_wave_private(ACCEL) && seg_threads(ACCEL) <= 1023),
                   "chain launches: REGION == SEG, workgroup scan");
     constexpr uint32_t SEG = seg_threads(ACCEL);
@@ -435,20 +418,6 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
     // multi-bounce launches: paths that went on to the launch's 2nd .. 6th bounce, 10 bits each (a workgroup has <= 512):
     // bounces 2 - 4 in wave_mid, 5 - 6 in wave_mid_hi
     __shared__ uint32_t wave_mid[2][NB > 1 ? SEG / 64 : 1], wave_mid_hi[2][NB > 1 ? SEG / 64 : 1];
-    // Repack inside a chain launch (round 4, build switch -DPBRT_CHAIN_REPACK: measured, lost): in the Cornell
-    // box 100 / 87 / 67 / 56 / 47 / 9 % of the lanes carry a path at bounces 0 .. 5.  After the bounces the host names
-    // (a.repack_mask, PBRT_CHAIN_REPACK=mask in the environment) the workgroup packs its live paths to its first lanes through LDS
-    // -- 15 dwords each, [row][thread] so that both sides are conflict-free -- and the waves left without a path retire (s_endpgm;
-    // the barriers do not wait for them).  Same paths, same arithmetic, other lanes: the film does not change.  What it gives is
-    // 2 % (a wave with few live lanes skips most of a bounce anyway); what its code costs the kernel at the 64-register budget is
-    // 8 % (20 spilled VGPRs, 30 KB of LDS per workgroup): 6.33 -> 6.84 ms with the switch compiled in and no bounce named, 6.69 at best.
-#ifdef PBRT_CHAIN_REPACK
-    constexpr bool REPACK = NB > 1 && ACCEL == ACCEL_K_BRUTE;
-#else
-    constexpr bool REPACK = false;
-#endif
-    __shared__ uint32_t rp_cnt[REPACK ? SEG / 64 : 1];
-    __shared__ float rp_state[REPACK ? N_STATE : 1][REPACK ? SEG : 1];
 
     const uint32_t seg = xcd_swizzle(blockIdx.x, gridDim.x);  // region index
     const uint32_t tid = threadIdx.x;
@@ -457,15 +426,12 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
     // not care, it keeps the long paths of a chain launch (the pixels of the glass and the mirror sphere) together in the same
     // waves instead of one or two lanes in every wave of a row: Cornell box, one launch per pass, 6.41 -> 6.25 ms
     constexpr bool TILED = true;
-    constexpr bool DYN = rad_dynamic(ACCEL);                  // chunk queue + slot reservation in LDS (BVH kernels)
-    constexpr bool WP = rad_wave_private(ACCEL) && !DYN;      // fixed per-wave shares (diagnostic fallback)
-    constexpr bool PERWAVE = WP || DYN;                       // the waves walk 64-path chunks on their own
-    constexpr uint32_t W = SEG / 64, WREG = REGION / W;       // waves per workgroup, slots owned by one wave (WP)
-    constexpr uint32_t CH = PERWAVE ? 64u : SEG;              // paths per chunk of the walk
-    const uint32_t lane_c = PERWAVE ? (tid & 63u) : tid;      // position inside the chunk
-    const uint32_t own = WP ? seg * W + (tid >> 6) : seg;     // live counter of this wave / workgroup
-    const uint32_t row_id = PERWAVE ? seg * W + (tid >> 6) : seg;  // statistics row
-    const uint32_t base = WP ? seg * REGION + (tid >> 6) * WREG : seg * REGION;
+    constexpr bool DYN = rad_dynamic(ACCEL);  // chunk queue + slot reservation in LDS (BVH kernels): the waves walk 64-path chunks on their own
+    constexpr uint32_t W = SEG / 64;          // waves per workgroup
+    constexpr uint32_t CH = DYN ? 64u : SEG;  // paths per chunk of the walk
+    const uint32_t lane_c = DYN ? (tid & 63u) : tid;              // position inside the chunk
+    const uint32_t row_id = DYN ? seg * W + (tid >> 6) : seg;     // statistics row
+    const uint32_t base = seg * REGION;
     __shared__ uint32_t q_in, q_out, q_done;                  // DYN: next chunk, next free output slot, finished waves
     if (DYN && tid == 0) {
         q_in = 0;
@@ -474,23 +440,11 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
     }
     uint32_t cnt_in;
     if (FIRST) {
-        cnt_in = a.n_paths > base ? min(a.n_paths - base, WP ? WREG : REGION) : 0u;
+        cnt_in = a.n_paths > base ? min(a.n_paths - base, REGION) : 0u;
     } else {
-        cnt_in = a.seg_in[own];
+        cnt_in = a.seg_in[seg];
     }
-    if (WP) {
-        // the workgroup stages the scene together: leave only if no wave of it has work (same answer in every wave)
-        cnt_in = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt_in);
-        uint32_t c = 0;
-        if ((tid & 63u) < W) {
-            const uint32_t b2 = seg * REGION + (tid & 63u) * WREG;
-            c = FIRST ? (a.n_paths > b2 ? 1u : 0u) : a.seg_in[seg * W + (tid & 63u)];
-        }
-        if (__ballot(c != 0) == 0) {
-            if ((tid & 63u) == 0) a.seg_out[own] = 0;
-            return;
-        }
-    } else if (cnt_in == 0) {  // uniform across the workgroup
+    if (cnt_in == 0) {  // uniform across the workgroup
         if (tid == 0) a.seg_out[seg] = 0;
         return;
     }
@@ -499,7 +453,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
     // are free for the next workgroup's waves (late bounces run at 10-50 % fill).  They publish a zero survivor
     // count first; s_barrier does not wait for terminated waves.
 #ifndef PBRT_ABLATE_EARLY_EXIT
-    constexpr bool early_exit = ACCEL == ACCEL_K_BRUTE && !FIRST && rad_region_segs(ACCEL) == 1 && !PERWAVE;
+    constexpr bool early_exit = ACCEL == ACCEL_K_BRUTE && !FIRST && rad_region_segs(ACCEL) == 1 && !DYN;
 #else
     constexpr bool early_exit = false;
 #endif
@@ -528,7 +482,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
     if (DYN && ACCEL != ACCEL_K_BVH_LDS) __syncthreads();               // publishes the queue words
     __shared__ uint32_t tab_lds[ACCEL == ACCEL_K_BRUTE ? TAB_DW : 1];
     const Tables tb = make_tables<ACCEL>(a.sc, ls, tab_lds);
-    if (ACCEL == ACCEL_K_BRUTE && (FIRST || PERWAVE)) fill_tables_lds(a.sc, tab_lds, SEG);  // (PERWAVE: no barrier in the walk)
+    if (ACCEL == ACCEL_K_BRUTE && (FIRST || DYN)) fill_tables_lds(a.sc, tab_lds, SEG);  // (DYN: no barrier in the walk)
 
     const uint32_t cap = a.cap;
     const Rsrc r_in = make_rsrc(a.in, a.state_cap * (N_STATE * 4u)), r_out = make_rsrc(a.out, a.state_cap * (N_STATE * 4u));
@@ -579,7 +533,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
         }
     }
     // shading tables -> LDS, behind the state loads so that the two memory round trips overlap
-    if (ACCEL == ACCEL_K_BRUTE && !FIRST && !PERWAVE && it0 == 0) fill_tables_lds(a.sc, tab_lds, live_threads);
+    if (ACCEL == ACCEL_K_BRUTE && !FIRST && !DYN && it0 == 0) fill_tables_lds(a.sc, tab_lds, live_threads);
     if (alive && !FIRST) path_key<TILED>(a, home, &ka, &kb, &px, &py);
     bool live = alive;                        // the lane still carries a path
     uint32_t nseg_w = 0, nshd_w = 0, nmid_w = 0, nmid_hi_w = 0;  // wave-uniform counts over the launch's bounces
@@ -612,70 +566,6 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
     live = survive;
     nseg_w += (uint32_t)__popcll(__ballot(did_seg));
     nshd_w += (uint32_t)__popcll(__ballot(did_shadow));
-    if (REPACK && ((a.repack_mask >> bounce) & 1u) && bounce + 1 < nb_run && depth + 1 < a.max_depth) {  // uniform
-        const uint32_t wid_r = tid >> 6;
-        const unsigned long long bl = __ballot(live);
-        const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bl >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bl, 0u));
-        if ((tid & 63u) == 0) rp_cnt[wid_r] = (uint32_t)__popcll(bl);
-        __syncthreads();
-        const uint32_t c_lane = rp_cnt[tid & (SEG / 64 - 1)];
-        const uint32_t wid_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wid_r);
-        uint32_t off_r = 0, total_r = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < SEG / 64; ++w) {
-            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)c_lane, (int)w);
-            off_r += (w < wid_s) ? t : 0u;
-            total_r += t;
-        }
-        if (live) {
-            const uint32_t k = off_r + pre;
-            rp_state[0][k] = o.x;
-            rp_state[1][k] = o.y;
-            rp_state[2][k] = o.z;
-            rp_state[3][k] = d.x;
-            rp_state[4][k] = d.y;
-            rp_state[5][k] = d.z;
-            rp_state[6][k] = thr.x;
-            rp_state[7][k] = thr.y;
-            rp_state[8][k] = thr.z;
-            rp_state[9][k] = L.x;
-            rp_state[10][k] = L.y;
-            rp_state[11][k] = L.z;
-            rp_state[12][k] = eta;
-            rp_state[13][k] = prev_pdf;
-            rp_state[14][k] = __uint_as_float(home);
-        }
-        __syncthreads();
-        live = tid < total_r;
-        if (live) {
-            o = {rp_state[0][tid], rp_state[1][tid], rp_state[2][tid]};
-            d = {rp_state[3][tid], rp_state[4][tid], rp_state[5][tid]};
-            thr = {rp_state[6][tid], rp_state[7][tid], rp_state[8][tid]};
-            L = {rp_state[9][tid], rp_state[10][tid], rp_state[11][tid]};
-            eta = rp_state[12][tid];
-            prev_pdf = rp_state[13][tid];
-            home = __float_as_uint(rp_state[14][tid]);
-            path_key<TILED>(a, home, &ka, &kb, &px, &py);
-        }
-        // a wave left without a path retires: it publishes what the end of the kernel expects from it (its counts of this launch,
-        // no survivors) and ends; the waves that go on never wait for it.  (The next repack must see it with no live lane: rp_cnt.)
-        // s_endpgm behind the compiler's back keeps the kernel single-exit for the structurizer (as the early exit above).
-        const uint32_t wave_first_r = (uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u;
-        if ((tid & 63u) == 0 && wave_first_r >= total_r && wave_first_r != 0u) {  // (wave 0 stays: thread 0 writes the region's counters)
-            rp_cnt[wid_r] = 0;
-            wave_tot[buf][wid_r] = 0;
-            wave_seg[buf][wid_r] = nseg_w;
-            wave_shd[buf][wid_r] = nshd_w;
-            wave_mid[buf][wid_r] = nmid_w;
-            wave_mid_hi[buf][wid_r] = nmid_hi_w;
-        }
-        const uint32_t keep = (uint32_t)__builtin_amdgcn_readfirstlane((int)((wave_first_r < total_r || wave_first_r == 0u) ? 1u : 0u));
-        asm volatile("s_cmp_lg_u32 %0, 0\n\t"
-                     "s_cbranch_scc1 .Lstay_%=\n\t"
-                     "s_waitcnt lgkmcnt(0)\n\t"
-                     "s_endpgm\n"
-                     ".Lstay_%=:" ::"s"(keep) : "scc", "memory");
-    }
     }  // bounces of this launch
     // ---- segment-local stream compaction: ballot + mbcnt inside the wave, LDS scan across waves
     const uint32_t wid = tid >> 6;
@@ -690,10 +580,6 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
         ns_acc += nseg_w;
         nh_acc += nshd_w;
         live_acc += (uint32_t)__popcll(__ballot(alive));
-    } else if (WP) {  // the wave packs its own survivors behind its own cursor: no LDS, no barrier
-        total = (uint32_t)__popcll(bal);
-        ns_acc += nseg_w;
-        nh_acc += nshd_w;
     } else {
     if ((tid & 63) == 0) {
         wave_tot[buf][wid] = (uint32_t)__popcll(bal);
@@ -736,7 +622,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
         bst(r_out, v4 + 14 * row, 0, __uint_as_float(home));
     }
     out_off += total;
-    if (!PERWAVE && tid == 0) {
+    if (!DYN && tid == 0) {
         for (uint32_t w = 0; w < SEG / 64; ++w) {
             ns_acc += wave_seg[buf][w];
             nh_acc += wave_shd[buf][w];
@@ -759,8 +645,8 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
         }
         return;
     }
-    if (WP ? (tid & 63u) == 0 : tid == 0) {
-        a.seg_out[own] = out_off;
+    if (tid == 0) {
+        a.seg_out[seg] = out_off;
         // per-region statistics rows (plain read-modify-write by the owning workgroup; launches of a
         // call are ordered on the stream).  NOT global atomics: 3 same-line atomics per workgroup
         // serialise at ~12 ns each and were the whole kernel time (DESIGN.md "What did not work").

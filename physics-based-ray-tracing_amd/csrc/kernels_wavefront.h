@@ -120,9 +120,6 @@ DEV void wf_camera_ray(const WfArgs &a, uint32_t home, V3 *o, V3 *d, float *tmax
 #define WF_PROBE(i, v)
 #endif
 #define WF_IDLE 0xfffffffeu     // cursor of a lane without a ray (BVH_SENT = 0xffffffff: its ray has finished)
-#ifndef WF_WALK_UNROLL
-#define WF_WALK_UNROLL 1     // node visits between two looks at the wave's walkers (the refill test and the guard)
-#endif
 
 template <int ACCEL>
 struct WfTree {
@@ -308,18 +305,12 @@ __global__ __launch_bounds__(1024, WF_TRACE_WAVES_PER_EU) void k_trace(const WfA
             const bool walking = (int32_t)c.cur >= 0;
             const uint32_t n_walk = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(walking));
             if (n_walk < walk_min) break;
-#ifdef WF_WALK_ADAPT  // A/B (round 5): also stop walking once the lanes that wait with a leaf outnumber the walkers WF_WALK_ADAPT : 1
-            if (n_walk * WF_WALK_ADAPT < (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(c.cur - 0x80000000u < 0x7ffffffeu))) break;
-#endif
             WF_PROBE(0, 1);
             WF_PROBE(1, __builtin_popcountll(__builtin_amdgcn_ballot_w64(walking)));
             WF_PROBE(7, __builtin_popcountll(__builtin_amdgcn_ballot_w64(c.cur - 0x80000000u < 0x7ffffffeu)));  // lanes that hold a leaf through this visit
-            turns = (uint32_t)__builtin_amdgcn_readfirstlane((int)(turns + WF_WALK_UNROLL));
+            turns = (uint32_t)__builtin_amdgcn_readfirstlane((int)(turns + 1u));
             if (turns > WF_GUARD_TURNS) break;  // (the main loop's guard reports)
             if (walking) bvh_visit(tr, st, c, ovf, br, best);
-#pragma unroll
-            for (int j = 1; j < WF_WALK_UNROLL; ++j)
-                if ((int32_t)c.cur >= 0) bvh_visit(tr, st, c, ovf, br, best);
         }
         // the held leaves: a wave-uniform loop over the primitive index, every lane with a leaf of more than k primitives takes
         // part; the closest-hit update is a select (a hit at the distance of the best one so far wins with the lower primitive

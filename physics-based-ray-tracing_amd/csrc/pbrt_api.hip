@@ -242,39 +242,6 @@ static inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b
 // plane: it then sits on the boundary of the scene's convex hull and a segment whose end points are in the
 // hull cannot cross it.  Exact comparisons (>= 0 in f64 on the f32 data), so nearly-coplanar scenes just
 // keep their primitives.
-#ifdef PBRT_BRUTE_PAIRS
-// Consecutive planar primitives two by two, their v0 / e1 / e2 interleaved; everything else (spheres) on its own.
-static std::vector<PairItem> build_pair_items(const pbrt_prim *prims, uint32_t n) {
-    auto planar = [](const pbrt_prim &P) { return P.type == PBRT_PRIM_TRIANGLE || P.type == PBRT_PRIM_PARALLELOGRAM; };
-    std::vector<PairItem> items;
-    for (uint32_t i = 0; i < n;) {
-        PairItem it;
-        std::memset(&it, 0, sizeof it);
-        it.dw[21] = i;
-        if (!planar(prims[i])) {
-            std::memcpy(it.dw, &prims[i], sizeof(pbrt_prim));
-            it.dw[18] = prims[i].type;
-            it.dw[19] = 0xffffffffu;
-            it.dw[20] = 1;
-            it.dw[21] = i;
-            i += 1;
-        } else {
-            const bool two = i + 1 < n && planar(prims[i + 1]);
-            const pbrt_prim &A = prims[i], &B = prims[two ? i + 1 : i];
-            for (int k = 0; k < 9; ++k) {
-                std::memcpy(&it.dw[2 * k], &A.g[k], 4);
-                std::memcpy(&it.dw[2 * k + 1], &B.g[k], 4);
-            }
-            it.dw[18] = A.type;
-            it.dw[19] = two ? B.type : 0xffffffffu;
-            it.dw[20] = 0;
-            i += two ? 2 : 1;
-        }
-        items.push_back(it);
-    }
-    return items;
-}
-#endif
 
 static std::vector<pbrt_prim> find_occluders(const pbrt_scene_desc *d) {
     std::vector<pbrt_prim> occ;
@@ -545,13 +512,6 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
         std::vector<pbrt_prim> occ = find_occluders(d);
         UP(upload(s, occ.data(), occ.size(), &s->ds.occ_prims));
         s->ds.n_occ = (uint32_t)occ.size();
-#ifdef PBRT_BRUTE_PAIRS
-        if (s->accel_kernel == ACCEL_K_BRUTE) {  // pair records for brute_closest_pairs (device_scene.h)
-            std::vector<PairItem> items = build_pair_items(d->prims, d->n_prims);
-            UP(upload(s, items.data(), items.size(), &s->ds.pair_items));
-            s->ds.n_pair_items = (uint32_t)items.size();
-        }
-#endif
     } else {
         HostBvh bvh;
         // (a tree whose leaf records alone exceed the LDS stays in global memory whatever its shape: the SAH constant of those trees)
@@ -653,12 +613,6 @@ static void launch_walk(pbrt_scene *s, const RadArgs &a, uint32_t nseg, uint32_t
     }
 }
 #endif
-// In-kernel repack of a chain launch (kernels_radiance.h k_bounce, REPACK): after which of its bounces the workgroup packs its live
-// paths together.  PBRT_CHAIN_REPACK=mask overrides (0: never).
-static uint32_t chain_repack_mask() {
-    static const char *e = getenv("PBRT_CHAIN_REPACK");
-    return e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
-}
 // nb: bounces this launch walks (>= 2: the multi-bounce variants of the brute-force kernels, kernels_radiance.h; a.nb = nb)
 template <bool FIRST>
 static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, uint32_t nb = 1) {
@@ -778,29 +732,20 @@ struct WfPlan {
     size_t lds = 0;
 };
 // Workgroup shape of k_trace: the image plus (rows + 1) stack rows per workgroup; two 1024-thread workgroups per CU when both fit
-// (8 waves per SIMD at <= 64 VGPRs), else one.  PBRT_WF_THREADS / PBRT_WF_ROWS / PBRT_WF_GRID_MULT override (diagnostic A/B).
+// (8 waves per SIMD at <= 64 VGPRs), else one.
 static WfPlan wf_plan(const pbrt_scene *s) {
     WfPlan p;
-    static const char *e_thr = getenv("PBRT_WF_THREADS"), *e_rows = getenv("PBRT_WF_ROWS"), *e_grid = getenv("PBRT_WF_GRID_MULT");
     const uint32_t limit = s->ctx->lds_limit ? s->ctx->lds_limit : 65536u;
     const uint32_t image = s->accel_kernel == ACCEL_K_BVH_LDS ? s->lds_bytes : 0u;
     // 1024-thread workgroups for trees in global memory as well: what counts is the size of the queue a workgroup's waves share
     // (bunny.ply 1024^2 x 64: 256 / 512 / 1024 threads 38.5 / 31.6 / 30.2 ms), not the LDS -- a copy of the top of the tree (the
     // first 16 .. 1008 nodes in breadth-first order) in LDS on top of that was worth 1 - 2 %: the vector caches hold those nodes anyway
     p.threads = 1024u;
-    if (e_thr) {  // a power of two (the stack rows are addressed by a shift)
-        const uint32_t want = (uint32_t)atoi(e_thr);
-        p.threads = want >= 1024u ? 1024u : want >= 512u ? 512u : want >= 256u ? 256u : want >= 128u ? 128u : 64u;
-    }
     const uint32_t statics = 1024;  // queue words and the segment table, with slack
     uint32_t budget = limit / 2;     // two workgroups per CU
     if (image + statics + 3u * p.threads * 4u > budget) budget = limit;
     const uint32_t rows_fit = (budget - image - statics) / (p.threads * 4u);
     p.rows = std::max(2u, std::min(rows_fit, 8u));
-    if (e_rows) p.rows = std::max(2u, std::min((uint32_t)atoi(e_rows), 15u));
-    if (e_grid) p.grid_mult = std::max(1u, (uint32_t)atoi(e_grid));
-    static const char *e_deep = getenv("PBRT_WF_GRID_DEEP");
-    if (e_deep) p.grid_deep = std::max(1u, (uint32_t)atoi(e_deep));
     static const char *e_pkt = getenv("PBRT_WF_PACKET");
     if (e_pkt) p.packet = atoi(e_pkt) != 0;
     if (3u * s->bvh_depth > 64u) p.packet = false;  // the wave's stack is the 64 lanes of one register (bvh_packet_closest)
@@ -1384,7 +1329,6 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
             const uint32_t nb = brute ? chain_len(fuse_plan, depth, f->max_depth) : 1u;
             a.depth = depth;
             a.nb = nb;
-            a.repack_mask = chain_repack_mask();
             a.in = in;
             a.out = out;
             a.seg_in = sin;
@@ -2112,8 +2056,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         const uint32_t nseg_pass = div_up(a.n_paths, REGION);
         a.blk_mul = 0;
         const char *e_perm = getenv("PBRT_US_EMIT_PERMUTE");  // A/B and test: 0 keeps workgroup b on region b (read per call)
-        const char *e_perm_all = getenv("PBRT_US_PERMUTE_ALL");  // A/B: the integrator's own rays as well
-        if ((emit || (e_perm_all && atoi(e_perm_all) != 0)) && !streams && nseg_pass > 2u * NA && !(e_perm && atoi(e_perm) == 0)) {
+        if (emit && !streams && nseg_pass > 2u * NA && !(e_perm && atoi(e_perm) == 0)) {
             uint32_t m = (nseg_pass / NA) | 1u;
             if (e_perm && atoi(e_perm) > 1) m = (uint32_t)atoi(e_perm) | 1u;  // (A/B: another stride)
             while (std::gcd(m, nseg_pass) != 1u) m += 2u;
@@ -2534,16 +2477,11 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
     DasGrid g;
     g.ntx = div_up(p->nx, DAS_TILE);
     g.ntz = div_up(p->nz, DAS_TILE);
-#ifdef DAS_NO_XCD_BANDS
-    g.m = g.ntz;
-    const uint32_t blocks = g.ntx * g.ntz;
-#else
     // z-tiles of the largest XCD share (bands k and 15 - k, kernels_beamform.h das_tile_of); the grid gives every XCD that many slots
     g.m = 0;
     auto lo = [&](uint32_t band) { return (band * g.ntz + DAS_BANDS - 1u) / DAS_BANDS; };
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
-#endif
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
     if (p->interpolation == PBRT_DAS_NEAREST) {
         if (ttx)
