@@ -454,8 +454,11 @@ typedef struct pbrt_das_params {
  * out[ix][iz] = sum_a sum_e data[a][e](t_tx(a; x, z) + |(x, z) - (elem_x[e], 0)| / c), where the transmit time is the
  * first arrival of the emitted wavefront, t_tx = min_e' (tx_delays[a][e'] + |(x, z) - (elem_x[e'], 0)| / c)  (equal to
  * (x sin(theta) + z cos(theta)) / c for the plane-wave delays of pbrt_us_tx_delays inside the aperture's shadow).
- * Sample positions are evaluated in f64, samples interpolated and summed in f32 in the order (groups of 8 transmissions, element,
- * transmission within the group).  Host pointers. */
+ * Sample positions are evaluated in f64 and kept as whole samples plus an f32 fraction; samples are interpolated and summed in f32
+ * in the order (wave = e % 4, trip of 5 transmissions, element, transmission within the trip), the four waves' partial sums added
+ * last.  Linear: floor(s) in [0, T - 1), or s == T - 1 exactly; nearest: round half to even into [0, T - 1].  The tests hold every
+ * pixel to (n_terms + 16) 2^-24 sum_terms max(|v0|, |v1|) of an f64 evaluation (tests/das_util.py), and constant traces to the
+ * exact sum.  Host pointers. */
 int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
                       const float *elem_x, const float *x, const float *z, float *out);
 

@@ -242,6 +242,7 @@ class _RenderPlan:
         self.d_rf = _capi.DeviceBuffer(cx, (A, E, T)) if gaussian else None
         self.d_tx = _capi.DeviceBuffer(cx, (A, E))
         self.tx_host = None
+        self.table_c = None   # the sound speed d_table was made with
         self.d_ex = _capi.DeviceBuffer.from_host(cx, _capi.f32(elem_x))
         self.d_x = _capi.DeviceBuffer.from_host(cx, _capi.f32(x_scan))
         self.d_z = _capi.DeviceBuffer.from_host(cx, _capi.f32(z_scan))
@@ -354,11 +355,12 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
         queue_acquisition()
         t1 = _time.perf_counter()
         delays = np.asarray(integ.transmission_delays_buf, dtype=np.float32).reshape(A, E)             # :121
-        if plan.tx_host is None or not np.array_equal(plan.tx_host, delays):
+        if plan.tx_host is None or not np.array_equal(plan.tx_host, delays) or plan.table_c != float(integ.sound_speed):
             plan.d_tx.upload(delays)
             plan.tx_host = delays.copy()
-            # the scan's first-arrival times follow the delays and the grid: made again only when those change (never, in the
-            # loop of USMain.py:262-289)
+            plan.table_c = float(integ.sound_speed)
+            # the scan's first-arrival times follow the delays, the sound speed and the grid: made again only when those change
+            # (never, in the loop of USMain.py:262-289).  (A single 0 degree angle has zero delays at every sound speed.)
             das_first_arrival(plan.d_tx, plan.d_ex, plan.d_x, plan.d_z, integ.sound_speed, out=plan.d_table)
             plan.graph = plan.graph_key = plan.warm_key = None
         queue_image_formation()

@@ -432,3 +432,59 @@ def test_us_render_hands_its_images_over_on_the_device(mi):
     assert np.allclose(t_img.T.cpu().numpy(), disp, rtol=0, atol=1e-3) and np.allclose(t_env.cpu().numpy(), env, rtol=0, atol=2e-5 * env.max())
     loss = torch.mean((t_img - torch.as_tensor(disp.T.copy(), device="cuda")) ** 2).item()   # a loss that never leaves the GPU
     assert 0.0 <= loss < 1e-6
+
+
+def test_us_render_remakes_the_first_arrival_table_when_the_sound_speed_changes(mi, tmp_path):
+    """The cached first-arrival table depends on the sound speed as well as on the transmit delays.  With the single angle 0 the delays
+    are zero at every sound speed and, with an explicit step, the grid does not move: after a change of c the chain (queued, then
+    recorded, then replayed) must use a table made with the new c, as the host chain does"""
+    xml = open(scene_path("us_plate.xml")).read()
+    assert 'value="-15 -7.5 0 7.5 15"' in xml
+    path = tmp_path / "us_plate_0deg.xml"
+    path.write_text(xml.replace('value="-15 -7.5 0 7.5 15"', 'value="0"'))
+    sc = mi.load_file(str(path), paths_per_ray=16, seed=5)
+    ui = sc.integrator()
+    assert ui.n_angles == 1
+    kw = dict(x_range=(-0.012, 0.012), z_range=(0.03, 0.07), step=1e-4)
+    mi.us_render(sc, **kw)                                                      # c = 1540: table made
+    ui.sound_speed = 1480.0
+    imgs, flags = [], []
+    for _ in range(3):                                                          # queued, queued + recorded, replayed
+        tm = {}
+        imgs.append(mi.us_render(sc, timing=tm, **kw)[1])
+        flags.append(tm["replayed"])
+    assert flags == [False, False, True] and not ui.transmission_delays_buf.any()
+    host = mi.us_render(sc, device_resident=False, **kw)[1]
+    for b in imgs:
+        assert np.allclose(b, host, rtol=0, atol=2e-5 * host.max())
+
+
+@pytest.mark.parametrize("n", [1, 3, 5, 1025, 70001])
+def test_log_compress_at_odd_lengths_and_an_unaligned_pointer(mi, n):
+    """pbrt_log_compress_dev at a device pointer 4 bytes past a buffer's start (k_env_max's scalar loop; every DeviceBuffer is 16-byte
+    aligned) and at the start (the 16-byte loop and its scalar tail), the maximum in the tail; and a constant envelope"""
+    cx = mi.default_context()
+    rng = np.random.default_rng(n)
+    env = (np.abs(rng.normal(size=n + 1)) ** 3).astype(np.float32)
+    env[n - 1] = 3.0 * env.max()                                                # last of the n values read from either start
+    for vals in (env, np.full(n + 1, 0.25, np.float32)):
+        buf = mi.DeviceBuffer.from_host(cx, vals)
+        for off in (0, 1):
+            out = mi.DeviceBuffer(cx, (n,))
+            cx.check(cx.lib.pbrt_log_compress_dev(cx.handle, n, buf.ptr + 4 * off, 60.0, out.ptr), "pbrt_log_compress_dev")
+            got, ref = out.numpy(), obf.log_compress(vals[off:off + n], 60.0)
+            assert np.allclose(got, ref, rtol=0, atol=2e-6), (off, np.abs(got - ref).max())
+
+
+def test_apply_pulse_of_a_trace_shorter_than_the_pulse(mi):
+    """traces of T < K samples (K the half-width of the pulse; T < 256, one workgroup): the whole trace lies inside one pulse"""
+    rng = np.random.default_rng(12)
+    cx = mi.default_context()
+    for fs, fc, sigma, T in ((50e6, 3e6, 5 / (4 * 3e6), 20), (20e6, 1e6, 3e-6, 100), (50e6, 5e6, 2 / (4 * 5e6), 1)):
+        K = obf.pulse_taps(fs, fc, sigma)[1]
+        assert T < K and T < 256
+        x = rng.normal(size=(3, T)).astype(np.float32)
+        got = mi.apply_pulse(x, fs, fc, sigma)
+        ref = obf.apply_pulse(x, fs, fc, sigma)
+        assert got.shape == x.shape and np.allclose(got, ref, rtol=0, atol=3e-5 * np.abs(ref).max())
+        assert np.array_equal(mi.apply_pulse(mi.DeviceBuffer.from_host(cx, x), fs, fc, sigma).numpy(), got)
