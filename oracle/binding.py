@@ -42,7 +42,8 @@ def lib():
         L.oracle_ggx_angle_deg.argtypes = [C.c_double, C.c_uint32, _P, _P]
         L.oracle_ggx_pdf_raw.argtypes = [C.c_double, C.c_uint32, _P, _P]
         for name in ("oracle_scene_create", "oracle_scene_destroy", "oracle_scene_update_material",
-                     "oracle_render_radiance", "oracle_integrator_sample", "oracle_us_acquire", "oracle_us_tx_delays", "oracle_ray_intersect",
+                     "oracle_render_radiance", "oracle_integrator_sample", "oracle_us_acquire", "oracle_us_acquire_bounds",
+                     "oracle_us_tx_delays", "oracle_ray_intersect",
                      "oracle_ray_test", "oracle_bsdf_sample", "oracle_bsdf_eval_pdf", "oracle_emitter_sample_direction",
                      "oracle_sensor_sample_ray", "oracle_us_sensor_sample_ray", "oracle_us_emitter_sample_ray",
                      "oracle_us_put_data"):
@@ -98,16 +99,25 @@ class OracleScene:
                                             C.c_uint32(rr_depth), _P(A(rgb))), "oracle_integrator_sample")
         return rgb.T.copy()
 
-    def us_acquire(self, p, seed, paths_per_ray, path_offset=0, norm_paths=None):
+    def us_acquire(self, p, seed, paths_per_ray, path_offset=0, norm_paths=None, bounds=False):
+        """-> (buf, tx), or with bounds=True (buf, tx, dict(abs_sum, count, ramp_sum)): per bin of buf, sum |pressure| of the echoes
+        deposited there (scaled like buf), their number, and sum |pressure / directivity| of those on the directivity ramp
+        (tests/us_util.py).  buf is the same bit for bit either way."""
         n = p.n_angles * p.n_elements
-        buf = np.empty((p.n_angles, p.n_elements, p.time_samples), np.float32)
+        shape = (p.n_angles, p.n_elements, p.time_samples)
+        buf = np.empty(shape, np.float32)
         tx = np.empty(n, np.float32)
         stats = (C.c_uint64 * 2)()
-        _chk(lib().oracle_us_acquire(self.handle, C.byref(p), C.c_uint32(seed), C.c_uint32(paths_per_ray),
-                                     C.c_uint32(path_offset), C.c_uint32(norm_paths or paths_per_ray), _P(A(buf)),
-                                     _P(A(tx)), stats), "oracle_us_acquire")
+        args = (self.handle, C.byref(p), C.c_uint32(seed), C.c_uint32(paths_per_ray), C.c_uint32(path_offset),
+                C.c_uint32(norm_paths or paths_per_ray), _P(A(buf)), _P(A(tx)), stats)
+        if bounds:
+            extra = dict(abs_sum=np.empty(shape, np.float32), count=np.empty(shape, np.uint32), ramp_sum=np.empty(shape, np.float32))
+            _chk(lib().oracle_us_acquire_bounds(*args, _P(A(extra["abs_sum"])), _P(A(extra["count"])), _P(A(extra["ramp_sum"]))),
+                 "oracle_us_acquire_bounds")
+        else:
+            _chk(lib().oracle_us_acquire(*args), "oracle_us_acquire")
         self.last_stats = dict(segments=int(stats[0]), shadow_rays=int(stats[1]))
-        return buf, tx
+        return (buf, tx, extra) if bounds else (buf, tx)
 
     def ray_intersect(self, o, d, tmax):
         o, d, tmax = f32(np.asarray(o).T), f32(np.asarray(d).T), f32(tmax)

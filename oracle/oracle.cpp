@@ -1169,16 +1169,22 @@ static inline EmitRay emitter_ray(const pbrt_us_emitter &e, float time, float s1
     return r;
 }
 
-static inline float directivity_weight_i(V3 sec_dir, V3 tn, float am, float ac) {  // :289-304
+static inline float directivity_weight_i(V3 sec_dir, V3 tn, float am, float ac, float *alpha_out = nullptr) {  // :289-304
     V3 w = -sec_dir;
     float dt = dot(tn, w);
     float alpha = fabsf(acosf(dt));
+    if (alpha_out) *alpha_out = alpha;
     float mid = (ac - alpha) / (ac - am);
     return alpha <= am ? 1.0f : (alpha <= ac ? mid : 0.0f);
 }
 
-int oracle_us_acquire(oracle_scene *s, const pbrt_us_params *p, uint32_t seed, uint32_t paths_per_ray,
-                      uint32_t path_offset, uint32_t norm_paths, float *channel_buf, float *tx_delays, uint64_t *stats) {
+// abs_sum / count / ramp_sum (each optional, [NA][NE][T] like the channel buffer): what each bin is a sum of, for the per-bin
+// tolerance of tests/us_util.py -- sum |pressure| of the echoes deposited there (scaled like the buffer), how many there were, and
+// sum |pressure / directivity| of those whose directivity angle lies on the ramp [am, ac] (with a margin of 2^-16 ac on either
+// side: there the weight depends on the last bits of acosf).  Asking for them leaves the channel buffer bit for bit as it is.
+static int us_acquire_impl(oracle_scene *s, const pbrt_us_params *p, uint32_t seed, uint32_t paths_per_ray, uint32_t path_offset,
+                           uint32_t norm_paths, float *channel_buf, float *tx_delays, uint64_t *stats, float *abs_sum,
+                           uint32_t *count, float *ramp_sum) {
     if (!s || !p || !channel_buf || p->n_angles > PBRT_US_MAX_ANGLES) return PBRT_E_INVALID;
     const Scene &sc = s->sc;
     const uint32_t NA = p->n_angles, NE = p->n_elements, T = p->time_samples;
@@ -1186,6 +1192,8 @@ int oracle_us_acquire(oracle_scene *s, const pbrt_us_params *p, uint32_t seed, u
     oracle_us_tx_delays(p, tx.data());
     if (tx_delays) std::memcpy(tx_delays, tx.data(), tx.size() * sizeof(float));
     std::vector<double> acc((size_t)NA * NE * T, 0.0);  // deterministic order, double accumulators
+    std::vector<double> acc_abs(abs_sum ? acc.size() : 0, 0.0), acc_ramp(ramp_sum ? acc.size() : 0, 0.0);
+    if (count) std::fill(count, count + acc.size(), 0u);
     const float num_rays = (float)(NA * NE);                                                   // :243
     const V3 tn = normalize(xf_vec(p->sensor_to_world, v3(0, 0, 1)));                          // :292,369
     const float am = p->main_beam_angle * (kPi / 180.0f), ac = p->cutoff_angle * (kPi / 180.0f);
@@ -1271,13 +1279,22 @@ int oracle_us_acquire(oracle_scene *s, const pbrt_us_params *p, uint32_t seed, u
                     float cos_theta = dot(si.ns, -d);                                          // :340 (si.sh_frame.n)
                     amp *= a_resp * cos_theta * fmaxf(bpdf, 1e-6f);                            // :341
                     float w_o = dot(d, si.ns) / num_rays;                                      // :286-287,345 (si.sh_frame.n)
-                    float fd = directivity_weight_i(sec_dir, tn, am, ac) * w_o;                // :345
-                    float pressure = atten * amp * fd * ((p->quirks & PBRT_USQ_NO_CARRIER) ? 1.0f : sinf(phase));  // :348 / f-3
+                    float alpha;
+                    float fd = directivity_weight_i(sec_dir, tn, am, ac, &alpha) * w_o;        // :345
+                    const float carrier = (p->quirks & PBRT_USQ_NO_CARRIER) ? 1.0f : sinf(phase);
+                    float pressure = atten * amp * fd * carrier;                               // :348 / f-3
                     pressure *= w_ray;                                                         // (x 1, or the emitter ray's weight)
                     float tf = rintf(total_time * p->fs);                                      // :351-352 (half-to-even)
                     if (p->quirks & PBRT_USQ_CLAMP_TIME) tf = fminf(fmaxf(tf, 0.0f), (float)(T - 1));
-                    if (tf >= 0.0f && tf < (float)T && visible)                                // :353
-                        acc[((size_t)a * NE + recv) * T + (size_t)tf] += (double)pressure;     // :354
+                    if (tf >= 0.0f && tf < (float)T && visible) {                              // :353
+                        const size_t ci = ((size_t)a * NE + recv) * T + (size_t)tf;
+                        acc[ci] += (double)pressure;                                           // :354
+                        if (abs_sum) acc_abs[ci] += fabs((double)pressure);
+                        if (count) count[ci] += 1;
+                        const double margin = ldexp((double)ac, -16);
+                        if (ramp_sum && alpha >= (double)am - margin && alpha <= (double)ac + margin)
+                            acc_ramp[ci] += fabs((double)atten * (double)amp * (double)w_o * (double)carrier * (double)w_ray);
+                    }
                     d = normalize(new_dir);                                                    // :358-359
                     o = offset_origin(si.p, si.n, d);
                     depth += 1;                                                                // :361
@@ -1298,11 +1315,25 @@ int oracle_us_acquire(oracle_scene *s, const pbrt_us_params *p, uint32_t seed, u
         }
     const double inv_norm = 1.0 / (double)(norm_paths ? norm_paths : 1);
     for (size_t i = 0; i < acc.size(); ++i) channel_buf[i] = (float)(acc[i] * inv_norm);
+    for (size_t i = 0; i < acc_abs.size(); ++i) abs_sum[i] = (float)(acc_abs[i] * inv_norm);
+    for (size_t i = 0; i < acc_ramp.size(); ++i) ramp_sum[i] = (float)(acc_ramp[i] * inv_norm);
     if (stats) {
         stats[0] = segs;
         stats[1] = shadows;
     }
     return PBRT_OK;
+}
+
+int oracle_us_acquire(oracle_scene *s, const pbrt_us_params *p, uint32_t seed, uint32_t paths_per_ray,
+                      uint32_t path_offset, uint32_t norm_paths, float *channel_buf, float *tx_delays, uint64_t *stats) {
+    return us_acquire_impl(s, p, seed, paths_per_ray, path_offset, norm_paths, channel_buf, tx_delays, stats, nullptr, nullptr, nullptr);
+}
+
+int oracle_us_acquire_bounds(oracle_scene *s, const pbrt_us_params *p, uint32_t seed, uint32_t paths_per_ray, uint32_t path_offset,
+                             uint32_t norm_paths, float *channel_buf, float *tx_delays, uint64_t *stats, float *abs_sum,
+                             uint32_t *count, float *ramp_sum) {
+    return us_acquire_impl(s, p, seed, paths_per_ray, path_offset, norm_paths, channel_buf, tx_delays, stats, abs_sum, count,
+                           ramp_sum);
 }
 
 // ------------------------------------------------------------------------------------------------

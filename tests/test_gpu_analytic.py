@@ -126,34 +126,55 @@ def test_cosine_hemisphere_moments_on_the_device(mi):
 
 @pytest.mark.parametrize("tables", [True, False])
 def test_single_plate_echo_arrival_bins_on_the_device(mi, capi, tables):
-    """Plate perpendicular to the beam at depth z: the first echo of element e received at element r arrives at
-    t = z / c + sqrt(z^2 + (x_r - x_e)^2) / c  ->  bin round(t fs)  (CustomIntegrator.py:316,329,351-352); the on-axis echo at
-    round(2 z / c fs).  With and without the first-bounce tables (k_us_first + table-driven depth 0 / every path walks)."""
+    """the 16-element probe, unsteered (see _plate_echo_bins)"""
+    _plate_echo_bins(mi, capi, tables, 16, 0.0)
+
+
+@pytest.mark.parametrize("N,theta", [(1, 0.0), (7, 0.0), (128, 0.0), (16, 12.0), (7, -9.0), (128, 17.0)])
+@pytest.mark.parametrize("tables", [True, False])
+def test_single_plate_echo_arrival_bins_beyond_the_probe(mi, capi, tables, N, theta):
+    """other element counts and steered plane waves (see _plate_echo_bins)"""
+    _plate_echo_bins(mi, capi, tables, N, theta)
+
+
+def _plate_echo_bins(mi, capi, tables, N, theta):
+    """Plate perpendicular to the probe axis at depth z, plane wave steered by theta: element e fires at tx = x_e sin(theta) / c
+    (:254,257), its ray meets the plate at x_e + z tan(theta) after z / (c cos(theta)), and the echo received at element r arrives at
+    t = x_e sin(theta) / c + z / (c cos(theta)) + sqrt(z^2 + (x_r - x_e - z tan(theta))^2) / c  ->  bin round(t fs)
+    (CustomIntegrator.py:316,329,351-352), within one bin; at theta = 0 the on-axis echo at round(2 z / c fs).  1, 7, 16 and 128
+    elements (FastDiv's is_one, general and power-of-two paths).  With and without the first-bounce tables (k_us_first +
+    table-driven depth 0 / every path walks)."""
     T = mi.ScalarTransform4f
-    z, c, fs, N, pitch = 0.03, 1540.0, 50e6, 16, 3e-4
+    z, c, fs, pitch, n_t = 0.03, 1540.0, 50e6, 3e-4, 4000
     d = {"type": "scene",
          "integrator": {"type": "ultrasound_integrator", "max_depth": 1, "sampling_rate": fs, "frequency": 5e6, "sound_speed": c,
                         "attenuation": 0.0, "main_beam_angle": 80, "cutoff_angle": 85, "n_elements": N, "pitch": pitch,
-                        "time_samples": 4000, "angles": np.array([0.0], np.float32)},
+                        "time_samples": n_t, "angles": np.array([theta], np.float32)},
          "sensor": {"type": "ultrasound_sensor", "to_world": T().look_at([0, 0, 0], [0, 0, 0.03], [0, 1, 0])},
          "plate": {"type": "rectangle", "to_world": T().translate([0, 0, z]).rotate([0, 1, 0], 180).scale(0.5),
                    "bsdf": {"type": "ultrasound_bsdf", "impedance": 7.8, "roughness": 0.7}}}
     sc = mi.load_dict(d)
     ui = sc.integrator()
     q = ui.quirks | (0 if tables else capi.USQ_NO_FIRST_TABLES)
-    buf = ui._acquire(sc, q, paths_per_ray=400, seed=5)
-    assert np.all(ui.transmission_delays_buf == 0) and buf.shape == (1, N, 4000)
-    ex = ui.elem_x.numpy()
-    allowed = np.zeros((N, 4000), bool)
+    ppr = 400
+    buf = ui._acquire(sc, q, paths_per_ray=ppr, seed=5)
+    assert buf.shape == (1, N, n_t) and mi.default_context().stats()["samples"] == N * ppr
+    ex = ui.elem_x.numpy().astype(np.float64)
+    th = math.radians(float(np.float32(theta)))
+    if theta == 0:
+        assert np.all(ui.transmission_delays_buf == 0)
+    np.testing.assert_allclose(ui.transmission_delays_buf, ex * math.sin(th) / c, rtol=1e-5, atol=1e-12)
+    allowed = np.zeros((N, n_t), bool)
     for r in range(N):
         for e in range(N):
-            t = z / c + math.sqrt(z * z + (ex[r] - ex[e]) ** 2) / c
+            t = ex[e] * math.sin(th) / c + z / (c * math.cos(th)) + math.sqrt(z * z + (ex[r] - ex[e] - z * math.tan(th)) ** 2) / c
+            b = int(np.rint(t * fs))
             allowed[r, int(np.rint(np.float32(t) * np.float32(fs)))] = True
-            allowed[r, min(3999, int(np.rint(t * fs)) + 1)] = True
-            allowed[r, int(np.rint(t * fs)) - 1] = True
+            allowed[r, max(0, b - 1):min(n_t, b + 2)] = True
     nz = buf[0] != 0
-    assert nz.sum() > 0 and not np.any(nz & ~allowed)
-    assert np.argwhere(nz)[:, 1].min() == int(np.rint(2 * z / c * fs))      # on-axis echo: 2 z / c
+    assert nz.sum() >= N and nz.any(axis=1).all() and not np.any(nz & ~allowed)     # every receiver hears the plate, nowhere else
+    if theta == 0:
+        assert np.argwhere(nz)[:, 1].min() == int(np.rint(2 * z / c * fs))      # on-axis echo: 2 z / c
 
 
 def test_emitter_rays_without_jitter_are_the_integrators_own_rays(mi, capi):
