@@ -463,11 +463,14 @@ int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data
                       const float *elem_x, const float *x, const float *z, float *out);
 
 /* replaces: ultraspy DelayAndSum.compute_envelope(d_output, scan) on RF data (USMain.py:205): modulus of the
- * analytic signal along the axial (z, fastest) axis, i.e. |scipy.signal.hilbert(rf, axis=-1)|.  nz <= 4096. */
+ * analytic signal along the axial (z, fastest) axis, i.e. |scipy.signal.hilbert(rf, axis=-1)|.  nz <= 4096.
+ * A column that holds a NaN or an infinity comes out NaN at every sample, as the FFT of the definition makes it; the other
+ * columns are not affected.  Finite input gives the same bits whichever of the two kernels (odd / even nz) runs. */
 int pbrt_envelope(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const float *rf, float *env);
 
 /* replaces: the manual log compression of USMain.py:210-218: db = 20 log10(env + 1e-12), clipped to
- * [max(db) - dynamic_range_db, max(db)], mapped to [0, 1].  n values in, n values out. */
+ * [max(db) - dynamic_range_db, max(db)], mapped to [0, 1].  n values in, n values out.  As np.max does there, a NaN
+ * propagates: if any value is NaN, or so negative that env + 1e-12f < 0, max(db) is NaN and every output is NaN. */
 int pbrt_log_compress(pbrt_ctx *ctx, uint32_t n, const float *env, float dynamic_range_db, float *out);
 
 /* SURVEY.md section 8 f-3, the pulse model of the reference's prototype (RayTracingV0.py:194-204, "UltraRay Eq. 14"):
@@ -514,9 +517,9 @@ int pbrt_das_first_arrival_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const vo
                                const void *d_x, const void *d_z, void *d_table);
 int pbrt_das_beamform_table_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table,
                                 const void *d_elem_x, const void *d_x, const void *d_z, void *d_out);
-/* replaces: DelayAndSum.compute_envelope (USMain.py:205); d_rf, d_env [nx][nz], distinct buffers */
+/* replaces: DelayAndSum.compute_envelope (USMain.py:205); d_rf, d_env [nx][nz], distinct buffers; NaN as pbrt_envelope */
 int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf, void *d_env);
-/* replaces: the log compression of USMain.py:210-218; d_env, d_out [n] (may be the same buffer) */
+/* replaces: the log compression of USMain.py:210-218; d_env, d_out [n] (may be the same buffer); NaN as pbrt_log_compress */
 int pbrt_log_compress_dev(pbrt_ctx *ctx, uint32_t n, const void *d_env, float dynamic_range_db, void *d_out);
 /* the pulse model (RayTracingV0.py:194-204) on a channel buffer in HBM; d_in, d_out [n_traces][time_samples], distinct */
 int pbrt_us_apply_pulse_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,

@@ -284,6 +284,24 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
 #define ENV_TAPS_EVEN (2u * ENV_MAX_N + 8u)
 __host__ DEV uint32_t env_even_len(uint32_t Mp) { return 2u * Mp + 16u; }  // entries of one compact table of k_hilbert_env_even
 #define ENV_TAPS_FLOATS (ENV_TAPS_EVEN + 4u * (ENV_MAX_N + 16u))
+// Non-finite input: the analytic signal of a column that holds a NaN or an infinity is NaN at every sample (the FFT of the definition
+// spreads it over the whole column).  Both kernels note, during the copy of the column into LDS, whether a thread copied such a value;
+// the barrier after the copy ORs the notes over the workgroup, and a column with one writes NaN to all of its outputs.  (Without it
+// k_hilbert_env_even, which never multiplies by the zero taps, left the outputs of the same parity as the NaN finite.)
+DEV bool env_nonfinite(float v) { return !(__builtin_fabsf(v) <= 3.402823466e38f); }
+// __syncthreads() that also returns the OR of `p` over the workgroup (whole waves: the envelope kernels run a multiple of 64 threads)
+DEV bool env_sync_or(bool p) {
+    __shared__ uint32_t vote[4];
+    const bool wave = __ballot(p) != 0ull;
+    if ((threadIdx.x & 63u) == 0u) vote[threadIdx.x >> 6] = wave ? 1u : 0u;
+    __syncthreads();
+    uint32_t any = 0u;
+    for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) any |= vote[w];
+    return any != 0u;
+}
+DEV void env_column_nan(uint32_t N, float *__restrict__ out) {
+    for (uint32_t n = threadIdx.x; n < N; n += blockDim.x) out[n] = __builtin_nanf("");
+}
 DEV float hilbert_tap(uint32_t N, int32_t k) {  // h[k] for 0 < |k| < N (odd symmetry), 0 elsewhere
     const uint32_t n = (uint32_t)(k < 0 ? -k : k);
     double h = 0.0;
@@ -322,6 +340,7 @@ __global__ __launch_bounds__(256) void k_hilbert_env(uint32_t nz, const float *_
     float *xs = lds_env;      // [Np], zero beyond N (the tail of the column, and the outputs' own samples)
     float *g = lds_env + Np;  // the tap table
     const float *xr = rf + (size_t)col * N;
+    bool bad = false;  // this thread copied a NaN or an infinity
     // (four loads in flight per thread and round: one at a time, this copy is a chain of L2 round trips)
     for (uint32_t j0 = threadIdx.x; j0 < G; j0 += 4u * blockDim.x) {
         float v[4], w[4];
@@ -335,9 +354,13 @@ __global__ __launch_bounds__(256) void k_hilbert_env(uint32_t nz, const float *_
             const uint32_t j = j0 + u * blockDim.x;
             if (j < G) g[j] = v[u];
             if (j < Np) xs[j] = j < N ? w[u] : 0.0f;
+            bad |= j < N && env_nonfinite(w[u]);
         }
     }
-    __syncthreads();
+    if (env_sync_or(bad)) {
+        env_column_nan(N, env + (size_t)col * N);
+        return;
+    }
     // The kernel is bound by LDS reads, not by its multiply-adds: three 16-byte reads per 16 of them (the four samples as a broadcast,
     // the tap window as two quads) kept the LDS of a CU busy for 3 x as long as its SIMDs.  The window of trip m + 4 starts four taps
     // below the window of trip m, so its upper quad IS the lower quad of the trip before: one tap read per trip.  And the four samples
@@ -378,12 +401,14 @@ __global__ __launch_bounds__(256) void k_hilbert_env(uint32_t nz, const float *_
 // consecutive outputs (two of each parity) over eight consecutive inputs per trip -- all eight are used, so they stay wave-uniform
 // scalar loads -- and reads one tap quad per parity and trip; the two tables are kept at two alignments each so that the quad of
 // a thread with p0 = 2 (mod 4) is a 16-byte read as well.  Same sums in the same order as k_hilbert_env (a product with a zero tap
-// leaves the accumulator unchanged), so the same bits for finite input.  1040 columns of 638: 27.5 -> 20 us, not the 14 the
-// multiply-adds promise: a column is 160 quads = two and a half waves, so a sixth of the lanes idle, and a wave issues its 1 280
-// multiply-adds in 80 trips that each wait for their loads with three waves per SIMD to cover them (SQ counters: VALU issue 35 %
-// busy, 38 % of a wave's life in s_waitcnt).  Tried on top, both flat: the loads of trip q + 1 requested before the
-// multiply-adds of trip q (two register sets taking turns: 20.6 us, the copies cost what the waits gave), the copies of a table
-// 32 banks apart instead of 16 (20.8 us; the counters show 4 % of the LDS cycles in bank conflicts).
+// leaves the accumulator unchanged), so the same bits -- for FINITE input only: a NaN times a zero tap is NaN, so k_hilbert_env
+// would make every output NaN and these sums would not; both kernels therefore write a column with a non-finite sample as all NaN
+// (env_sync_or above).  1040 columns of 638: 27.5 -> 20 us, not the 14 the multiply-adds promise: a column is 160 quads = two
+// and a half waves, so a sixth of the lanes idle, and a wave issues its 1 280 multiply-adds in 80 trips that each wait for their
+// loads with three waves per SIMD to cover them (SQ counters: VALU issue 35 % busy, 38 % of a wave's life in s_waitcnt).  Tried
+// on top, both flat: the loads of trip q + 1 requested before the multiply-adds of trip q (two register sets taking turns:
+// 20.6 us, the copies cost what the waits gave), the copies of a table 32 banks apart instead of 16 (20.8 us; the counters show
+// 4 % of the LDS cycles in bank conflicts).
 // LDS: column [2 Mp] + four tables [2 Mp + 16], M = N / 2, Mp = M rounded up to 4.
 __global__ __launch_bounds__(256) void k_hilbert_env_even(uint32_t nz, const float *__restrict__ rf, const float *__restrict__ taps,
                                                           float *__restrict__ env) {
@@ -393,6 +418,7 @@ __global__ __launch_bounds__(256) void k_hilbert_env_even(uint32_t nz, const flo
     float *xs = lds_env;              // [2 Mp], zero beyond N
     float *tab = lds_env + 2u * Mp;   // [4][L]: U0 (even outputs) at origin Mp + 3 / Mp + 1, U1 (odd outputs) at origin Mp + 3 / Mp + 1
     const float *xr = rf + (size_t)col * N;
+    bool bad = false;  // this thread copied a NaN or an infinity
     // the column and the four tables (made once by k_hilbert_taps, in this layout) into LDS: four 16-byte loads in flight per thread
     // and round -- one load per round made this copy a chain of 17 L2 round trips, half of the kernel's time
     {
@@ -412,11 +438,16 @@ __global__ __launch_bounds__(256) void k_hilbert_env_even(uint32_t nz, const flo
 #pragma unroll
             for (uint32_t u = 0; u < 4u; ++u) v[u] = xr[min(j0 + u * blockDim.x, N - 1u)];
 #pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u)
+            for (uint32_t u = 0; u < 4u; ++u) {
                 if (j0 + u * blockDim.x < 2u * Mp) xs[j0 + u * blockDim.x] = j0 + u * blockDim.x < N ? v[u] : 0.0f;
+                bad |= j0 + u * blockDim.x < N && env_nonfinite(v[u]);
+            }
         }
     }
-    __syncthreads();
+    if (env_sync_or(bad)) {
+        env_column_nan(N, env + (size_t)col * N);
+        return;
+    }
     const uint32_t items = (N + 3u) >> 2;
     for (uint32_t it = threadIdx.x; it < items; it += blockDim.x) {
         const uint32_t p0 = 2u * it;   // outputs n = 4 it + (0, 1, 2, 3) = even p0, odd p0, even p0 + 1, odd p0 + 1
@@ -461,10 +492,15 @@ __global__ __launch_bounds__(256) void k_hilbert_env_even(uint32_t nz, const flo
 // Log compression (USMain.py:210-218).  Pass 1: every block leaves the maximum of its share of the (non-negative) envelope in its own
 // word; pass 2: every block folds those <= ENV_MAX_BLOCKS words and maps its pixels.  (Round 1 had 1024 blocks meet in one atomicMax on
 // a word the host had to clear first: 14 us for 2.6 MB, most of it the same-word atomics, plus a fill command per call.)
+// Non-finite input as USMain.py:213-218 has it, where np.max propagates NaN: a value whose log is NaN (NaN itself, or e + 1e-12 < 0)
+// makes the maximum NaN, and with it every pixel of the image.  fmaxf alone would drop the NaN, so each block also ORs a flag and
+// writes NaN as its maximum; the floor at 0 stays for finite input.  (+inf needs nothing: max_db = min_db = inf, inf - inf = NaN.)
 #define ENV_MAX_BLOCKS 256u
+DEV bool log_nan(float e) { return !(e + 1e-12f >= 0.0f); }  // 20 log10f(e + 1e-12f) is NaN
 __global__ __launch_bounds__(256) void k_env_max(uint32_t n, const float *__restrict__ env, float *__restrict__ block_max) {
     __shared__ float part[4];
     float m = 0.0f;
+    bool bad = false;
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     // (the maximum does not depend on the order: 16-byte loads where the buffer allows them, a wave folds its lanes through DPP moves,
     // one barrier.  Both passes together 11.3 -> 11.0 us by HIP events for the 2.65 MB image of USMain.py: what they cost is two launches)
@@ -474,26 +510,44 @@ __global__ __launch_bounds__(256) void k_env_max(uint32_t n, const float *__rest
         for (uint32_t i = tid; i < n4; i += stride) {
             const float4 v = e4[i];
             m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+            bad = bad || log_nan(v.x) || log_nan(v.y) || log_nan(v.z) || log_nan(v.w);
         }
-        for (uint32_t i = (n4 << 2) + tid; i < n; i += stride) m = fmaxf(m, env[i]);
+        for (uint32_t i = (n4 << 2) + tid; i < n; i += stride) {
+            m = fmaxf(m, env[i]);
+            bad |= log_nan(env[i]);
+        }
     } else {
-        for (uint32_t i = tid; i < n; i += stride) m = fmaxf(m, env[i]);
+        for (uint32_t i = tid; i < n; i += stride) {
+            m = fmaxf(m, env[i]);
+            bad |= log_nan(env[i]);
+        }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = m;
+    const bool wave_bad = __ballot(bad) != 0ull;  // (all lanes vote: not inside the branch below)
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = wave_bad ? __builtin_nanf("") : m;
     __syncthreads();
-    if (threadIdx.x == 0) block_max[blockIdx.x] = fmaxf(fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3])), 0.0f);
+    if (threadIdx.x == 0) {
+        const float p = fmaxf(fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3])), 0.0f);
+        const bool nan = part[0] != part[0] || part[1] != part[1] || part[2] != part[2] || part[3] != part[3];
+        block_max[blockIdx.x] = nan ? __builtin_nanf("") : p;
+    }
 }
 __global__ __launch_bounds__(256) void k_log_compress(uint32_t n, const float *__restrict__ env, const float *__restrict__ block_max,
                                                       uint32_t n_blocks, float dr, float *__restrict__ out) {
     // every wave folds the <= ENV_MAX_BLOCKS maxima by itself (four loads per lane, DPP moves): no LDS, no barrier
     const uint32_t lane = threadIdx.x & 63u;
     float gm = 0.0f;
+    bool nan = false;  // a block's maximum is NaN: so is the image's
 #pragma unroll
-    for (uint32_t k = 0; k < ENV_MAX_BLOCKS / 64u; ++k) gm = fmaxf(gm, lane + 64u * k < n_blocks ? block_max[lane + 64u * k] : 0.0f);
+    for (uint32_t k = 0; k < ENV_MAX_BLOCKS / 64u; ++k) {
+        const float b = lane + 64u * k < n_blocks ? block_max[lane + 64u * k] : 0.0f;
+        gm = fmaxf(gm, b);
+        nan |= b != b;
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) gm = fmaxf(gm, __shfl_xor(gm, off));
+    if (__ballot(nan) != 0ull) gm = __builtin_nanf("");
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float max_db = 20.0f * log10f(gm + 1e-12f);

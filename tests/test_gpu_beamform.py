@@ -251,7 +251,8 @@ def test_envelope_of_odd_and_even_columns_against_scipy_definition(mi):
 
 def test_even_columns_skip_the_zero_taps_and_change_no_bit(mi, monkeypatch):
     """k_hilbert_env_even (even column lengths: every even tap of the discrete Hilbert kernel is zero, so an even output is a sum over
-    the odd inputs only) against k_hilbert_env on the same columns: the same sums in the same order, bit for bit"""
+    the odd inputs only) against k_hilbert_env on the same columns: the same sums in the same order, bit for bit (finite columns; one
+    with a NaN or an infinity is all NaN in both, test_gpu_imgform_shapes.py)"""
     for N in (8, 10, 12, 14, 30, 256, 638, 1000, 4094, 4096):
         rng = np.random.default_rng(500 + N)
         rf = rng.normal(size=(5, N)).astype(np.float32)
