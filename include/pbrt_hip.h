@@ -50,14 +50,20 @@ extern "C" {
  *   CONE           g = row-major 3x4 world -> object matrix of the closed unit cone (apex (0,0,1), base disc of
  *                  radius 1 in z = 0): any affine to_world, e.g. the 0.06 / 0.06 / 0.10 scale of
  *                  MitsubaScenes/Cone_Box.xml:36-47.  Hits report u = 0 (lateral surface) / 1 (base disc), v = 0.
+ *   CYLINDER       g = row-major 3x4 world -> object matrix of the OPEN unit tube x^2 + y^2 = 1, 0 <= z <= 1 (no caps;
+ *                  Mitsuba 'cylinder': object -> world = to_world * translate(p0) * to_frame((p1-p0)/L) *
+ *                  scale(radius, radius, L), L = |p1 - p0|).  Orientation is the sign of det(3x3 part): > 0 normals
+ *                  point away from the axis, < 0 towards it (flip_normals; the tube is symmetric under x -> -x, so the
+ *                  host mirrors object x to pick the sign).  Hits report u = v = 0.
  * The scenes that feed these: scenes/cbox.xml (12 triangles + 2 spheres), scenes/simple.xml
- * (teapot.ply, 2256 triangles), MitsubaScenes/ *.xml (sphere / rectangle / cone),
+ * (teapot.ply, 2256 triangles), MitsubaScenes/ *.xml (sphere / rectangle / cone), RayTracingV0.py (cylinder),
  * TestRing/TestRing.obj (1152 triangles).
  */
 #define PBRT_PRIM_TRIANGLE 0u
 #define PBRT_PRIM_SPHERE 1u
 #define PBRT_PRIM_PARALLELOGRAM 2u
 #define PBRT_PRIM_CONE 3u /* analytic; cannot carry an area emitter (like SPHERE) */
+#define PBRT_PRIM_CYLINDER 4u /* analytic; cannot carry an area emitter (like SPHERE) */
 
 typedef struct pbrt_prim {
     float g[12];

@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("PBRT_HIP_LIB") or os.path.join(_HERE, "csrc", "libpbr
 PBRT_ABI_VERSION = 5
 
 # primitive / material / emitter / filter / accel enums (include/pbrt_hip.h)
-PRIM_TRIANGLE, PRIM_SPHERE, PRIM_PARALLELOGRAM, PRIM_CONE = 0, 1, 2, 3
+PRIM_TRIANGLE, PRIM_SPHERE, PRIM_PARALLELOGRAM, PRIM_CONE, PRIM_CYLINDER = 0, 1, 2, 3, 4
 MAT_DIFFUSE, MAT_CONDUCTOR, MAT_DIELECTRIC, MAT_ULTRA, MAT_NONE = 0, 1, 2, 3, 4
 EMIT_AREA, EMIT_POINT = 0, 1
 ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH, ACCEL_BVH_GLOBAL = 0, 1, 2, 3

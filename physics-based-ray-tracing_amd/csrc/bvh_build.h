@@ -47,6 +47,12 @@ inline bool cone_world_frame(const pbrt_prim &P, double c[3], double a[3], doubl
     return true;
 }
 
+// World-space frame of a CYLINDER primitive (D16): the centres c0, c1 of the end discs z = 0 / z = 1 and the images a, b of the
+// object x / y unit vectors (end disc k is ck + a cos + b sin).  The cone's inverse: its apex is the image of (0, 0, 1).
+inline bool cylinder_world_frame(const pbrt_prim &P, double c0[3], double c1[3], double a[3], double b[3]) {
+    return cone_world_frame(P, c0, a, b, c1);
+}
+
 // SAH parameters (A/B-able): cost of one node step relative to one primitive test, and the largest leaf.
 // Measured on MI355X (ring 1024^2 x 64 spp / 896-triangle cone phantom): 0.25 / 0.5 / 1 / 2 at <= 4 per leaf:
 // 21.95 / 22.05 / 22.10 / 24.13 ms; leaves of <= 2 / 6 / 8: 22.07 / 22.13 / 24.04 ms -- flat around the defaults.
@@ -95,6 +101,16 @@ inline Box prim_box(const pbrt_prim &P) {
             const double r = std::sqrt(a[k] * a[k] + bb[k] * bb[k]);
             b.lo[k] = std::nextafter((float)std::min(c[k] - r, apex[k]), -INFINITY);
             b.hi[k] = std::nextafter((float)std::max(c[k] + r, apex[k]), INFINITY);
+        }
+        return b;
+    }
+    if (P.type == PBRT_PRIM_CYLINDER) {  // box of the two end ellipses (padded like every box by the builder)
+        double c0[3], c1[3], a[3], bb[3];
+        cylinder_world_frame(P, c0, c1, a, bb);  // validated at scene creation
+        for (int k = 0; k < 3; ++k) {
+            const double r = std::sqrt(a[k] * a[k] + bb[k] * bb[k]);
+            b.lo[k] = std::nextafter((float)(std::min(c0[k], c1[k]) - r), -INFINITY);
+            b.hi[k] = std::nextafter((float)(std::max(c0[k], c1[k]) + r), INFINITY);
         }
         return b;
     }
@@ -396,7 +412,7 @@ inline void make_leaf_prims(const pbrt_prim *prims, const std::vector<uint32_t> 
     for (size_t s = 0; s < order.size(); ++s) {
         const pbrt_prim &P = prims[order[s]];
         HostLeafPrim L{};
-        for (int k = 0; k < 9; ++k) L.g[k] = P.g[k];  // cone: the record is read from the full table (meta holds the index)
+        for (int k = 0; k < 9; ++k) L.g[k] = P.g[k];  // cone / cylinder: the record is read from the full table (meta holds the index)
         L.meta = (P.type << 28) | (order[s] & 0x0fffffffu);
         (*out)[s] = L;
     }

@@ -185,6 +185,36 @@ DEV bool cone_hit(const pbrt_prim &P, V3 o, V3 d, float tmax, float *t, float *f
     return found;
 }
 
+// Analytic cylinder (Mitsuba 'cylinder', RayTracingV0.py:13-47; [DEFINE] D16): the open unit tube x^2 + y^2 = 1, 0 <= z <= 1 in
+// object space, reached like the cone through the world -> object matrix (t preserved, direction not re-normalised).  Same
+// cancellation-free root pair; the nearest root in [0, tmax] whose z lies in [0, 1] (a ray from inside meets the far wall).  A ray
+// parallel to the axis has A = b = 0: q / A is NaN and C / q is +-inf (or NaN on the wall itself), and both fail the range tests.
+DEV bool cylinder_hit(const pbrt_prim &P, V3 o, V3 d, float tmax, float *t) {
+    const V3 r0 = g3(P, 0), r1 = g3(P, 4), r2 = g3(P, 8);
+    const V3 oo = {dot(r0, o) + P.g[3], dot(r1, o) + P.g[7], dot(r2, o) + P.g[11]};
+    const V3 dd = {dot(r0, d), dot(r1, d), dot(r2, d)};
+    const float A = fma_(dd.x, dd.x, dd.y * dd.y);
+    const float b = fma_(oo.x, dd.x, oo.y * dd.y);
+    const float C = fma_(oo.x, oo.x, fma_(oo.y, oo.y, -1.0f));
+    const float disc = fma_(b, b, -(A * C));
+    if (!(disc >= 0.0f)) return false;
+    const float q = -(b + copysignf(sqrtf(disc), b));
+    const float ta = q / A, tb = C / q;
+    const float za = fma_(ta, dd.z, oo.z), zb = fma_(tb, dd.z, oo.z);
+    float best = tmax;
+    bool found = false;
+    if (ta >= 0.0f && ta <= best && za >= 0.0f && za <= 1.0f) {
+        best = ta;
+        found = true;
+    }
+    if (tb >= 0.0f && tb <= best && zb >= 0.0f && zb <= 1.0f && (!found || tb < best)) {
+        best = tb;
+        found = true;
+    }
+    *t = best;
+    return found;
+}
+
 // One primitive against one ray; identical arithmetic to the oracle's prim_hit (Mitsuba
 // Mesh::ray_intersect_triangle / Sphere / Rectangle reached via scene.ray_intersect,
 // CustomIntegrator.py:309).  The barycentric test runs on det-scaled values so that the division
@@ -232,6 +262,8 @@ DEV bool planar_hit(bool triangle, V3 v0, V3 e1, V3 e2, V3 o, V3 d, float tmax, 
     *v = vs * inv;
     return true;
 }
+// CYL = false: the cylinder test is compiled out (the stream shading kernels of scenes without one, pbrt_api.hip)
+template <bool CYL = true>
 DEV bool prim_hit(const pbrt_prim &P, V3 o, V3 d, float tmax, float *t, float *u, float *v) {
     const uint32_t type = P.type;
     if (type == PBRT_PRIM_SPHERE) {
@@ -244,6 +276,11 @@ DEV bool prim_hit(const pbrt_prim &P, V3 o, V3 d, float tmax, float *t, float *u
     if (type == PBRT_PRIM_CONE) {
         *v = 0.0f;
         return cone_hit(P, o, d, tmax, t, u);
+    }
+    if (CYL && type == PBRT_PRIM_CYLINDER) {
+        *u = 0.0f;
+        *v = 0.0f;
+        return cylinder_hit(P, o, d, tmax, t);
     }
     return false;
 }
@@ -270,9 +307,10 @@ DEV pbrt_prim load_prim_uniform(const pbrt_prim *p) {
     return __builtin_bit_cast(pbrt_prim, r);
 }
 
-// CONES: the kernel variant understands PBRT_PRIM_CONE records.  Compile-time, because the cone branch costs the
+// CONES: the kernel variant understands the analytic quadrics, PBRT_PRIM_CONE and PBRT_PRIM_CYLINDER records.  Compile-time,
+// because the cone branch costs the
 // 64-VGPR brute-force radiance kernel 9 VGPRs and puts it into scratch (measured: 54 / 60 -> 63 VGPRs + 4 spilled);
-// small scenes with a cone run the ACCEL_K_BRUTE_BIG variant instead (pbrt_api.hip).
+// small scenes with a cone or a cylinder run the ACCEL_K_BRUTE_BIG variant instead (pbrt_api.hip).
 template <bool ANY, bool SEGMENT = false, bool CONES = true>
 DEV bool brute_intersect(const DevScene &sc, V3 o, V3 d, float tmax, Hit *h) {
     bool found = false;
@@ -292,12 +330,12 @@ DEV bool brute_intersect(const DevScene &sc, V3 o, V3 d, float tmax, Hit *h) {
         const uint32_t type = P.type;  // wave-uniform
         bool ok;
         float num, den, us, vs;
-        if (type == PBRT_PRIM_SPHERE || (CONES && type == PBRT_PRIM_CONE)) {  // curved primitives report (t, 1)
+        if (type == PBRT_PRIM_SPHERE || (CONES && (type == PBRT_PRIM_CONE || type == PBRT_PRIM_CYLINDER))) {  // curved: (t, 1)
             float t, u, v;
             ok = prim_hit(P, o, d, tmax, &t, &u, &v);
             num = t;
             den = 1.0f;
-            us = u;  // 0 for spheres; cone: 0 lateral surface / 1 base disc (den = 1: passes through unscaled)
+            us = u;  // 0 for spheres / cylinders; cone: 0 lateral surface / 1 base disc (den = 1: passes through unscaled)
             vs = 0.0f;
         } else {
             V3 v0 = g3(P, 0), e1 = g3(P, 3), e2 = g3(P, 6);
@@ -485,8 +523,8 @@ DEV void bvh_visit(const Tree &tr, const BvhStack &st, BvhCursor &c, BvhOvf &ovf
     bvh_push(st, c, ovf, n_more != 0u, entry);
 }
 
-// One leaf record against the ray (`full`: the 64-byte table, read for cones only).  CURVED = false: the scene holds triangles
-// and parallelograms only (the host knows), the sphere and cone tests are compiled out.
+// One leaf record against the ray (`full`: the 64-byte table, read for cones and cylinders only).  CURVED = false: the scene holds
+// triangles and parallelograms only (the host knows), the sphere, cone and cylinder tests are compiled out.
 template <bool CURVED = true>
 DEV bool lprim_hit(const LeafQ &L, const pbrt_prim *full, V3 o, V3 d, float tmax, float *t, float *u, float *v, uint32_t *id) {
     const uint32_t meta = L.e.y, type = meta >> 28;
@@ -500,6 +538,11 @@ DEV bool lprim_hit(const LeafQ &L, const pbrt_prim *full, V3 o, V3 d, float tmax
     if (CURVED && type == PBRT_PRIM_CONE) {
         *v = 0.0f;
         return cone_hit(full[*id], o, d, tmax, t, u);
+    }
+    if (CURVED && type == PBRT_PRIM_CYLINDER) {
+        *u = 0.0f;
+        *v = 0.0f;
+        return cylinder_hit(full[*id], o, d, tmax, t);
     }
     const V3 e1 = {__uint_as_float(L.b.y), __uint_as_float(L.c.x), __uint_as_float(L.c.y)};
     const V3 e2 = {__uint_as_float(L.d.x), __uint_as_float(L.d.y), __uint_as_float(L.e.x)};
@@ -657,6 +700,14 @@ DEV V3 shading_normal(const pbrt_prim &P, V3 n, float u, float v, const float *v
     const float b0 = 1.0f - u - v;
     return normalize(madd(n0, b0, madd(n1, u, n2 * v)));
 }
+// Cylinder normal at a world point p of the tube: M^T (x_o, y_o, 0) (object-space gradient of x^2 + y^2, to world space by the
+// transpose of the world -> object matrix), away from the axis; towards it when det(M) < 0 (flip_normals, pbrt_hip.h).
+DEV V3 cylinder_normal(const pbrt_prim &P, V3 p) {
+    const V3 r0 = g3(P, 0), r1 = g3(P, 4), r2 = g3(P, 8);
+    const float xo = dot(r0, p) + P.g[3], yo = dot(r1, p) + P.g[7];
+    const V3 n = normalize(madd(r0, xo, r1 * yo));
+    return dot(r2, cross(r0, r1)) < 0.0f ? v3(-n.x, -n.y, -n.z) : n;
+}
 template <bool CONES = true>
 DEV SI make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, const float *vn = nullptr, uint32_t slot = 0) {
     SI si;
@@ -677,6 +728,9 @@ DEV SI make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, const 
         }
         si.n = normalize(v3(fma_(r0.x, no.x, fma_(r1.x, no.y, r2.x * no.z)), fma_(r0.y, no.x, fma_(r1.y, no.y, r2.y * no.z)),
                             fma_(r0.z, no.x, fma_(r1.z, no.y, r2.z * no.z))));
+    } else if (CONES && P.type == PBRT_PRIM_CYLINDER) {
+        si.p = madd(d, t, o);
+        si.n = cylinder_normal(P, si.p);
     } else {
         si.p = madd(g3(P, 6), v, madd(g3(P, 3), u, g3(P, 0)));
         si.n = g3(P, 9);
@@ -691,10 +745,13 @@ DEV SI make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, const 
 //   sphere: 2 pi (-y, x, 0) of the hit point about the centre (Sphere::compute_surface_interaction; the record holds
 //     centre + radius only, so the sphere's object axes are taken parallel to the world's)
 //   cone ([DEFINE] shape, no Mitsuba definition): none -> coordinate_system(n)
-template <bool CONES = true>
+//   cylinder (D16): Mitsuba's dp/dphi = to_world (-y, x, 0), i.e. along axis x n_outward.  The axis image is (r0 x r1) / det(M)
+//     and si.n = sign(det(M)) n_outward, so (r0 x r1) x si.n points that way whichever orientation the record encodes
+template <bool CONES = true, bool CYL = CONES>
 DEV V3 si_dp_du(const pbrt_prim &P, const SI &si) {
     if (P.type == PBRT_PRIM_SPHERE) return {-(si.p.y - P.g[1]), si.p.x - P.g[0], 0.0f};
     if (CONES && P.type == PBRT_PRIM_CONE) return {0.0f, 0.0f, 0.0f};
+    if (CYL && P.type == PBRT_PRIM_CYLINDER) return cross(cross(g3(P, 0), g3(P, 4)), si.n);
     return g3(P, 3);
 }
 

@@ -58,8 +58,9 @@ __global__ __launch_bounds__(256) void k_us_init_wf(const UsArgs a, float4 *st, 
     st[3u * cp + i] = q3;
 }
 
-// TAB: depth 0 with the first-bounce tables (the paths are generated from their index, nothing is read but the tables)
-template <bool TAB>
+// TAB: depth 0 with the first-bounce tables (the paths are generated from their index, nothing is read but the tables).
+// CYL: the scene holds cylinders (else their code is compiled out)
+template <bool TAB, bool CYL>
 __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_shade(const UsWfArgs w) {
     constexpr uint32_t T_ = WF_SHADE_THREADS, W = T_ / 64;
     constexpr int NCH = WF_SHADE_CHUNKS;
@@ -209,11 +210,11 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
             if (!TAB) {  // (t, u, v) of the hit k_trace found; a repetition that disagrees fails the call (kernels_wavefront.h k_shade)
                 h.t = K_INF;
                 h.u = h.v = 0.0f;
-                if (!prim_hit(P, o, d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(w.guard + WF_GUARD_REHIT, 1u);
+                if (!prim_hit<CYL>(P, o, d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(w.guard + WF_GUARD_REHIT, 1u);
             }
             const uint32_t depth = a.depth;
             const V3 tn = {uni[12], uni[13], uni[14]};
-            const SI si = wf_make_si(P, o, d, h.t, h.u, h.v, has_vn, vn);
+            const SI si = wf_make_si<CYL>(P, o, d, h.t, h.u, h.v, has_vn, vn);
             const float distance = h.t;                                                   // :314
             geo_len += distance;                                                          // :315
             const bool no_acc = (a.p.quirks & PBRT_USQ_NO_TOF_ACCUM) != 0;
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
             }
             atten *= expf(uni[18] * distance / 8.686f);                                   // :328
             const pbrt_material M = a.sc.mats[P.material];
-            const Frame fr = make_sh_frame(si.ns, si_dp_du<true>(P, si));
+            const Frame fr = make_sh_frame(si.ns, si_dp_du<true, CYL>(P, si));
             const V3 wi = to_local(fr, -d);
             float a_resp, bpdf;
             V3 new_dir;

@@ -426,7 +426,9 @@ DEV WfVn wf_load_vn(const float *vn, uint32_t slot) {  // vn != nullptr
     for (int k = 0; k < 9; ++k) o.n[k] = r[k];
     return o;
 }
-// make_si on the preloaded record (same statements as device_scene.h make_si / shading_normal)
+// make_si on the preloaded record (same statements as device_scene.h make_si / shading_normal).  CYL = false: the scene has no
+// cylinder and its branch is compiled out (k_shade / k_us_shade keep their registers on every other scene)
+template <bool CYL>
 DEV SI wf_make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, bool has_vn, const WfVn &vn) {
     SI si;
     if (P.type == PBRT_PRIM_SPHERE) {
@@ -444,6 +446,9 @@ DEV SI wf_make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, boo
         }
         si.n = normalize(v3(fma_(r0.x, no.x, fma_(r1.x, no.y, r2.x * no.z)), fma_(r0.y, no.x, fma_(r1.y, no.y, r2.y * no.z)),
                             fma_(r0.z, no.x, fma_(r1.z, no.y, r2.z * no.z))));
+    } else if (CYL && P.type == PBRT_PRIM_CYLINDER) {
+        si.p = madd(d, t, o);
+        si.n = cylinder_normal(P, si.p);
     } else {
         si.p = madd(g3(P, 6), v, madd(g3(P, 3), u, g3(P, 0)));
         si.n = g3(P, 9);
@@ -464,13 +469,13 @@ DEV SI wf_make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, boo
 }
 
 // bounce_step from the shading on, with the shadow ray handed out instead of traced (same statements, same order)
-template <int ACCEL>
+template <int ACCEL, bool CYL>
 DEV bool wf_shade_step(const WfArgs &a, const Tables &tb, uint32_t depth, uint32_t ka, uint32_t kb, const Hit &h, const pbrt_prim &P,
                        bool has_vn, const WfVn &vn, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, WfShadow &sh) {
     bool survive = false;
     sh.on = false;
     const uint32_t nE = a.sc.n_emitters;
-    SI si = wf_make_si(P, o, d, h.t, h.u, h.v, has_vn, vn);
+    SI si = wf_make_si<CYL>(P, o, d, h.t, h.u, h.v, has_vn, vn);
     const int32_t emitter = P.emitter;
     const uint32_t mat_id = P.material;
     if (emitter >= 0) {
@@ -563,8 +568,8 @@ DEV Tables wf_tables_lds(const DevScene &sc, uint32_t *lds, uint32_t n_threads) 
     return tb;
 }
 
-// TABS: the small tables fit LDS (wf_tables_lds), else everything is read from global memory
-template <bool FIRST, bool TABS>
+// TABS: the small tables fit LDS (wf_tables_lds), else everything is read from global memory.  CYL: the scene holds cylinders
+template <bool FIRST, bool TABS, bool CYL>
 __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_shade(const WfArgs a) {
     constexpr uint32_t T = WF_SHADE_THREADS, W = T / 64;
     constexpr int NCH = WF_SHADE_CHUNKS;  // chunks of 64 hit indices a wave reads per step
@@ -720,8 +725,8 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_sha
             // PBRT_E_DEVICE instead of shading with whatever the registers held: guard word WF_GUARD_REHIT counts the cases.
             h.t = K_INF;
             h.u = h.v = 0.0f;
-            if (!prim_hit(P, o, d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(a.guard + WF_GUARD_REHIT, 1u);
-            survive = wf_shade_step<ACCEL_K_BVH_GLOBAL>(a, tb, a.depth, ka, kb, h, P, has_vn, vn, o, d, thr, L, eta, prev_pdf, sh);
+            if (!prim_hit<CYL>(P, o, d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(a.guard + WF_GUARD_REHIT, 1u);
+            survive = wf_shade_step<ACCEL_K_BVH_GLOBAL, CYL>(a, tb, a.depth, ka, kb, h, P, has_vn, vn, o, d, thr, L, eta, prev_pdf, sh);
         }
         n_seg_w += take;
         // survivors -> front of the region of the `out` state

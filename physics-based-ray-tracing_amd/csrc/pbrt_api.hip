@@ -189,7 +189,8 @@ struct pbrt_scene {
     int accel_kernel = ACCEL_K_BRUTE;
     uint32_t lds_bytes = 0;
     uint32_t bvh_depth = 0;  // levels of inner nodes of the BVH4
-    bool curved = true;      // the scene holds spheres or cones (else the BVH stream kernels run without their tests)
+    bool curved = true;      // the scene holds spheres, cones or cylinders (else the BVH stream kernels run without their tests)
+    bool cylinders = false;  // the scene holds cylinders (else the stream shading kernels run without their code)
     std::vector<void *> allocs;
     pbrt_material *d_mats = nullptr;
     uint32_t n_mats = 0;
@@ -274,6 +275,16 @@ static std::vector<pbrt_prim> find_occluders(const pbrt_scene_desc *d) {
                     acc(s - r);
                     acc(s + r);
                     acc(side(cx[0], cx[1], cx[2]));
+                } else if (Q.type == PBRT_PRIM_CYLINDER) {  // extent of both end ellipses along n
+                    double c0[3], c1[3], ca[3], cb[3];
+                    cylinder_world_frame(Q, c0, c1, ca, cb);
+                    const double an = n[0] * ca[0] + n[1] * ca[1] + n[2] * ca[2], bn = n[0] * cb[0] + n[1] * cb[1] + n[2] * cb[2];
+                    const double r = std::sqrt(an * an + bn * bn) * (1.0 + 1e-12);
+                    const double s0 = side(c0[0], c0[1], c0[2]), s1 = side(c1[0], c1[1], c1[2]);
+                    acc(s0 - r);
+                    acc(s0 + r);
+                    acc(s1 - r);
+                    acc(s1 + r);
                 } else {
                     const double v0[3] = {Q.g[0], Q.g[1], Q.g[2]}, e1[3] = {Q.g[3], Q.g[4], Q.g[5]}, e2[3] = {Q.g[6], Q.g[7], Q.g[8]};
                     acc(side(v0[0], v0[1], v0[2]));
@@ -445,11 +456,16 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
     NEED(c, d->n_light_prims == 0 || (d->light_prims && d->light_cdf));
     for (uint32_t i = 0; i < d->n_prims; ++i) {
         const pbrt_prim &p = d->prims[i];
-        if (p.type > PBRT_PRIM_CONE) return c->fail(PBRT_E_UNSUPPORTED, "primitive %u: type %u is not supported", i, p.type);
+        if (p.type > PBRT_PRIM_CYLINDER) return c->fail(PBRT_E_UNSUPPORTED, "primitive %u: type %u is not supported", i, p.type);
         if (p.type == PBRT_PRIM_CONE) {
             double cc[3], ca[3], cb[3], cx[3];
             if (!cone_world_frame(p, cc, ca, cb, cx))
                 return c->fail(PBRT_E_INVALID, "primitive %u: cone needs an invertible, finite world -> object matrix", i);
+        }
+        if (p.type == PBRT_PRIM_CYLINDER) {
+            double c0[3], c1[3], ca[3], cb[3];
+            if (!cylinder_world_frame(p, c0, c1, ca, cb))
+                return c->fail(PBRT_E_INVALID, "primitive %u: cylinder needs an invertible, finite world -> object matrix", i);
         }
         if (p.material >= d->n_materials) return c->fail(PBRT_E_INVALID, "primitive %u: material out of range", i);
         if (p.emitter >= 0 && (uint32_t)p.emitter >= d->n_emitters)
@@ -462,7 +478,8 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
                 return c->fail(PBRT_E_INVALID, "emitter %u: light primitive range out of bounds", i);
             for (uint32_t k = 0; k < e.count; ++k) {
                 uint32_t pi = d->light_prims[e.first + k];
-                if (pi >= d->n_prims || d->prims[pi].type == PBRT_PRIM_SPHERE || d->prims[pi].type == PBRT_PRIM_CONE)
+                if (pi >= d->n_prims || d->prims[pi].type == PBRT_PRIM_SPHERE || d->prims[pi].type == PBRT_PRIM_CONE ||
+                    d->prims[pi].type == PBRT_PRIM_CYLINDER)
                     return c->fail(PBRT_E_UNSUPPORTED, "emitter %u: area lights need triangle/parallelogram primitives", i);
             }
         } else if (e.type != PBRT_EMIT_POINT) {
@@ -505,7 +522,8 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
         s->ds.n_nodes = 0;
         bool small = d->n_prims <= TAB_MAX && d->n_materials <= TAB_MAX && d->n_emitters <= TAB_MAX;
         for (uint32_t i = 0; i < d->n_prims; ++i)
-            if (d->prims[i].type == PBRT_PRIM_CONE) small = false;  // only the _BIG variant carries the cone code
+            if (d->prims[i].type == PBRT_PRIM_CONE || d->prims[i].type == PBRT_PRIM_CYLINDER)
+                small = false;  // only the _BIG variant carries the cone / cylinder code
         if (d->vertex_normals) small = false;                      // ... and the shading-normal code
         if (d->vertex_normals) UP(upload(s, d->vertex_normals, (size_t)d->n_prims * 9, &s->ds.vnormals));
         s->accel_kernel = small ? ACCEL_K_BRUTE : ACCEL_K_BRUTE_BIG;
@@ -539,8 +557,10 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
         s->ds.n_nodes = (uint32_t)b4.nodes.size();
         s->bvh_depth = b4.depth;
         s->curved = false;
-        for (uint32_t i = 0; i < d->n_prims; ++i)
+        for (uint32_t i = 0; i < d->n_prims; ++i) {
             if (d->prims[i].type != PBRT_PRIM_TRIANGLE && d->prims[i].type != PBRT_PRIM_PARALLELOGRAM) s->curved = true;
+            if (d->prims[i].type == PBRT_PRIM_CYLINDER) s->cylinders = true;
+        }
         // the LDS image: 56 bytes per node (planes, device_scene.h TreeLds) + the leaf records
         const size_t lds = b4.nodes.size() * LDS_IMAGE_NODE_BYTES + (size_t)d->n_prims * sizeof(DevLeafPrim);
         // beside the image: the traversal stacks of a 1024-thread workgroup and the kernels' small static arrays (1 KiB of slack)
@@ -874,6 +894,15 @@ static uint32_t wf_trace_grid(uint32_t nr, uint32_t mult, uint32_t cus) {
 
 // The bounces of one pass.  camera: depth 0 generates its rays from the film keys (else the rays are in b.stA / b.segA).
 // Returns the number of launches through *launches.
+// k_shade with or without the cylinder code (the instance without it is the one every other scene runs)
+template <bool FIRST, bool TABS>
+static void wf_launch_shade(bool cyl, dim3 g, dim3 t, hipStream_t st, const WfArgs &a) {
+    if (cyl)
+        hipLaunchKernelGGL((k_shade<FIRST, TABS, true>), g, t, 0, st, a);
+    else
+        hipLaunchKernelGGL((k_shade<FIRST, TABS, false>), g, t, 0, st, a);
+}
+
 static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p, uint32_t nreg, bool camera, uint32_t *launches) {
     pbrt_ctx *c = s->ctx;
     const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
@@ -936,14 +965,14 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
         const dim3 g(regn[h]), t(WF_SHADE_THREADS);
         if (first) {
             if (tabs)
-                hipLaunchKernelGGL((k_shade<true, true>), g, t, 0, st, a);
+                wf_launch_shade<true, true>(s->cylinders, g, t, st, a);
             else
-                hipLaunchKernelGGL((k_shade<true, false>), g, t, 0, st, a);
+                wf_launch_shade<true, false>(s->cylinders, g, t, st, a);
         } else {
             if (tabs)
-                hipLaunchKernelGGL((k_shade<false, true>), g, t, 0, st, a);
+                wf_launch_shade<false, true>(s->cylinders, g, t, st, a);
             else
-                hipLaunchKernelGGL((k_shade<false, false>), g, t, 0, st, a);
+                wf_launch_shade<false, false>(s->cylinders, g, t, st, a);
         }
         ++*launches;
     };
@@ -1812,10 +1841,15 @@ static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p,
         w.seg_out = sout;
         w.nsh_in = have_shadows ? ni : nullptr;
         w.nsh_out = no;
-        if (tab)
-            hipLaunchKernelGGL(k_us_shade<true>, dim3(nreg), dim3(WF_SHADE_THREADS), 0, st, w);
+        const dim3 g(nreg), t(WF_SHADE_THREADS);
+        if (tab && s->cylinders)
+            hipLaunchKernelGGL((k_us_shade<true, true>), g, t, 0, st, w);
+        else if (tab)
+            hipLaunchKernelGGL((k_us_shade<true, false>), g, t, 0, st, w);
+        else if (s->cylinders)
+            hipLaunchKernelGGL((k_us_shade<false, true>), g, t, 0, st, w);
         else
-            hipLaunchKernelGGL(k_us_shade<false>, dim3(nreg), dim3(WF_SHADE_THREADS), 0, st, w);
+            hipLaunchKernelGGL((k_us_shade<false, false>), g, t, 0, st, w);
         ++*launches;
     };
     auto flip = [&]() {

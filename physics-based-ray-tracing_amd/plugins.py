@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _capi
-from .scene import (BSDFBase, ConeShape, EmitterBase, Film, IntegratorBase, MeshShape, ParamFlags,
+from .scene import (BSDFBase, ConeShape, CylinderShape, EmitterBase, Film, IntegratorBase, MeshShape, ParamFlags,
                     ReconstructionFilter, RectangleShape, Sampler, SensorBase, SphereShape, rgb3, _register)
 from .transforms import Properties, ScalarTransform4f
 
@@ -858,7 +858,7 @@ for _n, _c in (("area", AreaEmitter), ("ultraray", AreaEmitter), ("point", Point
 for _n, _c in (("perspective", PerspectiveSensor), ("ultrasound_sensor", UltraSensor), ("custom_sensor", CustomSensor)):
     _register("sensor", _n, _c)
 for _n, _c in (("obj", MeshShape), ("ply", MeshShape), ("sphere", SphereShape), ("rectangle", RectangleShape),
-               ("cone", ConeShape)):
+               ("cone", ConeShape), ("cylinder", CylinderShape)):
     _register("shape", _n, _c)
 _register("film", "hdrfilm", Film)
 _register("sampler", "independent", Sampler)

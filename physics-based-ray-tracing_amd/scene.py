@@ -258,6 +258,54 @@ class RectangleShape(Shape):
         return _tri_records(v0, v1, v2, _capi.PRIM_PARALLELOGRAM)
 
 
+def _to_frame(n):
+    """Mitsuba Transform4f::to_frame(Frame3f(n)): columns s, t, n of coordinate_system(n) (unit n)."""
+    sign = math.copysign(1.0, n[2])
+    a = -1.0 / (sign + n[2])
+    b = n[0] * n[1] * a
+    m = np.eye(4)
+    m[:3, 0] = [1.0 + sign * n[0] * n[0] * a, sign * b, -sign * n[0]]
+    m[:3, 1] = [b, sign + n[1] * n[1] * a, -n[1]]
+    m[:3, 2] = n
+    return ScalarTransform4f(m)
+
+
+class CylinderShape(Shape):
+    """'cylinder' (Mitsuba 3; the scene of the reference's first prototype, RayTracingV0.py:13-47).  [DEFINE] D16: the OPEN unit
+    tube x^2 + y^2 = 1, 0 <= z <= 1 (no caps) under object -> world = to_world @ translate(p0) @ to_frame((p1 - p0) / L) @
+    scale(radius, radius, L), L = |p1 - p0|.  One analytic PRIM_CYLINDER record carrying the world -> object matrix; its
+    orientation is the sign of the matrix's determinant (> 0: normals away from the axis, < 0: flip_normals), picked by
+    mirroring object x, under which the tube is symmetric.  Any invertible affine to_world is intersected exactly (a non-uniform
+    x / y scale gives an elliptic tube)."""
+
+    def __init__(self, props):
+        super().__init__(props)
+        p0 = np.asarray(props.get("p0", [0.0, 0.0, 0.0]), dtype=np.float64).reshape(3)
+        p1 = np.asarray(props.get("p1", [0.0, 0.0, 1.0]), dtype=np.float64).reshape(3)
+        r = float(props.get("radius", 1.0))
+        if not (math.isfinite(r) and r > 0):
+            raise ValueError(f"cylinder: radius must be finite and > 0 (got {r})")
+        if not (np.isfinite(p0).all() and np.isfinite(p1).all()):
+            raise ValueError("cylinder: p0 and p1 must be finite")
+        L = float(np.linalg.norm(p1 - p0))
+        if not L > 0:
+            raise ValueError("cylinder: p0 and p1 must differ")
+        M = self.to_world.matrix
+        if not (np.isfinite(M).all() and abs(np.linalg.det(M[:3, :3])) >= 1e-300):
+            raise ValueError("cylinder: to_world must be finite and invertible")
+        self.object_to_world = self.to_world @ ScalarTransform4f().translate(p0) @ _to_frame((p1 - p0) / L) @ \
+            ScalarTransform4f().scale([r, r, L])
+
+    def primitives(self):
+        W = np.linalg.inv(self.object_to_world.matrix)[:3, :4]
+        if (np.linalg.det(W[:, :3]) < 0) != self.flip_normals:
+            W[0] = -W[0]   # mirror object x: the same tube, the other orientation
+        rec = np.zeros(1, dtype=_capi.PRIM_DTYPE)
+        rec["g"][0] = W.reshape(12)
+        rec["type"] = _capi.PRIM_CYLINDER
+        return rec
+
+
 class ConeShape(Shape):
     """'cone' (MitsubaScenes/Cone_Box.xml:36-47, Cone_FLoating.xml) has no Mitsuba-3 definition.
     [DEFINE]: the closed unit cone -- apex (0, 0, 1), base disc of radius 1
@@ -480,8 +528,8 @@ class Scene(Object):
             if em is None:
                 continue
             rec = prim_blocks[si]
-            if np.any((rec["type"] == _capi.PRIM_SPHERE) | (rec["type"] == _capi.PRIM_CONE)):
-                raise NotImplementedError("area emitters on spheres / analytic cones are not supported")
+            if np.any((rec["type"] == _capi.PRIM_SPHERE) | (rec["type"] == _capi.PRIM_CONE) | (rec["type"] == _capi.PRIM_CYLINDER)):
+                raise NotImplementedError("area emitters on spheres / analytic cones / cylinders are not supported")
             e1 = rec["g"][:, 3:6].astype(np.float64)
             e2 = rec["g"][:, 6:9].astype(np.float64)
             area = np.linalg.norm(np.cross(e1, e2), axis=1)
@@ -595,6 +643,16 @@ class Scene(Object):
             nw = nw / np.maximum(np.linalg.norm(nw, axis=1, keepdims=True), 1e-300)
             p = np.where(cone[:, None], pc, p)
             nrm = np.where(cone[:, None], nw, nrm)
+        cyl = (typ == _capi.PRIM_CYLINDER) & valid
+        if np.any(cyl):    # same formulas as cylinder_normal: p = o + t d, n = +-M^T (x_o, y_o, 0), the sign of det(M)
+            M = g.reshape(-1, 3, 4).astype(np.float64)
+            pc = o + np.where(cyl, t, 0.0)[:, None] * d
+            q = np.einsum("nij,nj->ni", M[:, :, :3], pc) + M[:, :, 3]
+            nw = np.einsum("nji,nj->ni", M[:, :2, :3], q[:, :2])
+            nw = nw / np.maximum(np.linalg.norm(nw, axis=1, keepdims=True), 1e-300)
+            nw = nw * np.where(np.linalg.det(M[:, :, :3]) < 0, -1.0, 1.0)[:, None]
+            p = np.where(cyl[:, None], pc, p)
+            nrm = np.where(cyl[:, None], nw, nrm)
         p[~valid] = 0
         nrm[~valid] = 0
         return dict(p=p.astype(np.float32), n=nrm.astype(np.float32), shape=np.where(valid, P["shape"][idx], -1))
