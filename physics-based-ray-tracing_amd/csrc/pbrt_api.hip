@@ -903,6 +903,17 @@ static void wf_launch_shade(bool cyl, dim3 g, dim3 t, hipStream_t st, const WfAr
         hipLaunchKernelGGL((k_shade<FIRST, TABS, false>), g, t, 0, st, a);
 }
 
+// Unbounded depth (Mitsuba max_depth = -1): the live paths of a pass, summed over its n counters (one per region or wave of it)
+// once the stream has drained.  The caller decides when to poll and what a total of 0 ends.
+static int live_paths(pbrt_ctx *c, const uint32_t *d_counts, uint32_t n, uint64_t *live) {
+    std::vector<uint32_t> cnt(n);
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), d_counts, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *live = 0;
+    for (uint32_t v : cnt) *live += v;
+    return PBRT_OK;
+}
+
 static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p, uint32_t nreg, bool camera, uint32_t *launches) {
     pbrt_ctx *c = s->ctx;
     const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
@@ -1005,11 +1016,8 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
         HIPCHK(c, hipGetLastError());
         // unbounded depth (Mitsuba max_depth = -1): poll the live count every 8 bounces (never split: one stream)
         if (a.max_depth > 32 && (depth & 7u) == 7u) {
-            std::vector<uint32_t> cnt(nreg);
-            HIPCHK(c, hipMemcpyAsync(cnt.data(), sin, (size_t)nreg * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            uint64_t live = 0;
-            for (uint32_t v : cnt) live += v;
+            uint64_t live;
+            if (int rc = live_paths(c, sin, nreg, &live)) return rc;
             if (live == 0) {
                 flush = depth + 1 < a.max_depth;  // the last bounce may have left shadow rays behind
                 a.depth = depth + 1;
@@ -1113,6 +1121,170 @@ static uint64_t wavefront_model_bytes(const unsigned long long *live, const unsi
     return tr + sh;
 }
 
+// ---- pass handling of the radiance and ultrasound drivers ---------------------------------------------------------------------
+// ONE event pair per pass around its bounce launches (a pair per launch costs ~8 us of queue bubbles each): pair i is
+// ev_pool[2 i], ev_pool[2 i + 1].  While an acquisition is recorded (timed = false) the events are taken but not recorded: event
+// pairs recorded into a graph cannot be read back.  (Internal linkage: the library exports the ABI of include/pbrt_hip.h.)
+namespace {
+struct PassTimer {
+    pbrt_ctx *c;
+    bool timed = true;
+    size_t n_ev = 0;  // events taken so far (call_stats reads the pairs; us_finish through PendingAcq::n_ev)
+    hipEvent_t e1 = nullptr;
+    int begin() {
+        e1 = c->event(n_ev + 1);
+        hipEvent_t e0 = c->event(n_ev);
+        if (!e0 || !e1) return c->fail(PBRT_E_DEVICE, "hipEventCreate failed");
+        n_ev += 2;
+        if (timed) HIPCHK(c, hipEventRecord(e0, c->stream));
+        return PBRT_OK;
+    }
+    int end() {
+        if (timed) HIPCHK(c, hipEventRecord(e1, c->stream));
+        return PBRT_OK;
+    }
+};
+}  // namespace
+// The pbrt_stats members both drivers fill alike, from the reduced rows (segments, shadow rays, live paths per depth) and the events
+// of the call (timed: kernel_ms = c->ev0 .. c->ev1, bounce_ms = the pass pairs among the first n_ev events of the pool, added up;
+// else 0 ms).  The driver adds what is its own to c->stats.
+static int call_stats(pbrt_ctx *c, const unsigned long long *hstats, uint64_t samples, uint32_t launches, uint32_t passes, bool timed,
+                      size_t n_ev) {
+    float ms = 0.0f;
+    double bounce_ms = 0.0;
+    if (timed) {
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        for (size_t i = 0; i + 1 < n_ev; i += 2) {
+            float t = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&t, c->ev_pool[i], c->ev_pool[i + 1]));
+            bounce_ms += t;
+        }
+    }
+    pbrt_stats &S = c->stats;
+    S = pbrt_stats{};
+    S.samples = samples;
+    S.segments = hstats[0];
+    S.shadow_rays = hstats[1];
+    S.kernel_ms = ms;
+    S.bounce_ms = bounce_ms;
+    S.bounce_launches = launches;
+    S.passes = passes;
+    for (int d = 0; d < 16; ++d) S.live[d] = hstats[2 + d];
+    S.workspace_bytes = c->ws_total();
+    return PBRT_OK;
+}
+
+// Sizing a pass: `per_call` units (samples of a film region of `unit` pixels, paths per ray of `unit` rays) in passes of at most
+// pass_paths paths, rounded up to whole regions.  The free-memory figure behind a default pass_paths is a snapshot (torch or another
+// process may allocate between the query and the hipMalloc): alloc(cap, nseg) returns PBRT_E_NOMEM when the pass buffers do not fit,
+// and then they go back, the pass is halved and tried again -- the result does not depend on the pass size (global path keys).  A
+// caller-fixed pass size (fixed) gives up at once.  What did fit goes back too when even the smallest pass does not (the caller may be
+// about to give the memory to someone else); the message of the failed request stands.  Any other code from alloc is returned as is.
+// equal: passes of equal size instead of full ones plus a small remainder.
+static const uint64_t PASS_MIN_PATHS = 1u << 20;
+struct PassShape {
+    uint32_t per_pass = 1, cap = 0, nseg = 0;
+};
+template <typename Alloc>
+static int size_pass(pbrt_ctx *c, uint64_t pass_paths, bool fixed, uint32_t per_call, uint64_t unit, uint32_t region, bool equal,
+                     Alloc alloc, PassShape *ps) {
+    for (;;) {
+        uint32_t k = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(per_call, pass_paths / std::max<uint64_t>(unit, 1)));
+        if (equal) k = div_up(per_call, div_up(per_call, k));
+        NEED(c, unit * k < 0xfffffc00ull);
+        ps->per_pass = k;
+        ps->cap = div_up(unit * k, region) * region;
+        ps->nseg = ps->cap / region;  // regions (one workgroup each)
+        const int rc = alloc(ps->cap, ps->nseg);
+        if (rc != PBRT_E_NOMEM) return rc;
+        release_pass_buffers(c);
+        if (fixed || k <= 1 || pass_paths <= PASS_MIN_PATHS) return PBRT_E_NOMEM;
+        pass_paths = std::max<uint64_t>(PASS_MIN_PATHS, std::min<uint64_t>(pass_paths, unit * k) / 2);
+    }
+}
+// Default paths in flight per pass: the trace / shade streams size it from the free device memory (wf_default_pass_paths); the fused
+// kernels take `paths`, halved under a workspace limit until bytes_per_path of each fit it (the small buffers: 64 MB)
+static uint64_t default_pass_paths(pbrt_ctx *c, bool streams, uint64_t paths, uint32_t bytes_per_path) {
+    if (streams) return wf_default_pass_paths(c, PASS_MIN_PATHS);
+    if (c->ws_limit)
+        while (paths > PASS_MIN_PATHS && (double)paths * (double)bytes_per_path > (double)c->ws_limit - 64e6) paths /= 2;
+    return paths;
+}
+
+// self-check of a fast divisor (device_math.h make_fastdiv) against `/` at the probe values of its caller
+static bool fastdiv_exact(const FastDiv &fd, uint32_t d, std::initializer_list<uint32_t> probes) {
+    for (uint32_t n : probes)
+        if (udiv_fast_host(n, fd) != n / d) return false;
+    return true;
+}
+
+// ---- radiance passes ----------------------------------------------------------------------------------------------------------
+// The members WfArgs shares with RadArgs (scene, camera, radiance records, statistics rows, paths, depth, seed, path keys): the
+// radiance drivers fill a RadArgs, and the trace / shade streams of BVH scenes take these from it.
+static WfArgs wf_args(const RadArgs &a) {
+    WfArgs w{};
+    w.sc = a.sc;
+    w.cam = a.cam;
+    w.Lhome = a.Lhome;
+    w.stats = a.stats;
+    w.stat_stride = a.stat_stride;
+    w.cap = a.cap;
+    w.n_paths = a.n_paths;
+    w.max_depth = a.max_depth;
+    w.rr_depth = a.rr_depth;
+    w.seed = a.seed;
+    w.key_mode = a.key_mode;
+    w.rx0 = a.rx0;
+    w.ry0 = a.ry0;
+    w.rw = a.rw;
+    w.npix_r = a.npix_r;
+    w.s_first = a.s_first;
+    w.film_w = a.film_w;
+    w.film_h = a.film_h;
+    w.tile_rows = a.tile_rows;
+    w.div_npix = a.div_npix;
+    w.div_rw = a.div_rw;
+    w.index_offset = a.index_offset;
+    w.sample_index = a.sample_index;
+    return w;
+}
+// Film accumulation of one pass (k_film_accum, or the tiled gather of the tent and Gaussian filters)
+static void film_accum(pbrt_ctx *c, const FilmArgs &fa) {
+    hipStream_t st = c->stream;
+    if (fa.filter == PBRT_FILTER_BOX) {
+        hipLaunchKernelGGL(k_film_accum, dim3(div_up((uint64_t)fa.cw * fa.ch, 256)), dim3(256), 0, st, fa);
+        return;
+    }
+    // small crops: 4 x as many (single-wave) workgroups; same sums, pixel by pixel
+    const bool big = (uint64_t)div_up(fa.cw, 16) * div_up(fa.ch, 16) >= 4ull * (uint64_t)c->n_cu;
+    const bool tent = fa.filter == PBRT_FILTER_TENT;
+    const dim3 g16(div_up(fa.cw, 16), div_up(fa.ch, 16)), g8(div_up(fa.cw, 8), div_up(fa.ch, 8));
+    if (big && tent)
+        hipLaunchKernelGGL((k_film_accum_tiled<16, PBRT_FILTER_TENT>), g16, dim3(16, 16), 0, st, fa);
+    else if (big)
+        hipLaunchKernelGGL((k_film_accum_tiled<16, PBRT_FILTER_GAUSSIAN>), g16, dim3(16, 16), 0, st, fa);
+    else if (tent)
+        hipLaunchKernelGGL((k_film_accum_tiled<8, PBRT_FILTER_TENT>), g8, dim3(8, 8), 0, st, fa);
+    else
+        hipLaunchKernelGGL((k_film_accum_tiled<8, PBRT_FILTER_GAUSSIAN>), g8, dim3(8, 8), 0, st, fa);
+}
+
+// The fuse plan learnt from the probe pass of a render: its statistics rows reduced and read back (one synchronisation, ~30 us); the
+// reduction target is cleared again, the final reduction adds every row once more
+static int probe_plan(pbrt_ctx *c, unsigned long long *segstats, uint32_t n_rows, uint32_t stat_rows, unsigned long long *dstats,
+                      uint32_t max_depth, uint32_t *plan) {
+    hipStream_t st = c->stream;
+    unsigned long long hp[2 + MAX_DEPTH_STATS];
+    hipLaunchKernelGGL(k_reduce_stats, dim3(stat_rows, REDUCE_SLICES), dim3(256), 0, st, segstats, n_rows, (size_t)n_rows, dstats);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hp, dstats, (size_t)stat_rows * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipMemsetAsync(dstats, 0, (2 + 2 * MAX_DEPTH_STATS) * 8, st));
+    for (uint32_t d = stat_rows; d < 2 + MAX_DEPTH_STATS; ++d) hp[d] = 0;
+    *plan = plan_from_survival(hp + 2, std::min<uint32_t>(max_depth, MAX_DEPTH_STATS));
+    return PBRT_OK;
+}
+
 static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_desc *f, void *d_out) {
     pbrt_ctx *c = s->ctx;
     if (int rcs = ctx_settle(c)) return rcs;
@@ -1123,13 +1295,16 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     NEED(c, f->spp > 0 && f->max_depth > 0 && f->filter <= PBRT_FILTER_GAUSSIAN);
     NEED(c, (uint64_t)W * H <= 0xffffffffull);
     HIPCHK(c, hipSetDevice(c->device));
+    // Brute-force scenes, or BVH scenes: these run intersection and shading as separate streams (kernels_wavefront.h);
+    // PBRT_FILM_NO_HIT_POOL keeps the fused k_bounce (one launch per bounce, shading in the lanes the traversal leaves) as the A/B
+    // reference
+    const bool brute = s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG;
+    const bool wavefront = !brute && !(f->flags & PBRT_FILM_NO_HIT_POOL);
 #ifndef PBRT_DIAG
-    {   // launch structures that lost their A/B live in the diagnostic build only (make -C csrc diag -> libpbrt_hip_diag.so)
-        const bool bvh = s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS;
-        if ((f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || (bvh && (f->flags & PBRT_FILM_NO_HIT_POOL)))
-            return c->fail(PBRT_E_UNSUPPORTED, "PBRT_FILM_REGEN / PBRT_FILM_WALK_FROM / PBRT_FILM_NO_HIT_POOL select diagnostic launch "
-                                               "structures: build libpbrt_hip_diag.so (make -C csrc diag)");
-    }
+    // launch structures that lost their A/B live in the diagnostic build only (make -C csrc diag -> libpbrt_hip_diag.so)
+    if ((f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || (!brute && (f->flags & PBRT_FILM_NO_HIT_POOL)))
+        return c->fail(PBRT_E_UNSUPPORTED, "PBRT_FILM_REGEN / PBRT_FILM_WALK_FROM / PBRT_FILM_NO_HIT_POOL select diagnostic launch "
+                                           "structures: build libpbrt_hip_diag.so (make -C csrc diag)");
 #endif
     int rc = set_lds_attr(s);
     if (rc) return rc;
@@ -1142,58 +1317,35 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     // default paths in flight per pass, measured on cbox 512^2 x 256 (one box): 2 / 4 / 8 / 16 / 32 / 64 Mi -> 9.55 / 8.56 / 8.14 / 7.92 /
     // 8.13 / 8.20 ms (fewer launch tails against cache residency of the ping-pong state)
     // round 2, fused first launch: 2 / 4 / 8 / 16 / 32 / 64 Mi -> 9.09 / 8.07 / 7.65 / 7.37 / 7.31 / 7.39 ms; BVH scenes keep 16 Mi
-    const bool brute_scene = s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG;
     // round 2, chains of up to six bounces per launch (one launch per pass on the Cornell box): 2 / 4 / 8 / 16 / 32 / 64 Mi -> 7.85 / 7.01 /
     // 6.72 / 6.56 / 6.49 / 6.43 ms
     // round 3, BVH scenes as trace / shade streams (twelve launches per pass: their tails and the thinly filled late bounces weigh
     // less in larger passes): ring 1024^2 x 64: 1 / 2 / 4 / 8 / 16 / 32 / 64 Mi -> 50.8 / 37.6 / 25.5 / 22.2 / 19.6 / 18.0 / 17.3 ms;
     // 64 Mi paths = 23 GB of workspace (356 B per path in flight then, 340 B since round 4); the fused BVH kernels (PBRT_FILM_NO_HIT_POOL) keep 16 Mi
-    const bool wf_scene = !brute_scene && !(f->flags & PBRT_FILM_NO_HIT_POOL);
     // and beyond: 1024^2 x 512: 64 / 128 / 256 Mi -> 144 / 134 / 115 ms.  Default for BVH scenes: the largest power of two whose
     // workspace (WF_BYTES_PER_PATH = 340 B per path in flight, allocated as asked) fits two thirds of the free device memory and
     // the context's workspace limit, 1 .. 512 Mi (round 4, 1024^2 x 512: 128 / 256 / 512 Mi -> 105.9 / 99.5 / 94.6 ms; 512 Mi paths =
     // 183 GB of the 288 GB of an MI355X -- a renderer that owns the device takes it; one that shares it sets a limit, see
-    // pbrt_ctx_set_workspace_limit, and pbrt_ctx_trim hands the memory back).  The free-memory figure is a snapshot
-    // (another process may allocate between the query and the hipMalloc), so a failed allocation halves the pass and tries again.
+    // pbrt_ctx_set_workspace_limit, and pbrt_ctx_trim hands the memory back).  A failed allocation halves the pass (size_pass).
+    // Brute-force scenes under a workspace limit: 16 B of radiance record per path, and the ping-pong state (2 x 60 B) if the
+    // launch plan turns out to need it.
     // (pbrt_ctx::call_seq was bumped by the entry point, before its first workspace request.)
-    const uint64_t WF_MIN_PASS = 1u << 20;
-    uint64_t pass_paths = f->pass_paths ? f->pass_paths : (brute_scene ? (64u << 20) : (16u << 20));
-    if (!f->pass_paths && wf_scene) {
-        pass_paths = wf_default_pass_paths(c, WF_MIN_PASS);
-    } else if (!f->pass_paths && c->ws_limit) {
-        // brute-force scenes under a workspace limit: 16 B of radiance record per path, and the ping-pong state (2 x 60 B) if the
-        // launch plan turns out to need it
-        const double budget = (double)c->ws_limit - 64e6;
-        while (pass_paths > WF_MIN_PASS && (double)pass_paths * (16 + 2 * N_STATE * 4) > budget) pass_paths /= 2;
-    }
-    // BVH scenes: intersection and shading as separate streams (kernels_wavefront.h); PBRT_FILM_NO_HIT_POOL keeps the fused
-    // k_bounce (one launch per bounce, shading in the lanes the traversal leaves) as the A/B reference
-    const bool bvh_scene = s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS;
-    const bool wavefront = bvh_scene && !(f->flags & PBRT_FILM_NO_HIT_POOL);
+    const uint64_t pass_paths = f->pass_paths ? f->pass_paths
+                                              : default_pass_paths(c, wavefront, brute ? (64u << 20) : (16u << 20), 16 + 2 * N_STATE * 4);
     static_assert(WF_REGION == REGION_SEGS_BVH * SEG_BVH, "both BVH launch structures cut a pass into the same regions");
     const uint32_t REGION = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
-    uint32_t s_pass = 1, cap = 0, nseg = 0;
     WfBufs wfb{};
-    WfPlan wfp;
     float *Lhome = nullptr;
-    for (;;) {
-        s_pass = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(f->spp, pass_paths / std::max<uint64_t>(npix_r, 1)));
-        s_pass = div_up(f->spp, div_up(f->spp, s_pass));  // equal passes instead of full ones plus a small remainder
-        NEED(c, npix_r * s_pass < 0xfffffc00ull);
-        cap = div_up(npix_r * s_pass, REGION) * REGION;
-        nseg = cap / REGION;  // regions (one workgroup each)
-        NEED(c, wf_scene || (uint64_t)cap * N_STATE * 4 < 0xffffffffull);  // the tiled state arrays are addressed through 32-bit buffer offsets
+    auto alloc_pass = [&](uint32_t cap, uint32_t nseg) -> int {
+        NEED(c, wavefront || (uint64_t)cap * N_STATE * 4 < 0xffffffffull);  // the tiled state arrays are addressed through 32-bit buffer offsets
         if (wavefront) NEED(c, cap < WF_DEAD);  // ray records are addressed with two flag bits on top
         Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
-        if (Lhome && (!wavefront || wf_alloc(c, cap, nseg, &wfb))) break;
-        // out of memory (or over the context's limit): give the pass buffers back and try with half the paths in flight
-        if (f->pass_paths || s_pass <= 1 || pass_paths <= WF_MIN_PASS) {
-            release_pass_buffers(c);  // what did fit goes back too: the caller may be about to give the memory to someone else
-            return PBRT_E_NOMEM;
-        }
-        release_pass_buffers(c);
-        pass_paths = std::max<uint64_t>(WF_MIN_PASS, std::min<uint64_t>(pass_paths, npix_r * s_pass) / 2);
-    }
+        return Lhome && (!wavefront || wf_alloc(c, cap, nseg, &wfb)) ? PBRT_OK : PBRT_E_NOMEM;
+    };
+    PassShape ps;
+    if ((rc = size_pass(c, pass_paths, f->pass_paths != 0, f->spp, npix_r, REGION, true, alloc_pass, &ps)) != 0) return rc;
+    const uint32_t s_pass = ps.per_pass, cap = ps.cap, nseg = ps.nseg;
+    WfPlan wfp;
     if (wavefront) {
         wfp = wf_plan(s);
         if ((rc = wf_set_attr(s, wfp)) != 0) return rc;
@@ -1204,7 +1356,7 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     float *stA = wavefront ? (float *)wfb.stA : nullptr;
     float *stB = wavefront ? (float *)wfb.stB : nullptr;
     // fused BVH kernels: the live paths are made dense again before every bounce of depth >= 2 (k_scan_owners / k_repack_copy)
-    const bool repack = bvh_scene && !wavefront && rad_wave_private(s->accel_kernel) && !(f->flags & PBRT_FILM_NO_REPACK);
+    const bool repack = !brute && !wavefront && rad_wave_private(s->accel_kernel) && !(f->flags & PBRT_FILM_NO_REPACK);
     float *stC = repack ? (float *)c->buf("stateC", (size_t)cap * N_STATE * 4) : nullptr;
     // live counters and statistics rows: one per region, or one per wave of it (BVH kernels: wave-private compaction)
     const uint32_t n_own = nseg * rad_owners_per_region(s->accel_kernel);
@@ -1222,9 +1374,8 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     unsigned long long *segstats = (unsigned long long *)c->buf("segstats", (size_t)(2 + 2 * MAX_DEPTH_STATS) * n_rows * 8);
     if (!segstats) return PBRT_E_NOMEM;
     if (!Lhome || !segA || !segB || !acc || !dstats) return PBRT_E_NOMEM;
-    // k_bounce_pool launches also count the rays of every depth that hit something (rows HIT_ROW0 + d, for the byte model)
-    const bool hit_pool = wavefront;  // k_shade counts the rays of every depth that hit something (rows HIT_ROW0 + d, for the byte model)
-    const uint32_t hit_rows = hit_pool ? stat_rows - 2 : 0;
+    // k_shade counts the rays of every depth that hit something (rows HIT_ROW0 + d, for the byte model)
+    const uint32_t hit_rows = wavefront ? stat_rows - 2 : 0;
     if (repack && (!stC || !segC || !offs || !quota)) return PBRT_E_NOMEM;
     hipStream_t st = c->stream;
     HIPCHK(c, hipMemsetAsync(acc, 0, film_px * 16, st));
@@ -1232,59 +1383,77 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     HIPCHK(c, hipMemsetAsync(segstats, 0, segstats_bytes, st));
     if (hit_rows) HIPCHK(c, hipMemsetAsync(segstats + (size_t)HIT_ROW0 * n_rows, 0, (size_t)hit_rows * n_rows * 8, st));
     HIPCHK(c, hipEventRecord(c->ev0, st));
-    size_t n_ev = 0;
-    hipEvent_t pass_e1 = nullptr;
+    PassTimer timer{c};
     uint32_t passes = 0, launches = 0;
     // the fuse plan of this call: the caller's, or the one learnt from the last render of this scene, or the library default
-    const bool brute_scene_k = s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG;
-    const bool plan_was_learnt = brute_scene_k && s->plan_hint_valid;
-    uint32_t call_plan = !brute_scene_k ? 0u
-                         : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? ((f->flags >> 8) & 0xffu)
-                         : (s->plan_hint_valid ? s->plan_hint : PBRT_DEFAULT_FUSE_PLAN);
+    const bool plan_was_learnt = brute && s->plan_hint_valid;
+    uint32_t plan = !brute ? 0u
+                    : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? ((f->flags >> 8) & 0xffu)
+                    : (s->plan_hint_valid ? s->plan_hint : PBRT_DEFAULT_FUSE_PLAN);
     // First render of a brute-force scene with the plan left to the library: the first PROBE_SPP samples are a pass of their own,
-    // their path survival is read back (one synchronisation, ~30 us) and decides the plan of all the other passes.  The film does
-    // not depend on how the samples are split into passes, nor on the plan.
+    // their path survival is read back (probe_plan) and decides the plan of all the other passes.  The film does not depend on how
+    // the samples are split into passes, nor on the plan.
     constexpr uint32_t PROBE_SPP = 2;
-    const bool probe = brute_scene_k && !s->plan_hint_valid && f->spp >= 8 * PROBE_SPP && s_pass >= PROBE_SPP &&
+    const bool probe = brute && !s->plan_hint_valid && f->spp >= 8 * PROBE_SPP && s_pass >= PROBE_SPP &&
                        !(f->flags & (PBRT_FILM_FUSE_PLAN_SET | PBRT_FILM_WALK_SET | PBRT_FILM_REGEN));
+    const uint32_t walk_from = (f->flags & PBRT_FILM_WALK_SET) ? ((f->flags >> 17) & 0xffu) : PBRT_DEFAULT_WALK_FROM;
+    // the arguments of every pass (key_mode 0: home -> (pixel of the rendered region, sample s_first + home / npix_r))
+    RadArgs base{};
+    base.sc = s->ds;
+    if ((f->flags & PBRT_FILM_NO_OCCLUDER_PRUNING) && base.sc.occ_prims) {  // diagnostic: shadow segments walk every primitive
+        base.sc.occ_prims = base.sc.prims;
+        base.sc.n_occ = base.sc.n_prims;
+    }
+    base.cam = *cam;
+    base.Lhome = Lhome;
+    base.stats = segstats;
+    base.stat_stride = n_rows;
+    base.cap = cap;
+    base.state_cap = cap;
+    base.max_depth = f->max_depth;
+    base.rr_depth = f->rr_depth;
+    base.seed = f->seed;
+    base.key_mode = 0;
+    base.rx0 = rx0;
+    base.ry0 = ry0;
+    base.rw = rw;
+    base.npix_r = (uint32_t)npix_r;
+    base.tile_rows = rh & ~7u;
+    base.div_npix = make_fastdiv(base.npix_r);
+    base.div_rw = make_fastdiv(rw);
+    const std::initializer_list<uint32_t> probes = {0u, 1u, rw - 1, rw, rw + 1, base.npix_r - 1, base.npix_r, base.npix_r + 1, cap - 1, cap, 0xffffffffu};
+    NEED(c, fastdiv_exact(base.div_npix, base.npix_r, probes) && fastdiv_exact(base.div_rw, rw, probes));
+    base.film_w = W;
+    base.film_h = H;
+    base.lds_bytes = s->lds_bytes;
+    FilmArgs fa{};
+    fa.Lhome = Lhome;
+    fa.acc = acc;
+    fa.cap = cap;
+    fa.cx0 = f->crop_x;
+    fa.cy0 = f->crop_y;
+    fa.cw = f->crop_w;
+    fa.ch = f->crop_h;
+    fa.rx0 = rx0;
+    fa.ry0 = ry0;
+    fa.rw = rw;
+    fa.rh = rh;
+    fa.npix_r = (uint32_t)npix_r;
+    fa.tile_rows = base.tile_rows;
+    fa.film_w = W;
+    fa.film_h = H;
+    fa.filter = f->filter;
+    fa.seed = f->seed;
     uint32_t s_step = s_pass;  // samples of a regular pass
     for (uint32_t s0 = 0; s0 < f->spp; ++passes) {
         const uint32_t sc = (probe && passes == 0) ? PROBE_SPP : std::min(s_step, f->spp - s0);
-        RadArgs a{};
-        a.sc = s->ds;
-        if ((f->flags & PBRT_FILM_NO_OCCLUDER_PRUNING) && a.sc.occ_prims) {  // diagnostic: shadow segments walk every primitive
-            a.sc.occ_prims = a.sc.prims;
-            a.sc.n_occ = a.sc.n_prims;
-        }
-        a.cam = *cam;
-        a.Lhome = Lhome;
-        a.stats = segstats;
-        a.stat_stride = n_rows;
-        a.cap = cap;
-        a.state_cap = cap;
+        RadArgs a = base;
         a.n_paths = (uint32_t)(npix_r * sc);
-        a.max_depth = f->max_depth;
-        a.rr_depth = f->rr_depth;
-        a.seed = f->seed;
-        a.key_mode = 0;
-        a.rx0 = rx0;
-        a.ry0 = ry0;
-        a.rw = rw;
-        a.npix_r = (uint32_t)npix_r;
-        a.tile_rows = rh & ~7u;
-        a.div_npix = make_fastdiv(a.npix_r);
-        a.div_rw = make_fastdiv(rw);
-        for (uint32_t n : {0u, 1u, rw - 1, rw, rw + 1, a.npix_r - 1, a.npix_r, a.npix_r + 1, cap - 1, cap, 0xffffffffu}) {
-            NEED(c, udiv_fast_host(n, a.div_npix) == n / a.npix_r && udiv_fast_host(n, a.div_rw) == n / rw);
-        }
         a.s_first = f->sample_offset + s0;
-        a.film_w = W;
-        a.film_h = H;
-        a.lds_bytes = s->lds_bytes;
         const uint32_t nseg_pass = div_up(a.n_paths, REGION);
         if (!wavefront) {  // state for this pass: none if one launch walks all its bounces
-            const bool one_launch = brute_scene_k && !(f->flags & (PBRT_FILM_WALK_SET | PBRT_FILM_REGEN)) &&
-                                    chain_len(call_plan, 0, f->max_depth) >= f->max_depth;
+            const bool one_launch = brute && !(f->flags & (PBRT_FILM_WALK_SET | PBRT_FILM_REGEN)) &&
+                                    chain_len(plan, 0, f->max_depth) >= f->max_depth;
             const size_t need = one_launch ? (size_t)REGION : (size_t)nseg_pass * REGION;
             stA = (float *)c->buf("stateA", need * N_STATE * 4);
             stB = (float *)c->buf("stateB", need * N_STATE * 4);
@@ -1293,38 +1462,9 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
         }
         float *in = stA, *out = stB;
         uint32_t *sin = segA, *sout = segB;
-        const bool brute = s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG;
-        const uint32_t fuse_plan = call_plan;
-        const uint32_t walk_from = (f->flags & PBRT_FILM_WALK_SET) ? ((f->flags >> 17) & 0xffu) : PBRT_DEFAULT_WALK_FROM;
         if (wavefront) {
-            WfArgs w{};
-            w.sc = a.sc;
-            w.cam = a.cam;
-            w.Lhome = Lhome;
-            w.stats = segstats;
-            w.stat_stride = n_rows;
-            w.cap = cap;
-            w.n_paths = a.n_paths;
-            w.max_depth = a.max_depth;
-            w.rr_depth = a.rr_depth;
-            w.seed = a.seed;
-            w.key_mode = 0;
-            w.rx0 = a.rx0;
-            w.ry0 = a.ry0;
-            w.rw = a.rw;
-            w.npix_r = a.npix_r;
-            w.s_first = a.s_first;
-            w.film_w = a.film_w;
-            w.film_h = a.film_h;
-            w.tile_rows = a.tile_rows;
-            w.div_npix = a.div_npix;
-            w.div_rw = a.div_rw;
-            pass_e1 = c->event(n_ev + 1);
-            hipEvent_t e0 = c->event(n_ev);
-            if (!e0 || !pass_e1) return c->fail(PBRT_E_DEVICE, "hipEventCreate failed");
-            n_ev += 2;
-            HIPCHK(c, hipEventRecord(e0, st));
-            if ((rc = wf_bounces(s, w, wfb, wfp, nseg_pass, true, &launches)) != 0) return rc;
+            if ((rc = timer.begin()) != 0) return rc;
+            if ((rc = wf_bounces(s, wf_args(a), wfb, wfp, nseg_pass, true, &launches)) != 0) return rc;
         }
 #ifdef PBRT_DIAG
         else if (brute && (f->flags & PBRT_FILM_REGEN)) {
@@ -1338,11 +1478,7 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
             grid = std::min(grid, std::max(1u, n_rows / wpw));            // one statistics row per wave
             grid = std::min(grid, div_up(a.n_paths, REGEN_WG));
             a.depth = 0;
-            pass_e1 = c->event(n_ev + 1);
-            hipEvent_t e0 = c->event(n_ev);
-            if (!e0 || !pass_e1) return c->fail(PBRT_E_DEVICE, "hipEventCreate failed");
-            n_ev += 2;
-            HIPCHK(c, hipEventRecord(e0, st));
+            if ((rc = timer.begin()) != 0) return rc;
             if (s->accel_kernel == ACCEL_K_BRUTE)
                 hipLaunchKernelGGL(k_regen<ACCEL_K_BRUTE>, dim3(grid), dim3(REGEN_WG), 0, st, a);
             else
@@ -1355,7 +1491,7 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
         for (uint32_t depth = 0; depth < f->max_depth;) {
             // bounces this launch walks: 2 at the depths of the fuse plan (brute-force kernels; the last bounce of a
             // path only looks for emitters, so it is never worth a launch slot of its own either)
-            const uint32_t nb = brute ? chain_len(fuse_plan, depth, f->max_depth) : 1u;
+            const uint32_t nb = brute ? chain_len(plan, depth, f->max_depth) : 1u;
             a.depth = depth;
             a.nb = nb;
             a.in = in;
@@ -1376,17 +1512,10 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
                 a.seg_in = segC;
             }
 #endif
-            // ONE event pair per pass around its bounce launches (a pair per launch costs ~8 us of queue bubbles each)
-            if (depth == 0) {
-                pass_e1 = c->event(n_ev + 1);
-                hipEvent_t e0 = c->event(n_ev);
-                if (!e0 || !pass_e1) return c->fail(PBRT_E_DEVICE, "hipEventCreate failed");
-                n_ev += 2;
-                HIPCHK(c, hipEventRecord(e0, st));
-            }
+            if (depth == 0 && (rc = timer.begin()) != 0) return rc;
             const bool walk = brute && depth >= walk_from;  // this launch walks every remaining bounce of the pass
 #ifdef PBRT_DIAG
-            const uint32_t pair_m = (brute && depth == 0 && !walk) ? pair_merge_bounce(fuse_plan, f->max_depth) : 0u;
+            const uint32_t pair_m = (brute && depth == 0 && !walk) ? pair_merge_bounce(plan, f->max_depth) : 0u;
             if (pair_m) {  // the whole path in one launch, two tiles per wave
                 a.merge_at = pair_m;
                 const uint32_t g2 = div_up(a.n_paths, 2u * SEG_BRUTE);
@@ -1411,62 +1540,19 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
             depth += nb;
             // unbounded depth (Mitsuba max_depth = -1): poll the live count every 8 bounces
             if (f->max_depth > 32 && (depth >> 3) != (depth_before >> 3)) {
-                std::vector<uint32_t> cnt(n_own);
-                HIPCHK(c, hipMemcpyAsync(cnt.data(), sin, (size_t)n_own * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(c, hipStreamSynchronize(st));
-                uint64_t live = 0;
-                for (uint32_t v : cnt) live += v;
+                uint64_t live;
+                if ((rc = live_paths(c, sin, n_own, &live)) != 0) return rc;
                 if (live == 0) break;
             }
         }
-        HIPCHK(c, hipEventRecord(pass_e1, st));
-        FilmArgs fa{};
-        fa.Lhome = Lhome;
-        fa.acc = acc;
-        fa.cap = cap;
-        fa.cx0 = f->crop_x;
-        fa.cy0 = f->crop_y;
-        fa.cw = f->crop_w;
-        fa.ch = f->crop_h;
-        fa.rx0 = rx0;
-        fa.ry0 = ry0;
-        fa.rw = rw;
-        fa.rh = rh;
-        fa.npix_r = (uint32_t)npix_r;
-        fa.tile_rows = a.tile_rows;
+        if ((rc = timer.end()) != 0) return rc;
         fa.s_first = a.s_first;
         fa.s_count = sc;
-        fa.film_w = W;
-        fa.film_h = H;
-        fa.filter = f->filter;
-        fa.seed = f->seed;
-        if (f->filter == PBRT_FILTER_BOX)
-            hipLaunchKernelGGL(k_film_accum, dim3(div_up(film_px, 256)), dim3(256), 0, st, fa);
-        else {
-            // small crops: 4 x as many (single-wave) workgroups; same sums, pixel by pixel
-            const bool big = (uint64_t)div_up(f->crop_w, 16) * div_up(f->crop_h, 16) >= 4ull * (uint64_t)c->n_cu;
-            const bool tent = f->filter == PBRT_FILTER_TENT;
-            const dim3 g16(div_up(f->crop_w, 16), div_up(f->crop_h, 16)), g8(div_up(f->crop_w, 8), div_up(f->crop_h, 8));
-            if (big && tent)
-                hipLaunchKernelGGL((k_film_accum_tiled<16, PBRT_FILTER_TENT>), g16, dim3(16, 16), 0, st, fa);
-            else if (big)
-                hipLaunchKernelGGL((k_film_accum_tiled<16, PBRT_FILTER_GAUSSIAN>), g16, dim3(16, 16), 0, st, fa);
-            else if (tent)
-                hipLaunchKernelGGL((k_film_accum_tiled<8, PBRT_FILTER_TENT>), g8, dim3(8, 8), 0, st, fa);
-            else
-                hipLaunchKernelGGL((k_film_accum_tiled<8, PBRT_FILTER_GAUSSIAN>), g8, dim3(8, 8), 0, st, fa);
-        }
+        film_accum(c, fa);
         HIPCHK(c, hipGetLastError());
         s0 += sc;
         if (probe && passes == 0) {  // learn the plan from the probe pass
-            unsigned long long hp[2 + MAX_DEPTH_STATS];
-            hipLaunchKernelGGL(k_reduce_stats, dim3(stat_rows, REDUCE_SLICES), dim3(256), 0, st, segstats, n_rows, (size_t)n_rows, dstats);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(hp, dstats, (size_t)stat_rows * 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            HIPCHK(c, hipMemsetAsync(dstats, 0, (2 + 2 * MAX_DEPTH_STATS) * 8, st));  // the final reduction adds every row again
-            for (uint32_t d = stat_rows; d < 2 + MAX_DEPTH_STATS; ++d) hp[d] = 0;
-            call_plan = plan_from_survival(hp + 2, (uint32_t)std::min<uint64_t>(f->max_depth, MAX_DEPTH_STATS));
+            if ((rc = probe_plan(c, segstats, n_rows, stat_rows, dstats, f->max_depth, &plan)) != 0) return rc;
             const uint32_t rem = f->spp - s0;
             s_step = div_up(rem, div_up(rem, s_pass));  // equal passes for what is left
         }
@@ -1486,41 +1572,21 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     if (wavefront && (rc = wf_guard_fetch(c, hguard)) != 0) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     if (wavefront && (rc = wf_check_guard(c, hguard)) != 0) return rc;
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    double bounce_ms = 0.0;
-    for (size_t i = 0; i + 1 < n_ev; i += 2) {
-        float t = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev_pool[i], c->ev_pool[i + 1]));
-        bounce_ms += t;
-    }
+    if ((rc = call_stats(c, hstats, npix_r * f->spp, launches, passes, true, timer.n_ev)) != 0) return rc;
     pbrt_stats &S = c->stats;
-    S = pbrt_stats{};
-    S.samples = npix_r * f->spp;
-    S.segments = hstats[0];
-    S.shadow_rays = hstats[1];
-    S.kernel_ms = ms;
-    S.bounce_ms = bounce_ms;
-    S.bounce_launches = launches;
-    S.passes = passes;
-    S.fuse_plan = call_plan;
+    S.fuse_plan = plan;
     S.plan_source = wavefront ? PBRT_PLAN_STREAMS
                     : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? PBRT_PLAN_CALLER
                     : probe ? PBRT_PLAN_PROBED
                     : plan_was_learnt ? PBRT_PLAN_LEARNT : PBRT_PLAN_DEFAULT;
     S.pass_paths = (uint64_t)npix_r * s_pass;
-    S.workspace_bytes = 0;
-    for (const auto &kv : c->ws) S.workspace_bytes += kv.second.bytes;
-    uint64_t tot, bb;
-    for (int d = 0; d < 16; ++d) S.live[d] = hstats[2 + d];
-    const bool brute_k = s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG;
-    const uint32_t plan = call_plan;
-    if (brute_k && hstats[2] > 0) {  // remember what this scene's paths do for the next render of it
+    if (brute && hstats[2] > 0) {  // remember what this scene's paths do for the next render of it
         s->plan_hint = plan_from_survival(hstats + 2, (uint32_t)std::min<uint64_t>(f->max_depth, MAX_DEPTH_STATS));
         s->plan_hint_valid = true;
     }
+    uint64_t tot, bb;
     radiance_model_bytes(hstats + 2, MAX_DEPTH_STATS, S.samples, film_px, passes, plan, f->max_depth,
-                         hit_pool ? hstats + HIT_ROW0 : nullptr, &tot, &bb);
+                         wavefront ? hstats + HIT_ROW0 : nullptr, &tot, &bb);
     if (wavefront) {
         tot -= bb;
         uint64_t trb = 0;
@@ -1528,7 +1594,7 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
         tot += bb;
         S.trace_model_bytes = trb;
     }
-    if (brute_k && (f->flags & PBRT_FILM_REGEN)) {  // k_regen keeps the paths in registers: only the radiance records are written
+    if (brute && (f->flags & PBRT_FILM_REGEN)) {  // k_regen keeps the paths in registers: only the radiance records are written
         tot -= bb;
         bb = S.samples * 12;
         tot += bb;
@@ -1586,6 +1652,28 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
     ++c->call_seq;
     const uint32_t REGION = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
     const uint32_t cap = div_up(n, REGION) * REGION, nseg = cap / REGION;
+    // key_mode 1: key = (index_offset + home, sample_index) for the caller's n rays
+    auto ray_args = [&](float *Lhome, unsigned long long *rows, uint32_t n_rows) {
+        RadArgs a{};
+        a.sc = s->ds;
+        a.Lhome = Lhome;
+        a.stats = rows;
+        a.stat_stride = n_rows;
+        a.cap = cap;
+        a.state_cap = cap;
+        a.n_paths = n;
+        a.max_depth = max_depth;
+        a.rr_depth = rr_depth;
+        a.seed = seed;
+        a.key_mode = 1;
+        a.npix_r = 1;
+        a.rw = 1;
+        a.div_npix = a.div_rw = make_fastdiv(1);
+        a.index_offset = index_offset;
+        a.sample_index = sample_index;
+        a.lds_bytes = s->lds_bytes;
+        return a;
+    };
     if (s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS) {  // trace / shade streams
         NEED(c, cap < WF_DEAD);
         WfBufs b{};
@@ -1605,24 +1693,8 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
         HIPCHK(c, hipMemsetAsync(Lh, 0, (size_t)cap * 16, st));
         hipLaunchKernelGGL(k_init_rays_wf, dim3(div_up(std::max(n, nseg), 256)), dim3(256), 0, st, b.stA, cap, b.segA, nseg, n, io,
                            io + 3 * (size_t)n, io + 6 * (size_t)n);
-        WfArgs w{};
-        w.sc = s->ds;
-        w.Lhome = Lh;
-        w.stats = rows;
-        w.stat_stride = n_rows;
-        w.cap = cap;
-        w.n_paths = n;
-        w.max_depth = max_depth;
-        w.rr_depth = rr_depth;
-        w.seed = seed;
-        w.key_mode = 1;
-        w.npix_r = 1;
-        w.rw = 1;
-        w.div_npix = w.div_rw = make_fastdiv(1);
-        w.index_offset = index_offset;
-        w.sample_index = sample_index;
         uint32_t launches = 0;
-        if ((rc = wf_bounces(s, w, b, p, nseg, false, &launches)) != 0) return rc;
+        if ((rc = wf_bounces(s, wf_args(ray_args(Lh, rows, n_rows)), b, p, nseg, false, &launches)) != 0) return rc;
         uint32_t hguard[WF_GUARD_WORDS] = {0};
         if ((rc = wf_guard_fetch(c, hguard)) != 0) return rc;
         HIPCHK(c, hipStreamSynchronize(st));
@@ -1655,24 +1727,7 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
     HIPCHK(c, hipMemsetAsync(Lhome, 0, (size_t)cap * 16, st));
     hipLaunchKernelGGL(k_init_rays, dim3(div_up(std::max(n, n_own), 256)), dim3(256), 0, st, stA, segA, n_own, REGION / owners, n, io,
                        io + 3 * (size_t)n, io + 6 * (size_t)n);
-    RadArgs a{};
-    a.sc = s->ds;
-    a.Lhome = Lhome;
-    a.stats = segstats;
-    a.stat_stride = n_rows;
-    a.cap = cap;
-    a.state_cap = cap;
-    a.n_paths = n;
-    a.max_depth = max_depth;
-    a.rr_depth = rr_depth;
-    a.seed = seed;
-    a.key_mode = 1;
-    a.npix_r = 1;
-    a.rw = 1;
-    a.div_npix = a.div_rw = make_fastdiv(1);
-    a.index_offset = index_offset;
-    a.sample_index = sample_index;
-    a.lds_bytes = s->lds_bytes;
+    RadArgs a = ray_args(Lhome, segstats, n_rows);
     float *in = stA, *out = stB;
     uint32_t *sin = segA, *sout = segB;
     for (uint32_t depth = 0; depth < max_depth; ++depth) {
@@ -1686,11 +1741,8 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
         std::swap(in, out);
         std::swap(sin, sout);
         if (max_depth > 32 && (depth & 7) == 7) {
-            std::vector<uint32_t> cnt(n_own);
-            HIPCHK(c, hipMemcpyAsync(cnt.data(), sin, (size_t)n_own * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            uint64_t live = 0;
-            for (uint32_t v : cnt) live += v;
+            uint64_t live;
+            if ((rc = live_paths(c, sin, n_own, &live)) != 0) return rc;
             if (live == 0) break;
         }
     }
@@ -1706,14 +1758,18 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
 // ultrasound mode driver
 // ------------------------------------------------------------------------------------------------
 static inline float host_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// :248 float32 elem_x = pitch * (arange_f32 - (N-1)/2)
+static inline float us_elem_x(const pbrt_us_params *p, uint32_t e) {
+    return (float)((double)p->pitch * ((double)(float)e - ((double)p->n_elements - 1.0) / 2.0));
+}
 
 int pbrt_us_tx_delays(const pbrt_us_params *p, float *tx) {
     if (!p || !tx || p->n_angles > PBRT_US_MAX_ANGLES || p->n_angles == 0 || p->n_elements == 0) return PBRT_E_INVALID;
     for (uint32_t a = 0; a < p->n_angles; ++a) {
         double ar = (double)p->angles_deg[a] * (M_PI / 180.0);  // np.deg2rad, CustomIntegrator.py:247
         for (uint32_t e = 0; e < p->n_elements; ++e) {
-            // :248 float32 elem_x = pitch * (arange_f32 - (N-1)/2); :254,257 tx = f32(elem_x * sin(a) / c)
-            float ex = (float)((double)p->pitch * ((double)(float)e - ((double)p->n_elements - 1.0) / 2.0));
+            // :254,257 tx = f32(elem_x * sin(a) / c)
+            const float ex = us_elem_x(p, e);
             tx[a * p->n_elements + e] = (float)(((double)ex * std::sin(ar)) / (double)p->sound_speed);
         }
     }
@@ -1930,8 +1986,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         xfv(sinf(ar), 0.0f, cosf(ar), &dir0[3 * a]);
         nrm(&dir0[3 * a]);
     }
-    for (uint32_t e = 0; e < NE; ++e)
-        ex[e] = (float)((double)p->pitch * ((double)(float)e - ((double)NE - 1.0) / 2.0));  // :248
+    for (uint32_t e = 0; e < NE; ++e) ex[e] = us_elem_x(p, e);
 #ifndef US_PASS_PATHS
 // paths in flight per pass.  Config 3 (268 M paths), one launch per bounce: 8 / 16 / 32 / 64 Mi -> 13.1 / 12.7 / 13.0 /
 // 13.2 ms; with all bounces of a pass in one launch the survivors are re-read while still cached and smaller passes
@@ -1947,40 +2002,25 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     if (const char *e = getenv("PBRT_US_FUSED_BVH")) streams = streams && atoi(e) == 0;
 #endif
     // paths in flight per pass.  Streams: 2 x 10 launches per pass whatever is still alive, so passes as large as the radiance
-    // streams take (wf_default_pass_paths; the shared trace / shade workspace)
-    uint64_t pass_paths = streams ? wf_default_pass_paths(c, 1u << 20) : US_PASS_PATHS;
-    if (!streams && c->ws_limit)  // the pass buffers must fit the context's workspace limit
-        while (pass_paths > (1u << 20) && (double)pass_paths * (double)(2 * N_STATE * 4) > (double)c->ws_limit - 64e6) pass_paths /= 2;
-    // The free-memory figure behind the default is a snapshot (torch or another process may allocate between the query and the
-    // hipMalloc): a failed allocation gives the pass buffers back, halves the pass and tries again, like render_impl; the
-    // echoes do not depend on the pass size (global path keys).  What did fit is released when even the smallest pass does not.
-    const uint64_t US_MIN_PASS = 1u << 20;
+    // streams take (wf_default_pass_paths; the shared trace / shade workspace).  The fused kernels: the pass buffers must fit the
+    // context's workspace limit.  A failed allocation halves the pass (size_pass); the echoes do not depend on the pass size.
     const uint32_t REGION = streams ? WF_REGION : us_region_segs(s->accel_kernel, emit) * seg_threads(s->accel_kernel);
-    uint32_t ppr_pass = 1, cap = 0, nseg = 0;
     WfBufs wfb{};
-    WfPlan wfp;
     float *stA = nullptr, *stB = nullptr;
     uint32_t *segA = nullptr, *segB = nullptr;
-    for (;;) {
-        ppr_pass = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(ppr, pass_paths / n_rays));
-        NEED(c, (uint64_t)n_rays * ppr_pass < 0xfffffc00ull);
-        cap = div_up((uint64_t)n_rays * ppr_pass, REGION) * REGION;
-        nseg = cap / REGION;
+    auto alloc_pass = [&](uint32_t cap, uint32_t nseg) -> int {
         NEED(c, streams || (uint64_t)cap * US_N_STATE * 4 < 0xffffffffull);  // the state tiles are addressed through 32-bit buffer offsets
         NEED(c, !streams || cap < WF_DEAD);
-        bool ok;
-        if (streams) {
-            ok = wf_alloc(c, cap, nseg, &wfb);
-        } else {
-            stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
-            stB = stA ? (float *)c->buf("stateB", (size_t)cap * N_STATE * 4) : nullptr;
-            ok = stA && stB;
-        }
-        if (ok) break;
-        release_pass_buffers(c);
-        if (ppr_pass <= 1 || pass_paths <= US_MIN_PASS) return PBRT_E_NOMEM;  // (the message of the failed request stands)
-        pass_paths = std::max<uint64_t>(US_MIN_PASS, std::min<uint64_t>(pass_paths, (uint64_t)n_rays * ppr_pass) / 2);
-    }
+        if (streams) return wf_alloc(c, cap, nseg, &wfb) ? PBRT_OK : PBRT_E_NOMEM;
+        stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
+        stB = stA ? (float *)c->buf("stateB", (size_t)cap * N_STATE * 4) : nullptr;
+        return stA && stB ? PBRT_OK : PBRT_E_NOMEM;
+    };
+    const uint64_t pass_paths = default_pass_paths(c, streams, US_PASS_PATHS, 2 * N_STATE * 4);
+    PassShape ps;
+    if ((rc = size_pass(c, pass_paths, false, ppr, n_rays, REGION, false, alloc_pass, &ps)) != 0) return rc;
+    const uint32_t ppr_pass = ps.per_pass, cap = ps.cap, nseg = ps.nseg;
+    WfPlan wfp;
     if (streams) {
         wfp = wf_plan(s);
         wfp.packet = false;
@@ -2061,7 +2101,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     a.lds_bytes = s->lds_bytes;
     a.fuse = (p->quirks & PBRT_USQ_NO_FUSED_BOUNCES) ? 0u : 1u;
     a.div_ne = make_fastdiv(NE);
-    for (uint32_t n : {0u, 1u, NE - 1, NE, NE + 1, n_rays - 1, n_rays}) NEED(c, udiv_fast_host(n, a.div_ne) == n / NE);
+    NEED(c, fastdiv_exact(a.div_ne, NE, {0u, 1u, NE - 1, NE, NE + 1, n_rays - 1, n_rays}));
     // first-bounce tables (kernels_us.h k_us_first): worth it once a ray has more paths than receive elements
     if (ppr >= NE && !(p->quirks & PBRT_USQ_NO_FIRST_TABLES) && !emit) {  // (emitter rays: every path has its own origin)
         float4 *fh = (float4 *)c->buf("us_first_hit", (size_t)n_rays * 16);
@@ -2076,20 +2116,18 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         a.first_hit = fh;
         a.first_rx = fv;
     }
-    size_t n_ev = 0;
-    hipEvent_t pass_e1 = nullptr;
+    PassTimer timer{c, timed};
     uint32_t passes = 0, launches = 0;
+    const char *e_perm = getenv("PBRT_US_EMIT_PERMUTE");  // A/B and test: 0 keeps workgroup b on region b (read per call)
     for (uint32_t k0 = 0; k0 < ppr; k0 += ppr_pass, ++passes) {
         const uint32_t kc = std::min(ppr_pass, ppr - k0);
         a.ppr_pass = kc;
         a.div_ppr = make_fastdiv(kc);
-        for (uint32_t n : {0u, 1u, kc - 1, kc, kc + 1, n_rays * kc - 1, n_rays * kc, 0xfffffbffu})
-            NEED(c, udiv_fast_host(n, a.div_ppr) == n / kc);
+        NEED(c, fastdiv_exact(a.div_ppr, kc, {0u, 1u, kc - 1, kc, kc + 1, n_rays * kc - 1, n_rays * kc, 0xfffffbffu}));
         a.path_first = path_offset + k0;
         a.n_paths = n_rays * kc;
         const uint32_t nseg_pass = div_up(a.n_paths, REGION);
         a.blk_mul = 0;
-        const char *e_perm = getenv("PBRT_US_EMIT_PERMUTE");  // A/B and test: 0 keeps workgroup b on region b (read per call)
         if (emit && !streams && nseg_pass > 2u * NA && !(e_perm && atoi(e_perm) == 0)) {
             uint32_t m = (nseg_pass / NA) | 1u;
             if (e_perm && atoi(e_perm) > 1) m = (uint32_t)atoi(e_perm) | 1u;  // (A/B: another stride)
@@ -2097,13 +2135,9 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
             a.blk_mul = m % nseg_pass;
         }
         if (streams) {
-            pass_e1 = c->event(n_ev + 1);
-            hipEvent_t e0 = c->event(n_ev);
-            if (!e0 || !pass_e1) return c->fail(PBRT_E_DEVICE, "hipEventCreate failed");
-            n_ev += 2;
-            if (timed) HIPCHK(c, hipEventRecord(e0, st));
+            if ((rc = timer.begin()) != 0) return rc;
             if ((rc = us_wf_pass(s, a, wfb, wfp, nseg_pass, &launches)) != 0) return rc;
-            if (timed) HIPCHK(c, hipEventRecord(pass_e1, st));
+            if ((rc = timer.end()) != 0) return rc;
             continue;
         }
         float *in = stA, *out = stB;
@@ -2114,14 +2148,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
             a.out = out;
             a.seg_in = sin;
             a.seg_out = sout;
-            // ONE event pair per pass around its bounce launches (a pair per launch costs ~8 us of queue bubbles each)
-            if (depth == 0) {
-                pass_e1 = c->event(n_ev + 1);
-                hipEvent_t e0 = c->event(n_ev);
-                if (!e0 || !pass_e1) return c->fail(PBRT_E_DEVICE, "hipEventCreate failed");
-                n_ev += 2;
-                if (timed) HIPCHK(c, hipEventRecord(e0, st));
-            }
+            if (depth == 0 && (rc = timer.begin()) != 0) return rc;
             bool first_kernel = depth == 0;
             if (depth == 0 && emit && !emit_fused) {
                 // emitter rays: the primary rays into the state (k_us_emit_init writes a.out / a.seg_out), then the later-bounce
@@ -2142,7 +2169,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
             std::swap(in, out);
             std::swap(sin, sout);
         }
-        if (timed) HIPCHK(c, hipEventRecord(pass_e1, st));
+        if ((rc = timer.end()) != 0) return rc;
     }
     const float inv_norm = 1.0f / (float)(norm_paths ? norm_paths : 1);
     // (one path per ray, the reference's own setting (USMain.py:36): the factor is exactly 1 and the pass over the buffer changes no bit)
@@ -2163,7 +2190,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     P.scaled = inv_norm != 1.0f;
     P.streams = streams;
     P.tab0 = a.first_hit != nullptr;
-    P.n_ev = n_ev;
+    P.n_ev = timer.n_ev;
     P.passes = passes;
     P.launches = launches;
     P.samples = (uint64_t)n_rays * ppr;
@@ -2187,24 +2214,8 @@ static int us_finish(pbrt_ctx *c) {
         for (uint32_t sl = 0; sl < REDUCE_SLICES; ++sl) t += c->pin_stats()[(size_t)r * REDUCE_SLICES + sl];
         hstats[r] = t;
     }
-    float ms = 0.0f;
-    if (P.timed) HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    double bounce_ms = 0.0;
-    for (size_t i = 0; P.timed && i + 1 < P.n_ev; i += 2) {
-        float t = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev_pool[i], c->ev_pool[i + 1]));
-        bounce_ms += t;
-    }
+    if ((rc = call_stats(c, hstats, P.samples, P.launches, P.passes, P.timed, P.n_ev)) != 0) return rc;
     pbrt_stats &S = c->stats;
-    S = pbrt_stats{};
-    S.samples = P.samples;
-    S.segments = hstats[0];
-    S.shadow_rays = hstats[1];
-    S.kernel_ms = ms;
-    S.bounce_ms = bounce_ms;
-    S.bounce_launches = P.launches;
-    S.passes = P.passes;
-    for (int d = 0; d < 16; ++d) S.live[d] = hstats[2 + d];
     uint64_t bb = 0;
     for (uint32_t d = 0; d < MAX_DEPTH_STATS; ++d) {
         uint64_t in = hstats[2 + d], next = d + 1 < MAX_DEPTH_STATS ? hstats[2 + d + 1] : 0;
@@ -2236,7 +2247,6 @@ static int us_finish(pbrt_ctx *c) {
     }
     S.bounce_model_bytes = bb;
     S.model_bytes = bb + P.nchan * (P.scaled ? 12 : 4);  // clear (+ scale pass) over the channel buffer
-    S.workspace_bytes = c->ws_total();
     return PBRT_OK;
 }
 
