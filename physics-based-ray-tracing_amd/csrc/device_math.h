@@ -50,6 +50,42 @@ DEV uint32_t udiv_fast(uint32_t n, FastDiv f) {
     return f.is_one ? n : q;
 }
 
+// ---- short correctly rounded forms -----------------------------------------------------------------------
+// A correctly rounded result is unique, so any sequence that provably returns RN(1/b), RN(a/b) or RN(sqrt x) has the bits of
+// the compiler's '/' and sqrtf and of the CPU oracle.  The compiler's expansion pays for operand scaling and special values on
+// every call (~11 VALU per division, ~13 per sqrtf); these forms are checked bit for bit against '/' and sqrtf on the device
+// (tests/native/fp_short_forms.hip), over every f32 input for the one-operand forms.
+//
+// rcp_core(b): one Newton step on v_rcp_f32 (e = 1 - b y0 is exact because y0 is within an ulp of 1/b).  Equal to RN(1/b) for
+// every b with 2^-126 <= |b| <= 2^126 (the device check: all 2^32 inputs, mismatches only for subnormal b and |b| > 2^126);
+// rcp_rn adds v_div_fixup for 0, inf and NaN.  The reciprocal of a sqrtf or sqrt_rn result is always in that range.
+DEV float rcp_core(float b) {
+    const float y0 = __builtin_amdgcn_rcpf(b);
+    const float e = __builtin_fmaf(-b, y0, 1.0f);
+    return __builtin_fmaf(e, y0, y0);
+}
+DEV float rcp_rn(float b) { return __builtin_amdgcn_div_fixupf(rcp_core(b), b, 1.0f); }
+// sqrt_rn(x): v_sqrt_f32 (not correctly rounded by itself) and a neighbour check (s - 1 ulp and s + 1 ulp by their fma
+// residuals), without the compiler's operand scaling and class fix-up.  Equal to sqrtf for every x except 0 < |x| < 2^-104
+// (there v_sqrt_f32 or the residuals leave the normal range): +-0, +inf, NaN and negative normals included.
+DEV float sqrt_rn(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
+    const float rdn = __builtin_fmaf(-dn, s, x), rup = __builtin_fmaf(-up, s, x);
+    float r = rdn <= 0.0f ? dn : s;
+    return rup > 0.0f ? up : r;
+}
+// div_rn(a, b): Markstein's correction on q = a RN(1/b): r = a - b q is exact and q + r y rounds to RN(a/b) while
+// 2^-126 <= |b| <= 2^126 and either a == 0 or |a| >= 2^-100 with a quotient 2^-126 <= |a/b| < 2^127 (q = a y must not overflow);
+// v_div_fixup for the signs and special operands.  Device check: every divisor mantissa at 11 exponents x 2050 numerators,
+// and 1.3e10 random pairs of that domain.
+DEV float div_rn(float a, float b) {
+    const float y = rcp_core(b);
+    const float q = a * y;
+    const float r = __builtin_fmaf(-b, q, a);
+    return __builtin_amdgcn_div_fixupf(__builtin_fmaf(r, y, q), b, a);
+}
+
 struct V3 {
     float x, y, z;
 };
@@ -67,7 +103,7 @@ DEV V3 cross(V3 a, V3 b) {
 }
 DEV V3 madd(V3 a, float s, V3 b) { return {fma_(a.x, s, b.x), fma_(a.y, s, b.y), fma_(a.z, s, b.z)}; }
 DEV V3 normalize(V3 v) {
-    float inv = 1.0f / sqrtf(dot(v, v));
+    float inv = rcp_rn(sqrtf(dot(v, v)));  // the reciprocal of a sqrtf result: inside rcp_rn's range
     return v * inv;
 }
 DEV float max3(V3 v) { return fmaxf(v.x, fmaxf(v.y, v.z)); }
@@ -123,7 +159,9 @@ DEV void square_to_disk(float sx, float sy, float *dx, float *dy) {
     bool is_zero = (x == 0.0f) && (y == 0.0f);
     bool q13 = fabsf(x) < fabsf(y);
     float r = q13 ? y : x, rp = q13 ? x : y;
-    float a = is_zero ? 0.0f : K_PI_OVER_4 * (rp / r);
+    // sx, sy in [0, 1]: x and y are 0 or multiples of 2^-24 in [-1, 1] and |rp| <= |r|, so r is in [2^-24, 1] and the quotient
+    // 0 or in [2^-24, 1] (div_rn's domain); r == 0 only with is_zero, whose quotient is discarded
+    float a = is_zero ? 0.0f : K_PI_OVER_4 * div_rn(rp, r);
     float s, c;
     sincos_pi4(a, &s, &c);
     *dx = r * (q13 ? s : c);
@@ -133,13 +171,13 @@ DEV V3 square_to_cosine_hemisphere(float sx, float sy) {
     float dx, dy;
     square_to_disk(sx, sy, &dx, &dy);
     float z2 = 1.0f - fma_(dx, dx, dy * dy);
-    return {dx, dy, sqrtf(fmaxf(z2, 0.0f))};
+    return {dx, dy, sqrt_rn(fmaxf(z2, 0.0f))};  // z2 = 1 - t, t >= 0: 0, >= 1/2, or a multiple of 2^-24 (Sterbenz)
 }
 DEV V3 square_to_uniform_hemisphere(float sx, float sy) {
     float dx, dy;
     square_to_disk(sx, sy, &dx, &dy);
     float z = 1.0f - fma_(dx, dx, dy * dy);
-    float k = sqrtf(z + 1.0f);
+    float k = sqrt_rn(z + 1.0f);  // z + 1 = 2 - t with t = dx^2 + dy^2 <= 1 (rounded): at least 1 - 2^-23
     return {dx * k, dy * k, z};
 }
 
@@ -149,7 +187,7 @@ struct Frame {
 };
 DEV Frame make_frame(V3 n) {
     float sign = copysignf(1.0f, n.z);
-    float a = -1.0f / (sign + n.z);
+    float a = -rcp_rn(sign + n.z);  // |sign + n.z| >= 1: inside rcp_rn's range
     float b = n.x * n.y * a;
     Frame f;
     f.s = {fma_(sign * n.x, n.x * a, 1.0f), sign * b, -sign * n.x};
@@ -164,7 +202,7 @@ DEV Frame make_sh_frame(V3 n, V3 dp_du) {
     float l2 = dot(s, s);
     if (!(l2 > 0.0f)) return make_frame(n);
     Frame f;
-    f.s = s * (1.0f / sqrtf(l2));
+    f.s = s * rcp_rn(sqrtf(l2));
     f.t = cross(n, f.s);
     f.n = n;
     return f;

@@ -964,7 +964,7 @@ DEV ESample sample_emitter(const Tables &sc, V3 p, F4 u) {
         V3 dv = e.q - p;
         float d2 = dot(dv, dv);
         e.dist = sqrtf(d2);
-        float inv = 1.0f / e.dist;
+        float inv = rcp_rn(e.dist);  // the reciprocal of a sqrtf result
         e.d = dv * inv;
         e.pdf = 1.0f;
         e.delta = true;
@@ -978,7 +978,7 @@ DEV ESample sample_emitter(const Tables &sc, V3 p, F4 u) {
     const pbrt_prim &P = sc.prims_by_id[sc.light_prims[E.first + k]];
     float b1, b2;
     if (P.type == PBRT_PRIM_TRIANGLE) {
-        float t = sqrtf(fmaxf(1.0f - u.z, 0.0f));
+        float t = sqrt_rn(fmaxf(1.0f - u.z, 0.0f));  // u.z a multiple of 2^-24 in [0, 1): 1 - u.z in [2^-24, 1]
         b1 = 1.0f - t;
         b2 = t * u.w;
     } else {
@@ -990,7 +990,7 @@ DEV ESample sample_emitter(const Tables &sc, V3 p, F4 u) {
     V3 dv = e.q - p;
     float d2 = dot(dv, dv);
     e.dist = sqrtf(d2);
-    float inv = 1.0f / e.dist;
+    float inv = rcp_rn(e.dist);  // the reciprocal of a sqrtf result
     e.d = dv * inv;
     float cosl = -dot(nl, e.d);
     if (!(cosl > 0.0f)) return e;
@@ -1001,13 +1001,17 @@ DEV ESample sample_emitter(const Tables &sc, V3 p, F4 u) {
     return e;
 }
 
+// pixel position px + jitter -> film coordinate: f is 0 or in [2^-24, 2^32] and the film side a nonzero uint32, so the
+// quotient is 0 or >= 2^-56 (div_rn's domain)
+DEV float film_coord(float f, uint32_t side) { return div_rn(f, (float)side); }
+
 // ---- Sensor.sample_ray: Mitsuba 'perspective' ---------------------------------------------------
 DEV void camera_ray(const pbrt_camera &cam, float sx, float sy, V3 *o, V3 *d, float *tmax) {
     float tx = cam.tan_half_fov_x;
     float ty = tx * (float)cam.film_h / (float)cam.film_w;
     V3 dc = normalize(v3(fma_(-2.0f, sx, 1.0f) * tx, fma_(-2.0f, sy, 1.0f) * ty, 1.0f));
     V3 dw = normalize(xf_vec(cam.to_world, dc));
-    float inv_z = 1.0f / dc.z;
+    float inv_z = rcp_rn(dc.z);  // dc.z = 1 / |(.., .., 1)|: in [2^-64, 1]
     V3 org = {cam.to_world[3], cam.to_world[7], cam.to_world[11]};
     *o = madd(dw, cam.near_clip * inv_z, org);
     *d = dw;

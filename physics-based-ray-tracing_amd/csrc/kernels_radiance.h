@@ -342,7 +342,7 @@ DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsr
                             V3 so = offset_origin(si.p, si.n, es.d);
                             V3 sv = es.q - so;
                             float sd = sqrtf(dot(sv, sv));
-                            V3 sdir = sv * (1.0f / sd);
+                            V3 sdir = sv * rcp_rn(sd);  // the reciprocal of a sqrtf result
                             did_shadow = true;
                             Hit hs;
 #ifdef PBRT_ABLATE_SHADOW
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
             path_key<TILED>(a, home, &ka, &kb, &px, &py);
             F4 uj = rng4(ka, kb, 0, a.seed);
             float fx = (float)px + uj.x, fy = (float)py + uj.y;
-            camera_ray(a.cam, fx / (float)a.film_w, fy / (float)a.film_h, &o, &d, &tmax);
+            camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
             thr = {1, 1, 1};
             L = {0, 0, 0};
             eta = 1.0f;
@@ -716,7 +716,7 @@ __global__ __launch_bounds__(SEG_BRUTE, ACCEL == ACCEL_K_BRUTE ? FUSED_WAVES_PER
                 path_key<true>(a, home, &ka, &kb, &px, &py);
                 F4 uj = rng4(ka, kb, 0, a.seed);
                 float fx = (float)px + uj.x, fy = (float)py + uj.y;
-                camera_ray(a.cam, fx / (float)a.film_w, fy / (float)a.film_h, &o, &d, &tmax);
+                camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
                 thr = {1, 1, 1};
                 L = {0, 0, 0};
                 eta = 1.0f;
@@ -868,7 +868,7 @@ __global__ __launch_bounds__(SEG_BRUTE, WALK_WAVES_PER_EU) void k_walk(const Rad
                 path_key<true>(a, home, &ka, &kb, &px, &py);
                 F4 uj = rng4(ka, kb, 0, a.seed);
                 float fx = (float)px + uj.x, fy = (float)py + uj.y;
-                camera_ray(a.cam, fx / (float)a.film_w, fy / (float)a.film_h, &o, &d, &tmax);
+                camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
             } else {
                 const uint32_t v4 = state_voff(slot);
                 constexpr uint32_t row = STATE_ROW_BYTES;
@@ -1028,7 +1028,7 @@ __global__ __launch_bounds__(REGEN_WG, REGEN_WAVES_PER_EU) void k_regen(const Ra
                 path_key<true>(a, home, &ka, &kb, &px, &py);
                 F4 uj = rng4(ka, kb, 0, a.seed);
                 float fx = (float)px + uj.x, fy = (float)py + uj.y;
-                camera_ray(a.cam, fx / (float)a.film_w, fy / (float)a.film_h, &o, &d, &tmax);
+                camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
                 thr = {1, 1, 1};
                 L = {0, 0, 0};
                 eta = 1.0f;

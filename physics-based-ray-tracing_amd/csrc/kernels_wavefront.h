@@ -103,7 +103,7 @@ DEV void wf_camera_ray(const WfArgs &a, uint32_t home, V3 *o, V3 *d, float *tmax
     path_key<true>(ra, home, ka, kb, &px, &py);
     F4 uj = rng4(*ka, *kb, 0, a.seed);
     float fx = (float)px + uj.x, fy = (float)py + uj.y;
-    camera_ray(a.cam, fx / (float)a.film_w, fy / (float)a.film_h, o, d, tmax);
+    camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), o, d, tmax);
 }
 
 // Every loop of the stream has an exit that each wave reaches; the guard below is the net under it: a wave that exceeds
@@ -506,7 +506,7 @@ DEV bool wf_shade_step(const WfArgs &a, const Tables &tb, uint32_t depth, uint32
                     V3 so = offset_origin(si.p, si.n, es.d);
                     V3 sv = es.q - so;
                     float sd = sqrtf(dot(sv, sv));
-                    V3 sdir = sv * (1.0f / sd);
+                    V3 sdir = sv * rcp_rn(sd);  // the reciprocal of a sqrtf result
                     float mis = es.delta ? 1.0f : mis_weight(es.pdf, bpdf);
                     sh.on = true;
                     sh.so = so;
