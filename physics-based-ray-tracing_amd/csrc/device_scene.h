@@ -690,11 +690,12 @@ struct SI {
 // Mitsuba Mesh::compute_surface_interaction: sh_frame.n = normalize(b0 n0 + b1 n1 + b2 n2) with the barycentrics of the hit.
 // SHN: compiled into the BVH and the _BIG brute-force kernels only (a small scene with vertex normals takes the _BIG
 // variant, like one with a cone: the 64-VGPR Cornell-box kernel has no registers to spare).
-template <bool SHN>
-DEV V3 shading_normal(const pbrt_prim &P, V3 n, float u, float v, const float *vn, uint32_t slot) {
-    if (!SHN || vn == nullptr || (P.type != PBRT_PRIM_TRIANGLE && P.type != PBRT_PRIM_PARALLELOGRAM)) return n;
-    const float *r = vn + 9u * slot;
-    const V3 n0 = {r[0], r[1], r[2]}, n1 = {r[3], r[4], r[5]}, n2 = {r[6], r[7], r[8]};
+// has_vn / vn(k): whether the scene has vertex normals, and float k of the nine of this primitive -- read on demand from the
+// scene's array (make_si below) or from the batch the stream kernels preload with the primitive's record (wf_load_vn).
+template <bool SHN, class Vn>
+DEV V3 shading_normal(const pbrt_prim &P, V3 n, float u, float v, bool has_vn, Vn &&vn) {
+    if (!SHN || !has_vn || (P.type != PBRT_PRIM_TRIANGLE && P.type != PBRT_PRIM_PARALLELOGRAM)) return n;
+    const V3 n0 = {vn(0), vn(1), vn(2)}, n1 = {vn(3), vn(4), vn(5)}, n2 = {vn(6), vn(7), vn(8)};
     if (!(dot(n0, n0) + dot(n1, n1) + dot(n2, n2) > 0.0f)) return n;  // no vertex normals on this primitive
     if (P.type == PBRT_PRIM_PARALLELOGRAM) return normalize(n0);      // a merged quad: all its vertex normals agree
     const float b0 = 1.0f - u - v;
@@ -708,8 +709,10 @@ DEV V3 cylinder_normal(const pbrt_prim &P, V3 p) {
     const V3 n = normalize(madd(r0, xo, r1 * yo));
     return dot(r2, cross(r0, r1)) < 0.0f ? v3(-n.x, -n.y, -n.z) : n;
 }
-template <bool CONES = true>
-DEV SI make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, const float *vn = nullptr, uint32_t slot = 0) {
+// CONES / CYL: the primitive types compiled in besides spheres, triangles and parallelograms.  CONES = false also drops the vertex
+// normals (the 64-VGPR brute-force kernel); the stream kernels compile cylinders in only for scenes that hold one.
+template <bool CONES, bool CYL, class Vn>
+DEV SI make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, bool has_vn, Vn &&vn) {
     SI si;
     if (P.type == PBRT_PRIM_SPHERE) {
         V3 c = g3(P, 0);
@@ -728,15 +731,20 @@ DEV SI make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, const 
         }
         si.n = normalize(v3(fma_(r0.x, no.x, fma_(r1.x, no.y, r2.x * no.z)), fma_(r0.y, no.x, fma_(r1.y, no.y, r2.y * no.z)),
                             fma_(r0.z, no.x, fma_(r1.z, no.y, r2.z * no.z))));
-    } else if (CONES && P.type == PBRT_PRIM_CYLINDER) {
+    } else if (CYL && P.type == PBRT_PRIM_CYLINDER) {
         si.p = madd(d, t, o);
         si.n = cylinder_normal(P, si.p);
     } else {
         si.p = madd(g3(P, 6), v, madd(g3(P, 3), u, g3(P, 0)));
         si.n = g3(P, 9);
     }
-    si.ns = shading_normal<CONES>(P, si.n, u, v, vn, slot);
+    si.ns = shading_normal<CONES>(P, si.n, u, v, has_vn, vn);
     return si;
+}
+// ... with the vertex normals read on demand from the scene's array (the fused kernels)
+template <bool CONES = true>
+DEV SI make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, const float *vn = nullptr, uint32_t slot = 0) {
+    return make_si<CONES, CONES>(P, o, d, t, u, v, vn != nullptr, [&](int k) { return vn[(size_t)(9u * slot) + k]; });
 }
 
 // dp_du of the interaction, the input of Mitsuba's shading frame (make_sh_frame):

@@ -289,104 +289,121 @@ DEV TreeLds stage_tree_lds(const DevScene &sc, uint32_t *lds) {
     return TreeLds{reinterpret_cast<const LDS_AS uint32_t *>(img), plane, leaf_off};
 }
 
-// One bounce of one path (the body shared by k_bounce and k_walk): closest hit, emission + MIS, next-event estimation with
-// its shadow segment, BSDF sample, Russian roulette.  Returns whether the path goes on; a path that ends writes its
-// radiance to Lhome[home].
+// The arithmetic of one bounce from the surface interaction on -- emission + MIS, emitter sampling (next-event estimation) up to its
+// shadow segment, BSDF sample, Russian roulette: the ONE definition behind the fused kernels (bounce_step) and the streams
+// (kernels_wavefront.h k_shade), whose films agree bit for bit because they run these statements in this order.  What becomes of
+// the shadow segment is the caller's: segment(so, sdir, tmax) either traces it at once and says whether it got through, or stores it
+// and says yes; contribute(A, B) then adds fma(A, B, L) or stores the two factors for the kernel that learns the visibility.
+// Args: RadArgs or WfArgs (n_emitters, max_depth, rr_depth, seed).  Returns whether the path goes on.
+template <class Args, class Segment, class Contribute>
+DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka, uint32_t kb, float t_hit, const pbrt_prim &P,
+                    const SI &si, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, Segment &&segment,
+                    Contribute &&contribute) {
+    bool survive = false;
+    const uint32_t nE = a.sc.n_emitters;
+    const int32_t emitter = P.emitter;
+    const uint32_t mat_id = P.material;
+    // ---- direct emission (one-sided area emitters), MIS against emitter sampling
+    if (emitter >= 0) {
+        const pbrt_emitter &E = tb.emitters[emitter];
+        float cosl = -dot(si.ns, d);  // Frame::cos_theta(si.wi): the shading frame (== n on emitters)
+        if (cosl > 0.0f) {
+            float w = 1.0f;
+            if (prev_pdf >= 0.0f) {
+                float pdf_em = (t_hit * t_hit) / (cosl * E.area * (float)nE);
+                w = mis_weight(prev_pdf, pdf_em);
+            }
+            L = {fma_(thr.x * E.radiance[0], w, L.x), fma_(thr.y * E.radiance[1], w, L.y), fma_(thr.z * E.radiance[2], w, L.z)};
+        }
+    }
+    if (depth + 1 < a.max_depth) {
+        const pbrt_material M = tb.mats[mat_id];
+        Frame fr = make_frame(si.ns);
+        V3 wi = to_local(fr, -d);
+        // ---- emitter sampling (next-event estimation) + shadow segment
+#ifdef PBRT_ABLATE_NEE  // diagnostic builds only (tools/ablate.sh): never defined in the shipped library
+        if (false) {
+#else
+        if (M.type == PBRT_MAT_DIFFUSE && nE > 0) {
+#endif
+            F4 u = rng4(ka, kb, 1 + 2 * depth, a.seed);
+            ESample es = sample_emitter(tb, si.p, u);
+            if (es.valid) {
+                V3 wo = to_local(fr, es.d);
+                V3 f;
+                float bpdf;
+                bsdf_eval_pdf(M, wi, wo, &f, &bpdf);
+                if (bpdf > 0.0f) {
+                    V3 so = offset_origin(si.p, si.n, es.d);
+                    V3 sv = es.q - so;
+                    float sd = sqrtf(dot(sv, sv));
+                    V3 sdir = sv * rcp_rn(sd);  // the reciprocal of a sqrtf result
+                    if (segment(so, sdir, sd * (1.0f - K_SHADOW_EPS))) {
+                        float mis = es.delta ? 1.0f : mis_weight(es.pdf, bpdf);
+                        contribute(v3(thr.x * f.x, thr.y * f.y, thr.z * f.z), v3(es.weight.x * mis, es.weight.y * mis, es.weight.z * mis));
+                    }
+                }
+            }
+        }
+        // ---- BSDF sampling, continuation ray, Russian roulette
+        F4 ub = rng4(ka, kb, 2 + 2 * depth, a.seed);
+        BSample bs = bsdf_sample(M, PBRT_USQ_REFERENCE, wi, si.n, si.ns, fr, ub.x, ub.y, ub.z);
+        if (bs.valid) {
+            thr = thr * bs.weight;
+            eta *= bs.eta;
+            V3 nd = to_world(fr, bs.wo);
+            if (M.type == PBRT_MAT_ULTRA) nd = normalize(nd);
+            o = offset_origin(si.p, si.n, nd);
+            d = nd;
+            prev_pdf = bs.delta ? -1.0f : bs.pdf;
+            float tm = max3(thr);
+            survive = true;
+            if (depth + 1 >= a.rr_depth) {
+                float q = fminf(tm * eta * eta, 0.95f);
+                float rq = 1.0f / q;
+                thr = thr * rq;
+                if (!(ub.w < q)) survive = false;
+            }
+            if (tm == 0.0f) survive = false;
+        }
+    }
+    return survive;
+}
+
+// One bounce of one path (the body shared by k_bounce and k_walk): closest hit, the surface interaction, shade_step with its
+// shadow segment traced at once.  Returns whether the path goes on; a path that ends writes its radiance to Lhome[home].
 // HAVE_HIT: the closest hit was found earlier (k_bounce_pool) and comes in through h_in; the step starts at the shading.
 template <int ACCEL, bool HAVE_HIT = false>
 DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsrc r_L, uint32_t depth, uint32_t ka, uint32_t kb,
                      uint32_t home, float tmax, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, bool &did_seg,
                      bool &did_shadow, const Hit *h_in = nullptr) {
     bool survive = false;
-        const uint32_t nE = a.sc.n_emitters;
-        Hit h;
-        if (HAVE_HIT) h = *h_in;
-        if (HAVE_HIT || scene_intersect<ACCEL, false>(a.sc, ls, o, d, tmax, &h)) {
-            did_seg = true;
-            const pbrt_prim &P = tb.prims_by_slot[h.slot];
-            SI si = make_si<ACCEL != ACCEL_K_BRUTE>(P, o, d, h.t, h.u, h.v, a.sc.vnormals, h.slot);
-            const int32_t emitter = P.emitter;
-            const uint32_t mat_id = P.material;
-            // ---- direct emission (one-sided area emitters), MIS against emitter sampling
-            if (emitter >= 0) {
-                const pbrt_emitter &E = tb.emitters[emitter];
-                float cosl = -dot(si.ns, d);  // Frame::cos_theta(si.wi): the shading frame (== n on emitters)
-                if (cosl > 0.0f) {
-                    float w = 1.0f;
-                    if (prev_pdf >= 0.0f) {
-                        float pdf_em = (h.t * h.t) / (cosl * E.area * (float)nE);
-                        w = mis_weight(prev_pdf, pdf_em);
-                    }
-                    L = {fma_(thr.x * E.radiance[0], w, L.x), fma_(thr.y * E.radiance[1], w, L.y),
-                         fma_(thr.z * E.radiance[2], w, L.z)};
-                }
-            }
-            if (depth + 1 < a.max_depth) {
-                const pbrt_material M = tb.mats[mat_id];
-                Frame fr = make_frame(si.ns);
-                V3 wi = to_local(fr, -d);
-                // ---- emitter sampling (next-event estimation) + shadow ray
-#ifdef PBRT_ABLATE_NEE  // diagnostic builds only (tools/ablate.sh): never defined in the shipped library
-                if (false) {
+    Hit h;
+    if (HAVE_HIT) h = *h_in;
+    if (HAVE_HIT || scene_intersect<ACCEL, false>(a.sc, ls, o, d, tmax, &h)) {
+        did_seg = true;
+        const pbrt_prim &P = tb.prims_by_slot[h.slot];
+        const SI si = make_si<ACCEL != ACCEL_K_BRUTE>(P, o, d, h.t, h.u, h.v, a.sc.vnormals, h.slot);
+        survive = shade_step(
+            a, tb, depth, ka, kb, h.t, P, si, o, d, thr, L, eta, prev_pdf,
+            [&](V3 so, V3 sdir, float smax) {
+                did_shadow = true;
+#ifdef PBRT_ABLATE_SHADOW  // diagnostic builds only (tools/ablate.sh)
+                return smax > 0.0f;
 #else
-                if (M.type == PBRT_MAT_DIFFUSE && nE > 0) {
+                Hit hs;
+                return !scene_intersect<ACCEL, true, true>(a.sc, ls, so, sdir, smax, &hs);
 #endif
-                    F4 u = rng4(ka, kb, 1 + 2 * depth, a.seed);
-                    ESample es = sample_emitter(tb, si.p, u);
-                    if (es.valid) {
-                        V3 wo = to_local(fr, es.d);
-                        V3 f;
-                        float bpdf;
-                        bsdf_eval_pdf(M, wi, wo, &f, &bpdf);
-                        if (bpdf > 0.0f) {
-                            V3 so = offset_origin(si.p, si.n, es.d);
-                            V3 sv = es.q - so;
-                            float sd = sqrtf(dot(sv, sv));
-                            V3 sdir = sv * rcp_rn(sd);  // the reciprocal of a sqrtf result
-                            did_shadow = true;
-                            Hit hs;
-#ifdef PBRT_ABLATE_SHADOW
-                            if (sd > 0.0f) {
-#else
-                            if (!scene_intersect<ACCEL, true, true>(a.sc, ls, so, sdir, sd * (1.0f - K_SHADOW_EPS), &hs)) {
-#endif
-                                float mis = es.delta ? 1.0f : mis_weight(es.pdf, bpdf);
-                                L = {fma_(thr.x * f.x, es.weight.x * mis, L.x), fma_(thr.y * f.y, es.weight.y * mis, L.y),
-                                     fma_(thr.z * f.z, es.weight.z * mis, L.z)};
-                            }
-                        }
-                    }
-                }
-                // ---- BSDF sampling, continuation ray, Russian roulette
-                F4 ub = rng4(ka, kb, 2 + 2 * depth, a.seed);
-                BSample bs = bsdf_sample(M, PBRT_USQ_REFERENCE, wi, si.n, si.ns, fr, ub.x, ub.y, ub.z);
-                if (bs.valid) {
-                    thr = thr * bs.weight;
-                    eta *= bs.eta;
-                    V3 nd = to_world(fr, bs.wo);
-                    if (M.type == PBRT_MAT_ULTRA) nd = normalize(nd);
-                    o = offset_origin(si.p, si.n, nd);
-                    d = nd;
-                    prev_pdf = bs.delta ? -1.0f : bs.pdf;
-                    float tm = max3(thr);
-                    survive = true;
-                    if (depth + 1 >= a.rr_depth) {
-                        float q = fminf(tm * eta * eta, 0.95f);
-                        float rq = 1.0f / q;
-                        thr = thr * rq;
-                        if (!(ub.w < q)) survive = false;
-                    }
-                    if (tm == 0.0f) survive = false;
-                }
-            }
-        }
-        if (!survive) {
-            // one 16-byte record per finished path: three 4-byte row stores at a scattered `home` cost three
-            // 32-byte HBM sectors (measured: k_bounce WRITE_SIZE 1.23 x algorithmic), one dwordx4 store costs one
-            typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-            const u32x4 rec = {__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u};
-            __builtin_amdgcn_raw_buffer_store_b128(rec, r_L, home * 16u, 0, 0);
-        }
+            },
+            [&](V3 A, V3 B) { L = {fma_(A.x, B.x, L.x), fma_(A.y, B.y, L.y), fma_(A.z, B.z, L.z)}; });
+    }
+    if (!survive) {
+        // one 16-byte record per finished path: three 4-byte row stores at a scattered `home` cost three
+        // 32-byte HBM sectors (measured: k_bounce WRITE_SIZE 1.23 x algorithmic), one dwordx4 store costs one
+        typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
+        const u32x4 rec = {__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u};
+        __builtin_amdgcn_raw_buffer_store_b128(rec, r_L, home * 16u, 0, 0);
+    }
     return survive;
 }
 

@@ -164,6 +164,168 @@ __host__ __device__ constexpr uint32_t us_owners_per_region(int accel) {
     return rad_wave_private(accel) ? seg_threads(accel) / 64 : 1;
 }
 
+// ---- the pieces of one ultrasound bounce that the launch structures share --------------------------------------------------------
+// k_us_bounce (fused: the occlusion ray is traced in the kernel), kernels_us_wavefront.h k_us_shade (streams: it is handed out and
+// the echo waits for its visibility) and k_us_first (the first-bounce tables) deposit the same echoes because they run THESE
+// statements; the hit, the path state, compaction and statistics belong to the launch structures.
+
+// The launch-uniform floats of the bounce are read from LDS (broadcast ds_read) instead of living in SGPRs: the kernel wants
+// more scalars than the 102 it has and spills them into VGPR lanes (v_writelane / v_readlane).  Staging these 23 took the
+// SGPR spills 105 -> 73 and config 3 14.16 -> 13.85 ms; staging the integer uniforms as well (64 spills) was slower, 13.92 ms.
+// Slots of `__shared__ float uni[U_COUNT]` (U_M: the 12 floats of sensor_to_world, U_TN: the 3 of the transducer normal):
+enum {
+    U_M = 0, U_TN = 12, U_AM = 15, U_AC = 16, U_COSMIN = 17, U_KATT = 18, U_2PIF = 19, U_INVC = 20, U_FS = 21, U_MAXLEN = 22,
+    U_COUNT = 24
+};
+DEV void us_stage_uniforms(const UsArgs &a, float *uni) {  // the caller's next barrier publishes them
+    if (threadIdx.x < 12) uni[threadIdx.x] = a.p.sensor_to_world[threadIdx.x];
+    if (threadIdx.x == 12) {
+        uni[12] = a.tn[0]; uni[13] = a.tn[1]; uni[14] = a.tn[2]; uni[15] = a.am; uni[16] = a.ac; uni[17] = a.cos_min;
+        uni[18] = a.katt; uni[19] = a.two_pi_f; uni[20] = a.inv_c; uni[21] = a.p.fs; uni[22] = a.p.max_path_len;
+    }
+}
+
+// Echo aggregation: the paths of a workgroup belong to few (angle, element) rays -- at the first bounce to ONE
+// ray whose paths all hit the same point, so 4096 echoes land on <= n_elements channel-buffer words.  Global
+// float atomics on the same word serialise in L2 (measured: 64 % of the kernel).  Echoes are therefore summed
+// in a small LDS table keyed by the channel index (ds_cmpst claims a bin, ds_add_f32 adds); a bin owned by
+// another index falls back to the global atomic; one global atomic per used bin when the workgroup is done.
+// The two arrays of 1 << LOG2 bins are the kernel's (US_AGG_LOG2 / US_AGG_LOG2_EMIT above).
+template <uint32_t BINS>
+DEV void us_echo_clear(uint32_t (&agg_idx)[BINS], float (&agg_sum)[BINS], uint32_t tid, uint32_t n_threads) {  // the caller's next barrier publishes it
+    for (uint32_t t = tid; t < BINS; t += n_threads) {
+        agg_idx[t] = 0xffffffffu;
+        agg_sum[t] = 0.0f;
+    }
+}
+template <uint32_t BINS>
+DEV void us_echo_deposit(uint32_t (&agg_idx)[BINS], float (&agg_sum)[BINS], float *channel, uint32_t ci, float pressure) {
+#if defined(PBRT_ABLATE_US_DEPOSIT) && PBRT_ABLATE_US_DEPOSIT == 1  // timing probe only (wrong channel buffer): no echo is deposited
+    if (pressure != 12345.0f) return;
+#endif
+#ifdef PBRT_ABLATE_US_AGG  // diagnostic builds only
+    atomicAdd(&channel[ci], pressure);
+#else
+    uint32_t bin = (ci * 2654435761u) >> (32 - ilog2_c(BINS));
+    bool mine = false;
+#pragma unroll
+    for (uint32_t pr = 0; pr < US_AGG_PROBES; ++pr) {  // (a bin owned by another index: the next one, US_AGG_PROBES tries)
+        if (!mine) {
+            const uint32_t owner = atomicCAS(&agg_idx[bin], 0xffffffffu, ci);
+            mine = owner == 0xffffffffu || owner == ci;
+            if (!mine) bin = (bin + 1u) & (BINS - 1u);
+        }
+    }
+    if (mine)
+        __hip_atomic_fetch_add(&agg_sum[bin], pressure, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else
+        atomicAdd(&channel[ci], pressure);
+#endif
+}
+template <uint32_t BINS>
+DEV void us_echo_flush(uint32_t (&agg_idx)[BINS], float (&agg_sum)[BINS], float *channel, uint32_t tid, uint32_t n_threads) {  // after the barrier behind the last deposit
+    for (uint32_t t = tid; t < BINS; t += n_threads) {
+        const uint32_t ci = agg_idx[t];
+        if (ci != 0xffffffffu) atomicAdd(&channel[ci], agg_sum[t]);
+    }
+}
+
+// The connection of the hit point p to receive element recv: direction and length of the occlusion ray (the caller traces it, or
+// hands it out), then the arrival time of the echo.  Two functions with the occlusion ray between them, not one that takes the
+// trace as a callable or computes the time first: either shape costs the k_us_bounce instances at the 80-VGPR budget spilled
+// registers (profiles/shared_bounce_arithmetic.md).  M / inv_c: from LDS (uni) in the bounce kernels, from the arguments in k_us_first.
+struct UsRecv {
+    V3 sec_dir;
+    float dist_recv;
+};
+DEV UsRecv us_receive(const UsArgs &a, const float *M, V3 p, uint32_t recv) {
+    UsRecv r;
+    V3 target = xf_point(M, v3(a.elem_x[recv], 0.0f, 0.0f));                           // :320-321
+    V3 tv = target - p;
+    r.dist_recv = sqrtf(dot(tv, tv));
+    r.sec_dir = tv * (1.0f / r.dist_recv);                                             // :322
+    return r;
+}
+DEV float us_arrival(const UsArgs &a, float inv_c, uint32_t quirks, uint32_t ray_id, float tof, float distance, float dist_recv) {
+    float tof_hit = (quirks & PBRT_USQ_NO_TOF_ACCUM) ? tof + distance * inv_c : tof;
+    return a.tx[ray_id] + tof_hit + dist_recv * inv_c;                                 // :329
+}
+// ... whether its echo lands in the channel buffer (visible, inside the time window), and the word it lands on.
+// NE / T: n_elements / time_samples as the caller holds them (read once per kernel: inside the bounce loop they cost scalar registers)
+DEV bool us_echo_bin(uint32_t NE, uint32_t T, uint32_t quirks, float total_time, float fs, uint32_t ang, uint32_t recv, bool visible,
+                     uint32_t *ci) {
+    float tf = rintf(total_time * fs);                                                 // :351-352
+    if (quirks & PBRT_USQ_CLAMP_TIME) tf = fminf(fmaxf(tf, 0.0f), (float)(T - 1));
+    if (!(tf >= 0.0f && tf < (float)T && visible)) return false;                       // :353
+    *ci = (ang * NE + recv) * T + (uint32_t)tf;                                        // :354 (host checks it fits 32 bits)
+    return true;
+}
+// ... and the echo's weight and carrier.  Apart from the bin: the bounce kernels evaluate them only where an echo is deposited --
+// acosf and sinf are a tenth of the bounce, and e.g. every second bounce of the Sphere_Box phantom runs inside the sphere, unseen
+DEV void us_echo_weight(const UsArgs &a, uint32_t NE, uint32_t quirks, V3 d, V3 ns, V3 sec_dir, V3 tn, float am, float ac, float phase,
+                        float *fd, float *carrier) {
+    float w_o = dot(d, ns) / (float)(a.p.n_angles * NE);                               // :286-287,345 (si.sh_frame.n)
+#if defined(PBRT_ABLATE_US_DEPOSIT) && PBRT_ABLATE_US_DEPOSIT == 2  // timing probe only: the deposit stays, its weight is 1
+    *fd = w_o;
+    *carrier = phase * 1e-9f;
+#else
+    *fd = directivity_weight_i(sec_dir, tn, am, ac) * w_o;                             // :345
+    // f-3 pulse model: plain amplitude here, the carrier is applied by k_apply_pulse afterwards
+    *carrier = (quirks & PBRT_USQ_NO_CARRIER) ? 1.0f : sinf(phase);
+#endif
+}
+
+// The scatter step: attenuation over the segment, shading frame, UltraBSDF / BSDF sample, amplitude, -- echo() --, continuation
+// ray, Russian roulette, termination.  echo() is the caller's (the echo of this bounce with the updated amp and atten and the
+// incoming d: deposited, or left pending).  quirks: a compile-time constant where the caller has one.  CONES / CYL: as make_si.
+// Returns whether the path goes on.
+template <bool CONES, bool CYL, class Echo>
+DEV bool us_scatter_step(const UsArgs &a, const float *uni, uint32_t quirks, const pbrt_material *mats, const pbrt_prim &P, const SI &si,
+                         float distance, const F4 &u, uint32_t ray_id, uint32_t k, uint32_t block, uint32_t depth, V3 tn, V3 &o, V3 &d,
+                         float &amp, float &atten, float geo_len, Echo &&echo) {
+    atten *= expf(uni[U_KATT] * distance / 8.686f);                                    // :328
+    const pbrt_material M = mats[P.material];
+    // si.sh_frame as Mitsuba builds it (from dp_du, not coordinate_system(n)): si.wi, si.to_local, si.to_world
+    const Frame fr = make_sh_frame(si.ns, si_dp_du<CONES, CYL>(P, si));
+    V3 wi = to_local(fr, -d);                                                          // si.wi (CustomBSDF.py:90)
+    float a_resp, bpdf;
+    V3 new_dir;
+    bool ok = true;
+    if (M.type == PBRT_MAT_ULTRA) {
+        // intent arithmetic (no diagonal broadcast, A2 off): the micro-normal's second variate comes from a second
+        // block of the path's stream -- u.w also decides the roulette below and must not steer the facet as well
+        const float s1b = (quirks & PBRT_USQ_DIAG_SAMPLE) ? u.w : rng4(ray_id, k, block | 0x40000000u, a.seed).x;
+        UltraOut uo = ultra_core(M, quirks, wi, si.n, si.ns, u.y, u.z, s1b);           // :338
+        a_resp = uo.amp;
+        bpdf = uo.pdf;
+        new_dir = to_world(fr, to_local(fr, uo.chosen));                               // CustomBSDF.py:165 + :358
+    } else {
+        BSample bs = bsdf_sample(M, quirks, wi, si.n, si.ns, fr, u.y, u.z, u.w);
+        ok = bs.valid;
+        a_resp = bs.weight.x;
+        bpdf = bs.pdf;
+        new_dir = to_world(fr, bs.wo);
+    }
+    if (!ok) return false;
+    float cos_theta = dot(si.ns, -d);                                                  // :340 (si.sh_frame.n)
+    amp *= a_resp * cos_theta * fmaxf(bpdf, 1e-6f);                                    // :341
+    echo();                                                                            // :345-354
+    d = normalize(new_dir);                                                            // :358-359
+    o = offset_origin(si.p, si.n, d);
+    bool surv;
+    if (quirks & PBRT_USQ_SIGNED_RR) {                                                 // Dr.Jit variant :219-224
+        const float rr_prob = fminf(atten * amp, 1.0f);
+        surv = u.w < rr_prob;
+        atten = surv ? atten / rr_prob : 0.0f;
+    } else {
+        const float rr_prob = fminf(fabsf(atten * amp), 1.0f);                         // :364
+        surv = !(u.w > rr_prob);                                                       // :365-366
+        atten /= rr_prob;                                                              // :367
+    }
+    bool within = dot(d, tn) >= uni[U_COSMIN];                                         // :371
+    return within && (geo_len < uni[U_MAXLEN]) && (depth + 1 < a.p.max_depth) && surv;  // :372-376
+}
+
 // EMIT: the instances of PBRT_US_PRIMARY_EMITTER -- the first bounce draws every path's primary ray from CustomEmitter.sample_ray,
 // every echo is multiplied by the ray's weight; instances of their own so that the deterministic-ray kernels keep their register
 // allocation (they sit at the 6-wave budget).
@@ -217,37 +379,12 @@ __global__ __launch_bounds__(seg_threads(ACCEL), us_waves_per_eu(ACCEL)) void k_
     if (ACCEL == ACCEL_K_BVH_LDS) ls.tree = stage_tree_lds(a.sc, dyn_lds);
     __shared__ uint32_t tab_lds[ACCEL == ACCEL_K_BRUTE ? TAB_DW : 1];
     const Tables tb = make_tables<ACCEL>(a.sc, ls, tab_lds);
-    // Echo aggregation: the paths of a workgroup belong to few (angle, element) rays -- at the first bounce to ONE
-    // ray whose paths all hit the same point, so 4096 echoes land on <= n_elements channel-buffer words.  Global
-    // float atomics on the same word serialise in L2 (measured: 64 % of the kernel).  Echoes are therefore summed
-    // in a small LDS table keyed by the channel index (ds_cmpst claims a bin, ds_add_f32 adds); a bin owned by
-    // another index falls back to the global atomic; one global atomic per used bin when the workgroup is done.
-    constexpr uint32_t AGG_LOG2 = EMIT ? US_AGG_LOG2_EMIT : US_AGG_LOG2, AGG_BINS = 1u << AGG_LOG2;
-    __shared__ uint32_t agg_idx[AGG_BINS];
-    __shared__ float agg_sum[AGG_BINS];
-    for (uint32_t t = threadIdx.x; t < AGG_BINS; t += blockDim.x) {
-        agg_idx[t] = 0xffffffffu;
-        agg_sum[t] = 0.0f;
-    }
-    // the launch-uniform floats of the bounce are read from LDS (broadcast ds_read) instead of living in SGPRs: the kernel wants
-    // more scalars than the 102 it has and spills them into VGPR lanes (v_writelane / v_readlane).  Staging these 23 took the
-    // SGPR spills 105 -> 73 and config 3 14.16 -> 13.85 ms; staging the integer uniforms as well (64 spills) was slower, 13.92 ms.
-    __shared__ float uni[24];
-    if (threadIdx.x < 12) uni[threadIdx.x] = a.p.sensor_to_world[threadIdx.x];
-    if (threadIdx.x == 12) {
-        uni[12] = a.tn[0]; uni[13] = a.tn[1]; uni[14] = a.tn[2]; uni[15] = a.am; uni[16] = a.ac; uni[17] = a.cos_min;
-        uni[18] = a.katt; uni[19] = a.two_pi_f; uni[20] = a.inv_c; uni[21] = a.p.fs; uni[22] = a.p.max_path_len;
-    }
-#define U_M uni
-#define U_TN(k) uni[12 + (k)]
-#define U_AM uni[15]
-#define U_AC uni[16]
-#define U_COSMIN uni[17]
-#define U_KATT uni[18]
-#define U_2PIF uni[19]
-#define U_INVC uni[20]
-#define U_FS uni[21]
-#define U_MAXLEN uni[22]
+    constexpr uint32_t AGG_LOG2 = EMIT ? US_AGG_LOG2_EMIT : US_AGG_LOG2;
+    __shared__ uint32_t agg_idx[1u << AGG_LOG2];
+    __shared__ float agg_sum[1u << AGG_LOG2];
+    us_echo_clear(agg_idx, agg_sum, threadIdx.x, blockDim.x);
+    __shared__ float uni[U_COUNT];
+    us_stage_uniforms(a, uni);
     if (ACCEL == ACCEL_K_BRUTE)
         fill_tables_lds(a.sc, tab_lds, blockDim.x);  // ends with the barrier that also publishes the empty bins
     else
@@ -295,13 +432,13 @@ __global__ __launch_bounds__(seg_threads(ACCEL), us_waves_per_eu(ACCEL)) void k_
             ray_id = udiv_fast(home, a.div_ppr);
             k = a.path_first + (home - ray_id * a.ppr_pass);
             const uint32_t ang = udiv_fast(ray_id, a.div_ne), el = ray_id - ang * NE;
-            o = xf_point(U_M, v3(a.elem_x[el], 0.0f, 0.0f));           // :270,273
+            o = xf_point(uni, v3(a.elem_x[el], 0.0f, 0.0f));           // :270,273
             d = v3(a.dir0[3 * ang], a.dir0[3 * ang + 1], a.dir0[3 * ang + 2]);         // :271,273
             amp = 1.0f;
             atten = 1.0f;
             tof = 0.0f;
             geo_len = 0.0f;                                                            // :276-279
-            if (EMIT) w_ray = us_emitter_primary(a.p, U_M, ray_id, k, ang, el, a.seed, &o, &d, &tof);  // (a.tx is all zero then)
+            if (EMIT) w_ray = us_emitter_primary(a.p, uni, ray_id, k, ang, el, a.seed, &o, &d, &tof);  // (a.tx is all zero then)
         } else {
             const uint32_t v4 = us_state_voff(slot, ROWS);
             constexpr uint32_t row = STATE_ROW_BYTES;
@@ -317,7 +454,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), us_waves_per_eu(ACCEL)) void k_
             k = a.path_first + (home - ray_id * a.ppr_pass);
         }
         const uint32_t ang = udiv_fast(ray_id, a.div_ne);
-        const V3 tn = {U_TN(0), U_TN(1), U_TN(2)};
+        const V3 tn = {uni[U_TN], uni[U_TN + 1], uni[U_TN + 2]};
         Hit h;
         bool hit;
         if (first && have_hit_tab) {  // shared first hit of the ray (k_us_first)
@@ -337,121 +474,43 @@ __global__ __launch_bounds__(seg_threads(ACCEL), us_waves_per_eu(ACCEL)) void k_
             SI si = make_si<ACCEL != ACCEL_K_BRUTE>(P, o, d, h.t, h.u, h.v, a.sc.vnormals, h.slot);
             const float distance = h.t;                                                // :314
             geo_len += distance;                                                       // :315
-            const bool no_acc = (quirks & PBRT_USQ_NO_TOF_ACCUM) != 0;
-            if (!no_acc) tof += distance * U_INVC;                                    // :316
+            if (!(quirks & PBRT_USQ_NO_TOF_ACCUM)) tof += distance * uni[U_INVC];       // :316
             // B1 (Dr.Jit variant): the draws are constants of the traced loop body -- every bounce reuses block 0
             const uint32_t block = (quirks & PBRT_USQ_FROZEN_DRAWS) ? 0u : depth;
             F4 u = rng4(ray_id, k, block, a.seed);
             uint32_t recv = min((uint32_t)(u.x * (float)NE), NE - 1);                  // :319
             const bool tab = first && have_rx_tab;  // (ray, receive element) record of k_us_first
             float4 rx = {0.0f, 0.0f, 0.0f, 0.0f};
-            V3 sec_dir = {0.0f, 0.0f, 0.0f};
+            UsRecv rc = {{0.0f, 0.0f, 0.0f}, 0.0f};
             bool visible = false;
             float total_time = 0.0f, phase = 0.0f;
             if (tab) {
                 rx = a.first_rx[(size_t)ray_id * NE + recv];
             } else {
-                V3 target = xf_point(U_M, v3(a.elem_x[recv], 0.0f, 0.0f)); // :320-321
-                V3 tv = target - si.p;
-                float dist_recv = sqrtf(dot(tv, tv));
-                sec_dir = tv * (1.0f / dist_recv);                                     // :322
+                rc = us_receive(a, uni, si.p, recv);
                 Hit hs;
-                visible = !scene_intersect<ACCEL, true>(a.sc, ls, offset_origin(si.p, si.n, sec_dir), sec_dir, K_INF,
-                                                        &hs);                           // :324-325
-                float tof_hit = no_acc ? tof + distance * U_INVC : tof;
-                total_time = a.tx[ray_id] + tof_hit + dist_recv * U_INVC;             // :329
-                phase = U_2PIF * total_time;                                       // :330
+                visible = !scene_intersect<ACCEL, true>(a.sc, ls, offset_origin(si.p, si.n, rc.sec_dir), rc.sec_dir, K_INF, &hs);  // :324-325
+                total_time = us_arrival(a, uni[U_INVC], quirks, ray_id, tof, distance, rc.dist_recv);
+                phase = uni[U_2PIF] * total_time;                                      // :330
             }
-            atten *= expf(U_KATT * distance / 8.686f);                                 // :328
-            const pbrt_material M = tb.mats[P.material];
-            // si.sh_frame as Mitsuba builds it (from dp_du, not coordinate_system(n)): si.wi, si.to_local, si.to_world
-            const Frame fr = make_sh_frame(si.ns, si_dp_du<ACCEL != ACCEL_K_BRUTE>(P, si));
-            V3 wi = to_local(fr, -d);                                                  // si.wi (CustomBSDF.py:90)
-            float a_resp, bpdf;
-            V3 new_dir;
-            bool ok = true;
-            if (M.type == PBRT_MAT_ULTRA) {
-                // intent arithmetic (no diagonal broadcast, A2 off): the micro-normal's second variate comes from a second
-                // block of the path's stream -- u.w also decides the roulette below and must not steer the facet as well
-                const float s1b = (quirks & PBRT_USQ_DIAG_SAMPLE) ? u.w : rng4(ray_id, k, block | 0x40000000u, a.seed).x;
-                UltraOut uo = ultra_core(M, quirks, wi, si.n, si.ns, u.y, u.z, s1b); // :338
-                a_resp = uo.amp;
-                bpdf = uo.pdf;
-                new_dir = to_world(fr, to_local(fr, uo.chosen));                       // CustomBSDF.py:165 + :358
-            } else {
-                BSample bs = bsdf_sample(M, quirks, wi, si.n, si.ns, fr, u.y, u.z, u.w);
-                ok = bs.valid;
-                a_resp = bs.weight.x;
-                bpdf = bs.pdf;
-                new_dir = to_world(fr, bs.wo);
-            }
-            if (ok) {
-                float cos_theta = dot(si.ns, -d);                                      // :340 (si.sh_frame.n)
-                amp *= a_resp * cos_theta * fmaxf(bpdf, 1e-6f);                        // :341
+            constexpr bool CONES = ACCEL != ACCEL_K_BRUTE;
+            survive = us_scatter_step<CONES, CONES>(a, uni, quirks, tb.mats, P, si, distance, u, ray_id, k, block, depth, tn, o, d, amp, atten,
+                                                    geo_len, [&] {
                 float fd = 0.0f, carrier = 0.0f;
                 uint32_t ci = 0xffffffffu;
                 if (tab) {
                     fd = rx.x;
                     carrier = rx.y;
                     ci = __float_as_uint(rx.z);
-                } else {
-                    float tf = rintf(total_time * U_FS);                             // :351-352
-                    if (quirks & PBRT_USQ_CLAMP_TIME) tf = fminf(fmaxf(tf, 0.0f), (float)(T - 1));
-                    if (tf >= 0.0f && tf < (float)T && visible) {                      // :353
-                        ci = (ang * NE + recv) * T + (uint32_t)tf;                     // :354 (host checks it fits 32 bits)
-                        // the echo's weight and carrier only where an echo is deposited: acosf and sinf are a tenth of the
-                        // bounce, and e.g. every second bounce of the Sphere_Box phantom runs inside the sphere, unseen
-                        float w_o = dot(d, si.ns) / (float)(a.p.n_angles * NE);        // :286-287,345 (si.sh_frame.n)
-#if defined(PBRT_ABLATE_US_DEPOSIT) && PBRT_ABLATE_US_DEPOSIT == 2
-                        fd = w_o;
-                        carrier = phase * 1e-9f;
-#else
-                        fd = directivity_weight_i(sec_dir, tn, U_AM, U_AC) * w_o;      // :345
-                        // f-3 pulse model: plain amplitude here, the carrier is applied by k_apply_pulse afterwards
-                        carrier = (quirks & PBRT_USQ_NO_CARRIER) ? 1.0f : sinf(phase);
-#endif
-                    }
+                } else if (us_echo_bin(NE, T, quirks, total_time, uni[U_FS], ang, recv, visible, &ci)) {
+                    us_echo_weight(a, NE, quirks, d, si.ns, rc.sec_dir, tn, uni[U_AM], uni[U_AC], phase, &fd, &carrier);
                 }
                 float pressure = atten * amp * fd * carrier;                           // :348
-#ifdef PBRT_ABLATE_US_DEPOSIT  // timing probe only (wrong channel buffer): no echo is deposited; =2: the deposit stays, its weight is 1
-                if (PBRT_ABLATE_US_DEPOSIT == 1) ci = pressure != 12345.0f ? 0xffffffffu : ci;
-#endif
                 if (ci != 0xffffffffu) {
                     if (EMIT) pressure *= w_ray;  // the weight of the path's primary ray (DESIGN D15)
-#ifdef PBRT_ABLATE_US_AGG  // diagnostic builds only
-                    atomicAdd(&a.channel[ci], pressure);
-#else
-                    uint32_t bin = (ci * 2654435761u) >> (32 - AGG_LOG2);
-                    bool mine = false;
-#pragma unroll
-                    for (uint32_t pr = 0; pr < US_AGG_PROBES; ++pr) {  // (a bin owned by another index: the next one, US_AGG_PROBES tries)
-                        if (!mine) {
-                            const uint32_t owner = atomicCAS(&agg_idx[bin], 0xffffffffu, ci);
-                            mine = owner == 0xffffffffu || owner == ci;
-                            if (!mine) bin = (bin + 1u) & (AGG_BINS - 1u);
-                        }
-                    }
-                    if (mine)
-                        __hip_atomic_fetch_add(&agg_sum[bin], pressure, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    else
-                        atomicAdd(&a.channel[ci], pressure);
-#endif
+                    us_echo_deposit(agg_idx, agg_sum, a.channel, ci, pressure);
                 }
-                d = normalize(new_dir);                                                // :358-359
-                o = offset_origin(si.p, si.n, d);
-                bool surv;
-                if (quirks & PBRT_USQ_SIGNED_RR) {                                 // Dr.Jit variant :219-224
-                    const float rr_prob = fminf(atten * amp, 1.0f);
-                    surv = u.w < rr_prob;
-                    atten = surv ? atten / rr_prob : 0.0f;
-                } else {
-                    const float rr_prob = fminf(fabsf(atten * amp), 1.0f);             // :364
-                    surv = !(u.w > rr_prob);                                           // :365-366
-                    atten /= rr_prob;                                                  // :367
-                }
-                bool within = dot(d, tn) >= U_COSMIN;                                 // :371
-                survive = within && (geo_len < U_MAXLEN) && (depth + 1 < a.p.max_depth) && surv;  // :372-376
-            }
+            });
         }
     }
     const uint32_t wid = tid >> 6;
@@ -514,22 +573,9 @@ __global__ __launch_bounds__(seg_threads(ACCEL), us_waves_per_eu(ACCEL)) void k_
     ++depth;
     }  // bounce loop
     __syncthreads();  // all echoes of the workgroup are in the bins
-    for (uint32_t t = tid; t < AGG_BINS; t += SEG) {
-        const uint32_t ci = agg_idx[t];
-        if (ci != 0xffffffffu) atomicAdd(&a.channel[ci], agg_sum[t]);
-    }
+    us_echo_flush(agg_idx, agg_sum, a.channel, tid, SEG);
     if (WP ? (tid & 63u) == 0 : tid == 0) a.seg_out[own] = out_off;
 }
-#undef U_M
-#undef U_TN
-#undef U_AM
-#undef U_AC
-#undef U_COSMIN
-#undef U_KATT
-#undef U_2PIF
-#undef U_INVC
-#undef U_FS
-#undef U_MAXLEN
 
 // PBRT_US_PRIMARY_EMITTER, brute-force scenes, PBRT_US_EMIT_FUSED=0: the primary rays of a pass written into the (twelve-row) path
 // state, so that k_us_bounce<false, ., EMIT> can walk every bounce from depth 0.  The shipped path draws the ray inside the
@@ -562,7 +608,7 @@ __global__ __launch_bounds__(256) void k_us_emit_init(const UsArgs a, uint32_t r
 }
 
 // First-bounce tables, one thread per (ray, receive element): the primary ray, its closest hit, and the occlusion test
-// towards the element -- the statements of k_us_bounce<FIRST> up to `visible`, once instead of once per path.
+// towards the element -- what k_us_bounce<FIRST> does up to `visible` (us_receive .. us_echo_weight), once instead of once per path.
 // ACCEL: ACCEL_K_BRUTE_BIG or ACCEL_K_BVH_GLOBAL (no LDS image needed for n_rays * n_elements rays; same primitive
 // order / same tree, so the same hit).
 template <int ACCEL>
@@ -585,29 +631,21 @@ __global__ __launch_bounds__(256) void k_us_first(const UsArgs a, uint32_t n_ray
     }
     float4 rx = {0.0f, 0.0f, __uint_as_float(0xffffffffu), 0.0f};
     if (hit) {
-        const uint32_t T = a.p.time_samples;
         const V3 tn = {a.tn[0], a.tn[1], a.tn[2]};
         const pbrt_prim &P = a.sc.prims[h.slot];
         SI si = make_si(P, o, d, h.t, h.u, h.v, a.sc.vnormals, h.slot);
         const float distance = h.t;                                                      // :314
-        const bool no_acc = (a.p.quirks & PBRT_USQ_NO_TOF_ACCUM) != 0;
         float tof = 0.0f;                                                                // :278
-        if (!no_acc) tof += distance * a.inv_c;                                          // :316
-        V3 target = xf_point(a.p.sensor_to_world, v3(a.elem_x[recv], 0.0f, 0.0f));       // :320-321
-        V3 tv = target - si.p;
-        float dist_recv = sqrtf(dot(tv, tv));
-        V3 sec_dir = tv * (1.0f / dist_recv);                                            // :322
+        if (!(a.p.quirks & PBRT_USQ_NO_TOF_ACCUM)) tof += distance * a.inv_c;            // :316
+        const UsRecv rc = us_receive(a, a.p.sensor_to_world, si.p, recv);
         Hit hs;
-        const bool visible = !scene_intersect<ACCEL, true>(a.sc, ls, offset_origin(si.p, si.n, sec_dir), sec_dir, K_INF, &hs);
-        float tof_hit = no_acc ? tof + distance * a.inv_c : tof;
-        float total_time = a.tx[ray_id] + tof_hit + dist_recv * a.inv_c;                 // :329
-        float phase = a.two_pi_f * total_time;                                           // :330
-        float w_o = dot(d, si.ns) / (float)(a.p.n_angles * NE);                          // :286-287,345 (si.sh_frame.n)
-        rx.x = directivity_weight_i(sec_dir, tn, a.am, a.ac) * w_o;                      // :345
-        rx.y = (a.p.quirks & PBRT_USQ_NO_CARRIER) ? 1.0f : sinf(phase);
-        float tf = rintf(total_time * a.p.fs);                                           // :351-352
-        if (a.p.quirks & PBRT_USQ_CLAMP_TIME) tf = fminf(fmaxf(tf, 0.0f), (float)(T - 1));
-        if (tf >= 0.0f && tf < (float)T && visible) rx.z = __uint_as_float((ang * NE + recv) * T + (uint32_t)tf);  // :353-354
+        const bool visible = !scene_intersect<ACCEL, true>(a.sc, ls, offset_origin(si.p, si.n, rc.sec_dir), rc.sec_dir, K_INF, &hs);
+        const float total_time = us_arrival(a, a.inv_c, a.p.quirks, ray_id, tof, distance, rc.dist_recv);
+        const float phase = a.two_pi_f * total_time;                                     // :330
+        us_echo_weight(a, NE, a.p.quirks, d, si.ns, rc.sec_dir, tn, a.am, a.ac, phase, &rx.x, &rx.y);
+        uint32_t ci = 0xffffffffu;
+        us_echo_bin(NE, a.p.time_samples, a.p.quirks, total_time, a.p.fs, ang, recv, visible, &ci);
+        rx.z = __uint_as_float(ci);
     }
     first_rx[i] = rx;
 }

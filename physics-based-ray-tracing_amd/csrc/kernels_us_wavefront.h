@@ -7,7 +7,7 @@
 //   k_trace      unchanged: the continuation rays of the live paths (closest hit) and the occlusion rays the previous bounce
 //                emitted (any hit, unbounded), 64 VGPRs, eight waves per SIMD
 //   k_us_shade   every wave on its own: paths whose ray left the scene end, the others are listed and shaded 64 at a time --
-//                the statements of k_us_bounce from the hit on (:314-376) -- except that the occlusion ray is handed out instead of
+//                the bounce from the hit on (:314-376; kernels_us.h us_receive .. us_scatter_step) -- the occlusion ray is handed out instead of
 //                traced: the echo (channel index, pressure) rides in the path state as PENDING and is deposited by the next
 //                k_us_shade once k_trace has written its visibility (a path that ended meanwhile leaves a record of its own).
 //                A flush (k_trace + k_us_shade on the records alone) follows the last bounce.
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
     __shared__ uint32_t q_out, q_shd, q_dead, q_done;
     __shared__ uint32_t agg_idx[US_AGG_BINS];
     __shared__ float agg_sum[US_AGG_BINS];
-    __shared__ float uni[24];
+    __shared__ float uni[U_COUNT];
     const uint32_t r = w.region0 + xcd_swizzle(blockIdx.x, gridDim.x), base = r * WF_REGION;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
     const uint32_t cnt_in = TAB ? (a.n_paths > base ? min(a.n_paths - base, WF_REGION) : 0u) : w.seg_in[r];
@@ -87,32 +87,15 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
         q_dead = 0;
         q_done = 0;
     }
-    for (uint32_t t = tid; t < US_AGG_BINS; t += T_) {
-        agg_idx[t] = 0xffffffffu;
-        agg_sum[t] = 0.0f;
-    }
-    // the launch-uniform floats through LDS (broadcast reads), as in k_us_bounce: the kernel wants more scalars than a wave has
-    if (tid < 12) uni[tid] = a.p.sensor_to_world[tid];
-    if (tid == 12) {
-        uni[12] = a.tn[0]; uni[13] = a.tn[1]; uni[14] = a.tn[2]; uni[15] = a.am; uni[16] = a.ac; uni[17] = a.cos_min;
-        uni[18] = a.katt; uni[19] = a.two_pi_f; uni[20] = a.inv_c; uni[21] = a.p.fs; uni[22] = a.p.max_path_len;
-    }
+    us_echo_clear(agg_idx, agg_sum, tid, T_);
+    us_stage_uniforms(a, uni);  // through LDS as in k_us_bounce: the kernel wants more scalars than a wave has
     __syncthreads();
-    // an echo into the workgroup's table (kernels_us.h: ds_cmpst claims a bin, ds_add_f32 adds, foreign bins go to the global atomic)
-    auto deposit = [&](uint32_t ci, float pressure) {
-        const uint32_t bin = (ci * 2654435761u) >> (32 - US_AGG_LOG2);
-        const uint32_t owner = atomicCAS(&agg_idx[bin], 0xffffffffu, ci);
-        if (owner == 0xffffffffu || owner == ci)
-            __hip_atomic_fetch_add(&agg_sum[bin], pressure, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        else
-            atomicAdd(&a.channel[ci], pressure);
-    };
     const uint32_t NE = a.p.n_elements, T = a.p.time_samples;
     const size_t cp = a.cap;
     // ---- occlusion rays of paths that ended at the previous bounce: their echo, if the ray got through
     for (uint32_t k = tid; k < n_dead; k += T_) {
         const float4 rec = w.shd_in[2u * cp + (base + WF_REGION - n_dead + k)];
-        if (rec.w != 0.0f) deposit(__float_as_uint(rec.y), rec.x);
+        if (rec.w != 0.0f) us_echo_deposit(agg_idx, agg_sum, a.channel, __float_as_uint(rec.y), rec.x);
     }
     uint32_t list_n = 0, n_seg_w = 0;
     uint32_t c0 = wid * 64u;
@@ -142,7 +125,8 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
                 const uint32_t s = c0 + (uint32_t)j * (W * 64u) + lane;
                 const uint32_t hid = hidv[j];
                 // the pending echo of the previous bounce (every path, whether it goes on or not)
-                if (!TAB && s < cnt_in && q3v[j].w != 0.0f && __float_as_uint(q2v[j].w) != 0xffffffffu) deposit(__float_as_uint(q2v[j].w), q3v[j].x);
+                if (!TAB && s < cnt_in && q3v[j].w != 0.0f && __float_as_uint(q2v[j].w) != 0xffffffffu)
+                    us_echo_deposit(agg_idx, agg_sum, a.channel, __float_as_uint(q2v[j].w), q3v[j].x);
                 const bool is_hit = hid != 0xffffffffu;
                 const unsigned long long bh = __ballot(is_hit);
                 if (is_hit) {
@@ -158,8 +142,8 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
             break;
         }
         if (list_n < 64u && c0 < cnt_in) continue;
-        // ---- shade 64 listed paths: kernels_us.h k_us_bounce from the hit on, statement for statement (the list is emptied below 64
-        // entries before the wave reads its next chunks)
+        // ---- shade 64 listed paths: the bounce from the hit on, through the pieces of kernels_us.h that k_us_bounce runs (the list is
+        // emptied below 64 entries before the wave reads its next chunks)
         for (;;) {
         const uint32_t take = min(list_n, 64u);
         const bool act = lane < take;
@@ -213,12 +197,11 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
                 if (!prim_hit<CYL>(P, o, d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(w.guard + WF_GUARD_REHIT, 1u);
             }
             const uint32_t depth = a.depth;
-            const V3 tn = {uni[12], uni[13], uni[14]};
-            const SI si = wf_make_si<CYL>(P, o, d, h.t, h.u, h.v, has_vn, vn);
+            const V3 tn = {uni[U_TN], uni[U_TN + 1], uni[U_TN + 2]};
+            const SI si = make_si<true, CYL>(P, o, d, h.t, h.u, h.v, has_vn, [&](int k) { return vn.n[k]; });
             const float distance = h.t;                                                   // :314
             geo_len += distance;                                                          // :315
-            const bool no_acc = (a.p.quirks & PBRT_USQ_NO_TOF_ACCUM) != 0;
-            if (!no_acc) tof += distance * uni[20];                                       // :316
+            if (!(a.p.quirks & PBRT_USQ_NO_TOF_ACCUM)) tof += distance * uni[U_INVC];     // :316
             const uint32_t block = (a.p.quirks & PBRT_USQ_FROZEN_DRAWS) ? 0u : depth;
             const F4 u = rng4(ray_id, k, block, a.seed);
             const uint32_t recv = min((uint32_t)(u.x * (float)NE), NE - 1);               // :319
@@ -226,77 +209,32 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
             if (TAB) {
                 rx = a.first_rx[(size_t)ray_id * NE + recv];
             } else {
-                const V3 target = xf_point(uni, v3(a.elem_x[recv], 0.0f, 0.0f));          // :320-321
-                const V3 tv = target - si.p;
-                const float dist_recv = sqrtf(dot(tv, tv));
-                sdir = tv * (1.0f / dist_recv);                                           // :322
+                const UsRecv rc = us_receive(a, uni, si.p, recv);
+                sdir = rc.sec_dir;
                 so = offset_origin(si.p, si.n, sdir);                                     // :324 (the ray k_trace walks)
-                const float tof_hit = no_acc ? tof + distance * uni[20] : tof;
-                total_time = a.tx[ray_id] + tof_hit + dist_recv * uni[20];                // :329
-                phase = uni[19] * total_time;                                             // :330
+                total_time = us_arrival(a, uni[U_INVC], a.p.quirks, ray_id, tof, distance, rc.dist_recv);
+                phase = uni[U_2PIF] * total_time;                                         // :330
             }
-            atten *= expf(uni[18] * distance / 8.686f);                                   // :328
-            const pbrt_material M = a.sc.mats[P.material];
-            const Frame fr = make_sh_frame(si.ns, si_dp_du<true, CYL>(P, si));
-            const V3 wi = to_local(fr, -d);
-            float a_resp, bpdf;
-            V3 new_dir;
-            bool ok = true;
-            if (M.type == PBRT_MAT_ULTRA) {
-                const float s1b = (a.p.quirks & PBRT_USQ_DIAG_SAMPLE) ? u.w : rng4(ray_id, k, block | 0x40000000u, a.seed).x;
-                const UltraOut uo = ultra_core(M, a.p.quirks, wi, si.n, si.ns, u.y, u.z, s1b);  // :338
-                a_resp = uo.amp;
-                bpdf = uo.pdf;
-                new_dir = to_world(fr, to_local(fr, uo.chosen));                          // CustomBSDF.py:165 + :358
-            } else {
-                const BSample bs = bsdf_sample(M, a.p.quirks, wi, si.n, si.ns, fr, u.y, u.z, u.w);
-                ok = bs.valid;
-                a_resp = bs.weight.x;
-                bpdf = bs.pdf;
-                new_dir = to_world(fr, bs.wo);
-            }
-            if (ok) {
-                const float cos_theta = dot(si.ns, -d);                                   // :340
-                amp *= a_resp * cos_theta * fmaxf(bpdf, 1e-6f);                           // :341
+            survive = us_scatter_step<true, CYL>(a, uni, a.p.quirks, a.sc.mats, P, si, distance, u, ray_id, k, block, depth, tn, o, d, amp, atten,
+                                                 geo_len, [&] {
                 float fd = 0.0f, carrier = 0.0f;
                 if (TAB) {
                     fd = rx.x;
                     carrier = rx.y;
                     ci = __float_as_uint(rx.z);                                           // (visibility included)
-                } else {
-                    float tf = rintf(total_time * uni[21]);                               // :351-352
-                    if (a.p.quirks & PBRT_USQ_CLAMP_TIME) tf = fminf(fmaxf(tf, 0.0f), (float)(T - 1));
-                    if (tf >= 0.0f && tf < (float)T) {                                    // :353, `visible` comes from k_trace
-                        ci = (ang * NE + recv) * T + (uint32_t)tf;                        // :354
-                        const float w_o = dot(d, si.ns) / (float)(a.p.n_angles * NE);     // :286-287,345
-                        fd = directivity_weight_i(sdir, tn, uni[15], uni[16]) * w_o;      // :345
-                        carrier = (a.p.quirks & PBRT_USQ_NO_CARRIER) ? 1.0f : sinf(phase);
-                    }
+                } else if (us_echo_bin(NE, T, a.p.quirks, total_time, uni[U_FS], ang, recv, true, &ci)) {
+                    us_echo_weight(a, NE, a.p.quirks, d, si.ns, sdir, tn, uni[U_AM], uni[U_AC], phase, &fd, &carrier);
                 }
                 pressure = atten * amp * fd * carrier * w_ray;                            // :348 (x 1, or the emitter ray's weight: D15)
                 if (ci != 0xffffffffu) {
                     if (TAB) {
-                        deposit(ci, pressure);
+                        us_echo_deposit(agg_idx, agg_sum, a.channel, ci, pressure);
                         ci = 0xffffffffu;
                     } else {
                         pend = true;  // an occlusion ray decides
                     }
                 }
-                d = normalize(new_dir);                                                   // :358-359
-                o = offset_origin(si.p, si.n, d);
-                bool surv;
-                if (a.p.quirks & PBRT_USQ_SIGNED_RR) {                                    // Dr.Jit variant :219-224
-                    const float rr_prob = fminf(atten * amp, 1.0f);
-                    surv = u.w < rr_prob;
-                    atten = surv ? atten / rr_prob : 0.0f;
-                } else {
-                    const float rr_prob = fminf(fabsf(atten * amp), 1.0f);                // :364
-                    surv = !(u.w > rr_prob);                                              // :365-366
-                    atten /= rr_prob;                                                     // :367
-                }
-                const bool within = dot(d, tn) >= uni[17];                                // :371
-                survive = within && (geo_len < uni[22]) && (depth + 1 < a.p.max_depth) && surv;  // :372-376
-            }
+            });
         }
         n_seg_w += take;
         // survivors -> front of the region of the `out` state
@@ -361,8 +299,5 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
         }
     }
     __syncthreads();  // all echoes of the workgroup are in the bins (every wave gets here: no exit after the set-up)
-    for (uint32_t t = tid; t < US_AGG_BINS; t += T_) {
-        const uint32_t ci = agg_idx[t];
-        if (ci != 0xffffffffu) atomicAdd(&a.channel[ci], agg_sum[t]);
-    }
+    us_echo_flush(agg_idx, agg_sum, a.channel, tid, T_);
 }

@@ -426,121 +426,6 @@ DEV WfVn wf_load_vn(const float *vn, uint32_t slot) {  // vn != nullptr
     for (int k = 0; k < 9; ++k) o.n[k] = r[k];
     return o;
 }
-// make_si on the preloaded record (same statements as device_scene.h make_si / shading_normal).  CYL = false: the scene has no
-// cylinder and its branch is compiled out (k_shade / k_us_shade keep their registers on every other scene)
-template <bool CYL>
-DEV SI wf_make_si(const pbrt_prim &P, V3 o, V3 d, float t, float u, float v, bool has_vn, const WfVn &vn) {
-    SI si;
-    if (P.type == PBRT_PRIM_SPHERE) {
-        V3 c = g3(P, 0);
-        V3 p = madd(d, t, o);
-        si.n = normalize(p - c);
-        si.p = madd(si.n, P.g[3], c);
-    } else if (P.type == PBRT_PRIM_CONE) {
-        const V3 r0 = g3(P, 0), r1 = g3(P, 4), r2 = g3(P, 8);
-        si.p = madd(d, t, o);
-        V3 no = {0.0f, 0.0f, -1.0f};
-        if (u == 0.0f) {
-            no = {dot(r0, si.p) + P.g[3], dot(r1, si.p) + P.g[7], 1.0f - (dot(r2, si.p) + P.g[11])};
-            if (!(dot(no, no) > 0.0f)) no = {0.0f, 0.0f, 1.0f};  // the apex itself
-        }
-        si.n = normalize(v3(fma_(r0.x, no.x, fma_(r1.x, no.y, r2.x * no.z)), fma_(r0.y, no.x, fma_(r1.y, no.y, r2.y * no.z)),
-                            fma_(r0.z, no.x, fma_(r1.z, no.y, r2.z * no.z))));
-    } else if (CYL && P.type == PBRT_PRIM_CYLINDER) {
-        si.p = madd(d, t, o);
-        si.n = cylinder_normal(P, si.p);
-    } else {
-        si.p = madd(g3(P, 6), v, madd(g3(P, 3), u, g3(P, 0)));
-        si.n = g3(P, 9);
-    }
-    si.ns = si.n;
-    if (has_vn && (P.type == PBRT_PRIM_TRIANGLE || P.type == PBRT_PRIM_PARALLELOGRAM)) {
-        const V3 n0 = {vn.n[0], vn.n[1], vn.n[2]}, n1 = {vn.n[3], vn.n[4], vn.n[5]}, n2 = {vn.n[6], vn.n[7], vn.n[8]};
-        if (dot(n0, n0) + dot(n1, n1) + dot(n2, n2) > 0.0f) {
-            if (P.type == PBRT_PRIM_PARALLELOGRAM) {
-                si.ns = normalize(n0);
-            } else {
-                const float b0 = 1.0f - u - v;
-                si.ns = normalize(madd(n0, b0, madd(n1, u, n2 * v)));
-            }
-        }
-    }
-    return si;
-}
-
-// bounce_step from the shading on, with the shadow ray handed out instead of traced (same statements, same order)
-template <int ACCEL, bool CYL>
-DEV bool wf_shade_step(const WfArgs &a, const Tables &tb, uint32_t depth, uint32_t ka, uint32_t kb, const Hit &h, const pbrt_prim &P,
-                       bool has_vn, const WfVn &vn, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, WfShadow &sh) {
-    bool survive = false;
-    sh.on = false;
-    const uint32_t nE = a.sc.n_emitters;
-    SI si = wf_make_si<CYL>(P, o, d, h.t, h.u, h.v, has_vn, vn);
-    const int32_t emitter = P.emitter;
-    const uint32_t mat_id = P.material;
-    if (emitter >= 0) {
-        const pbrt_emitter &E = tb.emitters[emitter];
-        float cosl = -dot(si.ns, d);
-        if (cosl > 0.0f) {
-            float w = 1.0f;
-            if (prev_pdf >= 0.0f) {
-                float pdf_em = (h.t * h.t) / (cosl * E.area * (float)nE);
-                w = mis_weight(prev_pdf, pdf_em);
-            }
-            L = {fma_(thr.x * E.radiance[0], w, L.x), fma_(thr.y * E.radiance[1], w, L.y), fma_(thr.z * E.radiance[2], w, L.z)};
-        }
-    }
-    if (depth + 1 < a.max_depth) {
-        const pbrt_material M = tb.mats[mat_id];
-        Frame fr = make_frame(si.ns);
-        V3 wi = to_local(fr, -d);
-        if (M.type == PBRT_MAT_DIFFUSE && nE > 0) {
-            F4 u = rng4(ka, kb, 1 + 2 * depth, a.seed);
-            ESample es = sample_emitter(tb, si.p, u);
-            if (es.valid) {
-                V3 wo = to_local(fr, es.d);
-                V3 f;
-                float bpdf;
-                bsdf_eval_pdf(M, wi, wo, &f, &bpdf);
-                if (bpdf > 0.0f) {
-                    V3 so = offset_origin(si.p, si.n, es.d);
-                    V3 sv = es.q - so;
-                    float sd = sqrtf(dot(sv, sv));
-                    V3 sdir = sv * rcp_rn(sd);  // the reciprocal of a sqrtf result
-                    float mis = es.delta ? 1.0f : mis_weight(es.pdf, bpdf);
-                    sh.on = true;
-                    sh.so = so;
-                    sh.sdir = sdir;
-                    sh.tmax = sd * (1.0f - K_SHADOW_EPS);
-                    sh.A = {thr.x * f.x, thr.y * f.y, thr.z * f.z};
-                    sh.B = {es.weight.x * mis, es.weight.y * mis, es.weight.z * mis};
-                }
-            }
-        }
-        F4 ub = rng4(ka, kb, 2 + 2 * depth, a.seed);
-        BSample bs = bsdf_sample(M, PBRT_USQ_REFERENCE, wi, si.n, si.ns, fr, ub.x, ub.y, ub.z);
-        if (bs.valid) {
-            thr = thr * bs.weight;
-            eta *= bs.eta;
-            V3 nd = to_world(fr, bs.wo);
-            if (M.type == PBRT_MAT_ULTRA) nd = normalize(nd);
-            o = offset_origin(si.p, si.n, nd);
-            d = nd;
-            prev_pdf = bs.delta ? -1.0f : bs.pdf;
-            float tm = max3(thr);
-            survive = true;
-            if (depth + 1 >= a.rr_depth) {
-                float q = fminf(tm * eta * eta, 0.95f);
-                float rq = 1.0f / q;
-                thr = thr * rq;
-                if (!(ub.w < q)) survive = false;
-            }
-            if (tm == 0.0f) survive = false;
-        }
-    }
-    return survive;
-}
-
 // LDS copies of the small shading tables of a BVH scene (materials, emitters, and the records of the LIGHT primitives only:
 // the table of all primitives stays in global memory and is read once per hit).  Layout [light prims | mats | emitters | cdf];
 // light_prims becomes the identity, so sample_emitter runs unchanged.  Used when every table has <= TAB_MAX entries.
@@ -726,7 +611,21 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_sha
             h.t = K_INF;
             h.u = h.v = 0.0f;
             if (!prim_hit<CYL>(P, o, d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(a.guard + WF_GUARD_REHIT, 1u);
-            survive = wf_shade_step<ACCEL_K_BVH_GLOBAL, CYL>(a, tb, a.depth, ka, kb, h, P, has_vn, vn, o, d, thr, L, eta, prev_pdf, sh);
+            const SI si = make_si<true, CYL>(P, o, d, h.t, h.u, h.v, has_vn, [&](int k) { return vn.n[k]; });
+            // the bounce's arithmetic (kernels_radiance.h shade_step), its shadow segment handed out instead of traced
+            survive = shade_step(
+                a, tb, a.depth, ka, kb, h.t, P, si, o, d, thr, L, eta, prev_pdf,
+                [&](V3 so, V3 sdir, float smax) {
+                    sh.on = true;
+                    sh.so = so;
+                    sh.sdir = sdir;
+                    sh.tmax = smax;
+                    return true;
+                },
+                [&](V3 A, V3 B) {
+                    sh.A = A;
+                    sh.B = B;
+                });
         }
         n_seg_w += take;
         // survivors -> front of the region of the `out` state
