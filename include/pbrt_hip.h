@@ -81,12 +81,21 @@ typedef struct pbrt_prim {
  * ULTRA       p[0] = impedance, p[1] = roughness, p[2] = medium_z (1.2)
  *                                                        (UltraBSDF, CustomBSDF.py:7-26,105)
  * NONE        absorbs everything
+ * ROUGHCONDUCTOR      p[0] = alpha, p[1..3] = eta (r, g, b), p[4..6] = k (r, g, b): isotropic GGX microfacet conductor with
+ *                     visible-normal sampling (Mitsuba 'roughconductor', distribution 'ggx', sample_visible true).  eta = 0,
+ *                     k = 1 is Mitsuba's material 'none': Fresnel reflectance exactly 1
+ * CONDUCTOR_FRESNEL   p[1..3] = eta, p[4..6] = k: smooth conductor, a delta lobe of weight F(cos theta_i) per channel
+ *                     (Mitsuba 'conductor' given eta / k)
+ * Records of the last two types are checked by pbrt_scene_create / pbrt_scene_update_material / the BSDF leaf operators:
+ * PBRT_E_INVALID unless alpha is finite and > 0 and every eta, k is finite and >= 0.  An alpha below 1e-3 is used as 1e-3.
  */
 #define PBRT_MAT_DIFFUSE 0u
 #define PBRT_MAT_CONDUCTOR 1u
 #define PBRT_MAT_DIELECTRIC 2u
 #define PBRT_MAT_ULTRA 3u
 #define PBRT_MAT_NONE 4u
+#define PBRT_MAT_ROUGHCONDUCTOR 5u
+#define PBRT_MAT_CONDUCTOR_FRESNEL 6u
 
 typedef struct pbrt_material {
     uint32_t type;

@@ -21,7 +21,7 @@ from ._capi import (USQ_CLAMP_TIME, USQ_DIAG_SAMPLE, USQ_DOUBLE_LOCAL, USQ_MIXED
                     default_context, load_library)
 from .plugins import (AreaEmitter, BSDF, BSDFContext, BSDFFlags, BSDFSample3f, ConductorBSDF, CustomEmitter,
                       DielectricBSDF, DiffuseBSDF, DirectIntegrator, DrArray, Emitter, EmitterFlags,
-                      PathIntegrator, PerspectiveSensor, PointEmitter, SamplingIntegrator, Sensor,
+                      PathIntegrator, PerspectiveSensor, PointEmitter, RoughConductorBSDF, SamplingIntegrator, Sensor,
                       SurfaceInteraction3f, UltraBSDF, UltraIntegrator, UltraSensor)
 from .scene import (Film, Object, ParamFlags, ReconstructionFilter, Sampler, Scene, SceneParameters, Shape, load_dict,
                     load_file, register_bsdf, register_emitter, register_film, register_integrator, register_rfilter,

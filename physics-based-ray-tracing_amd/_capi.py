@@ -21,6 +21,7 @@ PBRT_ABI_VERSION = 5
 # primitive / material / emitter / filter / accel enums (include/pbrt_hip.h)
 PRIM_TRIANGLE, PRIM_SPHERE, PRIM_PARALLELOGRAM, PRIM_CONE, PRIM_CYLINDER = 0, 1, 2, 3, 4
 MAT_DIFFUSE, MAT_CONDUCTOR, MAT_DIELECTRIC, MAT_ULTRA, MAT_NONE = 0, 1, 2, 3, 4
+MAT_ROUGHCONDUCTOR, MAT_CONDUCTOR_FRESNEL = 5, 6
 EMIT_AREA, EMIT_POINT = 0, 1
 ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH, ACCEL_BVH_GLOBAL = 0, 1, 2, 3
 FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN = 0, 1, 2

@@ -849,6 +849,52 @@ struct BSample {
     uint32_t lobe;
 };
 
+// ---- rough / Fresnel conductors (D17): Mitsuba's roughconductor with an isotropic GGX distribution and sample_visible = true
+// Smallest alpha the arithmetic is trusted at; smaller values of a record are raised to it
+#define K_GGX_ALPHA_MIN 1e-3f
+// Mitsuba fresnel_conductor(cos_theta_i, eta + i k): the exact unpolarised reflectance through a^2 + b^2.  eta = 0, k = 1 gives 1
+// exactly: sqrtf(t1 * t1) == |t1| (correctly rounded), so a == 0, both quotients are x / x and F = 0.5 * (1 + 1).
+DEV float fresnel_conductor(float ci, float eta, float k) {
+    const float ci2 = ci * ci, si2 = 1.0f - ci2, si4 = si2 * si2;
+    const float t1 = fma_(eta, eta, -(k * k)) - si2;
+    const float k_eta = k * eta;
+    const float a2pb2 = sqrtf(fmaxf(fma_(t1, t1, 4.0f * (k_eta * k_eta)), 0.0f));
+    const float a = sqrtf(fmaxf(0.5f * (a2pb2 + t1), 0.0f));
+    const float term1 = a2pb2 + ci2, term2 = 2.0f * (a * ci);
+    const float rs = (term1 - term2) / (term1 + term2);
+    const float term3 = fma_(a2pb2, ci2, si4), term4 = term2 * si2;
+    const float den = term3 + term4;
+    // den == 0 only for eta = k = 0 at normal incidence (0 / 0 in Mitsuba): the parallel term then equals the perpendicular one
+    const float rp = den > 0.0f ? rs * ((term3 - term4) / den) : rs;
+    return 0.5f * (rs + rp);
+}
+DEV V3 fresnel_conductor_rgb(const pbrt_material &m, float ci) {
+    return {fresnel_conductor(ci, m.p[1], m.p[4]), fresnel_conductor(ci, m.p[2], m.p[5]), fresnel_conductor(ci, m.p[3], m.p[6])};
+}
+// Smith G1 of the GGX distribution for v against the microfacet normal h (vh = v . h): 2 / (1 + sqrt(1 + a2 tan^2(theta_v)))
+DEV float ggx_g1(float a2, V3 v, float vh) {
+    if (!(vh * v.z > 0.0f)) return 0.0f;
+    const float t2 = fma_(v.x, v.x, v.y * v.y) / (v.z * v.z);
+    return 2.0f / (1.0f + sqrtf(fma_(a2, t2, 1.0f)));
+}
+// The factors of the rough conductor for wi.z > 0, wo.z > 0, with h = normalize(wi + wo): F(wi . h) per channel, the density of wo
+// dg = D(h) G1(wi) / (4 wi.z), and G1(wo).  eval: f cos(theta_o) = F (dg G1(wo)), pdf = dg; sample: weight = F G1(wo), pdf = dg.
+// D is evaluated as a2 / (pi (a2 h.z^2 + h.x^2 + h.y^2)^2): the value of a2 / (pi ((a2 - 1) h.z^2 + 1)^2) without its cancellation
+// at small alpha.
+DEV void ggx_terms(const pbrt_material &m, V3 wi, V3 wo, V3 *F, float *dg, float *g1o) {
+    const float alpha = fmaxf(m.p[0], K_GGX_ALPHA_MIN), a2 = alpha * alpha;
+    const V3 h = normalize(wi + wo);
+    const float wih = dot(wi, h), woh = dot(wo, h);
+    const float dd = fma_(a2, h.z * h.z, fma_(h.x, h.x, h.y * h.y));
+    const float D = a2 / (K_PI * (dd * dd));
+    *dg = (D * ggx_g1(a2, wi, wih)) / (4.0f * wi.z);
+    *g1o = ggx_g1(a2, wo, woh);
+    *F = fresnel_conductor_rgb(m, wih);
+}
+
+// GLOSSY: the ROUGHCONDUCTOR / CONDUCTOR_FRESNEL arms are compiled in (the kernels of scenes that hold such a material, and
+// the leaf operators); the instances every other scene runs leave them out
+template <bool GLOSSY = false>
 DEV void bsdf_eval_pdf(const pbrt_material &m, V3 wi, V3 wo, V3 *f, float *pdf) {
     *f = {0, 0, 0};
     *pdf = 0.0f;
@@ -856,10 +902,16 @@ DEV void bsdf_eval_pdf(const pbrt_material &m, V3 wi, V3 wo, V3 *f, float *pdf) 
         float c = K_INV_PI * wo.z;
         *f = v3(m.p[0], m.p[1], m.p[2]) * c;
         *pdf = c;
+    } else if (GLOSSY && m.type == PBRT_MAT_ROUGHCONDUCTOR && wi.z > 0.0f && wo.z > 0.0f) {
+        V3 F;
+        float g1o;
+        ggx_terms(m, wi, wo, &F, pdf, &g1o);
+        *f = F * (*pdf * g1o);
     }
 }
 
 // shf: the interaction's shading frame (si.to_local at CustomBSDF.py:165; read by ULTRA only)
+template <bool GLOSSY = false>
 DEV BSample bsdf_sample(const pbrt_material &m, uint32_t quirks, V3 wi, V3 n_geo, V3 n_sh, const Frame &shf, float s1,
                         float s2x, float s2y) {
     BSample b;
@@ -922,6 +974,43 @@ DEV BSample bsdf_sample(const pbrt_material &m, uint32_t quirks, V3 wi, V3 n_geo
         b.pdf = o.pdf;
         b.weight = {o.amp, o.amp, o.amp};
         b.lobe = o.reflect ? 0u : 1u;
+        b.delta = true;
+        b.valid = true;
+    } else if (GLOSSY && type == PBRT_MAT_ROUGHCONDUCTOR) {
+        if (!(wi.z > 0.0f)) return b;
+        // a visible normal for wi (Heitz's hemisphere method): stretch wi, a disk sample warped towards the projected hemisphere,
+        // back onto the hemisphere around the stretched wi, unstretch
+        const float alpha = fmaxf(m.p[0], K_GGX_ALPHA_MIN);
+        const V3 ws = normalize(v3(alpha * wi.x, alpha * wi.y, wi.z));
+        const float l2 = fma_(ws.x, ws.x, ws.y * ws.y);
+        V3 T1 = {1.0f, 0.0f, 0.0f};
+        if (l2 > 0.0f) {
+            const float inv_len = rcp_rn(sqrtf(l2));  // the reciprocal of a sqrtf result
+            T1 = {-ws.y * inv_len, ws.x * inv_len, 0.0f};
+        }
+        const V3 T2 = cross(ws, T1);
+        float dx, dy;
+        square_to_disk(s2x, s2y, &dx, &dy);
+        const float S = 0.5f * (1.0f + ws.z);
+        dy = fma_(1.0f - S, sqrtf(fmaxf(fma_(-dx, dx, 1.0f), 0.0f)), S * dy);
+        const float mz = sqrtf(fmaxf(1.0f - fma_(dx, dx, dy * dy), 0.0f));
+        const V3 ms = madd(ws, mz, madd(T2, dy, T1 * dx));
+        const V3 mm = normalize(v3(alpha * ms.x, alpha * ms.y, fmaxf(ms.z, 0.0f)));
+        b.wo = madd(mm, 2.0f * dot(wi, mm), -wi);
+        if (!(b.wo.z > 0.0f)) return b;
+        // weight = F(wi . m) G1(wo) and the density of wo, through the statements of eval / pdf (m == normalize(wi + wo)): the pdf of
+        // a sample is the pdf that eval_pdf returns for its direction, bit for bit
+        V3 F;
+        float g1o;
+        ggx_terms(m, wi, b.wo, &F, &b.pdf, &g1o);
+        if (!(b.pdf > 0.0f)) return b;
+        b.weight = F * g1o;
+        b.valid = true;
+    } else if (GLOSSY && type == PBRT_MAT_CONDUCTOR_FRESNEL) {
+        if (!(wi.z > 0.0f)) return b;
+        b.wo = {-wi.x, -wi.y, wi.z};
+        b.pdf = 1.0f;
+        b.weight = fresnel_conductor_rgb(m, wi.z);
         b.delta = true;
         b.valid = true;
     }

@@ -60,6 +60,10 @@ __host__ __device__ constexpr uint32_t us_region_segs(int, bool emit = false) { 
 // ACCEL_K_BVH_LDS    stackless BVH, nodes + primitives + ids staged in LDS per workgroup
 // ACCEL_K_BRUTE_BIG  uniform primitive loop, tables in global memory (brute force forced on a large scene)
 enum { ACCEL_K_BRUTE = 0, ACCEL_K_BVH_GLOBAL = 1, ACCEL_K_BVH_LDS = 2, ACCEL_K_BRUTE_BIG = 3 };
+// k_bounce only: ACCEL_K_BRUTE_BIG with the rough / Fresnel conductor code (scenes that hold such a material).  A template
+// argument of that kernel, never a pbrt_scene::accel_kernel: inside the kernel it is ACCEL_K_BRUTE_BIG + GLOSSY.
+enum { ACCEL_K_BRUTE_GLOSSY = 4 };
+__host__ __device__ constexpr int accel_base(int accel) { return accel == ACCEL_K_BRUTE_GLOSSY ? ACCEL_K_BRUTE_BIG : accel; }
 __host__ __device__ constexpr uint32_t rad_region_segs(int accel) {
     return (accel == ACCEL_K_BVH_GLOBAL || accel == ACCEL_K_BVH_LDS) ? REGION_SEGS_BVH : REGION_SEGS_BRUTE;
 }
@@ -295,7 +299,8 @@ DEV TreeLds stage_tree_lds(const DevScene &sc, uint32_t *lds) {
 // the shadow segment is the caller's: segment(so, sdir, tmax) either traces it at once and says whether it got through, or stores it
 // and says yes; contribute(A, B) then adds fma(A, B, L) or stores the two factors for the kernel that learns the visibility.
 // Args: RadArgs or WfArgs (n_emitters, max_depth, rr_depth, seed).  Returns whether the path goes on.
-template <class Args, class Segment, class Contribute>
+// GLOSSY: the scene holds a ROUGHCONDUCTOR / CONDUCTOR_FRESNEL material (device_scene.h bsdf_sample); else their code is compiled out
+template <bool GLOSSY, class Args, class Segment, class Contribute>
 DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka, uint32_t kb, float t_hit, const pbrt_prim &P,
                     const SI &si, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, Segment &&segment,
                     Contribute &&contribute) {
@@ -324,7 +329,7 @@ DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka
 #ifdef PBRT_ABLATE_NEE  // diagnostic builds only (tools/ablate.sh): never defined in the shipped library
         if (false) {
 #else
-        if (M.type == PBRT_MAT_DIFFUSE && nE > 0) {
+        if ((M.type == PBRT_MAT_DIFFUSE || (GLOSSY && M.type == PBRT_MAT_ROUGHCONDUCTOR)) && nE > 0) {
 #endif
             F4 u = rng4(ka, kb, 1 + 2 * depth, a.seed);
             ESample es = sample_emitter(tb, si.p, u);
@@ -332,7 +337,7 @@ DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka
                 V3 wo = to_local(fr, es.d);
                 V3 f;
                 float bpdf;
-                bsdf_eval_pdf(M, wi, wo, &f, &bpdf);
+                bsdf_eval_pdf<GLOSSY>(M, wi, wo, &f, &bpdf);
                 if (bpdf > 0.0f) {
                     V3 so = offset_origin(si.p, si.n, es.d);
                     V3 sv = es.q - so;
@@ -347,7 +352,7 @@ DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka
         }
         // ---- BSDF sampling, continuation ray, Russian roulette
         F4 ub = rng4(ka, kb, 2 + 2 * depth, a.seed);
-        BSample bs = bsdf_sample(M, PBRT_USQ_REFERENCE, wi, si.n, si.ns, fr, ub.x, ub.y, ub.z);
+        BSample bs = bsdf_sample<GLOSSY>(M, PBRT_USQ_REFERENCE, wi, si.n, si.ns, fr, ub.x, ub.y, ub.z);
         if (bs.valid) {
             thr = thr * bs.weight;
             eta *= bs.eta;
@@ -373,7 +378,9 @@ DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka
 // One bounce of one path (the body shared by k_bounce and k_walk): closest hit, the surface interaction, shade_step with its
 // shadow segment traced at once.  Returns whether the path goes on; a path that ends writes its radiance to Lhome[home].
 // HAVE_HIT: the closest hit was found earlier (k_bounce_pool) and comes in through h_in; the step starts at the shading.
-template <int ACCEL, bool HAVE_HIT = false>
+// GLOSSY: as shade_step.  Only k_bounce of the brute-force scenes has instances without it: every other kernel that comes through
+// here (the diagnostic build's launch structures, on the _BIG tables) always carries the arms.
+template <int ACCEL, bool HAVE_HIT = false, bool GLOSSY = ACCEL != ACCEL_K_BRUTE>
 DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsrc r_L, uint32_t depth, uint32_t ka, uint32_t kb,
                      uint32_t home, float tmax, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, bool &did_seg,
                      bool &did_shadow, const Hit *h_in = nullptr) {
@@ -384,7 +391,7 @@ DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsr
         did_seg = true;
         const pbrt_prim &P = tb.prims_by_slot[h.slot];
         const SI si = make_si<ACCEL != ACCEL_K_BRUTE>(P, o, d, h.t, h.u, h.v, a.sc.vnormals, h.slot);
-        survive = shade_step(
+        survive = shade_step<GLOSSY>(
             a, tb, depth, ka, kb, h.t, P, si, o, d, thr, L, eta, prev_pdf,
             [&](V3 so, V3 sdir, float smax) {
                 did_shadow = true;
@@ -413,7 +420,9 @@ DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsr
 // Cornell box, 20 % at depth 4 -- where the second bounce is the last one and only looks for emitters).  Same arithmetic
 // per bounce, same RNG keys: the film does not change.  Which depths start a two-bounce launch is the host's fuse plan
 // (pbrt_api.hip PBRT_DEFAULT_FUSE_PLAN: every pair).
-template <bool FIRST, int ACCEL, int NB = 1>
+// ACCEL_T: ACCEL_K_*, or ACCEL_K_BRUTE_GLOSSY for the instances of brute-force scenes with a ROUGHCONDUCTOR / CONDUCTOR_FRESNEL
+// material; the fused BVH bounce of the diagnostic build always carries those arms.
+template <bool FIRST, int ACCEL_T, int NB = 1>
 // two-bounce variants of ACCEL_K_BRUTE at the 64-register budget: 8 waves per SIMD with ONE spilled VGPR (a 4-byte scratch store
 // and load per bounce).  Without the budget the kernel takes 67 VGPRs = 7 waves, i.e. three 512-thread workgroups per CU instead of
 // four: 6.99 - 7.03 -> 6.82 - 6.85 ms on the Cornell box.  (Before -fno-slp-vectorize the same budget spilled 5 VGPRs and wrote
@@ -421,8 +430,17 @@ template <bool FIRST, int ACCEL, int NB = 1>
 #ifndef FUSED_WAVES_PER_EU
 #define FUSED_WAVES_PER_EU 8
 #endif
-__global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUTE ? FUSED_WAVES_PER_EU : BIG_WAVES_PER_EU) : seg_waves_per_eu(ACCEL)) void k_bounce(const RadArgs a) {
+// ACCEL_K_BRUTE_GLOSSY: at the 64-register budget of their twins the GGX + Fresnel arms spill 18 - 38 VGPRs to scratch;
+// those instances take the 128-register budget instead (4 waves per SIMD, two 512-thread workgroups per CU) and spill none.
+// Measured on the rough tube of examples/ (512^2 x 256 spp): 4.06 - 4.13 ms at 8 against 3.80 - 3.84 ms at 4 (alpha 0.4), level at
+// alpha 0.1 (profiles/rough_conductor.md).  One scene with one primitive: a scene with many may weigh occupancy higher.
+#ifndef GLOSSY_WAVES_PER_EU
+#define GLOSSY_WAVES_PER_EU 4
+#endif
+__global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_K_BRUTE_GLOSSY ? GLOSSY_WAVES_PER_EU : NB > 1 ? (ACCEL_T == ACCEL_K_BRUTE ? FUSED_WAVES_PER_EU : BIG_WAVES_PER_EU) : seg_waves_per_eu(ACCEL_T)) void k_bounce(const RadArgs a) {
+    constexpr int ACCEL = accel_base(ACCEL_T);
     static_assert(NB == 1 || ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG, "fused bounces: brute-force kernels only");
+    constexpr bool GL = ACCEL_T == ACCEL_K_BRUTE_GLOSSY || ACCEL == ACCEL_K_BVH_GLOBAL || ACCEL == ACCEL_K_BVH_LDS;
     // the per-bounce survivor counts of a chain are packed 10 bits each per WORKGROUP and summed by thread 0: one segment per region,
     // workgroup-level compaction (a -DREGION_SEGS_BRUTE build would silently lose them)
     static_assert(NB == 1 || (rad_region_segs(ACCEL) == 1 && !rad_wave_private(ACCEL) && seg_threads(ACCEL) <= 1023),
@@ -578,7 +596,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), NB > 1 ? (ACCEL == ACCEL_K_BRUT
             if (probe == 12345.678f) o.x = probe;  // never true; keeps the chain alive
         }
 #endif
-        survive = bounce_step<ACCEL>(a, tb, ls, r_L, depth, ka, kb, home, tmax, o, d, thr, L, eta, prev_pdf, did_seg, did_shadow);
+        survive = bounce_step<ACCEL, false, GL>(a, tb, ls, r_L, depth, ka, kb, home, tmax, o, d, thr, L, eta, prev_pdf, did_seg, did_shadow);
     }
     live = survive;
     nseg_w += (uint32_t)__popcll(__ballot(did_seg));

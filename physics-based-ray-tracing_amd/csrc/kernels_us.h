@@ -697,7 +697,7 @@ __global__ __launch_bounds__(256) void k_bsdf_sample(pbrt_material m, uint32_t q
     V3 s = ns ? v3(ns[i], ns[n + i], ns[2 * n + i]) : v3(0, 0, 1);
     // si.sh_frame: its tangent when the caller has one (dp_du / sh_frame.s), else coordinate_system(n_sh)
     const Frame shf = shs ? make_sh_frame(s, v3(shs[i], shs[n + i], shs[2 * n + i])) : make_frame(s);
-    BSample b = bsdf_sample(m, quirks, v3(wi[i], wi[n + i], wi[2 * n + i]), g, s, shf, s1[i], s2[i], s2[n + i]);
+    BSample b = bsdf_sample<true>(m, quirks, v3(wi[i], wi[n + i], wi[2 * n + i]), g, s, shf, s1[i], s2[i], s2[n + i]);
     wo[i] = b.wo.x;
     wo[n + i] = b.wo.y;
     wo[2 * n + i] = b.wo.z;
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(256) void k_bsdf_eval_pdf(pbrt_material m, uint32_t
     if (i >= n) return;
     V3 fv;
     float p;
-    bsdf_eval_pdf(m, v3(wi[i], wi[n + i], wi[2 * n + i]), v3(wo[i], wo[n + i], wo[2 * n + i]), &fv, &p);
+    bsdf_eval_pdf<true>(m, v3(wi[i], wi[n + i], wi[2 * n + i]), v3(wo[i], wo[n + i], wo[2 * n + i]), &fv, &p);
     f[i] = fv.x;
     f[n + i] = fv.y;
     f[2 * n + i] = fv.z;

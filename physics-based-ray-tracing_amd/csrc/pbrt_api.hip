@@ -191,6 +191,11 @@ struct pbrt_scene {
     uint32_t bvh_depth = 0;  // levels of inner nodes of the BVH4
     bool curved = true;      // the scene holds spheres, cones or cylinders (else the BVH stream kernels run without their tests)
     bool cylinders = false;  // the scene holds cylinders (else the stream shading kernels run without their code)
+    // a material is a ROUGHCONDUCTOR or CONDUCTOR_FRESNEL (else the bounce and the stream shading kernels run the instances
+    // without their code); follows pbrt_scene_update_material through mat_types
+    bool glossy = false;
+    bool small_tables = false;  // brute-force scenes: everything the ACCEL_K_BRUTE variant needs holds (tables <= 32 entries, no quadrics, no vertex normals)
+    std::vector<uint32_t> mat_types;
     std::vector<void *> allocs;
     pbrt_material *d_mats = nullptr;
     uint32_t n_mats = 0;
@@ -447,6 +452,29 @@ int pbrt_get_stats(pbrt_ctx *c, pbrt_stats *out) {
     return PBRT_OK;
 }
 
+}  // extern "C"
+
+// ROUGHCONDUCTOR / CONDUCTOR_FRESNEL records (include/pbrt_hip.h): alpha finite and > 0, eta and k finite and >= 0
+static bool material_is_glossy(uint32_t type) { return type == PBRT_MAT_ROUGHCONDUCTOR || type == PBRT_MAT_CONDUCTOR_FRESNEL; }
+static int check_material(pbrt_ctx *c, const pbrt_material &m, uint32_t index) {
+    if (!material_is_glossy(m.type)) return PBRT_OK;
+    if (m.type == PBRT_MAT_ROUGHCONDUCTOR && !(std::isfinite(m.p[0]) && m.p[0] > 0.0f))
+        return c->fail(PBRT_E_INVALID, "material %u: roughconductor alpha must be finite and > 0", index);
+    for (int k = 1; k < 7; ++k)
+        if (!(std::isfinite(m.p[k]) && m.p[k] >= 0.0f))
+            return c->fail(PBRT_E_INVALID, "material %u: conductor %s must be finite and >= 0", index, k < 4 ? "eta" : "k");
+    return PBRT_OK;
+}
+// the kernel variant of a brute-force scene: only ACCEL_K_BRUTE_BIG carries the rough / Fresnel conductor code
+static void scene_set_glossy(pbrt_scene *s) {
+    s->glossy = false;
+    for (uint32_t t : s->mat_types) s->glossy = s->glossy || material_is_glossy(t);
+    if (s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG)
+        s->accel_kernel = s->small_tables && !s->glossy ? ACCEL_K_BRUTE : ACCEL_K_BRUTE_BIG;
+}
+
+extern "C" {
+
 int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
     if (!c) return PBRT_E_INVALID;
     NEED(c, d && out);
@@ -471,6 +499,8 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
         if (p.emitter >= 0 && (uint32_t)p.emitter >= d->n_emitters)
             return c->fail(PBRT_E_INVALID, "primitive %u: emitter out of range", i);
     }
+    for (uint32_t i = 0; i < d->n_materials; ++i)
+        if (int rc = check_material(c, d->materials[i], i)) return rc;
     for (uint32_t i = 0; i < d->n_emitters; ++i) {
         const pbrt_emitter &e = d->emitters[i];
         if (e.type == PBRT_EMIT_AREA) {
@@ -507,6 +537,7 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
     s->ds.mats = dm;
     s->d_mats = const_cast<pbrt_material *>(dm);
     s->n_mats = s->ds.n_mats = d->n_materials;
+    for (uint32_t i = 0; i < d->n_materials; ++i) s->mat_types.push_back(d->materials[i].type);
     UP(upload(s, d->emitters, d->n_emitters, &s->ds.emitters));
     s->ds.n_emitters = d->n_emitters;
     UP(upload(s, d->light_prims, d->n_light_prims, &s->ds.light_prims));
@@ -526,6 +557,7 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
                 small = false;  // only the _BIG variant carries the cone / cylinder code
         if (d->vertex_normals) small = false;                      // ... and the shading-normal code
         if (d->vertex_normals) UP(upload(s, d->vertex_normals, (size_t)d->n_prims * 9, &s->ds.vnormals));
+        s->small_tables = small;
         s->accel_kernel = small ? ACCEL_K_BRUTE : ACCEL_K_BRUTE_BIG;
         std::vector<pbrt_prim> occ = find_occluders(d);
         UP(upload(s, occ.data(), occ.size(), &s->ds.occ_prims));
@@ -572,6 +604,7 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
         }
     }
 #undef UP
+    scene_set_glossy(s);
     *out = s;
     return PBRT_OK;
 }
@@ -581,10 +614,13 @@ int pbrt_scene_update_material(pbrt_scene *s, uint32_t index, const pbrt_materia
     pbrt_ctx *c = s->ctx;
     NEED(c, m && index < s->n_mats);
     NOT_RECORDING(c);  // (a recorded copy would replay the bytes of THIS call's host block)
+    if (int rc = check_material(c, *m, index)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // in the order of the context's stream: behind an acquisition that is still queued, ahead of the next one (the 32 bytes are
     // staged before the call returns)
     HIPCHK(c, hipMemcpyAsync(s->d_mats + index, m, sizeof *m, hipMemcpyHostToDevice, c->stream));
+    s->mat_types[index] = m->type;
+    scene_set_glossy(s);  // the launches queued from now on
     return PBRT_OK;
 }
 
@@ -645,7 +681,12 @@ static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, uint32_
                 hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
             break;
         case ACCEL_K_BRUTE_BIG:
-            if (nb >= 2)
+            if (s->glossy) {  // the instances with the rough / Fresnel conductor code
+                if (nb >= 2)
+                    hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_GLOSSY, 2>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
+                else
+                    hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_GLOSSY, 1>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
+            } else if (nb >= 2)
                 hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_BIG, 2>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
             else
                 hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_BIG>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
@@ -894,10 +935,13 @@ static uint32_t wf_trace_grid(uint32_t nr, uint32_t mult, uint32_t cus) {
 
 // The bounces of one pass.  camera: depth 0 generates its rays from the film keys (else the rays are in b.stA / b.segA).
 // Returns the number of launches through *launches.
-// k_shade with or without the cylinder code (the instance without it is the one every other scene runs)
+// k_shade with or without the cylinder code (the instance without it is the one every other scene runs), or with the rough /
+// Fresnel conductor code on top of it
 template <bool FIRST, bool TABS>
-static void wf_launch_shade(bool cyl, dim3 g, dim3 t, hipStream_t st, const WfArgs &a) {
-    if (cyl)
+static void wf_launch_shade(bool cyl, bool glossy, dim3 g, dim3 t, hipStream_t st, const WfArgs &a) {
+    if (glossy)
+        hipLaunchKernelGGL((k_shade_glossy<FIRST, TABS, true>), g, t, 0, st, a);
+    else if (cyl)
         hipLaunchKernelGGL((k_shade<FIRST, TABS, true>), g, t, 0, st, a);
     else
         hipLaunchKernelGGL((k_shade<FIRST, TABS, false>), g, t, 0, st, a);
@@ -976,14 +1020,14 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
         const dim3 g(regn[h]), t(WF_SHADE_THREADS);
         if (first) {
             if (tabs)
-                wf_launch_shade<true, true>(s->cylinders, g, t, st, a);
+                wf_launch_shade<true, true>(s->cylinders, s->glossy, g, t, st, a);
             else
-                wf_launch_shade<true, false>(s->cylinders, g, t, st, a);
+                wf_launch_shade<true, false>(s->cylinders, s->glossy, g, t, st, a);
         } else {
             if (tabs)
-                wf_launch_shade<false, true>(s->cylinders, g, t, st, a);
+                wf_launch_shade<false, true>(s->cylinders, s->glossy, g, t, st, a);
             else
-                wf_launch_shade<false, false>(s->cylinders, g, t, st, a);
+                wf_launch_shade<false, false>(s->cylinders, s->glossy, g, t, st, a);
         }
         ++*launches;
     };
@@ -2377,6 +2421,7 @@ int pbrt_bsdf_sample(pbrt_ctx *ctx, const pbrt_material *m, uint32_t quirks, uin
                      float *pdf, float *weight, uint32_t *sampled) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && s1 && s2 && wo && pdf && weight && sampled);
+    if (int rc = check_material(ctx, *m, 0)) return rc;
     LEAF_BEGIN(ctx, (size_t)n * 4 * 25);
     float *dwi = S.in(wi, 3 * (size_t)n), *dng = S.in(n_geo, 3 * (size_t)n), *dns = S.in(n_sh, 3 * (size_t)n);
     float *dss = S.in(sh_s, 3 * (size_t)n);
@@ -2395,6 +2440,7 @@ int pbrt_bsdf_eval_pdf(pbrt_ctx *ctx, const pbrt_material *m, uint32_t n, const 
                        float *pdf) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && wo && f && pdf);
+    if (int rc = check_material(ctx, *m, 0)) return rc;
     LEAF_BEGIN(ctx, (size_t)n * 4 * 12);
     float *dwi = S.in(wi, 3 * (size_t)n), *dwo = S.in(wo, 3 * (size_t)n);
     float *rf = S.out<float>(3 * (size_t)n), *rp = S.out<float>(n);

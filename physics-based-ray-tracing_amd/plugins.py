@@ -154,21 +154,121 @@ class DiffuseBSDF(BSDF):
         cb.put_parameter("reflectance", self.reflectance, ParamFlags.Differentiable)
 
 
+def _conductor_eta_k(props, plugin):
+    """eta, k of a conductor plugin as rgb triples (Mitsuba's material 'none': eta = 0, k = 1, reflectance 1) and whether either
+    was given.  Named material presets are spectral data files of Mitsuba that this package does not carry."""
+    mat = props.get("material", "none")
+    if mat != "none":
+        raise NotImplementedError(f"{plugin}: material {mat!r} is not supported (only 'none'); give eta and k as numbers")
+    given = props.has_property("eta") or props.has_property("k")
+    eta, k = _checked_eta_k(props.get("eta", 0.0), props.get("k", 1.0), plugin)
+    return eta, k, given
+
+
+def _checked_eta_k(eta, k, plugin):
+    """eta, k as rgb triples, or the ValueError of the constructor and of parameters_changed"""
+    eta, k = rgb3(eta), rgb3(k)
+    for name, v in (("eta", eta), ("k", k)):
+        if not (np.isfinite(v).all() and (v >= 0).all()):
+            raise ValueError(f"{plugin}: {name} must be finite and >= 0, got {v.tolist()}")
+    return eta, k
+
+
+def _checked_alpha(alpha):
+    alpha = float(np.asarray(alpha).ravel()[0])
+    if not (math.isfinite(alpha) and alpha > 0.0):
+        raise ValueError(f"roughconductor: alpha must be finite and > 0, got {alpha}")
+    return alpha
+
+
 class ConductorBSDF(BSDF):
-    """Mitsuba 'conductor' with no material preset: eta = 0, k = 1, a perfect mirror."""
+    """Mitsuba 'conductor'.  Without eta / k: material 'none' (eta = 0, k = 1), a perfect mirror tinted by
+    specular_reflectance.  With eta and / or k: a smooth conductor whose delta lobe weighs F(cos theta_i) per channel."""
 
     def __init__(self, props):
         super().__init__(props)
-        mat = props.get("material", "none")
-        if mat != "none" or props.has_property("eta") or props.has_property("k"):
-            raise NotImplementedError("conductor: only the default perfect mirror (material 'none') is supported")
+        self.eta, self.k, self._fresnel = _conductor_eta_k(props, "conductor")
         self.specular_reflectance = rgb3(props.get("specular_reflectance", 1.0))
+        if self._fresnel and not np.all(self.specular_reflectance == 1.0):
+            raise NotImplementedError("conductor: specular_reflectance other than 1 cannot be combined with eta / k "
+                                      "(the material record has no room for it)")
+        self._valid = (self.eta, self.k)
 
     def to_material(self):
+        if self._fresnel:
+            return _capi.MAT_CONDUCTOR_FRESNEL, [0.0, *rgb3(self.eta), *rgb3(self.k)]
         return _capi.MAT_CONDUCTOR, list(self.specular_reflectance)
 
     def traverse(self, cb):
-        cb.put_parameter("specular_reflectance", self.specular_reflectance, ParamFlags.Differentiable)
+        if self._fresnel:
+            cb.put_parameter("eta", self.eta, ParamFlags.Differentiable | ParamFlags.Discontinuous)
+            cb.put_parameter("k", self.k, ParamFlags.Differentiable | ParamFlags.Discontinuous)
+        else:
+            cb.put_parameter("specular_reflectance", self.specular_reflectance, ParamFlags.Differentiable)
+
+    def parameters_changed(self, keys=None):
+        """what the constructor refuses is refused here as well; the object keeps the values it had"""
+        if not self._fresnel:
+            return
+        try:
+            self.eta, self.k = _checked_eta_k(self.eta, self.k, "conductor")
+        except ValueError:
+            self.eta, self.k = self._valid
+            raise
+        self._valid = (self.eta, self.k)
+
+
+class RoughConductorBSDF(BSDF):
+    """Mitsuba 'roughconductor' restricted to what the device implements: an isotropic GGX distribution sampled through its
+    visible normals.  props: alpha (0.1), distribution (must be 'ggx'), sample_visible (true), eta / k (scalar or rgb; default
+    material 'none': eta = 0, k = 1, Fresnel reflectance 1), material ('none'), specular_reflectance (1)."""
+
+    def __init__(self, props):
+        super().__init__(props)
+        dist = props.get("distribution", "beckmann")  # Mitsuba's default when the key is absent
+        if dist != "ggx":
+            raise NotImplementedError(f"roughconductor: distribution {dist!r} is not supported; pass distribution='ggx' "
+                                      "(Mitsuba's default, 'beckmann', is not built)")
+        if not bool(props.get("sample_visible", True)):
+            raise NotImplementedError("roughconductor: sample_visible=false is not supported (visible-normal sampling only)")
+        if props.has_property("alpha_u") or props.has_property("alpha_v"):
+            au, av = props.get("alpha_u", None), props.get("alpha_v", None)
+            if au is None or av is None or float(au) != float(av):
+                raise NotImplementedError("roughconductor: alpha_u != alpha_v (anisotropic roughness) is not supported")
+            if props.has_property("alpha"):
+                raise ValueError("roughconductor: give either alpha or alpha_u / alpha_v")
+            self.alpha = _checked_alpha(au)
+        else:
+            self.alpha = _checked_alpha(props.get("alpha", 0.1))
+        self.eta, self.k, _ = _conductor_eta_k(props, "roughconductor")
+        sr = rgb3(props.get("specular_reflectance", 1.0))
+        if not np.all(sr == 1.0):
+            raise NotImplementedError("roughconductor: specular_reflectance other than 1 is not supported "
+                                      "(the material record holds alpha, eta and k only)")
+        self.m_components = [BSDFFlags.GlossyReflection | BSDFFlags.FrontSide]
+        self.m_flags = self.m_components[0]
+        self._valid = (self.alpha, self.eta, self.k)
+
+    def to_material(self):
+        return _capi.MAT_ROUGHCONDUCTOR, [float(self.alpha), *rgb3(self.eta), *rgb3(self.k)]
+
+    def _sampled_type(self, lobe):
+        return np.where(lobe == 0, BSDFFlags.GlossyReflection, 0).astype(np.uint32)
+
+    def traverse(self, cb):
+        cb.put_parameter("alpha", self.alpha, ParamFlags.Differentiable | ParamFlags.Discontinuous)
+        cb.put_parameter("eta", self.eta, ParamFlags.Differentiable | ParamFlags.Discontinuous)
+        cb.put_parameter("k", self.k, ParamFlags.Differentiable | ParamFlags.Discontinuous)
+
+    def parameters_changed(self, keys=None):
+        """what the constructor refuses is refused here as well; the object keeps the values it had"""
+        try:
+            self.alpha = _checked_alpha(self.alpha)
+            self.eta, self.k = _checked_eta_k(self.eta, self.k, "roughconductor")
+        except ValueError:
+            self.alpha, self.eta, self.k = self._valid
+            raise
+        self._valid = (self.alpha, self.eta, self.k)
 
 
 _IOR = {"vacuum": 1.0, "air": 1.000277, "water": 1.3330, "bk7": 1.5046, "diamond": 2.419, "glass": 1.5046}
@@ -849,8 +949,8 @@ class UltraIntegrator(SamplingIntegrator):
 # ------------------------------------------------------------------------------------------------
 for _n, _c in (("path", PathIntegrator), ("direct", DirectIntegrator), ("ultrasound_integrator", UltraIntegrator)):
     _register("integrator", _n, _c)
-for _n, _c in (("diffuse", DiffuseBSDF), ("conductor", ConductorBSDF), ("dielectric", DielectricBSDF),
-               ("ultrasound_bsdf", UltraBSDF)):
+for _n, _c in (("diffuse", DiffuseBSDF), ("conductor", ConductorBSDF), ("roughconductor", RoughConductorBSDF),
+               ("dielectric", DielectricBSDF), ("ultrasound_bsdf", UltraBSDF)):
     _register("bsdf", _n, _c)
 for _n, _c in (("area", AreaEmitter), ("ultraray", AreaEmitter), ("point", PointEmitter),
                ("ultrasound_emitter", CustomEmitter)):
