@@ -243,6 +243,29 @@ static int upload(pbrt_scene *s, const T *src, size_t n, const T **dst) {
 
 static inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
+// Runtime flags as template arguments: with_flags(f, a, b, ...) calls the generic lambda f with one std::true_type / std::false_type
+// per flag and returns what f returns.  Every kernel family has ONE selector built on it (bounce_kernel, trace_kernel, ...), which
+// both its launch site and the site that sets its LDS attribute call; f names exactly the instances that exist.
+template <class F>
+static auto with_flags(F f) { return f(); }
+template <class F, class... Bs>
+static auto with_flags(F f, bool b, Bs... rest) {
+    auto bind = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return b ? bind(std::true_type{}) : bind(std::false_type{});
+}
+// the limit of dynamic LDS of the kernel a selector returned
+template <class K>
+static hipError_t set_max_lds(K kernel, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+using RadKern = void (*)(RadArgs);
+using WfKern = void (*)(WfArgs);
+using UsKern = void (*)(UsArgs);
+using UsWfKern = void (*)(UsWfArgs);
+using UsFirstKern = void (*)(UsArgs, uint32_t, float4 *, float4 *);
+using RayIntersectKern = void (*)(DevScene, uint32_t, const float *, const float *, const float *, float *, uint32_t *, float *, float *);
+using RayTestKern = void (*)(DevScene, uint32_t, const float *, const float *, const float *, uint8_t *);
+
 // Primitives that can occlude a segment between two points of the scene (DevScene::occ_prims).  A planar
 // primitive is dropped when all OTHER geometry and every point emitter lie in one closed half-space of its
 // plane: it then sits on the boundary of the scene's convex hull and a segment whose end points are in the
@@ -652,77 +675,71 @@ int pbrt_scene_destroy(pbrt_scene *s) {
 #define PBRT_DEFAULT_WALK_FROM 0xffu
 #endif
 
+// The fused bounce kernel of a launch that walks nb bounces (>= 2: the multi-bounce variants of the brute-force kernels,
+// kernels_radiance.h; a.nb = nb) -- or, walk (diagnostic build), every remaining bounce of the pass (k_walk).  Glossy brute-force
+// scenes have instances of their own.  nullptr: BVH scenes run k_trace / k_shade (wf_bounces); their fused bounce
+// (PBRT_FILM_NO_HIT_POOL) exists in the diagnostic build only.
+static RadKern bounce_kernel(const pbrt_scene *s, bool first, uint32_t nb, bool walk = false) {
+    const bool two = nb >= 2;
 #ifdef PBRT_DIAG
-template <bool FIRST>
-static void launch_walk(pbrt_scene *s, const RadArgs &a, uint32_t nseg, uint32_t nb0) {
-    hipStream_t st = s->ctx->stream;
-    if (s->accel_kernel == ACCEL_K_BRUTE) {
-        if (nb0 == 2)
-            hipLaunchKernelGGL((k_walk<FIRST, ACCEL_K_BRUTE, 2>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-        else
-            hipLaunchKernelGGL((k_walk<FIRST, ACCEL_K_BRUTE, 1>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-    } else {
-        if (nb0 == 2)
-            hipLaunchKernelGGL((k_walk<FIRST, ACCEL_K_BRUTE_BIG, 2>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-        else
-            hipLaunchKernelGGL((k_walk<FIRST, ACCEL_K_BRUTE_BIG, 1>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-    }
-}
+    if (walk)
+        return with_flags(
+            [](auto F, auto B, auto N) -> RadKern { return &k_walk<F(), B() ? ACCEL_K_BRUTE_BIG : ACCEL_K_BRUTE, N() ? 2 : 1>; }, first,
+            s->accel_kernel != ACCEL_K_BRUTE, nb == 2);
+    if (s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS)
+        return with_flags([](auto F, auto L) -> RadKern { return &k_bounce<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL>; }, first,
+                          s->accel_kernel == ACCEL_K_BVH_LDS);
 #endif
-// nb: bounces this launch walks (>= 2: the multi-bounce variants of the brute-force kernels, kernels_radiance.h; a.nb = nb)
-template <bool FIRST>
-static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, uint32_t nb = 1) {
-    hipStream_t st = s->ctx->stream;
     switch (s->accel_kernel) {
         case ACCEL_K_BRUTE:
-            if (nb >= 2)
-                hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE, 2>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-            else
-                hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-            break;
+            return with_flags([](auto F, auto N) -> RadKern { return &k_bounce<F(), ACCEL_K_BRUTE, N() ? 2 : 1>; }, first, two);
         case ACCEL_K_BRUTE_BIG:
-            if (s->glossy) {  // the instances with the rough / Fresnel conductor code
-                if (nb >= 2)
-                    hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_GLOSSY, 2>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-                else
-                    hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_GLOSSY, 1>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-            } else if (nb >= 2)
-                hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_BIG, 2>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-            else
-                hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BRUTE_BIG>), dim3(nseg), dim3(SEG_BRUTE), 0, st, a);
-            break;
-#ifdef PBRT_DIAG  // the fused BVH bounce (PBRT_FILM_NO_HIT_POOL): diagnostic build only
-        case ACCEL_K_BVH_GLOBAL:
-            hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BVH_GLOBAL>), dim3(nseg), dim3(SEG_BVH), 0, st, a);
-            break;
+            return with_flags([](auto F, auto G, auto N) -> RadKern {
+                return &k_bounce<F(), G() ? ACCEL_K_BRUTE_GLOSSY : ACCEL_K_BRUTE_BIG, N() ? 2 : 1>; }, first, s->glossy, two);
         default:
-            hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_K_BVH_LDS>), dim3(nseg), dim3(SEG_BVH), s->lds_bytes, st, a);
-            break;
-#else
-        default:  // BVH scenes run k_trace / k_shade (wf_bounces); the fused BVH bounce exists in the diagnostic build only
-            return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_bounce: no fused bounce kernel for accelerator %d in this build", s->accel_kernel);
-#endif
+            return nullptr;
     }
+}
+static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool first, uint32_t nb = 1, bool walk = false) {
+    const RadKern k = bounce_kernel(s, first, nb, walk);
+    if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_bounce: no fused bounce kernel for accelerator %d in this build", s->accel_kernel);
+    const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
+    hipLaunchKernelGGL(k, dim3(nseg), dim3(seg_threads(s->accel_kernel)), lds ? s->lds_bytes : 0u, s->ctx->stream, a);
     return PBRT_OK;
 }
 
+// The fused ultrasound bounce.  q: us_kernel_quirks; tab: first-bounce tables both there (1), both absent (0), else -1.
+// ACCEL_K_BRUTE with a compiled-in quirk set (the kernels of BASELINE config 3, both readings, and of the reference's own loop)
+// has its table mode compiled in too: -1 on later bounces, 0 for emitter rays (never any tables).  Everything else reads both at
+// run time.  nullptr: BVH scenes run k_trace / k_us_shade (us_wf_pass); their fused bounce (PBRT_US_FUSED_BVH=1, no emitter rays)
+// exists in the diagnostic build only.
+static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint32_t q, int tab) {
+    if (!first) tab = -1;
+    switch (s->accel_kernel) {
+        case ACCEL_K_BRUTE:
+            if (q != US_Q_RUNTIME && (tab >= 0 || !first))
+                return with_flags([](auto F, auto E, auto C, auto T) -> UsKern {
+                    return &k_us_bounce<F(), ACCEL_K_BRUTE, E(), C() ? PBRT_USQ_REFERENCE : (PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER),
+                                        !F() ? -1 : (!E() && T()) ? 1 : 0>; }, first, emit, q == PBRT_USQ_REFERENCE, tab == 1);
+            return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce<F(), ACCEL_K_BRUTE, E()>; }, first, emit);
+        case ACCEL_K_BRUTE_BIG:
+            return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce<F(), ACCEL_K_BRUTE_BIG, E()>; }, first, emit);
+        default:
+#ifdef PBRT_DIAG
+            if (!emit)
+                return with_flags([](auto F, auto L) -> UsKern { return &k_us_bounce<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL>; },
+                                  first, s->accel_kernel == ACCEL_K_BVH_LDS);
+#endif
+            return nullptr;
+    }
+}
+// Scenes whose tree is in LDS: the LDS limit of their fused kernels (the diagnostic build has them; nullptr: not in this build)
 static int set_lds_attr(pbrt_scene *s) {
     if (s->accel_kernel != ACCEL_K_BVH_LDS) return PBRT_OK;
-    pbrt_ctx *c = s->ctx;
-    int bytes = (int)s->lds_bytes;
-#ifdef PBRT_DIAG
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bounce<true, ACCEL_K_BVH_LDS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bounce<false, ACCEL_K_BVH_LDS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_us_bounce<true, ACCEL_K_BVH_LDS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_us_bounce<false, ACCEL_K_BVH_LDS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-#else
-    (void)c;
-    (void)bytes;
-#endif
+    for (bool first : {true, false}) {
+        if (const RadKern k = bounce_kernel(s, first, 1)) HIPCHK(s->ctx, set_max_lds(k, s->lds_bytes));
+        if (const UsKern k = us_bounce_kernel(s, first, false, US_Q_RUNTIME, -1)) HIPCHK(s->ctx, set_max_lds(k, s->lds_bytes));
+    }
     return PBRT_OK;
 }
 
@@ -787,7 +804,7 @@ static void radiance_model_bytes(const unsigned long long *live, uint32_t nd, ui
 
 // ---- BVH scenes: intersection and shading as separate streams (kernels_wavefront.h) -------------------------------------------
 struct WfPlan {
-    bool packet = true;      // camera rays: one tree walk per 64-path tile (k_trace_primary); PBRT_WF_PACKET=0: k_trace<true> (A/B)
+    bool packet = true;      // camera rays: one tree walk per 64-path tile (k_trace_primary); PBRT_WF_PACKET=0: k_trace (A/B)
     uint32_t grid_deep = 2;  // workgroups per CU from bounce 2 on (few rays: a resident round of larger shares; ring 8 / 2 / 1: 139.7 / 137.1 / 134.9 ms)
     uint32_t threads = 1024, rows = 2, grid_mult = 8;  // grid: ring 1024^2 x 64: 2 / 4 / 8 / 16 workgroups per CU -> 27.6 / 21.3 / 20.4 / 21.3 ms
     size_t lds = 0;
@@ -813,20 +830,28 @@ static WfPlan wf_plan(const pbrt_scene *s) {
     p.lds = (size_t)image + (size_t)p.rows * p.threads * 4u;
     return p;
 }
+// The intersection kernel of a bounce with its workgroup size and dynamic LDS: camera rays as packets (k_trace_primary), else
+// k_trace.  Template arguments: <first bounce,> tree in LDS / in global memory, scene with curved primitives.
+struct TraceLaunch {
+    WfKern kernel;
+    uint32_t threads;
+    size_t lds;
+};
+static TraceLaunch trace_kernel(const pbrt_scene *s, const WfPlan &p, bool first) {
+    const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
+    if (first && p.packet) {
+        auto primary = [](auto L, auto C) -> WfKern { return &k_trace_primary<L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL, C()>; };
+        return {with_flags(primary, lds, s->curved), 1024u, lds ? s->lds_bytes : 0u};
+    }
+    auto trace = [](auto F, auto L, auto C) -> WfKern { return &k_trace<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL, C()>; };
+    return {with_flags(trace, first, lds, s->curved), p.threads, p.lds};
+}
+// trees in LDS: the LDS limit of the kernels this scene's bounces launch (first bounce, later bounces)
 static int wf_set_attr(pbrt_scene *s, const WfPlan &p) {
-    pbrt_ctx *c = s->ctx;
-    if (s->accel_kernel == ACCEL_K_BVH_LDS) {
-#define WF_ATTR(fn, bytes) HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
-        if (s->curved) {
-            WF_ATTR((k_trace<true, ACCEL_K_BVH_LDS, true>), p.lds);
-            WF_ATTR((k_trace<false, ACCEL_K_BVH_LDS, true>), p.lds);
-            WF_ATTR((k_trace_primary<ACCEL_K_BVH_LDS, true>), s->lds_bytes);
-        } else {
-            WF_ATTR((k_trace<true, ACCEL_K_BVH_LDS, false>), p.lds);
-            WF_ATTR((k_trace<false, ACCEL_K_BVH_LDS, false>), p.lds);
-            WF_ATTR((k_trace_primary<ACCEL_K_BVH_LDS, false>), s->lds_bytes);
-        }
-#undef WF_ATTR
+    if (s->accel_kernel != ACCEL_K_BVH_LDS) return PBRT_OK;
+    for (bool first : {true, false}) {
+        const TraceLaunch t = trace_kernel(s, p, first);
+        HIPCHK(s->ctx, set_max_lds(t.kernel, t.lds));
     }
     return PBRT_OK;
 }
@@ -857,6 +882,26 @@ static bool wf_alloc(pbrt_ctx *c, uint32_t cap, uint32_t nreg, WfBufs *b) {
     b->nshA = (uint32_t *)c->buf("wf_nshA", (size_t)nreg * 4);
     b->nshB = (uint32_t *)c->buf("wf_nshB", (size_t)nreg * 4);
     return b->stA && b->stB && b->hit_id && b->shA && b->shB && b->segA && b->segB && b->nshA && b->nshB;
+}
+// the buffers of a pass in their in / out roles: state, shadow rays, live counters, shadow-ray counters; flip() after every bounce
+struct WfPing {
+    float4 *in, *out, *shi, *sho;
+    uint32_t *sin, *sout, *ni, *no;
+    explicit WfPing(const WfBufs &b) : in(b.stA), out(b.stB), shi(b.shA), sho(b.shB), sin(b.segA), sout(b.segB), ni(b.nshA), no(b.nshB) {}
+    void flip() {
+        std::swap(in, out);
+        std::swap(shi, sho);
+        std::swap(sin, sout);
+        std::swap(ni, no);
+    }
+};
+// the tree and stack members of a k_trace launch, and the guard words (false: out of memory)
+static bool wf_tree_args(pbrt_scene *s, const WfPlan &p, WfArgs *a) {
+    a->lds_bytes = s->accel_kernel == ACCEL_K_BVH_LDS ? s->lds_bytes : 0u;
+    a->stk_rows = p.rows;
+    a->stk_shift = 0;
+    while ((1u << a->stk_shift) < p.threads) ++a->stk_shift;
+    return (a->guard = wf_guard(s->ctx)) != nullptr;
 }
 // BVH scenes, opt-in (PBRT_WF_SPLIT=s[,parts]): the CUs are split between the two kernels of a bounce.  k_trace is bound by
 // instruction issue and k_shade by HBM, but run side by side on the same CUs they only trade wave slots (round 3: +2.8 %).  Here
@@ -896,55 +941,22 @@ static int wf_split_streams(pbrt_ctx *c, uint32_t s_cus) {
     return PBRT_OK;
 }
 
-// one k_trace / k_trace_primary launch over a.n_regions regions.  template arguments: <first bounce,> tree in LDS / in global
-// memory, scene with curved primitives
+// one k_trace / k_trace_primary launch over a.n_regions regions
 static void wf_launch_trace(pbrt_scene *s, const WfArgs &a, const WfPlan &p, uint32_t G, bool first, hipStream_t st) {
-    const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
-#define WF_TRACE(F, A, C) hipLaunchKernelGGL((k_trace<F, A, C>), dim3(G), dim3(p.threads), p.lds, st, a)
-#define WF_PRIMARY(A, C) hipLaunchKernelGGL((k_trace_primary<A, C>), dim3(G), dim3(1024), lds ? s->lds_bytes : 0u, st, a)
-    const int variant = (lds ? 2 : 0) | (s->curved ? 1 : 0);
-    if (first && p.packet) {
-        switch (variant) {
-            case 3: WF_PRIMARY(ACCEL_K_BVH_LDS, true); break;
-            case 2: WF_PRIMARY(ACCEL_K_BVH_LDS, false); break;
-            case 1: WF_PRIMARY(ACCEL_K_BVH_GLOBAL, true); break;
-            default: WF_PRIMARY(ACCEL_K_BVH_GLOBAL, false); break;
-        }
-    } else if (first) {
-        switch (variant) {
-            case 3: WF_TRACE(true, ACCEL_K_BVH_LDS, true); break;
-            case 2: WF_TRACE(true, ACCEL_K_BVH_LDS, false); break;
-            case 1: WF_TRACE(true, ACCEL_K_BVH_GLOBAL, true); break;
-            default: WF_TRACE(true, ACCEL_K_BVH_GLOBAL, false); break;
-        }
-    } else {
-        switch (variant) {
-            case 3: WF_TRACE(false, ACCEL_K_BVH_LDS, true); break;
-            case 2: WF_TRACE(false, ACCEL_K_BVH_LDS, false); break;
-            case 1: WF_TRACE(false, ACCEL_K_BVH_GLOBAL, true); break;
-            default: WF_TRACE(false, ACCEL_K_BVH_GLOBAL, false); break;
-        }
-    }
-#undef WF_TRACE
-#undef WF_PRIMARY
+    const TraceLaunch t = trace_kernel(s, p, first);
+    hipLaunchKernelGGL(t.kernel, dim3(G), dim3(t.threads), t.lds, st, a);
 }
 // workgroups of a k_trace launch over nr regions: at least nr / WF_KMAX (a workgroup walks at most WF_KMAX regions), else `mult` per CU
 static uint32_t wf_trace_grid(uint32_t nr, uint32_t mult, uint32_t cus) {
     return std::min(nr, std::max(div_up(nr, WF_KMAX), std::max(1u, mult * cus)));
 }
 
-// The bounces of one pass.  camera: depth 0 generates its rays from the film keys (else the rays are in b.stA / b.segA).
-// Returns the number of launches through *launches.
 // k_shade with or without the cylinder code (the instance without it is the one every other scene runs), or with the rough /
-// Fresnel conductor code on top of it
-template <bool FIRST, bool TABS>
-static void wf_launch_shade(bool cyl, bool glossy, dim3 g, dim3 t, hipStream_t st, const WfArgs &a) {
-    if (glossy)
-        hipLaunchKernelGGL((k_shade_glossy<FIRST, TABS, true>), g, t, 0, st, a);
-    else if (cyl)
-        hipLaunchKernelGGL((k_shade<FIRST, TABS, true>), g, t, 0, st, a);
-    else
-        hipLaunchKernelGGL((k_shade<FIRST, TABS, false>), g, t, 0, st, a);
+// Fresnel conductor code on top of it; the small shading tables in LDS when they fit (kernels_wavefront.h wf_tables_lds)
+static WfKern shade_kernel(const pbrt_scene *s, bool first) {
+    const bool tabs = s->ds.n_mats <= TAB_MAX && s->ds.n_emitters <= TAB_MAX && s->ds.n_light_prims <= TAB_MAX;
+    if (s->glossy) return with_flags([](auto F, auto T) -> WfKern { return &k_shade_glossy<F(), T(), true>; }, first, tabs);
+    return with_flags([](auto F, auto T, auto C) -> WfKern { return &k_shade<F(), T(), C()>; }, first, tabs, s->cylinders);
 }
 
 // Unbounded depth (Mitsuba max_depth = -1): the live paths of a pass, summed over its n counters (one per region or wave of it)
@@ -958,17 +970,12 @@ static int live_paths(pbrt_ctx *c, const uint32_t *d_counts, uint32_t n, uint64_
     return PBRT_OK;
 }
 
+// The bounces of one pass.  camera: depth 0 generates its rays from the film keys (else the rays are in b.stA / b.segA).
+// Returns the number of launches through *launches.
 static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p, uint32_t nreg, bool camera, uint32_t *launches) {
     pbrt_ctx *c = s->ctx;
-    const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
-    a.lds_bytes = lds ? s->lds_bytes : 0u;
-    a.stk_rows = p.rows;
-    a.stk_shift = 0;
-    while ((1u << a.stk_shift) < p.threads) ++a.stk_shift;
-    if (!(a.guard = wf_guard(c))) return PBRT_E_NOMEM;
+    if (!wf_tree_args(s, p, &a)) return PBRT_E_NOMEM;
     a.vis_q = 4;
-    // the small shading tables in LDS when they fit (kernels_wavefront.h wf_tables_lds)
-    const bool tabs = s->ds.n_mats <= TAB_MAX && s->ds.n_emitters <= TAB_MAX && s->ds.n_light_prims <= TAB_MAX;
     const WfSplit sp = wf_split_env();
     const bool split = sp.s != 0 && c->n_cu == 256 && nreg >= 64u * sp.parts && a.max_depth <= 32;
     const uint32_t parts = split ? sp.parts : 1u;
@@ -991,19 +998,18 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
             HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
             c->sync_ev.push_back(e);
         }
-    float4 *in = b.stA, *out = b.stB, *shi = b.shA, *sho = b.shB;
-    uint32_t *sin = b.segA, *sout = b.segB, *ni = b.nshA, *no = b.nshB;
+    WfPing pp(b);
     auto fill = [&](uint32_t depth, bool have_shadows, uint32_t h) {
         a.depth = depth;
-        a.st_in = in;
-        a.st_out = out;
+        a.st_in = pp.in;
+        a.st_out = pp.out;
         a.hit_id = b.hit_id;
-        a.shd_in = shi;
-        a.shd_out = sho;
-        a.seg_in = sin;
-        a.seg_out = sout;
-        a.nsh_in = have_shadows ? ni : nullptr;
-        a.nsh_out = no;
+        a.shd_in = pp.shi;
+        a.shd_out = pp.sho;
+        a.seg_in = pp.sin;
+        a.seg_out = pp.sout;
+        a.nsh_in = have_shadows ? pp.ni : nullptr;
+        a.nsh_out = pp.no;
         a.region0 = reg0[h];
         a.n_regions = regn[h];
     };
@@ -1016,26 +1022,8 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
     };
     auto shade = [&](uint32_t depth, bool first, bool have_shadows, uint32_t h) {
         fill(depth, have_shadows, h);
-        hipStream_t st = st_s;
-        const dim3 g(regn[h]), t(WF_SHADE_THREADS);
-        if (first) {
-            if (tabs)
-                wf_launch_shade<true, true>(s->cylinders, s->glossy, g, t, st, a);
-            else
-                wf_launch_shade<true, false>(s->cylinders, s->glossy, g, t, st, a);
-        } else {
-            if (tabs)
-                wf_launch_shade<false, true>(s->cylinders, s->glossy, g, t, st, a);
-            else
-                wf_launch_shade<false, false>(s->cylinders, s->glossy, g, t, st, a);
-        }
+        hipLaunchKernelGGL(shade_kernel(s, first), dim3(regn[h]), dim3(WF_SHADE_THREADS), 0, st_s, a);
         ++*launches;
-    };
-    auto flip = [&]() {
-        std::swap(in, out);
-        std::swap(shi, sho);
-        std::swap(sin, sout);
-        std::swap(ni, no);
     };
     if (split) {  // both masked streams start behind whatever the context's stream holds
         hipEvent_t e0 = c->sync_ev[2u * parts];
@@ -1056,12 +1044,12 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
             shade(depth, first, depth > 0, h);
             if (split) HIPCHK(c, hipEventRecord(c->sync_ev[2u * h + 1u], st_s));
         }
-        flip();
+        pp.flip();
         HIPCHK(c, hipGetLastError());
         // unbounded depth (Mitsuba max_depth = -1): poll the live count every 8 bounces (never split: one stream)
         if (a.max_depth > 32 && (depth & 7u) == 7u) {
             uint64_t live;
-            if (int rc = live_paths(c, sin, nreg, &live)) return rc;
+            if (int rc = live_paths(c, pp.sin, nreg, &live)) return rc;
             if (live == 0) {
                 flush = depth + 1 < a.max_depth;  // the last bounce may have left shadow rays behind
                 a.depth = depth + 1;
@@ -1073,7 +1061,7 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
         const uint32_t d = a.depth;
         trace(d, false, true, 0);
         shade(d, false, true, 0);
-        flip();
+        pp.flip();
         HIPCHK(c, hipGetLastError());
     }
     if (split)  // the context's stream goes on (film gather) when every part has been shaded
@@ -1567,14 +1555,9 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
                     hipLaunchKernelGGL(k_chain_pair<ACCEL_K_BRUTE>, dim3(g2), dim3(SEG_BRUTE), 0, st, a);
                 else
                     hipLaunchKernelGGL(k_chain_pair<ACCEL_K_BRUTE_BIG>, dim3(g2), dim3(SEG_BRUTE), 0, st, a);
-            } else if (walk) {
-                if (depth == 0)
-                    launch_walk<true>(s, a, nseg_pass, nb);
-                else
-                    launch_walk<false>(s, a, nseg_pass, nb);
             } else
 #endif
-            if ((rc = depth == 0 ? launch_bounce<true>(s, a, nseg_pass, nb) : launch_bounce<false>(s, a, nseg_pass, nb)) != 0) return rc;
+            if ((rc = launch_bounce(s, a, nseg_pass, depth == 0, nb, walk)) != 0) return rc;
             HIPCHK(c, hipGetLastError());
             ++launches;
             if (walk) break;
@@ -1780,7 +1763,7 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
         a.out = out;
         a.seg_in = sin;
         a.seg_out = sout;
-        if ((rc = launch_bounce<false>(s, a, nseg)) != 0) return rc;
+        if ((rc = launch_bounce(s, a, nseg, false)) != 0) return rc;
         HIPCHK(c, hipGetLastError());
         std::swap(in, out);
         std::swap(sin, sout);
@@ -1831,67 +1814,32 @@ static uint32_t us_kernel_quirks(const UsArgs &a) {
     const uint32_t q = a.p.quirks & ~host_only;
     return (q == PBRT_USQ_REFERENCE || q == (PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER)) ? q : US_Q_RUNTIME;
 }
-template <bool FIRST, int ACCEL, bool EMIT>
-static void launch_us_instance(const UsArgs &a, uint32_t nseg, uint32_t threads, size_t lds, hipStream_t st) {
-    const uint32_t q = us_kernel_quirks(a);
-    const int tab = !FIRST ? -1 : (a.first_hit && a.first_rx) ? 1 : (!a.first_hit && !a.first_rx) ? 0 : -1;
-#define US_LAUNCH(QQ, TT) hipLaunchKernelGGL((k_us_bounce<FIRST, ACCEL, EMIT, QQ, TT>), dim3(nseg), dim3(threads), lds, st, a)
-    if constexpr (ACCEL == ACCEL_K_BRUTE) {  // the kernels of BASELINE config 3 (both readings) and of the reference's own loop
-        if (q != US_Q_RUNTIME && (tab >= 0 || !FIRST)) {
-            const bool carrier = q == PBRT_USQ_REFERENCE;
-            if constexpr (!FIRST) {
-                if (carrier) US_LAUNCH(PBRT_USQ_REFERENCE, -1); else US_LAUNCH(PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER, -1);
-            } else if constexpr (EMIT) {  // (emitter rays: never any tables)
-                if (carrier) US_LAUNCH(PBRT_USQ_REFERENCE, 0); else US_LAUNCH(PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER, 0);
-            } else {
-                if (tab == 1) {
-                    if (carrier) US_LAUNCH(PBRT_USQ_REFERENCE, 1); else US_LAUNCH(PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER, 1);
-                } else {
-                    if (carrier) US_LAUNCH(PBRT_USQ_REFERENCE, 0); else US_LAUNCH(PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER, 0);
-                }
-            }
-            return;
-        }
-    }
-    US_LAUNCH(US_Q_RUNTIME, -1);
-#undef US_LAUNCH
-}
-
-template <bool FIRST>
-static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg) {
-    hipStream_t st = s->ctx->stream;
-    if (a.p.primary == PBRT_US_PRIMARY_EMITTER) {  // primary rays from CustomEmitter.sample_ray, echoes times the ray's weight
-        switch (s->accel_kernel) {
-            case ACCEL_K_BRUTE:
-                launch_us_instance<FIRST, ACCEL_K_BRUTE, true>(a, nseg, SEG_BRUTE, 0, st);
-                return PBRT_OK;
-            case ACCEL_K_BRUTE_BIG:
-                launch_us_instance<FIRST, ACCEL_K_BRUTE_BIG, true>(a, nseg, SEG_BRUTE, 0, st);
-                return PBRT_OK;
-            default:
-                return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: emitter primary rays on BVH scenes run as streams (us_wf_pass)");
-        }
-    }
-    switch (s->accel_kernel) {
-        case ACCEL_K_BRUTE:
-            launch_us_instance<FIRST, ACCEL_K_BRUTE, false>(a, nseg, SEG_BRUTE, 0, st);
-            break;
-        case ACCEL_K_BRUTE_BIG:
-            launch_us_instance<FIRST, ACCEL_K_BRUTE_BIG, false>(a, nseg, SEG_BRUTE, 0, st);
-            break;
-#ifdef PBRT_DIAG  // the fused ultrasound bounce on BVH scenes (PBRT_US_FUSED_BVH=1): diagnostic build only
-        case ACCEL_K_BVH_GLOBAL:
-            launch_us_instance<FIRST, ACCEL_K_BVH_GLOBAL, false>(a, nseg, SEG_BVH, 0, st);
-            break;
-        default:
-            launch_us_instance<FIRST, ACCEL_K_BVH_LDS, false>(a, nseg, SEG_BVH, s->lds_bytes, st);
-            break;
-#else
-        default:  // BVH scenes run k_trace / k_us_shade (us_wf_pass)
-            return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: no fused ultrasound bounce for accelerator %d in this build", s->accel_kernel);
-#endif
-    }
+static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg, bool first) {
+    const bool emit = a.p.primary == PBRT_US_PRIMARY_EMITTER;  // primary rays from CustomEmitter.sample_ray, echoes times the ray's weight
+    const int tab = (a.first_hit && a.first_rx) ? 1 : (!a.first_hit && !a.first_rx) ? 0 : -1;
+    const UsKern k = us_bounce_kernel(s, first, emit, us_kernel_quirks(a), tab);
+    if (!k && emit)
+        return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: emitter primary rays on BVH scenes run as streams (us_wf_pass)");
+    if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: no fused ultrasound bounce for accelerator %d in this build", s->accel_kernel);
+    const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
+    hipLaunchKernelGGL(k, dim3(nseg), dim3(seg_threads(s->accel_kernel)), lds ? s->lds_bytes : 0u, s->ctx->stream, a);
     return PBRT_OK;
+}
+// The kernels that meet one ray with the scene and nothing else (first-bounce tables, leaf operators): the brute-force loop over
+// the full tables, or the tree in global memory
+static bool brute_scene(const pbrt_scene *s) { return s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG; }
+static UsFirstKern us_first_kernel(const pbrt_scene *s) {
+    return brute_scene(s) ? &k_us_first<ACCEL_K_BRUTE_BIG> : &k_us_first<ACCEL_K_BVH_GLOBAL>;
+}
+static RayIntersectKern ray_intersect_kernel(const pbrt_scene *s) {
+    return brute_scene(s) ? &k_ray_intersect<ACCEL_K_BRUTE_BIG> : &k_ray_intersect<ACCEL_K_BVH_GLOBAL>;
+}
+static RayTestKern ray_test_kernel(const pbrt_scene *s) {
+    return brute_scene(s) ? &k_ray_test<ACCEL_K_BRUTE_BIG> : &k_ray_test<ACCEL_K_BVH_GLOBAL>;
+}
+// k_us_shade: first bounce from the tables, scene with cylinders
+static UsWfKern us_shade_kernel(const pbrt_scene *s, bool tab) {
+    return with_flags([](auto T, auto C) -> UsWfKern { return &k_us_shade<T(), C()>; }, tab, s->cylinders);
 }
 
 // BVH scenes: the bounces of one ultrasound pass as k_trace / k_us_shade streams (kernels_us_wavefront.h).  a: the pass's UsArgs
@@ -1907,71 +1855,52 @@ static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p,
     t.key_mode = 0;
     t.vis_q = US_WF_VIS_Q;
     t.hit_id = b.hit_id;
-    t.lds_bytes = s->accel_kernel == ACCEL_K_BVH_LDS ? s->lds_bytes : 0u;
-    t.stk_rows = p.rows;
-    t.stk_shift = 0;
-    while ((1u << t.stk_shift) < p.threads) ++t.stk_shift;
     t.region0 = 0;
     t.n_regions = nreg;
-    if (!(t.guard = wf_guard(c))) return PBRT_E_NOMEM;
+    if (!wf_tree_args(s, p, &t)) return PBRT_E_NOMEM;
     UsWfArgs w{};
     w.hit_id = b.hit_id;
     w.region0 = 0;
     w.n_regions = nreg;
     w.guard = t.guard;
-    float4 *in = b.stA, *out = b.stB, *shi = b.shA, *sho = b.shB;
-    uint32_t *sin = b.segA, *sout = b.segB, *ni = b.nshA, *no = b.nshB;
+    WfPing pp(b);
     auto trace = [&](uint32_t depth, bool have_shadows) {
         t.depth = depth;
-        t.st_in = in;
-        t.shd_in = shi;
-        t.seg_in = sin;
-        t.nsh_in = have_shadows ? ni : nullptr;
+        t.st_in = pp.in;
+        t.shd_in = pp.shi;
+        t.seg_in = pp.sin;
+        t.nsh_in = have_shadows ? pp.ni : nullptr;
         wf_launch_trace(s, t, p, wf_trace_grid(nreg, depth >= 2 ? p.grid_deep : p.grid_mult, (uint32_t)c->n_cu), false, st);
         ++*launches;
     };
     auto shade = [&](uint32_t depth, bool tab, bool have_shadows) {
         a.depth = depth;
         w.u = a;
-        w.st_in = in;
-        w.st_out = out;
-        w.shd_in = shi;
-        w.shd_out = sho;
-        w.seg_in = sin;
-        w.seg_out = sout;
-        w.nsh_in = have_shadows ? ni : nullptr;
-        w.nsh_out = no;
-        const dim3 g(nreg), t(WF_SHADE_THREADS);
-        if (tab && s->cylinders)
-            hipLaunchKernelGGL((k_us_shade<true, true>), g, t, 0, st, w);
-        else if (tab)
-            hipLaunchKernelGGL((k_us_shade<true, false>), g, t, 0, st, w);
-        else if (s->cylinders)
-            hipLaunchKernelGGL((k_us_shade<false, true>), g, t, 0, st, w);
-        else
-            hipLaunchKernelGGL((k_us_shade<false, false>), g, t, 0, st, w);
+        w.st_in = pp.in;
+        w.st_out = pp.out;
+        w.shd_in = pp.shi;
+        w.shd_out = pp.sho;
+        w.seg_in = pp.sin;
+        w.seg_out = pp.sout;
+        w.nsh_in = have_shadows ? pp.ni : nullptr;
+        w.nsh_out = pp.no;
+        hipLaunchKernelGGL(us_shade_kernel(s, tab), dim3(nreg), dim3(WF_SHADE_THREADS), 0, st, w);
         ++*launches;
-    };
-    auto flip = [&]() {
-        std::swap(in, out);
-        std::swap(shi, sho);
-        std::swap(sin, sout);
-        std::swap(ni, no);
     };
     const bool tab = a.first_hit != nullptr && a.first_rx != nullptr;
     if (tab) {
         shade(0, true, false);
     } else {
-        hipLaunchKernelGGL(k_us_init_wf, dim3(div_up(std::max(a.n_paths, nreg), 256)), dim3(256), 0, st, a, in, sin, nreg);
+        hipLaunchKernelGGL(k_us_init_wf, dim3(div_up(std::max(a.n_paths, nreg), 256)), dim3(256), 0, st, a, pp.in, pp.sin, nreg);
         trace(0, false);
         shade(0, false, false);
     }
-    flip();
+    pp.flip();
     HIPCHK(c, hipGetLastError());
     for (uint32_t depth = 1; depth < a.p.max_depth; ++depth) {
         trace(depth, true);
         shade(depth, false, true);
-        flip();
+        pp.flip();
         HIPCHK(c, hipGetLastError());
     }
     // the occlusion rays of the last bounce (every path has ended: records of ended paths only), and their echoes
@@ -2085,7 +2014,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     if ((!streams && (!segA || !segB)) || !dstats || !tabs) return PBRT_E_NOMEM;
     hipStream_t st = c->stream;
     float *d_tx = tabs, *d_dir = tabs + n_rays, *d_ex = d_dir + 3 * NA;
-    // emitter rays are drawn inside the first-bounce instance (k_us_bounce<true, ., EMIT>: 17.1 against 18.4 ms since the echo table
+    // emitter rays are drawn inside the first-bounce instance (the EMIT instances of k_us_bounce: 17.1 against 18.4 ms since the echo table
     // grew); PBRT_US_EMIT_FUSED=0 (A/B, test) writes them into the path state first (k_us_emit_init) and walks every bounce with the
     // later-bounce instance.  (Two default bench runs of this form showed steps of 38 - 43 ms; host stalls of that size hit the
     // two-kernel form as well and went away when bench.py took Python's cyclic collector out of its timed steps: three runs of
@@ -2152,10 +2081,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         float4 *fv = (float4 *)c->buf("us_first_rx", (size_t)n_rays * NE * 16);
         if (!fh || !fv) return PBRT_E_NOMEM;
         const dim3 g(div_up((uint64_t)n_rays * NE, 256)), b(256);
-        if (s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG)
-            hipLaunchKernelGGL(k_us_first<ACCEL_K_BRUTE_BIG>, g, b, 0, st, a, n_rays, fh, fv);
-        else
-            hipLaunchKernelGGL(k_us_first<ACCEL_K_BVH_GLOBAL>, g, b, 0, st, a, n_rays, fh, fv);
+        hipLaunchKernelGGL(us_first_kernel(s), g, b, 0, st, a, n_rays, fh, fv);
         HIPCHK(c, hipGetLastError());
         a.first_hit = fh;
         a.first_rx = fv;
@@ -2206,7 +2132,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
                 a.seg_out = sout;
                 first_kernel = false;
             }
-            if ((rc = first_kernel ? launch_us<true>(s, a, nseg_pass) : launch_us<false>(s, a, nseg_pass)) != 0) return rc;
+            if ((rc = launch_us(s, a, nseg_pass, first_kernel)) != 0) return rc;
             HIPCHK(c, hipGetLastError());
             ++launches;
             if (a.fuse) break;  // that launch walked every bounce (kernels_us.h)
@@ -2391,10 +2317,7 @@ int pbrt_ray_intersect(pbrt_scene *s, uint32_t n, const float *o, const float *d
     float *dO = S.in(o, 3 * (size_t)n), *dD = S.in(d, 3 * (size_t)n), *dT = S.in(tmax, n);
     float *rt = S.out<float>(n), *ru = S.out<float>(n), *rv = S.out<float>(n);
     uint32_t *rp = S.out<uint32_t>(n);
-    if (s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG)
-        hipLaunchKernelGGL(k_ray_intersect<ACCEL_K_BRUTE_BIG>, grid, block, 0, st, s->ds, n, dO, dD, dT, rt, rp, ru, rv);
-    else
-        hipLaunchKernelGGL(k_ray_intersect<ACCEL_K_BVH_GLOBAL>, grid, block, 0, st, s->ds, n, dO, dD, dT, rt, rp, ru, rv);
+    hipLaunchKernelGGL(ray_intersect_kernel(s), grid, block, 0, st, s->ds, n, dO, dD, dT, rt, rp, ru, rv);
     S.back(t, rt, n);
     S.back(prim, rp, n);
     S.back(u, ru, n);
@@ -2408,10 +2331,7 @@ int pbrt_ray_test(pbrt_scene *s, uint32_t n, const float *o, const float *d, con
     LEAF_BEGIN(s->ctx, (size_t)n * 4 * 9);
     float *dO = S.in(o, 3 * (size_t)n), *dD = S.in(d, 3 * (size_t)n), *dT = S.in(tmax, n);
     uint8_t *rh = S.out<uint8_t>(n);
-    if (s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG)
-        hipLaunchKernelGGL(k_ray_test<ACCEL_K_BRUTE_BIG>, grid, block, 0, st, s->ds, n, dO, dD, dT, rh);
-    else
-        hipLaunchKernelGGL(k_ray_test<ACCEL_K_BVH_GLOBAL>, grid, block, 0, st, s->ds, n, dO, dD, dT, rh);
+    hipLaunchKernelGGL(ray_test_kernel(s), grid, block, 0, st, s->ds, n, dO, dD, dT, rh);
     S.back(hit, rh, n);
     return S.finish();
 }
@@ -2573,17 +2493,9 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    if (p->interpolation == PBRT_DAS_NEAREST) {
-        if (ttx)
-            hipLaunchKernelGGL((k_das_beamform<PBRT_DAS_NEAREST, true>), grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
-        else
-            hipLaunchKernelGGL((k_das_beamform<PBRT_DAS_NEAREST, false>), grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
-    } else {
-        if (ttx)
-            hipLaunchKernelGGL((k_das_beamform<PBRT_DAS_LINEAR, true>), grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
-        else
-            hipLaunchKernelGGL((k_das_beamform<PBRT_DAS_LINEAR, false>), grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
-    }
+    const auto kernel = with_flags([](auto L, auto T) { return &k_das_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T()>; },
+                                   p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr);
+    hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
     c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * 4;
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
