@@ -229,24 +229,32 @@ def test_emitting_box_around_a_diffuse_tube(mi, capi, integrator, accel):
 
 
 # ---- 4. echo arrival bins -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tables", [True, False])
-def test_vessel_echo_arrival_bins(mi, capi, tables):
-    """a vessel whose axis lies along the probe's elevation direction, depth D, radius r, one bounce, unsteered, an odd element count
-    (one element on the axis): element e with |x_e| < r hits at z_h = D - sqrt(r^2 - x_e^2) and its echo at receiver j arrives in bin
-    round(fs (z_h + sqrt((x_j - x_e)^2 + z_h^2)) / c) within one; nothing else is heard, and the earliest bin is round(2 (D - r) / c fs)"""
+V_D, V_R, V_C, V_FS, V_N, V_PITCH, V_T = 0.03, 0.004, 1540.0, 50e6, 15, 3e-4, 3000    # the vessel scene: depth, radius, c, fs, elements
+
+
+def _vessel_scene(mi, max_depth=1, attenuation=0.0, emitter=False, x0=0.0):
+    """a vessel whose axis lies along the probe's elevation direction at x = x0, unsteered, an odd element count (one element on the
+    axis when x0 = 0);
+    emitter=True adds an ultrasound_emitter without jitter: point elements, one steering angle of 0 degrees, three rays per element
+    (every one the integrator's own ray, weight 1 / (N * 3)); the integrator keeps its own rays until primary_rays is set"""
     T = mi.ScalarTransform4f
-    D, r, c, fs, N, pitch, n_t = 0.03, 0.004, 1540.0, 50e6, 15, 3e-4, 3000
     d = {"type": "scene",
-         "integrator": {"type": "ultrasound_integrator", "max_depth": 1, "sampling_rate": fs, "frequency": 5e6, "sound_speed": c,
-                        "attenuation": 0.0, "main_beam_angle": 80, "cutoff_angle": 85, "n_elements": N, "pitch": pitch,
-                        "time_samples": n_t, "angles": np.array([0.0], np.float32)},
+         "integrator": {"type": "ultrasound_integrator", "max_depth": max_depth, "sampling_rate": V_FS, "frequency": 5e6, "sound_speed": V_C,
+                        "attenuation": attenuation, "main_beam_angle": 80, "cutoff_angle": 85, "n_elements": V_N, "pitch": V_PITCH,
+                        "time_samples": V_T, "angles": np.array([0.0], np.float32)},
          "sensor": {"type": "ultrasound_sensor", "to_world": T().look_at([0, 0, 0], [0, 0, 0.03], [0, 1, 0])},
-         "vessel": {"type": "cylinder", "p0": [0, -0.05, D], "p1": [0, 0.05, D], "radius": r,
+         "vessel": {"type": "cylinder", "p0": [x0, -0.05, V_D], "p1": [x0, 0.05, V_D], "radius": V_R,
                     "bsdf": {"type": "ultrasound_bsdf", "impedance": 7.8, "roughness": 0.7}}}
-    sc = mi.load_dict(d)
-    ui = sc.integrator()
-    q = ui.quirks | (0 if tables else capi.USQ_NO_FIRST_TABLES)
-    buf = ui._acquire(sc, q, paths_per_ray=300, seed=5)
+    if emitter:
+        d["emitter"] = {"type": "ultrasound_emitter", "number_of_elements": V_N, "pitch": V_PITCH, "element_width": 0.0, "element_height": 0.0,
+                        "number_of_rays_per_element": 3, "speed_of_sound": V_C, "steering_angle_min": 0.0, "steering_angle_max": 0.0}
+    return mi.load_dict(d)
+
+
+def _check_vessel_arrival_bins(ui, buf):
+    """element e with |x_e| < r hits at z_h = D - sqrt(r^2 - x_e^2) and its echo at receiver j arrives in bin
+    round(fs (z_h + sqrt((x_j - x_e)^2 + z_h^2)) / c) within one; nothing else is heard, and the earliest bin is round(2 (D - r) / c fs)"""
+    D, r, c, fs, N, n_t = V_D, V_R, V_C, V_FS, V_N, V_T
     assert buf.shape == (1, N, n_t)
     ex = ui.elem_x.numpy().astype(np.float64)
     assert np.any(np.abs(ex) < 1e-12) and np.abs(ex).max() < r
@@ -260,6 +268,59 @@ def test_vessel_echo_arrival_bins(mi, capi, tables):
     nz = buf[0] != 0
     assert nz.sum() >= N and nz.any(axis=1).all() and not np.any(nz & ~allowed)
     assert np.argwhere(nz)[:, 1].min() == int(np.rint(2 * (D - r) / c * fs))
+
+
+@pytest.mark.parametrize("tables", [True, False])
+def test_vessel_echo_arrival_bins(mi, capi, tables):
+    """the vessel scene at depth D, radius r, one bounce: the arrival bins of _check_vessel_arrival_bins, with and without the
+    first-bounce tables"""
+    sc = _vessel_scene(mi)
+    ui = sc.integrator()
+    q = ui.quirks | (0 if tables else capi.USQ_NO_FIRST_TABLES)
+    _check_vessel_arrival_bins(ui, ui._acquire(sc, q, paths_per_ray=300, seed=5))
+
+
+@pytest.mark.parametrize("accel", ["brute", "bvh"])
+def test_vessel_echo_arrival_bins_with_emitter_rays(mi, capi, accel):
+    """the same bins when every path's primary ray comes from the jitter-free emitter: drawn inside k_us_bounce<true, _BIG, true>
+    (brute force), written by k_us_init_wf for k_trace + k_us_shade<., true> (the BVH streams); a ray from another element's origin
+    lands outside the allowed bins"""
+    sc = _vessel_scene(mi, emitter=True)
+    sc.accel = _accel(capi, accel)
+    ui = sc.integrator()
+    ui.primary_rays = "emitter"
+    assert ui.us_params(sc).primary == capi.US_PRIMARY_EMITTER
+    _check_vessel_arrival_bins(ui, ui._acquire(sc, ui.quirks, paths_per_ray=300, seed=5))
+
+
+@pytest.mark.parametrize("accel", ["brute", "bvh"])
+def test_vessel_emitter_rays_without_jitter_are_the_integrators_own_rays(mi, capi, accel):
+    """test_gpu_analytic.py::test_emitter_rays_without_jitter_are_the_integrators_own_rays on the vessel, four bounces: the emitter
+    without jitter draws exactly the integrator's own primary ray, so every path is the same path and every echo the integrator's
+    times the ray's weight 1 / (15 * 3).  The bounds are that test's: the emitter places its elements with linspace, the integrator
+    with pitch * (i - (N - 1) / 2), positions that can differ in the last bit, so a roulette or time-bin decision may fall the other
+    way for a path in a million.
+    The vessel's axis lies half a pitch beside the probe's: with it at x = 0 the integrator's middle element (x = 0 exactly) meets the
+    wall at exactly normal incidence, where the reference's literal arithmetic gives NaN echoes and ends the path,
+    while the emitter's middle element lies at x = -5.8e-11 and goes on -- measured there, brute force and BVH alike: 15 NaN bins and
+    1984 segments with the integrator's own rays, none and 2054 with the emitter's, rel. L2 7e-8 on the other bins.  Measured here:
+    2058 segments on both sides, rel. L2 2.3e-6."""
+    ppr = 96
+    sc = _vessel_scene(mi, max_depth=4, attenuation=0.1, emitter=True, x0=V_PITCH / 2)
+    sc.accel = _accel(capi, accel)
+    ui = sc.integrator()
+    own = ui._acquire(sc, ui.quirks, paths_per_ray=ppr, seed=4)
+    st_own = mi.default_context().stats()
+    ui.primary_rays = "emitter"
+    assert ui.us_params(sc).primary == capi.US_PRIMARY_EMITTER
+    em = ui._acquire(sc, ui.quirks, paths_per_ray=ppr, seed=4)
+    st_em = mi.default_context().stats()
+    w = 1.0 / (V_N * 3)
+    assert st_own["segments"] >= V_N * ppr and abs(st_em["segments"] - st_own["segments"]) <= 1e-3 * st_own["segments"]
+    assert all(abs(a - b) <= 1e-3 * max(b, 1) + 2 for a, b in zip(st_em["live"], st_own["live"]))
+    assert np.isfinite(own).all() and np.abs(own).max() > 0 and np.mean((em != 0) == (own != 0)) > 0.9999
+    ref = own.astype(np.float64) * w
+    assert np.linalg.norm(em - ref) <= 1e-3 * np.linalg.norm(ref)
 
 
 # ---- 5. the vessel phantom ------------------------------------------------------------------------------------------------------
@@ -299,8 +360,48 @@ def test_vessel_phantom_path_sharding_adds_up(mi):
     assert _rel_l2(a + b, full) <= 1e-5 and np.array_equal((a + b) != 0, full != 0)
 
 
-def test_vessel_phantom_emitter_primary_rays(mi):
-    sc = mi.load_file(scene_path("us_vessel_box.xml"), primary_rays="emitter", paths_per_ray=256, seed=3)
-    ui = sc.integrator()
-    buf = ui._acquire(sc, ui.quirks)
+def _emitter_vessel_phantom(mi, capi, accel, ppr, seed):
+    sc = mi.load_file(scene_path("us_vessel_box.xml"), primary_rays="emitter", paths_per_ray=ppr, seed=seed)
+    sc.accel = _accel(capi, accel)
+    return sc, sc.integrator()
+
+
+def test_vessel_phantom_emitter_primary_rays(mi, capi, monkeypatch):
+    """emitter rays on the vessel phantom by three routes of ray generation: drawn inside the fused brute-force bounce
+    (k_us_bounce<true, _BIG, true>), written by k_us_init_wf for the BVH streams with the tree in LDS and in global memory -- the
+    same echoes, by the criteria of test_vessel_phantom_fused_bounce_against_the_bvh_streams; and on the brute-force scene the rays
+    through k_us_emit_init and the path state (PBRT_US_EMIT_FUSED=0): one computation in two instances, by the criterion of
+    test_gpu_ultrasound.py::test_specialised_and_generic_bounce_kernels_agree.
+    Measured: rel. L2 2.6e-8 for both BVH routes against brute force, far below the 1e-3 this comparison is held to."""
+    ctx = mi.default_context()
+    bufs, stats = {}, {}
+    for name in ("brute", "bvh", "bvh_global"):
+        sc, ui = _emitter_vessel_phantom(mi, capi, name, 256, 3)
+        assert ui.us_params(sc).primary == capi.US_PRIMARY_EMITTER
+        bufs[name] = ui._acquire(sc, ui.quirks)
+        stats[name] = ctx.stats()
+    buf = bufs["brute"]
     assert buf.shape == (5, 64, 10000) and np.isfinite(buf).all() and (buf != 0).sum() > 1000
+    for name in ("bvh", "bvh_global"):
+        print(f"\nemitter rays on the vessel phantom, {name} against brute: rel. L2 {_rel_l2(bufs[name], buf):.3g}")
+        assert np.isfinite(bufs[name]).all() and np.array_equal(bufs[name] != 0, buf != 0), name
+        assert _rel_l2(bufs[name], buf) <= 1e-3, name
+    assert stats["bvh"]["bounce_launches"] > 1 and stats["bvh_global"]["bounce_launches"] > 1
+    sc, ui = _emitter_vessel_phantom(mi, capi, "brute", 256, 3)
+    monkeypatch.setenv("PBRT_US_EMIT_FUSED", "0")
+    unfused = ui._acquire(sc, ui.quirks)
+    st_u = ctx.stats()
+    monkeypatch.delenv("PBRT_US_EMIT_FUSED")
+    st = stats["brute"]
+    assert (st_u["segments"], st_u["shadow_rays"], st_u["live"]) == (st["segments"], st["shadow_rays"], st["live"]) and st["segments"] > 0
+    assert np.array_equal(unfused != 0, buf != 0) and np.allclose(unfused, buf, rtol=2e-5, atol=1e-7 * np.abs(buf).max())
+
+
+def test_vessel_phantom_emitter_rays_path_sharding_adds_up(mi, capi):
+    """a path's emitter ray is a function of its index in the whole acquisition (path_offset + k), not of the call it is drawn in"""
+    sc, ui = _emitter_vessel_phantom(mi, capi, "brute", 300, 6)
+    full = ui._acquire(sc, ui.quirks, paths_per_ray=300, seed=6)
+    a = ui._acquire(sc, ui.quirks, paths_per_ray=100, path_offset=0, norm_paths=300, seed=6)
+    b = ui._acquire(sc, ui.quirks, paths_per_ray=200, path_offset=100, norm_paths=300, seed=6)
+    assert (full != 0).sum() > 1000
+    assert _rel_l2(a + b, full) <= 1e-5 and np.array_equal((a + b) != 0, full != 0)

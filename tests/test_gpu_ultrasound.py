@@ -375,6 +375,33 @@ def test_emitter_primary_rays_on_a_mesh_phantom_and_their_refusals(mi, ob, capi)
         ui.us_params(sc)
 
 
+@pytest.mark.parametrize("kw", [{}, dict(tessellate="true")], ids=["analytic", "tessellated"])
+def test_emitter_primary_rays_on_the_cone_phantom(mi, ob, capi, kw):
+    """PBRT_US_PRIMARY_EMITTER on the reference's cone phantom, which holds no ultrasound_emitter of its own: as one analytic cone
+    (brute force: k_us_bounce<., ACCEL_K_BRUTE_BIG, true> draws the rays) and tessellated (896 triangles: k_us_init_wf writes them,
+    then k_trace + k_us_shade), against the oracle; the echoes carry the ray's weight 1 / (64 * 64)"""
+    ppr = 64
+    sc = mi.load_file(scene_path("us_cone_box.xml"), paths_per_ray=ppr, seed=14, **kw)
+    ui = sc.integrator()
+    assert (len(sc.flatten()["prims"]) > 32) == bool(kw)
+    own = ui._acquire(sc, ui.quirks)
+    em = mi.CustomEmitter(mi.Properties("ultrasound_emitter", dict(number_of_elements=ui.n_elements, pitch=ui.pitch, element_width=1e-4,
+                                                                   element_height=4e-4, number_of_rays_per_element=ppr, speed_of_sound=ui.sound_speed,
+                                                                   steering_angle_min=-12.0, steering_angle_max=12.0)))
+    sc._emitters.append(em)
+    ui.primary_rays = "emitter"
+    p = ui.us_params(sc)
+    assert p.primary == capi.US_PRIMARY_EMITTER and p.emitter.number_of_elements == ui.n_elements
+    got = ui._acquire(sc, ui.quirks)
+    st = mi.default_context().stats()
+    ref, tx, tol = oracle(ob, sc, p, 14, ppr)
+    check(got, ref, tol)
+    assert np.array_equal(ui.transmission_delays_buf, tx)
+    assert st["samples"] == ui.n_angles * ui.n_elements * ppr and (st["bounce_launches"] > 1) == bool(kw)
+    assert np.abs(got).max() > 0 and (got != 0).sum() > 1000
+    assert np.abs(got).max() < 0.01 * np.abs(own).max()
+
+
 @pytest.mark.parametrize("scene,ppr", [("us_sphere_box.xml", 128), ("us_sphere_box.xml", 24), ("us_plate.xml", 200)])
 def test_specialised_and_generic_bounce_kernels_agree(mi, capi, monkeypatch, scene, ppr):
     """k_us_bounce exists with the library's default switches compiled in (PBRT_USQ_REFERENCE, with / without the carrier; with /

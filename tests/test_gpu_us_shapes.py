@@ -8,7 +8,11 @@ What the shapes reach (csrc/device_math.h, csrc/kernels_us.h, csrc/pbrt_api.hip 
 - paths per ray at E - 1, E, E + 1: the first-bounce tables switch on at ppr >= E; with them and with PBRT_USQ_NO_FIRST_TABLES;
 - time_samples 1, 2, 17 with most echoes past the end (the tf < T drop) and the same with PBRT_USQ_CLAMP_TIME (every echo piles
   into the last bin: many echoes per channel word in the echo table); 2047, 2048, 2049 across the echoes; a 20 000-sample trace;
-- emitter primary rays (EMIT instances) at E = 128, A = 1 and E = 33, A = 9, where the region permutation engages, and without it;
+- emitter primary rays (EMIT instances) at E = 128, A = 1 and E = 33, A = 9, where the region permutation engages, and without it:
+  on the spheres and plates (k_us_bounce<., ACCEL_K_BRUTE, true>), beside an analytic cone (<., ACCEL_K_BRUTE_BIG, true>) and on the
+  BVH streams (k_us_init_wf writes the emitter's rays, then k_trace + k_us_shade);
+- with emitter rays, on the cone and the BVH phantom: the rays through k_us_emit_init and the path state (PBRT_US_EMIT_FUSED=0, brute
+  force only), one launch per bounce, the intent set (quirks = 0) and the Dr.Jit variant;
 - the generic (run-time quirks) instance and one launch per bounce at a non-default shape;
 - the BVH streams (k_trace + k_us_shade) at E = 1 and 128;
 - a pass split with a short last pass (div_ppr remade per pass), forced by a failing large allocation."""
@@ -25,8 +29,9 @@ def angles(n):
     return [0.0] if n == 1 else list(np.linspace(-20.0, 20.0, n))
 
 
-def run(mi, ob, case, kind, E, A, T, ppr, seed, quirks=0, emitter=False, max_depth=4, nonzero=True):
-    sc = uu.phantom(mi, kind, E, angles(A), T, ppr, seed, max_depth=max_depth, emitter=emitter)
+def run(mi, ob, case, kind, E, A, T, ppr, seed, quirks=0, emitter=False, max_depth=4, nonzero=True, ui_quirks=None):
+    """quirks: switches added to the integrator's set; ui_quirks: the integrator's set itself (None: PBRT_USQ_REFERENCE)"""
+    sc = uu.phantom(mi, kind, E, angles(A), T, ppr, seed, max_depth=max_depth, emitter=emitter, quirks=ui_quirks)
     ui = sc.integrator()
     q = ui.quirks | quirks
     buf = ui._acquire(sc, q)
@@ -88,6 +93,34 @@ def test_emitter_primary_rays(mi, ob, monkeypatch, E, A, ppr, permute):
     if not permute:
         monkeypatch.setenv("PBRT_US_EMIT_PERMUTE", "0")
     run(mi, ob, f"emit E={E} A={A} permute={permute}", "few", E, A, 4000, ppr, 16, emitter=True)
+
+
+@pytest.mark.parametrize("permute", [True, False])
+@pytest.mark.parametrize("E,A,ppr", [(128, 1, 400), (33, 9, 600)])
+@pytest.mark.parametrize("kind", ["cone", "bvh"])
+def test_emitter_primary_rays_on_cone_and_bvh_phantoms(mi, ob, monkeypatch, kind, E, A, ppr, permute):
+    """the shapes of test_emitter_primary_rays beside an analytic cone (brute force, the _BIG instances of k_us_bounce draw the rays)
+    and on 41 primitives (k_us_init_wf writes them into the path state of the streams)"""
+    assert -(-A * E * ppr // 8192) > 2 * A
+    if not permute:
+        monkeypatch.setenv("PBRT_US_EMIT_PERMUTE", "0")
+    _, _, st = run(mi, ob, f"emit {kind} E={E} A={A} permute={permute}", kind, E, A, 4000, ppr, 16, emitter=True)
+    assert (st["bounce_launches"] > 1) == (kind == "bvh")
+
+
+@pytest.mark.parametrize("kind,switch", [("cone", "unfused_rays"), ("cone", "per_bounce"), ("cone", "intent"), ("cone", "drjit"),
+                                         ("bvh", "per_bounce"), ("bvh", "intent"), ("bvh", "drjit")])
+def test_emitter_primary_rays_under_the_switches(mi, ob, capi, monkeypatch, kind, switch):
+    """emitter rays at E = 33, A = 9 with the rays written into the path state first (k_us_emit_init, then k_us_bounce<false, ., true>
+    from depth 0; PBRT_US_EMIT_FUSED is read for brute-force scenes only), one launch per bounce, the intent arithmetic and the
+    Dr.Jit variant (both through the run-time quirks instance)"""
+    if switch == "unfused_rays":
+        monkeypatch.setenv("PBRT_US_EMIT_FUSED", "0")
+    q = {"per_bounce": capi.USQ_NO_FUSED_BOUNCES, "drjit": capi.USQ_DRJIT_VARIANT}.get(switch, 0)
+    _, _, st = run(mi, ob, f"emit {kind} {switch}", kind, 33, 9, 4000, 600, 16, quirks=q, emitter=True,
+                   ui_quirks=0 if switch == "intent" else None)
+    if kind == "bvh" or switch == "per_bounce":
+        assert st["bounce_launches"] > 1
 
 
 @pytest.mark.parametrize("variant", ["generic", "per_bounce"])

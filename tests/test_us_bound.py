@@ -23,7 +23,8 @@ def acq(mi, ob, capi):
     return out
 
 
-@pytest.mark.parametrize("kind,emitter,quirks", [("plate", False, 0), ("few", False, 0x40), ("few", True, 0), ("bvh", False, 0x100)])
+@pytest.mark.parametrize("kind,emitter,quirks", [("plate", False, 0), ("few", False, 0x40), ("few", True, 0), ("bvh", False, 0x100),
+                                                ("cone", True, 0), ("bvh", True, 0)])
 def test_bounds_leave_the_channel_buffer_bit_for_bit(mi, ob, kind, emitter, quirks):
     sc = uu.phantom(mi, kind, 20, [-8.0, 0.0, 8.0], 3000, 40, 2, emitter=emitter)
     ui = sc.integrator()

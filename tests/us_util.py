@@ -92,6 +92,8 @@ def phantom(mi, kind, n_elements, angles, time_samples, ppr, seed, max_depth=4, 
              divides 0 by 0, DESIGN.md D12);
     "few":   two spheres and three plates between 15 and 55 mm, echoes over bins ~800 - 3000 (brute force, fused k_us_bounce);
     "bvh":   "few" and 36 small plates more: > 32 primitives, the BVH streams (k_trace + k_us_shade)
+    "cone":  "few" and one analytic cone between 21 and 28 mm, its base turned half towards the probe: at 128 elements the rays of
+             about 18 elements meet its base and those of 18 more its lateral surface (brute force, the _BIG instances of k_us_bounce)
     emitter=True adds an ultrasound_emitter with the probe's elements and primary_rays="emitter" (the EMIT instances)"""
     T = mi.ScalarTransform4f
     rng = np.random.default_rng(seed)
@@ -120,6 +122,11 @@ def phantom(mi, kind, n_elements, angles, time_samples, ppr, seed, max_depth=4, 
                 T().rotate([0, 1, 0], float(rng.uniform(-40, 40))) @ T().rotate([1, 0, 0], float(rng.uniform(150, 210))) @ \
                 T().scale([float(rng.uniform(0.001, 0.003)), float(rng.uniform(0.002, 0.005)), 1])
             d[f"q{i}"] = {"type": "rectangle", "to_world": tw, "bsdf": bsdf(float(rng.uniform(2, 8)), float(rng.uniform(0.3, 0.9)))}
+    if kind == "cone":     # the closed unit cone (apex (0, 0, 1), base disc of radius 1 at z = 0) under to_world
+        d["c"] = {"type": "cone", "to_world": T().translate([0.0065, 0.0005, 0.024]) @ T().rotate([1, 0, 0], 10) @ T().rotate([0, 1, 0], 60)
+                  @ T().scale([0.0035, 0.0035, 0.007]), "bsdf": bsdf(6.0, 0.7)}
     sc = mi.load_dict(d)
-    assert (len(sc.flatten()["prims"]) > 32) == (kind == "bvh")
+    P = sc.flatten()["prims"]
+    assert (len(P) > 32) == (kind == "bvh")
+    assert bool(np.any(P["type"] == mi._capi.PRIM_CONE)) == (kind == "cone")
     return sc
