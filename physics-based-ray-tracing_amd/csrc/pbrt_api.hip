@@ -17,14 +17,20 @@
 #include "kernels_wavefront.h"
 #include "kernels_us_wavefront.h"
 #include "kernels_beamform.h"
+#include "workspace.h"
 
 static std::string g_ctxless_error;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;   // allocated
-    size_t need = 0;    // what the most recent request asked for
-    uint64_t stamp = 0; // pbrt_ctx::call_seq of that request
+// the device allocator of a context's workspace (workspace.h)
+struct HipAlloc {
+    static const int out_of_memory = hipErrorOutOfMemory;
+    static int alloc(void **p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) (void)hipGetLastError();
+        return e;
+    }
+    static void free(void *p) { (void)hipFree(p); }
+    static const char *error_string(int e) { return hipGetErrorString((hipError_t)e); }
 };
 
 // the context's pinned host page: partial sums of the ultrasound counters (written by k_us_reduce_stats itself), then the guard words
@@ -40,27 +46,12 @@ struct pbrt_ctx {
     std::vector<hipEvent_t> sync_ev;
     std::string err;
     pbrt_stats stats{};
-    // Workspace: named device buffers that grow on demand and are re-used by later calls.  ws_limit (0: none) caps their sum --
-    // PBRT_WORKSPACE_LIMIT_BYTES at pbrt_ctx_create, pbrt_ctx_set_workspace_limit later; a request that would exceed it fails with
-    // PBRT_E_NOMEM and the render paths answer by taking smaller passes -- and pbrt_ctx_trim gives back what the last call did
-    // not need (a caller that shares the device with another allocator, e.g. torch beside the renderer as in USMain.py:5).
-    std::map<std::string, DevBuf> ws;
-    size_t ws_limit = 0;
+    // Workspace (workspace.h): named device buffers that grow on demand and are re-used by later calls.  work.limit (0: none) caps
+    // their sum -- PBRT_WORKSPACE_LIMIT_BYTES at pbrt_ctx_create, pbrt_ctx_set_workspace_limit later; a request that would exceed it
+    // fails with PBRT_E_NOMEM and the render paths answer by taking smaller passes -- and pbrt_ctx_trim gives back what the last call
+    // did not need (a caller that shares the device with another allocator, e.g. torch beside the renderer as in USMain.py:5).
+    Workspace<HipAlloc> work;
     uint64_t call_seq = 0;  // bumped by every entry point that takes workspace
-    size_t ws_total() const {
-        size_t t = 0;
-        for (const auto &kv : ws) t += kv.second.bytes;
-        return t;
-    }
-    void release(const char *name) {
-        auto it = ws.find(name);
-        if (it == ws.end()) return;
-        if (it->second.p) {
-            (void)hipFree(it->second.p);
-            ++ws_epoch;
-        }
-        ws.erase(it);
-    }
     std::vector<hipEvent_t> ev_pool;
     // An acquisition that was queued without waiting (pbrt_us_acquire_queue_dev, ABI 5): what us_finish needs to turn the counters
     // the device leaves in the pinned page into pbrt_stats once the stream has drained.  Every entry point that waits for the
@@ -79,32 +70,32 @@ struct pbrt_ctx {
     unsigned long long *pin_stats() { return (unsigned long long *)pinned; }              // [2 + MAX_DEPTH_STATS][REDUCE_SLICES] partial sums
     uint32_t *pin_guard() { return (uint32_t *)((char *)pinned + PIN_GUARD_OFFSET); }      // [WF_GUARD_WORDS]
     // the ultrasound counters (workspace "us_stats") as the last acquisition left them: k_us_reduce_stats zeroes what it reads, so a
-    // call that finds the same buffer and this flag set skips the fill command
-    const void *us_rows_clean = nullptr;
-    size_t us_rows_clean_bytes = 0;
-    uint64_t us_rows_epoch = 0;  // ws_epoch when the rows were left clean: a buffer freed since may have come back at the same address
-    // the small tables of the last acquisition (transmit delays, primary directions, element positions) as uploaded: the
-    // reference's loop calls the acquisition 51 times with the same ones (USMain.py:260,279-283), three host-to-device copies each
+    // call that finds the same allocation (its generation; 0: not clean) and the same size skips the fill command
+    uint64_t us_rows_gen = 0;
+    size_t us_rows_bytes = 0;
+    // the small tables of the last acquisition (transmit delays, primary directions, element positions) as uploaded into the
+    // allocation us_tab_gen of workspace "us_tables": the reference's loop calls the acquisition 51 times with the same ones
+    // (USMain.py:260,279-283), three host-to-device copies each
     std::vector<float> us_tab_host;
-    const void *us_tab_dev = nullptr;
+    uint64_t us_tab_gen = 0;
     // image formation (f-1): event pairs per step when profiling is on (pbrt_ctx_set_profiling), read by pbrt_get_image_stats
     bool profiling = false;
     hipEvent_t img_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint32_t img_mask = 0;
     uint64_t img_das_bytes = 0;
     size_t env_lds_attr = 0;
-    uint32_t env_taps_n = 0;  // column length the context's tap table (workspace "env_taps") was made for
+    uint32_t env_taps_n = 0;  // column length the context's tap table (workspace "env_taps") was made for ...
+    uint64_t env_taps_gen = 0;  // ... in this allocation of it
+    uint64_t wf_guard_gen = 0;  // the allocation of workspace "wf_guard" that was cleared
     bool img_event(int i) { return img_ev[i] || hipEventCreate(&img_ev[i]) == hipSuccess; }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint32_t lds_limit = 0;
     // A recording of the queued chain (pbrt_ctx_record_begin .. pbrt_ctx_record_end; replayed by pbrt_graph_launch): while it is
-    // open the context's stream captures instead of running, nothing may wait for it, allocate or upload.  ws_epoch counts the
+    // open the context's stream captures instead of running, nothing may wait for it, allocate or upload.  work.epoch() counts the
     // events that make a finished recording stale: memory it may refer to freed or replaced, other acquisition tables uploaded,
     // the envelope's tap table made for another column length.
     bool recording = false, rec_failed = false;
     std::string rec_msg;
-    uint64_t ws_epoch = 0;
-    uint32_t n_graphs = 0;
 
     int fail(int code, const char *fmt, ...) {
         char buf[1024];
@@ -124,54 +115,11 @@ struct pbrt_ctx {
         err = std::string("a recording is open on this context (pbrt_ctx_record_begin): ") + what;
         return PBRT_E_INVALID;
     }
-    // returns nullptr on failure (err set)
+    // returns nullptr on failure (err set; the caller reports PBRT_E_NOMEM with this message)
     void *buf(const char *name, size_t bytes) {
-        DevBuf &b = ws[name];
-        b.need = bytes;
-        b.stamp = call_seq;
-        if (b.bytes >= bytes && b.p) return b.p;
-        if (recording) {  // (the caller reports PBRT_E_NOMEM with this message)
-            fail(PBRT_E_NOMEM, "recording: workspace buffer %s (%zu bytes) is not there yet -- run the chain once before recording it", name, bytes);
-            return nullptr;
-        }
-        if (b.p) {
-            (void)hipFree(b.p);
-            ++ws_epoch;
-        }
-        b.p = nullptr;
-        b.bytes = 0;
-        // small buffers get 12.5 % of slack (a slightly larger request re-uses them); the large ones -- path state, ray and
-        // radiance records, sized by the pass -- are allocated as asked
-        const size_t want = bytes < (size_t(64) << 20) ? bytes + bytes / 8 + 256 : bytes + 256;
-        if (ws_limit && ws_total() + want > ws_limit) {  // make room: what this call has not asked for goes first
-            for (auto it = ws.begin(); it != ws.end();) {
-                if (it->second.stamp != call_seq && &it->second != &b) {
-                    if (it->second.p) {
-                        (void)hipFree(it->second.p);
-                        ++ws_epoch;
-                    }
-                    it = ws.erase(it);
-                } else {
-                    ++it;
-                }
-            }
-        }
-        if (ws_limit && ws_total() + want > ws_limit) {
-            fail(PBRT_E_NOMEM, "workspace limit: %s wants %zu bytes on top of %zu held, limit %zu", name, want, ws_total(), ws_limit);
-            return nullptr;
-        }
-        // PBRT_DEBUG_ALLOC_FAIL_BYTES (tests of the halve-the-pass retry): a request above this size fails the way a hipMalloc
-        // that lost the race against another allocator does
-        const char *dbg_fail = getenv("PBRT_DEBUG_ALLOC_FAIL_BYTES");  // read per allocation: a test sets and clears it
-        hipError_t e = (dbg_fail && want > (size_t)strtoull(dbg_fail, nullptr, 0)) ? hipErrorOutOfMemory : hipMalloc(&b.p, want);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            fail(PBRT_E_NOMEM, "hipMalloc(%zu) for %s: %s", want, name, hipGetErrorString(e));
-            b.p = nullptr;
-            return nullptr;
-        }
-        b.bytes = want;
-        return b.p;
+        void *p = work.get(name, bytes, call_seq, recording);
+        if (!p) fail(PBRT_E_NOMEM, "%s", work.error.c_str());
+        return p;
     }
     hipEvent_t event(size_t i) {
         while (ev_pool.size() <= i) {
@@ -387,7 +335,7 @@ int pbrt_ctx_create(int device, pbrt_ctx **out) {
         return PBRT_E_NOMEM;
     }
     std::memset(c->pinned, 0, PIN_BYTES);
-    if (const char *lim = getenv("PBRT_WORKSPACE_LIMIT_BYTES")) c->ws_limit = (size_t)strtoull(lim, nullptr, 0);
+    if (const char *lim = getenv("PBRT_WORKSPACE_LIMIT_BYTES")) c->work.limit = (size_t)strtoull(lim, nullptr, 0);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
         c->lds_limit = (uint32_t)prop.sharedMemPerBlock;
@@ -411,8 +359,7 @@ int pbrt_ctx_destroy(pbrt_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->st_trace) (void)hipStreamSynchronize(c->st_trace);
     if (c->st_shade) (void)hipStreamSynchronize(c->st_shade);
-    for (auto &kv : c->ws)
-        if (kv.second.p) (void)hipFree(kv.second.p);
+    c->work.release_all();
     if (c->pinned) (void)hipHostFree(c->pinned);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -432,13 +379,11 @@ const char *pbrt_last_error(pbrt_ctx *c) { return c ? c->err.c_str() : g_ctxless
 int pbrt_ctx_set_workspace_limit(pbrt_ctx *c, uint64_t bytes) {
     if (!c) return PBRT_E_INVALID;
     if (int rc = ctx_settle(c)) return rc;
-    c->ws_limit = (size_t)bytes;
-    if (bytes && c->ws_total() > bytes) {  // a limit below what the context holds: everything goes back (calls are synchronous, nothing is in use)
+    c->work.limit = (size_t)bytes;
+    if (bytes && c->work.total() > bytes) {  // a limit below what the context holds: everything goes back (calls are synchronous, nothing is in use)
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (auto &kv : c->ws)
-            if (kv.second.p) (void)hipFree(kv.second.p);
-        c->ws.clear();
+        c->work.release_all();
         c->stats.workspace_bytes = 0;
     }
     return PBRT_OK;
@@ -450,20 +395,8 @@ int pbrt_ctx_trim(pbrt_ctx *c, uint64_t *held_after) {
     if (int rc = ctx_settle(c)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (auto it = c->ws.begin(); it != c->ws.end();) {
-        DevBuf &b = it->second;
-        const size_t fit = b.need < (size_t(64) << 20) ? b.need + b.need / 8 + 256 : b.need + 256;
-        if (b.stamp != c->call_seq || b.bytes > fit || !b.p) {
-            if (b.p) {
-                (void)hipFree(b.p);
-                ++c->ws_epoch;
-            }
-            it = c->ws.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    c->stats.workspace_bytes = c->ws_total();
+    c->work.trim(c->call_seq);
+    c->stats.workspace_bytes = c->work.total();
     if (held_after) *held_after = c->stats.workspace_bytes;
     return PBRT_OK;
 }
@@ -653,13 +586,72 @@ int pbrt_scene_destroy(pbrt_scene *s) {
     (void)hipSetDevice(s->ctx->device);
     (void)ctx_settle(s->ctx);
     (void)hipStreamSynchronize(s->ctx->stream);  // queued work may still read the scene
-    ++s->ctx->ws_epoch;
+    s->ctx->work.invalidate_recordings();
     for (void *p : s->allocs) (void)hipFree(p);
     delete s;
     return PBRT_OK;
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// environment switches
+// ------------------------------------------------------------------------------------------------
+// Every environment variable the library reads (INTEGRATION.md has the same table):
+//
+//   variable                      selects                                                                    read
+//   PBRT_WORKSPACE_LIMIT_BYTES    cap of the context's workspace (pbrt_ctx_set_workspace_limit later)         pbrt_ctx_create
+//   PBRT_DEBUG_ALLOC_FAIL_BYTES   test hook: workspace requests above this size fail like a lost hipMalloc    per allocation (workspace.h)
+//   PBRT_WF_PACKET                0: camera rays of BVH scenes through k_trace, not k_trace_primary (A/B)     once per process
+//   PBRT_WF_SPLIT                 s[,parts]: k_trace and k_shade on disjoint CUs through two masked streams   once per process
+//   PBRT_US_GENERIC_KERNEL        1: the k_us_bounce instance that reads the quirks at run time              per call (us_impl)
+//   PBRT_US_EMIT_FUSED            0: emitter rays through k_us_emit_init and the later-bounce instance         per call (us_impl)
+//   PBRT_US_EMIT_PERMUTE          0: workgroup b walks region b; k > 1: another stride of the permutation     per call (us_impl)
+//   PBRT_ENV_GENERAL              1: every column length through k_hilbert_env                                per call (env_enqueue)
+//   diagnostic build (-DPBRT_DIAG) only:
+//   PBRT_PAIR_MERGE               k: k_chain_pair with merge bounce k instead of the k_bounce chain           per call (render_impl)
+//   PBRT_US_FUSED_BVH             1: BVH scenes through the fused ultrasound bounce, not the streams          per call (us_impl)
+//   -DPBRT_CU_MASK_PROBE only:
+//   PBRT_CU_MASK                  even | odd | low | pairs | ...: the CUs the context's stream runs on        pbrt_ctx_create
+//
+// "per call": read_switches() at the top of the driver call, so a caller (a test) may change them between two calls of one process.
+struct Switches {
+    bool wf_packet = true;
+    uint32_t wf_split_s = 0, wf_split_parts = 1;  // s = 0: off
+    bool us_generic_kernel = false, us_emit_fused = true, env_general = false;
+    int us_emit_permute = 1;  // 0: off, 1: the library's stride, > 1: that stride
+#ifdef PBRT_DIAG
+    uint32_t pair_merge = 0;  // 0: off
+    bool us_fused_bvh = false;
+#endif
+};
+static Switches read_switches() {
+    static const Switches once = [] {  // the two that hold for the process
+        Switches w;
+        if (const char *e = getenv("PBRT_WF_PACKET")) w.wf_packet = atoi(e) != 0;
+        unsigned s_ = 0, p_ = 2;
+        const char *e = getenv("PBRT_WF_SPLIT");
+        if (e && sscanf(e, "%u%*[,:]%u", &s_, &p_) >= 1 && s_ >= 1 && s_ <= 7) {
+            w.wf_split_s = s_;
+            w.wf_split_parts = std::max(2u, std::min(p_, 8u));
+        }
+        return w;
+    }();
+    Switches w = once;
+    auto flag = [](const char *name, bool unset) {
+        const char *e = getenv(name);
+        return e ? atoi(e) != 0 : unset;
+    };
+    w.us_generic_kernel = flag("PBRT_US_GENERIC_KERNEL", false);
+    w.us_emit_fused = flag("PBRT_US_EMIT_FUSED", true);
+    w.env_general = flag("PBRT_ENV_GENERAL", false);
+    if (const char *e = getenv("PBRT_US_EMIT_PERMUTE")) w.us_emit_permute = atoi(e);
+#ifdef PBRT_DIAG
+    if (const char *e = getenv("PBRT_PAIR_MERGE")) w.pair_merge = (uint32_t)atoi(e);
+    w.us_fused_bvh = flag("PBRT_US_FUSED_BVH", false);
+#endif
+    return w;
+}
 
 // ------------------------------------------------------------------------------------------------
 // radiance mode driver
@@ -768,10 +760,8 @@ static uint32_t plan_from_survival(const unsigned long long *live, uint32_t max_
 // k_chain_pair (two tiles per wave, kernels_radiance.h; lost its A/B): diagnostic builds launch it instead of the k_bounce chain
 // when PBRT_PAIR_MERGE=k names the merge bounce and the plan walks the whole path in one launch.
 #ifdef PBRT_DIAG
-static uint32_t pair_merge_bounce(uint32_t plan, uint32_t max_depth) {
-    const char *e = getenv("PBRT_PAIR_MERGE");  // (read per pass: a test switches it between renders)
-    if (!e || max_depth > MAX_CHAIN || max_depth < 2 || chain_len(plan, 0, max_depth) < max_depth) return 0;
-    const uint32_t k = (uint32_t)atoi(e);
+static uint32_t pair_merge_bounce(uint32_t k, uint32_t plan, uint32_t max_depth) {
+    if (max_depth > MAX_CHAIN || max_depth < 2 || chain_len(plan, 0, max_depth) < max_depth) return 0;
     return k < max_depth ? k : 0u;
 }
 #endif
@@ -808,10 +798,11 @@ struct WfPlan {
     uint32_t grid_deep = 2;  // workgroups per CU from bounce 2 on (few rays: a resident round of larger shares; ring 8 / 2 / 1: 139.7 / 137.1 / 134.9 ms)
     uint32_t threads = 1024, rows = 2, grid_mult = 8;  // grid: ring 1024^2 x 64: 2 / 4 / 8 / 16 workgroups per CU -> 27.6 / 21.3 / 20.4 / 21.3 ms
     size_t lds = 0;
+    uint32_t split_s = 0, split_parts = 1;  // PBRT_WF_SPLIT (wf_bounces); s = 0: off
 };
 // Workgroup shape of k_trace: the image plus (rows + 1) stack rows per workgroup; two 1024-thread workgroups per CU when both fit
 // (8 waves per SIMD at <= 64 VGPRs), else one.
-static WfPlan wf_plan(const pbrt_scene *s) {
+static WfPlan wf_plan(const pbrt_scene *s, const Switches &sw) {
     WfPlan p;
     const uint32_t limit = s->ctx->lds_limit ? s->ctx->lds_limit : 65536u;
     const uint32_t image = s->accel_kernel == ACCEL_K_BVH_LDS ? s->lds_bytes : 0u;
@@ -824,8 +815,9 @@ static WfPlan wf_plan(const pbrt_scene *s) {
     if (image + statics + 3u * p.threads * 4u > budget) budget = limit;
     const uint32_t rows_fit = (budget - image - statics) / (p.threads * 4u);
     p.rows = std::max(2u, std::min(rows_fit, 8u));
-    static const char *e_pkt = getenv("PBRT_WF_PACKET");
-    if (e_pkt) p.packet = atoi(e_pkt) != 0;
+    p.packet = sw.wf_packet;
+    p.split_s = sw.wf_split_s;
+    p.split_parts = sw.wf_split_parts;
     if (3u * s->bvh_depth > 64u) p.packet = false;  // the wave's stack is the 64 lanes of one register (bvh_packet_closest)
     p.lds = (size_t)image + (size_t)p.rows * p.threads * 4u;
     return p;
@@ -857,15 +849,18 @@ static int wf_set_attr(pbrt_scene *s, const WfPlan &p) {
 }
 // the context's guard words (k_trace's turn guard): allocated and cleared once, cleared again after a trip
 static uint32_t *wf_guard(pbrt_ctx *c) {
-    const bool fresh = c->ws["wf_guard"].p == nullptr;
     uint32_t *g = (uint32_t *)c->buf("wf_guard", WF_GUARD_WORDS * 4);
-    if (g && fresh && hipMemsetAsync(g, 0, WF_GUARD_WORDS * 4, c->stream) != hipSuccess) return nullptr;
+    const uint64_t gen = c->work.generation("wf_guard");
+    if (g && gen != c->wf_guard_gen) {
+        if (hipMemsetAsync(g, 0, WF_GUARD_WORDS * 4, c->stream) != hipSuccess) return nullptr;
+        c->wf_guard_gen = gen;
+    }
     return g;
 }
 #define WF_BYTES_PER_PATH (2 * WF_STATE_Q * 16 + 4 + 2 * 64 + 16)  // two state sets, hit index, two shadow sets, Lhome
 // the buffers whose size follows the pass: given back before a retry with half the paths in flight (render_impl, us_impl)
 static void release_pass_buffers(pbrt_ctx *c) {
-    for (const char *nm : {"wf_stateA", "wf_stateB", "wf_shadowA", "wf_shadowB", "wf_hit_id", "Lhome", "stateA", "stateB"}) c->release(nm);
+    for (const char *nm : {"wf_stateA", "wf_stateB", "wf_shadowA", "wf_shadowB", "wf_hit_id", "Lhome", "stateA", "stateB"}) c->work.release(nm);
 }
 struct WfBufs {
     float4 *stA, *stB, *shA, *shB;
@@ -909,21 +904,6 @@ static bool wf_tree_args(pbrt_scene *s, const WfPlan &p, WfArgs *a) {
 // cut into `parts` sets of regions that go through the two streams one phase apart: trace(part, d) -> shade(part, d) ->
 // trace(part, d + 1), with trace of one part running beside shade of another.  Regions share nothing (their own slots of every
 // buffer, their own statistics rows), so any order renders the same film.
-struct WfSplit {
-    uint32_t s = 0, parts = 1;  // s = 0: off
-};
-static WfSplit wf_split_env() {
-    WfSplit w;
-    static const char *e = getenv("PBRT_WF_SPLIT");
-    if (e) {
-        unsigned s_ = 0, p_ = 2;
-        if (sscanf(e, "%u%*[,:]%u", &s_, &p_) >= 1 && s_ >= 1 && s_ <= 7) {
-            w.s = s_;
-            w.parts = std::max(2u, std::min(p_, 8u));
-        }
-    }
-    return w;
-}
 static int wf_split_streams(pbrt_ctx *c, uint32_t s_cus) {
     if (c->st_trace && c->split_s == s_cus) return PBRT_OK;
     if (c->st_trace) {
@@ -970,20 +950,29 @@ static int live_paths(pbrt_ctx *c, const uint32_t *d_counts, uint32_t n, uint64_
     return PBRT_OK;
 }
 
+// When to poll: a pass of more than 32 bounces looks whenever its bounces pass a multiple of 8 (from depth `before` to `after`).
+static int poll_live(pbrt_ctx *c, uint32_t max_depth, uint32_t before, uint32_t after, const uint32_t *d_counts, uint32_t n, bool *dead) {
+    *dead = false;
+    if (max_depth <= 32 || (after >> 3) == (before >> 3)) return PBRT_OK;
+    uint64_t live;
+    if (int rc = live_paths(c, d_counts, n, &live)) return rc;
+    *dead = live == 0;
+    return PBRT_OK;
+}
+
 // The bounces of one pass.  camera: depth 0 generates its rays from the film keys (else the rays are in b.stA / b.segA).
 // Returns the number of launches through *launches.
 static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p, uint32_t nreg, bool camera, uint32_t *launches) {
     pbrt_ctx *c = s->ctx;
     if (!wf_tree_args(s, p, &a)) return PBRT_E_NOMEM;
     a.vis_q = 4;
-    const WfSplit sp = wf_split_env();
-    const bool split = sp.s != 0 && c->n_cu == 256 && nreg >= 64u * sp.parts && a.max_depth <= 32;
-    const uint32_t parts = split ? sp.parts : 1u;
+    const bool split = p.split_s != 0 && c->n_cu == 256 && nreg >= 64u * p.split_parts && a.max_depth <= 32;
+    const uint32_t parts = split ? p.split_parts : 1u;
     if (split) {
-        int rc = wf_split_streams(c, sp.s);
+        int rc = wf_split_streams(c, p.split_s);
         if (rc) return rc;
     }
-    const uint32_t cu_trace = split ? 256u - 32u * sp.s : (uint32_t)c->n_cu;
+    const uint32_t cu_trace = split ? 256u - 32u * p.split_s : (uint32_t)c->n_cu;
     hipStream_t st_t = split ? c->st_trace : c->stream, st_s = split ? c->st_shade : c->stream;
     uint32_t reg0[8], regn[8];
     for (uint32_t h = 0; h < parts; ++h) {
@@ -1046,15 +1035,12 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
         }
         pp.flip();
         HIPCHK(c, hipGetLastError());
-        // unbounded depth (Mitsuba max_depth = -1): poll the live count every 8 bounces (never split: one stream)
-        if (a.max_depth > 32 && (depth & 7u) == 7u) {
-            uint64_t live;
-            if (int rc = live_paths(c, pp.sin, nreg, &live)) return rc;
-            if (live == 0) {
-                flush = depth + 1 < a.max_depth;  // the last bounce may have left shadow rays behind
-                a.depth = depth + 1;
-                break;
-            }
+        bool dead;  // (never split: one stream)
+        if (int rc = poll_live(c, a.max_depth, depth, depth + 1, pp.sin, nreg, &dead)) return rc;
+        if (dead) {
+            flush = depth + 1 < a.max_depth;  // the last bounce may have left shadow rays behind
+            a.depth = depth + 1;
+            break;
         }
     }
     if (flush) {
@@ -1075,15 +1061,12 @@ static uint64_t wf_default_pass_paths(pbrt_ctx *c, uint64_t min_pass) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
     size_t held = 0;
-    for (const char *nm : {"wf_stateA", "wf_stateB", "wf_shadowA", "wf_shadowB", "wf_hit_id", "Lhome"}) {
-        auto it = c->ws.find(nm);
-        if (it != c->ws.end()) held += it->second.bytes;
-    }
+    for (const char *nm : {"wf_stateA", "wf_stateB", "wf_shadowA", "wf_shadowB", "wf_hit_id", "Lhome"}) held += c->work.bytes(nm);
     // two thirds of what is free, and never more than half of the device: a tenant that arrives second (torch beside the renderer,
     // USMain.py:5) still finds room, and the pass size depends less on who allocated first.  A caller that owns the device asks
     // for more per call (pbrt_film_desc.pass_paths) -- bench.py does for BASELINE config 4.
     double budget = std::min((2.0 / 3.0) * (double)(free_b + held), 0.5 * (double)total_b);
-    if (c->ws_limit) budget = std::min(budget, (double)c->ws_limit - (double)(c->ws_total() - held) - 64e6 /* the small buffers */);
+    if (c->work.limit) budget = std::min(budget, (double)c->work.limit - (double)(c->work.total() - held) - 64e6 /* the small buffers */);
     uint64_t pass_paths = min_pass;
     while (pass_paths < (512u << 20) && 2.0 * (double)pass_paths * WF_BYTES_PER_PATH <= budget) pass_paths *= 2;
     return pass_paths;
@@ -1202,7 +1185,7 @@ static int call_stats(pbrt_ctx *c, const unsigned long long *hstats, uint64_t sa
     S.bounce_launches = launches;
     S.passes = passes;
     for (int d = 0; d < 16; ++d) S.live[d] = hstats[2 + d];
-    S.workspace_bytes = c->ws_total();
+    S.workspace_bytes = c->work.total();
     return PBRT_OK;
 }
 
@@ -1238,8 +1221,8 @@ static int size_pass(pbrt_ctx *c, uint64_t pass_paths, bool fixed, uint32_t per_
 // kernels take `paths`, halved under a workspace limit until bytes_per_path of each fit it (the small buffers: 64 MB)
 static uint64_t default_pass_paths(pbrt_ctx *c, bool streams, uint64_t paths, uint32_t bytes_per_path) {
     if (streams) return wf_default_pass_paths(c, PASS_MIN_PATHS);
-    if (c->ws_limit)
-        while (paths > PASS_MIN_PATHS && (double)paths * (double)bytes_per_path > (double)c->ws_limit - 64e6) paths /= 2;
+    if (c->work.limit)
+        while (paths > PASS_MIN_PATHS && (double)paths * (double)bytes_per_path > (double)c->work.limit - 64e6) paths /= 2;
     return paths;
 }
 
@@ -1332,6 +1315,7 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     // reference
     const bool brute = s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG;
     const bool wavefront = !brute && !(f->flags & PBRT_FILM_NO_HIT_POOL);
+    const Switches sw = read_switches();
 #ifndef PBRT_DIAG
     // launch structures that lost their A/B live in the diagnostic build only (make -C csrc diag -> libpbrt_hip_diag.so)
     if ((f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || (!brute && (f->flags & PBRT_FILM_NO_HIT_POOL)))
@@ -1379,7 +1363,7 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     const uint32_t s_pass = ps.per_pass, cap = ps.cap, nseg = ps.nseg;
     WfPlan wfp;
     if (wavefront) {
-        wfp = wf_plan(s);
+        wfp = wf_plan(s, sw);
         if ((rc = wf_set_attr(s, wfp)) != 0) return rc;
     }
     // Brute-force scenes: the ping-pong path state (2 x 60 B per slot, 8 GB at 64 Mi paths) is only touched by a pass that needs
@@ -1547,7 +1531,7 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
             if (depth == 0 && (rc = timer.begin()) != 0) return rc;
             const bool walk = brute && depth >= walk_from;  // this launch walks every remaining bounce of the pass
 #ifdef PBRT_DIAG
-            const uint32_t pair_m = (brute && depth == 0 && !walk) ? pair_merge_bounce(plan, f->max_depth) : 0u;
+            const uint32_t pair_m = (brute && depth == 0 && !walk) ? pair_merge_bounce(sw.pair_merge, plan, f->max_depth) : 0u;
             if (pair_m) {  // the whole path in one launch, two tiles per wave
                 a.merge_at = pair_m;
                 const uint32_t g2 = div_up(a.n_paths, 2u * SEG_BRUTE);
@@ -1565,12 +1549,9 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
             std::swap(sin, sout);
             const uint32_t depth_before = depth;
             depth += nb;
-            // unbounded depth (Mitsuba max_depth = -1): poll the live count every 8 bounces
-            if (f->max_depth > 32 && (depth >> 3) != (depth_before >> 3)) {
-                uint64_t live;
-                if ((rc = live_paths(c, sin, n_own, &live)) != 0) return rc;
-                if (live == 0) break;
-            }
+            bool dead;
+            if ((rc = poll_live(c, f->max_depth, depth_before, depth, sin, n_own, &dead)) != 0) return rc;
+            if (dead) break;
         }
         if ((rc = timer.end()) != 0) return rc;
         fa.s_first = a.s_first;
@@ -1677,103 +1658,90 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
     int rc = set_lds_attr(s);
     if (rc) return rc;
     ++c->call_seq;
+    const Switches sw = read_switches();
     const uint32_t REGION = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
     const uint32_t cap = div_up(n, REGION) * REGION, nseg = cap / REGION;
-    // key_mode 1: key = (index_offset + home, sample_index) for the caller's n rays
-    auto ray_args = [&](float *Lhome, unsigned long long *rows, uint32_t n_rows) {
-        RadArgs a{};
-        a.sc = s->ds;
-        a.Lhome = Lhome;
-        a.stats = rows;
-        a.stat_stride = n_rows;
-        a.cap = cap;
-        a.state_cap = cap;
-        a.n_paths = n;
-        a.max_depth = max_depth;
-        a.rr_depth = rr_depth;
-        a.seed = seed;
-        a.key_mode = 1;
-        a.npix_r = 1;
-        a.rw = 1;
-        a.div_npix = a.div_rw = make_fastdiv(1);
-        a.index_offset = index_offset;
-        a.sample_index = sample_index;
-        a.lds_bytes = s->lds_bytes;
-        return a;
-    };
-    if (s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS) {  // trace / shade streams
-        NEED(c, cap < WF_DEAD);
-        WfBufs b{};
-        if (!wf_alloc(c, cap, nseg, &b)) return PBRT_E_NOMEM;
-        const WfPlan p = wf_plan(s);
-        if ((rc = wf_set_attr(s, p)) != 0) return rc;
-        float *Lh = (float *)c->buf("Lhome", (size_t)cap * 16);
-        const uint32_t n_rows = nseg * (WF_SHADE_THREADS / 64u);
-        unsigned long long *rows = (unsigned long long *)c->buf("segstats", (size_t)(2 + 2 * MAX_DEPTH_STATS) * n_rows * 8);
-        float *io = (float *)c->buf("leaf_io", (size_t)n * 7 * 4);
-        if (!Lh || !rows || !io) return PBRT_E_NOMEM;
-        hipStream_t st = c->stream;
-        HIPCHK(c, hipMemcpyAsync(io, o, (size_t)n * 12, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(io + 3 * (size_t)n, d, (size_t)n * 12, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(io + 6 * (size_t)n, tmax, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemsetAsync(rows, 0, (size_t)(2 + 2 * MAX_DEPTH_STATS) * n_rows * 8, st));
-        HIPCHK(c, hipMemsetAsync(Lh, 0, (size_t)cap * 16, st));
-        hipLaunchKernelGGL(k_init_rays_wf, dim3(div_up(std::max(n, nseg), 256)), dim3(256), 0, st, b.stA, cap, b.segA, nseg, n, io,
-                           io + 3 * (size_t)n, io + 6 * (size_t)n);
-        uint32_t launches = 0;
-        if ((rc = wf_bounces(s, wf_args(ray_args(Lh, rows, n_rows)), b, p, nseg, false, &launches)) != 0) return rc;
-        uint32_t hguard[WF_GUARD_WORDS] = {0};
-        if ((rc = wf_guard_fetch(c, hguard)) != 0) return rc;
-        HIPCHK(c, hipStreamSynchronize(st));
-        if ((rc = wf_check_guard(c, hguard)) != 0) return rc;
-        std::vector<float> rec((size_t)n * 4);
-        HIPCHK(c, hipMemcpy(rec.data(), Lh, (size_t)n * 16, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n; ++i)
-            for (int k = 0; k < 3; ++k) rgb[(size_t)k * n + i] = rec[(size_t)i * 4 + k];
-        return PBRT_OK;
-    }
-    float *stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
-    float *stB = (float *)c->buf("stateB", (size_t)cap * N_STATE * 4);
-    float *Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
+    const bool streams = s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS;  // trace / shade streams
+    // what differs: the path state and live counters of the two launch structures
+    WfBufs wfb{};
+    WfPlan wfp;
+    float *stA = nullptr, *stB = nullptr;
+    uint32_t *segA = nullptr, *segB = nullptr;
+    unsigned long long *dstats = nullptr;
     const uint32_t owners = rad_owners_per_region(s->accel_kernel), n_own = nseg * owners;  // see render_impl
-    uint32_t *segA = (uint32_t *)c->buf("segA", (size_t)n_own * 4);
-    uint32_t *segB = (uint32_t *)c->buf("segB", (size_t)n_own * 4);
-    unsigned long long *dstats = (unsigned long long *)c->buf("stats", (2 + MAX_DEPTH_STATS) * 8);
-    const uint32_t n_rows = nseg * rad_rows_per_region(s->accel_kernel);
-    const size_t segstats_bytes = (size_t)(2 + MAX_DEPTH_STATS) * n_rows * 8;  // rows, reduced at the end
-    unsigned long long *segstats = (unsigned long long *)c->buf("segstats", segstats_bytes);
-    if (!segstats) return PBRT_E_NOMEM;
+    if (streams) {
+        NEED(c, cap < WF_DEAD);
+        if (!wf_alloc(c, cap, nseg, &wfb)) return PBRT_E_NOMEM;
+        wfp = wf_plan(s, sw);
+        if ((rc = wf_set_attr(s, wfp)) != 0) return rc;
+    } else {
+        stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
+        stB = (float *)c->buf("stateB", (size_t)cap * N_STATE * 4);
+        segA = (uint32_t *)c->buf("segA", (size_t)n_own * 4);
+        segB = (uint32_t *)c->buf("segB", (size_t)n_own * 4);
+        dstats = (unsigned long long *)c->buf("stats", (2 + MAX_DEPTH_STATS) * 8);
+        if (!stA || !stB || !segA || !segB || !dstats) return PBRT_E_NOMEM;
+    }
+    float *Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
+    const uint32_t n_rows = nseg * (streams ? WF_SHADE_THREADS / 64u : rad_rows_per_region(s->accel_kernel));
+    const size_t rows_bytes = (size_t)(2 + (streams ? 2 : 1) * MAX_DEPTH_STATS) * n_rows * 8;  // statistics rows (k_shade: and its hit rows)
+    unsigned long long *rows = (unsigned long long *)c->buf("segstats", rows_bytes);
     float *io = (float *)c->buf("leaf_io", (size_t)n * 7 * 4);
-    if (!stA || !stB || !Lhome || !segA || !segB || !dstats || !io) return PBRT_E_NOMEM;
+    if (!Lhome || !rows || !io) return PBRT_E_NOMEM;
+    const float *dO = io, *dD = io + 3 * (size_t)n, *dT = io + 6 * (size_t)n;
     hipStream_t st = c->stream;
     HIPCHK(c, hipMemcpyAsync(io, o, (size_t)n * 12, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(io + 3 * (size_t)n, d, (size_t)n * 12, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(io + 6 * (size_t)n, tmax, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dstats, 0, (2 + MAX_DEPTH_STATS) * 8, st));
-    HIPCHK(c, hipMemsetAsync(segstats, 0, segstats_bytes, st));
+    if (dstats) HIPCHK(c, hipMemsetAsync(dstats, 0, (2 + MAX_DEPTH_STATS) * 8, st));
+    HIPCHK(c, hipMemsetAsync(rows, 0, rows_bytes, st));
     HIPCHK(c, hipMemsetAsync(Lhome, 0, (size_t)cap * 16, st));
-    hipLaunchKernelGGL(k_init_rays, dim3(div_up(std::max(n, n_own), 256)), dim3(256), 0, st, stA, segA, n_own, REGION / owners, n, io,
-                       io + 3 * (size_t)n, io + 6 * (size_t)n);
-    RadArgs a = ray_args(Lhome, segstats, n_rows);
-    float *in = stA, *out = stB;
-    uint32_t *sin = segA, *sout = segB;
-    for (uint32_t depth = 0; depth < max_depth; ++depth) {
-        a.depth = depth;
-        a.in = in;
-        a.out = out;
-        a.seg_in = sin;
-        a.seg_out = sout;
-        if ((rc = launch_bounce(s, a, nseg, false)) != 0) return rc;
-        HIPCHK(c, hipGetLastError());
-        std::swap(in, out);
-        std::swap(sin, sout);
-        if (max_depth > 32 && (depth & 7) == 7) {
-            uint64_t live;
-            if ((rc = live_paths(c, sin, n_own, &live)) != 0) return rc;
-            if (live == 0) break;
+    // key_mode 1: key = (index_offset + home, sample_index) for the caller's n rays
+    RadArgs a{};
+    a.sc = s->ds;
+    a.Lhome = Lhome;
+    a.stats = rows;
+    a.stat_stride = n_rows;
+    a.cap = cap;
+    a.state_cap = cap;
+    a.n_paths = n;
+    a.max_depth = max_depth;
+    a.rr_depth = rr_depth;
+    a.seed = seed;
+    a.key_mode = 1;
+    a.npix_r = 1;
+    a.rw = 1;
+    a.div_npix = a.div_rw = make_fastdiv(1);
+    a.index_offset = index_offset;
+    a.sample_index = sample_index;
+    a.lds_bytes = s->lds_bytes;
+    uint32_t hguard[WF_GUARD_WORDS] = {0};
+    if (streams) {
+        hipLaunchKernelGGL(k_init_rays_wf, dim3(div_up(std::max(n, nseg), 256)), dim3(256), 0, st, wfb.stA, cap, wfb.segA, nseg, n, dO, dD, dT);
+        uint32_t launches = 0;
+        if ((rc = wf_bounces(s, wf_args(a), wfb, wfp, nseg, false, &launches)) != 0) return rc;
+        if ((rc = wf_guard_fetch(c, hguard)) != 0) return rc;
+    } else {
+        hipLaunchKernelGGL(k_init_rays, dim3(div_up(std::max(n, n_own), 256)), dim3(256), 0, st, stA, segA, n_own, REGION / owners, n, dO, dD, dT);
+        float *in = stA, *out = stB;
+        uint32_t *sin = segA, *sout = segB;
+        for (uint32_t depth = 0; depth < max_depth; ++depth) {
+            a.depth = depth;
+            a.in = in;
+            a.out = out;
+            a.seg_in = sin;
+            a.seg_out = sout;
+            if ((rc = launch_bounce(s, a, nseg, false)) != 0) return rc;
+            HIPCHK(c, hipGetLastError());
+            std::swap(in, out);
+            std::swap(sin, sout);
+            bool dead;
+            if ((rc = poll_live(c, max_depth, depth, depth + 1, sin, n_own, &dead)) != 0) return rc;
+            if (dead) break;
         }
     }
     HIPCHK(c, hipStreamSynchronize(st));
+    if (streams && (rc = wf_check_guard(c, hguard)) != 0) return rc;
     std::vector<float> rec((size_t)n * 4);
     HIPCHK(c, hipMemcpy(rec.data(), Lhome, (size_t)n * 16, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; ++i)
@@ -1807,17 +1775,16 @@ int pbrt_us_tx_delays(const pbrt_us_params *p, float *tx) {
 
 // which instance of k_us_bounce: the switches of the library's default (with / without the carrier) are compiled in, any other set
 // -- and PBRT_US_GENERIC_KERNEL=1 -- takes the instance that reads them at run time (kernels_us.h)
-static uint32_t us_kernel_quirks(const UsArgs &a) {
-    const char *gen = getenv("PBRT_US_GENERIC_KERNEL");  // read per launch: a test runs both instances in one process
-    if (gen && atoi(gen) != 0) return US_Q_RUNTIME;
+static uint32_t us_kernel_quirks(const UsArgs &a, bool generic) {
+    if (generic) return US_Q_RUNTIME;
     const uint32_t host_only = PBRT_USQ_NO_FIRST_TABLES | PBRT_USQ_NO_FUSED_BOUNCES;  // decided on the host: tables null, a.fuse 0
     const uint32_t q = a.p.quirks & ~host_only;
     return (q == PBRT_USQ_REFERENCE || q == (PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER)) ? q : US_Q_RUNTIME;
 }
-static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg, bool first) {
+static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg, bool first, bool generic) {
     const bool emit = a.p.primary == PBRT_US_PRIMARY_EMITTER;  // primary rays from CustomEmitter.sample_ray, echoes times the ray's weight
     const int tab = (a.first_hit && a.first_rx) ? 1 : (!a.first_hit && !a.first_rx) ? 0 : -1;
-    const UsKern k = us_bounce_kernel(s, first, emit, us_kernel_quirks(a), tab);
+    const UsKern k = us_bounce_kernel(s, first, emit, us_kernel_quirks(a, generic), tab);
     if (!k && emit)
         return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: emitter primary rays on BVH scenes run as streams (us_wf_pass)");
     if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: no fused ultrasound bounce for accelerator %d in this build", s->accel_kernel);
@@ -1937,6 +1904,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     HIPCHK(c, hipSetDevice(c->device));
     int rc = set_lds_attr(s);
     if (rc) return rc;
+    const Switches sw = read_switches();
     const uint32_t NA = p->n_angles, NE = p->n_elements, T = p->time_samples;
     const uint32_t n_rays = NA * NE;
     std::vector<float> tx(n_rays), dir0(3 * NA), ex(NE);
@@ -1972,7 +1940,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     const bool bvh_scene = s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS;
     bool streams = bvh_scene;
 #ifdef PBRT_DIAG
-    if (const char *e = getenv("PBRT_US_FUSED_BVH")) streams = streams && atoi(e) == 0;
+    streams = streams && !sw.us_fused_bvh;
 #endif
     // paths in flight per pass.  Streams: 2 x 10 launches per pass whatever is still alive, so passes as large as the radiance
     // streams take (wf_default_pass_paths; the shared trace / shade workspace).  The fused kernels: the pass buffers must fit the
@@ -1995,7 +1963,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     const uint32_t ppr_pass = ps.per_pass, cap = ps.cap, nseg = ps.nseg;
     WfPlan wfp;
     if (streams) {
-        wfp = wf_plan(s);
+        wfp = wf_plan(s, sw);
         wfp.packet = false;
         if ((rc = wf_set_attr(s, wfp)) != 0) return rc;
     }
@@ -2019,8 +1987,6 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     // later-bounce instance.  (Two default bench runs of this form showed steps of 38 - 43 ms; host stalls of that size hit the
     // two-kernel form as well and went away when bench.py took Python's cyclic collector out of its timed steps: three runs of
     // either form clean since.)
-    const char *e_fused = getenv("PBRT_US_EMIT_FUSED");
-    const bool emit_fused = !(e_fused && atoi(e_fused) == 0);
     // the three small tables in one host image; uploaded only when they differ from what the device copy already holds
     {
         std::vector<float> img((size_t)n_rays + 3 * NA + NE);
@@ -2030,23 +1996,24 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
             std::copy(tx.begin(), tx.end(), img.begin());
         std::copy(dir0.begin(), dir0.end(), img.begin() + n_rays);
         std::copy(ex.begin(), ex.end(), img.begin() + n_rays + 3 * NA);
-        if (c->us_tab_dev != (const void *)tabs || c->us_tab_host != img) {
+        const uint64_t gen = c->work.generation("us_tables");
+        if (c->us_tab_gen != gen || c->us_tab_host != img) {
             if (c->recording) return c->fail(PBRT_E_INVALID, "recording: the acquisition's tables are not on the device yet -- run the chain once before recording it");
-            ++c->ws_epoch;  // (a finished recording was made with the tables that are replaced now)
+            c->work.invalidate_recordings();  // (a finished recording was made with the tables that are replaced now)
             HIPCHK(c, hipMemcpyAsync(tabs, img.data(), img.size() * 4, hipMemcpyHostToDevice, st));
             c->us_tab_host.swap(img);
-            c->us_tab_dev = tabs;
+            c->us_tab_gen = gen;
         }
     }
     const size_t nchan = (size_t)n_rays * T;
     HIPCHK(c, hipMemsetAsync(d_channel, 0, nchan * 4, st));
-    // (the rows are clean if the last acquisition's reduction has swept exactly this buffer; anything else -- a fresh or resized buffer,
-    // a call that failed half-way -- gets the fill)
-    if (c->us_rows_clean != (const void *)dstats || c->us_rows_clean_bytes != segstats_bytes || c->us_rows_epoch != c->ws_epoch) {
+    // (the rows are clean if the last acquisition's reduction has swept exactly this allocation; anything else -- a fresh or resized
+    // buffer, a call that failed half-way -- gets the fill)
+    if (c->us_rows_gen != c->work.generation("us_stats") || c->us_rows_bytes != segstats_bytes) {
         if (c->recording) return c->fail(PBRT_E_INVALID, "recording: the acquisition's counters are not clean yet -- run the chain once before recording it");
         HIPCHK(c, hipMemsetAsync(dstats, 0, segstats_bytes, st));
     }
-    c->us_rows_clean = nullptr;
+    c->us_rows_gen = 0;
     if (timed) HIPCHK(c, hipEventRecord(c->ev0, st));
     UsArgs a{};
     a.sc = s->ds;
@@ -2088,7 +2055,6 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     }
     PassTimer timer{c, timed};
     uint32_t passes = 0, launches = 0;
-    const char *e_perm = getenv("PBRT_US_EMIT_PERMUTE");  // A/B and test: 0 keeps workgroup b on region b (read per call)
     for (uint32_t k0 = 0; k0 < ppr; k0 += ppr_pass, ++passes) {
         const uint32_t kc = std::min(ppr_pass, ppr - k0);
         a.ppr_pass = kc;
@@ -2098,9 +2064,9 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         a.n_paths = n_rays * kc;
         const uint32_t nseg_pass = div_up(a.n_paths, REGION);
         a.blk_mul = 0;
-        if (emit && !streams && nseg_pass > 2u * NA && !(e_perm && atoi(e_perm) == 0)) {
+        if (emit && !streams && nseg_pass > 2u * NA && sw.us_emit_permute != 0) {  // (PBRT_US_EMIT_PERMUTE=0, A/B and test: workgroup b stays on region b)
             uint32_t m = (nseg_pass / NA) | 1u;
-            if (e_perm && atoi(e_perm) > 1) m = (uint32_t)atoi(e_perm) | 1u;  // (A/B: another stride)
+            if (sw.us_emit_permute > 1) m = (uint32_t)sw.us_emit_permute | 1u;  // (A/B: another stride)
             while (std::gcd(m, nseg_pass) != 1u) m += 2u;
             a.blk_mul = m % nseg_pass;
         }
@@ -2120,7 +2086,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
             a.seg_out = sout;
             if (depth == 0 && (rc = timer.begin()) != 0) return rc;
             bool first_kernel = depth == 0;
-            if (depth == 0 && emit && !emit_fused) {
+            if (depth == 0 && emit && !sw.us_emit_fused) {
                 // emitter rays: the primary rays into the state (k_us_emit_init writes a.out / a.seg_out), then the later-bounce
                 // instance from depth 0
                 hipLaunchKernelGGL(k_us_emit_init, dim3(div_up(std::max(a.n_paths, nseg_pass), 256)), dim3(256), 0, st, a, REGION, nseg_pass);
@@ -2132,7 +2098,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
                 a.seg_out = sout;
                 first_kernel = false;
             }
-            if ((rc = launch_us(s, a, nseg_pass, first_kernel)) != 0) return rc;
+            if ((rc = launch_us(s, a, nseg_pass, first_kernel, sw.us_generic_kernel)) != 0) return rc;
             HIPCHK(c, hipGetLastError());
             ++launches;
             if (a.fuse) break;  // that launch walked every bounce (kernels_us.h)
@@ -2150,9 +2116,8 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     // a queued copy; both are read by us_finish once the stream has drained
     hipLaunchKernelGGL(k_us_reduce_stats, dim3(2 + MAX_DEPTH_STATS, REDUCE_SLICES), dim3(256), 0, st, segstats, n_own, (size_t)n_own, c->pin_stats());
     HIPCHK(c, hipGetLastError());
-    c->us_rows_clean = dstats;
-    c->us_rows_clean_bytes = segstats_bytes;
-    c->us_rows_epoch = c->ws_epoch;
+    c->us_rows_gen = c->work.generation("us_stats");
+    c->us_rows_bytes = segstats_bytes;
     if (streams && (rc = wf_guard_fetch(c, c->pin_guard())) != 0) return rc;
     pbrt_ctx::PendingAcq &P = c->pend;
     P.active = true;
@@ -2298,26 +2263,27 @@ struct Stage {
 
 extern "C" {
 
-#define LEAF_BEGIN(ctxp, total_bytes)          \
+// entering a call that stages host arrays of n items through the workspace: declares c and S
+#define STAGED_BEGIN(ctxp, total_bytes)        \
     pbrt_ctx *c = (ctxp);                      \
     if (!c) return PBRT_E_INVALID;             \
     if (n == 0) return PBRT_OK;                \
     NOT_RECORDING(c);                          \
     HIPCHK(c, hipSetDevice(c->device));        \
     Stage S(c, "leaf_io", (total_bytes));      \
-    if (S.rc) return S.rc;                     \
-    const dim3 grid(div_up(n, 256)), block(256); \
-    hipStream_t st = c->stream;
+    if (S.rc) return S.rc;
+// the launch of a leaf operator: one thread per item
+#define LEAF_LAUNCH(kernel, ...) hipLaunchKernelGGL(kernel, dim3(div_up(n, 256)), dim3(256), 0, c->stream, __VA_ARGS__)
 
 int pbrt_ray_intersect(pbrt_scene *s, uint32_t n, const float *o, const float *d, const float *tmax, float *t,
                        uint32_t *prim, float *u, float *v) {
     if (!s) return PBRT_E_INVALID;
     NEED(s->ctx, o && d && tmax && t && prim && u && v);
-    LEAF_BEGIN(s->ctx, (size_t)n * 4 * 12);
+    STAGED_BEGIN(s->ctx, (size_t)n * 4 * 12);
     float *dO = S.in(o, 3 * (size_t)n), *dD = S.in(d, 3 * (size_t)n), *dT = S.in(tmax, n);
     float *rt = S.out<float>(n), *ru = S.out<float>(n), *rv = S.out<float>(n);
     uint32_t *rp = S.out<uint32_t>(n);
-    hipLaunchKernelGGL(ray_intersect_kernel(s), grid, block, 0, st, s->ds, n, dO, dD, dT, rt, rp, ru, rv);
+    LEAF_LAUNCH(ray_intersect_kernel(s), s->ds, n, dO, dD, dT, rt, rp, ru, rv);
     S.back(t, rt, n);
     S.back(prim, rp, n);
     S.back(u, ru, n);
@@ -2328,10 +2294,10 @@ int pbrt_ray_intersect(pbrt_scene *s, uint32_t n, const float *o, const float *d
 int pbrt_ray_test(pbrt_scene *s, uint32_t n, const float *o, const float *d, const float *tmax, uint8_t *hit) {
     if (!s) return PBRT_E_INVALID;
     NEED(s->ctx, o && d && tmax && hit);
-    LEAF_BEGIN(s->ctx, (size_t)n * 4 * 9);
+    STAGED_BEGIN(s->ctx, (size_t)n * 4 * 9);
     float *dO = S.in(o, 3 * (size_t)n), *dD = S.in(d, 3 * (size_t)n), *dT = S.in(tmax, n);
     uint8_t *rh = S.out<uint8_t>(n);
-    hipLaunchKernelGGL(ray_test_kernel(s), grid, block, 0, st, s->ds, n, dO, dD, dT, rh);
+    LEAF_LAUNCH(ray_test_kernel(s), s->ds, n, dO, dD, dT, rh);
     S.back(hit, rh, n);
     return S.finish();
 }
@@ -2342,13 +2308,13 @@ int pbrt_bsdf_sample(pbrt_ctx *ctx, const pbrt_material *m, uint32_t quirks, uin
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && s1 && s2 && wo && pdf && weight && sampled);
     if (int rc = check_material(ctx, *m, 0)) return rc;
-    LEAF_BEGIN(ctx, (size_t)n * 4 * 25);
+    STAGED_BEGIN(ctx, (size_t)n * 4 * 25);
     float *dwi = S.in(wi, 3 * (size_t)n), *dng = S.in(n_geo, 3 * (size_t)n), *dns = S.in(n_sh, 3 * (size_t)n);
     float *dss = S.in(sh_s, 3 * (size_t)n);
     float *d1 = S.in(s1, n), *d2 = S.in(s2, 2 * (size_t)n);
     float *rwo = S.out<float>(3 * (size_t)n), *rpdf = S.out<float>(n), *rw = S.out<float>(3 * (size_t)n);
     uint32_t *rs = S.out<uint32_t>(n);
-    hipLaunchKernelGGL(k_bsdf_sample, grid, block, 0, st, *m, quirks, n, dwi, dng, dns, dss, d1, d2, rwo, rpdf, rw, rs);
+    LEAF_LAUNCH(k_bsdf_sample, *m, quirks, n, dwi, dng, dns, dss, d1, d2, rwo, rpdf, rw, rs);
     S.back(wo, rwo, 3 * (size_t)n);
     S.back(pdf, rpdf, n);
     S.back(weight, rw, 3 * (size_t)n);
@@ -2361,10 +2327,10 @@ int pbrt_bsdf_eval_pdf(pbrt_ctx *ctx, const pbrt_material *m, uint32_t n, const 
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && wo && f && pdf);
     if (int rc = check_material(ctx, *m, 0)) return rc;
-    LEAF_BEGIN(ctx, (size_t)n * 4 * 12);
+    STAGED_BEGIN(ctx, (size_t)n * 4 * 12);
     float *dwi = S.in(wi, 3 * (size_t)n), *dwo = S.in(wo, 3 * (size_t)n);
     float *rf = S.out<float>(3 * (size_t)n), *rp = S.out<float>(n);
-    hipLaunchKernelGGL(k_bsdf_eval_pdf, grid, block, 0, st, *m, n, dwi, dwo, rf, rp);
+    LEAF_LAUNCH(k_bsdf_eval_pdf, *m, n, dwi, dwo, rf, rp);
     S.back(f, rf, 3 * (size_t)n);
     S.back(pdf, rp, n);
     return S.finish();
@@ -2374,12 +2340,12 @@ int pbrt_emitter_sample_direction(pbrt_scene *s, uint32_t n, const float *p, con
                                   float *pdf, float *weight, float *q, uint32_t *emitter) {
     if (!s) return PBRT_E_INVALID;
     NEED(s->ctx, p && u && d && dist && pdf && weight && q && emitter);
-    LEAF_BEGIN(s->ctx, (size_t)n * 4 * 22);
+    STAGED_BEGIN(s->ctx, (size_t)n * 4 * 22);
     float *dp = S.in(p, 3 * (size_t)n), *du = S.in(u, 4 * (size_t)n);
     float *rd = S.out<float>(3 * (size_t)n), *rdist = S.out<float>(n), *rpdf = S.out<float>(n);
     float *rw = S.out<float>(3 * (size_t)n), *rq = S.out<float>(3 * (size_t)n);
     uint32_t *re = S.out<uint32_t>(n);
-    hipLaunchKernelGGL(k_emitter_sample, grid, block, 0, st, s->ds, n, dp, du, rd, rdist, rpdf, rw, rq, re);
+    LEAF_LAUNCH(k_emitter_sample, s->ds, n, dp, du, rd, rdist, rpdf, rw, rq, re);
     S.back(d, rd, 3 * (size_t)n);
     S.back(dist, rdist, n);
     S.back(pdf, rpdf, n);
@@ -2393,10 +2359,10 @@ int pbrt_sensor_sample_ray(pbrt_ctx *ctx, const pbrt_camera *cam, uint32_t n, co
                            float *tmax) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, cam && pos && o && d && tmax);
-    LEAF_BEGIN(ctx, (size_t)n * 4 * 10);
+    STAGED_BEGIN(ctx, (size_t)n * 4 * 10);
     float *dp = S.in(pos, 2 * (size_t)n);
     float *ro = S.out<float>(3 * (size_t)n), *rd = S.out<float>(3 * (size_t)n), *rt = S.out<float>(n);
-    hipLaunchKernelGGL(k_sensor_sample_ray, grid, block, 0, st, *cam, n, dp, ro, rd, rt);
+    LEAF_LAUNCH(k_sensor_sample_ray, *cam, n, dp, ro, rd, rt);
     S.back(o, ro, 3 * (size_t)n);
     S.back(d, rd, 3 * (size_t)n);
     S.back(tmax, rt, n);
@@ -2408,11 +2374,11 @@ int pbrt_us_sensor_sample_ray(pbrt_ctx *ctx, const pbrt_us_sensor *sn, int use_h
                               const float *aperture_sample, float *o, float *d, float *weight) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, sn && time && wavelength_sample && position_sample && aperture_sample && o && d && weight);
-    LEAF_BEGIN(ctx, (size_t)n * 4 * 14);
+    STAGED_BEGIN(ctx, (size_t)n * 4 * 14);
     float *dt = S.in(time, n), *dw = S.in(wavelength_sample, n), *dp = S.in(position_sample, 2 * (size_t)n),
           *da = S.in(aperture_sample, 2 * (size_t)n);
     float *ro = S.out<float>(3 * (size_t)n), *rd = S.out<float>(3 * (size_t)n), *rw = S.out<float>(n);
-    hipLaunchKernelGGL(k_us_sensor_sample_ray, grid, block, 0, st, *sn, use_hemisphere_warp, n, dt, dw, dp, da, ro, rd, rw);
+    LEAF_LAUNCH(k_us_sensor_sample_ray, *sn, use_hemisphere_warp, n, dt, dw, dp, da, ro, rd, rw);
     S.back(o, ro, 3 * (size_t)n);
     S.back(d, rd, 3 * (size_t)n);
     S.back(weight, rw, n);
@@ -2424,11 +2390,11 @@ int pbrt_us_emitter_sample_ray(pbrt_ctx *ctx, const pbrt_us_emitter *e, uint32_t
                                float *pdf_pos) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, e && time && s1 && s2 && s3 && o && d && ray_time && weight && pdf_pos);
-    LEAF_BEGIN(ctx, (size_t)n * 4 * 16);
+    STAGED_BEGIN(ctx, (size_t)n * 4 * 16);
     float *dt = S.in(time, n), *d1 = S.in(s1, n), *d2 = S.in(s2, 2 * (size_t)n), *d3 = S.in(s3, n);
     float *ro = S.out<float>(3 * (size_t)n), *rd = S.out<float>(3 * (size_t)n), *rt = S.out<float>(n),
           *rw = S.out<float>(n), *rp = S.out<float>(n);
-    hipLaunchKernelGGL(k_us_emitter_sample_ray, grid, block, 0, st, *e, n, dt, d1, d2, d3, ro, rd, rt, rw, rp);
+    LEAF_LAUNCH(k_us_emitter_sample_ray, *e, n, dt, d1, d2, d3, ro, rd, rt, rw, rp);
     S.back(o, ro, 3 * (size_t)n);
     S.back(d, rd, 3 * (size_t)n);
     S.back(ray_time, rt, n);
@@ -2442,10 +2408,10 @@ int pbrt_us_put_data(pbrt_ctx *ctx, const pbrt_us_receiver *r, uint32_t n, const
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, r && ox && time && d && amplitude && channel_buffer);
     const size_t nb = (size_t)r->number_of_elements * r->time_samples;
-    LEAF_BEGIN(ctx, (size_t)n * 4 * 7 + nb * 4);
+    STAGED_BEGIN(ctx, (size_t)n * 4 * 7 + nb * 4);
     float *dx = S.in(ox, n), *dt = S.in(time, n), *dd = S.in(d, 3 * (size_t)n), *da = S.in(amplitude, n);
     float *db = S.in(channel_buffer, nb);
-    hipLaunchKernelGGL(k_us_put_data, grid, block, 0, st, *r, n, dx, dt, dd, da, db);
+    LEAF_LAUNCH(k_us_put_data, *r, n, dx, dt, dd, da, db);
     S.back(channel_buffer, db, nb);
     return S.finish();
 }
@@ -2503,20 +2469,22 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
 static int env_enqueue(pbrt_ctx *c, uint32_t nx, uint32_t nz, const float *din, float *dout) {
     const uint32_t np = (nz + 3u) & ~3u, G = 2u * np + 8u;
     // the tap table of this column length: made once, kept while the workspace buffer lives (pbrt_ctx_trim may take it)
-    const bool fresh = c->ws.find("env_taps") == c->ws.end() || c->ws["env_taps"].p == nullptr;
     float *taps = (float *)c->buf("env_taps", (size_t)ENV_TAPS_FLOATS * 4);
     if (!taps) return PBRT_E_NOMEM;
+    const uint64_t gen = c->work.generation("env_taps");
+    const Switches sw = read_switches();
     ImgTimer tm(c, IMG_ENV);
-    if (fresh || c->env_taps_n != nz) {
-        ++c->ws_epoch;  // (a finished recording holds no launch of this kernel: its taps are replaced now)
+    if (gen != c->env_taps_gen || c->env_taps_n != nz) {
+        c->work.invalidate_recordings();  // (a finished recording holds no launch of this kernel: its taps are replaced now)
         hipLaunchKernelGGL(k_hilbert_taps, dim3(div_up(G + 4u * env_even_len(((nz >> 1) + 3u) & ~3u), 256)), dim3(256), 0, c->stream, nz, taps);
         c->env_taps_n = nz;
+        c->env_taps_gen = gen;
     }
     // even column lengths: half of the taps are zero, k_hilbert_env_even leaves their multiply-adds out (kernels_beamform.h)
     const uint32_t mp = ((nz >> 1) + 3u) & ~3u;
     const size_t lds_even = (size_t)(2u * mp + 4u * env_even_len(mp)) * 4;  // (its four tap tables: 3.3 x the column; 80 KB at 4096 samples)
-    const char *e_gen = getenv("PBRT_ENV_GENERAL");  // A/B and test: every column length through k_hilbert_env (read per call)
-    const bool even = (nz & 1u) == 0u && nz >= 8u && lds_even <= (c->lds_limit ? c->lds_limit : 65536u) && !(e_gen && atoi(e_gen) != 0);
+    // (PBRT_ENV_GENERAL=1, A/B and test: every column length through k_hilbert_env)
+    const bool even = (nz & 1u) == 0u && nz >= 8u && lds_even <= (c->lds_limit ? c->lds_limit : 65536u) && !sw.env_general;
     const size_t lds = even ? lds_even : (size_t)(3u * np + 8u) * 4;
     if (lds > c->env_lds_attr) {
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hilbert_env), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2603,10 +2571,7 @@ int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data
     if (rc) return rc;
     const size_t nd = (size_t)p->n_angles * p->n_elements * p->time_samples, ne = (size_t)p->n_angles * p->n_elements;
     const uint32_t n = p->nx * p->nz;
-    LEAF_BEGIN(ctx, (nd + ne + p->n_elements + p->nx + p->nz + (size_t)n) * 4 + 256);
-    (void)grid;
-    (void)block;
-    (void)st;
+    STAGED_BEGIN(ctx, (nd + ne + p->n_elements + p->nx + p->nz + (size_t)n) * 4 + 256);
     float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem_x, p->n_elements);
     float *dx = S.in(x, p->nx), *dz = S.in(z, p->nz);
     float *dout = S.out<float>(n);
@@ -2628,10 +2593,7 @@ int pbrt_envelope(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const float *rf, floa
     NEED(ctx, rf && env && nz <= ENV_MAX_N);
     const uint32_t n = nx * nz;
     NEED(ctx, (uint64_t)nx * nz < 0xffffffffull);
-    LEAF_BEGIN(ctx, (size_t)n * 8 + 64);
-    (void)grid;
-    (void)block;
-    (void)st;
+    STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
     float *din = S.in(rf, n), *dout = S.out<float>(n);
     int rc = env_enqueue(c, nx, nz, din, dout);
     if (rc) return rc;
@@ -2650,10 +2612,7 @@ int pbrt_log_compress_dev(pbrt_ctx *ctx, uint32_t n, const void *d_env, float dy
 int pbrt_log_compress(pbrt_ctx *ctx, uint32_t n, const float *env, float dynamic_range_db, float *out) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, env && out && dynamic_range_db > 0.0f);
-    LEAF_BEGIN(ctx, (size_t)n * 8 + 64);
-    (void)grid;
-    (void)block;
-    (void)st;
+    STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
     float *din = S.in(env, n), *dout = S.out<float>(n);
     int rc = log_enqueue(c, n, din, dynamic_range_db, dout);
     if (rc) return rc;
@@ -2681,10 +2640,7 @@ int pbrt_us_apply_pulse(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples,
     int rc = pulse_check(ctx, n_traces, time_samples, fs, frequency, sigma, &K);
     if (rc) return rc;
     const uint32_t n = n_traces * time_samples;
-    LEAF_BEGIN(ctx, (size_t)n * 8 + 64);
-    (void)grid;
-    (void)block;
-    (void)st;
+    STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
     float *din = S.in(in, n), *dout = S.out<float>(n);
     if ((rc = pulse_enqueue(c, n_traces, time_samples, K, fs, frequency, sigma, din, dout)) != 0) return rc;
     S.back(out, dout, n);
@@ -2746,7 +2702,7 @@ int pbrt_dev_free(pbrt_ctx *c, void *p) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // queued work may still read or write it
     (void)ctx_settle(c);
-    ++c->ws_epoch;  // (a recording may hold this pointer)
+    c->work.invalidate_recordings();  // (a recording may hold this pointer)
     HIPCHK(c, hipFree(p));
     return PBRT_OK;
 }
@@ -2778,9 +2734,9 @@ struct pbrt_graph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     pbrt_ctx::PendingAcq pend;  // what the recorded acquisition leaves for us_finish (inactive: the recording holds none)
-    uint64_t epoch = 0;         // ctx->ws_epoch at the end of the recording
+    uint64_t epoch = 0;         // ctx->work.epoch() at the end of the recording
     uint64_t das_bytes = 0;
-    const void *rows = nullptr; // the counter rows the recorded acquisition expects clean (it was recorded without their fill command)
+    uint64_t rows_gen = 0;      // the counter rows the recorded acquisition expects clean (it was recorded without their fill command)
     size_t rows_bytes = 0;
 };
 
@@ -2826,13 +2782,12 @@ int pbrt_ctx_record_end(pbrt_ctx *c, pbrt_graph **out) {
     G->exec = x;
     G->pend = P;
     G->pend.timed = false;
-    G->epoch = c->ws_epoch;
+    G->epoch = c->work.epoch();
     G->das_bytes = c->img_das_bytes;
     if (P.active) {
-        G->rows = c->us_rows_clean;
-        G->rows_bytes = c->us_rows_clean_bytes;
+        G->rows_gen = c->us_rows_gen;
+        G->rows_bytes = c->us_rows_bytes;
     }
-    ++c->n_graphs;
     *out = G;
     return PBRT_OK;
 }
@@ -2841,13 +2796,13 @@ int pbrt_graph_launch(pbrt_graph *G) {
     if (!G) return PBRT_E_INVALID;
     pbrt_ctx *c = G->ctx;
     if (int rc = ctx_settle(c)) return rc;
-    if (G->epoch != c->ws_epoch)
+    if (G->epoch != c->work.epoch())
         return c->fail(PBRT_E_INVALID, "the recording is stale: memory or tables it refers to were freed or replaced since it was made; record again");
-    if (G->pend.active && (c->us_rows_clean != G->rows || c->us_rows_clean_bytes != G->rows_bytes))
+    if (G->pend.active && (c->us_rows_gen != G->rows_gen || c->us_rows_bytes != G->rows_bytes))
         return c->fail(PBRT_E_INVALID, "the recording is stale: another acquisition (or one that failed) used the counters since it was made; record again");
     HIPCHK(c, hipSetDevice(c->device));
     ++c->call_seq;
-    for (auto &kv : c->ws) kv.second.stamp = c->call_seq;  // (a trim between launches must not take what the replay uses)
+    c->work.touch_all(c->call_seq);
     HIPCHK(c, hipGraphLaunch(G->exec, c->stream));
     c->pend = G->pend;
     c->img_das_bytes = G->das_bytes;
@@ -2861,7 +2816,6 @@ int pbrt_graph_destroy(pbrt_graph *G) {
     if (!c->recording) (void)hipStreamSynchronize(c->stream);  // a replay may still run
     if (G->exec) (void)hipGraphExecDestroy(G->exec);
     if (G->graph) (void)hipGraphDestroy(G->graph);
-    if (c->n_graphs) --c->n_graphs;
     delete G;
     return PBRT_OK;
 }

@@ -227,3 +227,62 @@ def test_acquisition_counters_survive_what_happens_between_two_acquisitions(mi):
         ui.simulate_acquisition_parallel(us)
         st = ctx.stats()
         assert (st["samples"], st["segments"], st["shadow_rays"], st["live"]) == (ref["samples"], ref["segments"], ref["shadow_rays"], ref["live"]), between
+
+
+def _small_acquisition(mi):
+    """the smallest acquisition that still has every table: 2 angles x 8 elements x 128 samples, 4 paths per ray (the sampling rate
+    lowered so that the phantom's echoes arrive within the 128 samples)"""
+    sc = mi.load_file(scene_path("us_sphere_box.xml"), paths_per_ray=4, seed=5)
+    ui = sc.integrator()
+    ui.angles, ui.n_angles, ui.n_elements, ui.time_samples, ui.fs = np.asarray([-7.5, 7.5], np.float32), 2, 8, 128, 2e6
+    return sc, ui
+
+
+def test_a_recorded_acquisition_is_refused_after_a_workspace_reset(mi):
+    """set_workspace_limit(1); set_workspace_limit(0) -- the reset the tests above use -- gives every workspace buffer back: a
+    recording made before refers to freed memory and must say that it is stale; a recording made afterwards replays the acquisition"""
+    sc, ui = _small_acquisition(mi)
+    ctx = sc.device().ctx
+    d = mi.DeviceBuffer(ctx, (2, 8, 128))
+    try:
+        ui._acquire(sc, ui.quirks, out_dev=d.ptr, pulse=False, queue=True)
+        first = d.numpy()
+        assert first.any()
+        with ctx.record() as rec:
+            ui._acquire(sc, ui.quirks, out_dev=d.ptr, pulse=False, queue=True)
+        ctx.set_workspace_limit(1)
+        ctx.set_workspace_limit(0)
+        with pytest.raises(RuntimeError, match="stale"):
+            rec.graph.launch()
+        rec.graph.close()
+        ui._acquire(sc, ui.quirks, out_dev=d.ptr, pulse=False, queue=True)      # the workspace is there again
+        assert np.array_equal(d.numpy(), first)
+        with ctx.record() as rec2:
+            ui._acquire(sc, ui.quirks, out_dev=d.ptr, pulse=False, queue=True)
+        d.upload(np.zeros_like(first))
+        rec2.graph.launch()
+        assert np.array_equal(d.numpy(), first)
+        rec2.graph.close()
+    finally:
+        ctx.set_workspace_limit(0)
+        d.close()
+
+
+def test_acquisition_tables_survive_a_reallocation(mi):
+    """the acquisition's small tables (transmit delays, primary directions, element positions) are uploaded only when they differ
+    from what the device holds: after a reset of the workspace their buffer is another allocation -- possibly at the same address --
+    and the same host image must be uploaded again"""
+    sc, ui = _small_acquisition(mi)
+    ctx = sc.device().ctx
+    try:
+        first = ui._acquire(sc, ui.quirks)
+        tx, st = ui.transmission_delays_buf.copy(), ctx.stats()
+        assert first.any()
+        ctx.set_workspace_limit(1)
+        ctx.set_workspace_limit(0)
+        again = ui._acquire(sc, ui.quirks)
+        st2 = ctx.stats()
+        assert np.array_equal(again, first) and np.array_equal(ui.transmission_delays_buf, tx)
+        assert (st2["segments"], st2["shadow_rays"], st2["live"]) == (st["segments"], st["shadow_rays"], st["live"])
+    finally:
+        ctx.set_workspace_limit(0)
