@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """The reference's ultrasound driver flow on this library: scene dict -> acquisition -> delay-and-sum -> envelope ->
 log compression -> finite-difference roughness loop (what USMain.py does at :26-90, :93-224, :257-289), without the
-plotting.  Writes the B-mode image and the channel buffer as .npy.   python examples/us_bmode.py [out_dir]"""
+plotting.  Writes the B-mode image and the channel buffer as .npy.   python examples/us_bmode.py [--convex] [out_dir]
+--convex: the same flow under a curved (abdominal) array -- 64 elements on a 40 mm arc of 40 degrees (DESIGN D18); the sensor
+transform puts the apex where the linear array sits, and the scan is given in the sensor's frame, whose origin is the centre of
+curvature."""
 import os
 import sys
 import time
@@ -13,18 +16,22 @@ import pbrt_amd as mi                       # was: import mitsuba as mi
 import pbrt_amd.drjit_compat as dr          # was: import drjit as dr
 
 mi.set_variant("llvm_ad_mono")              # accepted; the one backend is HIP on gfx950
-out_dir = sys.argv[1] if len(sys.argv) > 1 else "."
+args = [a for a in sys.argv[1:] if a != "--convex"]
+convex = "--convex" in sys.argv[1:]
+out_dir = args[0] if args else "."
 T = mi.ScalarTransform4f
+RADIUS = 0.04 if convex else 0.0            # centre of curvature RADIUS behind the apex; the scan's z is measured from it
+Z_RANGE = (RADIUS + 0.02, RADIUS + 0.08)
 
 scene = mi.load_dict({
     "type": "scene",
     "integrator": {"type": "ultrasound_integrator", "max_depth": 10, "sampling_rate": 50e6, "frequency": 5e6,
                    "sound_speed": 1540, "attenuation": 0.2, "wave_cycles": 5, "main_beam_angle": 24, "cutoff_angle": 30,
                    "n_elements": 64, "pitch": 1.2e-4, "time_samples": 10000, "angles": dr.linspace(mi.Float, -15, 15, 5),
-                   "paths_per_ray": 4096, "seed": 1},
+                   "paths_per_ray": 4096, "seed": 1, **({"radius": RADIUS, "opening_angle": 40.0} if convex else {})},
     "sensor": {"type": "ultrasound_sensor", "num_elements_lateral": 1280, "elements_width": 0.003, "elements_height": 0.01,
                "pitch": 0.0003, "center_frequency": 5e6, "sound_speed": 1540, "directivity": 1.0,
-               "to_world": T().look_at(origin=[0, 0, 0], target=[0, 0, 0.03], up=[0, 1, 0])},
+               "to_world": T().look_at(origin=[0, 0, -RADIUS], target=[0, 0, 0.03], up=[0, 1, 0])},
     "flat_plate": {"type": "rectangle",
                    "to_world": T().translate([0, 0, 0.05]) @ T().rotate([0, 1, 0], 45) @ T().scale([0.17, 0.17, 0.14]),
                    "bsdf": {"type": "ultrasound_bsdf", "impedance": 7.8, "roughness": 0.7}},
@@ -34,7 +41,7 @@ scene = mi.load_dict({
 })
 
 t = time.perf_counter()
-display, bmode, (x_scan, z_scan) = mi.us_render(scene, x_range=(-0.02, 0.02), z_range=(0.02, 0.08))
+display, bmode, (x_scan, z_scan) = mi.us_render(scene, x_range=(-0.02, 0.02), z_range=Z_RANGE)
 print(f"B-mode {display.shape[0]} x {display.shape[1]} pixels in {(time.perf_counter() - t) * 1e3:.1f} ms; "
       f"channel_buf sum {float(np.sum(scene.integrator().channel_buf)):.4g}, max {float(np.max(scene.integrator().channel_buf)):.4g}")
 np.save(os.path.join(out_dir, "bmode_display.npy"), display)
@@ -49,7 +56,7 @@ target = bmode.astype(np.float64)
 def forward(rough):
     params[key] = rough
     params.update()
-    return mi.us_render(scene, x_range=(-0.02, 0.02), z_range=(0.02, 0.08))[1].astype(np.float64)
+    return mi.us_render(scene, x_range=(-0.02, 0.02), z_range=Z_RANGE)[1].astype(np.float64)
 
 
 rough, eps = 0.5, 1e-2

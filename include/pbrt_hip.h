@@ -235,6 +235,29 @@ typedef struct pbrt_us_emitter {
  *          origin. */
 #define PBRT_US_PRIMARY_ELEMENT 0u
 #define PBRT_US_PRIMARY_EMITTER 1u
+/* The convex (curved) array, OR-ed into pbrt_us_params.primary beside PBRT_US_PRIMARY_ELEMENT or _EMITTER.  The
+ * reference's integrator knows no curved array; these statements are this library's definition.
+ * Geometry   CustomEmitter's, literally (CustomEmmitter.py:41-47), in the sensor's local frame and read from pbrt_us_params.emitter:
+ *            the centre of curvature is the origin, theta_e = linspace(-span / 2, +span / 2, N) with span = opening_angle in radians
+ *            (`pitch` is not read), element e sits at (R sin theta_e, 0, R cos theta_e) with normal (sin theta_e, 0, cos theta_e);
+ *            the apex is (0, 0, R).  emitter.radius must be finite and > 0, emitter.opening_angle finite, > 0 and < 180,
+ *            emitter.number_of_elements == n_elements: PBRT_E_INVALID otherwise.  pbrt_us_array_elements returns the table
+ *            (x, z, nx, nz) per element that the kernels read; sin / cos of theta_e are the emitter's own (so the position a ray is
+ *            emitted from and the position the receive connection aims at are the same floats up to |theta_e| = 45 degrees; beyond,
+ *            host and device library sin / cos may differ in the last bits).
+ * Delays     tx[a, e] = (x_e sin theta_a + (z_e - R) cos theta_a) / c: the plane wave along (sin theta_a, 0, cos theta_a), referenced
+ *            to the apex.  For R -> inf with the apex held fixed this is the linear x_e sin theta_a / c.  pbrt_us_tx_delays honours the
+ *            bit, and the tx_delays an acquisition returns are this table.
+ * ELEMENT    the primary ray starts on the arc: origin T (x_e, 0, z_e), direction normalize(T (sin theta_a, 0, cos theta_a)),
+ *            amplitude 1, emission time tx[a, e].
+ * EMITTER    unchanged: CustomEmitter.sample_ray is convex by itself when radius != 0.
+ * Receive    the connection (CustomIntegrator.py:320-322) aims at T (x_r, 0, z_r), and the directivity angle (:289-304) is taken against
+ *            the receive element's own normal, normalize(T (nx_r, 0, nz_r)).  Everything else keeps the array axis T (0, 0, 1): the
+ *            cut-off cone of :371, w_o, the roulette, quirks and RNG blocks.
+ * Without the bit, PBRT_US_PRIMARY_EMITTER with emitter.radius != 0 (transmit from an arc, receive on a line: never defined) is
+ * refused with PBRT_E_UNSUPPORTED.  No struct changes size; a library from before D18 refuses the bit (PBRT_E_INVALID).
+ * Kernels: instances of their own; they read the behaviour switches at run time (no compiled-in quirk set). */
+#define PBRT_US_ARRAY_CONVEX 0x100u
 
 typedef struct pbrt_us_params {
     uint32_t max_depth;    /* CustomIntegrator.py:16 */
@@ -252,8 +275,8 @@ typedef struct pbrt_us_params {
     float sensor_to_world[12]; /* row-major 3x4 */
     float max_path_len;        /* hard-coded 0.2 in the reference (:307,372) */
     uint32_t quirks;           /* PBRT_USQ_* */
-    uint32_t primary;          /* PBRT_US_PRIMARY_* (ABI 5) */
-    pbrt_us_emitter emitter;   /* read when primary == PBRT_US_PRIMARY_EMITTER */
+    uint32_t primary;          /* PBRT_US_PRIMARY_* (ABI 5), | PBRT_US_ARRAY_CONVEX */
+    pbrt_us_emitter emitter;   /* read with PBRT_US_PRIMARY_EMITTER; with PBRT_US_ARRAY_CONVEX its radius, opening_angle, number_of_elements */
 } pbrt_us_params;
 
 /* Behaviour switches; each bit reproduces one reference quirk.
@@ -449,6 +472,10 @@ int pbrt_us_put_data(pbrt_ctx *ctx, const pbrt_us_receiver *r, uint32_t n, const
 /* tx_delay[a,e] = elem_x[e] * sin(theta_a) / c  (CustomIntegrator.py:246-257); host-only helper
  * shared by pbrt_us_acquire. */
 int pbrt_us_tx_delays(const pbrt_us_params *p, float *tx_delays);
+/* The elements of the array in the sensor's frame, elem[n_elements][4] = (x_e, z_e, nx_e, nz_e): the curved array of
+ * PBRT_US_ARRAY_CONVEX, else the line (x_e, 0, 0, 1).  Host-only helper shared by pbrt_us_acquire; the table the *_probe forms of
+ * the beamformer take.  PBRT_E_INVALID for a curved array whose parameters the acquisition would refuse. */
+int pbrt_us_array_elements(const pbrt_us_params *p, float *elem);
 
 /* ---- image formation behind the hot path ------------------------------------------
  * The reference hands the channel buffer to the third-party `ultraspy` package (absent here; parity unpinned):
@@ -476,6 +503,15 @@ typedef struct pbrt_das_params {
  * exact sum.  Host pointers. */
 int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
                       const float *elem_x, const float *x, const float *z, float *out);
+/* The same on an element table elem[n_elements][4] = (x_e, z_e, nx_e, nz_e) (pbrt_us_array_elements; a curved probe):
+ * distances are |(x, z) - (x_e, z_e)| on the first-arrival and on the receive side, and the f-number aperture lies in the element's
+ * frame -- with v = (x - x_e, z - z_e), depth d_n = v . n_e and lateral d_t = v x n_e, element e receives the pixel iff d_n > 0 and
+ * 2 f_number |d_t| <= d_n (f_number <= 0: every element receives every pixel).  For n_e = (0, 1), z_e = 0 that is pbrt_das_beamform's
+ * |x - x_e| <= z / (2 f_number).  Summation order, f64 sample positions and interpolation as above.  No tile of the scan is skipped
+ * up front (the linear form leaves tiles outside the array's span early); an element outside every aperture of a tile still costs
+ * no square root.  Same argument checks; the *_probe_dev forms below are queued and recordable like the forms they sit beside. */
+int pbrt_das_beamform_probe(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
+                            const float *elem, const float *x, const float *z, float *out);
 
 /* replaces: ultraspy DelayAndSum.compute_envelope(d_output, scan) on RF data (USMain.py:205): modulus of the
  * analytic signal along the axial (z, fastest) axis, i.e. |scipy.signal.hilbert(rf, axis=-1)|.  nz <= 4096.
@@ -532,6 +568,14 @@ int pbrt_das_first_arrival_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const vo
                                const void *d_x, const void *d_z, void *d_table);
 int pbrt_das_beamform_table_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table,
                                 const void *d_elem_x, const void *d_x, const void *d_z, void *d_out);
+/* pbrt_das_beamform_probe in HBM: d_elem [n_elements][4], every other argument as in the three calls above; the table form is
+ * bit-equal to the direct form here too. */
+int pbrt_das_beamform_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays,
+                                const void *d_elem, const void *d_x, const void *d_z, void *d_out);
+int pbrt_das_first_arrival_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem,
+                                     const void *d_x, const void *d_z, void *d_table);
+int pbrt_das_beamform_table_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table,
+                                      const void *d_elem, const void *d_x, const void *d_z, void *d_out);
 /* replaces: DelayAndSum.compute_envelope (USMain.py:205); d_rf, d_env [nx][nz], distinct buffers; NaN as pbrt_envelope */
 int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf, void *d_env);
 /* replaces: the log compression of USMain.py:210-218; d_env, d_out [n] (may be the same buffer); NaN as pbrt_log_compress */

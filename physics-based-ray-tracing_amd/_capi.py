@@ -115,6 +115,7 @@ class UsParams(C.Structure):
 
 
 US_PRIMARY_ELEMENT, US_PRIMARY_EMITTER = 0, 1
+US_ARRAY_CONVEX = 0x100  # OR-ed into UsParams.primary: the curved array (include/pbrt_hip.h, DESIGN D18)
 
 
 class UsSensor(C.Structure):
@@ -187,7 +188,9 @@ SIGNATURES = {
     "pbrt_us_emitter_sample_ray": (C.c_int, [_P, C.POINTER(UsEmitter), C.c_uint32, _F, _F, _F, _F, _F, _F, _F, _F, _F]),
     "pbrt_us_put_data": (C.c_int, [_P, C.POINTER(UsReceiver), C.c_uint32, _F, _F, _F, _F, _F]),
     "pbrt_us_tx_delays": (C.c_int, [C.POINTER(UsParams), _F]),
+    "pbrt_us_array_elements": (C.c_int, [C.POINTER(UsParams), _F]),
     "pbrt_das_beamform": (C.c_int, [_P, C.POINTER(DasParams), _F, _F, _F, _F, _F, _F]),
+    "pbrt_das_beamform_probe": (C.c_int, [_P, C.POINTER(DasParams), _F, _F, _F, _F, _F, _F]),
     "pbrt_envelope": (C.c_int, [_P, C.c_uint32, C.c_uint32, _F, _F]),
     "pbrt_log_compress": (C.c_int, [_P, C.c_uint32, _F, C.c_float, _F]),
     "pbrt_us_apply_pulse": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, _F, _F]),
@@ -195,6 +198,9 @@ SIGNATURES = {
     "pbrt_das_beamform_dev": (C.c_int, [_P, C.POINTER(DasParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_das_first_arrival_dev": (C.c_int, [_P, C.POINTER(DasParams), _P, _P, _P, _P, _P]),
     "pbrt_das_beamform_table_dev": (C.c_int, [_P, C.POINTER(DasParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_das_beamform_probe_dev": (C.c_int, [_P, C.POINTER(DasParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_das_first_arrival_probe_dev": (C.c_int, [_P, C.POINTER(DasParams), _P, _P, _P, _P, _P]),
+    "pbrt_das_beamform_table_probe_dev": (C.c_int, [_P, C.POINTER(DasParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_envelope_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "pbrt_log_compress_dev": (C.c_int, [_P, C.c_uint32, _P, C.c_float, _P]),
     "pbrt_us_apply_pulse_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),

@@ -33,6 +33,19 @@ def _is_dev(a) -> bool:
     return isinstance(a, _capi.DeviceBuffer)
 
 
+def _elem_arg(elem, E):
+    """the element argument of the beamformer: positions [E] on the line z = 0 (-> the plain entry points), or the element table
+    [E, 4] = (x, z, nx, nz) of a curved probe (-> the *_probe entry points; Probe.elements, pbrt_us_array_elements)"""
+    if not _is_dev(elem):
+        elem = np.asarray(elem)
+    shape = tuple(elem.shape)
+    probe = shape == (E, 4)
+    # (a device buffer goes to the kernel as it is: a table of another size would be read out of bounds)
+    if not probe and int(np.prod(shape)) != E:
+        raise ValueError(f"element positions must be [{E}] or an element table [{E}, 4], got {list(shape)}")
+    return elem, probe, ((E, 4) if probe else (E,))
+
+
 def _to_dev(cx, a, shape=None) -> "_capi.DeviceBuffer":
     if _is_dev(a):
         return a
@@ -42,12 +55,13 @@ def _to_dev(cx, a, shape=None) -> "_capi.DeviceBuffer":
 
 def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
     """first-arrival table of a scan, [n_angles, nx, nz] float64 in HBM: t_tx(a; x, z) = min_e (tx_delays[a, e] + distance to element e / c)
-    (pbrt_das_first_arrival_dev).  It depends on the delays and the grid only: a loop that changes neither (USMain.py:262-289) makes it
+    (pbrt_das_first_arrival_dev; elem_x an element table [n_elements, 4]: pbrt_das_first_arrival_probe_dev).  It depends on the delays and the grid only: a loop that changes neither (USMain.py:262-289) makes it
     once and hands it to every das_beamform(..., table=...) call, which then skips its pass over all elements (same image bit for bit)."""
     cx = next((a.ctx for a in (tx_delays, elem_x, x, z) if _is_dev(a)), None) or _capi.default_context()
     d_tx = tx_delays if _is_dev(tx_delays) else _to_dev(cx, np.atleast_2d(np.asarray(tx_delays)))
     A, E = d_tx.shape
-    d_ex = _to_dev(cx, elem_x, (E,))
+    elem_x, probe, eshape = _elem_arg(elem_x, E)
+    d_ex = _to_dev(cx, elem_x, eshape)
     d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
     d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
     nx, nz = d_x.shape[0], d_z.shape[0]
@@ -55,7 +69,8 @@ def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
     tab = out if out is not None else _capi.DeviceBuffer(cx, (A, nx, nz), np.float64)
     if tab.nbytes != A * nx * nz * 8:
         raise ValueError("out must hold n_angles * nx * nz float64")
-    cx.check(cx.lib.pbrt_das_first_arrival_dev(cx.handle, C.byref(p), d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, tab.ptr), "pbrt_das_first_arrival_dev")
+    name = "pbrt_das_first_arrival_probe_dev" if probe else "pbrt_das_first_arrival_dev"
+    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, tab.ptr), name)
     tab._keep = (d_tx, d_ex, d_x, d_z)
     return tab
 
@@ -67,13 +82,16 @@ def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_numbe
     Host arrays in: pbrt_das_beamform, a host array out.  `data` a DeviceBuffer (the channel buffer of an acquisition that
     stayed in HBM): pbrt_das_beamform_dev -- the small tables are uploaded if they are host arrays, the kernel is queued on
     the context's stream and the result is a DeviceBuffer (`out`, or a new one); nothing waits.  table: the scan's first-arrival
-    times from das_first_arrival (pbrt_das_beamform_table_dev)."""
+    times from das_first_arrival (pbrt_das_beamform_table_dev).
+    elem_x [n_elements, 4] = (x, z, nx, nz): the element table of a curved probe; the same calls with `_probe` in their names
+    (distances to (x_e, z_e), the f-number aperture in the element's frame: include/pbrt_hip.h)."""
     cx = data.ctx if _is_dev(data) else _capi.default_context()
     if _is_dev(data):
         if len(data.shape) != 3:
             raise ValueError("data must be [n_angles, n_elements, time_samples]")
         A, E, T = data.shape
-        d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem_x, (E,))
+        elem_x, probe, eshape = _elem_arg(elem_x, E)
+        d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem_x, eshape)
         d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
         d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
         nx, nz = d_x.shape[0], d_z.shape[0]
@@ -84,11 +102,11 @@ def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_numbe
         if table is not None:   # the first-arrival times of this scan, made once (das_first_arrival)
             if table.nbytes != A * nx * nz * 8:
                 raise ValueError("table must be the [n_angles, nx, nz] float64 buffer of das_first_arrival for this scan")
-            cx.check(cx.lib.pbrt_das_beamform_table_dev(cx.handle, C.byref(p), data.ptr, table.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr),
-                     "pbrt_das_beamform_table_dev")
+            name = "pbrt_das_beamform_table_probe_dev" if probe else "pbrt_das_beamform_table_dev"
+            cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), data.ptr, table.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr), name)
         else:
-            cx.check(cx.lib.pbrt_das_beamform_dev(cx.handle, C.byref(p), data.ptr, d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr),
-                     "pbrt_das_beamform_dev")
+            name = "pbrt_das_beamform_probe_dev" if probe else "pbrt_das_beamform_dev"
+            cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), data.ptr, d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr), name)
         d_out._keep = (d_tx, d_ex, d_x, d_z, table)  # the queued kernel reads them: they live as long as its result
         return d_out
     data = _capi.f32(np.asarray(data))
@@ -96,12 +114,14 @@ def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_numbe
         raise ValueError("data must be [n_angles, n_elements, time_samples]")
     A, E, T = data.shape
     tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
-    ex = _capi.f32(np.asarray(elem_x).reshape(E))
+    elem_x, probe, eshape = _elem_arg(elem_x, E)
+    ex = _capi.f32(np.asarray(elem_x).reshape(eshape))
     gx, gz = _capi.f32(np.asarray(x).ravel()), _capi.f32(np.asarray(z).ravel())
     p = _das_params(A, E, T, len(gx), len(gz), fs, sound_speed, t0, f_number, interpolation, compound)
     res = np.empty((p.nx, p.nz), dtype=np.float32)
-    cx.check(cx.lib.pbrt_das_beamform(cx.handle, C.byref(p), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
-                                      _capi.addr(gz), _capi.addr(res)), "pbrt_das_beamform")
+    name = "pbrt_das_beamform_probe" if probe else "pbrt_das_beamform"
+    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
+                                   _capi.addr(gz), _capi.addr(res)), name)
     return res
 
 
@@ -158,22 +178,72 @@ def apply_pulse(traces, fs, frequency, sigma, out=None):
 
 
 # ---- ultraspy-shaped front end (USMain.py:126-205) ---------------------------------------------------------------
+def convex_params(n_elements, radius, opening_angle, params=None) -> "_capi.UsParams":
+    """the array part of a pbrt_us_params for a curved array (PBRT_US_ARRAY_CONVEX, DESIGN D18); raises on what the library refuses"""
+    import math
+    n, radius, opening_angle = int(n_elements), float(radius), float(opening_angle)
+    if not (math.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"convex array: radius must be finite and > 0, got {radius}")
+    if not (math.isfinite(opening_angle) and 0.0 < opening_angle < 180.0):
+        raise ValueError(f"convex array: opening_angle must lie in (0, 180) degrees, got {opening_angle}")
+    if n <= 0:
+        raise ValueError("convex array: no elements")
+    p = params if params is not None else _capi.UsParams()
+    p.n_elements = n
+    p.primary = int(p.primary) | _capi.US_ARRAY_CONVEX
+    p.emitter.number_of_elements = n
+    p.emitter.radius, p.emitter.opening_angle = radius, opening_angle
+    return p
+
+
+def array_elements(params) -> np.ndarray:
+    """[n_elements, 4] = (x, z, nx, nz) of the array a pbrt_us_params describes (pbrt_us_array_elements; host only, no device)"""
+    elem = np.empty((int(params.n_elements), 4), np.float32)
+    rc = _capi.load_library().pbrt_us_array_elements(C.byref(params), _capi.addr(elem))
+    if rc != 0:
+        raise ValueError(f"pbrt_us_array_elements refused the array (rc={rc})")
+    return elem
+
+
 class Probe:
-    def __init__(self, geometry_type, nb_elements, pitch, central_freq, bandwidth=70):
-        if geometry_type != "linear":
-            raise NotImplementedError("only the linear probe of USMain.py:130-136 is built (convex: SURVEY f-4)")
+    def __init__(self, geometry_type, nb_elements, pitch, central_freq, bandwidth=70, radius=None, opening_angle=None):
+        if geometry_type not in ("linear", "convex"):
+            raise NotImplementedError(f"probe geometry '{geometry_type}': 'linear' (USMain.py:130-136) and 'convex' are built")
         self.geometry_type = geometry_type
         self.nb_elements = int(nb_elements)
         self.pitch = float(pitch)
         self.central_freq = float(central_freq)
         self.bandwidth = float(bandwidth)
-        # same element positions as the integrator (CustomIntegrator.py:248)
         self.geometry = np.zeros((3, self.nb_elements), dtype=np.float32)
-        self.geometry[0] = self.pitch * (np.arange(self.nb_elements, dtype=np.float32) - (self.nb_elements - 1) / 2)
+        self.normals = np.zeros((3, self.nb_elements), dtype=np.float32)
+        if geometry_type == "linear":
+            if radius or opening_angle:
+                raise ValueError("a linear probe has no radius / opening_angle")
+            # same element positions as the integrator (CustomIntegrator.py:248)
+            self.geometry[0] = self.pitch * (np.arange(self.nb_elements, dtype=np.float32) - (self.nb_elements - 1) / 2)
+            self.normals[2] = 1.0
+            self.radius = self.opening_angle = 0.0
+            self.elements = None
+        else:
+            # the curved array of CustomEmmitter.py:41-47 as the library places it (pbrt_us_array_elements, DESIGN D18): centre of
+            # curvature at the origin, apex (0, 0, radius); `pitch` is kept but not read
+            if radius is None or opening_angle is None:
+                # (ultraspy describes a curved probe by its pitch; that description is not built: the arc is CustomEmitter's)
+                raise NotImplementedError("build_probe('convex', ...) is built for radius= (m) and opening_angle= (degrees) only")
+            self.radius, self.opening_angle = float(radius), float(opening_angle)
+            self.elements = array_elements(convex_params(self.nb_elements, self.radius, self.opening_angle))
+            self.geometry[0], self.geometry[2] = self.elements[:, 0], self.elements[:, 1]
+            self.normals[0], self.normals[2] = self.elements[:, 2], self.elements[:, 3]
+
+    @property
+    def das_elements(self):
+        """what the beamformer takes: positions [E] (linear), the element table [E, 4] (convex)"""
+        return self.geometry[0] if self.elements is None else self.elements
 
 
-def build_probe(geometry_type="linear", nb_elements=64, pitch=1.2e-4, central_freq=3e6, bandwidth=70):
-    return Probe(geometry_type, nb_elements, pitch, central_freq, bandwidth)
+def build_probe(geometry_type="linear", nb_elements=64, pitch=1.2e-4, central_freq=3e6, bandwidth=70, radius=None,
+                opening_angle=None):
+    return Probe(geometry_type, nb_elements, pitch, central_freq, bandwidth, radius=radius, opening_angle=opening_angle)
 
 
 class GridScan:
@@ -217,7 +287,7 @@ class DelayAndSum:
                 data = data[0]
         # tables that already sit in HBM (us_render keeps them there between calls) are used where the data is a DeviceBuffer
         dev = _is_dev(data)
-        ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.geometry[0]
+        ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
         gx = scan.d_x if dev and getattr(scan, "d_x", None) is not None else scan.x_axis
         gz = scan.d_z if dev and getattr(scan, "d_z", None) is not None else scan.z_axis
         return das_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], t0=ai.get("t0", 0.0) or 0.0,
@@ -283,7 +353,11 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     x_scan = np.arange(x_range[0], x_range[1] + step, step)                                            # :193
     z_scan = np.arange(z_range[0], z_range[1] + step, step)                                            # :194
     scan = GridScan(x_scan, z_scan)
-    probe = build_probe("linear", E, integ.pitch, integ.frequency, 70)                                 # :130-136
+    convex = float(getattr(integ, "radius", 0.0)) != 0.0
+    if convex:  # the curved array (DESIGN D18): element table instead of positions, the *_probe beamformer
+        probe = build_probe("convex", E, integ.pitch, integ.frequency, 70, radius=integ.radius, opening_angle=integ.opening_angle)
+    else:
+        probe = build_probe("linear", E, integ.pitch, integ.frequency, 70)                             # :130-136
     bf = beamformer or DelayAndSum(on_gpu=True)
     seq = {"emitted": np.tile(np.arange(E), (A, 1)), "received": np.tile(np.arange(E), (A, 1))}
 
@@ -305,10 +379,11 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
 
     cx = scene.device().ctx
     gaussian = integ.pulse_model == "gaussian"
-    key = (A, E, T, float(integ.pitch), x_scan.tobytes(), z_scan.tobytes(), gaussian, id(cx))
+    key = (A, E, T, float(integ.pitch), x_scan.tobytes(), z_scan.tobytes(), gaussian, id(cx), probe.geometry_type, probe.radius,
+           probe.opening_angle)
     plan = getattr(integ, "_render_plan", None)
     if plan is None or plan.key != key:
-        plan = _RenderPlan(cx, A, E, T, probe.geometry[0], x_scan, z_scan, gaussian)
+        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian)
         plan.key = key
         integ._render_plan = plan
     rf = plan.d_rf if gaussian else plan.d_channel

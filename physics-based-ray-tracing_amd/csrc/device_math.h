@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #define DEV __device__ __forceinline__
+#define HDEV __host__ __device__ __forceinline__  // the few statements the host evaluates too (the curved array's element table)
 
 // Exact unsigned division by a launch-uniform divisor (Granlund-Montgomery round-up multiplier, the
 // branch-free 33-bit form):  n / d == (((n - hi) >> 1) + hi) >> shift  with hi = mulhi(n, magic), for every
@@ -96,7 +97,7 @@ DEV V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 DEV V3 operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
 DEV V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 DEV V3 operator*(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
-DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+HDEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 DEV float dot(V3 a, V3 b) { return fma_(a.x, b.x, fma_(a.y, b.y, a.z * b.z)); }
 DEV V3 cross(V3 a, V3 b) {
     return {fma_(a.y, b.z, -(a.z * b.y)), fma_(a.z, b.x, -(a.x * b.z)), fma_(a.x, b.y, -(a.y * b.x))};
@@ -141,7 +142,7 @@ DEV F4 rng4(uint32_t a, uint32_t b, uint32_t c, uint32_t seed) {
 }
 
 // ---- sin/cos on [-pi/4, pi/4] -------------------------------------------------------------------
-DEV void sincos_pi4(float x, float *s, float *c) {
+HDEV void sincos_pi4(float x, float *s, float *c) {
     float x2 = x * x;
     float ps = fma_(x2, 2.7557319223985893e-06f, -1.9841269841269841e-04f);
     ps = fma_(x2, ps, 8.3333333333333332e-03f);

@@ -89,8 +89,19 @@ DEV double das_lane_f64(double v, uint32_t e) {
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
+// CONVEX (the *_probe entry points, DESIGN D18): `elem_x` is the element table [n_elements][4] = (x_e, z_e, nx_e, nz_e) of a curved
+// array instead of [n_elements] positions on the line z = 0.  Distances are |(x, z) - (x_e, z_e)| on the transmit and on the receive
+// side, and the f-number aperture lies in the element's own frame: with v = (x - x_e, z - z_e), depth d_n = v . n_e and lateral
+// d_t = v x n_e, element e receives the pixel iff d_n > 0 and 2 f# |d_t| <= d_n (f# <= 0: every element receives every pixel).  For
+// n_e = (0, 1), z_e = 0 that is |x - x_e| <= z / (2 f#).  The tile early-out is ABSENT in the CONVEX instances: every tile walks the
+// elements, and an element no pixel of the tile sees is left before its square root, as in the linear form.
+// distance of pixel (x, z) to an element: dx = x - x_e, and zz = z * z (linear) or dz = z - z_e (CONVEX)
+template <bool CONVEX>
+DEV double das_dist2(double dx, double zz, double dz) { return CONVEX ? dx * dx + dz * dz : dx * dx + zz; }
+
 // first-arrival table of a scan: ttx[a][ix][iz] = min_e (tx[a][e] + |(x, z) - (x_e, 0)| / c), the statement of k_das_beamform's first
 // pass (same operands, same operations: the same doubles).  One thread per pixel, z fastest.
+template <bool CONVEX = false>
 __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, const float *__restrict__ tx, const float *__restrict__ elem_x,
                                                            const float *__restrict__ gx, const float *__restrict__ gz,
                                                            double *__restrict__ ttx) {
@@ -106,8 +117,9 @@ __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, co
 #pragma unroll
         for (uint32_t j = 0; j < DAS_ANG; ++j) tmin[j] = 1e300;
         for (uint32_t e = 0; e < E; ++e) {
-            const double dx = x - (double)elem_x[e];
-            const double d = sqrt(dx * dx + zz) * inv_c;
+            const double dx = x - (double)elem_x[CONVEX ? 4u * e : e];
+            const double dz = CONVEX ? z - (double)elem_x[4u * e + 1u] : 0.0;
+            const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
 #pragma unroll
             for (uint32_t j = 0; j < DAS_ANG; ++j)
                 if (j < na) tmin[j] = fmin(tmin[j], (double)tx[(size_t)(a0 + j) * E + e] + d);
@@ -121,7 +133,8 @@ __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, co
 // TABLE: the first-arrival times come from a table [n_angles][nx][nz] of doubles (k_das_first_arrival: the same minimum, made once
 // for a scan whose delays and grid do not change -- the 51 renders of USMain.py share one) instead of a pass over all elements
 // per call; the rest of the kernel, and every bit of its result, is the same.
-template <uint32_t INTERP, bool TABLE>
+// CONVEX: the element table of a curved array (above); its four columns are held in lanes and picked with v_readlane like elem_x.
+template <uint32_t INTERP, bool TABLE, bool CONVEX = false>
 #ifdef DAS_WAVES_PER_EU  // A/B: register budget of the kernel (default: what the compiler takes, 70 VGPRs = 7 waves per SIMD)
 __attribute__((amdgpu_waves_per_eu(DAS_WAVES_PER_EU, DAS_WAVES_PER_EU)))
 #endif
@@ -150,21 +163,25 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
     // conservative otherwise -- a tile that passes without an element in any aperture just adds nothing.  The loop over all
     // elements this replaces was a fifth of a wave's instruction stream.)
     float ex_lo = 3.0e38f, ex_hi = -3.0e38f;
-    for (uint32_t eb = 0; eb < E; eb += 64u) {
+    for (uint32_t eb = 0; !CONVEX && eb < E; eb += 64u) {
         const float v = elem_x[eb + min(lane, E - eb - 1u)];
         ex_lo = fminf(ex_lo, v);
         ex_hi = fmaxf(ex_hi, v);
     }
+    if (!CONVEX) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
-        ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
+        for (int off = 32; off > 0; off >>= 1) {
+            ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
+            ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
+        }
     }
-    bool any = valid && x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi;
+    // (CONVEX: no early-out -- the apertures of a curved array fan out, the span of the x_e bounds nothing)
+    bool any = valid && (CONVEX || (x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi));
     if (__ballot(any) == 0ull) {
         if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = 0.0f;
         return;
     }
+    const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;  // CONVEX: 2 f# |d_t| <= d_n
     float acc = 0.0f;
     const double last = (double)(T - 1u);
     for (uint32_t a0 = 0; a0 < A; a0 += DAS_ANG) {
@@ -181,13 +198,15 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
         }
         for (uint32_t eb = 0; !TABLE && eb < E; eb += 64u) {
             const uint32_t ne = min(64u, E - eb), le = min(lane, ne - 1u);
-            const double ex_l = (double)elem_x[eb + le];
+            const double ex_l = (double)elem_x[CONVEX ? 4u * (eb + le) : eb + le];
+            const double ez_l = CONVEX ? (double)elem_x[4u * (eb + le) + 1u] : 0.0;
             double tx_l[DAS_ANG];
 #pragma unroll
             for (uint32_t j = 0; j < DAS_ANG; ++j) tx_l[j] = j < na ? (double)tx[(size_t)(a0 + j) * E + eb + le] : 0.0;
             for (uint32_t e = wave; e < ne; e += DAS_SPLIT) {
                 const double dx = x - das_lane_f64(ex_l, e);
-                const double d = sqrt(dx * dx + zz) * inv_c;
+                const double dz = CONVEX ? z - das_lane_f64(ez_l, e) : 0.0;
+                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
 #pragma unroll
                 for (uint32_t j = 0; j < DAS_ANG; ++j)
                     if (j < na) tmin[j] = fmin(tmin[j], das_lane_f64(tx_l[j], e) + d);
@@ -216,13 +235,25 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
         }
         for (uint32_t eb = 0; eb < E; eb += 64u) {
             const uint32_t ne = min(64u, E - eb);
-            const double ex_l = (double)elem_x[eb + min(lane, ne - 1u)];
+            const uint32_t ee = eb + min(lane, ne - 1u);
+            const double ex_l = (double)elem_x[CONVEX ? 4u * ee : ee];
+            const double ez_l = CONVEX ? (double)elem_x[4u * ee + 1u] : 0.0, nx_l = CONVEX ? (double)elem_x[4u * ee + 2u] : 0.0,
+                         nz_l = CONVEX ? (double)elem_x[4u * ee + 3u] : 0.0;
             for (uint32_t el = wave; el < ne; el += DAS_SPLIT) {
                 const uint32_t e = eb + el;
                 const double dx = x - das_lane_f64(ex_l, el);
-                const bool in_ap = any && fabs(dx) <= half_ap;
+                double dz = 0.0;
+                bool in_ap;
+                if (CONVEX) {
+                    dz = z - das_lane_f64(ez_l, el);
+                    const double enx = das_lane_f64(nx_l, el), enz = das_lane_f64(nz_l, el);
+                    const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
+                    in_ap = any && (p.f_number > 0.0f ? (dn > 0.0 && two_f * fabs(dt) <= dn) : true);
+                } else {
+                    in_ap = any && fabs(dx) <= half_ap;
+                }
                 if (__ballot(in_ap) == 0ull) continue;
-                const double d = sqrt(dx * dx + zz) * inv_c;
+                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
                 if (INTERP == PBRT_DAS_NEAREST) {
 #pragma unroll
                     for (uint32_t j = 0; j < DAS_ANG; ++j) {

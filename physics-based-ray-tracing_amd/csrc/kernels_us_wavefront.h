@@ -38,13 +38,15 @@ struct UsWfArgs {
 };
 
 // primary rays of a pass into the path state (depth 0 without first-bounce tables): CustomIntegrator.py:270-279
+// CONVEX: the curved array's origins come from the element table (kernels_us.h us_elem_point)
+template <bool CONVEX = false>
 __global__ __launch_bounds__(256) void k_us_init_wf(const UsArgs a, float4 *st, uint32_t *seg_cnt, uint32_t n_regions) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_regions) seg_cnt[i] = a.n_paths > i * WF_REGION ? min(a.n_paths - i * WF_REGION, WF_REGION) : 0u;
     if (i >= a.n_paths) return;
     const uint32_t ray_id = udiv_fast(i, a.div_ppr);
     const uint32_t ang = udiv_fast(ray_id, a.div_ne), el = ray_id - ang * a.p.n_elements;
-    V3 o = xf_point(a.p.sensor_to_world, v3(a.elem_x[el], 0.0f, 0.0f));
+    V3 o = us_elem_point<CONVEX>(a, a.p.sensor_to_world, el);
     V3 d = v3(a.dir0[3 * ang], a.dir0[3 * ang + 1], a.dir0[3 * ang + 2]);
     float tof = 0.0f, w_ray = 1.0f;
     if (a.p.primary == PBRT_US_PRIMARY_EMITTER)  // the path's own ray from CustomEmitter.sample_ray (kernels_us.h us_emitter_primary)
@@ -59,8 +61,8 @@ __global__ __launch_bounds__(256) void k_us_init_wf(const UsArgs a, float4 *st, 
 }
 
 // TAB: depth 0 with the first-bounce tables (the paths are generated from their index, nothing is read but the tables).
-// CYL: the scene holds cylinders (else their code is compiled out)
-template <bool TAB, bool CYL>
+// CYL: the scene holds cylinders (else their code is compiled out).  CONVEX: the curved array (kernels_us.h us_elem_point)
+template <bool TAB, bool CYL, bool CONVEX = false>
 __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_shade(const UsWfArgs w) {
     constexpr uint32_t T_ = WF_SHADE_THREADS, W = T_ / 64;
     constexpr int NCH = WF_SHADE_CHUNKS;
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
                 k = a.path_first + (home - ray_id * a.ppr_pass);
                 ang = udiv_fast(ray_id, a.div_ne);
                 const uint32_t el = ray_id - ang * NE;
-                o = xf_point(uni, v3(a.elem_x[el], 0.0f, 0.0f));                         // :270,273
+                o = us_elem_point<CONVEX>(a, uni, el);                                   // :270,273
                 d = v3(a.dir0[3 * ang], a.dir0[3 * ang + 1], a.dir0[3 * ang + 2]);        // :271,273
                 const float4 fh = a.first_hit[ray_id];
                 h.t = fh.x;
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
             if (TAB) {
                 rx = a.first_rx[(size_t)ray_id * NE + recv];
             } else {
-                const UsRecv rc = us_receive(a, uni, si.p, recv);
+                const UsRecv rc = us_receive<CONVEX>(a, uni, si.p, recv);
                 sdir = rc.sec_dir;
                 so = offset_origin(si.p, si.n, sdir);                                     // :324 (the ray k_trace walks)
                 total_time = us_arrival(a, uni[U_INVC], a.p.quirks, ray_id, tof, distance, rc.dist_recv);
@@ -223,7 +225,8 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_us_
                     carrier = rx.y;
                     ci = __float_as_uint(rx.z);                                           // (visibility included)
                 } else if (us_echo_bin(NE, T, a.p.quirks, total_time, uni[U_FS], ang, recv, true, &ci)) {
-                    us_echo_weight(a, NE, a.p.quirks, d, si.ns, sdir, tn, uni[U_AM], uni[U_AC], phase, &fd, &carrier);
+                    us_echo_weight(a, NE, a.p.quirks, d, si.ns, sdir, us_recv_normal<CONVEX>(a, uni, recv, tn), uni[U_AM], uni[U_AC], phase, &fd,
+                                   &carrier);
                 }
                 pressure = atten * amp * fd * carrier * w_ray;                            // :348 (x 1, or the emitter ray's weight: D15)
                 if (ci != 0xffffffffu) {

@@ -705,8 +705,25 @@ static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool fi
 // has its table mode compiled in too: -1 on later bounces, 0 for emitter rays (never any tables).  Everything else reads both at
 // run time.  nullptr: BVH scenes run k_trace / k_us_shade (us_wf_pass); their fused bounce (PBRT_US_FUSED_BVH=1, no emitter rays)
 // exists in the diagnostic build only.
-static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint32_t q, int tab) {
+// convex (PBRT_US_ARRAY_CONVEX, D18): the instances of the curved array -- the generic ones only (quirks and tables read at run time).
+static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint32_t q, int tab, bool convex = false) {
     if (!first) tab = -1;
+    if (convex) {
+        switch (s->accel_kernel) {
+            case ACCEL_K_BRUTE:
+                return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce_convex<F(), ACCEL_K_BRUTE, E()>; }, first, emit);
+            case ACCEL_K_BRUTE_BIG:
+                return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce_convex<F(), ACCEL_K_BRUTE_BIG, E()>; }, first, emit);
+            default:
+#ifdef PBRT_DIAG
+                if (!emit)
+                    return with_flags([](auto F, auto L) -> UsKern {
+                        return &k_us_bounce_convex<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL>; },
+                                      first, s->accel_kernel == ACCEL_K_BVH_LDS);
+#endif
+                return nullptr;
+        }
+    }
     switch (s->accel_kernel) {
         case ACCEL_K_BRUTE:
             if (q != US_Q_RUNTIME && (tab >= 0 || !first))
@@ -730,7 +747,8 @@ static int set_lds_attr(pbrt_scene *s) {
     if (s->accel_kernel != ACCEL_K_BVH_LDS) return PBRT_OK;
     for (bool first : {true, false}) {
         if (const RadKern k = bounce_kernel(s, first, 1)) HIPCHK(s->ctx, set_max_lds(k, s->lds_bytes));
-        if (const UsKern k = us_bounce_kernel(s, first, false, US_Q_RUNTIME, -1)) HIPCHK(s->ctx, set_max_lds(k, s->lds_bytes));
+        for (bool convex : {false, true})
+            if (const UsKern k = us_bounce_kernel(s, first, false, US_Q_RUNTIME, -1, convex)) HIPCHK(s->ctx, set_max_lds(k, s->lds_bytes));
     }
     return PBRT_OK;
 }
@@ -1758,8 +1776,60 @@ static inline float us_elem_x(const pbrt_us_params *p, uint32_t e) {
     return (float)((double)p->pitch * ((double)(float)e - ((double)p->n_elements - 1.0) / 2.0));
 }
 
+// The curved array (PBRT_US_ARRAY_CONVEX, DESIGN D18).  The geometry is CustomEmitter's (CustomEmmitter.py:41-47), evaluated with the
+// float statements of kernels_us.h us_emitter_ray, so that the position an emitter ray starts from and the position the receive
+// connection aims at are the same floats (sin / cos: kernels_us.h emit_sincos itself, compiled for the host -- the polynomial of
+// device_math.h sincos_pi4 up to 45 degrees; beyond, the host's sinf / cosf where the kernel calls the device library's, which agree
+// to a few ulp).
+static bool us_convex(const pbrt_us_params *p) { return (p->primary & PBRT_US_ARRAY_CONVEX) != 0; }
+static bool us_convex_valid(const pbrt_us_params *p) {
+    const pbrt_us_emitter &E = p->emitter;
+    return std::isfinite(E.radius) && E.radius > 0.0f && std::isfinite(E.opening_angle) && E.opening_angle > 0.0f &&
+           E.opening_angle < 180.0f && E.number_of_elements == p->n_elements;
+}
+// element e of the array: (x, z, nx, nz) in the sensor's frame
+static void us_array_element(const pbrt_us_params *p, uint32_t e, float *out) {
+    if (!us_convex(p)) {
+        out[0] = us_elem_x(p, e);
+        out[1] = 0.0f;
+        out[2] = 0.0f;
+        out[3] = 1.0f;
+        return;
+    }
+    const float N = (float)p->n_elements, idx = (float)e;
+    const float span = p->emitter.opening_angle * (K_PI / 180.0f);                            // CustomEmmitter.py:42
+    const float lo = -span / 2.0f, hi = span / 2.0f;
+    const float th = N > 1.0f ? host_fma(idx, (hi - lo) / (N - 1.0f), lo) : lo;               // :43
+    float sth, cth;
+    emit_sincos(th, &sth, &cth);  // (kernels_us.h: the one text host and kernels share)
+    out[0] = p->emitter.radius * sth;                                                         // :44-46
+    out[1] = p->emitter.radius * cth;
+    out[2] = sth;                                                                             // :47
+    out[3] = cth;
+}
+
+int pbrt_us_array_elements(const pbrt_us_params *p, float *elem) {
+    if (!p || !elem || p->n_elements == 0) return PBRT_E_INVALID;
+    if (us_convex(p) && !us_convex_valid(p)) return PBRT_E_INVALID;
+    for (uint32_t e = 0; e < p->n_elements; ++e) us_array_element(p, e, elem + 4 * (size_t)e);
+    return PBRT_OK;
+}
+
 int pbrt_us_tx_delays(const pbrt_us_params *p, float *tx) {
     if (!p || !tx || p->n_angles > PBRT_US_MAX_ANGLES || p->n_angles == 0 || p->n_elements == 0) return PBRT_E_INVALID;
+    if (us_convex(p)) {  // the plane wave along (sin a, 0, cos a), referenced to the apex (0, 0, R): (x_e sin a + (z_e - R) cos a) / c
+        if (!us_convex_valid(p)) return PBRT_E_INVALID;
+        for (uint32_t a = 0; a < p->n_angles; ++a) {
+            const double ar = (double)p->angles_deg[a] * (M_PI / 180.0);
+            for (uint32_t e = 0; e < p->n_elements; ++e) {
+                float el[4];
+                us_array_element(p, e, el);
+                tx[a * p->n_elements + e] = (float)(((double)el[0] * std::sin(ar) + ((double)el[1] - (double)p->emitter.radius) * std::cos(ar)) /
+                                                    (double)p->sound_speed);
+            }
+        }
+        return PBRT_OK;
+    }
     for (uint32_t a = 0; a < p->n_angles; ++a) {
         double ar = (double)p->angles_deg[a] * (M_PI / 180.0);  // np.deg2rad, CustomIntegrator.py:247
         for (uint32_t e = 0; e < p->n_elements; ++e) {
@@ -1781,10 +1851,10 @@ static uint32_t us_kernel_quirks(const UsArgs &a, bool generic) {
     const uint32_t q = a.p.quirks & ~host_only;
     return (q == PBRT_USQ_REFERENCE || q == (PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER)) ? q : US_Q_RUNTIME;
 }
-static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg, bool first, bool generic) {
+static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg, bool first, bool generic, bool convex) {
     const bool emit = a.p.primary == PBRT_US_PRIMARY_EMITTER;  // primary rays from CustomEmitter.sample_ray, echoes times the ray's weight
     const int tab = (a.first_hit && a.first_rx) ? 1 : (!a.first_hit && !a.first_rx) ? 0 : -1;
-    const UsKern k = us_bounce_kernel(s, first, emit, us_kernel_quirks(a, generic), tab);
+    const UsKern k = us_bounce_kernel(s, first, emit, us_kernel_quirks(a, generic), tab, convex);
     if (!k && emit)
         return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: emitter primary rays on BVH scenes run as streams (us_wf_pass)");
     if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: no fused ultrasound bounce for accelerator %d in this build", s->accel_kernel);
@@ -1795,8 +1865,9 @@ static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg, bool first, 
 // The kernels that meet one ray with the scene and nothing else (first-bounce tables, leaf operators): the brute-force loop over
 // the full tables, or the tree in global memory
 static bool brute_scene(const pbrt_scene *s) { return s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG; }
-static UsFirstKern us_first_kernel(const pbrt_scene *s) {
-    return brute_scene(s) ? &k_us_first<ACCEL_K_BRUTE_BIG> : &k_us_first<ACCEL_K_BVH_GLOBAL>;
+static UsFirstKern us_first_kernel(const pbrt_scene *s, bool convex) {
+    return with_flags([](auto B, auto X) -> UsFirstKern { return &k_us_first<B() ? ACCEL_K_BRUTE_BIG : ACCEL_K_BVH_GLOBAL, X()>; },
+                      brute_scene(s), convex);
 }
 static RayIntersectKern ray_intersect_kernel(const pbrt_scene *s) {
     return brute_scene(s) ? &k_ray_intersect<ACCEL_K_BRUTE_BIG> : &k_ray_intersect<ACCEL_K_BVH_GLOBAL>;
@@ -1804,15 +1875,15 @@ static RayIntersectKern ray_intersect_kernel(const pbrt_scene *s) {
 static RayTestKern ray_test_kernel(const pbrt_scene *s) {
     return brute_scene(s) ? &k_ray_test<ACCEL_K_BRUTE_BIG> : &k_ray_test<ACCEL_K_BVH_GLOBAL>;
 }
-// k_us_shade: first bounce from the tables, scene with cylinders
-static UsWfKern us_shade_kernel(const pbrt_scene *s, bool tab) {
-    return with_flags([](auto T, auto C) -> UsWfKern { return &k_us_shade<T(), C()>; }, tab, s->cylinders);
+// k_us_shade: first bounce from the tables, scene with cylinders, curved array
+static UsWfKern us_shade_kernel(const pbrt_scene *s, bool tab, bool convex) {
+    return with_flags([](auto T, auto C, auto X) -> UsWfKern { return &k_us_shade<T(), C(), X()>; }, tab, s->cylinders, convex);
 }
 
 // BVH scenes: the bounces of one ultrasound pass as k_trace / k_us_shade streams (kernels_us_wavefront.h).  a: the pass's UsArgs
 // (cap, n_paths, ppr_pass, path_first, tables set).  One launch at depth 0 with the first-bounce tables (else k_us_init_wf +
 // k_trace + k_us_shade), two per later bounce, and a flush for the occlusion rays of the last one.
-static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p, uint32_t nreg, uint32_t *launches) {
+static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p, uint32_t nreg, bool convex, uint32_t *launches) {
     pbrt_ctx *c = s->ctx;
     hipStream_t st = c->stream;
     WfArgs t{};
@@ -1851,14 +1922,15 @@ static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p,
         w.seg_out = pp.sout;
         w.nsh_in = have_shadows ? pp.ni : nullptr;
         w.nsh_out = pp.no;
-        hipLaunchKernelGGL(us_shade_kernel(s, tab), dim3(nreg), dim3(WF_SHADE_THREADS), 0, st, w);
+        hipLaunchKernelGGL(us_shade_kernel(s, tab, convex), dim3(nreg), dim3(WF_SHADE_THREADS), 0, st, w);
         ++*launches;
     };
     const bool tab = a.first_hit != nullptr && a.first_rx != nullptr;
     if (tab) {
         shade(0, true, false);
     } else {
-        hipLaunchKernelGGL(k_us_init_wf, dim3(div_up(std::max(a.n_paths, nreg), 256)), dim3(256), 0, st, a, pp.in, pp.sin, nreg);
+        hipLaunchKernelGGL(convex ? k_us_init_wf<true> : k_us_init_wf<false>, dim3(div_up(std::max(a.n_paths, nreg), 256)), dim3(256), 0, st, a, pp.in,
+                           pp.sin, nreg);
         trace(0, false);
         shade(0, false, false);
     }
@@ -1893,13 +1965,24 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     NEED(c, (uint64_t)p->n_angles * p->n_elements * p->time_samples < 0xffffffffull);  // channel index is 32-bit (echo bins)
     NEED(c, p->max_depth > 0 && ppr > 0 && p->sound_speed > 0 && p->fs > 0);
     NEED(c, p->max_depth < 0x40000000u);  // RNG block = bounce index; bit 30 marks a path's second block of a bounce, bit 31 the emitter's
-    NEED(c, p->primary <= PBRT_US_PRIMARY_EMITTER);
-    const bool emit = p->primary == PBRT_US_PRIMARY_EMITTER;
+    const bool convex = us_convex(p);  // the curved array (DESIGN D18): geometry from p->emitter, kernels of their own
+    const uint32_t primary = p->primary & ~PBRT_US_ARRAY_CONVEX;
+    NEED(c, primary <= PBRT_US_PRIMARY_EMITTER);
+    const bool emit = primary == PBRT_US_PRIMARY_EMITTER;
     if (emit) {  // CustomEmitter as the source of the primary rays: its elements are the acquisition's (include/pbrt_hip.h)
         const pbrt_us_emitter &E = p->emitter;
         NEED(c, E.number_of_elements == p->n_elements && E.number_of_rays_per_element > 0 && E.speed_of_sound > 0.0f);
         NEED(c, std::isfinite(E.pitch) && std::isfinite(E.element_width) && std::isfinite(E.element_height) && std::isfinite(E.radius));
         NEED(c, std::isfinite(E.steering_angle_min) && std::isfinite(E.steering_angle_max) && std::isfinite(E.opening_angle));
+        // an emitter on an arc and receivers on a line: never defined (D18) -- the curved array is asked for with PBRT_US_ARRAY_CONVEX
+        if (!convex && E.radius != 0.0f)
+            return c->fail(PBRT_E_UNSUPPORTED, "emitter.radius != 0 transmits from an arc: set PBRT_US_ARRAY_CONVEX in pbrt_us_params.primary");
+    }
+    if (convex) {
+        const pbrt_us_emitter &E = p->emitter;
+        NEED(c, std::isfinite(E.radius) && E.radius > 0.0f);
+        NEED(c, std::isfinite(E.opening_angle) && E.opening_angle > 0.0f && E.opening_angle < 180.0f);
+        NEED(c, E.number_of_elements == p->n_elements);
     }
     HIPCHK(c, hipSetDevice(c->device));
     int rc = set_lds_attr(s);
@@ -1907,7 +1990,8 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     const Switches sw = read_switches();
     const uint32_t NA = p->n_angles, NE = p->n_elements, T = p->time_samples;
     const uint32_t n_rays = NA * NE;
-    std::vector<float> tx(n_rays), dir0(3 * NA), ex(NE);
+    const uint32_t n_ex = convex ? 4u * NE : NE;  // element positions, or the curved array's (x, z, nx, nz) table
+    std::vector<float> tx(n_rays), dir0(3 * NA), ex(n_ex);
     pbrt_us_tx_delays(p, tx.data());
     if (tx_host) std::memcpy(tx_host, tx.data(), tx.size() * 4);
     const float *M = p->sensor_to_world;
@@ -1927,7 +2011,10 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         xfv(sinf(ar), 0.0f, cosf(ar), &dir0[3 * a]);
         nrm(&dir0[3 * a]);
     }
-    for (uint32_t e = 0; e < NE; ++e) ex[e] = us_elem_x(p, e);
+    if (convex)
+        pbrt_us_array_elements(p, ex.data());
+    else
+        for (uint32_t e = 0; e < NE; ++e) ex[e] = us_elem_x(p, e);
 #ifndef US_PASS_PATHS
 // paths in flight per pass.  Config 3 (268 M paths), one launch per bounce: 8 / 16 / 32 / 64 Mi -> 13.1 / 12.7 / 13.0 /
 // 13.2 ms; with all bounces of a pass in one launch the survivors are re-read while still cached and smaller passes
@@ -1978,7 +2065,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     unsigned long long *dstats = (unsigned long long *)c->buf("us_stats", segstats_bytes);
     if (!dstats) return PBRT_E_NOMEM;
     unsigned long long *segstats = dstats;
-    float *tabs = (float *)c->buf("us_tables", ((size_t)n_rays + 3 * NA + NE) * 4);
+    float *tabs = (float *)c->buf("us_tables", ((size_t)n_rays + 3 * NA + n_ex) * 4);
     if ((!streams && (!segA || !segB)) || !dstats || !tabs) return PBRT_E_NOMEM;
     hipStream_t st = c->stream;
     float *d_tx = tabs, *d_dir = tabs + n_rays, *d_ex = d_dir + 3 * NA;
@@ -1989,7 +2076,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     // either form clean since.)
     // the three small tables in one host image; uploaded only when they differ from what the device copy already holds
     {
-        std::vector<float> img((size_t)n_rays + 3 * NA + NE);
+        std::vector<float> img((size_t)n_rays + 3 * NA + n_ex);
         if (emit)  // the ray's own emission time rides in its time of flight (CustomEmmitter.py:93-94); t0 of :329 is 0
             std::fill(img.begin(), img.begin() + n_rays, 0.0f);
         else
@@ -2018,6 +2105,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     UsArgs a{};
     a.sc = s->ds;
     a.p = *p;
+    a.p.primary = primary;  // (the kernels compare it with PBRT_US_PRIMARY_*; the array is a template switch of theirs)
     a.stats = segstats;
     a.stat_stride = n_own;
     a.channel = d_channel;
@@ -2048,7 +2136,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         float4 *fv = (float4 *)c->buf("us_first_rx", (size_t)n_rays * NE * 16);
         if (!fh || !fv) return PBRT_E_NOMEM;
         const dim3 g(div_up((uint64_t)n_rays * NE, 256)), b(256);
-        hipLaunchKernelGGL(us_first_kernel(s), g, b, 0, st, a, n_rays, fh, fv);
+        hipLaunchKernelGGL(us_first_kernel(s, convex), g, b, 0, st, a, n_rays, fh, fv);
         HIPCHK(c, hipGetLastError());
         a.first_hit = fh;
         a.first_rx = fv;
@@ -2072,7 +2160,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         }
         if (streams) {
             if ((rc = timer.begin()) != 0) return rc;
-            if ((rc = us_wf_pass(s, a, wfb, wfp, nseg_pass, &launches)) != 0) return rc;
+            if ((rc = us_wf_pass(s, a, wfb, wfp, nseg_pass, convex, &launches)) != 0) return rc;
             if ((rc = timer.end()) != 0) return rc;
             continue;
         }
@@ -2098,7 +2186,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
                 a.seg_out = sout;
                 first_kernel = false;
             }
-            if ((rc = launch_us(s, a, nseg_pass, first_kernel, sw.us_generic_kernel)) != 0) return rc;
+            if ((rc = launch_us(s, a, nseg_pass, first_kernel, sw.us_generic_kernel, convex)) != 0) return rc;
             HIPCHK(c, hipGetLastError());
             ++launches;
             if (a.fuse) break;  // that launch walked every bounce (kernels_us.h)
@@ -2447,8 +2535,9 @@ static int das_check(pbrt_ctx *ctx, const pbrt_das_params *p) {
     NEED(ctx, (uint64_t)div_up(p->nx, DAS_TILE) * (div_up(p->nz, DAS_TILE) + DAS_BANDS) * DAS_XCDS < 0x7fffffffull);
     return PBRT_OK;
 }
+// de: element positions [n_elements], or (probe) the element table [n_elements][4] of pbrt_us_array_elements
 static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, const float *dt, const float *de, const float *dx,
-                       const float *dz, float *dout, const double *ttx = nullptr) {
+                       const float *dz, float *dout, const double *ttx = nullptr, bool probe = false) {
     ImgTimer tm(c, IMG_DAS);
     DasGrid g;
     g.ntx = div_up(p->nx, DAS_TILE);
@@ -2459,8 +2548,8 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    const auto kernel = with_flags([](auto L, auto T) { return &k_das_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T()>; },
-                                   p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr);
+    const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_das_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
+                                   p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe);
     hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
     c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * 4;
     HIPCHK(c, hipGetLastError());
@@ -2526,58 +2615,94 @@ static int pulse_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, uint32_t K,
     return PBRT_OK;
 }
 
-extern "C" {
-
-int pbrt_das_beamform_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
-                          const void *d_x, const void *d_z, void *d_out) {
+// the four DAS entry points and their *_probe twins (element table instead of positions): one body each
+static int das_beamform_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
+                                 const void *d_x, const void *d_z, void *d_out, bool probe) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && d_data && d_tx_delays && d_elem_x && d_x && d_z && d_out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, p, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x,
-                       (const float *)d_z, (float *)d_out);
+                       (const float *)d_z, (float *)d_out, nullptr, probe);
 }
 
-int pbrt_das_first_arrival_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
-                               const void *d_z, void *d_table) {
+static int das_first_arrival_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
+                                      const void *d_z, void *d_table, bool probe) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && d_tx_delays && d_elem_x && d_x && d_z && d_table);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_das_first_arrival, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256), 0, ctx->stream, *p, (const float *)d_tx_delays,
-                       (const float *)d_elem_x, (const float *)d_x, (const float *)d_z, (double *)d_table);
+    hipLaunchKernelGGL(probe ? k_das_first_arrival<true> : k_das_first_arrival<false>, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256), 0,
+                       ctx->stream, *p, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x, (const float *)d_z,
+                       (double *)d_table);
     HIPCHK(ctx, hipGetLastError());
     return PBRT_OK;
 }
 
-int pbrt_das_beamform_table_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem_x,
-                                const void *d_x, const void *d_z, void *d_out) {
+static int das_beamform_table_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem_x,
+                                       const void *d_x, const void *d_z, void *d_out, bool probe) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && d_data && d_table && d_elem_x && d_x && d_z && d_out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, p, (const float *)d_data, nullptr, (const float *)d_elem_x, (const float *)d_x, (const float *)d_z,
-                       (float *)d_out, (const double *)d_table);
+                       (float *)d_out, (const double *)d_table, probe);
 }
 
-int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
-                      const float *elem_x, const float *x, const float *z, float *out) {
+static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays, const float *elem_x,
+                             const float *x, const float *z, float *out, bool probe) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && data && tx_delays && elem_x && x && z && out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     const size_t nd = (size_t)p->n_angles * p->n_elements * p->time_samples, ne = (size_t)p->n_angles * p->n_elements;
     const uint32_t n = p->nx * p->nz;
-    STAGED_BEGIN(ctx, (nd + ne + p->n_elements + p->nx + p->nz + (size_t)n) * 4 + 256);
-    float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem_x, p->n_elements);
+    const size_t nel = (size_t)p->n_elements * (probe ? 4u : 1u);
+    STAGED_BEGIN(ctx, (nd + ne + nel + p->nx + p->nz + (size_t)n) * 4 + 256);
+    float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem_x, nel);
     float *dx = S.in(x, p->nx), *dz = S.in(z, p->nz);
     float *dout = S.out<float>(n);
-    if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout)) != 0) return rc;
+    if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout, nullptr, probe)) != 0) return rc;
     S.back(out, dout, n);
     return S.finish();
+}
+
+extern "C" {
+
+int pbrt_das_beamform_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
+                          const void *d_x, const void *d_z, void *d_out) {
+    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, d_elem_x, d_x, d_z, d_out, false);
+}
+int pbrt_das_beamform_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
+                                const void *d_x, const void *d_z, void *d_out) {
+    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, d_elem, d_x, d_z, d_out, true);
+}
+int pbrt_das_first_arrival_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
+                               const void *d_z, void *d_table) {
+    return das_first_arrival_dev_impl(ctx, p, d_tx_delays, d_elem_x, d_x, d_z, d_table, false);
+}
+int pbrt_das_first_arrival_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem, const void *d_x,
+                                     const void *d_z, void *d_table) {
+    return das_first_arrival_dev_impl(ctx, p, d_tx_delays, d_elem, d_x, d_z, d_table, true);
+}
+int pbrt_das_beamform_table_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem_x,
+                                const void *d_x, const void *d_z, void *d_out) {
+    return das_beamform_table_dev_impl(ctx, p, d_data, d_table, d_elem_x, d_x, d_z, d_out, false);
+}
+int pbrt_das_beamform_table_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem,
+                                      const void *d_x, const void *d_z, void *d_out) {
+    return das_beamform_table_dev_impl(ctx, p, d_data, d_table, d_elem, d_x, d_z, d_out, true);
+}
+int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
+                      const float *elem_x, const float *x, const float *z, float *out) {
+    return das_beamform_impl(ctx, p, data, tx_delays, elem_x, x, z, out, false);
+}
+int pbrt_das_beamform_probe(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
+                            const float *elem, const float *x, const float *z, float *out) {
+    return das_beamform_impl(ctx, p, data, tx_delays, elem, x, z, out, true);
 }
 
 int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf, void *d_env) {

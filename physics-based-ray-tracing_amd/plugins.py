@@ -824,6 +824,11 @@ class UltraIntegrator(SamplingIntegrator):
         self.primary_rays = str(props.get("primary_rays", "element"))
         if self.primary_rays not in ("element", "emitter"):
             raise ValueError("primary_rays must be 'element' or 'emitter'")
+        # The array: radius 0 = the reference's line of elements; radius > 0 = the curved array of CustomEmmitter.py:41-47 -- centre of
+        # curvature at the sensor's origin, `opening_angle` degrees from the first element to the last, `pitch` not read
+        # [DEFINE, DESIGN D18: the reference's integrator knows no curved array]
+        self.radius = float(props.get("radius", 0.0))
+        self.opening_angle = float(props.get("opening_angle", 0.0))
 
     # ray_count (CustomIntegrator.py:231,360,402): segments traced by the last acquisition; after a queued acquisition the counter
     # is fetched when somebody reads it (that waits for the stream)
@@ -881,6 +886,7 @@ class UltraIntegrator(SamplingIntegrator):
         p.max_path_len = self.max_path_len
         p.quirks = int(self.quirks if quirks is None else quirks)
         p.primary = _capi.US_PRIMARY_ELEMENT
+        convex = float(self.radius) != 0.0
         if self.primary_rays == "emitter":
             ems = [e for e in (scene.emitters() if scene is not None else []) if getattr(e, "is_transducer", False)]
             if not ems:
@@ -888,8 +894,16 @@ class UltraIntegrator(SamplingIntegrator):
             if ems[0].number_of_elements != self.n_elements:
                 raise ValueError(f"the emitter has {ems[0].number_of_elements} elements, the integrator {self.n_elements}: "
                                  "the acquisition grid stratifies the emitter's elements, they must be the same array")
+            if not convex and ems[0].radius != 0.0:
+                raise ValueError("the emitter is a curved array (radius != 0) and the integrator a linear one: transmitting from an arc "
+                                 "and receiving on a line was never defined -- give the integrator the emitter's radius and opening_angle")
+            if convex and (float(ems[0].radius) != float(self.radius) or float(ems[0].opening_angle) != float(self.opening_angle)):
+                raise ValueError("emitter and integrator describe different arrays (radius / opening_angle)")
             p.primary = _capi.US_PRIMARY_EMITTER
             p.emitter = ems[0]._desc()
+        if convex:
+            from .beamform import convex_params
+            convex_params(self.n_elements, self.radius, self.opening_angle, params=p)  # raises on a radius / opening angle the library refuses
         return p
 
     def _acquire(self, scene, quirks, paths_per_ray=None, path_offset=0, norm_paths=None, seed=None, out_dev=None, pulse=None,
@@ -939,6 +953,8 @@ class UltraIntegrator(SamplingIntegrator):
 
     def traverse(self, callback):  # CustomIntegrator.py:408-409
         callback.put_parameter("pitch", self.pitch, ParamFlags.Differentiable)
+        callback.put_parameter("radius", self.radius, ParamFlags.Differentiable)
+        callback.put_parameter("opening_angle", self.opening_angle, ParamFlags.Differentiable)
 
     def parameters_changed(self, keys=None):
         self.elem_x = as_dr(self.pitch * (np.arange(self.n_elements, dtype=np.float32) - (self.n_elements - 1) / 2))
