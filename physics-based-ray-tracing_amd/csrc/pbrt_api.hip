@@ -705,24 +705,12 @@ static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool fi
 // has its table mode compiled in too: -1 on later bounces, 0 for emitter rays (never any tables).  Everything else reads both at
 // run time.  nullptr: BVH scenes run k_trace / k_us_shade (us_wf_pass); their fused bounce (PBRT_US_FUSED_BVH=1, no emitter rays)
 // exists in the diagnostic build only.
-// convex (PBRT_US_ARRAY_CONVEX, D18): the instances of the curved array -- the generic ones only (quirks and tables read at run time).
+// convex (PBRT_US_ARRAY_CONVEX, D18): the curved array has the generic instances only (quirks and tables read at run time).
 static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint32_t q, int tab, bool convex = false) {
     if (!first) tab = -1;
     if (convex) {
-        switch (s->accel_kernel) {
-            case ACCEL_K_BRUTE:
-                return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce_convex<F(), ACCEL_K_BRUTE, E()>; }, first, emit);
-            case ACCEL_K_BRUTE_BIG:
-                return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce_convex<F(), ACCEL_K_BRUTE_BIG, E()>; }, first, emit);
-            default:
-#ifdef PBRT_DIAG
-                if (!emit)
-                    return with_flags([](auto F, auto L) -> UsKern {
-                        return &k_us_bounce_convex<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL>; },
-                                      first, s->accel_kernel == ACCEL_K_BVH_LDS);
-#endif
-                return nullptr;
-        }
+        q = US_Q_RUNTIME;
+        tab = -1;
     }
     switch (s->accel_kernel) {
         case ACCEL_K_BRUTE:
@@ -730,14 +718,17 @@ static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint3
                 return with_flags([](auto F, auto E, auto C, auto T) -> UsKern {
                     return &k_us_bounce<F(), ACCEL_K_BRUTE, E(), C() ? PBRT_USQ_REFERENCE : (PBRT_USQ_REFERENCE | PBRT_USQ_NO_CARRIER),
                                         !F() ? -1 : (!E() && T()) ? 1 : 0>; }, first, emit, q == PBRT_USQ_REFERENCE, tab == 1);
-            return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce<F(), ACCEL_K_BRUTE, E()>; }, first, emit);
+            return with_flags([](auto F, auto E, auto X) -> UsKern {
+                return &k_us_bounce<F(), ACCEL_K_BRUTE, E(), US_Q_RUNTIME, -1, X()>; }, first, emit, convex);
         case ACCEL_K_BRUTE_BIG:
-            return with_flags([](auto F, auto E) -> UsKern { return &k_us_bounce<F(), ACCEL_K_BRUTE_BIG, E()>; }, first, emit);
+            return with_flags([](auto F, auto E, auto X) -> UsKern {
+                return &k_us_bounce<F(), ACCEL_K_BRUTE_BIG, E(), US_Q_RUNTIME, -1, X()>; }, first, emit, convex);
         default:
 #ifdef PBRT_DIAG
             if (!emit)
-                return with_flags([](auto F, auto L) -> UsKern { return &k_us_bounce<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL>; },
-                                  first, s->accel_kernel == ACCEL_K_BVH_LDS);
+                return with_flags([](auto F, auto L, auto X) -> UsKern {
+                    return &k_us_bounce<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL, false, US_Q_RUNTIME, -1, X()>; },
+                                  first, s->accel_kernel == ACCEL_K_BVH_LDS, convex);
 #endif
             return nullptr;
     }
@@ -950,10 +941,10 @@ static uint32_t wf_trace_grid(uint32_t nr, uint32_t mult, uint32_t cus) {
 }
 
 // k_shade with or without the cylinder code (the instance without it is the one every other scene runs), or with the rough /
-// Fresnel conductor code on top of it; the small shading tables in LDS when they fit (kernels_wavefront.h wf_tables_lds)
+// Fresnel conductor code on top of it (GLOSSY, always with CYL); the small shading tables in LDS when they fit (wf_tables_lds)
 static WfKern shade_kernel(const pbrt_scene *s, bool first) {
     const bool tabs = s->ds.n_mats <= TAB_MAX && s->ds.n_emitters <= TAB_MAX && s->ds.n_light_prims <= TAB_MAX;
-    if (s->glossy) return with_flags([](auto F, auto T) -> WfKern { return &k_shade_glossy<F(), T(), true>; }, first, tabs);
+    if (s->glossy) return with_flags([](auto F, auto T) -> WfKern { return &k_shade<F(), T(), true, true>; }, first, tabs);
     return with_flags([](auto F, auto T, auto C) -> WfKern { return &k_shade<F(), T(), C()>; }, first, tabs, s->cylinders);
 }
 

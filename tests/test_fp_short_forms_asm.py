@@ -20,9 +20,13 @@ IEEE_DIVISIONS_LEFT = 16  # each IEEE division is two v_div_scale_f32
 CEILINGS = {
     "_Z7k_traceILb1ELi2ELb0EEv6WfArgs": (51, 2),  # k_trace<true, 2, false>
     "_Z7k_traceILb0ELi2ELb0EEv6WfArgs": (4, 0),  # k_trace<false, 2, false>
-    "_Z7k_shadeILb1ELb1ELb1EEv6WfArgs": (23, 0),  # k_shade<true, true, true>
-    "_Z7k_shadeILb0ELb0ELb0EEv6WfArgs": (26, 0),  # k_shade<false, false, false>
-    "_Z11k_us_bounceILb1ELi0ELb0ELj319ELi0EEv6UsArgs": (13, 0),  # k_us_bounce<true, 0, false, 319, 0>
+    "_Z7k_shadeILb1ELb1ELb1ELb0EEv6WfArgs": (23, 0),  # k_shade<true, true, true, false>
+    "_Z7k_shadeILb0ELb0ELb0ELb0EEv6WfArgs": (26, 0),  # k_shade<false, false, false, false>
+    "_Z11k_us_bounceILb1ELi0ELb0ELj319ELi0ELb0EEv6UsArgs": (13, 0),  # k_us_bounce<true, 0, false, 319, 0, false>
+    # the glossy and the convex instance: what they spilled while they were k_shade_glossy<true, true, true> (23 / 0) and
+    # k_us_bounce_convex<true, 0, false> (50 / 3) -- the same code under the one kernel name, so no margin
+    "_Z7k_shadeILb1ELb1ELb1ELb1EEv6WfArgs": (23, 0),  # k_shade<true, true, true, true>
+    "_Z11k_us_bounceILb1ELi0ELb0ELj4294967295ELin1ELb1EEv6UsArgs": (50, 3),  # k_us_bounce<true, 0, false, 0xffffffff, -1, true>
 }
 
 
