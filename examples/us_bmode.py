@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """The reference's ultrasound driver flow on this library: scene dict -> acquisition -> delay-and-sum -> envelope ->
 log compression -> finite-difference roughness loop (what USMain.py does at :26-90, :93-224, :257-289), without the
-plotting.  Writes the B-mode image and the channel buffer as .npy.   python examples/us_bmode.py [--convex] [out_dir]
+plotting.  Writes the B-mode image and the channel buffer as .npy.
+    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [out_dir]
 --convex: the same flow under a curved (abdominal) array -- 64 elements on a 40 mm arc of 40 degrees (DESIGN D18); the sensor
 transform puts the apex where the linear array sits, and the scan is given in the sensor's frame, whose origin is the centre of
-curvature."""
+curvature.
+--beamformer: delay-and-sum (default), p-DAS (--p, default 2) or F-DMAS (DESIGN D19).  The non-linear beamformers band-pass their
+image along z, around the carrier (p-DAS) or twice the carrier (F-DMAS): the reference's lambda / 4 grid puts the axial Nyquist
+frequency AT the carrier, so the example picks lambda / 8 for p-DAS and lambda / 16 for F-DMAS itself and says so."""
+import argparse
 import os
 import sys
 import time
@@ -16,9 +21,13 @@ import pbrt_amd as mi                       # was: import mitsuba as mi
 import pbrt_amd.drjit_compat as dr          # was: import drjit as dr
 
 mi.set_variant("llvm_ad_mono")              # accepted; the one backend is HIP on gfx950
-args = [a for a in sys.argv[1:] if a != "--convex"]
-convex = "--convex" in sys.argv[1:]
-out_dir = args[0] if args else "."
+ap = argparse.ArgumentParser()
+ap.add_argument("--convex", action="store_true")
+ap.add_argument("--beamformer", choices=("das", "pdas", "fdmas"), default="das")
+ap.add_argument("--p", type=float, default=2.0)
+ap.add_argument("out_dir", nargs="?", default=".")
+args = ap.parse_args()
+convex, out_dir = args.convex, args.out_dir
 T = mi.ScalarTransform4f
 RADIUS = 0.04 if convex else 0.0            # centre of curvature RADIUS behind the apex; the scan's z is measured from it
 Z_RANGE = (RADIUS + 0.02, RADIUS + 0.08)
@@ -40,8 +49,20 @@ scene = mi.load_dict({
                   "bsdf": {"type": "ultrasound_bsdf", "impedance": 7.8, "roughness": 0.7}},
 })
 
+integ = scene.integrator()
+lam = integ.sound_speed / integ.frequency
+beamformer = {"das": lambda: mi.DelayAndSum(), "pdas": lambda: mi.PDelayAndSum(p=args.p),
+              "fdmas": lambda: mi.FilteredDelayMultiplyAndSum()}[args.beamformer]()
+step = {"das": lam / 4, "pdas": lam / 8, "fdmas": lam / 16}[args.beamformer]
+RENDER = dict(x_range=(-0.02, 0.02), z_range=Z_RANGE, step=step, beamformer=beamformer)
+if args.beamformer != "das":
+    f_lo, f_hi = beamformer.band(mi.build_probe("linear", 64, 1.2e-4, integ.frequency, 70))
+    print(f"{beamformer}: band {f_lo / 1e6:.2f} - {f_hi / 1e6:.2f} MHz needs an axial rate c / (2 step) above {2 * f_hi / 1e6:.2f} MHz; "
+          f"scan step lambda / {lam / step:.0f} = {step * 1e6:.1f} um gives {integ.sound_speed / (2 * step) / 1e6:.2f} MHz "
+          f"(the reference's lambda / 4: {integ.sound_speed / (2 * lam / 4) / 1e6:.2f} MHz)")
+
 t = time.perf_counter()
-display, bmode, (x_scan, z_scan) = mi.us_render(scene, x_range=(-0.02, 0.02), z_range=Z_RANGE)
+display, bmode, (x_scan, z_scan) = mi.us_render(scene, **RENDER)
 print(f"B-mode {display.shape[0]} x {display.shape[1]} pixels in {(time.perf_counter() - t) * 1e3:.1f} ms; "
       f"channel_buf sum {float(np.sum(scene.integrator().channel_buf)):.4g}, max {float(np.max(scene.integrator().channel_buf)):.4g}")
 np.save(os.path.join(out_dir, "bmode_display.npy"), display)
@@ -56,7 +77,7 @@ target = bmode.astype(np.float64)
 def forward(rough):
     params[key] = rough
     params.update()
-    return mi.us_render(scene, x_range=(-0.02, 0.02), z_range=Z_RANGE)[1].astype(np.float64)
+    return mi.us_render(scene, **RENDER)[1].astype(np.float64)
 
 
 rough, eps = 0.5, 1e-2

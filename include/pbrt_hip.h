@@ -584,6 +584,42 @@ int pbrt_log_compress_dev(pbrt_ctx *ctx, uint32_t n, const void *d_env, float dy
 int pbrt_us_apply_pulse_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,
                             const void *d_in, void *d_out);
 
+/* ---- p-DAS and F-DMAS beamformers, and the axial band-pass they need ------------------------------------------------
+ * `ultraspy` ships PDelayAndSum and FilteredDelayMultiplyAndSum beside DelayAndSum; it is absent here (as for pbrt_das_beamform above),
+ * so the arithmetic is this build's own definition, taken from the papers (Polichetti et al. 2018 for p-DAS, Matrone et al. 2015 for
+ * F-DMAS).  s_e, the delayed sample of transmission a and element e at a pixel, is exactly the term pbrt_das_beamform adds (first
+ * arrival, f64 position, range rules, f-number aperture of the line or of the element table, nearest / linear interpolation); U(a)
+ * the elements the pixel uses for transmission a.  Per transmission
+ *   PBRT_BF_PDAS:   r_e = sgn(s_e) |s_e|^(1/p),  q_a = sum_{e in U(a)} r_e,  y_a = sgn(q_a) |q_a|^p
+ *                   (p = 2: sqrtf and a product; every other p: powf with the exponents 1.0f / p and p)
+ *   PBRT_BF_FDMAS:  r_e = sgn(s_e) sqrt|s_e|,    y_a = sum_{i < j} r_i r_j, computed as ((sum_e r_e)^2 - sum_e |s_e|) / 2
+ * and out = sum_a y_a, divided by n_angles when compound_mean is set; a pixel that uses no element is exactly 0.  All in f32: wave
+ * w = e % 4 sums its share of sum r_e (and of sum |s_e|) per transmission, the four shares are added in wave order BEFORE the
+ * non-linearity, the y_a in order of a.  Non-finite samples get no special treatment.  The F-DMAS output still holds its baseband
+ * term: its band-pass around twice the carrier (and p-DAS's around the carrier) is pbrt_axial_fir, a separate step. */
+#define PBRT_BF_PDAS 1u
+#define PBRT_BF_FDMAS 2u
+typedef struct pbrt_bf_params {
+    pbrt_das_params das;
+    uint32_t method; /* PBRT_BF_PDAS / PBRT_BF_FDMAS; anything else (0 included: plain DAS has its own calls) is PBRT_E_INVALID */
+    float p;         /* PBRT_BF_PDAS: finite, 1 <= p <= 8, else PBRT_E_INVALID; not read for PBRT_BF_FDMAS */
+    uint32_t probe;  /* 0: element positions [n_elements]; 1: the element table [n_elements][4] of pbrt_us_array_elements */
+} pbrt_bf_params;
+/* host pointers, arguments as pbrt_das_beamform / pbrt_das_beamform_probe; everything those refuse is refused here */
+int pbrt_bf_beamform(pbrt_ctx *ctx, const pbrt_bf_params *p, const float *data, const float *tx_delays, const float *elem,
+                     const float *x, const float *z, float *out);
+/* device pointers, queued on the context's stream and recordable like pbrt_das_beamform_dev / pbrt_das_beamform_table_dev; the
+ * table is pbrt_das_first_arrival_dev's (or its _probe twin's), and the table form is bit-equal to the direct form */
+int pbrt_bf_beamform_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
+                         const void *d_x, const void *d_z, void *d_out);
+int pbrt_bf_beamform_table_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_table, const void *d_elem,
+                               const void *d_x, const void *d_z, void *d_out);
+/* Axial FIR of an image [nx][nz]: out[ix][n] = sum_{k = -K .. K} taps[K + k] in[ix][n - k], samples outside the column zero, f32
+ * multiply-adds in order of increasing k.  taps [2 K + 1] are the caller's (the library does not design them); K <= 1024 and
+ * nz > 0, else PBRT_E_INVALID; in and out distinct.  The _dev form takes device pointers (taps included), is queued and recordable. */
+int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const float *taps, const float *in, float *out);
+int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *d_taps, const void *d_in, void *d_out);
+
 /* waits for everything queued on the context's stream */
 int pbrt_ctx_synchronize(pbrt_ctx *ctx);
 /* Device buffers for a caller without a GPU library of its own (the reference's driver is NumPy: USMain.py:103-121).
@@ -610,7 +646,8 @@ int pbrt_get_image_stats(pbrt_ctx *ctx, pbrt_image_stats *out);
  * At the reference's own size (320 rays x 1 path, USMain.py:36) the chain above is eight small kernels, three fills and a copy:
  * the host spends as long queueing them as the device spends running them, 100 times per script.  Between
  * pbrt_ctx_record_begin and pbrt_ctx_record_end the queueing entry points (pbrt_us_acquire_queue_dev, pbrt_us_apply_pulse_dev,
- * pbrt_das_beamform_dev, pbrt_das_beamform_table_dev, pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
+ * pbrt_das_beamform_dev, pbrt_das_beamform_table_dev, pbrt_bf_beamform_dev, pbrt_bf_beamform_table_dev, pbrt_axial_fir_dev,
+ * pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
  * stream instead of run; pbrt_graph_launch replays the recording in one submission and returns without waiting, exactly as if
  * the recorded calls had just been made: same kernels, same arguments, same results bit for bit, the acquisition's statistics
  * arrive with the next call that waits (kernel_ms / bounce_ms are 0: a replay carries no event pairs).

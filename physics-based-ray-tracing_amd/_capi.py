@@ -138,6 +138,13 @@ class DasParams(C.Structure):
 DAS_NEAREST, DAS_LINEAR = 0, 1
 
 
+class BfParams(C.Structure):
+    _fields_ = [("das", DasParams), ("method", C.c_uint32), ("p", C.c_float), ("probe", C.c_uint32)]
+
+
+BF_PDAS, BF_FDMAS = 1, 2
+
+
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("kernel_ms", C.c_double), ("bounce_ms", C.c_double), ("bounce_launches", C.c_uint32),
@@ -204,6 +211,12 @@ SIGNATURES = {
     "pbrt_envelope_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "pbrt_log_compress_dev": (C.c_int, [_P, C.c_uint32, _P, C.c_float, _P]),
     "pbrt_us_apply_pulse_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),
+    # p-DAS / F-DMAS and the axial FIR (DESIGN D19)
+    "pbrt_bf_beamform": (C.c_int, [_P, C.POINTER(BfParams), _F, _F, _F, _F, _F, _F]),
+    "pbrt_bf_beamform_dev": (C.c_int, [_P, C.POINTER(BfParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_bf_beamform_table_dev": (C.c_int, [_P, C.POINTER(BfParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_axial_fir": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _F, _F, _F]),
+    "pbrt_axial_fir_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "pbrt_ctx_synchronize": (C.c_int, [_P]),
     "pbrt_dev_alloc": (C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     "pbrt_dev_free": (C.c_int, [_P, _P]),

@@ -9,6 +9,9 @@ restated in oracle/beamform.py; parity unpinned).  The classes keep the call sha
     d_output = beamformer.beamform(d_data, GridScan(x_scan, z_scan))                                    # :204
     envelope = beamformer.compute_envelope(d_output, scan)                                              # :205
 
+PDelayAndSum and FilteredDelayMultiplyAndSum (ultraspy's non-linear beamformers, which the reference does not call) have the same shape;
+their arithmetic, from the papers, and the axial band-pass they need are DESIGN.md D19.
+
 All work runs on the GPU through libpbrt_hip.so (no CPU fallback; `on_gpu` is accepted for compatibility)."""
 from __future__ import annotations
 
@@ -123,6 +126,126 @@ def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_numbe
     cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
                                    _capi.addr(gz), _capi.addr(res)), name)
     return res
+
+
+def _bf_params(das, method, p, probe) -> "_capi.BfParams":
+    bp = _capi.BfParams()
+    bp.das = das
+    bp.method = {"pdas": _capi.BF_PDAS, "fdmas": _capi.BF_FDMAS}[method]
+    bp.p, bp.probe = float(p), int(bool(probe))
+    return bp
+
+
+def nonlinear_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, method="fdmas", p=2.0, t0=0.0, f_number=1.0,
+                       interpolation="linear", compound="sum", out=None, table=None):
+    """p-DAS (method="pdas", 1 <= p <= 8) or F-DMAS (method="fdmas") of the channel buffer, BEFORE the axial band-pass both need
+    (axial_fir; DESIGN D19, include/pbrt_hip.h).  Arguments and the host / DeviceBuffer rule as das_beamform: host arrays in ->
+    pbrt_bf_beamform and a host array out; `data` a DeviceBuffer -> pbrt_bf_beamform_dev (or _table_dev with `table` from
+    das_first_arrival), queued, a DeviceBuffer out.  elem_x [n_elements] or the element table [n_elements, 4]."""
+    if method not in ("pdas", "fdmas"):
+        raise ValueError(f"method must be 'pdas' or 'fdmas', got {method!r}")
+    cx = data.ctx if _is_dev(data) else _capi.default_context()
+    if _is_dev(data):
+        if len(data.shape) != 3:
+            raise ValueError("data must be [n_angles, n_elements, time_samples]")
+        A, E, T = data.shape
+        elem_x, probe, eshape = _elem_arg(elem_x, E)
+        d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem_x, eshape)
+        d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
+        d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
+        nx, nz = d_x.shape[0], d_z.shape[0]
+        bp = _bf_params(_das_params(A, E, T, nx, nz, fs, sound_speed, t0, f_number, interpolation, compound), method, p, probe)
+        d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz))
+        if d_out.nbytes != nx * nz * 4:
+            raise ValueError("out must hold nx * nz float32")
+        if table is not None:
+            if table.nbytes != A * nx * nz * 8:
+                raise ValueError("table must be the [n_angles, nx, nz] float64 buffer of das_first_arrival for this scan")
+            cx.check(cx.lib.pbrt_bf_beamform_table_dev(cx.handle, C.byref(bp), data.ptr, table.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr),
+                     "pbrt_bf_beamform_table_dev")
+        else:
+            cx.check(cx.lib.pbrt_bf_beamform_dev(cx.handle, C.byref(bp), data.ptr, d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr),
+                     "pbrt_bf_beamform_dev")
+        d_out._keep = (d_tx, d_ex, d_x, d_z, table)
+        return d_out
+    data = _capi.f32(np.asarray(data))
+    if data.ndim != 3:
+        raise ValueError("data must be [n_angles, n_elements, time_samples]")
+    A, E, T = data.shape
+    tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
+    elem_x, probe, eshape = _elem_arg(elem_x, E)
+    ex = _capi.f32(np.asarray(elem_x).reshape(eshape))
+    gx, gz = _capi.f32(np.asarray(x).ravel()), _capi.f32(np.asarray(z).ravel())
+    bp = _bf_params(_das_params(A, E, T, len(gx), len(gz), fs, sound_speed, t0, f_number, interpolation, compound), method, p, probe)
+    res = np.empty((len(gx), len(gz)), dtype=np.float32)
+    cx.check(cx.lib.pbrt_bf_beamform(cx.handle, C.byref(bp), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
+                                     _capi.addr(gz), _capi.addr(res)), "pbrt_bf_beamform")
+    return res
+
+
+def axial_fir(rf, taps, out=None):
+    """out[ix, n] = sum_{k = -K .. K} taps[K + k] rf[ix, n - k] along the last (axial) axis of a [nx, nz] image, zero outside the
+    column; taps [2 K + 1], K <= 1024 (pbrt_axial_fir; a DeviceBuffer in gives a DeviceBuffer out, queued -- the taps then a
+    DeviceBuffer or a host array that is uploaded)."""
+    n_taps = taps.shape[0] if _is_dev(taps) else np.asarray(taps).size
+    if n_taps % 2 != 1:
+        raise ValueError("taps must be [2 K + 1]")
+    K = n_taps // 2
+    cx = rf.ctx if _is_dev(rf) else _capi.default_context()
+    if _is_dev(rf):
+        nx, nz = (rf.shape if len(rf.shape) == 2 else (1, rf.shape[0]))
+        d_taps = _to_dev(cx, taps, (n_taps,))
+        d_out = out if out is not None else _capi.DeviceBuffer(cx, rf.shape)
+        cx.check(cx.lib.pbrt_axial_fir_dev(cx.handle, nx, nz, K, d_taps.ptr, rf.ptr, d_out.ptr), "pbrt_axial_fir_dev")
+        d_out._keep = (rf, d_taps)
+        return d_out
+    rf = _capi.f32(np.atleast_2d(np.asarray(rf)))
+    h = _capi.f32(np.asarray(taps).ravel())
+    nx, nz = rf.shape
+    res = np.empty_like(rf)
+    cx.check(cx.lib.pbrt_axial_fir(cx.handle, nx, nz, K, _capi.addr(h), _capi.addr(rf), _capi.addr(res)), "pbrt_axial_fir")
+    return res
+
+
+FIR_MAX_K = 1024
+
+
+def axial_rate(z_axis, sound_speed) -> float:
+    """axial sampling rate of an image, fs_ax = c / (2 dz): a depth step dz is 2 dz / c of round-trip time.  ValueError for a z axis
+    that is not uniform to 1e-6 of its step."""
+    z = np.asarray(z_axis, dtype=np.float64).ravel()
+    if z.size < 2:
+        raise ValueError("the z axis needs two samples at least to have a sampling rate")
+    d = np.diff(z)
+    dz = (z[-1] - z[0]) / (z.size - 1)
+    if not (dz > 0.0 and np.all(np.abs(d - dz) <= 1e-6 * dz)):
+        raise ValueError("the axial band-pass needs a uniform, increasing z axis (to 1e-6 of its step)")
+    return float(sound_speed) / (2.0 * dz)
+
+
+def bandpass_taps(f_lo, f_hi, fs_ax, K=None) -> np.ndarray:
+    """Hamming-windowed sinc band-pass [f_lo, f_hi] at the sampling rate fs_ax (axial_rate), taps [2 K + 1] for axial_fir:
+        h[k] = (0.54 + 0.46 cos(pi k / K)) (2 f_hi / fs_ax sinc(2 f_hi k / fs_ax) - 2 f_lo / fs_ax sinc(2 f_lo k / fs_ax)),
+    in float64, rounded once to float32.  Default K = min(1024, ceil(4 fs_ax / (f_hi - f_lo))).  ValueError for f_lo >= f_hi,
+    f_lo < 0 and f_hi >= fs_ax / 2."""
+    f_lo, f_hi, fs_ax = float(f_lo), float(f_hi), float(fs_ax)
+    if not (fs_ax > 0.0 and np.isfinite(fs_ax)):
+        raise ValueError(f"band-pass: the sampling rate must be finite and > 0, got {fs_ax}")
+    if not f_lo >= 0.0:
+        raise ValueError(f"band-pass: f_lo must be >= 0, got {f_lo}")
+    if not f_lo < f_hi:
+        raise ValueError(f"band-pass: f_lo ({f_lo}) must lie below f_hi ({f_hi})")
+    if not f_hi < fs_ax / 2.0:
+        raise ValueError(f"band-pass: f_hi ({f_hi:.6g} Hz) must lie below the Nyquist frequency fs_ax / 2 = {fs_ax / 2.0:.6g} Hz")
+    if K is None:
+        K = min(FIR_MAX_K, int(np.ceil(4.0 * fs_ax / (f_hi - f_lo))))
+    K = int(K)
+    if not 1 <= K <= FIR_MAX_K:
+        raise ValueError(f"band-pass: K must lie in [1, {FIR_MAX_K}], got {K}")
+    k = np.arange(-K, K + 1, dtype=np.float64)
+    hi, lo = 2.0 * f_hi / fs_ax, 2.0 * f_lo / fs_ax
+    h = (0.54 + 0.46 * np.cos(np.pi * k / K)) * (hi * np.sinc(hi * k) - lo * np.sinc(lo * k))
+    return h.astype(np.float32)
 
 
 def envelope(rf, out=None):
@@ -301,11 +424,109 @@ class DelayAndSum:
         return f"DelayAndSum(MI355X, {self.setups})"
 
 
+class _NonlinearBeamformer(DelayAndSum):
+    """p-DAS / F-DMAS in the shape of DelayAndSum (DESIGN D19): beamform() runs the non-linear kernel and, unless the setup `band`
+    is None, the axial band-pass.  Setup keys: DelayAndSum's, `band` ("default": centre (1 -+ probe.bandwidth / 200) around
+    `_centre` x probe.central_freq; (f_lo, f_hi) in Hz; None: no filter) and `taps_half_length` (None: bandpass_taps' default)."""
+    _method = None
+    _centre = 1.0   # band centre in units of the probe's central frequency
+
+    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", band="default", taps_half_length=None):
+        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound)
+        self.setups.update(band=band, taps_half_length=taps_half_length)
+        self.scratch_dev = None           # a buffer for the unfiltered image (set by us_render)
+        self._taps_cache = (None, None)   # (the taps' bytes, the taps as a DeviceBuffer)
+
+    def band(self, probe=None):
+        """(f_lo, f_hi) in Hz, or None"""
+        b = self.setups["band"]
+        if b is None:
+            return None
+        if isinstance(b, str):
+            if b != "default":
+                raise ValueError(f"band must be None, 'default' or (f_lo, f_hi), got {b!r}")
+            probe = probe or self.probe
+            if probe is None:
+                raise RuntimeError("the default band follows the probe: automatic_setup(acquisition_info, probe) has not been called")
+            centre = self._centre * probe.central_freq
+            return centre * (1.0 - probe.bandwidth / 200.0), centre * (1.0 + probe.bandwidth / 200.0)
+        f_lo, f_hi = b
+        return float(f_lo), float(f_hi)
+
+    def filter_taps(self, scan, sound_speed, probe=None):
+        """the band-pass taps [2 K + 1] (float32) for a scan, None with band=None.  ValueError when the band does not fit under the
+        Nyquist frequency of the scan's depth step; the message names the step that would."""
+        band = self.band(probe)
+        if band is None:
+            return None
+        fs_ax = axial_rate(scan.z_axis, sound_speed)
+        f_lo, f_hi = band
+        if f_hi >= fs_ax / 2.0:
+            c, dz = float(sound_speed), float(sound_speed) / (2.0 * fs_ax)
+            raise ValueError(
+                f"{type(self).__name__}: the band [{f_lo:.4g}, {f_hi:.4g}] Hz does not fit under the axial Nyquist frequency "
+                f"{fs_ax / 2.0:.4g} Hz of a depth step of {dz:.4g} m (fs_ax = c / (2 dz)); a step below c / (4 f_hi) = "
+                f"{c / (4.0 * f_hi):.4g} m would fit -- pass step= to us_render (DESIGN D19)")
+        return bandpass_taps(f_lo, f_hi, fs_ax, self.setups["taps_half_length"])
+
+    def _raw(self, data, ai, ex, gx, gz, out, table):
+        return nonlinear_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], method=self._method,
+                                  p=self.setups.get("p", 2.0), t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
+                                  interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out, table=table)
+
+    def beamform(self, d_data, scan, out=None, table=None):
+        """host array in -> host array out; a DeviceBuffer in -> a DeviceBuffer out, queued (kernel, then the band-pass)"""
+        ai = self.acquisition_info
+        if ai is None or self.probe is None:
+            raise RuntimeError(f"{type(self).__name__}.automatic_setup(acquisition_info, probe) has not been called")
+        data = d_data
+        if not _is_dev(data):
+            data = np.asarray(d_data)
+            if data.ndim == 4:
+                data = data[0]
+        dev = _is_dev(data)
+        ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
+        gx = scan.d_x if dev and getattr(scan, "d_x", None) is not None else scan.x_axis
+        gz = scan.d_z if dev and getattr(scan, "d_z", None) is not None else scan.z_axis
+        taps = self.filter_taps(scan, ai["sound_speed"])
+        if taps is None:
+            return self._raw(data, ai, ex, gx, gz, out, table if dev else None)
+        if not dev:
+            return axial_fir(self._raw(data, ai, ex, gx, gz, None, None), taps)
+        # the taps in HBM: uploaded once per change (us_render puts its plan's copy here, with the buffer of the unfiltered image)
+        key = taps.tobytes()
+        if self._taps_cache[0] != key or self._taps_cache[1].ctx is not data.ctx:
+            self._taps_cache = (key, _capi.DeviceBuffer.from_host(data.ctx, taps))
+        d_taps = self._taps_cache[1]
+        raw = self._raw(data, ai, ex, gx, gz, self.scratch_dev if self.scratch_dev is not None and self.scratch_dev.shape == scan.shape else None,
+                        table)
+        return axial_fir(raw, d_taps, out=out)
+
+    def __str__(self):
+        return f"{type(self).__name__}(MI355X, {self.setups})"
+
+
+class PDelayAndSum(_NonlinearBeamformer):
+    """p-DAS (Polichetti et al. 2018): per transmission the signed p-th roots of the delayed samples are summed and the sum is raised
+    back to the p-th power, sign kept; band-pass around the carrier.  1 <= p <= 8; p = 1 is DelayAndSum."""
+    _method, _centre = "pdas", 1.0
+
+    def __init__(self, p=2.0, **kw):
+        super().__init__(**kw)
+        self.setups["p"] = p
+
+
+class FilteredDelayMultiplyAndSum(_NonlinearBeamformer):
+    """F-DMAS (Matrone et al. 2015): per transmission the sum over element pairs of the signed square roots' products, then the
+    band-pass around TWICE the carrier, where the products of the pairs put the signal."""
+    _method, _centre = "fdmas", 2.0
+
+
 class _RenderPlan:
     """Device buffers of one us_render configuration (acquisition shape, scan grid): allocated once, reused by every call of the
     reference's loop (USMain.py:262-289 calls us_render 50 times on one scene)."""
 
-    def __init__(self, cx, A, E, T, elem_x, x_scan, z_scan, gaussian):
+    def __init__(self, cx, A, E, T, elem_x, x_scan, z_scan, gaussian, taps=None):
         self.key = None
         self.cx = cx
         self.d_channel = _capi.DeviceBuffer(cx, (A, E, T))
@@ -321,6 +542,9 @@ class _RenderPlan:
         self.d_env = _capi.DeviceBuffer(cx, (nx, nz))
         self.d_img = _capi.DeviceBuffer(cx, (nx, nz))
         self.d_table = _capi.DeviceBuffer(cx, (A, nx, nz), np.float64)   # first-arrival times of this scan (das_first_arrival)
+        # p-DAS / F-DMAS with a band: the band-pass taps, and the image before the filter
+        self.d_taps = _capi.DeviceBuffer.from_host(cx, taps) if taps is not None else None
+        self.d_nl = _capi.DeviceBuffer(cx, (nx, nz)) if taps is not None else None
         # the queued chain of one key as a recording (pbrt_graph), made at the second call in a row with that key
         self.graph = self.graph_key = self.warm_key = self.no_graph_key = None
 
@@ -359,6 +583,9 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     else:
         probe = build_probe("linear", E, integ.pitch, integ.frequency, 70)                             # :130-136
     bf = beamformer or DelayAndSum(on_gpu=True)
+    # (p-DAS / F-DMAS: the band-pass taps of this scan -- refused here, before anything is acquired, when the band does not fit
+    # under the Nyquist frequency of the depth step: the reference's lambda / 4 grid puts that AT the carrier, DESIGN D19)
+    taps = bf.filter_taps(scan, integ.sound_speed, probe) if isinstance(bf, _NonlinearBeamformer) else None
     seq = {"emitted": np.tile(np.arange(E), (A, 1)), "received": np.tile(np.arange(E), (A, 1))}
 
     def info(delays):
@@ -380,15 +607,19 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     cx = scene.device().ctx
     gaussian = integ.pulse_model == "gaussian"
     key = (A, E, T, float(integ.pitch), x_scan.tobytes(), z_scan.tobytes(), gaussian, id(cx), probe.geometry_type, probe.radius,
-           probe.opening_angle)
+           probe.opening_angle, None if taps is None else taps.tobytes())
     plan = getattr(integ, "_render_plan", None)
     if plan is None or plan.key != key:
-        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian)
+        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian, taps)
         plan.key = key
         integ._render_plan = plan
     rf = plan.d_rf if gaussian else plan.d_channel
     scan.d_x, scan.d_z = plan.d_x, plan.d_z
     bf.probe_dev = plan.d_ex
+    if isinstance(bf, _NonlinearBeamformer):
+        bf.scratch_dev = plan.d_nl
+        if taps is not None:
+            bf._taps_cache = (taps.tobytes(), plan.d_taps)
 
     def queue_acquisition():
         integ._acquire(scene, integ.quirks, paths_per_ray=paths_per_ray, seed=seed, out_dev=plan.d_channel.ptr, pulse=False,
@@ -412,7 +643,7 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
         gkey = (bytes(integ.us_params(scene, integ.quirks)), getattr(h, "value", h),
                 int(integ.seed if seed is None else seed) & 0xFFFFFFFF,
                 int(paths_per_ray if paths_per_ray is not None else integ.paths_per_ray), float(dynamic_range),
-                tuple(sorted(bf.setups.items())), float(integ.pulse_sigma) if gaussian else None)
+                type(bf).__name__, tuple(sorted(bf.setups.items())), float(integ.pulse_sigma) if gaussian else None)
     replayed = False
     if gkey is not None and plan.graph is not None and plan.graph_key == gkey:
         try:

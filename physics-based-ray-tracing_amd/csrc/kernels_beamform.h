@@ -293,6 +293,222 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
     if (valid) out[(size_t)ix * p.nz + iz] = p.compound_mean ? acc / (float)A : acc;
 }
 
+// ---- p-DAS and F-DMAS (DESIGN D19) ------------------------------------------------------------------------------------------
+// The non-linear members of the beamformer family (`ultraspy` ships them beside DelayAndSum; absent here, so the arithmetic is this
+// build's own definition, include/pbrt_hip.h, taken from Polichetti et al. 2018 and Matrone et al. 2015).  The delayed sample s_e of
+// transmission a and element e at a pixel is exactly the term k_das_beamform adds; per transmission
+//   PBRT_BF_PDAS:   q_a = sum_e sgn(s_e) |s_e|^(1/p),   y_a = sgn(q_a) |q_a|^p          (p = 2: sqrtf and a product, else powf)
+//   PBRT_BF_FDMAS:  q_a = sum_e sgn(s_e) sqrt|s_e|,     y_a = ((q_a)^2 - sum_e |s_e|) / 2  = sum_{i<j} of the signed roots' products
+// and out = sum_a y_a (/ n_angles).  Wave w = e % DAS_SPLIT keeps its share of q_a (and of sum |s_e|) for the DAS_ANG angles of a trip
+// in registers, the shares meet in LDS rows [DAS_SPLIT][angles][64] and are added in wave order BEFORE the non-linearity; wave 0 adds
+// the y_a in angle order.  Non-finite samples propagate as this arithmetic carries them.
+// Why a kernel template of its own and not a fourth parameter of k_das_beamform: `p` is a launch argument, and one more argument
+// enlarges the kernarg segment of every instance of the template -- the existing instances would no longer be the parent's.  The
+// walk over tiles, elements and angles below is k_das_beamform's, statement for statement; only what happens to a sample differs.
+template <uint32_t METHOD>
+DEV float nl_root(float v, bool square, float inv_p) {
+    const float a = __builtin_fabsf(v);
+    return __builtin_copysignf((METHOD == PBRT_BF_FDMAS || square) ? sqrtf(a) : powf(a, inv_p), v);
+}
+template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD>
+__global__ __launch_bounds__(64 * DAS_SPLIT) void k_nl_beamform(pbrt_das_params p, DasGrid grid, const float *__restrict__ data,
+                                                                const float *__restrict__ tx, const float *__restrict__ elem_x,
+                                                                const float *__restrict__ gx, const float *__restrict__ gz,
+                                                                const double *__restrict__ ttx, float *__restrict__ out, float pw) {
+    constexpr uint32_t NL_ROWS = METHOD == PBRT_BF_FDMAS ? 2u * DAS_ANG : DAS_ANG;  // q_a, then (F-DMAS) sum |s_e|
+    __shared__ double s_tmin[DAS_SPLIT][DAS_ANG][64];
+    __shared__ float s_nl[DAS_SPLIT][NL_ROWS][64];
+    uint32_t tile_x, tile_z;
+    if (!das_tile_of(grid, blockIdx.x, &tile_x, &tile_z)) return;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ix = tile_x * DAS_TILE + (lane >> 3), iz = tile_z * DAS_TILE + (lane & 7u);
+    const bool valid = ix < p.nx && iz < p.nz;
+    const double x = (double)gx[min(ix, p.nx - 1u)], z = (double)gz[min(iz, p.nz - 1u)];
+    const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0;
+    const uint32_t A = p.n_angles, E = p.n_elements, T = p.time_samples;
+    const double half_ap = p.f_number > 0.0f ? z / (2.0 * (double)p.f_number) : 1e300;
+    const double zz = z * z;
+    const bool square = pw == 2.0f;
+    const float inv_p = 1.0f / pw;
+    // the tile early-out of k_das_beamform: a tile outside the span of a linear array writes exact zeros
+    float ex_lo = 3.0e38f, ex_hi = -3.0e38f;
+    for (uint32_t eb = 0; !CONVEX && eb < E; eb += 64u) {
+        const float v = elem_x[eb + min(lane, E - eb - 1u)];
+        ex_lo = fminf(ex_lo, v);
+        ex_hi = fmaxf(ex_hi, v);
+    }
+    if (!CONVEX) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
+            ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
+        }
+    }
+    bool any = valid && (CONVEX || (x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi));
+    if (__ballot(any) == 0ull) {
+        if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = 0.0f;
+        return;
+    }
+    const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;
+    float acc = 0.0f;  // wave 0: the y_a so far
+    const double last = (double)(T - 1u);
+    for (uint32_t a0 = 0; a0 < A; a0 += DAS_ANG) {
+        const uint32_t na = min((uint32_t)DAS_ANG, A - a0);
+        double tmin[DAS_ANG];
+#pragma unroll
+        for (uint32_t j = 0; j < DAS_ANG; ++j) tmin[j] = 1e300;
+        if (TABLE) {
+            const size_t pix = (size_t)min(ix, p.nx - 1u) * p.nz + min(iz, p.nz - 1u), plane = (size_t)p.nx * p.nz;
+#pragma unroll
+            for (uint32_t j = 0; j < DAS_ANG; ++j)
+                if (j < na) tmin[j] = ttx[(size_t)(a0 + j) * plane + pix];
+        }
+        for (uint32_t eb = 0; !TABLE && eb < E; eb += 64u) {
+            const uint32_t ne = min(64u, E - eb), le = min(lane, ne - 1u);
+            const double ex_l = (double)elem_x[CONVEX ? 4u * (eb + le) : eb + le];
+            const double ez_l = CONVEX ? (double)elem_x[4u * (eb + le) + 1u] : 0.0;
+            double tx_l[DAS_ANG];
+#pragma unroll
+            for (uint32_t j = 0; j < DAS_ANG; ++j) tx_l[j] = j < na ? (double)tx[(size_t)(a0 + j) * E + eb + le] : 0.0;
+            for (uint32_t e = wave; e < ne; e += DAS_SPLIT) {
+                const double dx = x - das_lane_f64(ex_l, e);
+                const double dz = CONVEX ? z - das_lane_f64(ez_l, e) : 0.0;
+                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
+#pragma unroll
+                for (uint32_t j = 0; j < DAS_ANG; ++j)
+                    if (j < na) tmin[j] = fmin(tmin[j], das_lane_f64(tx_l[j], e) + d);
+            }
+        }
+        if (!TABLE) {
+            if (a0) __syncthreads();  // the previous trip's tables have been read
+#pragma unroll
+            for (uint32_t j = 0; j < DAS_ANG; ++j)
+                if (j < na) s_tmin[wave][j][lane] = tmin[j];
+            __syncthreads();
+#pragma unroll
+            for (uint32_t j = 0; j < DAS_ANG; ++j) {
+                if (j >= na) break;
+                double m = s_tmin[0][j][lane];
+                for (uint32_t w = 1; w < DAS_SPLIT; ++w) m = fmin(m, s_tmin[w][j][lane]);
+                tmin[j] = m;
+            }
+        }
+        DasPos tp[DAS_ANG];
+        if (INTERP == PBRT_DAS_LINEAR) {
+#pragma unroll
+            for (uint32_t j = 0; j < DAS_ANG; ++j)
+                if (j < na) tp[j] = das_split((tmin[j] - t0) * fs);
+        }
+        float q[DAS_ANG], b[DAS_ANG];  // this wave's share of sum_e root(s_e) and (F-DMAS) of sum_e |s_e|, per angle of the trip
+#pragma unroll
+        for (uint32_t j = 0; j < DAS_ANG; ++j) q[j] = b[j] = 0.0f;
+        for (uint32_t eb = 0; eb < E; eb += 64u) {
+            const uint32_t ne = min(64u, E - eb);
+            const uint32_t ee = eb + min(lane, ne - 1u);
+            const double ex_l = (double)elem_x[CONVEX ? 4u * ee : ee];
+            const double ez_l = CONVEX ? (double)elem_x[4u * ee + 1u] : 0.0, nx_l = CONVEX ? (double)elem_x[4u * ee + 2u] : 0.0,
+                         nz_l = CONVEX ? (double)elem_x[4u * ee + 3u] : 0.0;
+            for (uint32_t el = wave; el < ne; el += DAS_SPLIT) {
+                const uint32_t e = eb + el;
+                const double dx = x - das_lane_f64(ex_l, el);
+                double dz = 0.0;
+                bool in_ap;
+                if (CONVEX) {
+                    dz = z - das_lane_f64(ez_l, el);
+                    const double enx = das_lane_f64(nx_l, el), enz = das_lane_f64(nz_l, el);
+                    const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
+                    in_ap = any && (p.f_number > 0.0f ? (dn > 0.0 && two_f * fabs(dt) <= dn) : true);
+                } else {
+                    in_ap = any && fabs(dx) <= half_ap;
+                }
+                if (__ballot(in_ap) == 0ull) continue;
+                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
+                const DasPos dp = INTERP == PBRT_DAS_LINEAR ? das_split(d * fs) : DasPos{0, 0.0f};
+#pragma unroll
+                for (uint32_t j = 0; j < DAS_ANG; ++j) {
+                    if (j >= na) break;
+                    const float *trace = data + ((size_t)(a0 + j) * E + e) * T;
+                    bool use = false;
+                    float v = 0.0f;
+                    if (INTERP == PBRT_DAS_NEAREST) {
+                        const double r = rint((tmin[j] + d - t0) * fs);
+                        use = in_ap && r >= 0.0 && r <= last;
+                        if (use) v = trace[(uint32_t)r];
+                    } else {
+                        const float fr = tp[j].f + dp.f;  // [0, 2)
+                        const float fl = floorf(fr);
+                        const float w = fr - fl;
+                        const uint32_t i0 = (uint32_t)(tp[j].i + dp.i + (int32_t)fl);
+                        if (in_ap && i0 < T - 1u) {
+                            const float v0 = trace[i0], v1 = trace[i0 + 1];
+                            v = fma_(w, v1 - v0, v0);
+                            use = true;
+                        } else if (in_ap && i0 == T - 1u && w == 0.0f) {  // exactly the last sample
+                            v = trace[T - 1u];
+                            use = true;
+                        }
+                    }
+                    if (use) {
+                        q[j] += nl_root<METHOD>(v, square, inv_p);
+                        if (METHOD == PBRT_BF_FDMAS) b[j] += __builtin_fabsf(v);
+                    }
+                }
+            }
+        }
+        // the waves' shares meet, in wave order, before the non-linearity; wave 0 adds the trip's y_a in angle order
+        if (TABLE && a0) __syncthreads();  // (without a table the barriers of s_tmin above stand between wave 0's reads and these writes)
+#pragma unroll
+        for (uint32_t j = 0; j < DAS_ANG; ++j) {
+            if (j >= na) break;
+            s_nl[wave][j][lane] = q[j];
+            if (METHOD == PBRT_BF_FDMAS) s_nl[wave][DAS_ANG + j][lane] = b[j];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (uint32_t j = 0; j < DAS_ANG; ++j) {
+                if (j >= na) break;
+                float qa = s_nl[0][j][lane];
+                for (uint32_t w = 1; w < DAS_SPLIT; ++w) qa += s_nl[w][j][lane];
+                if (METHOD == PBRT_BF_FDMAS) {
+                    float ba = s_nl[0][DAS_ANG + j][lane];
+                    for (uint32_t w = 1; w < DAS_SPLIT; ++w) ba += s_nl[w][DAS_ANG + j][lane];
+                    acc += 0.5f * (qa * qa - ba);
+                } else {
+                    const float m = __builtin_fabsf(qa);
+                    acc += __builtin_copysignf(square ? m * m : powf(m, pw), qa);
+                }
+            }
+        }
+    }
+    if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = p.compound_mean ? acc / (float)A : acc;
+}
+
+// Axial FIR (the band-pass both methods need, D19): out[ix][n] = sum_{k = -K .. K} h[k] in[ix][n - k], zero outside the column, f32
+// multiply-adds in order of increasing k.  The taps h [2K + 1] come from the caller (beamform.bandpass_taps designs them).  One
+// workgroup per 256 outputs of one column; taps and the 256 + 2K inputs staged in LDS, as in k_apply_pulse below.
+#define FIR_MAX_K 1024
+__global__ __launch_bounds__(256) void k_axial_fir(uint32_t nz, uint32_t K, uint32_t blocks_per_col, const float *__restrict__ taps,
+                                                   const float *__restrict__ in, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float lds_fir[];
+    float *h = lds_fir;              // [2K + 1], h[K + k]
+    float *x = lds_fir + 2 * K + 1;  // [256 + 2K]
+    const uint32_t col = blockIdx.x / blocks_per_col, n0 = (blockIdx.x - col * blocks_per_col) * 256u;
+    const float *src = in + (size_t)col * nz;
+    for (uint32_t i = threadIdx.x; i < 2 * K + 1; i += 256u) h[i] = taps[i];
+    for (uint32_t i = threadIdx.x; i < 256u + 2 * K; i += 256u) {
+        const int64_t n = (int64_t)n0 + (int64_t)i - (int64_t)K;
+        x[i] = (n >= 0 && n < (int64_t)nz) ? src[n] : 0.0f;
+    }
+    __syncthreads();
+    const uint32_t n = n0 + threadIdx.x;
+    if (n >= nz) return;
+    float acc = 0.0f;
+    // x index of in[n - k] is threadIdx.x + K - k = threadIdx.x + 2K - (K + k)
+    for (uint32_t j = 0; j < 2 * K + 1; ++j) acc = fma_(h[j], x[threadIdx.x + 2 * K - j], acc);
+    out[(size_t)col * nz + n] = acc;
+}
+
 // ---- envelope ---------------------------------------------------------------------------------------------------------------
 // Modulus of the analytic signal along z, by the definition of scipy.signal.hilbert: X = DFT(x); X[0] and X[N/2] (N even) kept,
 // positive frequencies doubled, negative ones zeroed; y = IDFT(X) = x + i xh; env = |y|.

@@ -2528,7 +2528,7 @@ static int das_check(pbrt_ctx *ctx, const pbrt_das_params *p) {
 }
 // de: element positions [n_elements], or (probe) the element table [n_elements][4] of pbrt_us_array_elements
 static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, const float *dt, const float *de, const float *dx,
-                       const float *dz, float *dout, const double *ttx = nullptr, bool probe = false) {
+                       const float *dz, float *dout, const double *ttx = nullptr, bool probe = false, uint32_t method = 0u, float pw = 0.0f) {
     ImgTimer tm(c, IMG_DAS);
     DasGrid g;
     g.ntx = div_up(p->nx, DAS_TILE);
@@ -2539,9 +2539,16 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_das_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
-                                   p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe);
-    hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
+    if (method) {  // p-DAS / F-DMAS (pbrt_bf_*): the same tiles, the method's arithmetic compiled in, p a launch argument
+        const auto kernel = with_flags([](auto L, auto T, auto X, auto F) {
+            return &k_nl_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), F() ? PBRT_BF_FDMAS : PBRT_BF_PDAS>; },
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe, method == PBRT_BF_FDMAS);
+        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout, pw);
+    } else {
+        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_das_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe);
+        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
+    }
     c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * 4;
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
@@ -2608,14 +2615,14 @@ static int pulse_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, uint32_t K,
 
 // the four DAS entry points and their *_probe twins (element table instead of positions): one body each
 static int das_beamform_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
-                                 const void *d_x, const void *d_z, void *d_out, bool probe) {
+                                 const void *d_x, const void *d_z, void *d_out, bool probe, uint32_t method = 0u, float pw = 0.0f) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && d_data && d_tx_delays && d_elem_x && d_x && d_z && d_out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, p, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x,
-                       (const float *)d_z, (float *)d_out, nullptr, probe);
+                       (const float *)d_z, (float *)d_out, nullptr, probe, method, pw);
 }
 
 static int das_first_arrival_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
@@ -2633,18 +2640,18 @@ static int das_first_arrival_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, c
 }
 
 static int das_beamform_table_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem_x,
-                                       const void *d_x, const void *d_z, void *d_out, bool probe) {
+                                       const void *d_x, const void *d_z, void *d_out, bool probe, uint32_t method = 0u, float pw = 0.0f) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && d_data && d_table && d_elem_x && d_x && d_z && d_out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, p, (const float *)d_data, nullptr, (const float *)d_elem_x, (const float *)d_x, (const float *)d_z,
-                       (float *)d_out, (const double *)d_table, probe);
+                       (float *)d_out, (const double *)d_table, probe, method, pw);
 }
 
 static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays, const float *elem_x,
-                             const float *x, const float *z, float *out, bool probe) {
+                             const float *x, const float *z, float *out, bool probe, uint32_t method = 0u, float pw = 0.0f) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && data && tx_delays && elem_x && x && z && out);
     int rc = das_check(ctx, p);
@@ -2656,12 +2663,69 @@ static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const floa
     float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem_x, nel);
     float *dx = S.in(x, p->nx), *dz = S.in(z, p->nz);
     float *dout = S.out<float>(n);
-    if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout, nullptr, probe)) != 0) return rc;
+    if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout, nullptr, probe, method, pw)) != 0) return rc;
     S.back(out, dout, n);
     return S.finish();
 }
 
+// p-DAS / F-DMAS: what pbrt_bf_params adds to das_check; the entry points then take the DAS path with a method
+static int bf_check(pbrt_ctx *ctx, const pbrt_bf_params *p) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, p && (p->method == PBRT_BF_PDAS || p->method == PBRT_BF_FDMAS) && p->probe <= 1u);
+    NEED(ctx, p->method != PBRT_BF_PDAS || (std::isfinite(p->p) && p->p >= 1.0f && p->p <= 8.0f));
+    return PBRT_OK;
+}
+static int fir_check(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K) {
+    NEED(ctx, K <= FIR_MAX_K && nz > 0);
+    NEED(ctx, (uint64_t)nx * nz < 0xffffffffull && (uint64_t)nx * div_up(nz, 256) < 0x7fffffffull);
+    return PBRT_OK;
+}
+static int fir_enqueue(pbrt_ctx *c, uint32_t nx, uint32_t nz, uint32_t K, const float *dtaps, const float *din, float *dout) {
+    const size_t lds = (size_t)(2 * K + 1 + 256 + 2 * K) * 4;
+    const uint32_t per_col = div_up(nz, 256);
+    hipLaunchKernelGGL(k_axial_fir, dim3(nx * per_col), dim3(256), lds, c->stream, nz, K, per_col, dtaps, din, dout);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
 extern "C" {
+
+int pbrt_bf_beamform_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
+                         const void *d_x, const void *d_z, void *d_out) {
+    int rc = bf_check(ctx, p);
+    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, d_tx_delays, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
+}
+int pbrt_bf_beamform_table_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_table, const void *d_elem,
+                               const void *d_x, const void *d_z, void *d_out) {
+    int rc = bf_check(ctx, p);
+    return rc ? rc : das_beamform_table_dev_impl(ctx, &p->das, d_data, d_table, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
+}
+int pbrt_bf_beamform(pbrt_ctx *ctx, const pbrt_bf_params *p, const float *data, const float *tx_delays, const float *elem,
+                     const float *x, const float *z, float *out) {
+    int rc = bf_check(ctx, p);
+    return rc ? rc : das_beamform_impl(ctx, &p->das, data, tx_delays, elem, x, z, out, p->probe != 0u, p->method, p->p);
+}
+int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *d_taps, const void *d_in, void *d_out) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, d_taps && d_in && d_out && d_in != d_out);
+    int rc = fir_check(ctx, nx, nz, K);
+    if (rc) return rc;
+    if (nx == 0) return PBRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return fir_enqueue(ctx, nx, nz, K, (const float *)d_taps, (const float *)d_in, (float *)d_out);
+}
+int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const float *taps, const float *in, float *out) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, taps && in && out && in != out);
+    int rc = fir_check(ctx, nx, nz, K);
+    if (rc) return rc;
+    const uint32_t n = nx * nz;
+    STAGED_BEGIN(ctx, (size_t)n * 8 + (size_t)(2 * K + 1) * 4 + 128);
+    float *dh = S.in(taps, 2 * (size_t)K + 1), *din = S.in(in, n), *dout = S.out<float>(n);
+    if ((rc = fir_enqueue(c, nx, nz, K, dh, din, dout)) != 0) return rc;
+    S.back(out, dout, n);
+    return S.finish();
+}
 
 int pbrt_das_beamform_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
                           const void *d_x, const void *d_z, void *d_out) {
