@@ -78,6 +78,54 @@ def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
     return tab
 
 
+def _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, *, t0, f_number, interpolation, compound, out, table, method=None,
+              p=2.0):
+    """das_beamform (method None) and nonlinear_beamform: shapes and uploads the arguments, validates `out` and `table`, selects the
+    entry point -- pbrt_das_beamform[_table][_probe][_dev], or pbrt_bf_beamform[_table][_dev] with the probe flag in its
+    parameters -- and keeps what the queued kernel reads alive with its result."""
+    dev = _is_dev(data)
+    cx = data.ctx if dev else _capi.default_context()
+    if not dev:
+        data = _capi.f32(np.asarray(data))
+    if len(data.shape) != 3:
+        raise ValueError("data must be [n_angles, n_elements, time_samples]")
+    A, E, T = data.shape
+    if dev:
+        elem_x, probe, eshape = _elem_arg(elem_x, E)
+        d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem_x, eshape)
+        d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
+        d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
+        nx, nz = d_x.shape[0], d_z.shape[0]
+    else:
+        tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
+        elem_x, probe, eshape = _elem_arg(elem_x, E)
+        ex = _capi.f32(np.asarray(elem_x).reshape(eshape))
+        gx, gz = _capi.f32(np.asarray(x).ravel()), _capi.f32(np.asarray(z).ravel())
+        nx, nz = len(gx), len(gz)
+    par = _das_params(A, E, T, nx, nz, fs, sound_speed, t0, f_number, interpolation, compound)
+    name = "pbrt_das_beamform"
+    if method is not None:
+        par, name = _bf_params(par, method, p, probe), "pbrt_bf_beamform"
+    if not dev:
+        name += "_probe" if probe and method is None else ""
+        res = np.empty((nx, nz), dtype=np.float32)
+        cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
+                                       _capi.addr(gz), _capi.addr(res)), name)
+        return res
+    d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz))
+    if d_out.nbytes != nx * nz * 4:
+        raise ValueError("out must hold nx * nz float32")
+    if table is not None:   # the first-arrival times of this scan, made once (das_first_arrival)
+        if table.nbytes != A * nx * nz * 8:
+            raise ValueError("table must be the [n_angles, nx, nz] float64 buffer of das_first_arrival for this scan")
+        name += "_table"
+    name += ("_probe" if probe and method is None else "") + "_dev"
+    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), data.ptr, (d_tx if table is None else table).ptr, d_ex.ptr, d_x.ptr,
+                                   d_z.ptr, d_out.ptr), name)
+    d_out._keep = (d_tx, d_ex, d_x, d_z, table)  # the queued kernel reads them: they live as long as its result
+    return d_out
+
+
 def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_number=1.0, interpolation="linear",
                  compound="sum", out=None, table=None):
     """data [n_angles, n_elements, T] f32, tx_delays [n_angles, n_elements] (s), elem_x [n_elements] (m),
@@ -88,44 +136,8 @@ def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_numbe
     times from das_first_arrival (pbrt_das_beamform_table_dev).
     elem_x [n_elements, 4] = (x, z, nx, nz): the element table of a curved probe; the same calls with `_probe` in their names
     (distances to (x_e, z_e), the f-number aperture in the element's frame: include/pbrt_hip.h)."""
-    cx = data.ctx if _is_dev(data) else _capi.default_context()
-    if _is_dev(data):
-        if len(data.shape) != 3:
-            raise ValueError("data must be [n_angles, n_elements, time_samples]")
-        A, E, T = data.shape
-        elem_x, probe, eshape = _elem_arg(elem_x, E)
-        d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem_x, eshape)
-        d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
-        d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
-        nx, nz = d_x.shape[0], d_z.shape[0]
-        p = _das_params(A, E, T, nx, nz, fs, sound_speed, t0, f_number, interpolation, compound)
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz))
-        if d_out.nbytes != nx * nz * 4:
-            raise ValueError("out must hold nx * nz float32")
-        if table is not None:   # the first-arrival times of this scan, made once (das_first_arrival)
-            if table.nbytes != A * nx * nz * 8:
-                raise ValueError("table must be the [n_angles, nx, nz] float64 buffer of das_first_arrival for this scan")
-            name = "pbrt_das_beamform_table_probe_dev" if probe else "pbrt_das_beamform_table_dev"
-            cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), data.ptr, table.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr), name)
-        else:
-            name = "pbrt_das_beamform_probe_dev" if probe else "pbrt_das_beamform_dev"
-            cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), data.ptr, d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr), name)
-        d_out._keep = (d_tx, d_ex, d_x, d_z, table)  # the queued kernel reads them: they live as long as its result
-        return d_out
-    data = _capi.f32(np.asarray(data))
-    if data.ndim != 3:
-        raise ValueError("data must be [n_angles, n_elements, time_samples]")
-    A, E, T = data.shape
-    tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
-    elem_x, probe, eshape = _elem_arg(elem_x, E)
-    ex = _capi.f32(np.asarray(elem_x).reshape(eshape))
-    gx, gz = _capi.f32(np.asarray(x).ravel()), _capi.f32(np.asarray(z).ravel())
-    p = _das_params(A, E, T, len(gx), len(gz), fs, sound_speed, t0, f_number, interpolation, compound)
-    res = np.empty((p.nx, p.nz), dtype=np.float32)
-    name = "pbrt_das_beamform_probe" if probe else "pbrt_das_beamform"
-    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
-                                   _capi.addr(gz), _capi.addr(res)), name)
-    return res
+    return _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
+                     compound=compound, out=out, table=table)
 
 
 def _bf_params(das, method, p, probe) -> "_capi.BfParams":
@@ -144,43 +156,8 @@ def nonlinear_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, method="f
     das_first_arrival), queued, a DeviceBuffer out.  elem_x [n_elements] or the element table [n_elements, 4]."""
     if method not in ("pdas", "fdmas"):
         raise ValueError(f"method must be 'pdas' or 'fdmas', got {method!r}")
-    cx = data.ctx if _is_dev(data) else _capi.default_context()
-    if _is_dev(data):
-        if len(data.shape) != 3:
-            raise ValueError("data must be [n_angles, n_elements, time_samples]")
-        A, E, T = data.shape
-        elem_x, probe, eshape = _elem_arg(elem_x, E)
-        d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem_x, eshape)
-        d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
-        d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
-        nx, nz = d_x.shape[0], d_z.shape[0]
-        bp = _bf_params(_das_params(A, E, T, nx, nz, fs, sound_speed, t0, f_number, interpolation, compound), method, p, probe)
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz))
-        if d_out.nbytes != nx * nz * 4:
-            raise ValueError("out must hold nx * nz float32")
-        if table is not None:
-            if table.nbytes != A * nx * nz * 8:
-                raise ValueError("table must be the [n_angles, nx, nz] float64 buffer of das_first_arrival for this scan")
-            cx.check(cx.lib.pbrt_bf_beamform_table_dev(cx.handle, C.byref(bp), data.ptr, table.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr),
-                     "pbrt_bf_beamform_table_dev")
-        else:
-            cx.check(cx.lib.pbrt_bf_beamform_dev(cx.handle, C.byref(bp), data.ptr, d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, d_out.ptr),
-                     "pbrt_bf_beamform_dev")
-        d_out._keep = (d_tx, d_ex, d_x, d_z, table)
-        return d_out
-    data = _capi.f32(np.asarray(data))
-    if data.ndim != 3:
-        raise ValueError("data must be [n_angles, n_elements, time_samples]")
-    A, E, T = data.shape
-    tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
-    elem_x, probe, eshape = _elem_arg(elem_x, E)
-    ex = _capi.f32(np.asarray(elem_x).reshape(eshape))
-    gx, gz = _capi.f32(np.asarray(x).ravel()), _capi.f32(np.asarray(z).ravel())
-    bp = _bf_params(_das_params(A, E, T, len(gx), len(gz), fs, sound_speed, t0, f_number, interpolation, compound), method, p, probe)
-    res = np.empty((len(gx), len(gz)), dtype=np.float32)
-    cx.check(cx.lib.pbrt_bf_beamform(cx.handle, C.byref(bp), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
-                                     _capi.addr(gz), _capi.addr(res)), "pbrt_bf_beamform")
-    return res
+    return _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
+                     compound=compound, out=out, table=table, method=method, p=p)
 
 
 def axial_fir(rf, taps, out=None):

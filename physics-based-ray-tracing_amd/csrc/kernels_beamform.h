@@ -50,7 +50,7 @@
 struct DasGrid {
     uint32_t ntx, ntz, m;
 };
-DEV uint32_t das_band_lo(uint32_t band, uint32_t ntz) { return (band * ntz + DAS_BANDS - 1u) / DAS_BANDS; }
+__host__ DEV uint32_t das_band_lo(uint32_t band, uint32_t ntz) { return (band * ntz + DAS_BANDS - 1u) / DAS_BANDS; }
 DEV bool das_tile_of(const DasGrid g, uint32_t b, uint32_t *tx, uint32_t *tz) {
     const uint32_t xcd = b % DAS_XCDS, i = b / DAS_XCDS;
     const uint32_t lo1 = das_band_lo(xcd, g.ntz), n1 = das_band_lo(xcd + 1u, g.ntz) - lo1;
@@ -130,20 +130,41 @@ __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, co
     }
 }
 
+// ---- the walk: delay-and-sum, p-DAS and F-DMAS --------------------------------------------------------------------------------
+// Two argument lists, one body: `p` is a launch argument, and one more argument enlarges the kernarg segment of every instance of a
+// template -- so k_nl_beamform is a __global__ template of its own beside k_das_beamform, and both are one call of das_walk below,
+// where delay-and-sum is a METHOD like the other two (BF_DAS: internal, not a pbrt_bf_params method).
+#define BF_DAS 0u
+// p-DAS and F-DMAS (DESIGN D19).  The non-linear members of the beamformer family (`ultraspy` ships them beside DelayAndSum; absent here, so the arithmetic is this
+// build's own definition, include/pbrt_hip.h, taken from Polichetti et al. 2018 and Matrone et al. 2015).  The delayed sample s_e of
+// transmission a and element e at a pixel is exactly the term delay-and-sum adds; per transmission
+//   PBRT_BF_PDAS:   q_a = sum_e sgn(s_e) |s_e|^(1/p),   y_a = sgn(q_a) |q_a|^p          (p = 2: sqrtf and a product, else powf)
+//   PBRT_BF_FDMAS:  q_a = sum_e sgn(s_e) sqrt|s_e|,     y_a = ((q_a)^2 - sum_e |s_e|) / 2  = sum_{i<j} of the signed roots' products
+// and out = sum_a y_a (/ n_angles).  Wave w = e % DAS_SPLIT keeps its share of q_a (and of sum |s_e|) for the DAS_ANG angles of a trip
+// in registers, the shares meet in LDS rows [DAS_SPLIT][angles][64] and are added in wave order BEFORE the non-linearity; wave 0 adds
+// the y_a in angle order.  Non-finite samples propagate as this arithmetic carries them.
+template <uint32_t METHOD>
+DEV float nl_root(float v, bool square, float inv_p) {
+    const float a = __builtin_fabsf(v);
+    return __builtin_copysignf((METHOD == PBRT_BF_FDMAS || square) ? sqrtf(a) : powf(a, inv_p), v);
+}
+
+// The walk over tiles, elements and angles of the comment at the top of this file, for all three methods.  What METHOD compiles in is
+// what happens to a delayed sample (BF_DAS: added to the wave's partial sum; else: its signed root into q[j] and, F-DMAS, its modulus
+// into b[j]), the per-trip meeting of the shares and the non-linearity (non-linear methods), and the final
+// reduction of the waves' partial sums (BF_DAS).
 // TABLE: the first-arrival times come from a table [n_angles][nx][nz] of doubles (k_das_first_arrival: the same minimum, made once
 // for a scan whose delays and grid do not change -- the 51 renders of USMain.py share one) instead of a pass over all elements
-// per call; the rest of the kernel, and every bit of its result, is the same.
+// per call; the rest of the walk, and every bit of its result, is the same.
 // CONVEX: the element table of a curved array (above); its four columns are held in lanes and picked with v_readlane like elem_x.
-template <uint32_t INTERP, bool TABLE, bool CONVEX = false>
-#ifdef DAS_WAVES_PER_EU  // A/B: register budget of the kernel (default: what the compiler takes, 70 VGPRs = 7 waves per SIMD)
-__attribute__((amdgpu_waves_per_eu(DAS_WAVES_PER_EU, DAS_WAVES_PER_EU)))
-#endif
-__global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params p, DasGrid grid, const float *__restrict__ data,
-                                                                 const float *__restrict__ tx, const float *__restrict__ elem_x,
-                                                                 const float *__restrict__ gx, const float *__restrict__ gz,
-                                                                 const double *__restrict__ ttx, float *__restrict__ out) {
+template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD>
+DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__restrict__ data, const float *__restrict__ tx,
+                  const float *__restrict__ elem_x, const float *__restrict__ gx, const float *__restrict__ gz,
+                  const double *__restrict__ ttx, float *__restrict__ out, float pw) {
+    // rows of a wave's share: the partial sum (BF_DAS), or per angle of a trip q_a, then (F-DMAS) sum |s_e|
+    constexpr uint32_t ROWS = METHOD == BF_DAS ? 1u : METHOD == PBRT_BF_FDMAS ? 2u * DAS_ANG : DAS_ANG;
     __shared__ double s_tmin[DAS_SPLIT][DAS_ANG][64];
-    __shared__ float s_acc[DAS_SPLIT][64];
+    __shared__ float s_sum[DAS_SPLIT][ROWS][64];
     uint32_t tile_x, tile_z;
     if (!das_tile_of(grid, blockIdx.x, &tile_x, &tile_z)) return;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -154,6 +175,8 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
     const uint32_t A = p.n_angles, E = p.n_elements, T = p.time_samples;
     const double half_ap = p.f_number > 0.0f ? z / (2.0 * (double)p.f_number) : 1e300;
     const double zz = z * z;
+    const bool square = pw == 2.0f;
+    const float inv_p = 1.0f / pw;
     // Element positions and transmit delays are tables of the launch, indexed by the (wave-uniform) element: as scalar loads they
     // put a trip to the scalar cache (or to L2) in front of every element of every loop -- a wave alone on its CU took 100 us for
     // 7 600 VALU instructions.  Instead lane l of the wave holds entry l of the current block of 64 elements, as doubles, and an
@@ -177,12 +200,12 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
     }
     // (CONVEX: no early-out -- the apertures of a curved array fan out, the span of the x_e bounds nothing)
     bool any = valid && (CONVEX || (x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi));
-    if (__ballot(any) == 0ull) {
+    if (__ballot(any) == 0ull) {  // a tile outside the span of a linear array writes exact zeros
         if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = 0.0f;
         return;
     }
     const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;  // CONVEX: 2 f# |d_t| <= d_n
-    float acc = 0.0f;
+    float acc = 0.0f;  // BF_DAS: this wave's partial sum; else, in wave 0: the y_a so far
     const double last = (double)(T - 1u);
     for (uint32_t a0 = 0; a0 < A; a0 += DAS_ANG) {
         const uint32_t na = min((uint32_t)DAS_ANG, A - a0);
@@ -214,172 +237,6 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params
         }
         // ... and the minimum over the waves
         if (DAS_SPLIT > 1 && !TABLE) {
-            if (a0) __syncthreads();  // the previous trip's table has been read
-#pragma unroll
-            for (uint32_t j = 0; j < DAS_ANG; ++j)
-                if (j < na) s_tmin[wave][j][lane] = tmin[j];
-            __syncthreads();
-#pragma unroll
-            for (uint32_t j = 0; j < DAS_ANG; ++j) {
-                if (j >= na) break;
-                double m = s_tmin[0][j][lane];
-                for (uint32_t w = 1; w < DAS_SPLIT; ++w) m = fmin(m, s_tmin[w][j][lane]);
-                tmin[j] = m;
-            }
-        }
-        DasPos tp[DAS_ANG];
-        if (INTERP == PBRT_DAS_LINEAR) {
-#pragma unroll
-            for (uint32_t j = 0; j < DAS_ANG; ++j)
-                if (j < na) tp[j] = das_split((tmin[j] - t0) * fs);
-        }
-        for (uint32_t eb = 0; eb < E; eb += 64u) {
-            const uint32_t ne = min(64u, E - eb);
-            const uint32_t ee = eb + min(lane, ne - 1u);
-            const double ex_l = (double)elem_x[CONVEX ? 4u * ee : ee];
-            const double ez_l = CONVEX ? (double)elem_x[4u * ee + 1u] : 0.0, nx_l = CONVEX ? (double)elem_x[4u * ee + 2u] : 0.0,
-                         nz_l = CONVEX ? (double)elem_x[4u * ee + 3u] : 0.0;
-            for (uint32_t el = wave; el < ne; el += DAS_SPLIT) {
-                const uint32_t e = eb + el;
-                const double dx = x - das_lane_f64(ex_l, el);
-                double dz = 0.0;
-                bool in_ap;
-                if (CONVEX) {
-                    dz = z - das_lane_f64(ez_l, el);
-                    const double enx = das_lane_f64(nx_l, el), enz = das_lane_f64(nz_l, el);
-                    const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
-                    in_ap = any && (p.f_number > 0.0f ? (dn > 0.0 && two_f * fabs(dt) <= dn) : true);
-                } else {
-                    in_ap = any && fabs(dx) <= half_ap;
-                }
-                if (__ballot(in_ap) == 0ull) continue;
-                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
-                if (INTERP == PBRT_DAS_NEAREST) {
-#pragma unroll
-                    for (uint32_t j = 0; j < DAS_ANG; ++j) {
-                        if (j >= na) break;
-                        const float *trace = data + ((size_t)(a0 + j) * E + e) * T;
-                        const double r = rint((tmin[j] + d - t0) * fs);
-                        if (in_ap && r >= 0.0 && r <= last) acc += trace[(uint32_t)r];
-                    }
-                } else {
-                    const DasPos dp = das_split(d * fs);
-#pragma unroll
-                    for (uint32_t j = 0; j < DAS_ANG; ++j) {
-                        if (j >= na) break;
-                        const float *trace = data + ((size_t)(a0 + j) * E + e) * T;
-                        const float fr = tp[j].f + dp.f;  // [0, 2)
-                        const float fl = floorf(fr);
-                        const float w = fr - fl;
-                        const uint32_t i0 = (uint32_t)(tp[j].i + dp.i + (int32_t)fl);
-                        if (in_ap && i0 < T - 1u) {
-                            const float v0 = trace[i0], v1 = trace[i0 + 1];
-                            acc += fma_(w, v1 - v0, v0);
-                        } else if (in_ap && i0 == T - 1u && w == 0.0f) {  // exactly the last sample
-                            acc += trace[T - 1u];
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (DAS_SPLIT > 1) {  // the waves' partial sums, added in wave order
-        s_acc[wave][lane] = acc;
-        __syncthreads();
-        if (wave != 0) return;
-        acc = s_acc[0][lane];
-        for (uint32_t w = 1; w < DAS_SPLIT; ++w) acc += s_acc[w][lane];
-    }
-    if (valid) out[(size_t)ix * p.nz + iz] = p.compound_mean ? acc / (float)A : acc;
-}
-
-// ---- p-DAS and F-DMAS (DESIGN D19) ------------------------------------------------------------------------------------------
-// The non-linear members of the beamformer family (`ultraspy` ships them beside DelayAndSum; absent here, so the arithmetic is this
-// build's own definition, include/pbrt_hip.h, taken from Polichetti et al. 2018 and Matrone et al. 2015).  The delayed sample s_e of
-// transmission a and element e at a pixel is exactly the term k_das_beamform adds; per transmission
-//   PBRT_BF_PDAS:   q_a = sum_e sgn(s_e) |s_e|^(1/p),   y_a = sgn(q_a) |q_a|^p          (p = 2: sqrtf and a product, else powf)
-//   PBRT_BF_FDMAS:  q_a = sum_e sgn(s_e) sqrt|s_e|,     y_a = ((q_a)^2 - sum_e |s_e|) / 2  = sum_{i<j} of the signed roots' products
-// and out = sum_a y_a (/ n_angles).  Wave w = e % DAS_SPLIT keeps its share of q_a (and of sum |s_e|) for the DAS_ANG angles of a trip
-// in registers, the shares meet in LDS rows [DAS_SPLIT][angles][64] and are added in wave order BEFORE the non-linearity; wave 0 adds
-// the y_a in angle order.  Non-finite samples propagate as this arithmetic carries them.
-// Why a kernel template of its own and not a fourth parameter of k_das_beamform: `p` is a launch argument, and one more argument
-// enlarges the kernarg segment of every instance of the template -- the existing instances would no longer be the parent's.  The
-// walk over tiles, elements and angles below is k_das_beamform's, statement for statement; only what happens to a sample differs.
-template <uint32_t METHOD>
-DEV float nl_root(float v, bool square, float inv_p) {
-    const float a = __builtin_fabsf(v);
-    return __builtin_copysignf((METHOD == PBRT_BF_FDMAS || square) ? sqrtf(a) : powf(a, inv_p), v);
-}
-template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD>
-__global__ __launch_bounds__(64 * DAS_SPLIT) void k_nl_beamform(pbrt_das_params p, DasGrid grid, const float *__restrict__ data,
-                                                                const float *__restrict__ tx, const float *__restrict__ elem_x,
-                                                                const float *__restrict__ gx, const float *__restrict__ gz,
-                                                                const double *__restrict__ ttx, float *__restrict__ out, float pw) {
-    constexpr uint32_t NL_ROWS = METHOD == PBRT_BF_FDMAS ? 2u * DAS_ANG : DAS_ANG;  // q_a, then (F-DMAS) sum |s_e|
-    __shared__ double s_tmin[DAS_SPLIT][DAS_ANG][64];
-    __shared__ float s_nl[DAS_SPLIT][NL_ROWS][64];
-    uint32_t tile_x, tile_z;
-    if (!das_tile_of(grid, blockIdx.x, &tile_x, &tile_z)) return;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t ix = tile_x * DAS_TILE + (lane >> 3), iz = tile_z * DAS_TILE + (lane & 7u);
-    const bool valid = ix < p.nx && iz < p.nz;
-    const double x = (double)gx[min(ix, p.nx - 1u)], z = (double)gz[min(iz, p.nz - 1u)];
-    const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0;
-    const uint32_t A = p.n_angles, E = p.n_elements, T = p.time_samples;
-    const double half_ap = p.f_number > 0.0f ? z / (2.0 * (double)p.f_number) : 1e300;
-    const double zz = z * z;
-    const bool square = pw == 2.0f;
-    const float inv_p = 1.0f / pw;
-    // the tile early-out of k_das_beamform: a tile outside the span of a linear array writes exact zeros
-    float ex_lo = 3.0e38f, ex_hi = -3.0e38f;
-    for (uint32_t eb = 0; !CONVEX && eb < E; eb += 64u) {
-        const float v = elem_x[eb + min(lane, E - eb - 1u)];
-        ex_lo = fminf(ex_lo, v);
-        ex_hi = fmaxf(ex_hi, v);
-    }
-    if (!CONVEX) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
-            ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
-        }
-    }
-    bool any = valid && (CONVEX || (x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi));
-    if (__ballot(any) == 0ull) {
-        if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = 0.0f;
-        return;
-    }
-    const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;
-    float acc = 0.0f;  // wave 0: the y_a so far
-    const double last = (double)(T - 1u);
-    for (uint32_t a0 = 0; a0 < A; a0 += DAS_ANG) {
-        const uint32_t na = min((uint32_t)DAS_ANG, A - a0);
-        double tmin[DAS_ANG];
-#pragma unroll
-        for (uint32_t j = 0; j < DAS_ANG; ++j) tmin[j] = 1e300;
-        if (TABLE) {
-            const size_t pix = (size_t)min(ix, p.nx - 1u) * p.nz + min(iz, p.nz - 1u), plane = (size_t)p.nx * p.nz;
-#pragma unroll
-            for (uint32_t j = 0; j < DAS_ANG; ++j)
-                if (j < na) tmin[j] = ttx[(size_t)(a0 + j) * plane + pix];
-        }
-        for (uint32_t eb = 0; !TABLE && eb < E; eb += 64u) {
-            const uint32_t ne = min(64u, E - eb), le = min(lane, ne - 1u);
-            const double ex_l = (double)elem_x[CONVEX ? 4u * (eb + le) : eb + le];
-            const double ez_l = CONVEX ? (double)elem_x[4u * (eb + le) + 1u] : 0.0;
-            double tx_l[DAS_ANG];
-#pragma unroll
-            for (uint32_t j = 0; j < DAS_ANG; ++j) tx_l[j] = j < na ? (double)tx[(size_t)(a0 + j) * E + eb + le] : 0.0;
-            for (uint32_t e = wave; e < ne; e += DAS_SPLIT) {
-                const double dx = x - das_lane_f64(ex_l, e);
-                const double dz = CONVEX ? z - das_lane_f64(ez_l, e) : 0.0;
-                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
-#pragma unroll
-                for (uint32_t j = 0; j < DAS_ANG; ++j)
-                    if (j < na) tmin[j] = fmin(tmin[j], das_lane_f64(tx_l[j], e) + d);
-            }
-        }
-        if (!TABLE) {
             if (a0) __syncthreads();  // the previous trip's tables have been read
 #pragma unroll
             for (uint32_t j = 0; j < DAS_ANG; ++j)
@@ -428,12 +285,24 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_nl_beamform(pbrt_das_params 
                 for (uint32_t j = 0; j < DAS_ANG; ++j) {
                     if (j >= na) break;
                     const float *trace = data + ((size_t)(a0 + j) * E + e) * T;
-                    bool use = false;
-                    float v = 0.0f;
+                    // a delayed sample: delay-and-sum and F-DMAS take it in the branch that gathered it, p-DAS carries it to the one site
+                    // below -- one call site of powf instead of two (the forms were measured: profiles/one_beamformer_walk.md)
+                    [[maybe_unused]] bool use = false;  // (p-DAS only)
+                    [[maybe_unused]] float v = 0.0f;
+                    const auto take = [&](float s) {
+                        if constexpr (METHOD == BF_DAS) {
+                            acc += s;
+                        } else if constexpr (METHOD == PBRT_BF_FDMAS) {
+                            q[j] += nl_root<METHOD>(s, square, inv_p);
+                            b[j] += __builtin_fabsf(s);
+                        } else {
+                            v = s;
+                            use = true;
+                        }
+                    };
                     if (INTERP == PBRT_DAS_NEAREST) {
                         const double r = rint((tmin[j] + d - t0) * fs);
-                        use = in_ap && r >= 0.0 && r <= last;
-                        if (use) v = trace[(uint32_t)r];
+                        if (in_ap && r >= 0.0 && r <= last) take(trace[(uint32_t)r]);
                     } else {
                         const float fr = tp[j].f + dp.f;  // [0, 2)
                         const float fl = floorf(fr);
@@ -441,38 +310,36 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_nl_beamform(pbrt_das_params 
                         const uint32_t i0 = (uint32_t)(tp[j].i + dp.i + (int32_t)fl);
                         if (in_ap && i0 < T - 1u) {
                             const float v0 = trace[i0], v1 = trace[i0 + 1];
-                            v = fma_(w, v1 - v0, v0);
-                            use = true;
+                            take(fma_(w, v1 - v0, v0));
                         } else if (in_ap && i0 == T - 1u && w == 0.0f) {  // exactly the last sample
-                            v = trace[T - 1u];
-                            use = true;
+                            take(trace[T - 1u]);
                         }
                     }
-                    if (use) {
-                        q[j] += nl_root<METHOD>(v, square, inv_p);
-                        if (METHOD == PBRT_BF_FDMAS) b[j] += __builtin_fabsf(v);
+                    if constexpr (METHOD == PBRT_BF_PDAS) {
+                        if (use) q[j] += nl_root<METHOD>(v, square, inv_p);
                     }
                 }
             }
         }
+        if (METHOD == BF_DAS) continue;  // (no per-trip LDS traffic for its sums, and no barrier)
         // the waves' shares meet, in wave order, before the non-linearity; wave 0 adds the trip's y_a in angle order
         if (TABLE && a0) __syncthreads();  // (without a table the barriers of s_tmin above stand between wave 0's reads and these writes)
 #pragma unroll
         for (uint32_t j = 0; j < DAS_ANG; ++j) {
             if (j >= na) break;
-            s_nl[wave][j][lane] = q[j];
-            if (METHOD == PBRT_BF_FDMAS) s_nl[wave][DAS_ANG + j][lane] = b[j];
+            s_sum[wave][j][lane] = q[j];
+            if (METHOD == PBRT_BF_FDMAS) s_sum[wave][DAS_ANG + j][lane] = b[j];
         }
         __syncthreads();
         if (wave == 0) {
 #pragma unroll
             for (uint32_t j = 0; j < DAS_ANG; ++j) {
                 if (j >= na) break;
-                float qa = s_nl[0][j][lane];
-                for (uint32_t w = 1; w < DAS_SPLIT; ++w) qa += s_nl[w][j][lane];
+                float qa = s_sum[0][j][lane];
+                for (uint32_t w = 1; w < DAS_SPLIT; ++w) qa += s_sum[w][j][lane];
                 if (METHOD == PBRT_BF_FDMAS) {
-                    float ba = s_nl[0][DAS_ANG + j][lane];
-                    for (uint32_t w = 1; w < DAS_SPLIT; ++w) ba += s_nl[w][DAS_ANG + j][lane];
+                    float ba = s_sum[0][DAS_ANG + j][lane];
+                    for (uint32_t w = 1; w < DAS_SPLIT; ++w) ba += s_sum[w][DAS_ANG + j][lane];
                     acc += 0.5f * (qa * qa - ba);
                 } else {
                     const float m = __builtin_fabsf(qa);
@@ -481,32 +348,59 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_nl_beamform(pbrt_das_params 
             }
         }
     }
+    if (METHOD == BF_DAS && DAS_SPLIT > 1) {  // the waves' partial sums, added in wave order
+        s_sum[wave][0][lane] = acc;
+        __syncthreads();
+        if (wave != 0) return;
+        acc = s_sum[0][0][lane];
+        for (uint32_t w = 1; w < DAS_SPLIT; ++w) acc += s_sum[w][0][lane];
+    }
     if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = p.compound_mean ? acc / (float)A : acc;
 }
+template <uint32_t INTERP, bool TABLE, bool CONVEX = false>
+__global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params p, DasGrid grid, const float *__restrict__ data,
+                                                                 const float *__restrict__ tx, const float *__restrict__ elem_x,
+                                                                 const float *__restrict__ gx, const float *__restrict__ gz,
+                                                                 const double *__restrict__ ttx, float *__restrict__ out) {
+    das_walk<INTERP, TABLE, CONVEX, BF_DAS>(p, grid, data, tx, elem_x, gx, gz, ttx, out, 0.0f);
+}
+template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD>
+__global__ __launch_bounds__(64 * DAS_SPLIT) void k_nl_beamform(pbrt_das_params p, DasGrid grid, const float *__restrict__ data,
+                                                                const float *__restrict__ tx, const float *__restrict__ elem_x,
+                                                                const float *__restrict__ gx, const float *__restrict__ gz,
+                                                                const double *__restrict__ ttx, float *__restrict__ out, float pw) {
+    das_walk<INTERP, TABLE, CONVEX, METHOD>(p, grid, data, tx, elem_x, gx, gz, ttx, out, pw);
+}
 
-// Axial FIR (the band-pass both methods need, D19): out[ix][n] = sum_{k = -K .. K} h[k] in[ix][n - k], zero outside the column, f32
-// multiply-adds in order of increasing k.  The taps h [2K + 1] come from the caller (beamform.bandpass_taps designs them).  One
-// workgroup per 256 outputs of one column; taps and the 256 + 2K inputs staged in LDS, as in k_apply_pulse below.
-#define FIR_MAX_K 1024
-__global__ __launch_bounds__(256) void k_axial_fir(uint32_t nz, uint32_t K, uint32_t blocks_per_col, const float *__restrict__ taps,
-                                                   const float *__restrict__ in, float *__restrict__ out) {
+// What k_axial_fir and k_apply_pulse share: one workgroup makes the 256 outputs n0 .. n0 + 255 of one row of N samples,
+// dst[n] = sum_{k = -K .. K} h[k] src[n - k], zero outside the row, f32 multiply-adds in order of increasing k.  The taps
+// h[k] = tap(K + k) and the 256 + 2K inputs are staged in LDS ((2K + 1) + (256 + 2K) floats of dynamic LDS).
+template <typename Tap>
+DEV void fir_256(uint32_t N, uint32_t K, uint32_t n0, const float *__restrict__ src, float *__restrict__ dst, Tap tap) {
     extern __shared__ __attribute__((aligned(16))) float lds_fir[];
     float *h = lds_fir;              // [2K + 1], h[K + k]
     float *x = lds_fir + 2 * K + 1;  // [256 + 2K]
-    const uint32_t col = blockIdx.x / blocks_per_col, n0 = (blockIdx.x - col * blocks_per_col) * 256u;
-    const float *src = in + (size_t)col * nz;
-    for (uint32_t i = threadIdx.x; i < 2 * K + 1; i += 256u) h[i] = taps[i];
+    for (uint32_t i = threadIdx.x; i < 2 * K + 1; i += 256u) h[i] = tap(i);
     for (uint32_t i = threadIdx.x; i < 256u + 2 * K; i += 256u) {
         const int64_t n = (int64_t)n0 + (int64_t)i - (int64_t)K;
-        x[i] = (n >= 0 && n < (int64_t)nz) ? src[n] : 0.0f;
+        x[i] = (n >= 0 && n < (int64_t)N) ? src[n] : 0.0f;
     }
     __syncthreads();
     const uint32_t n = n0 + threadIdx.x;
-    if (n >= nz) return;
+    if (n >= N) return;
     float acc = 0.0f;
-    // x index of in[n - k] is threadIdx.x + K - k = threadIdx.x + 2K - (K + k)
+    // x index of src[n - k] is threadIdx.x + K - k = threadIdx.x + 2K - (K + k)
     for (uint32_t j = 0; j < 2 * K + 1; ++j) acc = fma_(h[j], x[threadIdx.x + 2 * K - j], acc);
-    out[(size_t)col * nz + n] = acc;
+    dst[n] = acc;
+}
+
+// Axial FIR (the band-pass both methods need, D19): out[ix][n] = sum_{k = -K .. K} h[k] in[ix][n - k] along a column.  The taps
+// h [2K + 1] come from the caller (beamform.bandpass_taps designs them).  One workgroup per 256 outputs of one column.
+#define FIR_MAX_K 1024
+__global__ __launch_bounds__(256) void k_axial_fir(uint32_t nz, uint32_t K, uint32_t blocks_per_col, const float *__restrict__ taps,
+                                                   const float *__restrict__ in, float *__restrict__ out) {
+    const uint32_t col = blockIdx.x / blocks_per_col, n0 = (blockIdx.x - col * blocks_per_col) * 256u;
+    fir_256(nz, K, n0, in + (size_t)col * nz, out + (size_t)col * nz, [=](uint32_t i) { return taps[i]; });
 }
 
 // ---- envelope ---------------------------------------------------------------------------------------------------------------
@@ -805,30 +699,15 @@ __global__ __launch_bounds__(256) void k_log_compress(uint32_t n, const float *_
 }
 
 // Pulse model (SURVEY f-3; RayTracingV0.py:194-204): every trace convolved with the Gaussian-windowed carrier
-// h[k] = sin(2 pi fc k / fs) * exp(-(k / fs)^2 / sigma^2), |k| <= K.  One workgroup per 256 output samples of one
-// trace: taps and the 256 + 2K input samples staged in LDS.  HBM-bound (4 B in, 4 B out per sample).
+// h[k] = sin(2 pi fc k / fs) * exp(-(k / fs)^2 / sigma^2), |k| <= K (fir_256 above).  One workgroup per 256 output samples of one
+// trace.  HBM-bound (4 B in, 4 B out per sample).
 #define PULSE_MAX_K 1024
 __global__ __launch_bounds__(256) void k_apply_pulse(uint32_t T, uint32_t K, float fs, float fc, float sigma,
                                                      const float *__restrict__ in, float *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float lds_pulse[];
-    float *h = lds_pulse;            // [2K + 1], h[K + k]
-    float *x = lds_pulse + 2 * K + 1;  // [256 + 2K]
-    const uint32_t tr = blockIdx.y, n0 = blockIdx.x * 256u;
-    const float *src = in + (size_t)tr * T;
-    for (uint32_t i = threadIdx.x; i < 2 * K + 1; i += 256u) {
+    const size_t row = (size_t)blockIdx.y * T;
+    fir_256(T, K, blockIdx.x * 256u, in + row, out + row, [=](uint32_t i) {
         const float t = ((float)i - (float)K) / fs;
         // phase reduced per cycle: sin(2 pi fc t) = sinpi(2 fc t)
-        h[i] = sinpif(2.0f * fc * t) * expf(-(t * t) / (sigma * sigma));
-    }
-    for (uint32_t i = threadIdx.x; i < 256u + 2 * K; i += 256u) {
-        const int64_t n = (int64_t)n0 + (int64_t)i - (int64_t)K;
-        x[i] = (n >= 0 && n < (int64_t)T) ? src[n] : 0.0f;
-    }
-    __syncthreads();
-    const uint32_t n = n0 + threadIdx.x;
-    if (n >= T) return;
-    float acc = 0.0f;
-    // out[n] = sum_k in[n - k] h[k]: x index of in[n - k] is threadIdx.x + K - k
-    for (uint32_t j = 0; j < 2 * K + 1; ++j) acc = fma_(x[threadIdx.x + 2 * K - j], h[j], acc);
-    out[(size_t)tr * T + n] = acc;
+        return sinpif(2.0f * fc * t) * expf(-(t * t) / (sigma * sigma));
+    });
 }

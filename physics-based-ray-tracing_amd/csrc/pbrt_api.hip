@@ -2535,7 +2535,7 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
     g.ntz = div_up(p->nz, DAS_TILE);
     // z-tiles of the largest XCD share (bands k and 15 - k, kernels_beamform.h das_tile_of); the grid gives every XCD that many slots
     g.m = 0;
-    auto lo = [&](uint32_t band) { return (band * g.ntz + DAS_BANDS - 1u) / DAS_BANDS; };
+    auto lo = [&](uint32_t band) { return das_band_lo(band, g.ntz); };
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
@@ -2614,15 +2614,17 @@ static int pulse_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, uint32_t K,
 }
 
 // the four DAS entry points and their *_probe twins (element table instead of positions): one body each
-static int das_beamform_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
-                                 const void *d_x, const void *d_z, void *d_out, bool probe, uint32_t method = 0u, float pw = 0.0f) {
+// (d_tx_delays or d_table: the plain form passes its delays, the table form its first-arrival table, and the other one null)
+static int das_beamform_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_table,
+                                 const void *d_elem_x, const void *d_x, const void *d_z, void *d_out, bool probe, uint32_t method = 0u,
+                                 float pw = 0.0f) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && d_data && d_tx_delays && d_elem_x && d_x && d_z && d_out);
+    NEED(ctx, p && d_data && (d_tx_delays || d_table) && d_elem_x && d_x && d_z && d_out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, p, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x,
-                       (const float *)d_z, (float *)d_out, nullptr, probe, method, pw);
+                       (const float *)d_z, (float *)d_out, (const double *)d_table, probe, method, pw);
 }
 
 static int das_first_arrival_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
@@ -2637,17 +2639,6 @@ static int das_first_arrival_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, c
                        (double *)d_table);
     HIPCHK(ctx, hipGetLastError());
     return PBRT_OK;
-}
-
-static int das_beamform_table_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem_x,
-                                       const void *d_x, const void *d_z, void *d_out, bool probe, uint32_t method = 0u, float pw = 0.0f) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && d_data && d_table && d_elem_x && d_x && d_z && d_out);
-    int rc = das_check(ctx, p);
-    if (rc) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return das_enqueue(ctx, p, (const float *)d_data, nullptr, (const float *)d_elem_x, (const float *)d_x, (const float *)d_z,
-                       (float *)d_out, (const double *)d_table, probe, method, pw);
 }
 
 static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays, const float *elem_x,
@@ -2693,12 +2684,12 @@ extern "C" {
 int pbrt_bf_beamform_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
                          const void *d_x, const void *d_z, void *d_out) {
     int rc = bf_check(ctx, p);
-    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, d_tx_delays, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
+    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, d_tx_delays, nullptr, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
 }
 int pbrt_bf_beamform_table_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_table, const void *d_elem,
                                const void *d_x, const void *d_z, void *d_out) {
     int rc = bf_check(ctx, p);
-    return rc ? rc : das_beamform_table_dev_impl(ctx, &p->das, d_data, d_table, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
+    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, nullptr, d_table, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
 }
 int pbrt_bf_beamform(pbrt_ctx *ctx, const pbrt_bf_params *p, const float *data, const float *tx_delays, const float *elem,
                      const float *x, const float *z, float *out) {
@@ -2729,11 +2720,11 @@ int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const fl
 
 int pbrt_das_beamform_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
                           const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, d_elem_x, d_x, d_z, d_out, false);
+    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, nullptr, d_elem_x, d_x, d_z, d_out, false);
 }
 int pbrt_das_beamform_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
                                 const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, d_elem, d_x, d_z, d_out, true);
+    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, nullptr, d_elem, d_x, d_z, d_out, true);
 }
 int pbrt_das_first_arrival_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
                                const void *d_z, void *d_table) {
@@ -2745,11 +2736,11 @@ int pbrt_das_first_arrival_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, co
 }
 int pbrt_das_beamform_table_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem_x,
                                 const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_table_dev_impl(ctx, p, d_data, d_table, d_elem_x, d_x, d_z, d_out, false);
+    return das_beamform_dev_impl(ctx, p, d_data, nullptr, d_table, d_elem_x, d_x, d_z, d_out, false);
 }
 int pbrt_das_beamform_table_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem,
                                       const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_table_dev_impl(ctx, p, d_data, d_table, d_elem, d_x, d_z, d_out, true);
+    return das_beamform_dev_impl(ctx, p, d_data, nullptr, d_table, d_elem, d_x, d_z, d_out, true);
 }
 int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
                       const float *elem_x, const float *x, const float *z, float *out) {

@@ -1,9 +1,9 @@
 """p-DAS and F-DMAS on the device: k_nl_beamform against the float64 restatement of tests/nlbf_util.py, the axial FIR
 against np.convolve, the refusals, and us_render end to end with the new beamformer classes.
 
-The shapes are the smallest at which the kernel can still go wrong: 1 / 5 / 6 transmissions (a second trip of five angles with one
-angle in it), 3 / 64 / 65 elements (fewer elements than the four waves of a workgroup; a second block of 64 with one element in it),
-scans of 9 x 13 and 24 x 16 pixels (partial 8 x 8 tiles), traces of 160 samples.
+The shapes are the smallest at which the kernel can still go wrong: 1 / 5 / 6 / 11 transmissions (a second trip of five angles with one
+angle in it, a third one), 3 / 64 / 65 / 130 elements (fewer elements than the four waves of a workgroup; a second block of 64 with one
+element in it, a third with two), scans of 9 x 13, 9 x 17 and 24 x 16 pixels (partial 8 x 8 tiles), traces of 160 samples.
 
 The tolerance of the comparison is not a constant: per case, method and input family it is FOUR TIMES the float32 floor -- the
 largest |restatement in np.float32 - restatement in float64| / B over the pixels compared, B the size of what the pixel adds up
@@ -35,6 +35,9 @@ CASES = {
     "a1_e64_near_f0_mean": (1, 64, (24, 16), "nearest", 0.0, "mean", "line", 0.27e-3),
     "a5_e16_convex_lin_f1_sum": (5, 16, (24, 16), "linear", 1.0, "sum", "convex", 0.27e-3),
     "a6_e16_convex_small_near_f0_mean": (6, 16, (9, 13), "nearest", 0.0, "mean", "convex", 0.27e-3),
+    # a third trip of angles and a third block of elements: the walk is delay-and-sum's, which test_gpu_das_shapes.py takes as far
+    "a11_e130_small_lin_f1_mean": (11, 130, (9, 17), "linear", 1.0, "mean", "line", 0.27e-3),
+    "a11_e130_small_near_f0_sum": (11, 130, (9, 17), "nearest", 0.0, "sum", "line", 0.27e-3),
 }
 R_CONVEX, OPEN_CONVEX = 0.04, 60.0
 
