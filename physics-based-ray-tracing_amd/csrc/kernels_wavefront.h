@@ -14,7 +14,8 @@
 //            at a time with every lane busy: (t, u, v) of the hit from the primitive's record (the test k_trace made, repeated),
 //            pending shadow contribution of the previous bounce, emission + MIS, emitter sample -> shadow record, BSDF sample,
 //            Russian roulette; survivors and shadow records are packed to the front of the region (ballot + one LDS atomic
-//            per wave).
+//            per wave).  The region, chunk and list scaffold of this is the device function template shade_walk, which the
+//            ultrasound twin k_us_shade (kernels_us_wavefront.h) calls as well; k_shade is that walk with the mode RadShade.
 // The contribution of a shadow ray is added where the fused kernel added it -- L = fma(A, B, L) before the next bounce touches
 // L -- so the film does not change by a bit: same arithmetic per path, same RNG keys, same order of the radiance sums.
 //
@@ -56,6 +57,17 @@ static_assert(WF_REFILL_MIN + WF_WALK_MIN <= 65u, "k_trace: a wave below WF_WALK
 #define WF_DEAD 0x40000000u   // shadow ray of a path that has ended: dest = WF_DEAD | index of the ray's own record
 #define WF_SHADOW 0x80000000u
 #define WF_STATE_Q 6u         // float4s per path-state record
+
+// paths of region r when n paths fill the regions from the first one on
+DEV uint32_t wf_region_fill(uint32_t n, uint32_t r) { return n > r * WF_REGION ? min(n - r * WF_REGION, WF_REGION) : 0u; }
+// rank of a lane among the lanes of ballot b below it
+DEV uint32_t ballot_rank(unsigned long long b) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u)); }
+// one slot per lane of ballot b (b != 0) behind an LDS counter: one atomic of lane 0 for the wave; returns the lane's offset
+DEV uint32_t ballot_reserve(uint32_t *counter, unsigned long long b, uint32_t lane) {
+    uint32_t got = 0;
+    if (lane == 0) got = atomicAdd(counter, (uint32_t)__popcll(b));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)got) + ballot_rank(b);
+}
 
 struct WfArgs {
     DevScene sc;
@@ -260,7 +272,7 @@ __global__ __launch_bounds__(1024, WF_TRACE_WAVES_PER_EU) void k_trace(const WfA
             if (lane == 0) got = atomicAdd(&q_in, nw);
             const uint32_t i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
             if (i0 + nw >= total) q_empty = true;
-            const uint32_t i = i0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(bw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bw, 0u));
+            const uint32_t i = i0 + ballot_rank(bw);
             if (i0 < total) {
                 while (s_hint + 1u < 3u * K && i0 >= cum[s_hint + 1u]) ++s_hint;  // uniform
             }
@@ -395,11 +407,11 @@ __global__ __launch_bounds__(1024, WF_TRACE_WAVES_PER_EU) void k_trace_primary(c
     }
 }
 
-// ---- k_shade ---------------------------------------------------------------------------------------------------------------
+// ---- what the shading kernels load ------------------------------------------------------------------------------------------
 struct WfShadow {
     V3 so, sdir, A, B;
     float tmax;
-    bool on;
+    bool on = false;
 };
 // the 64-byte record of the primitive that was hit, in one batch of loads (so that the compiler cannot split it into
 // dependent pieces: type first, then the geometry of that type, then material / emitter)
@@ -453,31 +465,44 @@ DEV Tables wf_tables_lds(const DevScene &sc, uint32_t *lds, uint32_t n_threads) 
     return tb;
 }
 
-// TABS: the small tables fit LDS (wf_tables_lds), else everything is read from global memory.  CYL: the scene holds cylinders
-// GLOSSY: the scene holds a ROUGHCONDUCTOR / CONDUCTOR_FRESNEL material; instantiated with the cylinder code only (CYL = true).
-template <bool FIRST, bool TABS, bool CYL, bool GLOSSY = false>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_shade(const WfArgs a) {
+// ---- shade_walk: what k_shade and k_us_shade (kernels_us_wavefront.h) share -------------------------------------------------
+// One workgroup per region, every wave on its own after the set-up barrier.  The walk owns the region lookup and the uniform exit
+// of an empty region (before any barrier), the four LDS counters, the sweep over the records that ended paths left at the back
+// of the region, the chunk phase (WF_SHADE_CHUNKS chunks of 64 slots per step, their loads in one batch; the paths that hit
+// something go on the wave's list in LDS: slot within the region, primitive), the shading steps over 64 listed paths with every
+// lane busy, the three reservations (survivors to the front of the `out` state, their rays to the front of the records, rays of
+// ended paths to the back with WF_DEAD | k), the per-wave statistics rows and the publication of the region's counts by the last
+// wave.  It returns false from the empty-region exit and true from its end, which every wave of a region with work reaches: no
+// other return path, and one barrier (after m.stage()).
+// GEN: the region's paths are generated from u.n_paths, else counted in q.seg_in.  q: the stream members (WfArgs, UsWfArgs);
+// u: n_paths, depth and the statistics rows (WfArgs, UsArgs) -- both BY VALUE: handed in by reference the same text keeps 10 more
+// scalar registers alive than the budget holds (profiles/one_shade_walk.md).  The mode m supplies what differs between the families:
+//   Chunk, load(slot, c) -> hit index   the planes a chunk entry needs beside its hit index, read in the batch
+//   entry(slot, valid, is_hit, c)       per chunk entry: the pending contribution of the previous bounce; a path that missed
+//   keep(e, c)                          what a listed path keeps at list index e of its wave
+//   dead_record(i)                      the record i an ended path left behind, its visibility now known
+//   Path, shade(slot, prim, e, p)       one listed path: state in, the bounce, state out; true when the path goes on
+//   pending(p)                          the path has handed out a shadow / occlusion ray
+//   put_survivor, end_path, put_ray, put_dead_ray    the records of a survivor, of a path that ended, of their rays
+//   stage()                             set-up before the barrier;  stats(row, stride, segments, rays): the mode's rows
+constexpr uint32_t WF_SHADE_LIST = 64u * (WF_SHADE_CHUNKS + 1);  // entries of a wave's list: a full step of chunks on top of < 64
+template <bool GEN, class Q, class U, class M>
+DEV bool shade_walk(const Q q, const U u, M &m) {
     constexpr uint32_t T = WF_SHADE_THREADS, W = T / 64;
     constexpr int NCH = WF_SHADE_CHUNKS;  // chunks of 64 hit indices a wave reads per step
     // per wave: the paths that hit something and wait for a full wave -- slot within the region, and the primitive that was hit
-    __shared__ uint32_t wlist[W][64 * (NCH + 1)], wprim[W][64 * (NCH + 1)];
-    // ... and (bounces >= 1) its radiance so far with the pending shadow contribution folded in, and its home: the chunk phase streams
-    // the L / A / B planes of EVERY path of the chunk anyway (a path that missed needs them to end), so a path that hit keeps what
-    // they amount to -- L = fma(A, B, L), home -- on the list instead of gathering the three planes again in the shading step:
-    // 48 of the 96 gathered bytes per hit, at 128-byte lines for 16-byte records (round 4: traffic 1.25 x the model)
-    __shared__ float4 wlh[FIRST ? 1 : W][FIRST ? 1 : 64 * (NCH + 1)];
+    __shared__ uint32_t wlist[W][WF_SHADE_LIST], wprim[W][WF_SHADE_LIST];
     __shared__ uint32_t q_out, q_shd, q_dead, q_done;
-    __shared__ uint32_t tab_lds[TABS ? WF_TAB_DW : 1];
-    const uint32_t r = a.region0 + xcd_swizzle(blockIdx.x, gridDim.x), base = r * WF_REGION;
+    const uint32_t r = q.region0 + xcd_swizzle(blockIdx.x, gridDim.x), base = r * WF_REGION;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-    const uint32_t cnt_in = FIRST ? (a.n_paths > base ? min(a.n_paths - base, WF_REGION) : 0u) : a.seg_in[r];
-    const uint32_t n_dead = (!FIRST && a.nsh_in) ? a.nsh_in[r] >> 16 : 0u;
+    const uint32_t cnt_in = GEN ? wf_region_fill(u.n_paths, r) : q.seg_in[r];
+    const uint32_t n_dead = (!GEN && q.nsh_in) ? q.nsh_in[r] >> 16 : 0u;
     if (cnt_in == 0 && n_dead == 0) {  // uniform
         if (tid == 0) {
-            a.seg_out[r] = 0;
-            a.nsh_out[r] = 0;
+            q.seg_out[r] = 0;
+            q.nsh_out[r] = 0;
         }
-        return;
+        return false;
     }
     if (tid == 0) {
         q_out = 0;
@@ -485,71 +510,37 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_sha
         q_dead = 0;
         q_done = 0;
     }
-    const Tables tb = TABS ? wf_tables_lds(a.sc, tab_lds, T) : global_tables(a.sc);
-    __syncthreads();  // the only barrier
-    float4 *Lh = reinterpret_cast<float4 *>(a.Lhome);
-    // ---- shadow rays of paths that ended at the previous bounce: L = fma(A, B, L) on the radiance record
-    for (uint32_t k = tid; k < n_dead; k += T) {
-        const float4 *rec = a.shd_in + (base + WF_REGION - n_dead + k);
-        const float4 A = rec[2u * (size_t)a.cap], B = rec[3u * (size_t)a.cap];
-        if (A.w != 0.0f) {
-            float4 *Lp = Lh + __float_as_uint(B.w);
-            float4 Lv = *Lp;
-            Lv.x = fma_(A.x, B.x, Lv.x);
-            Lv.y = fma_(A.y, B.y, Lv.y);
-            Lv.z = fma_(A.z, B.z, Lv.z);
-            *Lp = Lv;
-        }
-    }
+    m.stage();
+    __syncthreads();  // the walk's only barrier
+    // ---- rays of paths that ended at the previous bounce
+    for (uint32_t k = tid; k < n_dead; k += T) m.dead_record(base + WF_REGION - n_dead + k);
     uint32_t list_n = 0;             // wave-uniform: entries on this wave's list
     uint32_t n_seg_w = 0, n_shd_w = 0;
     uint32_t c0 = wid * 64u;         // the wave's next chunk of the region
     for (;;) {
         if (c0 < cnt_in) {
-            // ---- WF_SHADE_CHUNKS chunks of hit records: paths whose ray left the scene end here, the others go on the list.  One
-            // batch of loads: the hit indices and (bounces >= 1) the three state planes a path that ends needs.
+            // ---- WF_SHADE_CHUNKS chunks of hit records, one batch of loads: the hit indices and the mode's planes
             uint32_t hidv[NCH];
-            float4 q3v[NCH], q4v[NCH], q5v[NCH];
+            typename M::Chunk ch[NCH];
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 const uint32_t s = c0 + (uint32_t)j * (W * 64u) + lane;
                 hidv[j] = 0xffffffffu;
-                q3v[j] = q4v[j] = q5v[j] = float4{0, 0, 0, 0};
-                if (s < cnt_in) {
-                    hidv[j] = a.hit_id[base + s];
-                    if (!FIRST) {
-                        const float4 *stp = a.st_in + (base + s);
-                        const size_t cp = a.cap;
-                        q3v[j] = stp[3u * cp];
-                        q4v[j] = stp[4u * cp];
-                        q5v[j] = stp[5u * cp];
-                    }
-                }
+                ch[j] = typename M::Chunk{};
+                if (s < cnt_in) hidv[j] = m.load(base + s, ch[j]);
             }
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 const uint32_t s = c0 + (uint32_t)j * (W * 64u) + lane;
-                const bool valid = s < cnt_in;
                 const uint32_t hid = hidv[j];
-                const float4 q3 = q3v[j], q4 = q4v[j], q5 = q5v[j];
                 const bool is_hit = hid != 0xffffffffu;
-                float4 Lv = q3;
-                if (!FIRST && q4.w != 0.0f) {  // its shadow ray of the previous bounce got through
-                    Lv.x = fma_(q4.x, q5.x, Lv.x);
-                    Lv.y = fma_(q4.y, q5.y, Lv.y);
-                    Lv.z = fma_(q4.z, q5.z, Lv.z);
-                }
-                if (valid && !is_hit) {
-                    float4 rec = Lv;
-                    rec.w = 0.0f;
-                    Lh[FIRST ? base + s : __float_as_uint(q3.w)] = rec;
-                }
+                m.entry(base + s, s < cnt_in, is_hit, ch[j]);
                 const unsigned long long bh = __ballot(is_hit);
                 if (is_hit) {
-                    const uint32_t e = list_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(bh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bh, 0u));
+                    const uint32_t e = list_n + ballot_rank(bh);
                     wlist[wid][e] = s;
                     wprim[wid][e] = hid;
-                    if (!FIRST) wlh[wid][e] = Lv;  // (L with the pending contribution, home in .w)
+                    m.keep(e, ch[j]);
                 }
                 list_n += (uint32_t)__popcll(bh);
             }
@@ -562,158 +553,229 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_sha
         // ---- shade 64 listed paths (or what is left at the end) with every lane busy; the list is emptied below 64 entries before
         // the wave reads its next chunks (the list holds 64 x (WF_SHADE_CHUNKS + 1))
         for (;;) {
-        const uint32_t take = min(list_n, 64u);
-        const bool act = lane < take;
-        list_n -= take;
-        bool survive = false;
-        WfShadow sh;
-        sh.on = false;
+            const uint32_t take = min(list_n, 64u);
+            const bool act = lane < take;
+            list_n -= take;
+            bool survive = false;
+            typename M::Path p;
+            if (act) survive = m.shade(base + wlist[wid][list_n + lane], wprim[wid][list_n + lane], list_n + lane, p);
+            n_seg_w += take;
+            // survivors -> front of the region of the `out` state
+            const unsigned long long bs = __ballot(survive);
+            uint32_t out_slot = 0;
+            if (bs) out_slot = base + ballot_reserve(&q_out, bs, lane);
+            const bool shd_live = m.pending(p) && survive, shd_dead = m.pending(p) && !survive;
+            if (survive)
+                m.put_survivor(out_slot, p, shd_live);
+            else if (act)
+                m.end_path(p);
+            const unsigned long long bl = __ballot(shd_live);
+            if (bl) {  // their rays -> front of the region's records
+                const uint32_t k = base + ballot_reserve(&q_shd, bl, lane);
+                n_shd_w += (uint32_t)__popcll(bl);
+                if (shd_live) m.put_ray(k, out_slot, p);
+            }
+            const unsigned long long bd = __ballot(shd_dead);
+            if (bd) {  // rays of paths that ended at this bounce -> back of the region's records
+                const uint32_t k = base + WF_REGION - 1u - ballot_reserve(&q_dead, bd, lane);
+                n_shd_w += (uint32_t)__popcll(bd);
+                if (shd_dead) m.put_dead_ray(k, p);
+            }
+            if (list_n < 64u && c0 < cnt_in) break;  // room for the next chunks
+            if (list_n == 0u) break;
+        }
+    }
+    if (lane == 0) {
+        unsigned long long *row = u.stats + (size_t)r * W + wid;  // per-wave statistics rows
+        const size_t stride = u.stat_stride;
+        m.stats(row, stride, n_seg_w, n_shd_w);
+        if (wid == 0) row[(2 + min(u.depth, (uint32_t)MAX_DEPTH_STATS - 1)) * stride] += cnt_in;
+        // the last wave to finish publishes the region's counts (LDS atomics of one CU are ordered)
+        if (atomicAdd(&q_done, 1u) == W - 1) {
+            q.seg_out[r] = atomicAdd(&q_out, 0u);
+            q.nsh_out[r] = atomicAdd(&q_shd, 0u) | (atomicAdd(&q_dead, 0u) << 16);
+        }
+    }
+    return true;
+}
+
+// ---- k_shade ---------------------------------------------------------------------------------------------------------------
+// TABS: the small tables fit LDS (wf_tables_lds), else everything is read from global memory.  CYL: the scene holds cylinders
+// GLOSSY: the scene holds a ROUGHCONDUCTOR / CONDUCTOR_FRESNEL material; instantiated with the cylinder code only (CYL = true).
+// wlh (bounces >= 1): a listed path's radiance so far with the pending shadow contribution folded in, and its home: the chunk phase
+// streams the L / A / B planes of EVERY path of the chunk anyway (a path that missed needs them to end), so a path that hit keeps what
+// they amount to -- L = fma(A, B, L), home -- on the list instead of gathering the three planes again in the shading step:
+// 48 of the 96 gathered bytes per hit, at 128-byte lines for 16-byte records (round 4: traffic 1.25 x the model)
+template <bool FIRST, bool TABS, bool CYL, bool GLOSSY>
+struct RadShade {
+    struct Chunk {
+        float4 q3, q4, q5;  // (L, home), (A, visibility of the previous bounce's shadow ray), (B, -)
+    };
+    struct Path {
         V3 o = {0, 0, 0}, d = {0, 0, 1}, thr = {1, 1, 1}, L = {0, 0, 0};
         float eta = 1.0f, prev_pdf = -1.0f;
         uint32_t home = 0;
-        if (act) {
-            const uint32_t s = wlist[wid][list_n + lane];
-            Hit h;
-            h.prim = wprim[wid][list_n + lane];
-            h.slot = h.prim;
-            // one batch of loads: the primitive's record, its vertex normals, the path state.  (t, u, v) of the hit are not carried
-            // through memory: k_trace hands over the primitive it found, and the test of THAT primitive against the ray is repeated
-            // here -- the same arithmetic on the same operands (a leaf record is the first nine floats of this record), so the same
-            // bits, for 60 VALU instructions of a kernel that waits on HBM instead of a 16-byte record written scattered (a 32-byte
-            // sector each) and gathered back (a 128-byte line each at the later bounces).
-            const pbrt_prim P = wf_load_prim(tb.prims_by_slot + h.slot);
-            const bool has_vn = a.sc.vnormals != nullptr;  // uniform
-            WfVn vn;
-            if (has_vn) vn = wf_load_vn(a.sc.vnormals, h.slot);
-            uint32_t ka, kb;
-            if (FIRST) {
-                float tm;
-                home = base + s;
-                wf_camera_ray(a, home, &o, &d, &tm, &ka, &kb);
-            } else {
-                const float4 *stp = a.st_in + (base + s);
-                const size_t cp = a.cap;
-                const float4 q0 = stp[0], q1 = stp[cp], q2 = stp[2u * cp];
-                const float4 lh = wlh[FIRST ? 0 : wid][FIRST ? 0 : list_n + lane];  // L (pending shadow contribution included), home
-                o = {q0.x, q0.y, q0.z};
-                d = {q1.x, q1.y, q1.z};
-                thr = {q2.x, q2.y, q2.z};
-                L = {lh.x, lh.y, lh.z};
-                eta = (a.key_mode == 1 && a.depth == 0) ? 1.0f : q0.w;  // caller rays carry tmax in the eta slot
-                prev_pdf = q1.w;
-                home = __float_as_uint(lh.w);
-                uint32_t px, py;
-                const RadArgs ra = wf_key_args(a);
-                path_key<true>(ra, home, &ka, &kb, &px, &py);
-            }
-            // (t, u, v) of the hit k_trace found: the same test on the same operands (a leaf record is the first nine floats of P).
-            // Should the repetition ever disagree (other build flags, another code path for the primitive) the call fails with
-            // PBRT_E_DEVICE instead of shading with whatever the registers held: guard word WF_GUARD_REHIT counts the cases.
-            h.t = K_INF;
-            h.u = h.v = 0.0f;
-            if (!prim_hit<CYL>(P, o, d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(a.guard + WF_GUARD_REHIT, 1u);
-            const SI si = make_si<true, CYL>(P, o, d, h.t, h.u, h.v, has_vn, [&](int k) { return vn.n[k]; });
-            // the bounce's arithmetic (kernels_radiance.h shade_step), its shadow segment handed out instead of traced
-            survive = shade_step<GLOSSY>(
-                a, tb, a.depth, ka, kb, h.t, P, si, o, d, thr, L, eta, prev_pdf,
-                [&](V3 so, V3 sdir, float smax) {
-                    sh.on = true;
-                    sh.so = so;
-                    sh.sdir = sdir;
-                    sh.tmax = smax;
-                    return true;
-                },
-                [&](V3 A, V3 B) {
-                    sh.A = A;
-                    sh.B = B;
-                });
+        WfShadow sh;
+    };
+    const WfArgs a;
+    uint32_t *tab_lds;
+    float4 *wlh;  // this wave's row
+    float4 *Lh;
+    Tables tb;
+
+    DEV void stage() { tb = TABS ? wf_tables_lds(a.sc, tab_lds, WF_SHADE_THREADS) : global_tables(a.sc); }
+    DEV void dead_record(uint32_t i) const {  // L = fma(A, B, L) on the radiance record
+        const float4 *rec = a.shd_in + i;
+        const float4 A = rec[2u * (size_t)a.cap], B = rec[3u * (size_t)a.cap];
+        if (A.w != 0.0f) {
+            float4 *Lp = Lh + __float_as_uint(B.w);
+            float4 Lv = *Lp;
+            Lv.x = fma_(A.x, B.x, Lv.x);
+            Lv.y = fma_(A.y, B.y, Lv.y);
+            Lv.z = fma_(A.z, B.z, Lv.z);
+            *Lp = Lv;
         }
-        n_seg_w += take;
-        // survivors -> front of the region of the `out` state
-        const unsigned long long bs = __ballot(survive);
-        uint32_t out_slot = 0;
-        if (bs) {
-            uint32_t got = 0;
-            if (lane == 0) got = atomicAdd(&q_out, (uint32_t)__popcll(bs));
-            const uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
-            out_slot = base + off + __builtin_amdgcn_mbcnt_hi((uint32_t)(bs >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bs, 0u));
-        }
-        const bool shd_live = sh.on && survive, shd_dead = sh.on && !survive;
-        if (survive) {
-            float4 *stp = a.st_out + out_slot;
+    }
+    DEV uint32_t load(uint32_t slot, Chunk &c) const {
+        const uint32_t hid = a.hit_id[slot];
+        if (!FIRST) {  // the three state planes a path that ends needs
+            const float4 *stp = a.st_in + slot;
             const size_t cp = a.cap;
-            const float4 q0 = {o.x, o.y, o.z, eta}, q1 = {d.x, d.y, d.z, prev_pdf}, q2 = {thr.x, thr.y, thr.z, 0.0f},
-                         q3 = {L.x, L.y, L.z, __uint_as_float(home)};
-            stp[0] = q0;
-            stp[cp] = q1;
-            stp[2u * cp] = q2;
-            stp[3u * cp] = q3;
-            const float4 q4 = {shd_live ? sh.A.x : 0.0f, shd_live ? sh.A.y : 0.0f, shd_live ? sh.A.z : 0.0f, 0.0f},
-                         q5 = {shd_live ? sh.B.x : 0.0f, shd_live ? sh.B.y : 0.0f, shd_live ? sh.B.z : 0.0f, 0.0f};
-            stp[4u * cp] = q4;
-            stp[5u * cp] = q5;
-        } else if (act) {  // the path ends (a pending shadow ray is added to this record by the next k_shade)
-            const float4 rec = {L.x, L.y, L.z, 0.0f};
+            c.q3 = stp[3u * cp];
+            c.q4 = stp[4u * cp];
+            c.q5 = stp[5u * cp];
+        }
+        return hid;
+    }
+    DEV void entry(uint32_t slot, bool valid, bool is_hit, Chunk &c) const {
+        const uint32_t home = FIRST ? slot : __float_as_uint(c.q3.w);
+        if (!FIRST && c.q4.w != 0.0f) {  // its shadow ray of the previous bounce got through
+            c.q3.x = fma_(c.q4.x, c.q5.x, c.q3.x);
+            c.q3.y = fma_(c.q4.y, c.q5.y, c.q3.y);
+            c.q3.z = fma_(c.q4.z, c.q5.z, c.q3.z);
+        }
+        if (valid && !is_hit) {  // the ray left the scene: the path ends
+            float4 rec = c.q3;
+            rec.w = 0.0f;
             Lh[home] = rec;
         }
-        const unsigned long long bl = __ballot(shd_live);
-        if (bl) {
-            uint32_t got = 0;
-            if (lane == 0) got = atomicAdd(&q_shd, (uint32_t)__popcll(bl));
-            const uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
-            n_shd_w += (uint32_t)__popcll(bl);
-            if (shd_live) {
-                const uint32_t k = base + off + __builtin_amdgcn_mbcnt_hi((uint32_t)(bl >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bl, 0u));
-                float4 *rec = a.shd_out + k;
-                const float4 q0 = {sh.so.x, sh.so.y, sh.so.z, sh.tmax}, q1 = {sh.sdir.x, sh.sdir.y, sh.sdir.z, __uint_as_float(out_slot)};
-                rec[0] = q0;
-                rec[a.cap] = q1;
-            }
-        }
-        const unsigned long long bd = __ballot(shd_dead);
-        if (bd) {  // rare: Russian roulette ended a path that had just sent a shadow ray
-            uint32_t got = 0;
-            if (lane == 0) got = atomicAdd(&q_dead, (uint32_t)__popcll(bd));
-            const uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
-            n_shd_w += (uint32_t)__popcll(bd);
-            if (shd_dead) {
-                const uint32_t k =
-                    base + WF_REGION - 1u - (off + __builtin_amdgcn_mbcnt_hi((uint32_t)(bd >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bd, 0u)));
-                float4 *rec = a.shd_out + k;
-                const size_t cp = a.cap;
-                const float4 q0 = {sh.so.x, sh.so.y, sh.so.z, sh.tmax},
-                             q1 = {sh.sdir.x, sh.sdir.y, sh.sdir.z, __uint_as_float(WF_DEAD | k)},
-                             q2 = {sh.A.x, sh.A.y, sh.A.z, 0.0f}, q3 = {sh.B.x, sh.B.y, sh.B.z, __uint_as_float(home)};
-                rec[0] = q0;
-                rec[cp] = q1;
-                rec[2u * cp] = q2;
-                rec[3u * cp] = q3;
-            }
-        }
-        if (list_n < 64u && c0 < cnt_in) break;  // room for the next chunks
-        if (list_n == 0u) break;
-        }  // shading steps
     }
-    if (lane == 0) {
-        unsigned long long *row = a.stats + (size_t)r * W + wid;  // per-wave statistics rows
-        const size_t stride = a.stat_stride;
-        row[0] += n_seg_w;
-        row[stride] += n_shd_w;
-        row[(HIT_ROW0 + min(a.depth, (uint32_t)MAX_DEPTH_STATS - 1)) * stride] += n_seg_w;  // hits of this depth (byte model)
-        if (wid == 0) row[(2 + min(a.depth, (uint32_t)MAX_DEPTH_STATS - 1)) * stride] += cnt_in;
-        // the last wave to finish publishes the region's counts (LDS atomics of one CU are ordered)
-        if (atomicAdd(&q_done, 1u) == W - 1) {
-            a.seg_out[r] = atomicAdd(&q_out, 0u);
-            a.nsh_out[r] = atomicAdd(&q_shd, 0u) | (atomicAdd(&q_dead, 0u) << 16);
-        }
+    DEV void keep(uint32_t e, const Chunk &c) const {
+        if (!FIRST) wlh[e] = c.q3;  // (L with the pending contribution, home in .w)
     }
+    DEV bool shade(uint32_t slot, uint32_t prim, uint32_t e, Path &p) const {
+        Hit h;
+        h.prim = prim;
+        h.slot = h.prim;
+        // one batch of loads: the primitive's record, its vertex normals, the path state.  (t, u, v) of the hit are not carried
+        // through memory: k_trace hands over the primitive it found, and the test of THAT primitive against the ray is repeated
+        // here -- the same arithmetic on the same operands (a leaf record is the first nine floats of this record), so the same
+        // bits, for 60 VALU instructions of a kernel that waits on HBM instead of a 16-byte record written scattered (a 32-byte
+        // sector each) and gathered back (a 128-byte line each at the later bounces).
+        const pbrt_prim P = wf_load_prim(tb.prims_by_slot + h.slot);
+        const bool has_vn = a.sc.vnormals != nullptr;  // uniform
+        WfVn vn;
+        if (has_vn) vn = wf_load_vn(a.sc.vnormals, h.slot);
+        uint32_t ka, kb;
+        if (FIRST) {
+            float tm;
+            p.home = slot;
+            wf_camera_ray(a, p.home, &p.o, &p.d, &tm, &ka, &kb);
+        } else {
+            const float4 *stp = a.st_in + slot;
+            const size_t cp = a.cap;
+            const float4 q0 = stp[0], q1 = stp[cp], q2 = stp[2u * cp];
+            const float4 lh = wlh[FIRST ? 0 : e];  // L (pending shadow contribution included), home
+            p.o = {q0.x, q0.y, q0.z};
+            p.d = {q1.x, q1.y, q1.z};
+            p.thr = {q2.x, q2.y, q2.z};
+            p.L = {lh.x, lh.y, lh.z};
+            p.eta = (a.key_mode == 1 && a.depth == 0) ? 1.0f : q0.w;  // caller rays carry tmax in the eta slot
+            p.prev_pdf = q1.w;
+            p.home = __float_as_uint(lh.w);
+            uint32_t px, py;
+            const RadArgs ra = wf_key_args(a);
+            path_key<true>(ra, p.home, &ka, &kb, &px, &py);
+        }
+        // (t, u, v) of the hit k_trace found: the same test on the same operands (a leaf record is the first nine floats of P).
+        // Should the repetition ever disagree (other build flags, another code path for the primitive) the call fails with
+        // PBRT_E_DEVICE instead of shading with whatever the registers held: guard word WF_GUARD_REHIT counts the cases.
+        h.t = K_INF;
+        h.u = h.v = 0.0f;
+        if (!prim_hit<CYL>(P, p.o, p.d, K_INF, &h.t, &h.u, &h.v)) atomicAdd(a.guard + WF_GUARD_REHIT, 1u);
+        const SI si = make_si<true, CYL>(P, p.o, p.d, h.t, h.u, h.v, has_vn, [&](int k) { return vn.n[k]; });
+        // the bounce's arithmetic (kernels_radiance.h shade_step), its shadow segment handed out instead of traced
+        return shade_step<GLOSSY>(
+            a, tb, a.depth, ka, kb, h.t, P, si, p.o, p.d, p.thr, p.L, p.eta, p.prev_pdf,
+            [&](V3 so, V3 sdir, float smax) {
+                p.sh.on = true;
+                p.sh.so = so;
+                p.sh.sdir = sdir;
+                p.sh.tmax = smax;
+                return true;
+            },
+            [&](V3 A, V3 B) {
+                p.sh.A = A;
+                p.sh.B = B;
+            });
+    }
+    DEV static bool pending(const Path &p) { return p.sh.on; }
+    DEV void put_survivor(uint32_t out_slot, const Path &p, bool shd_live) const {
+        float4 *stp = a.st_out + out_slot;
+        const size_t cp = a.cap;
+        const WfShadow &sh = p.sh;
+        const float4 q0 = {p.o.x, p.o.y, p.o.z, p.eta}, q1 = {p.d.x, p.d.y, p.d.z, p.prev_pdf}, q2 = {p.thr.x, p.thr.y, p.thr.z, 0.0f},
+                     q3 = {p.L.x, p.L.y, p.L.z, __uint_as_float(p.home)};
+        stp[0] = q0;
+        stp[cp] = q1;
+        stp[2u * cp] = q2;
+        stp[3u * cp] = q3;
+        const float4 q4 = {shd_live ? sh.A.x : 0.0f, shd_live ? sh.A.y : 0.0f, shd_live ? sh.A.z : 0.0f, 0.0f},
+                     q5 = {shd_live ? sh.B.x : 0.0f, shd_live ? sh.B.y : 0.0f, shd_live ? sh.B.z : 0.0f, 0.0f};
+        stp[4u * cp] = q4;
+        stp[5u * cp] = q5;
+    }
+    DEV void end_path(const Path &p) const {  // (a pending shadow ray is added to this record by the next k_shade)
+        const float4 rec = {p.L.x, p.L.y, p.L.z, 0.0f};
+        Lh[p.home] = rec;
+    }
+    DEV void put_ray(uint32_t k, uint32_t out_slot, const Path &p) const {
+        const WfShadow &sh = p.sh;
+        float4 *rec = a.shd_out + k;
+        const float4 q0 = {sh.so.x, sh.so.y, sh.so.z, sh.tmax}, q1 = {sh.sdir.x, sh.sdir.y, sh.sdir.z, __uint_as_float(out_slot)};
+        rec[0] = q0;
+        rec[a.cap] = q1;
+    }
+    DEV void put_dead_ray(uint32_t k, const Path &p) const {  // rare: Russian roulette ended a path that had just sent a shadow ray
+        const WfShadow &sh = p.sh;
+        float4 *rec = a.shd_out + k;
+        const size_t cp = a.cap;
+        const float4 q0 = {sh.so.x, sh.so.y, sh.so.z, sh.tmax}, q1 = {sh.sdir.x, sh.sdir.y, sh.sdir.z, __uint_as_float(WF_DEAD | k)},
+                     q2 = {sh.A.x, sh.A.y, sh.A.z, 0.0f}, q3 = {sh.B.x, sh.B.y, sh.B.z, __uint_as_float(p.home)};
+        rec[0] = q0;
+        rec[cp] = q1;
+        rec[2u * cp] = q2;
+        rec[3u * cp] = q3;
+    }
+    DEV void stats(unsigned long long *row, size_t stride, uint32_t n_seg, uint32_t n_rays) const {
+        row[0] += n_seg;
+        row[stride] += n_rays;
+        row[(HIT_ROW0 + min(a.depth, (uint32_t)MAX_DEPTH_STATS - 1)) * stride] += n_seg;  // hits of this depth (byte model)
+    }
+};
+template <bool FIRST, bool TABS, bool CYL, bool GLOSSY = false>
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES_PER_EU) void k_shade(const WfArgs a) {
+    __shared__ float4 wlh[FIRST ? 1 : WF_SHADE_THREADS / 64][FIRST ? 1 : WF_SHADE_LIST];
+    __shared__ uint32_t tab_lds[TABS ? WF_TAB_DW : 1];
+    RadShade<FIRST, TABS, CYL, GLOSSY> m = {a, tab_lds, wlh[FIRST ? 0 : threadIdx.x >> 6], reinterpret_cast<float4 *>(a.Lhome)};
+    shade_walk<FIRST>(a, a, m);
 }
 
 // upload of caller rays for Integrator.sample(): o, d [3][n] SoA + tmax -> path-state records (tmax rides in the eta slot)
 __global__ __launch_bounds__(256) void k_init_rays_wf(float4 *st, uint32_t cap, uint32_t *seg_cnt, uint32_t n_regions, uint32_t n,
                                                       const float *o, const float *d, const float *tmax) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_regions) seg_cnt[i] = n > i * WF_REGION ? min(n - i * WF_REGION, WF_REGION) : 0u;
+    if (i < n_regions) seg_cnt[i] = n > i * WF_REGION ? min(n - i * WF_REGION, WF_REGION) : 0u;  // (wf_region_fill, spelled out: the call compiles to another instruction order)
     if (i >= n) return;
     float4 *s = st + i;
     const size_t cp = cap;

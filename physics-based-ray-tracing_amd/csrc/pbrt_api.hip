@@ -898,6 +898,21 @@ struct WfPing {
         std::swap(sin, sout);
         std::swap(ni, no);
     }
+    // the stream members of a launch's arguments (WfArgs, UsWfArgs) in the current roles, over n regions from region0 on
+    template <class A>
+    void bind(A &a, const WfBufs &b, bool have_shadows, uint32_t region0, uint32_t n_regions) const {
+        a.st_in = in;
+        a.st_out = out;
+        a.hit_id = b.hit_id;
+        a.shd_in = shi;
+        a.shd_out = sho;
+        a.seg_in = sin;
+        a.seg_out = sout;
+        a.nsh_in = have_shadows ? ni : nullptr;
+        a.nsh_out = no;
+        a.region0 = region0;
+        a.n_regions = n_regions;
+    }
 };
 // the tree and stack members of a k_trace launch, and the guard words (false: out of memory)
 static bool wf_tree_args(pbrt_scene *s, const WfPlan &p, WfArgs *a) {
@@ -999,17 +1014,7 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
     WfPing pp(b);
     auto fill = [&](uint32_t depth, bool have_shadows, uint32_t h) {
         a.depth = depth;
-        a.st_in = pp.in;
-        a.st_out = pp.out;
-        a.hit_id = b.hit_id;
-        a.shd_in = pp.shi;
-        a.shd_out = pp.sho;
-        a.seg_in = pp.sin;
-        a.seg_out = pp.sout;
-        a.nsh_in = have_shadows ? pp.ni : nullptr;
-        a.nsh_out = pp.no;
-        a.region0 = reg0[h];
-        a.n_regions = regn[h];
+        pp.bind(a, b, have_shadows, reg0[h], regn[h]);
     };
     auto trace = [&](uint32_t depth, bool first, bool have_shadows, uint32_t h) {
         fill(depth, have_shadows, h);
@@ -1883,36 +1888,20 @@ static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p,
     t.n_paths = a.n_paths;
     t.key_mode = 0;
     t.vis_q = US_WF_VIS_Q;
-    t.hit_id = b.hit_id;
-    t.region0 = 0;
-    t.n_regions = nreg;
     if (!wf_tree_args(s, p, &t)) return PBRT_E_NOMEM;
     UsWfArgs w{};
-    w.hit_id = b.hit_id;
-    w.region0 = 0;
-    w.n_regions = nreg;
     w.guard = t.guard;
     WfPing pp(b);
     auto trace = [&](uint32_t depth, bool have_shadows) {
         t.depth = depth;
-        t.st_in = pp.in;
-        t.shd_in = pp.shi;
-        t.seg_in = pp.sin;
-        t.nsh_in = have_shadows ? pp.ni : nullptr;
+        pp.bind(t, b, have_shadows, 0, nreg);
         wf_launch_trace(s, t, p, wf_trace_grid(nreg, depth >= 2 ? p.grid_deep : p.grid_mult, (uint32_t)c->n_cu), false, st);
         ++*launches;
     };
     auto shade = [&](uint32_t depth, bool tab, bool have_shadows) {
         a.depth = depth;
         w.u = a;
-        w.st_in = pp.in;
-        w.st_out = pp.out;
-        w.shd_in = pp.shi;
-        w.shd_out = pp.sho;
-        w.seg_in = pp.sin;
-        w.seg_out = pp.sout;
-        w.nsh_in = have_shadows ? pp.ni : nullptr;
-        w.nsh_out = pp.no;
+        pp.bind(w, b, have_shadows, 0, nreg);
         hipLaunchKernelGGL(us_shade_kernel(s, tab, convex), dim3(nreg), dim3(WF_SHADE_THREADS), 0, st, w);
         ++*launches;
     };

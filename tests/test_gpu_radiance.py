@@ -175,6 +175,25 @@ def test_bvh_scene_depth_budgets(mi, ob, max_depth):
         assert st["bounce_launches"] == 2 * max_depth
 
 
+@pytest.mark.parametrize("w,h", [(1, 1), (8, 8), (65, 63), (64, 64), (17, 241), (23, 359)])
+def test_bvh_streams_at_the_edges_of_a_region(mi, ob, w, h):
+    """the scaffold k_shade shares with k_us_shade (shade_walk) at the path counts where it can go wrong, one sample per pixel and
+    regions of 4096 slots: a single lane (1 path), one chunk (64), one slot short of a region (4095), exactly one region (4096), a
+    second region with one path (4097: three of its four waves find no chunk on entry) and two full regions plus one chunk and one
+    lane (8257).  max_depth 8 lies beyond rr_depth, so Russian roulette ends paths that have just sent a shadow ray: the records at
+    the back of a region.  Box filter: the rendered region is the film."""
+    sc = mi.load_file(scene_path("testring.xml"), res=64, spp=1, max_depth=8)
+    film = sc.sensors()[0].film()
+    film.width, film.height, film.crop = w, h, (0, 0, w, h)
+    film.rfilter = mi.ReconstructionFilter(mi.Properties("box"))
+    img = mi.render(sc, seed=5)
+    st = mi.default_context().stats()
+    ref, _ = oracle_render(ob, sc, 5, 1)
+    assert img.shape == (h, w, 3) and np.array_equal(img, ref)
+    assert st["bounce_launches"] == 2 * 8      # no poll at a budget of 32 bounces or fewer: k_trace + k_shade per bounce
+    assert img.mean() > 0 or w * h < 4095
+
+
 def test_material_update_reaches_the_device(mi, ob):
     sc = mi.load_file(scene_path("cbox.xml"), res=24, spp=4)
     a = mi.render(sc, seed=0)

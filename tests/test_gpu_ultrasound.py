@@ -306,6 +306,28 @@ def test_mesh_phantoms_as_streams_and_as_the_fused_bounce(mi, ob, capi, scene, k
     assert st_f["bounce_launches"] == 1 and st_f["segments"] == st["segments"] and list(st_f["live"]) == list(st["live"])
 
 
+@pytest.mark.parametrize("ppr", [8, 511, 512, 513, 1032])
+def test_mesh_phantom_streams_at_the_edges_of_a_region(mi, ob, capi, ppr):
+    """the scaffold k_us_shade shares with k_shade (kernels_wavefront.h shade_walk) at the path counts where it can go wrong: 8
+    elements x one angle x ppr paths are 64 (one chunk), 4088, 4096 (exactly one region of 4096 slots), 4104 (a second region of
+    one short chunk) and 8256 paths (two regions plus one chunk); ppr >= the elements, so the first-bounce tables exist.  With and
+    without the tables: equal to the oracle, the same segments and live counts.  (Seed and time_samples chosen on the oracle alone:
+    39 non-zero bins at 64 paths, 62 at the others, and 11364 ... 22954 segments for 4088 ... 8256 paths: bounces beyond the first.)"""
+    sc = uu.phantom(mi, "bvh", n_elements=8, angles=[0.0], time_samples=2048, ppr=ppr, seed=3, max_depth=4)
+    ui = sc.integrator()
+    ref, _, tol = oracle(ob, sc, ui.us_params(sc), 3, ppr)
+    assert np.count_nonzero(ref) > 0
+    buf = ui._acquire(sc, ui.quirks)
+    st = mi.default_context().stats()
+    check(buf, ref, tol)
+    assert st["bounce_launches"] == 1 + 2 * (ui.max_depth - 1) + 2
+    no_tab = ui._acquire(sc, ui.quirks | capi.USQ_NO_FIRST_TABLES)
+    st_nt = mi.default_context().stats()
+    check(no_tab, ref, tol)
+    assert st_nt["bounce_launches"] == 2 * ui.max_depth + 2 and st_nt["segments"] == st["segments"] and list(st_nt["live"]) == list(st["live"])
+    assert st["live"][1] > 0 or 8 * ppr < 4088
+
+
 @pytest.mark.parametrize("case", ["intent", "drjit", "depth1", "depth2_no_tables", "pulse"])
 def test_mesh_phantom_variants_of_the_acquisition_loop(mi, ob, capi, case):
     """the stream kernels (k_trace + k_us_shade) under the switches of the acquisition loop, on the ring phantom, against the oracle:
