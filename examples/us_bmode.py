@@ -2,13 +2,16 @@
 """The reference's ultrasound driver flow on this library: scene dict -> acquisition -> delay-and-sum -> envelope ->
 log compression -> finite-difference roughness loop (what USMain.py does at :26-90, :93-224, :257-289), without the
 plotting.  Writes the B-mode image and the channel buffer as .npy.
-    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [out_dir]
+    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [--iq [--decimation D]] [out_dir]
 --convex: the same flow under a curved (abdominal) array -- 64 elements on a 40 mm arc of 40 degrees (DESIGN D18); the sensor
 transform puts the apex where the linear array sits, and the scan is given in the sensor's frame, whose origin is the centre of
 curvature.
 --beamformer: delay-and-sum (default), p-DAS (--p, default 2) or F-DMAS (DESIGN D19).  The non-linear beamformers band-pass their
 image along z, around the carrier (p-DAS) or twice the carrier (F-DMAS): the reference's lambda / 4 grid puts the axial Nyquist
-frequency AT the carrier, so the example picks lambda / 8 for p-DAS and lambda / 16 for F-DMAS itself and says so."""
+frequency AT the carrier, so the example picks lambda / 8 for p-DAS and lambda / 16 for F-DMAS itself and says so.
+--iq: the I/Q chain (DESIGN D20) -- the channel data are demodulated at the carrier and decimated by --decimation (default 4: 50 MHz ->
+12.5 MHz), delay-and-sum runs on complex samples and the envelope is the modulus of each pixel, which needs no carrier on the grid: the
+example then scans at lambda / 2 axially.  Delay-and-sum only."""
 import argparse
 import os
 import sys
@@ -25,8 +28,12 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--convex", action="store_true")
 ap.add_argument("--beamformer", choices=("das", "pdas", "fdmas"), default="das")
 ap.add_argument("--p", type=float, default=2.0)
+ap.add_argument("--iq", action="store_true")
+ap.add_argument("--decimation", type=int, default=4)
 ap.add_argument("out_dir", nargs="?", default=".")
 args = ap.parse_args()
+if args.iq and args.beamformer != "das":
+    ap.error("--iq takes delay-and-sum: the non-linear beamformers are defined on RF data (DESIGN D19)")
 convex, out_dir = args.convex, args.out_dir
 T = mi.ScalarTransform4f
 RADIUS = 0.04 if convex else 0.0            # centre of curvature RADIUS behind the apex; the scan's z is measured from it
@@ -55,6 +62,10 @@ beamformer = {"das": lambda: mi.DelayAndSum(), "pdas": lambda: mi.PDelayAndSum(p
               "fdmas": lambda: mi.FilteredDelayMultiplyAndSum()}[args.beamformer]()
 step = {"das": lam / 4, "pdas": lam / 8, "fdmas": lam / 16}[args.beamformer]
 RENDER = dict(x_range=(-0.02, 0.02), z_range=Z_RANGE, step=step, beamformer=beamformer)
+if args.iq:
+    RENDER.update(iq=True, decimation=args.decimation, step=lam / 2)
+    print(f"I/Q chain: demodulated at {integ.frequency / 1e6:.1f} MHz, {integ.fs / 1e6:.0f} -> {integ.fs / args.decimation / 1e6:.2f} MHz, "
+          f"scan step lambda / 2 = {lam / 2 * 1e6:.0f} um (the Hilbert envelope of the RF chain needs lambda / 4 or finer)")
 if args.beamformer != "das":
     f_lo, f_hi = beamformer.band(mi.build_probe("linear", 64, 1.2e-4, integ.frequency, 70))
     print(f"{beamformer}: band {f_lo / 1e6:.2f} - {f_hi / 1e6:.2f} MHz needs an axial rate c / (2 step) above {2 * f_hi / 1e6:.2f} MHz; "

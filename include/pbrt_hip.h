@@ -620,6 +620,55 @@ int pbrt_bf_beamform_table_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const voi
 int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const float *taps, const float *in, float *out);
 int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *d_taps, const void *d_in, void *d_out);
 
+/* ---- I/Q beamforming: demodulation, complex delay-and-sum, modulus envelope ---------------------------------------
+ * The other half of ultraspy's users (`ultraspy.rf2iq`, `beamformer.set_is_iq(True)`, `compute_envelope` = the modulus; absent here as
+ * above, so this is the build's own definition).  Complex samples and pixels are interleaved (re, im) float pairs.
+ *
+ * pbrt_rf2iq.  Sample j of a trace x[0 .. time_samples) was taken at t_j = t0 + j / fs.  Mixing: phi_j = frac(demod_freq * t_j),
+ * evaluated in f64 and rounded to f32; u_j = x_j cospi(2 phi_j), v_j = -x_j sinpi(2 phi_j) in f32.  Low-pass and decimation by
+ * D = decimation: for m in [0, Td), Td = ceil(time_samples / D),
+ *   out[m] = 2 * ( sum_{k = -K .. K} taps[K + k] u[m D - k],  sum_k taps[K + k] v[m D - k] ),
+ * samples outside the trace zero, f32 multiply-adds in order of increasing k, the factor 2 last.  Output sample m belongs to time
+ * t0 + m D / fs.  in [n_traces][time_samples] floats, out [n_traces][Td] pairs, taps [2 K + 1] the caller's (as pbrt_axial_fir).
+ * PBRT_E_INVALID for time_samples == 0, decimation outside [1, 8], K > 1024, fs not finite and > 0, t0 not finite, a non-finite or
+ * negative demod_freq, and in / out overlapping.
+ *
+ * pbrt_iq_beamform.  data [n_angles][n_elements][time_samples] PAIRS at the rate das.fs (the I/Q rate), sample m at das.t0 + m / fs.
+ * The delayed sample s_{a,e} of a pixel is what pbrt_das_beamform adds -- the same first arrival t_tx(a), f64 position, range
+ * rules, f-number aperture of the line (probe = 0) or of the element table (probe = 1), nearest / linear interpolation (on both
+ * components, with the one f32 weight) -- and is turned back by the carrier phase of its delay, split into a receive and a
+ * transmit factor:
+ *   rot_e = exp(i 2 pi frac(demod_freq * d_e / c)),   rot_a = exp(i 2 pi frac(demod_freq * t_tx(a)))
+ *   (each frac in f64, rounded to f32, then sincospif of twice that),
+ *   q_a = sum_{e in U(a)} rot_e * s_{a,e},   out = sum_a rot_a * q_a,   divided by n_angles when compound_mean is set.
+ * A complex product (c, s) * (x, y) is (fmaf(c, x, -(s y)), fmaf(c, y, s x)) in f32.  Wave w = e % 4 sums its share of q_a per
+ * transmission, the four shares are added in wave order, then rot_a is applied and the transmissions are added in order of a.  out
+ * [nx][nz] pairs; a pixel that uses no element is exactly (0, 0).  demod_freq = 0 and zero imaginary parts give pbrt_das_beamform's
+ * sums in another order.  Everything pbrt_das_beamform refuses is refused, and a non-finite or negative demod_freq, and probe > 1.
+ *
+ * pbrt_iq_envelope.  env[i] = sqrtf(fmaf(re, re, im * im)) for the n pixels of an image: no transform, so no limit on nz and no
+ * column rule -- NaN and infinity propagate by this arithmetic, per pixel.  iq and env distinct.
+ *
+ * The _dev forms take device pointers (taps included), are queued on the context's stream and recordable like their RF neighbours;
+ * the table of pbrt_iq_beamform_table_dev is pbrt_das_first_arrival_dev's (or its _probe twin's), bit-equal to the direct form. */
+typedef struct pbrt_iq_params {
+    pbrt_das_params das; /* das.fs: the rate of the I/Q data */
+    float demod_freq;    /* Hz, finite and >= 0 */
+    uint32_t probe;      /* 0: element positions [n_elements]; 1: the element table [n_elements][4] of pbrt_us_array_elements */
+} pbrt_iq_params;
+int pbrt_iq_beamform(pbrt_ctx *ctx, const pbrt_iq_params *p, const float *iq, const float *tx_delays, const float *elem,
+                     const float *x, const float *z, float *out);
+int pbrt_iq_beamform_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem,
+                         const void *d_x, const void *d_z, void *d_out);
+int pbrt_iq_beamform_table_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_table, const void *d_elem,
+                               const void *d_x, const void *d_z, void *d_out);
+int pbrt_rf2iq(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float t0, float demod_freq, uint32_t decimation,
+               uint32_t K, const float *taps, const float *in, float *out);
+int pbrt_rf2iq_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float t0, float demod_freq,
+                   uint32_t decimation, uint32_t K, const void *d_taps, const void *d_in, void *d_out);
+int pbrt_iq_envelope(pbrt_ctx *ctx, uint32_t n, const float *iq, float *env);
+int pbrt_iq_envelope_dev(pbrt_ctx *ctx, uint32_t n, const void *d_iq, void *d_env);
+
 /* waits for everything queued on the context's stream */
 int pbrt_ctx_synchronize(pbrt_ctx *ctx);
 /* Device buffers for a caller without a GPU library of its own (the reference's driver is NumPy: USMain.py:103-121).
@@ -647,6 +696,7 @@ int pbrt_get_image_stats(pbrt_ctx *ctx, pbrt_image_stats *out);
  * the host spends as long queueing them as the device spends running them, 100 times per script.  Between
  * pbrt_ctx_record_begin and pbrt_ctx_record_end the queueing entry points (pbrt_us_acquire_queue_dev, pbrt_us_apply_pulse_dev,
  * pbrt_das_beamform_dev, pbrt_das_beamform_table_dev, pbrt_bf_beamform_dev, pbrt_bf_beamform_table_dev, pbrt_axial_fir_dev,
+ * pbrt_rf2iq_dev, pbrt_iq_beamform_dev, pbrt_iq_beamform_table_dev, pbrt_iq_envelope_dev,
  * pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
  * stream instead of run; pbrt_graph_launch replays the recording in one submission and returns without waiting, exactly as if
  * the recorded calls had just been made: same kernels, same arguments, same results bit for bit, the acquisition's statistics

@@ -145,6 +145,10 @@ class BfParams(C.Structure):
 BF_PDAS, BF_FDMAS = 1, 2
 
 
+class IqParams(C.Structure):
+    _fields_ = [("das", DasParams), ("demod_freq", C.c_float), ("probe", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("kernel_ms", C.c_double), ("bounce_ms", C.c_double), ("bounce_launches", C.c_uint32),
@@ -217,6 +221,13 @@ SIGNATURES = {
     "pbrt_bf_beamform_table_dev": (C.c_int, [_P, C.POINTER(BfParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_axial_fir": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _F, _F, _F]),
     "pbrt_axial_fir_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "pbrt_iq_beamform": (C.c_int, [_P, C.POINTER(IqParams), _F, _F, _F, _F, _F, _F]),
+    "pbrt_iq_beamform_dev": (C.c_int, [_P, C.POINTER(IqParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_iq_beamform_table_dev": (C.c_int, [_P, C.POINTER(IqParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_rf2iq": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, _F, _F, _F]),
+    "pbrt_rf2iq_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "pbrt_iq_envelope": (C.c_int, [_P, C.c_uint32, _F, _F]),
+    "pbrt_iq_envelope_dev": (C.c_int, [_P, C.c_uint32, _P, _P]),
     "pbrt_ctx_synchronize": (C.c_int, [_P]),
     "pbrt_dev_alloc": (C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     "pbrt_dev_free": (C.c_int, [_P, _P]),

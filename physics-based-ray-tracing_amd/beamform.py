@@ -12,10 +12,14 @@ restated in oracle/beamform.py; parity unpinned).  The classes keep the call sha
 PDelayAndSum and FilteredDelayMultiplyAndSum (ultraspy's non-linear beamformers, which the reference does not call) have the same shape;
 their arithmetic, from the papers, and the axial band-pass they need are DESIGN.md D19.
 
+I/Q data (`data_info['is_iq']`, USMain.py:158): rf2iq demodulates and decimates, DelayAndSum(is_iq=True) / iq_beamform beamform complex
+samples, and the envelope of an I/Q image is its modulus (iq_envelope) -- DESIGN.md D20.
+
 All work runs on the GPU through libpbrt_hip.so (no CPU fallback; `on_gpu` is accepted for compatibility)."""
 from __future__ import annotations
 
 import ctypes as C
+import copy
 
 import numpy as np
 
@@ -79,14 +83,19 @@ def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
 
 
 def _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, *, t0, f_number, interpolation, compound, out, table, method=None,
-              p=2.0):
-    """das_beamform (method None) and nonlinear_beamform: shapes and uploads the arguments, validates `out` and `table`, selects the
-    entry point -- pbrt_das_beamform[_table][_probe][_dev], or pbrt_bf_beamform[_table][_dev] with the probe flag in its
-    parameters -- and keeps what the queued kernel reads alive with its result."""
+              p=2.0, demod_freq=None):
+    """das_beamform (method None), nonlinear_beamform and iq_beamform (demod_freq set): shapes and uploads the arguments, validates
+    `out` and `table`, selects the entry point -- pbrt_das_beamform[_table][_probe][_dev], or pbrt_bf_beamform[_table][_dev] /
+    pbrt_iq_beamform[_table][_dev] with the probe flag in their parameters -- and keeps what the queued kernel reads alive with its
+    result.  I/Q: data and result are complex64."""
     dev = _is_dev(data)
+    iq = demod_freq is not None
+    dtype, width = (np.complex64, 8) if iq else (np.float32, 4)
     cx = data.ctx if dev else _capi.default_context()
     if not dev:
-        data = _capi.f32(np.asarray(data))
+        data = np.ascontiguousarray(data, dtype=dtype)
+    elif iq != (data.dtype.kind == "c"):
+        raise ValueError(f"the channel data must be {'complex64 (I/Q)' if iq else 'float32 (RF)'}, got a {data.dtype} DeviceBuffer")
     if len(data.shape) != 3:
         raise ValueError("data must be [n_angles, n_elements, time_samples]")
     A, E, T = data.shape
@@ -106,20 +115,23 @@ def _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, *, t0, f_number, i
     name = "pbrt_das_beamform"
     if method is not None:
         par, name = _bf_params(par, method, p, probe), "pbrt_bf_beamform"
+    elif iq:
+        par, name = _iq_params(par, demod_freq, probe), "pbrt_iq_beamform"
+    flag_in_params = method is not None or iq   # (their parameter blocks carry the probe flag: no *_probe names)
     if not dev:
-        name += "_probe" if probe and method is None else ""
-        res = np.empty((nx, nz), dtype=np.float32)
+        name += "_probe" if probe and not flag_in_params else ""
+        res = np.empty((nx, nz), dtype=dtype)
         cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
                                        _capi.addr(gz), _capi.addr(res)), name)
         return res
-    d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz))
-    if d_out.nbytes != nx * nz * 4:
-        raise ValueError("out must hold nx * nz float32")
+    d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz), dtype)
+    if d_out.nbytes != nx * nz * width:
+        raise ValueError(f"out must hold nx * nz {np.dtype(dtype).name}")
     if table is not None:   # the first-arrival times of this scan, made once (das_first_arrival)
         if table.nbytes != A * nx * nz * 8:
             raise ValueError("table must be the [n_angles, nx, nz] float64 buffer of das_first_arrival for this scan")
         name += "_table"
-    name += ("_probe" if probe and method is None else "") + "_dev"
+    name += ("_probe" if probe and not flag_in_params else "") + "_dev"
     cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), data.ptr, (d_tx if table is None else table).ptr, d_ex.ptr, d_x.ptr,
                                    d_z.ptr, d_out.ptr), name)
     d_out._keep = (d_tx, d_ex, d_x, d_z, table)  # the queued kernel reads them: they live as long as its result
@@ -158,6 +170,122 @@ def nonlinear_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, method="f
         raise ValueError(f"method must be 'pdas' or 'fdmas', got {method!r}")
     return _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
                      compound=compound, out=out, table=table, method=method, p=p)
+
+
+def _iq_params(das, demod_freq, probe) -> "_capi.IqParams":
+    ip = _capi.IqParams()
+    ip.das = das
+    ip.demod_freq, ip.probe = float(demod_freq), int(bool(probe))
+    return ip
+
+
+def iq_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, t0=0.0, f_number=1.0, interpolation="linear",
+                compound="sum", out=None, table=None):
+    """Delay-and-sum of I/Q channel data (DESIGN D20, include/pbrt_hip.h): iq [n_angles, n_elements, T] complex64 at the rate fs_iq,
+    demodulated at demod_freq (rf2iq), sample m at t0 + m / fs_iq  ->  complex64 image [nx, nz].  The delayed samples are
+    das_beamform's (same delays, aperture and interpolation, on complex samples), each turned back by the carrier phase of its delay.
+    Arguments and the host / DeviceBuffer rule as das_beamform: host arrays in -> pbrt_iq_beamform and a host array out; `iq` a complex
+    DeviceBuffer -> pbrt_iq_beamform_dev (or _table_dev with `table` from das_first_arrival), queued, a complex DeviceBuffer out.
+    elem [n_elements] or the element table [n_elements, 4]."""
+    demod_freq = float(demod_freq)
+    if not (np.isfinite(demod_freq) and demod_freq >= 0.0):
+        raise ValueError(f"demod_freq must be finite and >= 0, got {demod_freq}")
+    return _beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
+                     compound=compound, out=out, table=table, demod_freq=demod_freq)
+
+
+RF2IQ_MAX_DECIMATION = 8
+
+
+def lowpass_taps(f_cut, fs, K=None) -> np.ndarray:
+    """Hamming-windowed sinc low-pass below f_cut at the sampling rate fs: bandpass_taps(0, f_cut, fs, K)"""
+    return bandpass_taps(0.0, f_cut, fs, K)
+
+
+def _rf2iq_lowpass(fc, fs, bandwidth, D) -> np.ndarray:
+    """rf2iq's default low-pass, cut-off fc * bandwidth / 200 at the rate fs; ValueError when it does not lie below the Nyquist
+    frequency fs / (2 D) of the decimated rate -- the message names the largest decimation that fits"""
+    f_cut = fc * float(bandwidth) / 200.0
+    if not f_cut > 0.0:
+        raise ValueError(f"rf2iq: the default low-pass needs central_freq * bandwidth > 0, got a cut-off of {f_cut} Hz")
+    if f_cut >= fs / (2.0 * D):
+        fits = min(RF2IQ_MAX_DECIMATION, int(np.ceil(fs / (2.0 * f_cut))) - 1)   # the largest D with f_cut < fs / (2 D)
+        raise ValueError(
+            f"rf2iq: the low-pass cut-off {f_cut:.6g} Hz does not lie below the Nyquist frequency {fs / (2.0 * D):.6g} Hz of "
+            f"{fs:.6g} Hz decimated by {D}; " + (f"the largest decimation that fits is {fits}" if fits >= 1 else
+                                                 "no decimation fits: the cut-off is not below sampling_freq / 2"))
+    return lowpass_taps(f_cut, fs)
+
+
+def rf2iq(data, central_freq, sampling_freq, t0=0.0, bandwidth=100, decimation=1, taps=None, out=None):
+    """RF traces [..., T] (sample j at t0 + j / sampling_freq) -> baseband I/Q [..., Td] complex64, Td = ceil(T / decimation), sample m
+    at t0 + m decimation / sampling_freq: mixed with exp(-2 pi i central_freq t), low-passed, decimated, times 2 (pbrt_rf2iq,
+    DESIGN D20).  The default low-pass is lowpass_taps(central_freq * bandwidth / 200, sampling_freq) (bandwidth in per cent of the
+    carrier, two-sided); it must lie below the Nyquist frequency of the decimated rate.  taps [2 K + 1]: the caller's own low-pass at
+    the rate sampling_freq (bandwidth is then not read).  A host array in gives a host array out; a DeviceBuffer in gives a
+    DeviceBuffer(dtype=complex64) out, queued (the taps then a DeviceBuffer or a host array that is uploaded)."""
+    fc, fs, D = float(central_freq), float(sampling_freq), int(decimation)
+    if not 1 <= D <= RF2IQ_MAX_DECIMATION or D != decimation:
+        raise ValueError(f"rf2iq: decimation must be an integer in [1, {RF2IQ_MAX_DECIMATION}], got {decimation}")
+    if not (np.isfinite(fc) and fc >= 0.0):
+        raise ValueError(f"rf2iq: central_freq must be finite and >= 0, got {fc}")
+    if not (np.isfinite(fs) and fs > 0.0):
+        raise ValueError(f"rf2iq: sampling_freq must be finite and > 0, got {fs}")
+    if taps is None:
+        taps = _rf2iq_lowpass(fc, fs, bandwidth, D)
+    n_taps = taps.shape[0] if _is_dev(taps) else np.asarray(taps).size
+    if n_taps % 2 != 1:
+        raise ValueError("taps must be [2 K + 1]")
+    K = n_taps // 2
+    dev = _is_dev(data)
+    if dev:
+        if data.dtype != np.float32:
+            raise ValueError(f"rf2iq takes float32 RF traces, got a {data.dtype} DeviceBuffer")
+        x = data
+    else:
+        if np.iscomplexobj(data):
+            raise ValueError("rf2iq takes real RF traces, got complex data")
+        x = _capi.f32(np.asarray(data))
+    cx = data.ctx if dev else _capi.default_context()
+    shape = tuple(x.shape)
+    T = shape[-1]
+    n_traces = int(np.prod(shape[:-1], dtype=np.int64))
+    oshape = shape[:-1] + (-(-T // D),)
+    args = (n_traces, T, fs, float(t0), fc, D, K)
+    if dev:
+        d_taps = taps if _is_dev(taps) else _capi.DeviceBuffer.from_host(cx, _capi.f32(np.asarray(taps).ravel()))
+        d_out = out if out is not None else _capi.DeviceBuffer(cx, oshape, np.complex64)
+        if d_out.nbytes != int(np.prod(oshape, dtype=np.int64)) * 8:
+            raise ValueError(f"out must hold {list(oshape)} complex64")
+        cx.check(cx.lib.pbrt_rf2iq_dev(cx.handle, *args, d_taps.ptr, x.ptr, d_out.ptr), "pbrt_rf2iq_dev")
+        d_out._keep = (x, d_taps)
+        return d_out
+    h = _capi.f32(np.asarray(taps).ravel())
+    res = np.empty(oshape, np.complex64)
+    cx.check(cx.lib.pbrt_rf2iq(cx.handle, *args, _capi.addr(h), _capi.addr(x), _capi.addr(res)), "pbrt_rf2iq")
+    return res
+
+
+def iq_envelope(iq, out=None):
+    """envelope of an I/Q image: the modulus of each pixel, on any grid and of any size (pbrt_iq_envelope; a complex DeviceBuffer in
+    gives a float32 DeviceBuffer out, queued)"""
+    if _is_dev(iq):
+        if iq.dtype.kind != "c":
+            raise ValueError(f"iq_envelope takes complex64 data, got a {iq.dtype} DeviceBuffer")
+        cx, n = iq.ctx, iq.nbytes // 8
+        d_out = out if out is not None else _capi.DeviceBuffer(cx, iq.shape)
+        if d_out.nbytes != n * 4:
+            raise ValueError("out must hold one float32 per pixel")
+        cx.check(cx.lib.pbrt_iq_envelope_dev(cx.handle, n, iq.ptr, d_out.ptr), "pbrt_iq_envelope_dev")
+        d_out._keep = (iq,)
+        return d_out
+    if not np.iscomplexobj(iq):
+        raise ValueError("iq_envelope takes complex data")
+    cx = _capi.default_context()
+    a = np.ascontiguousarray(iq, dtype=np.complex64)
+    res = np.empty(a.shape, np.float32)
+    cx.check(cx.lib.pbrt_iq_envelope(cx.handle, a.size, _capi.addr(a), _capi.addr(res)), "pbrt_iq_envelope")
+    return res
 
 
 def axial_fir(rf, taps, out=None):
@@ -358,9 +486,12 @@ class GridScan:
 
 
 class DelayAndSum:
-    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum"):
+    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", is_iq=False):
         self.on_gpu = on_gpu  # accepted for compatibility; the beamformer has no CPU path
-        self.setups = {"f_number": f_number, "interpolation": interpolation, "compound": compound}
+        # is_iq: the data are I/Q samples (complex64) at the rate acquisition_info['sampling_freq'], demodulated at `demod_freq`
+        # (None: probe.central_freq)
+        self.setups = {"f_number": f_number, "interpolation": interpolation, "compound": compound, "is_iq": False, "demod_freq": None}
+        self.set_is_iq(is_iq)
         self.acquisition_info = None
         self.probe = None
         self.probe_dev = None  # element positions as a DeviceBuffer (set by us_render)
@@ -373,10 +504,26 @@ class DelayAndSum:
     def update_setup(self, name, value):
         if name not in self.setups:
             raise KeyError(name)
+        if name == "is_iq":
+            return self.set_is_iq(value)
         self.setups[name] = value
 
+    def set_is_iq(self, flag):
+        """ultraspy's beamformer.set_is_iq: the data given to beamform() are I/Q samples, its result is complex and compute_envelope
+        is the modulus"""
+        self.setups["is_iq"] = bool(flag)
+
+    @property
+    def is_iq(self):
+        return bool(self.setups["is_iq"])
+
+    def demod_freq(self):
+        f = self.setups["demod_freq"]
+        return float(self.probe.central_freq if f is None else f)
+
     def beamform(self, d_data, scan, out=None, table=None):
-        """host array in -> host array out; a DeviceBuffer in (the channel buffer left in HBM) -> a DeviceBuffer out, queued"""
+        """host array in -> host array out; a DeviceBuffer in (the channel buffer left in HBM) -> a DeviceBuffer out, queued.
+        is_iq: complex64 in (host, or a complex DeviceBuffer), complex out."""
         ai = self.acquisition_info
         if ai is None or self.probe is None:
             raise RuntimeError("DelayAndSum.automatic_setup(acquisition_info, probe) has not been called")
@@ -385,20 +532,37 @@ class DelayAndSum:
             data = np.asarray(d_data)
             if data.ndim == 4:      # (frames, n_angles, n_elements, T): USMain passes reader.data[0]
                 data = data[0]
+        _check_iq(self, data)
         # tables that already sit in HBM (us_render keeps them there between calls) are used where the data is a DeviceBuffer
         dev = _is_dev(data)
         ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
         gx = scan.d_x if dev and getattr(scan, "d_x", None) is not None else scan.x_axis
         gz = scan.d_z if dev and getattr(scan, "d_z", None) is not None else scan.z_axis
+        if self.is_iq:
+            return iq_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], self.demod_freq(),
+                               t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
+                               interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out,
+                               table=table if dev else None)
         return das_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], t0=ai.get("t0", 0.0) or 0.0,
                             f_number=self.setups["f_number"], interpolation=self.setups["interpolation"],
                             compound=self.setups["compound"], out=out, table=table if dev else None)
 
     def compute_envelope(self, d_output, scan=None, out=None):
+        if self.is_iq:
+            return iq_envelope(d_output, out=out)
         return envelope(d_output, out=out)
 
     def __str__(self):
         return f"DelayAndSum(MI355X, {self.setups})"
+
+
+def _check_iq(bf, data):
+    """complex data belong to is_iq, real data to RF: anything else is a ValueError"""
+    is_complex = data.dtype.kind == "c"
+    if is_complex and not bf.is_iq:
+        raise ValueError(f"{type(bf).__name__}: complex (I/Q) data, but is_iq is off -- set_is_iq(True), or pass RF data")
+    if bf.is_iq and not is_complex:
+        raise ValueError(f"{type(bf).__name__}: is_iq is on, but the data are real -- demodulate them first (rf2iq), or set_is_iq(False)")
 
 
 class _NonlinearBeamformer(DelayAndSum):
@@ -408,11 +572,18 @@ class _NonlinearBeamformer(DelayAndSum):
     _method = None
     _centre = 1.0   # band centre in units of the probe's central frequency
 
-    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", band="default", taps_half_length=None):
-        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound)
+    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", band="default", taps_half_length=None,
+                 is_iq=False):
+        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound, is_iq=is_iq)
         self.setups.update(band=band, taps_half_length=taps_half_length)
         self.scratch_dev = None           # a buffer for the unfiltered image (set by us_render)
         self._taps_cache = (None, None)   # (the taps' bytes, the taps as a DeviceBuffer)
+
+    def set_is_iq(self, flag):
+        if flag:
+            raise NotImplementedError(f"{type(self).__name__}: is_iq is not built -- the non-linearity is defined on RF samples "
+                                      "(DESIGN D19); DelayAndSum beamforms I/Q data (D20)")
+        self.setups["is_iq"] = False
 
     def band(self, probe=None):
         """(f_lo, f_hi) in Hz, or None"""
@@ -461,6 +632,7 @@ class _NonlinearBeamformer(DelayAndSum):
             data = np.asarray(d_data)
             if data.ndim == 4:
                 data = data[0]
+        _check_iq(self, data)
         dev = _is_dev(data)
         ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
         gx = scan.d_x if dev and getattr(scan, "d_x", None) is not None else scan.x_axis
@@ -503,7 +675,7 @@ class _RenderPlan:
     """Device buffers of one us_render configuration (acquisition shape, scan grid): allocated once, reused by every call of the
     reference's loop (USMain.py:262-289 calls us_render 50 times on one scene)."""
 
-    def __init__(self, cx, A, E, T, elem_x, x_scan, z_scan, gaussian, taps=None):
+    def __init__(self, cx, A, E, T, elem_x, x_scan, z_scan, gaussian, taps=None, iq=None):
         self.key = None
         self.cx = cx
         self.d_channel = _capi.DeviceBuffer(cx, (A, E, T))
@@ -522,13 +694,20 @@ class _RenderPlan:
         # p-DAS / F-DMAS with a band: the band-pass taps, and the image before the filter
         self.d_taps = _capi.DeviceBuffer.from_host(cx, taps) if taps is not None else None
         self.d_nl = _capi.DeviceBuffer(cx, (nx, nz)) if taps is not None else None
+        # the I/Q chain (iq = (decimation, low-pass taps)): the taps, the demodulated channel data and the complex image
+        self.d_iq_taps = self.d_iq = self.d_bf_iq = None
+        if iq is not None:
+            D, lp = iq
+            self.d_iq_taps = _capi.DeviceBuffer.from_host(cx, lp)
+            self.d_iq = _capi.DeviceBuffer(cx, (A, E, -(-T // D)), np.complex64)
+            self.d_bf_iq = _capi.DeviceBuffer(cx, (nx, nz), np.complex64)
         # the queued chain of one key as a recording (pbrt_graph), made at the second call in a row with that key
         self.graph = self.graph_key = self.warm_key = self.no_graph_key = None
 
 
 def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range=60.0, step=None, seed=None,
               paths_per_ray=None, beamformer=None, device_resident=True, return_bmode=True, timing=None, graph=True,
-              on_device=False):
+              on_device=False, iq=False, decimation=1):
     """The reference's us_render (USMain.py:93-224) without the plotting: acquisition -> DAS -> envelope -> log
     compression.  Returns (display_image [nz, nx] in [0, 1], bmode envelope [nx, nz] (None with return_bmode=False),
     (x_scan, z_scan)).
@@ -545,7 +724,12 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     reference's display image is their transpose), still being written by the queued kernels; a caller that keeps its loss on
     the GPU (USMain.py:5 imports torch: `torch.as_tensor(buf, device="cuda")` through __cuda_array_interface__) calls
     scene.device().ctx.synchronize() before it reads them.  The buffers belong to the integrator's render plan: the next
-    us_render with the same scan overwrites them."""
+    us_render with the same scan overwrites them.
+    iq: the I/Q chain (DESIGN D20) -- acquisition -> [pulse] -> rf2iq at the integrator's frequency, decimated by `decimation` ->
+    I/Q delay-and-sum -> modulus -> log compression, on every path above.  The envelope is a modulus per pixel, so `step` is free
+    of the carrier (lambda / 2, a coarse loss grid) and nz has no limit.  A `beamformer` of the caller keeps its setups: the call
+    works on a copy of it that beamforms I/Q data; one that has is_iq set selects this chain by itself, and its setup `demod_freq`, where set,
+    is the frequency rf2iq demodulates at (default: the integrator's)."""
     import time as _time
     integ = scene.integrator()
     A, E, T = integ.n_angles, integ.n_elements, integ.time_samples
@@ -560,13 +744,34 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     else:
         probe = build_probe("linear", E, integ.pitch, integ.frequency, 70)                             # :130-136
     bf = beamformer or DelayAndSum(on_gpu=True)
+    iq, D = bool(iq) or bf.is_iq, int(decimation)      # (a beamformer that has is_iq set selects the I/Q chain by itself)
+    if iq and not bf.is_iq:
+        # the caller's beamformer keeps its setups: this call works on a copy of it that beamforms I/Q data (p-DAS / F-DMAS:
+        # NotImplementedError)
+        bf = copy.copy(bf)
+        bf.setups = dict(bf.setups)
+        bf.set_is_iq(True)
+    lp = None
+    f_demod = None
+    if iq:   # the frequency rf2iq demodulates at is the one the walk turns back by: the setup `demod_freq`, else the integrator's
+        f_demod = float(integ.frequency if bf.setups["demod_freq"] is None else bf.setups["demod_freq"])
+    if iq:
+        if not 1 <= D <= RF2IQ_MAX_DECIMATION or D != decimation:
+            raise ValueError(f"us_render: decimation must be an integer in [1, {RF2IQ_MAX_DECIMATION}], got {decimation}")
+        if -(-T // D) < 2:
+            raise ValueError(f"us_render: {T} samples decimated by {D} leave fewer than two")
+        # rf2iq's default low-pass (bandwidth = 100): refused here, before anything is acquired, when the decimation does not fit
+        lp = _rf2iq_lowpass(f_demod, float(integ.fs), 100, D)
+    elif D != 1:
+        raise ValueError("us_render: decimation belongs to the I/Q chain (iq=True)")
+    fs_img = integ.fs / D if iq else integ.fs   # the rate of the data the beamformer is given
     # (p-DAS / F-DMAS: the band-pass taps of this scan -- refused here, before anything is acquired, when the band does not fit
     # under the Nyquist frequency of the depth step: the reference's lambda / 4 grid puts that AT the carrier, DESIGN D19)
     taps = bf.filter_taps(scan, integ.sound_speed, probe) if isinstance(bf, _NonlinearBeamformer) else None
     seq = {"emitted": np.tile(np.arange(E), (A, 1)), "received": np.tile(np.arange(E), (A, 1))}
 
     def info(delays):
-        return {"sampling_freq": integ.fs, "t0": 0, "prf": None, "signal_duration": None, "delays": delays,
+        return {"sampling_freq": fs_img, "t0": 0, "prf": None, "signal_duration": None, "delays": delays,
                 "sound_speed": integ.sound_speed, "sequence_elements": seq}
 
     if not device_resident:
@@ -577,6 +782,8 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
         data = np.asarray(integ.channel_buf, dtype=np.float32).reshape(A, E, T)                        # :118
         delays = np.asarray(integ.transmission_delays_buf, dtype=np.float32).reshape(A, E)             # :121
         bf.automatic_setup(info(delays), probe)                                                        # :175
+        if iq:
+            data = rf2iq(data, f_demod, integ.fs, decimation=D, taps=lp)
         bmode = bf.compute_envelope(bf.beamform(data[np.newaxis], scan), scan).astype(np.float32)      # :204-207
         display = log_compress(bmode, dynamic_range).T                                                 # :210-221
         return display, bmode, (x_scan, z_scan)
@@ -584,10 +791,10 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     cx = scene.device().ctx
     gaussian = integ.pulse_model == "gaussian"
     key = (A, E, T, float(integ.pitch), x_scan.tobytes(), z_scan.tobytes(), gaussian, id(cx), probe.geometry_type, probe.radius,
-           probe.opening_angle, None if taps is None else taps.tobytes())
+           probe.opening_angle, None if taps is None else taps.tobytes(), iq, D if iq else 1, None if lp is None else lp.tobytes())
     plan = getattr(integ, "_render_plan", None)
     if plan is None or plan.key != key:
-        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian, taps)
+        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian, taps, (D, lp) if iq else None)
         plan.key = key
         integ._render_plan = plan
     rf = plan.d_rf if gaussian else plan.d_channel
@@ -606,8 +813,13 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
         if gaussian:                                                                                   # f-3: carrier on the device
             apply_pulse(plan.d_channel, integ.fs, integ.frequency, integ.pulse_sigma, out=plan.d_rf)
         bf.automatic_setup(info(plan.d_tx), probe)                                                     # :175
-        bf.beamform(rf, scan, out=plan.d_bf, table=plan.d_table)                                       # :204
-        bf.compute_envelope(plan.d_bf, scan, out=plan.d_env)                                           # :205
+        if iq:                                                                                         # D20: baseband, then complex DAS
+            rf2iq(rf, f_demod, integ.fs, decimation=D, taps=plan.d_iq_taps, out=plan.d_iq)
+            bf.beamform(plan.d_iq, scan, out=plan.d_bf_iq, table=plan.d_table)
+            bf.compute_envelope(plan.d_bf_iq, scan, out=plan.d_env)                                    # the modulus
+        else:
+            bf.beamform(rf, scan, out=plan.d_bf, table=plan.d_table)                                   # :204
+            bf.compute_envelope(plan.d_bf, scan, out=plan.d_env)                                       # :205
         log_compress(plan.d_env, dynamic_range, out=plan.d_img)                                        # :210-218
 
     # What the queued calls depend on besides the CONTENTS of device memory: a recording of them (pbrt_ctx_record_begin, one
@@ -620,7 +832,8 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
         gkey = (bytes(integ.us_params(scene, integ.quirks)), getattr(h, "value", h),
                 int(integ.seed if seed is None else seed) & 0xFFFFFFFF,
                 int(paths_per_ray if paths_per_ray is not None else integ.paths_per_ray), float(dynamic_range),
-                type(bf).__name__, tuple(sorted(bf.setups.items())), float(integ.pulse_sigma) if gaussian else None)
+                type(bf).__name__, tuple(sorted(bf.setups.items())), float(integ.pulse_sigma) if gaussian else None,
+                (D, f_demod) if iq else None)
     replayed = False
     if gkey is not None and plan.graph is not None and plan.graph_key == gkey:
         try:

@@ -130,11 +130,38 @@ __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, co
     }
 }
 
-// ---- the walk: delay-and-sum, p-DAS and F-DMAS --------------------------------------------------------------------------------
+// ---- the walk: delay-and-sum, p-DAS, F-DMAS and I/Q delay-and-sum ---------------------------------------------------------------
 // Two argument lists, one body: `p` is a launch argument, and one more argument enlarges the kernarg segment of every instance of a
 // template -- so k_nl_beamform is a __global__ template of its own beside k_das_beamform, and both are one call of das_walk below,
 // where delay-and-sum is a METHOD like the other two (BF_DAS: internal, not a pbrt_bf_params method).
 #define BF_DAS 0u
+// I/Q delay-and-sum (DESIGN D20; internal like BF_DAS: pbrt_iq_* select it, pbrt_bf_params refuses the value).  The channel data are
+// baseband samples (re, im) at the rate p.fs, demodulated at f_d (k_rf2iq below); the delayed sample s_{a,e} is delay-and-sum's --
+// the same first arrival, f64 position, range and aperture rules, nearest / linear interpolation, taken on both components -- and is
+// turned back by the carrier phase of its delay, split so that a pixel pays E + A sincos and not E x A:
+//   rot_e = exp(i 2 pi frac(f_d d_e / c)),  rot_a = exp(i 2 pi frac(f_d t_tx(a)))     (each frac in f64, then f32 through sincospif)
+//   q_a = sum_{e in U(a)} rot_e s_{a,e},  out = sum_a rot_a q_a  (/ n_angles)
+// Wave w = e % DAS_SPLIT keeps its share of q_a (re in q[j], im in b[j]: the two register rows per angle F-DMAS has), the shares meet
+// in LDS in wave order, wave 0 applies rot_a and adds in angle order.  A pixel that uses no element is exactly (0, 0).
+#define BF_IQ 3u
+template <uint32_t METHOD>
+struct DasSample {
+    typedef float type;
+};
+template <>
+struct DasSample<BF_IQ> {
+    typedef float2 type;
+};
+// linear interpolation of a sample: v0 + w (v1 - v0), per component
+DEV float das_lerp(float w, float v0, float v1) { return fma_(w, v1 - v0, v0); }
+DEV float2 das_lerp(float w, float2 v0, float2 v1) { return make_float2(fma_(w, v1.x - v0.x, v0.x), fma_(w, v1.y - v0.y, v0.y)); }
+// exp(i 2 pi frac(cycles)) -> (cos, sin): the fraction of a cycle in f64, rounded to f32, through sincospif
+DEV float2 iq_rot(double cycles) {
+    const float ph = (float)(cycles - floor(cycles));
+    float sn, cs;
+    sincospif(2.0f * ph, &sn, &cs);
+    return make_float2(cs, sn);
+}
 // p-DAS and F-DMAS (DESIGN D19).  The non-linear members of the beamformer family (`ultraspy` ships them beside DelayAndSum; absent here, so the arithmetic is this
 // build's own definition, include/pbrt_hip.h, taken from Polichetti et al. 2018 and Matrone et al. 2015).  The delayed sample s_e of
 // transmission a and element e at a pixel is exactly the term delay-and-sum adds; per transmission
@@ -149,20 +176,23 @@ DEV float nl_root(float v, bool square, float inv_p) {
     return __builtin_copysignf((METHOD == PBRT_BF_FDMAS || square) ? sqrtf(a) : powf(a, inv_p), v);
 }
 
-// The walk over tiles, elements and angles of the comment at the top of this file, for all three methods.  What METHOD compiles in is
-// what happens to a delayed sample (BF_DAS: added to the wave's partial sum; else: its signed root into q[j] and, F-DMAS, its modulus
-// into b[j]), the per-trip meeting of the shares and the non-linearity (non-linear methods), and the final
-// reduction of the waves' partial sums (BF_DAS).
+// The walk over tiles, elements and angles of the comment at the top of this file, for all four methods.  What METHOD compiles in is
+// what happens to a delayed sample (BF_DAS: added to the wave's partial sum; BF_IQ: turned by rot_e into q[j], b[j]; else: its signed
+// root into q[j] and, F-DMAS, its modulus into b[j]), the per-trip meeting of the shares and the non-linearity or rot_a (every method
+// but BF_DAS), and the final reduction of the waves' partial sums (BF_DAS).
 // TABLE: the first-arrival times come from a table [n_angles][nx][nz] of doubles (k_das_first_arrival: the same minimum, made once
 // for a scan whose delays and grid do not change -- the 51 renders of USMain.py share one) instead of a pass over all elements
 // per call; the rest of the walk, and every bit of its result, is the same.
 // CONVEX: the element table of a curved array (above); its four columns are held in lanes and picked with v_readlane like elem_x.
+// pw: the power p of p-DAS; BF_IQ: the demodulation frequency f_d.  The samples and the pixels are float2 (re, im) for BF_IQ.
 template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD>
-DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__restrict__ data, const float *__restrict__ tx,
-                  const float *__restrict__ elem_x, const float *__restrict__ gx, const float *__restrict__ gz,
-                  const double *__restrict__ ttx, float *__restrict__ out, float pw) {
-    // rows of a wave's share: the partial sum (BF_DAS), or per angle of a trip q_a, then (F-DMAS) sum |s_e|
-    constexpr uint32_t ROWS = METHOD == BF_DAS ? 1u : METHOD == PBRT_BF_FDMAS ? 2u * DAS_ANG : DAS_ANG;
+DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename DasSample<METHOD>::type *__restrict__ data,
+                  const float *__restrict__ tx, const float *__restrict__ elem_x, const float *__restrict__ gx,
+                  const float *__restrict__ gz, const double *__restrict__ ttx, typename DasSample<METHOD>::type *__restrict__ out,
+                  float pw) {
+    typedef typename DasSample<METHOD>::type Sample;
+    // rows of a wave's share: the partial sum (BF_DAS), or per angle of a trip q_a, then (F-DMAS) sum |s_e|, (BF_IQ) the imaginary part
+    constexpr uint32_t ROWS = METHOD == BF_DAS ? 1u : (METHOD == PBRT_BF_FDMAS || METHOD == BF_IQ) ? 2u * DAS_ANG : DAS_ANG;
     __shared__ double s_tmin[DAS_SPLIT][DAS_ANG][64];
     __shared__ float s_sum[DAS_SPLIT][ROWS][64];
     uint32_t tile_x, tile_z;
@@ -201,11 +231,12 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__r
     // (CONVEX: no early-out -- the apertures of a curved array fan out, the span of the x_e bounds nothing)
     bool any = valid && (CONVEX || (x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi));
     if (__ballot(any) == 0ull) {  // a tile outside the span of a linear array writes exact zeros
-        if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = 0.0f;
+        if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = Sample{};
         return;
     }
     const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;  // CONVEX: 2 f# |d_t| <= d_n
     float acc = 0.0f;  // BF_DAS: this wave's partial sum; else, in wave 0: the y_a so far
+    [[maybe_unused]] float acc_im = 0.0f;  // (BF_IQ: acc is the real part)
     const double last = (double)(T - 1u);
     for (uint32_t a0 = 0; a0 < A; a0 += DAS_ANG) {
         const uint32_t na = min((uint32_t)DAS_ANG, A - a0);
@@ -281,17 +312,22 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__r
                 if (__ballot(in_ap) == 0ull) continue;
                 const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
                 const DasPos dp = INTERP == PBRT_DAS_LINEAR ? das_split(d * fs) : DasPos{0, 0.0f};
+                [[maybe_unused]] float2 rot_e = make_float2(1.0f, 0.0f);
+                if constexpr (METHOD == BF_IQ) rot_e = iq_rot((double)pw * d);
 #pragma unroll
                 for (uint32_t j = 0; j < DAS_ANG; ++j) {
                     if (j >= na) break;
-                    const float *trace = data + ((size_t)(a0 + j) * E + e) * T;
+                    const Sample *trace = data + ((size_t)(a0 + j) * E + e) * T;
                     // a delayed sample: delay-and-sum and F-DMAS take it in the branch that gathered it, p-DAS carries it to the one site
                     // below -- one call site of powf instead of two (the forms were measured: profiles/one_beamformer_walk.md)
                     [[maybe_unused]] bool use = false;  // (p-DAS only)
                     [[maybe_unused]] float v = 0.0f;
-                    const auto take = [&](float s) {
+                    const auto take = [&](Sample s) {
                         if constexpr (METHOD == BF_DAS) {
                             acc += s;
+                        } else if constexpr (METHOD == BF_IQ) {
+                            q[j] += fma_(rot_e.x, s.x, -(rot_e.y * s.y));
+                            b[j] += fma_(rot_e.x, s.y, rot_e.y * s.x);
                         } else if constexpr (METHOD == PBRT_BF_FDMAS) {
                             q[j] += nl_root<METHOD>(s, square, inv_p);
                             b[j] += __builtin_fabsf(s);
@@ -309,8 +345,8 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__r
                         const float w = fr - fl;
                         const uint32_t i0 = (uint32_t)(tp[j].i + dp.i + (int32_t)fl);
                         if (in_ap && i0 < T - 1u) {
-                            const float v0 = trace[i0], v1 = trace[i0 + 1];
-                            take(fma_(w, v1 - v0, v0));
+                            const Sample v0 = trace[i0], v1 = trace[i0 + 1];
+                            take(das_lerp(w, v0, v1));
                         } else if (in_ap && i0 == T - 1u && w == 0.0f) {  // exactly the last sample
                             take(trace[T - 1u]);
                         }
@@ -328,7 +364,7 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__r
         for (uint32_t j = 0; j < DAS_ANG; ++j) {
             if (j >= na) break;
             s_sum[wave][j][lane] = q[j];
-            if (METHOD == PBRT_BF_FDMAS) s_sum[wave][DAS_ANG + j][lane] = b[j];
+            if (METHOD == PBRT_BF_FDMAS || METHOD == BF_IQ) s_sum[wave][DAS_ANG + j][lane] = b[j];
         }
         __syncthreads();
         if (wave == 0) {
@@ -337,7 +373,13 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__r
                 if (j >= na) break;
                 float qa = s_sum[0][j][lane];
                 for (uint32_t w = 1; w < DAS_SPLIT; ++w) qa += s_sum[w][j][lane];
-                if (METHOD == PBRT_BF_FDMAS) {
+                if constexpr (METHOD == BF_IQ) {
+                    float ba = s_sum[0][DAS_ANG + j][lane];
+                    for (uint32_t w = 1; w < DAS_SPLIT; ++w) ba += s_sum[w][DAS_ANG + j][lane];
+                    const float2 rot_a = iq_rot((double)pw * tmin[j]);
+                    acc += fma_(rot_a.x, qa, -(rot_a.y * ba));
+                    acc_im += fma_(rot_a.x, ba, rot_a.y * qa);
+                } else if (METHOD == PBRT_BF_FDMAS) {
                     float ba = s_sum[0][DAS_ANG + j][lane];
                     for (uint32_t w = 1; w < DAS_SPLIT; ++w) ba += s_sum[w][DAS_ANG + j][lane];
                     acc += 0.5f * (qa * qa - ba);
@@ -355,7 +397,12 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const float *__r
         acc = s_sum[0][0][lane];
         for (uint32_t w = 1; w < DAS_SPLIT; ++w) acc += s_sum[w][0][lane];
     }
-    if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = p.compound_mean ? acc / (float)A : acc;
+    if constexpr (METHOD == BF_IQ) {
+        if (valid && wave == 0)
+            out[(size_t)ix * p.nz + iz] = p.compound_mean ? make_float2(acc / (float)A, acc_im / (float)A) : make_float2(acc, acc_im);
+    } else {
+        if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = p.compound_mean ? acc / (float)A : acc;
+    }
 }
 template <uint32_t INTERP, bool TABLE, bool CONVEX = false>
 __global__ __launch_bounds__(64 * DAS_SPLIT) void k_das_beamform(pbrt_das_params p, DasGrid grid, const float *__restrict__ data,
@@ -370,6 +417,14 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_nl_beamform(pbrt_das_params 
                                                                 const float *__restrict__ gx, const float *__restrict__ gz,
                                                                 const double *__restrict__ ttx, float *__restrict__ out, float pw) {
     das_walk<INTERP, TABLE, CONVEX, METHOD>(p, grid, data, tx, elem_x, gx, gz, ttx, out, pw);
+}
+// the I/Q member (BF_IQ above): data [n_angles][n_elements][time_samples] and out [nx][nz] of (re, im) pairs, f_d a launch argument
+template <uint32_t INTERP, bool TABLE, bool CONVEX>
+__global__ __launch_bounds__(64 * DAS_SPLIT) void k_iq_beamform(pbrt_das_params p, DasGrid grid, const float2 *__restrict__ data,
+                                                                const float *__restrict__ tx, const float *__restrict__ elem_x,
+                                                                const float *__restrict__ gx, const float *__restrict__ gz,
+                                                                const double *__restrict__ ttx, float2 *__restrict__ out, float f_d) {
+    das_walk<INTERP, TABLE, CONVEX, BF_IQ>(p, grid, data, tx, elem_x, gx, gz, ttx, out, f_d);
 }
 
 // What k_axial_fir and k_apply_pulse share: one workgroup makes the 256 outputs n0 .. n0 + 255 of one row of N samples,
@@ -401,6 +456,64 @@ __global__ __launch_bounds__(256) void k_axial_fir(uint32_t nz, uint32_t K, uint
                                                    const float *__restrict__ in, float *__restrict__ out) {
     const uint32_t col = blockIdx.x / blocks_per_col, n0 = (blockIdx.x - col * blocks_per_col) * 256u;
     fir_256(nz, K, n0, in + (size_t)col * nz, out + (size_t)col * nz, [=](uint32_t i) { return taps[i]; });
+}
+
+// Demodulation to baseband (DESIGN D20): a trace x[0 .. T), sample j taken at t_j = t0 + j / fs, is mixed with the carrier f_d,
+//   phi_j = frac(f_d t_j) (f64, then rounded to f32),  u_j = x_j cospi(2 phi_j),  v_j = -x_j sinpi(2 phi_j)   (f32),
+// low-passed with the caller's taps h[2K + 1] and decimated by D: for m in [0, Td), Td = ceil(T / D),
+//   iq[m] = 2 (sum_{k = -K .. K} h[k] u[m D - k], sum_k h[k] v[m D - k]),  zero outside the trace,
+// f32 multiply-adds in order of increasing k, the factor 2 last.  Output sample m belongs to time t0 + m D / fs.  fir_256's
+// structure with the mix applied while staging: one workgroup makes 256 outputs of one trace from the 256 D + 2K mixed samples
+// (two planes) and the taps in LDS, (2K + 1) + 2 (256 D + 2K) floats of dynamic LDS -- 40 KB at D = 8, K = 1024.  A sibling of
+// fir_256, not a generalisation: k_axial_fir and k_apply_pulse keep their instructions.
+#define RF2IQ_MAX_D 8
+__global__ __launch_bounds__(256) void k_rf2iq(uint32_t T, uint32_t Td, uint32_t K, uint32_t D, uint32_t blocks_per_trace, float fs,
+                                               float t0, float f_d, const float *__restrict__ taps, const float *__restrict__ in,
+                                               float2 *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float lds_iq[];
+    const uint32_t W = 256u * D + 2 * K;  // staged inputs
+    float *h = lds_iq;                    // [2K + 1], h[K + k]
+    float *u = lds_iq + 2 * K + 1;        // [W]
+    float *v = u + W;                     // [W]
+    const uint32_t trace = blockIdx.x / blocks_per_trace, m0 = (blockIdx.x - trace * blocks_per_trace) * 256u;
+    const float *x = in + (size_t)trace * T;
+    for (uint32_t i = threadIdx.x; i < 2 * K + 1; i += 256u) h[i] = taps[i];
+    for (uint32_t i = threadIdx.x; i < W; i += 256u) {
+        const int64_t n = (int64_t)m0 * D + (int64_t)i - (int64_t)K;
+        float re = 0.0f, im = 0.0f;
+        if (n >= 0 && n < (int64_t)T) {
+            const double cyc = (double)f_d * ((double)t0 + (double)n / (double)fs);
+            const float ph = (float)(cyc - floor(cyc));
+            float sn, cs;
+            sincospif(2.0f * ph, &sn, &cs);
+            const float s = x[n];
+            re = s * cs;
+            im = -(s * sn);
+        }
+        u[i] = re;
+        v[i] = im;
+    }
+    __syncthreads();
+    const uint32_t m = m0 + threadIdx.x;
+    if (m >= Td) return;
+    float ar = 0.0f, ai = 0.0f;
+    // index of the mixed sample m D - k is threadIdx.x D + K - k = threadIdx.x D + 2K - (K + k)
+    const uint32_t base = threadIdx.x * D + 2 * K;
+    for (uint32_t j = 0; j < 2 * K + 1; ++j) {
+        const float hj = h[j];
+        ar = fma_(hj, u[base - j], ar);
+        ai = fma_(hj, v[base - j], ai);
+    }
+    out[(size_t)trace * Td + m] = make_float2(2.0f * ar, 2.0f * ai);
+}
+
+// Envelope of an I/Q image: the modulus of each pixel, env = sqrtf(fma(re, re, im * im)).  No transform, so no column rule and no
+// limit on nz; NaN and infinity propagate by the arithmetic, per pixel.
+__global__ __launch_bounds__(256) void k_iq_modulus(uint32_t n, const float2 *__restrict__ iq, float *__restrict__ env) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float2 s = iq[i];
+    env[i] = sqrtf(fma_(s.x, s.x, s.y * s.y));
 }
 
 // ---- envelope ---------------------------------------------------------------------------------------------------------------

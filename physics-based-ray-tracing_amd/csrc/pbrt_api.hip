@@ -2528,7 +2528,12 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    if (method) {  // p-DAS / F-DMAS (pbrt_bf_*): the same tiles, the method's arithmetic compiled in, p a launch argument
+    if (method == BF_IQ) {  // I/Q delay-and-sum (pbrt_iq_*): dd and dout hold (re, im) pairs, pw is the demodulation frequency
+        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_iq_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe);
+        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
+                           reinterpret_cast<float2 *>(dout), pw);
+    } else if (method) {  // p-DAS / F-DMAS (pbrt_bf_*): the same tiles, the method's arithmetic compiled in, p a launch argument
         const auto kernel = with_flags([](auto L, auto T, auto X, auto F) {
             return &k_nl_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), F() ? PBRT_BF_FDMAS : PBRT_BF_PDAS>; },
                                        p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe, method == PBRT_BF_FDMAS);
@@ -2538,7 +2543,7 @@ static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, c
                                        p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe);
         hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
     }
-    c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * 4;
+    c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * (method == BF_IQ ? 8 : 4);
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
 }
@@ -2636,15 +2641,16 @@ static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const floa
     NEED(ctx, p && data && tx_delays && elem_x && x && z && out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
-    const size_t nd = (size_t)p->n_angles * p->n_elements * p->time_samples, ne = (size_t)p->n_angles * p->n_elements;
+    const size_t width = method == BF_IQ ? 2u : 1u;  // floats per sample and per pixel
+    const size_t nd = (size_t)p->n_angles * p->n_elements * p->time_samples * width, ne = (size_t)p->n_angles * p->n_elements;
     const uint32_t n = p->nx * p->nz;
     const size_t nel = (size_t)p->n_elements * (probe ? 4u : 1u);
-    STAGED_BEGIN(ctx, (nd + ne + nel + p->nx + p->nz + (size_t)n) * 4 + 256);
+    STAGED_BEGIN(ctx, (nd + ne + nel + p->nx + p->nz + (size_t)n * width) * 4 + 256);
     float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem_x, nel);
     float *dx = S.in(x, p->nx), *dz = S.in(z, p->nz);
-    float *dout = S.out<float>(n);
+    float *dout = S.out<float>(n * width);
     if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout, nullptr, probe, method, pw)) != 0) return rc;
-    S.back(out, dout, n);
+    S.back(out, dout, n * width);
     return S.finish();
 }
 
@@ -2668,7 +2674,101 @@ static int fir_enqueue(pbrt_ctx *c, uint32_t nx, uint32_t nz, uint32_t K, const 
     return PBRT_OK;
 }
 
+// I/Q (DESIGN D20): what pbrt_iq_params adds to das_check; the entry points then take the DAS path with the method BF_IQ
+static int iq_check(pbrt_ctx *ctx, const pbrt_iq_params *p) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, p && p->probe <= 1u);
+    NEED(ctx, std::isfinite(p->demod_freq) && p->demod_freq >= 0.0f);
+    return PBRT_OK;
+}
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+static int rf2iq_check(pbrt_ctx *ctx, uint32_t n_traces, uint32_t T, float fs, float t0, float f_d, uint32_t D, uint32_t K, const void *in,
+                       const void *out) {
+    NEED(ctx, T > 0 && D >= 1u && D <= RF2IQ_MAX_D && K <= FIR_MAX_K);
+    NEED(ctx, std::isfinite(fs) && fs > 0.0f && std::isfinite(t0));
+    NEED(ctx, std::isfinite(f_d) && f_d >= 0.0f);
+    NEED(ctx, (uint64_t)n_traces * T < 0xffffffffull && (uint64_t)n_traces * div_up(div_up(T, D), 256) < 0x7fffffffull);
+    NEED(ctx, !ranges_overlap(in, (size_t)n_traces * T * 4, out, (size_t)n_traces * div_up(T, D) * 8));
+    return PBRT_OK;
+}
+static int rf2iq_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, float fs, float t0, float f_d, uint32_t D, uint32_t K,
+                         const float *dtaps, const float *din, float *dout) {
+    const uint32_t Td = div_up(T, D), per_trace = div_up(Td, 256);
+    const size_t lds = (size_t)(2 * K + 1 + 2 * (256 * D + 2 * K)) * 4;  // <= 40 KB
+    hipLaunchKernelGGL(k_rf2iq, dim3(n_traces * per_trace), dim3(256), lds, c->stream, T, Td, K, D, per_trace, fs, t0, f_d, dtaps, din,
+                       reinterpret_cast<float2 *>(dout));
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+static int iq_env_enqueue(pbrt_ctx *c, uint32_t n, const float *din, float *dout) {
+    ImgTimer tm(c, IMG_ENV);
+    hipLaunchKernelGGL(k_iq_modulus, dim3(div_up(n, 256)), dim3(256), 0, c->stream, n, reinterpret_cast<const float2 *>(din), dout);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
 extern "C" {
+
+int pbrt_iq_beamform_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem,
+                         const void *d_x, const void *d_z, void *d_out) {
+    int rc = iq_check(ctx, p);
+    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_iq, d_tx_delays, nullptr, d_elem, d_x, d_z, d_out, p->probe != 0u, BF_IQ, p->demod_freq);
+}
+int pbrt_iq_beamform_table_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_table, const void *d_elem,
+                               const void *d_x, const void *d_z, void *d_out) {
+    int rc = iq_check(ctx, p);
+    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_iq, nullptr, d_table, d_elem, d_x, d_z, d_out, p->probe != 0u, BF_IQ, p->demod_freq);
+}
+int pbrt_iq_beamform(pbrt_ctx *ctx, const pbrt_iq_params *p, const float *iq, const float *tx_delays, const float *elem,
+                     const float *x, const float *z, float *out) {
+    int rc = iq_check(ctx, p);
+    return rc ? rc : das_beamform_impl(ctx, &p->das, iq, tx_delays, elem, x, z, out, p->probe != 0u, BF_IQ, p->demod_freq);
+}
+int pbrt_rf2iq_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float t0, float demod_freq,
+                   uint32_t decimation, uint32_t K, const void *d_taps, const void *d_in, void *d_out) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, d_taps && d_in && d_out);
+    int rc = rf2iq_check(ctx, n_traces, time_samples, fs, t0, demod_freq, decimation, K, d_in, d_out);
+    if (rc) return rc;
+    if (n_traces == 0) return PBRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return rf2iq_enqueue(ctx, n_traces, time_samples, fs, t0, demod_freq, decimation, K, (const float *)d_taps, (const float *)d_in,
+                         (float *)d_out);
+}
+int pbrt_rf2iq(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float t0, float demod_freq, uint32_t decimation,
+               uint32_t K, const float *taps, const float *in, float *out) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, taps && in && out);
+    int rc = rf2iq_check(ctx, n_traces, time_samples, fs, t0, demod_freq, decimation, K, in, out);
+    if (rc) return rc;
+    const uint32_t n = n_traces * time_samples;
+    const size_t n_out = (size_t)n_traces * div_up(time_samples, decimation) * 2;
+    STAGED_BEGIN(ctx, ((size_t)n + n_out + 2 * (size_t)K + 1) * 4 + 128);
+    float *dh = S.in(taps, 2 * (size_t)K + 1), *din = S.in(in, n), *dout = S.out<float>(n_out);
+    if ((rc = rf2iq_enqueue(c, n_traces, time_samples, fs, t0, demod_freq, decimation, K, dh, din, dout)) != 0) return rc;
+    S.back(out, dout, n_out);
+    return S.finish();
+}
+int pbrt_iq_envelope_dev(pbrt_ctx *ctx, uint32_t n, const void *d_iq, void *d_env) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, d_iq && d_env && !ranges_overlap(d_iq, (size_t)n * 8, d_env, (size_t)n * 4));
+    if (n == 0) return PBRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return iq_env_enqueue(ctx, n, (const float *)d_iq, (float *)d_env);
+}
+int pbrt_iq_envelope(pbrt_ctx *ctx, uint32_t n, const float *iq, float *env) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, iq && env && !ranges_overlap(iq, (size_t)n * 8, env, (size_t)n * 4));
+    STAGED_BEGIN(ctx, (size_t)n * 12 + 64);
+    float *din = S.in(iq, 2 * (size_t)n), *dout = S.out<float>(n);
+    int rc = iq_env_enqueue(c, n, din, dout);
+    if (rc) return rc;
+    S.back(env, dout, n);
+    return S.finish();
+}
 
 int pbrt_bf_beamform_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
                          const void *d_x, const void *d_z, void *d_out) {

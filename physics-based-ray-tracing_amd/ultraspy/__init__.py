@@ -3,4 +3,5 @@
     from pbrt_amd.ultraspy.scan import GridScan
     from pbrt_amd.ultraspy.probes.factory import build_probe
 `ultraspy` itself is third-party and absent; the implementation (this build's own definition, GPU only) lives in
-beamform.py."""
+beamform.py.  `ultraspy.rf2iq` (demodulation of RF data, DESIGN D20) is exported here as the package has it."""
+from ..beamform import rf2iq  # noqa: F401
