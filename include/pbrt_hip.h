@@ -529,7 +529,7 @@ int pbrt_log_compress(pbrt_ctx *ctx, uint32_t n, const float *env, float dynamic
  * With echoes deposited as plain amplitudes on the sample grid (PBRT_USQ_NO_CARRIER) the RF trace is the discrete
  * convolution of every trace with h[k] = sin(2 pi fc k / fs) * exp(-(k / fs)^2 / sigma^2), |k| <= ceil(2.5 sigma fs):
  * out[tr][n] = sum_k in[tr][n - k] * h[k]  (zero outside the trace).  n_traces x time_samples values, host pointers;
- * in and out must not overlap.  [DEFINE] sigma = wave_cycles / (4 fc) turns the integrator's unused `wave_cycles`
+ * in and out must not overlap (PBRT_E_INVALID).  [DEFINE] sigma = wave_cycles / (4 fc) turns the integrator's unused `wave_cycles`
  * (CustomIntegrator.py:20) into the pulse length. */
 int pbrt_us_apply_pulse(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,
                         const float *in, float *out);
@@ -576,11 +576,11 @@ int pbrt_das_first_arrival_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, co
                                      const void *d_x, const void *d_z, void *d_table);
 int pbrt_das_beamform_table_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table,
                                       const void *d_elem, const void *d_x, const void *d_z, void *d_out);
-/* replaces: DelayAndSum.compute_envelope (USMain.py:205); d_rf, d_env [nx][nz], distinct buffers; NaN as pbrt_envelope */
+/* replaces: DelayAndSum.compute_envelope (USMain.py:205); d_rf, d_env [nx][nz], ranges that do not overlap (else PBRT_E_INVALID); NaN as pbrt_envelope */
 int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf, void *d_env);
 /* replaces: the log compression of USMain.py:210-218; d_env, d_out [n] (may be the same buffer); NaN as pbrt_log_compress */
 int pbrt_log_compress_dev(pbrt_ctx *ctx, uint32_t n, const void *d_env, float dynamic_range_db, void *d_out);
-/* the pulse model (RayTracingV0.py:194-204) on a channel buffer in HBM; d_in, d_out [n_traces][time_samples], distinct */
+/* the pulse model (RayTracingV0.py:194-204) on a channel buffer in HBM; d_in, d_out [n_traces][time_samples], not overlapping */
 int pbrt_us_apply_pulse_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,
                             const void *d_in, void *d_out);
 
@@ -616,7 +616,7 @@ int pbrt_bf_beamform_table_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const voi
                                const void *d_x, const void *d_z, void *d_out);
 /* Axial FIR of an image [nx][nz]: out[ix][n] = sum_{k = -K .. K} taps[K + k] in[ix][n - k], samples outside the column zero, f32
  * multiply-adds in order of increasing k.  taps [2 K + 1] are the caller's (the library does not design them); K <= 1024 and
- * nz > 0, else PBRT_E_INVALID; in and out distinct.  The _dev form takes device pointers (taps included), is queued and recordable. */
+ * nz > 0 and in / out not overlapping, else PBRT_E_INVALID.  The _dev form takes device pointers (taps included), is queued and recordable. */
 int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const float *taps, const float *in, float *out);
 int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *d_taps, const void *d_in, void *d_out);
 

@@ -301,6 +301,8 @@ def axial_fir(rf, taps, out=None):
         nx, nz = (rf.shape if len(rf.shape) == 2 else (1, rf.shape[0]))
         d_taps = _to_dev(cx, taps, (n_taps,))
         d_out = out if out is not None else _capi.DeviceBuffer(cx, rf.shape)
+        if d_out.nbytes != nx * nz * 4:
+            raise ValueError("out must hold nx * nz float32")
         cx.check(cx.lib.pbrt_axial_fir_dev(cx.handle, nx, nz, K, d_taps.ptr, rf.ptr, d_out.ptr), "pbrt_axial_fir_dev")
         d_out._keep = (rf, d_taps)
         return d_out

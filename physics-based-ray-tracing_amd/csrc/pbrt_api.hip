@@ -2787,7 +2787,7 @@ int pbrt_bf_beamform(pbrt_ctx *ctx, const pbrt_bf_params *p, const float *data, 
 }
 int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *d_taps, const void *d_in, void *d_out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_taps && d_in && d_out && d_in != d_out);
+    NEED(ctx, d_taps && d_in && d_out && !ranges_overlap(d_in, (size_t)nx * nz * 4, d_out, (size_t)nx * nz * 4));
     int rc = fir_check(ctx, nx, nz, K);
     if (rc) return rc;
     if (nx == 0) return PBRT_OK;
@@ -2796,7 +2796,7 @@ int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, cons
 }
 int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const float *taps, const float *in, float *out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, taps && in && out && in != out);
+    NEED(ctx, taps && in && out && !ranges_overlap(in, (size_t)nx * nz * 4, out, (size_t)nx * nz * 4));
     int rc = fir_check(ctx, nx, nz, K);
     if (rc) return rc;
     const uint32_t n = nx * nz;
@@ -2842,7 +2842,8 @@ int pbrt_das_beamform_probe(pbrt_ctx *ctx, const pbrt_das_params *p, const float
 
 int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf, void *d_env) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_rf && d_env && d_rf != d_env && nz <= ENV_MAX_N && (uint64_t)nx * nz < 0xffffffffull);
+    NEED(ctx, d_rf && d_env && nz <= ENV_MAX_N && (uint64_t)nx * nz < 0xffffffffull);
+    NEED(ctx, !ranges_overlap(d_rf, (size_t)nx * nz * 4, d_env, (size_t)nx * nz * 4));
     if (nx == 0 || nz == 0) return PBRT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return env_enqueue(ctx, nx, nz, (const float *)d_rf, (float *)d_env);
@@ -2883,7 +2884,7 @@ int pbrt_log_compress(pbrt_ctx *ctx, uint32_t n, const float *env, float dynamic
 int pbrt_us_apply_pulse_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,
                             const void *d_in, void *d_out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_in && d_out && d_in != d_out);
+    NEED(ctx, d_in && d_out && !ranges_overlap(d_in, (size_t)n_traces * time_samples * 4, d_out, (size_t)n_traces * time_samples * 4));
     uint32_t K = 0;
     int rc = pulse_check(ctx, n_traces, time_samples, fs, frequency, sigma, &K);
     if (rc) return rc;
@@ -2895,7 +2896,7 @@ int pbrt_us_apply_pulse_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samp
 int pbrt_us_apply_pulse(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,
                         const float *in, float *out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, in && out && in != out);
+    NEED(ctx, in && out && !ranges_overlap(in, (size_t)n_traces * time_samples * 4, out, (size_t)n_traces * time_samples * 4));
     uint32_t K = 0;
     int rc = pulse_check(ctx, n_traces, time_samples, fs, frequency, sigma, &K);
     if (rc) return rc;

@@ -30,6 +30,14 @@ def _unit(cycles, dtype):
     return np.cos(ang).astype(dtype), np.sin(ang).astype(dtype)
 
 
+def _complex(re, im):
+    """re + i im as complex128, component by component: the product 1j * im of complex arithmetic turns an infinite im into a NaN real
+    part (0 * inf), which no kernel computes"""
+    out = np.empty(np.shape(re), np.complex128)
+    out.real, out.imag = re, im
+    return out
+
+
 def rf2iq(x, fs, t0, f_d, D, taps, dtype=np.float64):
     """x [n, T] real, sample j at t0 + j / fs -> (iq [n, Td] complex, B [n, Td]), Td = ceil(T / D):
          u_j = x_j cos(2 pi f_d t_j), v_j = -x_j sin(2 pi f_d t_j),  iq[m] = 2 sum_{k = -K .. K} h[k] (u + i v)[m D - k], zero outside"""
@@ -47,7 +55,7 @@ def rf2iq(x, fs, t0, f_d, D, taps, dtype=np.float64):
     if dtype is np.float64:
         re = np.stack([np.convolve(row, h, "full")[K + m] for row in u])
         im = np.stack([np.convolve(row, h, "full")[K + m] for row in v])
-        return 2.0 * (re + 1j * im), B
+        return _complex(2.0 * re, 2.0 * im), B
     # float32: products and sums in order of increasing k
     pad = np.zeros((n, K), dtype)
     up, vp = np.concatenate([pad, u, pad, np.zeros((n, D), dtype)], axis=1), np.concatenate([pad, v, pad, np.zeros((n, D), dtype)], axis=1)
@@ -57,7 +65,7 @@ def rf2iq(x, fs, t0, f_d, D, taps, dtype=np.float64):
         idx = m + 2 * K - j
         re = re + hd[j] * up[:, idx]
         im = im + hd[j] * vp[:, idx]
-    return (dtype(2) * re).astype(np.float64) + 1j * (dtype(2) * im).astype(np.float64), B
+    return _complex(dtype(2) * re, dtype(2) * im), B
 
 
 def iq_beamform(iq, tx, elem, x, z, fs, c, f_d, t0=0.0, f_number=1.0, interpolation="linear", compound="sum", dtype=np.float64):
@@ -85,7 +93,7 @@ def iq_beamform(iq, tx, elem, x, z, fs, c, f_d, t0=0.0, f_number=1.0, interpolat
         B = b if B is None else B + b
     if compound == "mean":
         img_re, img_im, B = img_re / dtype(A), img_im / dtype(A), B / A
-    return img_re.astype(np.float64) + 1j * img_im.astype(np.float64), B
+    return _complex(img_re, img_im), B
 
 
 def modulus(iq):
@@ -98,3 +106,8 @@ def response(taps, f, fs):
     h = np.asarray(taps, np.float64).ravel()
     k = np.arange(len(h)) - len(h) // 2
     return np.sum(h * np.exp(-2j * np.pi * f * k / fs))
+
+
+def rf2iq_bad_mask(T, K, D, j):
+    """the outputs m in [0, ceil(T / D)) of a trace that a bad sample at index j reaches: |m D - j| <= K"""
+    return np.abs(np.arange(-(-T // D)) * D - j) <= K

@@ -199,3 +199,124 @@ def lateral_width(rf, iz, level=0.5):
         return abs(i - k) + (prof[i] - thr) / (prof[i] - prof[j])
 
     return reach(-1) + reach(+1)
+
+
+# ---- non-finite samples (test_imgform_nonfinite_restatement.py on the CPU, test_gpu_imgform_nonfinite.py on the GPU) --------------
+FINITE, NAN, POS_INF, NEG_INF = 0, 1, 2, 3
+
+
+def classes(img):
+    """the class of every value -- FINITE, NAN, POS_INF or NEG_INF; a complex image gives [..., 2], its real and imaginary parts"""
+    img = np.asarray(img)
+    if np.iscomplexobj(img):
+        return np.stack([classes(img.real), classes(img.imag)], axis=-1)
+    out = np.full(img.shape, FINITE, np.uint8)
+    out[np.isnan(img)] = NAN
+    out[img == np.inf] = POS_INF
+    out[img == -np.inf] = NEG_INF
+    return out
+
+
+def sample_reads(tx, elem, x, z, T, fs, c, t0=0.0, f_number=1.0, interpolation="linear"):
+    """for every transmission a: (lo, hi, ok, wlo, whi), each [E, nx, nz].  Where ok, the pair (a, e) of the pixel reads the samples
+    lo .. hi of its trace (the float64 position's window: floor(s) and the next sample, or the rounded one).  A position within
+    das_util.EDGE_SAMPLES of a whole sample (linear) or of a half sample (nearest) may take the neighbouring window in another order
+    of operations, or meet a weight of exactly 0 there: a bad sample in wlo .. whi leaves the pixel's class open (wlo > whi: none)"""
+    for s, use, _, _ in _positions(tx, elem, x, z, fs, c, t0, f_number):
+        fl = np.floor(s)
+        if interpolation == "nearest":
+            r = np.rint(s)
+            ok = (r >= 0) & (r <= T - 1) & use
+            lo = hi = r
+            near = np.abs(s - fl - 0.5) < du.EDGE_SAMPLES
+            wlo, whi = fl, fl + 1
+        else:
+            ok = (((fl >= 0) & (fl < T - 1)) | (s == T - 1)) & use
+            lo, hi = fl, np.minimum(fl + 1, T - 1)
+            n = np.rint(s)
+            near = np.abs(s - n) < du.EDGE_SAMPLES
+            wlo, whi = n - 1, n + 1
+        near &= use
+        yield (np.clip(lo, 0, T - 1).astype(int), np.clip(hi, 0, T - 1).astype(int), ok,
+               np.where(near, wlo, 1).astype(int), np.where(near, whi, 0).astype(int))
+
+
+def read_mask(g, T, c):
+    """[A, E, T]: the samples that at least one kept pixel of the case g (walk_cases.geometry) reads"""
+    keep = ~g["left_out"]
+    kw = g["kw"]
+    M = np.zeros((g["A"], g["E"], T), bool)
+    ee = np.broadcast_to(np.arange(g["E"])[:, None, None], (g["E"],) + keep.shape)
+    for a, (lo, hi, ok, _, _) in enumerate(sample_reads(g["tx"], g["elem"], g["x"], g["z"], T, g["fs"], c, f_number=kw["f_number"],
+                                                        interpolation=kw["interpolation"])):
+        sel = ok & keep[None]
+        M[a][ee[sel], lo[sel]] = True
+        M[a][ee[sel], hi[sel]] = True
+    return M
+
+
+def bad_sites(g, T, c, n, seed):
+    """n sites (a, e, t) that kept pixels read -- spread over the transmissions (every trip of angles) and over the elements in use, the
+    first and the last of them included (every block of 64) -- and, where some trace lies outside every kept pixel's aperture, one site
+    in such a trace, which must change nothing.  -> (sites [(a, e, t)], idle: the site no pixel reaches, or None)"""
+    M = read_mask(g, T, c)
+    rng = np.random.default_rng(seed)
+    A = g["A"]
+    sites = []
+    for k in range(n):
+        a = (k * A) // n if k < n - 1 else A - 1
+        used = np.flatnonzero(M[a].any(axis=1))
+        e = int(used[int(round(k / max(n - 1, 1) * (len(used) - 1)))])
+        sites.append((int(a), e, int(rng.choice(np.flatnonzero(M[a, e])))))
+    idle = None
+    unused = np.flatnonzero(~M.any(axis=(0, 2)))
+    if len(unused):
+        idle = (A // 2, int(unused[len(unused) // 2]), T // 2)
+        sites.append(idle)
+    return sites, idle
+
+
+def near_bad(g, T, c, sites):
+    """[nx, nz]: pixels with a pair whose interpolation window lies next to a bad sample and whose position lies within
+    das_util.EDGE_SAMPLES of a whole sample (linear) or of a half sample (nearest): left out, like the pixels of `margins`"""
+    kw = g["kw"]
+    out = np.zeros(g["left_out"].shape, bool)
+    for a, (_, _, _, wlo, whi) in enumerate(sample_reads(g["tx"], g["elem"], g["x"], g["z"], T, g["fs"], c, f_number=kw["f_number"],
+                                                         interpolation=kw["interpolation"])):
+        for sa, e, t in sites:
+            if sa == a:
+                out |= (wlo[e] <= t) & (t <= whi[e])
+    return out
+
+
+def with_bad(data, sites, value):
+    """a copy of the channel data with `value` at every site"""
+    out = np.array(data, copy=True)
+    for a, e, t in sites:
+        out[a, e, t] = value
+    return out
+
+
+def fir_bad_mask(nz, K, j):
+    """the outputs of a column of nz that a bad sample at index j reaches: |n - j| <= K"""
+    return np.abs(np.arange(nz) - j) <= K
+
+
+def bad_reads(bad, tx, elem, x, z, fs, c, t0=0.0, f_number=1.0, interpolation="linear"):
+    """bad [A, E, T]: the non-finite samples of some channel data -> (sure, open), each [nx, nz].  sure: a pair of the pixel reads a
+    bad sample and its position lies clear of every whole (linear) or half (nearest) sample; open: a pair within
+    das_util.EDGE_SAMPLES of one has a bad sample in the window it may take.  A pixel that is open and not sure has a class that rests
+    on such pairs alone."""
+    bad = np.asarray(bad, bool)
+    A, E, T = bad.shape
+    count = np.concatenate([np.zeros((A, E, 1), np.int64), np.cumsum(bad, axis=2)], axis=2)      # count[..., k]: bad samples below k
+    ee = np.arange(E)[:, None, None]
+    sure = open_ = None
+    for a, (lo, hi, ok, wlo, whi) in enumerate(sample_reads(tx, elem, x, z, T, fs, c, t0, f_number, interpolation)):
+        near = wlo <= whi
+        hit = ok & ~near & (count[a][ee, hi + 1] - count[a][ee, lo] > 0)
+        w0, w1 = np.clip(wlo, 0, T), np.clip(whi + 1, 0, T)
+        maybe = near & (w1 > w0) & (count[a][ee, np.maximum(w1, w0)] - count[a][ee, w0] > 0)
+        sure = hit.any(axis=0) if sure is None else sure | hit.any(axis=0)
+        open_ = maybe.any(axis=0) if open_ is None else open_ | maybe.any(axis=0)
+    return sure, open_
