@@ -2,7 +2,7 @@
 """The reference's ultrasound driver flow on this library: scene dict -> acquisition -> delay-and-sum -> envelope ->
 log compression -> finite-difference roughness loop (what USMain.py does at :26-90, :93-224, :257-289), without the
 plotting.  Writes the B-mode image and the channel buffer as .npy.
-    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [--iq [--decimation D]] [out_dir]
+    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [--iq [--decimation D]] [--polar] [out_dir]
 --convex: the same flow under a curved (abdominal) array -- 64 elements on a 40 mm arc of 40 degrees (DESIGN D18); the sensor
 transform puts the apex where the linear array sits, and the scan is given in the sensor's frame, whose origin is the centre of
 curvature.
@@ -11,7 +11,10 @@ image along z, around the carrier (p-DAS) or twice the carrier (F-DMAS): the ref
 frequency AT the carrier, so the example picks lambda / 8 for p-DAS and lambda / 16 for F-DMAS itself and says so.
 --iq: the I/Q chain (DESIGN D20) -- the channel data are demodulated at the carrier and decimated by --decimation (default 4: 50 MHz ->
 12.5 MHz), delay-and-sum runs on complex samples and the envelope is the modulus of each pixel, which needs no carrier on the grid: the
-example then scans at lambda / 2 axially.  Delay-and-sum only."""
+example then scans at lambda / 2 axially.  Delay-and-sum only.
+--polar: the beamformer runs on a sector (PolarScan, DESIGN D21) -- rays over the opening angle of the curved array, or over the x-range
+seen from the deepest z under the linear one -- the envelope is taken along the rays, and the scan conversion brings it onto the Cartesian
+grid of the other runs.  Combines with every option above; --profile prints the device time of each step (HIP events)."""
 import argparse
 import os
 import sys
@@ -30,6 +33,8 @@ ap.add_argument("--beamformer", choices=("das", "pdas", "fdmas"), default="das")
 ap.add_argument("--p", type=float, default=2.0)
 ap.add_argument("--iq", action="store_true")
 ap.add_argument("--decimation", type=int, default=4)
+ap.add_argument("--polar", action="store_true")
+ap.add_argument("--profile", action="store_true")
 ap.add_argument("out_dir", nargs="?", default=".")
 args = ap.parse_args()
 if args.iq and args.beamformer != "das":
@@ -66,6 +71,8 @@ if args.iq:
     RENDER.update(iq=True, decimation=args.decimation, step=lam / 2)
     print(f"I/Q chain: demodulated at {integ.frequency / 1e6:.1f} MHz, {integ.fs / 1e6:.0f} -> {integ.fs / args.decimation / 1e6:.2f} MHz, "
           f"scan step lambda / 2 = {lam / 2 * 1e6:.0f} um (the Hilbert envelope of the RF chain needs lambda / 4 or finer)")
+if args.polar:
+    RENDER.update(scan="polar")
 if args.beamformer != "das":
     f_lo, f_hi = beamformer.band(mi.build_probe("linear", 64, 1.2e-4, integ.frequency, 70))
     print(f"{beamformer}: band {f_lo / 1e6:.2f} - {f_hi / 1e6:.2f} MHz needs an axial rate c / (2 step) above {2 * f_hi / 1e6:.2f} MHz; "
@@ -76,6 +83,21 @@ t = time.perf_counter()
 display, bmode, (x_scan, z_scan) = mi.us_render(scene, **RENDER)
 print(f"B-mode {display.shape[0]} x {display.shape[1]} pixels in {(time.perf_counter() - t) * 1e3:.1f} ms; "
       f"channel_buf sum {float(np.sum(scene.integrator().channel_buf)):.4g}, max {float(np.max(scene.integrator().channel_buf)):.4g}")
+if args.polar:
+    sector = integ._render_plan.d_bf.shape
+    print(f"sector {sector[0]} rays x {sector[1]} samples = {sector[0] * sector[1]} pixels beamformed, "
+          f"{len(x_scan)} x {len(z_scan)} = {len(x_scan) * len(z_scan)} on the grid")
+if args.profile:   # per step, by HIP events on the library's stream (a context that profiles queues the chain call by call)
+    cx = scene.device().ctx
+    cx.set_profiling(True)
+    acc, N = {}, 10
+    for _ in range(N):
+        mi.us_render(scene, **RENDER)
+        for k, v in cx.image_stats().items():
+            if k.endswith("_ms"):
+                acc[k] = acc.get(k, 0.0) + v / N
+    cx.set_profiling(False)
+    print("device time per step: " + ", ".join(f"{k[:-3]} {v * 1e3:.1f} us" for k, v in acc.items()))
 np.save(os.path.join(out_dir, "bmode_display.npy"), display)
 np.save(os.path.join(out_dir, "channel_buf.npy"), np.asarray(scene.integrator().channel_buf))
 

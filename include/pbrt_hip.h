@@ -669,6 +669,59 @@ int pbrt_rf2iq_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, floa
 int pbrt_iq_envelope(pbrt_ctx *ctx, uint32_t n, const float *iq, float *env);
 int pbrt_iq_envelope_dev(pbrt_ctx *ctx, uint32_t n, const void *d_iq, void *d_env);
 
+/* ---- sector scans: beamforming on pixel tables, and scan conversion -------------------------------------------------
+ * replaces: ultraspy's beamformers on a PolarScan (its beamformers take ravelled pixel lists; absent here as above, so this is the
+ * build's own definition).  A scan is two tables px[n0][n1], pz[n0][n1] (float, axis 1 fastest, metres, in the probe's frame) instead
+ * of the axes x[nx], z[nz]: das.nx = n0, das.nz = n1, and pixel (i0, i1) sits at ((double)px[i0 n1 + i1], (double)pz[i0 n1 + i1]).
+ * Nothing else differs from the call the method names -- pbrt_das_beamform (PBRT_SCAN_DAS), pbrt_bf_beamform (PBRT_BF_PDAS,
+ * PBRT_BF_FDMAS) or pbrt_iq_beamform (PBRT_SCAN_IQ): the same first arrival, f64 sample position, range rules, f-number aperture of
+ * the line (probe = 0) or of the element table (probe = 1), interpolation, non-linearity or carrier rotation, and the same order of
+ * the sums (wave w = e % 4, trips of angles, elements, angles; tiles of 8 x 8 over (i0, i1)).  On the tables of a separable scan,
+ * px[i0][i1] = x[i0], pz[i0][i1] = z[i1], the result is that call's bit for bit.  out [n0][n1] floats, or (re, im) pairs for
+ * PBRT_SCAN_IQ, whose data are pairs too; a pixel that uses no element is exactly 0.
+ * One family carries the method and the probe flag in its parameter block.  Refused with PBRT_E_INVALID: everything pbrt_das_beamform
+ * refuses, a method other than the four, probe > 1, PBRT_BF_PDAS with p not finite or outside [1, 8], PBRT_SCAN_IQ with demod_freq
+ * not finite or negative (p is read by PBRT_BF_PDAS only, demod_freq by PBRT_SCAN_IQ only).
+ * The _dev forms take device pointers, are queued on the context's stream and recordable like pbrt_das_beamform_dev;
+ * pbrt_scan_first_arrival_dev writes d_table[a][i0][i1] (double) = min_e' (tx_delays[a][e'] + |pixel - element e'| / c), the statement
+ * of pbrt_das_first_arrival_dev on the tables, and pbrt_scan_beamform_table_dev beamforms with it: bit-equal to the direct form. */
+#define PBRT_SCAN_DAS 0u
+#define PBRT_SCAN_IQ 3u
+typedef struct pbrt_scan_params {
+    pbrt_das_params das; /* das.nx = n0, das.nz = n1; das.fs: the rate of the data (PBRT_SCAN_IQ: of the I/Q data) */
+    uint32_t method;     /* PBRT_SCAN_DAS, PBRT_BF_PDAS, PBRT_BF_FDMAS, PBRT_SCAN_IQ */
+    float p;             /* PBRT_BF_PDAS: finite, 1 <= p <= 8 */
+    float demod_freq;    /* PBRT_SCAN_IQ: Hz, finite and >= 0 */
+    uint32_t probe;      /* 0: element positions [n_elements]; 1: the element table [n_elements][4] of pbrt_us_array_elements */
+} pbrt_scan_params;
+int pbrt_scan_beamform(pbrt_ctx *ctx, const pbrt_scan_params *p, const float *data, const float *tx_delays, const float *elem,
+                       const float *px, const float *pz, float *out);
+int pbrt_scan_beamform_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
+                           const void *d_px, const void *d_pz, void *d_out);
+int pbrt_scan_beamform_table_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_data, const void *d_table, const void *d_elem,
+                                 const void *d_px, const void *d_pz, void *d_out);
+int pbrt_scan_first_arrival_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_tx_delays, const void *d_elem,
+                                const void *d_px, const void *d_pz, void *d_table);
+/* replaces: the scan conversion a sector image needs before it is displayed (ultraspy users interpolate a PolarScan image onto a
+ * grid with scipy).  src [n_theta][n_rho] (rho fastest) lies on the uniform axes theta_i = theta0 + i dtheta (radians, from the +z
+ * axis towards +x) and rho_j = rho0 + j drho around the origin (ox, oz); dst [nx][nz] on the axes x[nx], z[nz].  Per output pixel,
+ * in f64: dx = x - ox, dz = z - oz, rho = sqrt(dx dx + dz dz), theta = atan2(dx, dz), u = (theta - theta0) / dtheta,
+ * v = (rho - rho0) / drho.  Inside iff 0 <= u <= n_theta - 1 and 0 <= v <= n_rho - 1; outside pixels are `fill` (any float, NaN
+ * included).  Inside: i = min(floor(u), n_theta - 2), j = min(floor(v), n_rho - 2), the weights u - i and v - j rounded once to f32,
+ * and three linear interpolations v0 + w (v1 - v0) (one fmaf each) in f32, in this order: along rho in row i, along rho in row i + 1,
+ * then along theta.  Non-finite samples propagate through them and touch no pixel whose four corners do not hold them.
+ * PBRT_E_INVALID for n_theta or n_rho < 2, nx or nz == 0, a non-finite theta0 / dtheta / rho0 / drho / ox / oz, and a zero step.
+ * src and dst distinct.  The _dev form takes device pointers, is queued on the context's stream and recordable. */
+typedef struct pbrt_scan_convert_params {
+    uint32_t n_theta, n_rho, nx, nz;
+    double theta0, dtheta, rho0, drho, ox, oz;
+    float fill;
+    uint32_t pad;
+} pbrt_scan_convert_params;
+int pbrt_scan_convert(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const float *src, const float *x, const float *z, float *dst);
+int pbrt_scan_convert_dev(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *d_src, const void *d_x, const void *d_z,
+                          void *d_dst);
+
 /* waits for everything queued on the context's stream */
 int pbrt_ctx_synchronize(pbrt_ctx *ctx);
 /* Device buffers for a caller without a GPU library of its own (the reference's driver is NumPy: USMain.py:103-121).
@@ -697,6 +750,7 @@ int pbrt_get_image_stats(pbrt_ctx *ctx, pbrt_image_stats *out);
  * pbrt_ctx_record_begin and pbrt_ctx_record_end the queueing entry points (pbrt_us_acquire_queue_dev, pbrt_us_apply_pulse_dev,
  * pbrt_das_beamform_dev, pbrt_das_beamform_table_dev, pbrt_bf_beamform_dev, pbrt_bf_beamform_table_dev, pbrt_axial_fir_dev,
  * pbrt_rf2iq_dev, pbrt_iq_beamform_dev, pbrt_iq_beamform_table_dev, pbrt_iq_envelope_dev,
+ * pbrt_scan_beamform_dev, pbrt_scan_beamform_table_dev, pbrt_scan_first_arrival_dev, pbrt_scan_convert_dev,
  * pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
  * stream instead of run; pbrt_graph_launch replays the recording in one submission and returns without waiting, exactly as if
  * the recorded calls had just been made: same kernels, same arguments, same results bit for bit, the acquisition's statistics

@@ -149,6 +149,19 @@ class IqParams(C.Structure):
     _fields_ = [("das", DasParams), ("demod_freq", C.c_float), ("probe", C.c_uint32)]
 
 
+class ScanParams(C.Structure):
+    _fields_ = [("das", DasParams), ("method", C.c_uint32), ("p", C.c_float), ("demod_freq", C.c_float), ("probe", C.c_uint32)]
+
+
+SCAN_DAS, SCAN_IQ = 0, 3
+
+
+class ScanConvertParams(C.Structure):
+    _fields_ = [("n_theta", C.c_uint32), ("n_rho", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32), ("theta0", C.c_double),
+                ("dtheta", C.c_double), ("rho0", C.c_double), ("drho", C.c_double), ("ox", C.c_double), ("oz", C.c_double),
+                ("fill", C.c_float), ("pad", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("kernel_ms", C.c_double), ("bounce_ms", C.c_double), ("bounce_launches", C.c_uint32),
@@ -228,6 +241,13 @@ SIGNATURES = {
     "pbrt_rf2iq_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "pbrt_iq_envelope": (C.c_int, [_P, C.c_uint32, _F, _F]),
     "pbrt_iq_envelope_dev": (C.c_int, [_P, C.c_uint32, _P, _P]),
+    # pixel-table scans and scan conversion (DESIGN D21)
+    "pbrt_scan_beamform": (C.c_int, [_P, C.POINTER(ScanParams), _F, _F, _F, _F, _F, _F]),
+    "pbrt_scan_beamform_dev": (C.c_int, [_P, C.POINTER(ScanParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_scan_beamform_table_dev": (C.c_int, [_P, C.POINTER(ScanParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_scan_first_arrival_dev": (C.c_int, [_P, C.POINTER(ScanParams), _P, _P, _P, _P, _P]),
+    "pbrt_scan_convert": (C.c_int, [_P, C.POINTER(ScanConvertParams), _F, _F, _F, _F]),
+    "pbrt_scan_convert_dev": (C.c_int, [_P, C.POINTER(ScanConvertParams), _P, _P, _P, _P]),
     "pbrt_ctx_synchronize": (C.c_int, [_P]),
     "pbrt_dev_alloc": (C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     "pbrt_dev_free": (C.c_int, [_P, _P]),

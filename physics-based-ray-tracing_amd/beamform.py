@@ -15,6 +15,9 @@ their arithmetic, from the papers, and the axial band-pass they need are DESIGN.
 I/Q data (`data_info['is_iq']`, USMain.py:158): rf2iq demodulates and decimates, DelayAndSum(is_iq=True) / iq_beamform beamform complex
 samples, and the envelope of an I/Q image is its modulus (iq_envelope) -- DESIGN.md D20.
 
+Sector scans: PolarScan beside GridScan, scan_beamform / scan_first_arrival on pixel tables (every method above),
+scan_convert from the sector onto a Cartesian grid, us_render(scan="polar").
+
 All work runs on the GPU through libpbrt_hip.so (no CPU fallback; `on_gpu` is accepted for compatibility)."""
 from __future__ import annotations
 
@@ -192,6 +195,136 @@ def iq_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, t0=0.
         raise ValueError(f"demod_freq must be finite and >= 0, got {demod_freq}")
     return _beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
                      compound=compound, out=out, table=table, demod_freq=demod_freq)
+
+
+_SCAN_METHODS = ("das", "pdas", "fdmas", "iq")
+
+
+def _scan_params(das, method, p, demod_freq, probe) -> "_capi.ScanParams":
+    sp = _capi.ScanParams()
+    sp.das = das
+    sp.method = {"das": _capi.SCAN_DAS, "pdas": _capi.BF_PDAS, "fdmas": _capi.BF_FDMAS, "iq": _capi.SCAN_IQ}[method]
+    sp.p, sp.demod_freq, sp.probe = float(p), float(demod_freq or 0.0), int(bool(probe))
+    return sp
+
+
+def _pixel_tables(cx, px, pz, dev):
+    """the two pixel tables [n0, n1] of a scan as they are handed on (host float32 arrays, or DeviceBuffers), and (n0, n1)"""
+    if _is_dev(px) != _is_dev(pz):
+        raise ValueError("px and pz must both be host arrays or both DeviceBuffers")
+    if not _is_dev(px):
+        px, pz = _capi.f32(np.asarray(px)), _capi.f32(np.asarray(pz))
+    if len(px.shape) != 2 or tuple(px.shape) != tuple(pz.shape):
+        raise ValueError(f"px and pz must be two tables of one shape [n0, n1], got {list(px.shape)} and {list(pz.shape)}")
+    shape = tuple(int(v) for v in px.shape)
+    if dev and not _is_dev(px):
+        px, pz = _capi.DeviceBuffer.from_host(cx, px), _capi.DeviceBuffer.from_host(cx, pz)
+    return px, pz, shape
+
+
+def scan_first_arrival(tx_delays, elem, px, pz, sound_speed, out=None):
+    """das_first_arrival for a scan given as pixel tables px, pz [n0, n1] (metres, the probe's frame): [n_angles, n0, n1] float64 in
+    HBM, t_tx(a; pixel) = min_e (tx_delays[a, e] + distance to element e / c) (pbrt_scan_first_arrival_dev).  elem [n_elements] or
+    the element table [n_elements, 4].  On the tables of a separable scan it equals das_first_arrival bit for bit."""
+    cx = next((a.ctx for a in (tx_delays, elem, px, pz) if _is_dev(a)), None) or _capi.default_context()
+    d_tx = tx_delays if _is_dev(tx_delays) else _to_dev(cx, np.atleast_2d(np.asarray(tx_delays)))
+    A, E = d_tx.shape
+    elem, probe, eshape = _elem_arg(elem, E)
+    d_ex = _to_dev(cx, elem, eshape)
+    d_px, d_pz, (n0, n1) = _pixel_tables(cx, px, pz, True)
+    sp = _scan_params(_das_params(A, E, 2, n0, n1, 1.0, sound_speed, 0.0, 0.0, "linear", "sum"), "das", 2.0, None, probe)
+    tab = out if out is not None else _capi.DeviceBuffer(cx, (A, n0, n1), np.float64)
+    if tab.nbytes != A * n0 * n1 * 8:
+        raise ValueError("out must hold n_angles * n0 * n1 float64")
+    cx.check(cx.lib.pbrt_scan_first_arrival_dev(cx.handle, C.byref(sp), d_tx.ptr, d_ex.ptr, d_px.ptr, d_pz.ptr, tab.ptr),
+             "pbrt_scan_first_arrival_dev")
+    tab._keep = (d_tx, d_ex, d_px, d_pz)
+    return tab
+
+
+def scan_beamform(data, tx_delays, elem, px, pz, fs, sound_speed, method="das", p=2.0, demod_freq=None, t0=0.0, f_number=1.0,
+                  interpolation="linear", compound="sum", out=None, table=None):
+    """Beamforming on a scan given as two pixel tables px, pz [n0, n1] (metres, the probe's frame; a PolarScan's .pixels(), or any
+    other list of pixels) -> image [n0, n1] (DESIGN D21, pbrt_scan_beamform).  method: "das" (das_beamform's arithmetic), "pdas" (with
+    p) / "fdmas" (nonlinear_beamform's, BEFORE the axial band-pass) or "iq" (iq_beamform's: complex64 data at the rate fs, demodulated
+    at demod_freq, a complex64 image).  On np.meshgrid(x, z, indexing="ij") the result is that call's on the axes x, z, bit for bit.
+    The host / DeviceBuffer rule is das_beamform's: host arrays in -> a host array out; `data` a DeviceBuffer ->
+    pbrt_scan_beamform_dev, queued, a DeviceBuffer out (`out`, or a new one; host tables are uploaded), with `table` from
+    scan_first_arrival -> pbrt_scan_beamform_table_dev.  elem [n_elements] or the element table [n_elements, 4]."""
+    if method not in _SCAN_METHODS:
+        raise ValueError(f"method must be one of {_SCAN_METHODS}, got {method!r}")
+    iq = method == "iq"
+    if iq:
+        if demod_freq is None or not (np.isfinite(float(demod_freq)) and float(demod_freq) >= 0.0):
+            raise ValueError(f"demod_freq must be finite and >= 0, got {demod_freq}")
+    dev = _is_dev(data)
+    dtype, width = (np.complex64, 8) if iq else (np.float32, 4)
+    cx = data.ctx if dev else _capi.default_context()
+    if not dev:
+        data = np.ascontiguousarray(data, dtype=dtype)
+    elif iq != (data.dtype.kind == "c"):
+        raise ValueError(f"the channel data must be {'complex64 (I/Q)' if iq else 'float32 (RF)'}, got a {data.dtype} DeviceBuffer")
+    if len(data.shape) != 3:
+        raise ValueError("data must be [n_angles, n_elements, time_samples]")
+    A, E, T = data.shape
+    elem, probe, eshape = _elem_arg(elem, E)
+    gx, gz, (n0, n1) = _pixel_tables(cx, px, pz, dev)
+    sp = _scan_params(_das_params(A, E, T, n0, n1, fs, sound_speed, t0, f_number, interpolation, compound), method, p, demod_freq, probe)
+    if not dev:
+        tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
+        ex = _capi.f32(np.asarray(elem).reshape(eshape))
+        res = np.empty((n0, n1), dtype=dtype)
+        cx.check(cx.lib.pbrt_scan_beamform(cx.handle, C.byref(sp), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
+                                           _capi.addr(gz), _capi.addr(res)), "pbrt_scan_beamform")
+        return res
+    d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem, eshape)
+    d_out = out if out is not None else _capi.DeviceBuffer(cx, (n0, n1), dtype)
+    if d_out.nbytes != n0 * n1 * width:
+        raise ValueError(f"out must hold n0 * n1 {np.dtype(dtype).name}")
+    name = "pbrt_scan_beamform_dev"
+    if table is not None:   # the first-arrival times of this scan, made once (scan_first_arrival)
+        if table.nbytes != A * n0 * n1 * 8:
+            raise ValueError("table must be the [n_angles, n0, n1] float64 buffer of scan_first_arrival for this scan")
+        name = "pbrt_scan_beamform_table_dev"
+    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(sp), data.ptr, (d_tx if table is None else table).ptr, d_ex.ptr, gx.ptr, gz.ptr,
+                                   d_out.ptr), name)
+    d_out._keep = (d_tx, d_ex, gx, gz, table)  # the queued kernel reads them: they live as long as its result
+    return d_out
+
+
+def scan_convert(img, scan, x_axis, z_axis, fill=0.0, out=None):
+    """A sector image img [n_theta, n_rho] on the PolarScan `scan` resampled onto the Cartesian axes x_axis [nx], z_axis [nz] ->
+    [nx, nz] (pbrt_scan_convert, DESIGN D21): bilinear in (theta, rho), pixels outside the sector are `fill`.  A host array in gives a
+    host array out; a DeviceBuffer in gives a DeviceBuffer out, queued (the axes DeviceBuffers, or host arrays that are uploaded)."""
+    dev = _is_dev(img)
+    cx = img.ctx if dev else _capi.default_context()
+    if not dev:
+        img = _capi.f32(np.asarray(img))
+    if tuple(img.shape) != scan.shape:
+        raise ValueError(f"the image must have the scan's shape {list(scan.shape)} = [n_theta, n_rho], got {list(img.shape)}")
+    if dev and img.dtype != np.float32:
+        raise ValueError(f"scan_convert takes a float32 image (an envelope), got a {img.dtype} DeviceBuffer")
+    nx = x_axis.shape[0] if _is_dev(x_axis) else np.asarray(x_axis).size
+    nz = z_axis.shape[0] if _is_dev(z_axis) else np.asarray(z_axis).size
+    sc = _capi.ScanConvertParams()
+    sc.n_theta, sc.n_rho, sc.nx, sc.nz = scan.shape[0], scan.shape[1], int(nx), int(nz)
+    sc.theta0, sc.dtheta = float(scan.thetas[0]), float((scan.thetas[-1] - scan.thetas[0]) / (len(scan.thetas) - 1))
+    sc.rho0, sc.drho = float(scan.rhos[0]), float((scan.rhos[-1] - scan.rhos[0]) / (len(scan.rhos) - 1))
+    sc.ox, sc.oz = scan.origin
+    sc.fill = float(fill)
+    if dev:
+        d_x, d_z = _to_dev(cx, x_axis, (nx,)), _to_dev(cx, z_axis, (nz,))
+        d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz))
+        if d_out.nbytes != nx * nz * 4:
+            raise ValueError("out must hold nx * nz float32")
+        cx.check(cx.lib.pbrt_scan_convert_dev(cx.handle, C.byref(sc), img.ptr, d_x.ptr, d_z.ptr, d_out.ptr), "pbrt_scan_convert_dev")
+        d_out._keep = (img, d_x, d_z)
+        return d_out
+    gx, gz = _capi.f32(np.asarray(x_axis).ravel()), _capi.f32(np.asarray(z_axis).ravel())
+    res = np.empty((nx, nz), np.float32)
+    cx.check(cx.lib.pbrt_scan_convert(cx.handle, C.byref(sc), _capi.addr(img), _capi.addr(gx), _capi.addr(gz), _capi.addr(res)),
+             "pbrt_scan_convert")
+    return res
 
 
 RF2IQ_MAX_DECIMATION = 8
@@ -487,6 +620,78 @@ class GridScan:
         return (len(self.x_axis), len(self.z_axis))
 
 
+def _uniform_axis(axis, name) -> np.ndarray:
+    """a uniform, increasing axis of two samples at least (to 1e-6 of its step, as axial_rate asks of a z axis); ValueError otherwise"""
+    a = np.asarray(axis, dtype=np.float64).ravel()
+    if a.size < 2:
+        raise ValueError(f"PolarScan: the {name} axis needs two samples at least")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"PolarScan: the {name} axis must be finite")
+    d = np.diff(a)
+    step = (a[-1] - a[0]) / (a.size - 1)
+    if not (step > 0.0 and np.all(np.abs(d - step) <= 1e-6 * step)):
+        raise ValueError(f"PolarScan: the {name} axis must be uniform and increasing (to 1e-6 of its step)")
+    return a
+
+
+class PolarScan:
+    """ultraspy's PolarScan, the sector a curved or a steered array insonifies: pixel (i, j) lies at the angle thetas[i] (radians, from
+    the +z axis towards +x) and the distance rhos[j] from `origin` = (ox, oz), in the probe's frame -- x = ox + rho sin(theta),
+    z = oz + rho cos(theta).  shape == (n_theta, n_rho): rho is the last (axial) axis, so axial_fir and envelope run along the rays.
+    Both axes must be uniform and increasing (scan_convert's rule; ValueError otherwise).  `ultraspy` is absent: the signature
+    (rhos, thetas) is from memory and parity with it is unpinned, as everywhere in this file.  The beamformers take it where they take
+    a GridScan (scan_beamform on its pixel tables); scan_convert brings the result onto a Cartesian grid."""
+
+    def __init__(self, rhos, thetas, origin=(0.0, 0.0)):
+        self.rhos = _uniform_axis(rhos, "rho")
+        self.thetas = _uniform_axis(thetas, "theta")
+        ox, oz = (float(v) for v in origin)
+        if not (np.isfinite(ox) and np.isfinite(oz)):
+            raise ValueError(f"PolarScan: the origin must be finite, got {origin}")
+        self.origin = (ox, oz)
+        self.d_px = self.d_pz = None  # the pixel tables as DeviceBuffers (set by us_render)
+
+    @property
+    def shape(self):
+        return (len(self.thetas), len(self.rhos))
+
+    def pixels(self):
+        """(px, pz), float32 [n_theta, n_rho]: computed in float64, rounded once"""
+        th, rho = self.thetas[:, np.newaxis], self.rhos[np.newaxis, :]
+        return ((self.origin[0] + rho * np.sin(th)).astype(np.float32), (self.origin[1] + rho * np.cos(th)).astype(np.float32))
+
+
+def _axial_axis(scan) -> np.ndarray:
+    """the axis an image of this scan is sampled along in the propagation direction: rho of a PolarScan, z of a GridScan"""
+    return scan.rhos if isinstance(scan, PolarScan) else scan.z_axis
+
+
+def _scan_tables(scan, dev):
+    """what a beamformer hands on for a scan: (True, px, pz) for a PolarScan, (False, x, z) for a GridScan -- the copies in HBM
+    (us_render keeps them there between calls) where the data is a DeviceBuffer"""
+    if isinstance(scan, PolarScan):
+        if dev and scan.d_px is not None and scan.d_pz is not None:
+            return True, scan.d_px, scan.d_pz
+        return (True,) + scan.pixels()
+    gx = scan.d_x if dev and getattr(scan, "d_x", None) is not None else scan.x_axis
+    gz = scan.d_z if dev and getattr(scan, "d_z", None) is not None else scan.z_axis
+    return False, gx, gz
+
+
+def polar_n_theta(rho_max, theta_range, step) -> int:
+    """us_render's rule for the angles of a sector: the smallest count n_theta >= 2 with rho_max * dtheta <= step, dtheta =
+    (theta_range[1] - theta_range[0]) / (n_theta - 1) -- neighbouring rays are no further apart than neighbouring depths anywhere"""
+    rho_max, step, span = float(rho_max), float(step), float(theta_range[1]) - float(theta_range[0])
+    if not (span > 0.0 and rho_max > 0.0 and step > 0.0 and np.isfinite(span * rho_max / step)):
+        raise ValueError(f"a sector needs theta_range[0] < theta_range[1], rho_max > 0 and step > 0, got {theta_range}, {rho_max}, {step}")
+    n = max(2, int(np.ceil(rho_max * span / step)) + 1)
+    while n > 2 and rho_max * (span / (n - 2)) <= step:   # (the quotient above may round either way)
+        n -= 1
+    while rho_max * (span / (n - 1)) > step:
+        n += 1
+    return n
+
+
 class DelayAndSum:
     def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", is_iq=False):
         self.on_gpu = on_gpu  # accepted for compatibility; the beamformer has no CPU path
@@ -538,8 +743,13 @@ class DelayAndSum:
         # tables that already sit in HBM (us_render keeps them there between calls) are used where the data is a DeviceBuffer
         dev = _is_dev(data)
         ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
-        gx = scan.d_x if dev and getattr(scan, "d_x", None) is not None else scan.x_axis
-        gz = scan.d_z if dev and getattr(scan, "d_z", None) is not None else scan.z_axis
+        polar, gx, gz = _scan_tables(scan, dev)
+        if polar:   # a PolarScan: the same arithmetic on its pixel tables (DESIGN D21)
+            return scan_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"],
+                                 method="iq" if self.is_iq else "das", demod_freq=self.demod_freq() if self.is_iq else None,
+                                 t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
+                                 interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out,
+                                 table=table if dev else None)
         if self.is_iq:
             return iq_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], self.demod_freq(),
                                t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
@@ -609,7 +819,7 @@ class _NonlinearBeamformer(DelayAndSum):
         band = self.band(probe)
         if band is None:
             return None
-        fs_ax = axial_rate(scan.z_axis, sound_speed)
+        fs_ax = axial_rate(_axial_axis(scan), sound_speed)   # (a PolarScan: the rate along rho, its last axis)
         f_lo, f_hi = band
         if f_hi >= fs_ax / 2.0:
             c, dz = float(sound_speed), float(sound_speed) / (2.0 * fs_ax)
@@ -619,7 +829,11 @@ class _NonlinearBeamformer(DelayAndSum):
                 f"{c / (4.0 * f_hi):.4g} m would fit -- pass step= to us_render (DESIGN D19)")
         return bandpass_taps(f_lo, f_hi, fs_ax, self.setups["taps_half_length"])
 
-    def _raw(self, data, ai, ex, gx, gz, out, table):
+    def _raw(self, data, ai, ex, gx, gz, out, table, polar=False):
+        if polar:   # gx, gz are the pixel tables of a PolarScan (DESIGN D21)
+            return scan_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], method=self._method,
+                                 p=self.setups.get("p", 2.0), t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
+                                 interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out, table=table)
         return nonlinear_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], method=self._method,
                                   p=self.setups.get("p", 2.0), t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
                                   interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out, table=table)
@@ -637,20 +851,19 @@ class _NonlinearBeamformer(DelayAndSum):
         _check_iq(self, data)
         dev = _is_dev(data)
         ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
-        gx = scan.d_x if dev and getattr(scan, "d_x", None) is not None else scan.x_axis
-        gz = scan.d_z if dev and getattr(scan, "d_z", None) is not None else scan.z_axis
+        polar, gx, gz = _scan_tables(scan, dev)
         taps = self.filter_taps(scan, ai["sound_speed"])
         if taps is None:
-            return self._raw(data, ai, ex, gx, gz, out, table if dev else None)
+            return self._raw(data, ai, ex, gx, gz, out, table if dev else None, polar)
         if not dev:
-            return axial_fir(self._raw(data, ai, ex, gx, gz, None, None), taps)
+            return axial_fir(self._raw(data, ai, ex, gx, gz, None, None, polar), taps)
         # the taps in HBM: uploaded once per change (us_render puts its plan's copy here, with the buffer of the unfiltered image)
         key = taps.tobytes()
         if self._taps_cache[0] != key or self._taps_cache[1].ctx is not data.ctx:
             self._taps_cache = (key, _capi.DeviceBuffer.from_host(data.ctx, taps))
         d_taps = self._taps_cache[1]
         raw = self._raw(data, ai, ex, gx, gz, self.scratch_dev if self.scratch_dev is not None and self.scratch_dev.shape == scan.shape else None,
-                        table)
+                        table, polar)
         return axial_fir(raw, d_taps, out=out)
 
     def __str__(self):
@@ -677,7 +890,7 @@ class _RenderPlan:
     """Device buffers of one us_render configuration (acquisition shape, scan grid): allocated once, reused by every call of the
     reference's loop (USMain.py:262-289 calls us_render 50 times on one scene)."""
 
-    def __init__(self, cx, A, E, T, elem_x, x_scan, z_scan, gaussian, taps=None, iq=None):
+    def __init__(self, cx, A, E, T, elem_x, x_scan, z_scan, gaussian, taps=None, iq=None, polar=None):
         self.key = None
         self.cx = cx
         self.d_channel = _capi.DeviceBuffer(cx, (A, E, T))
@@ -688,10 +901,18 @@ class _RenderPlan:
         self.d_ex = _capi.DeviceBuffer.from_host(cx, _capi.f32(elem_x))
         self.d_x = _capi.DeviceBuffer.from_host(cx, _capi.f32(x_scan))
         self.d_z = _capi.DeviceBuffer.from_host(cx, _capi.f32(z_scan))
-        nx, nz = len(x_scan), len(z_scan)
+        # polar (a PolarScan, DESIGN D21): the beamformer's buffers have the sector's shape, d_px / d_pz are its pixel tables, d_env_sec
+        # its envelope; d_env is then the scan-converted envelope on the Cartesian grid, which d_img always has
+        self.d_px = self.d_pz = self.d_env_sec = None
+        gx, gz = len(x_scan), len(z_scan)
+        nx, nz = (gx, gz) if polar is None else polar.shape
+        if polar is not None:
+            px, pz = polar.pixels()
+            self.d_px, self.d_pz = _capi.DeviceBuffer.from_host(cx, px), _capi.DeviceBuffer.from_host(cx, pz)
+            self.d_env_sec = _capi.DeviceBuffer(cx, (nx, nz))
         self.d_bf = _capi.DeviceBuffer(cx, (nx, nz))
-        self.d_env = _capi.DeviceBuffer(cx, (nx, nz))
-        self.d_img = _capi.DeviceBuffer(cx, (nx, nz))
+        self.d_env = _capi.DeviceBuffer(cx, (gx, gz))
+        self.d_img = _capi.DeviceBuffer(cx, (gx, gz))
         self.d_table = _capi.DeviceBuffer(cx, (A, nx, nz), np.float64)   # first-arrival times of this scan (das_first_arrival)
         # p-DAS / F-DMAS with a band: the band-pass taps, and the image before the filter
         self.d_taps = _capi.DeviceBuffer.from_host(cx, taps) if taps is not None else None
@@ -709,7 +930,7 @@ class _RenderPlan:
 
 def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range=60.0, step=None, seed=None,
               paths_per_ray=None, beamformer=None, device_resident=True, return_bmode=True, timing=None, graph=True,
-              on_device=False, iq=False, decimation=1):
+              on_device=False, iq=False, decimation=1, scan="grid", theta_range=None):
     """The reference's us_render (USMain.py:93-224) without the plotting: acquisition -> DAS -> envelope -> log
     compression.  Returns (display_image [nz, nx] in [0, 1], bmode envelope [nx, nz] (None with return_bmode=False),
     (x_scan, z_scan)).
@@ -731,7 +952,13 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     I/Q delay-and-sum -> modulus -> log compression, on every path above.  The envelope is a modulus per pixel, so `step` is free
     of the carrier (lambda / 2, a coarse loss grid) and nz has no limit.  A `beamformer` of the caller keeps its setups: the call
     works on a copy of it that beamforms I/Q data; one that has is_iq set selects this chain by itself, and its setup `demod_freq`, where set,
-    is the frequency rf2iq demodulates at (default: the integrator's)."""
+    is the frequency rf2iq demodulates at (default: the integrator's).
+    scan: "grid" (the reference's GridScan) or "polar" (DESIGN D21) -- the beamformer runs on a PolarScan around the origin of the
+    probe's frame, rhos = np.arange(z_range[0], z_range[1] + step, step), thetas over `theta_range` (radians; default: +- opening_angle
+    / 2 of a curved array, atan(x_range / z_range[1]) of a linear one) with the smallest count that keeps rho_max * dtheta <= step
+    (polar_n_theta); the envelope (or modulus) is taken along rho, the propagation direction of every ray, and scan_convert brings it
+    onto the Cartesian grid of "grid" (0 outside the sector) before the log compression.  The display image, the returned envelope
+    and the axes have the shapes "grid" gives; every path above runs this chain."""
     import time as _time
     integ = scene.integrator()
     A, E, T = integ.n_angles, integ.n_elements, integ.time_samples
@@ -739,8 +966,21 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     step = step or lam / 4                                                                             # :189-191
     x_scan = np.arange(x_range[0], x_range[1] + step, step)                                            # :193
     z_scan = np.arange(z_range[0], z_range[1] + step, step)                                            # :194
-    scan = GridScan(x_scan, z_scan)
+    if scan not in ("grid", "polar"):
+        raise ValueError(f"us_render: scan must be 'grid' or 'polar', got {scan!r}")
+    polar = scan == "polar"
+    if theta_range is not None and not polar:
+        raise ValueError("us_render: theta_range belongs to scan='polar'")
     convex = float(getattr(integ, "radius", 0.0)) != 0.0
+    scan = GridScan(x_scan, z_scan)
+    if polar:
+        if theta_range is None and convex:      # the arc's own opening angle
+            theta_range = (-np.radians(float(integ.opening_angle)) / 2.0, np.radians(float(integ.opening_angle)) / 2.0)
+        elif theta_range is None:               # the x-range seen from the deepest z
+            theta_range = (np.arctan(x_range[0] / z_range[1]), np.arctan(x_range[1] / z_range[1]))
+        theta_range = (float(theta_range[0]), float(theta_range[1]))
+        rhos = z_scan   # measured from the origin of the probe's frame, as the scan's z is
+        scan = PolarScan(rhos, np.linspace(theta_range[0], theta_range[1], polar_n_theta(rhos[-1], theta_range, step)))
     if convex:  # the curved array (DESIGN D18): element table instead of positions, the *_probe beamformer
         probe = build_probe("convex", E, integ.pitch, integ.frequency, 70, radius=integ.radius, opening_angle=integ.opening_angle)
     else:
@@ -787,20 +1027,28 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
         if iq:
             data = rf2iq(data, f_demod, integ.fs, decimation=D, taps=lp)
         bmode = bf.compute_envelope(bf.beamform(data[np.newaxis], scan), scan).astype(np.float32)      # :204-207
+        if polar:
+            bmode = scan_convert(bmode, scan, x_scan, z_scan, fill=0.0)
         display = log_compress(bmode, dynamic_range).T                                                 # :210-221
         return display, bmode, (x_scan, z_scan)
 
     cx = scene.device().ctx
     gaussian = integ.pulse_model == "gaussian"
     key = (A, E, T, float(integ.pitch), x_scan.tobytes(), z_scan.tobytes(), gaussian, id(cx), probe.geometry_type, probe.radius,
-           probe.opening_angle, None if taps is None else taps.tobytes(), iq, D if iq else 1, None if lp is None else lp.tobytes())
+           probe.opening_angle, None if taps is None else taps.tobytes(), iq, D if iq else 1, None if lp is None else lp.tobytes(),
+           theta_range if polar else None, len(scan.thetas) if polar else None)
     plan = getattr(integ, "_render_plan", None)
     if plan is None or plan.key != key:
-        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian, taps, (D, lp) if iq else None)
+        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian, taps, (D, lp) if iq else None,
+                           scan if polar else None)
         plan.key = key
         integ._render_plan = plan
     rf = plan.d_rf if gaussian else plan.d_channel
-    scan.d_x, scan.d_z = plan.d_x, plan.d_z
+    if polar:
+        scan.d_px, scan.d_pz = plan.d_px, plan.d_pz
+    else:
+        scan.d_x, scan.d_z = plan.d_x, plan.d_z
+    d_env_bf = plan.d_env_sec if polar else plan.d_env   # the envelope on the scan the beamformer ran on
     bf.probe_dev = plan.d_ex
     if isinstance(bf, _NonlinearBeamformer):
         bf.scratch_dev = plan.d_nl
@@ -818,10 +1066,12 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
         if iq:                                                                                         # D20: baseband, then complex DAS
             rf2iq(rf, f_demod, integ.fs, decimation=D, taps=plan.d_iq_taps, out=plan.d_iq)
             bf.beamform(plan.d_iq, scan, out=plan.d_bf_iq, table=plan.d_table)
-            bf.compute_envelope(plan.d_bf_iq, scan, out=plan.d_env)                                    # the modulus
+            bf.compute_envelope(plan.d_bf_iq, scan, out=d_env_bf)                                      # the modulus
         else:
             bf.beamform(rf, scan, out=plan.d_bf, table=plan.d_table)                                   # :204
-            bf.compute_envelope(plan.d_bf, scan, out=plan.d_env)                                       # :205
+            bf.compute_envelope(plan.d_bf, scan, out=d_env_bf)                                         # :205
+        if polar:                                                                                      # D21: sector -> the grid
+            scan_convert(plan.d_env_sec, scan, plan.d_x, plan.d_z, fill=0.0, out=plan.d_env)
         log_compress(plan.d_env, dynamic_range, out=plan.d_img)                                        # :210-218
 
     # What the queued calls depend on besides the CONTENTS of device memory: a recording of them (pbrt_ctx_record_begin, one
@@ -835,7 +1085,7 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
                 int(integ.seed if seed is None else seed) & 0xFFFFFFFF,
                 int(paths_per_ray if paths_per_ray is not None else integ.paths_per_ray), float(dynamic_range),
                 type(bf).__name__, tuple(sorted(bf.setups.items())), float(integ.pulse_sigma) if gaussian else None,
-                (D, f_demod) if iq else None)
+                (D, f_demod) if iq else None, (theta_range, scan.shape) if polar else None)
     replayed = False
     if gkey is not None and plan.graph is not None and plan.graph_key == gkey:
         try:
@@ -859,7 +1109,10 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
             plan.table_c = float(integ.sound_speed)
             # the scan's first-arrival times follow the delays, the sound speed and the grid: made again only when those change
             # (never, in the loop of USMain.py:262-289).  (A single 0 degree angle has zero delays at every sound speed.)
-            das_first_arrival(plan.d_tx, plan.d_ex, plan.d_x, plan.d_z, integ.sound_speed, out=plan.d_table)
+            if polar:
+                scan_first_arrival(plan.d_tx, plan.d_ex, plan.d_px, plan.d_pz, integ.sound_speed, out=plan.d_table)
+            else:
+                das_first_arrival(plan.d_tx, plan.d_ex, plan.d_x, plan.d_z, integ.sound_speed, out=plan.d_table)
             plan.graph = plan.graph_key = plan.warm_key = None
         queue_image_formation()
         if gkey is not None and plan.warm_key == gkey and plan.no_graph_key != gkey:

@@ -47,9 +47,13 @@
 // the same number of pixels that see an element: the same work on every XCD.  (Measured neutral at the sizes of USMain.py, 151
 // against 148 us: the 4.2 MB that are read at all stay cached either way; kept for larger acquisitions.)
 // -> (tx, tz), or false for a slot beyond the XCD's share.  m = z-tiles of the largest share.
+// tab: the scan is a pair of pixel tables px[nx][nz], pz[nx][nz] (the pbrt_scan_* entry points, DESIGN D21) instead of the axes
+// x[nx], z[nz] -- the strides (1, 0) / (0, 1) of the axes against (nz, 1) of the tables differ in this one bit: pixel (ix, iz) reads
+// entry tab ? ix * nz + iz : ix of gx and tab ? ix * nz + iz : iz of gz, once per lane, and everything after that is per pixel already.
 struct DasGrid {
-    uint32_t ntx, ntz, m;
+    uint32_t ntx, ntz, m, tab;
 };
+DEV uint32_t das_px_index(uint32_t tab, uint32_t i, uint32_t pix) { return tab ? pix : i; }
 __host__ DEV uint32_t das_band_lo(uint32_t band, uint32_t ntz) { return (band * ntz + DAS_BANDS - 1u) / DAS_BANDS; }
 DEV bool das_tile_of(const DasGrid g, uint32_t b, uint32_t *tx, uint32_t *tz) {
     const uint32_t xcd = b % DAS_XCDS, i = b / DAS_XCDS;
@@ -100,15 +104,16 @@ template <bool CONVEX>
 DEV double das_dist2(double dx, double zz, double dz) { return CONVEX ? dx * dx + dz * dz : dx * dx + zz; }
 
 // first-arrival table of a scan: ttx[a][ix][iz] = min_e (tx[a][e] + |(x, z) - (x_e, 0)| / c), the statement of k_das_beamform's first
-// pass (same operands, same operations: the same doubles).  One thread per pixel, z fastest.
+// pass (same operands, same operations: the same doubles).  One thread per pixel, z fastest.  tab: gx, gz are pixel tables (DasGrid).
 template <bool CONVEX = false>
-__global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, const float *__restrict__ tx, const float *__restrict__ elem_x,
-                                                           const float *__restrict__ gx, const float *__restrict__ gz,
-                                                           double *__restrict__ ttx) {
+__global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, uint32_t tab, const float *__restrict__ tx,
+                                                           const float *__restrict__ elem_x, const float *__restrict__ gx,
+                                                           const float *__restrict__ gz, double *__restrict__ ttx) {
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= p.nx * p.nz) return;
     const uint32_t ix = idx / p.nz, iz = idx - ix * p.nz;
-    const double x = (double)gx[ix], z = (double)gz[iz], zz = z * z, inv_c = 1.0 / (double)p.sound_speed;
+    const double x = (double)gx[das_px_index(tab, ix, idx)], z = (double)gz[das_px_index(tab, iz, idx)], zz = z * z,
+                 inv_c = 1.0 / (double)p.sound_speed;
     const uint32_t A = p.n_angles, E = p.n_elements;
     const size_t plane = (size_t)p.nx * p.nz;
     for (uint32_t a0 = 0; a0 < A; a0 += DAS_ANG) {
@@ -200,7 +205,8 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t ix = tile_x * DAS_TILE + (lane >> 3), iz = tile_z * DAS_TILE + (lane & 7u);
     const bool valid = ix < p.nx && iz < p.nz;
-    const double x = (double)gx[min(ix, p.nx - 1u)], z = (double)gz[min(iz, p.nz - 1u)];
+    const uint32_t cx = min(ix, p.nx - 1u), cz = min(iz, p.nz - 1u), cpix = cx * p.nz + cz;  // (clamped: lanes beyond the scan read its edge)
+    const double x = (double)gx[das_px_index(grid.tab, cx, cpix)], z = (double)gz[das_px_index(grid.tab, cz, cpix)];
     const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0;
     const uint32_t A = p.n_angles, E = p.n_elements, T = p.time_samples;
     const double half_ap = p.f_number > 0.0f ? z / (2.0 * (double)p.f_number) : 1e300;
@@ -514,6 +520,34 @@ __global__ __launch_bounds__(256) void k_iq_modulus(uint32_t n, const float2 *__
     if (i >= n) return;
     const float2 s = iq[i];
     env[i] = sqrtf(fma_(s.x, s.x, s.y * s.y));
+}
+
+// ---- scan conversion (DESIGN D21) ---------------------------------------------------------------------------------------------
+// A polar image src[n_theta][n_rho] (rho fastest) on the uniform axes theta_i = theta0 + i dtheta (from the +z axis towards +x) and
+// rho_j = rho0 + j drho around (ox, oz), resampled onto the Cartesian axes x[nx], z[nz]: per output pixel, in f64,
+//   dx = x - ox, dz = z - oz, rho = sqrt(dx dx + dz dz), theta = atan2(dx, dz), u = (theta - theta0) / dtheta, v = (rho - rho0) / drho;
+// inside iff 0 <= u <= n_theta - 1 and 0 <= v <= n_rho - 1 (a NaN coordinate is outside), outside pixels get `fill`; inside,
+// i = min(floor(u), n_theta - 2), j = min(floor(v), n_rho - 2), the weights u - i and v - j rounded once to f32, and three das_lerp in
+// f32: along rho in the rows i and i + 1, then along theta.  All four corners are read and enter the lerps whatever the weights, so
+// a non-finite sample reaches exactly the pixels whose cell holds it.  One thread per output pixel, z fastest: neighbouring z fall on
+// neighbouring rho, so a wave's loads follow a few rows of the source.  No table of indices and weights: none was measured to pay.
+__global__ __launch_bounds__(256) void k_scan_convert(pbrt_scan_convert_params p, const float *__restrict__ src,
+                                                      const float *__restrict__ gx, const float *__restrict__ gz, float *__restrict__ dst) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= p.nx * p.nz) return;
+    const uint32_t ix = idx / p.nz, iz = idx - ix * p.nz;
+    const double dx = (double)gx[ix] - p.ox, dz = (double)gz[iz] - p.oz;
+    const double rho = sqrt(dx * dx + dz * dz), theta = atan2(dx, dz);
+    const double u = (theta - p.theta0) / p.dtheta, v = (rho - p.rho0) / p.drho;
+    float r = p.fill;
+    if (u >= 0.0 && u <= (double)(p.n_theta - 1u) && v >= 0.0 && v <= (double)(p.n_rho - 1u)) {
+        const uint32_t i = min((uint32_t)floor(u), p.n_theta - 2u), j = min((uint32_t)floor(v), p.n_rho - 2u);
+        const float wu = (float)(u - (double)i), wv = (float)(v - (double)j);
+        const float *row = src + (size_t)i * p.n_rho + j;
+        const float a = das_lerp(wv, row[0], row[1]), b = das_lerp(wv, row[p.n_rho], row[p.n_rho + 1u]);
+        r = das_lerp(wu, a, b);
+    }
+    dst[idx] = r;
 }
 
 // ---- envelope ---------------------------------------------------------------------------------------------------------------

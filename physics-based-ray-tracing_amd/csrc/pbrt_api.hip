@@ -2517,9 +2517,11 @@ static int das_check(pbrt_ctx *ctx, const pbrt_das_params *p) {
 }
 // de: element positions [n_elements], or (probe) the element table [n_elements][4] of pbrt_us_array_elements
 static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, const float *dt, const float *de, const float *dx,
-                       const float *dz, float *dout, const double *ttx = nullptr, bool probe = false, uint32_t method = 0u, float pw = 0.0f) {
+                       const float *dz, float *dout, const double *ttx = nullptr, bool probe = false, uint32_t method = 0u, float pw = 0.0f,
+                       bool tab = false) {
     ImgTimer tm(c, IMG_DAS);
     DasGrid g;
+    g.tab = tab ? 1u : 0u;  // dx, dz are the pixel tables [nx][nz] of a pbrt_scan_* call
     g.ntx = div_up(p->nx, DAS_TILE);
     g.ntz = div_up(p->nz, DAS_TILE);
     // z-tiles of the largest XCD share (bands k and 15 - k, kernels_beamform.h das_tile_of); the grid gives every XCD that many slots
@@ -2611,32 +2613,33 @@ static int pulse_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, uint32_t K,
 // (d_tx_delays or d_table: the plain form passes its delays, the table form its first-arrival table, and the other one null)
 static int das_beamform_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_table,
                                  const void *d_elem_x, const void *d_x, const void *d_z, void *d_out, bool probe, uint32_t method = 0u,
-                                 float pw = 0.0f) {
+                                 float pw = 0.0f, bool tab = false) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && d_data && (d_tx_delays || d_table) && d_elem_x && d_x && d_z && d_out);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, p, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x,
-                       (const float *)d_z, (float *)d_out, (const double *)d_table, probe, method, pw);
+                       (const float *)d_z, (float *)d_out, (const double *)d_table, probe, method, pw, tab);
 }
 
 static int das_first_arrival_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
-                                      const void *d_z, void *d_table, bool probe) {
+                                      const void *d_z, void *d_table, bool probe, bool tab = false) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && d_tx_delays && d_elem_x && d_x && d_z && d_table);
     int rc = das_check(ctx, p);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(probe ? k_das_first_arrival<true> : k_das_first_arrival<false>, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256), 0,
-                       ctx->stream, *p, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x, (const float *)d_z,
+                       ctx->stream, *p, tab ? 1u : 0u, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x, (const float *)d_z,
                        (double *)d_table);
     HIPCHK(ctx, hipGetLastError());
     return PBRT_OK;
 }
 
 static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays, const float *elem_x,
-                             const float *x, const float *z, float *out, bool probe, uint32_t method = 0u, float pw = 0.0f) {
+                             const float *x, const float *z, float *out, bool probe, uint32_t method = 0u, float pw = 0.0f,
+                             bool tab = false) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, p && data && tx_delays && elem_x && x && z && out);
     int rc = das_check(ctx, p);
@@ -2645,11 +2648,12 @@ static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const floa
     const size_t nd = (size_t)p->n_angles * p->n_elements * p->time_samples * width, ne = (size_t)p->n_angles * p->n_elements;
     const uint32_t n = p->nx * p->nz;
     const size_t nel = (size_t)p->n_elements * (probe ? 4u : 1u);
-    STAGED_BEGIN(ctx, (nd + ne + nel + p->nx + p->nz + (size_t)n * width) * 4 + 256);
+    const size_t ngx = tab ? (size_t)n : p->nx, ngz = tab ? (size_t)n : p->nz;  // axes, or the two pixel tables
+    STAGED_BEGIN(ctx, (nd + ne + nel + ngx + ngz + (size_t)n * width) * 4 + 256);
     float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem_x, nel);
-    float *dx = S.in(x, p->nx), *dz = S.in(z, p->nz);
+    float *dx = S.in(x, ngx), *dz = S.in(z, ngz);
     float *dout = S.out<float>(n * width);
-    if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout, nullptr, probe, method, pw)) != 0) return rc;
+    if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout, nullptr, probe, method, pw, tab)) != 0) return rc;
     S.back(out, dout, n * width);
     return S.finish();
 }
@@ -2685,6 +2689,31 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
     const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
     return pa < pb + nb && pb < pa + na;
 }
+// pixel-table scans (DESIGN D21): what pbrt_scan_params adds to das_check -- bf_check's and iq_check's rules for the method it names;
+// the entry points then take the DAS path with that method and the table flag.  -> the launch argument pw (p, or the demodulation frequency)
+static int scan_check(pbrt_ctx *ctx, const pbrt_scan_params *p, float *pw) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, p && p->probe <= 1u);
+    NEED(ctx, p->method == PBRT_SCAN_DAS || p->method == PBRT_BF_PDAS || p->method == PBRT_BF_FDMAS || p->method == PBRT_SCAN_IQ);
+    NEED(ctx, p->method != PBRT_BF_PDAS || (std::isfinite(p->p) && p->p >= 1.0f && p->p <= 8.0f));
+    NEED(ctx, p->method != PBRT_SCAN_IQ || (std::isfinite(p->demod_freq) && p->demod_freq >= 0.0f));
+    *pw = p->method == PBRT_SCAN_IQ ? p->demod_freq : p->method == PBRT_SCAN_DAS ? 0.0f : p->p;
+    return PBRT_OK;
+}
+static int scan_convert_check(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *src, const void *dst) {
+    NEED(ctx, p->n_theta >= 2u && p->n_rho >= 2u && p->nx > 0 && p->nz > 0);
+    NEED(ctx, (uint64_t)p->n_theta * p->n_rho < 0xffffffffull && (uint64_t)p->nx * p->nz < 0xffffffffull);
+    NEED(ctx, std::isfinite(p->theta0) && std::isfinite(p->dtheta) && std::isfinite(p->rho0) && std::isfinite(p->drho));
+    NEED(ctx, std::isfinite(p->ox) && std::isfinite(p->oz) && p->dtheta != 0.0 && p->drho != 0.0);
+    NEED(ctx, !ranges_overlap(src, (size_t)p->n_theta * p->n_rho * 4, dst, (size_t)p->nx * p->nz * 4));
+    return PBRT_OK;
+}
+static int scan_convert_enqueue(pbrt_ctx *c, const pbrt_scan_convert_params *p, const float *dsrc, const float *dx, const float *dz,
+                                float *ddst) {
+    hipLaunchKernelGGL(k_scan_convert, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256), 0, c->stream, *p, dsrc, dx, dz, ddst);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
 static int rf2iq_check(pbrt_ctx *ctx, uint32_t n_traces, uint32_t T, float fs, float t0, float f_d, uint32_t D, uint32_t K, const void *in,
                        const void *out) {
     NEED(ctx, T > 0 && D >= 1u && D <= RF2IQ_MAX_D && K <= FIR_MAX_K);
@@ -2711,6 +2740,53 @@ static int iq_env_enqueue(pbrt_ctx *c, uint32_t n, const float *din, float *dout
 }
 
 extern "C" {
+
+int pbrt_scan_beamform(pbrt_ctx *ctx, const pbrt_scan_params *p, const float *data, const float *tx_delays, const float *elem,
+                       const float *px, const float *pz, float *out) {
+    float pw;
+    int rc = scan_check(ctx, p, &pw);
+    return rc ? rc : das_beamform_impl(ctx, &p->das, data, tx_delays, elem, px, pz, out, p->probe != 0u, p->method, pw, true);
+}
+int pbrt_scan_beamform_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
+                           const void *d_px, const void *d_pz, void *d_out) {
+    float pw;
+    int rc = scan_check(ctx, p, &pw);
+    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, d_tx_delays, nullptr, d_elem, d_px, d_pz, d_out, p->probe != 0u, p->method, pw, true);
+}
+int pbrt_scan_beamform_table_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_data, const void *d_table, const void *d_elem,
+                                 const void *d_px, const void *d_pz, void *d_out) {
+    float pw;
+    int rc = scan_check(ctx, p, &pw);
+    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, nullptr, d_table, d_elem, d_px, d_pz, d_out, p->probe != 0u, p->method, pw, true);
+}
+int pbrt_scan_first_arrival_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_tx_delays, const void *d_elem, const void *d_px,
+                                const void *d_pz, void *d_table) {
+    float pw;
+    int rc = scan_check(ctx, p, &pw);
+    return rc ? rc : das_first_arrival_dev_impl(ctx, &p->das, d_tx_delays, d_elem, d_px, d_pz, d_table, p->probe != 0u, true);
+}
+int pbrt_scan_convert_dev(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *d_src, const void *d_x, const void *d_z,
+                          void *d_dst) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, p && d_src && d_x && d_z && d_dst);
+    int rc = scan_convert_check(ctx, p, d_src, d_dst);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return scan_convert_enqueue(ctx, p, (const float *)d_src, (const float *)d_x, (const float *)d_z, (float *)d_dst);
+}
+int pbrt_scan_convert(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const float *src, const float *x, const float *z, float *dst) {
+    if (!ctx) return PBRT_E_INVALID;
+    NEED(ctx, p && src && x && z && dst);
+    int rc = scan_convert_check(ctx, p, src, dst);
+    if (rc) return rc;
+    const size_t ns = (size_t)p->n_theta * p->n_rho, nd = (size_t)p->nx * p->nz;
+    const uint32_t n = p->nx * p->nz;
+    STAGED_BEGIN(ctx, (ns + nd + p->nx + p->nz) * 4 + 256);
+    float *dsrc = S.in(src, ns), *dx = S.in(x, p->nx), *dz = S.in(z, p->nz), *ddst = S.out<float>(nd);
+    if ((rc = scan_convert_enqueue(c, p, dsrc, dx, dz, ddst)) != 0) return rc;
+    S.back(dst, ddst, nd);
+    return S.finish();
+}
 
 int pbrt_iq_beamform_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem,
                          const void *d_x, const void *d_z, void *d_out) {

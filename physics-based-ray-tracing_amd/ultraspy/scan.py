@@ -1,2 +1,2 @@
 """USMain.py:9"""
-from ..beamform import GridScan  # noqa: F401
+from ..beamform import GridScan, PolarScan  # noqa: F401
