@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/pbrt_hip.h"
 #include "device_math.h"
+#include "prim_runs.h"
 
 // BVH4 inner node, 64 bytes (bvh_build.h HostNode4): lower corner of the node's box, a power-of-two grid step per axis and
 // the boxes of FOUR children on that 8-bit grid, rounded outward -- one node read decides four descents.
@@ -129,6 +130,10 @@ struct DevScene {
     // mode, pbrt_ray_test) always walk the full list.
     const pbrt_prim *occ_prims;
     uint32_t n_occ;
+    // BRUTE only: prims and occ_prims cut into maximal runs of one primitive class, in list order; a run is count << 2 | class
+    // (prim_runs.h).  brute_intersect walks a list run by run, one straight-line loop per class.
+    const uint32_t *prim_runs, *occ_runs;
+    uint32_t n_prim_runs, n_occ_runs;
     // optional: the vertex normals of mesh primitives, [n_prims][9], caller order (indexed by Hit::slot); nullptr: face normals
     const float *vnormals;
     uint32_t n_prims, n_nodes, n_emitters, n_mats, n_light_prims;
@@ -231,10 +236,11 @@ DEV bool sphere_hit(V3 c, float r, V3 o, V3 d, float tmax, float *t) {
     float cc = fma_(-r, r, dot(f, f));
     float t0 = cc / q, t1 = q;
     float tn = fminf(t0, t1), tf = fmaxf(t0, t1);
-    if (!(tn <= tmax && tf >= 0.0f)) return false;
-    if (tn < 0.0f && tf > tmax) return false;
+    // the acceptance tests as one conjunction and a select (no nested exec-mask regions behind the disc branch): the same
+    // comparisons on the same operands, so the same truth value for every input, NaN included.  *t is meaningful only on true.
+    const bool ok = (tn <= tmax) & (tf >= 0.0f) & !((tn < 0.0f) & (tf > tmax));
     *t = tn < 0.0f ? tf : tn;
-    return true;
+    return ok;
 }
 DEV bool planar_hit(bool triangle, V3 v0, V3 e1, V3 e2, V3 o, V3 d, float tmax, float *t, float *u, float *v) {
     V3 pvec = cross(d, e2);
@@ -295,16 +301,108 @@ DEV bool prim_hit(const pbrt_prim &P, V3 o, V3 d, float tmax, float *t, float *u
 // s_load, independent of the compiler's "is this memory clobbered earlier in the kernel" analysis (any barrier,
 // fence or inline asm ahead of the loop would otherwise turn the 16 dwords of every record into per-lane
 // global loads held in 16 VGPRs).  The scene is immutable while a kernel runs, so the promise holds.
+template <class T>
+DEV T load_uniform(const void *p) {
+    typedef const T __attribute__((address_space(4))) *cptr;
+    return *(cptr)(uintptr_t)p;
+}
 DEV pbrt_prim load_prim_uniform(const pbrt_prim *p) {
     typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-    typedef const u32x4 __attribute__((address_space(4))) *cptr;
     struct Raw {
         u32x4 q[4];
     };
     static_assert(sizeof(Raw) == sizeof(pbrt_prim), "pbrt_prim is 16 dwords");
-    cptr q = (cptr)(uintptr_t)p;
-    Raw r = {{q[0], q[1], q[2], q[3]}};
+    const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
+    Raw r = {{load_uniform<u32x4>(q), load_uniform<u32x4>(q + 1), load_uniform<u32x4>(q + 2), load_uniform<u32x4>(q + 3)}};
     return __builtin_bit_cast(pbrt_prim, r);
+}
+
+// The list is walked in runs of one primitive class (DevScene::prim_runs / occ_runs, cut on the host: prim_runs.h), one loop
+// per class: no type test per primitive, the triangle / parallelogram edge test chosen at compile time, a record pointer
+// that is bumped by one record, and loads of the dwords the class reads (9 of a planar record, 4 of a sphere).  The order of
+// the list is kept, so the lowest index still wins a tie.
+struct BruteBest {
+    float bn, bd, bu, bv;  // the best candidate (bn / bd, bu / bd, bv / bd)
+    uint32_t bp;           // its index, 0xffffffff: none yet (closest hit)
+    bool found;            // any-hit: this lane is occluded
+};
+// one tested candidate; returns true when an any-hit walk can stop (every active lane is occluded)
+template <bool ANY>
+DEV bool brute_take(BruteBest &b, bool ok, float num, float den, float us, float vs, uint32_t i) {
+    if (ANY) {
+        b.found = b.found | ok;
+        return __builtin_amdgcn_ballot_w64(!b.found) == 0;
+    }
+    const bool better = ok & ((b.bp == 0xffffffffu) | (num * b.bd < b.bn * den));
+    b.bn = better ? num : b.bn;
+    b.bd = better ? den : b.bd;
+    b.bu = better ? us : b.bu;
+    b.bv = better ? vs : b.bv;
+    b.bp = better ? i : b.bp;
+    return false;
+}
+// cnt >= 1 records of triangles (TRI) or parallelograms from p on; p and the primitive index i end behind the run
+template <bool ANY, bool TRI>
+DEV bool brute_planar_run(const pbrt_prim *&p, uint32_t &i, uint32_t cnt, V3 o, V3 d, float tmax, BruteBest &b) {
+    typedef float __attribute__((ext_vector_type(8))) f32x8;
+    const pbrt_prim *const pend = p + cnt;
+    do {
+        const f32x8 g = load_uniform<f32x8>(p->g);
+        const float g8 = load_uniform<float>(p->g + 8);
+        V3 v0 = {g[0], g[1], g[2]}, e1 = {g[3], g[4], g[5]}, e2 = {g[6], g[7], g8};
+        V3 pvec = cross(d, e2);
+        float det = dot(e1, pvec);
+        V3 tvec = o - v0;
+        V3 qvec = cross(tvec, e1);
+        float us = dot(tvec, pvec);
+        float vs = dot(d, qvec);
+        float ts = dot(e2, qvec);
+        const bool neg = det < 0.0f;
+        det = neg ? -det : det;
+        us = neg ? -us : us;
+        vs = neg ? -vs : vs;
+        ts = neg ? -ts : ts;
+        // (us >= 0 & vs >= 0 & ts >= 0) folded into min3: two compares less per primitive.  min3 drops a NaN (a ray with an
+        // infinite component), which the oracle's three compares reject; every NaN fails one of the tests that follow --
+        // ts in the range test, us or vs in the sum of the triangle, in its own upper bound for the parallelogram (which
+        // is why that bound is two compares and not max(us, vs) <= det) -- so the truth value is the oracle's for every input
+        bool ok = (det > 0.0f) & (fminf(fminf(us, vs), ts) >= 0.0f) & (ts <= tmax * det);
+        if (TRI)
+            ok = ok & (us + vs <= det);
+        else
+            ok = ok & (us <= det) & (vs <= det);
+        const bool stop = brute_take<ANY>(b, ok, ts, det, us, vs, i);
+        ++p;
+        ++i;
+        if (ANY && stop) return true;
+    } while (p != pend);
+    return false;
+}
+// cnt >= 1 records of spheres, and with CONES of cones and cylinders: candidates (t, 1)
+template <bool ANY, bool CONES>
+DEV bool brute_curved_run(const pbrt_prim *&p, uint32_t &i, uint32_t cnt, V3 o, V3 d, float tmax, BruteBest &b) {
+    typedef float __attribute__((ext_vector_type(4))) f32x4;
+    const pbrt_prim *const pend = p + cnt;
+    do {
+        bool ok;
+        float t, u;  // u: 0 for spheres / cylinders; cone: 0 lateral surface / 1 base disc (den = 1: passes through unscaled)
+        if (CONES) {
+            const pbrt_prim P = load_prim_uniform(p);
+            const uint32_t type = P.type;  // wave-uniform; named so that prim_hit's planar branch folds away
+            float v;
+            t = u = 0.0f;
+            ok = (type == PBRT_PRIM_SPHERE || type == PBRT_PRIM_CONE || type == PBRT_PRIM_CYLINDER) && prim_hit(P, o, d, tmax, &t, &u, &v);
+        } else {
+            const f32x4 c = load_uniform<f32x4>(p->g);
+            u = 0.0f;
+            ok = sphere_hit({c[0], c[1], c[2]}, c[3], o, d, tmax, &t);
+        }
+        const bool stop = brute_take<ANY>(b, ok, t, 1.0f, u, 0.0f, i);
+        ++p;
+        ++i;
+        if (ANY && stop) return true;
+    } while (p != pend);
+    return false;
 }
 
 // CONES: the kernel variant understands the analytic quadrics, PBRT_PRIM_CONE and PBRT_PRIM_CYLINDER records.  Compile-time,
@@ -313,74 +411,33 @@ DEV pbrt_prim load_prim_uniform(const pbrt_prim *p) {
 // small scenes with a cone or a cylinder run the ACCEL_K_BRUTE_BIG variant instead (pbrt_api.hip).
 template <bool ANY, bool SEGMENT = false, bool CONES = true>
 DEV bool brute_intersect(const DevScene &sc, V3 o, V3 d, float tmax, Hit *h) {
-    bool found = false;
-    float bn = 0.0f, bd = 1.0f, bu = 0.0f, bv = 0.0f;
-    uint32_t bp = 0xffffffffu;
-    const pbrt_prim *list = (ANY && SEGMENT) ? sc.occ_prims : sc.prims;
-    // readfirstlane: keeps the loop counter and the record address in SGPRs (s_min / s_lshl / s_add) -- without it
-    // the compiler carries n_list - 1 in a VGPR and spends 5 VALU + 2 readfirstlane per record on the address
-    const uint32_t n_list = (uint32_t)__builtin_amdgcn_readfirstlane((int)((ANY && SEGMENT) ? sc.n_occ : sc.n_prims));
-    if (n_list == 0) return false;
-    // software pipeline over the (wave-uniform) primitive records: the 64-byte scalar load of primitive
-    // i + 1 is in flight while primitive i is tested
-    pbrt_prim nxt = load_prim_uniform(list);
-    for (uint32_t i = 0; i < n_list; ++i) {
-        const pbrt_prim P = nxt;
-        nxt = load_prim_uniform(list + min(i + 1, n_list - 1));
-        const uint32_t type = P.type;  // wave-uniform
-        bool ok;
-        float num, den, us, vs;
-        if (type == PBRT_PRIM_SPHERE || (CONES && (type == PBRT_PRIM_CONE || type == PBRT_PRIM_CYLINDER))) {  // curved: (t, 1)
-            float t, u, v;
-            ok = prim_hit(P, o, d, tmax, &t, &u, &v);
-            num = t;
-            den = 1.0f;
-            us = u;  // 0 for spheres / cylinders; cone: 0 lateral surface / 1 base disc (den = 1: passes through unscaled)
-            vs = 0.0f;
-        } else {
-            V3 v0 = g3(P, 0), e1 = g3(P, 3), e2 = g3(P, 6);
-            V3 pvec = cross(d, e2);
-            float det = dot(e1, pvec);
-            V3 tvec = o - v0;
-            V3 qvec = cross(tvec, e1);
-            us = dot(tvec, pvec);
-            vs = dot(d, qvec);
-            float ts = dot(e2, qvec);
-            const bool neg = det < 0.0f;
-            det = neg ? -det : det;
-            us = neg ? -us : us;
-            vs = neg ? -vs : vs;
-            ts = neg ? -ts : ts;
-            // (us >= 0 & vs >= 0 & ts >= 0) and (us <= det & vs <= det) folded into min3 / max: same truth
-            // value for finite operands (all operands are finite here), three compares less per primitive
-            ok = (det > 0.0f) & (fminf(fminf(us, vs), ts) >= 0.0f) & (ts <= tmax * det);
-            if (type == PBRT_PRIM_TRIANGLE)
-                ok = ok & (us + vs <= det);
-            else
-                ok = ok & (fmaxf(us, vs) <= det);
-            num = ts;
-            den = det;
-        }
-        if (ANY) {
-            found = found | ok;
-            if (__builtin_amdgcn_ballot_w64(!found) == 0) break;  // every active lane is occluded
-        } else {
-            const bool better = ok & (!found | (num * bd < bn * den));
-            bn = better ? num : bn;
-            bd = better ? den : bd;
-            bu = better ? us : bu;
-            bv = better ? vs : bv;
-            bp = better ? i : bp;
-            found = found | better;
-        }
+    BruteBest b = {0.0f, 1.0f, 0.0f, 0.0f, 0xffffffffu, false};
+    constexpr bool OCC = ANY && SEGMENT;
+    const pbrt_prim *p = OCC ? sc.occ_prims : sc.prims;
+    const uint32_t *runs = OCC ? sc.occ_runs : sc.prim_runs;
+    const uint32_t n_runs = (uint32_t)__builtin_amdgcn_readfirstlane((int)(OCC ? sc.n_occ_runs : sc.n_prim_runs));
+    uint32_t i = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const uint32_t w = load_uniform<uint32_t>(runs + r);  // wave-uniform: count << 2 | class
+        const uint32_t cnt = w >> 2, cls = w & 3u;
+        bool stop;
+        if (cls == PRIM_RUN_QUAD)
+            stop = brute_planar_run<ANY, false>(p, i, cnt, o, d, tmax, b);
+        else if (cls == PRIM_RUN_TRI)
+            stop = brute_planar_run<ANY, true>(p, i, cnt, o, d, tmax, b);
+        else
+            stop = brute_curved_run<ANY, CONES>(p, i, cnt, o, d, tmax, b);
+        if (ANY && stop) break;
     }
-    if (!ANY && found) {
-        float inv = 1.0f / bd;
-        h->t = bn * inv;
-        h->u = bu * inv;
-        h->v = bv * inv;
-        h->prim = bp;
-        h->slot = bp;
+    if (ANY) return b.found;
+    const bool found = b.bp != 0xffffffffu;
+    if (found) {
+        float inv = 1.0f / b.bd;
+        h->t = b.bn * inv;
+        h->u = b.bu * inv;
+        h->v = b.bv * inv;
+        h->prim = b.bp;
+        h->slot = b.bp;
     }
     return found;
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "prim_runs.h"
 #include "kernels_us.h"
 #include "kernels_wavefront.h"
 #include "kernels_us_wavefront.h"
@@ -518,6 +519,12 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
         std::vector<pbrt_prim> occ = find_occluders(d);
         UP(upload(s, occ.data(), occ.size(), &s->ds.occ_prims));
         s->ds.n_occ = (uint32_t)occ.size();
+        // both lists cut into runs of one primitive class, in list order (prim_runs.h; brute_intersect walks them run by run)
+        const std::vector<uint32_t> runs = cut_prim_runs(d->prims, d->n_prims), occ_runs = cut_prim_runs(occ.data(), occ.size());
+        UP(upload(s, runs.data(), runs.size(), &s->ds.prim_runs));
+        s->ds.n_prim_runs = (uint32_t)runs.size();
+        UP(upload(s, occ_runs.data(), occ_runs.size(), &s->ds.occ_runs));
+        s->ds.n_occ_runs = (uint32_t)occ_runs.size();
     } else {
         HostBvh bvh;
         // (a tree whose leaf records alone exceed the LDS stays in global memory whatever its shape: the SAH constant of those trees)
@@ -1433,6 +1440,8 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     if ((f->flags & PBRT_FILM_NO_OCCLUDER_PRUNING) && base.sc.occ_prims) {  // diagnostic: shadow segments walk every primitive
         base.sc.occ_prims = base.sc.prims;
         base.sc.n_occ = base.sc.n_prims;
+        base.sc.occ_runs = base.sc.prim_runs;
+        base.sc.n_occ_runs = base.sc.n_prim_runs;
     }
     base.cam = *cam;
     base.Lhome = Lhome;
