@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 import copy
+import math
 
 import numpy as np
 
@@ -51,94 +52,125 @@ def _elem_arg(elem, E):
     shape = tuple(elem.shape)
     probe = shape == (E, 4)
     # (a device buffer goes to the kernel as it is: a table of another size would be read out of bounds)
-    if not probe and int(np.prod(shape)) != E:
+    if not probe and math.prod(shape) != E:
         raise ValueError(f"element positions must be [{E}] or an element table [{E}, 4], got {list(shape)}")
     return elem, probe, ((E, 4) if probe else (E,))
 
 
-def _to_dev(cx, a, shape=None) -> "_capi.DeviceBuffer":
+def _arg(cx, a, shape=None, dev=True):
+    """a small table as a call takes it: a DeviceBuffer as it is; a host array as float32 of `shape`, uploaded where the call is a
+    device form"""
     if _is_dev(a):
         return a
     a = _capi.f32(np.asarray(a))
-    return _capi.DeviceBuffer.from_host(cx, a if shape is None else a.reshape(shape))
+    a = a if shape is None else a.reshape(shape)
+    return _capi.DeviceBuffer.from_host(cx, a) if dev else a
+
+
+def _pixel_tables(cx, px, pz, dev):
+    """the two pixel tables [n0, n1] of a scan as they are handed on (host float32 arrays, or DeviceBuffers), and (n0, n1)"""
+    if _is_dev(px) != _is_dev(pz):
+        raise ValueError("px and pz must both be host arrays or both DeviceBuffers")
+    if not _is_dev(px):
+        px, pz = _capi.f32(np.asarray(px)), _capi.f32(np.asarray(pz))
+    if len(px.shape) != 2 or tuple(px.shape) != tuple(pz.shape):
+        raise ValueError(f"px and pz must be two tables of one shape [n0, n1], got {list(px.shape)} and {list(pz.shape)}")
+    return _arg(cx, px, None, dev), _arg(cx, pz, None, dev), tuple(int(v) for v in px.shape)
+
+
+def _pixels(cx, gx, gz, tables, dev):
+    """the pixel arguments of a call as they are handed on, and the image shape: two tables [n0, n1] (`tables`), or the axes x [nx], z [nz]"""
+    if tables:
+        return _pixel_tables(cx, gx, gz, dev)
+    gx, gz = _arg(cx, gx, (-1,), dev), _arg(cx, gz, (-1,), dev)
+    return gx, gz, (gx.shape[0], gz.shape[0])
+
+
+_METHODS = {"das": _capi.SCAN_DAS, "pdas": _capi.BF_PDAS, "fdmas": _capi.BF_FDMAS, "iq": _capi.SCAN_IQ}
+
+
+def _block(das, tables, method, p, demod_freq, probe):
+    """the parameter block of a request and the family of entry points that takes it: pbrt_scan_* for pixel tables (one block for
+    every method); on axes pbrt_das_* (the element table is in the NAME: *_probe), pbrt_bf_* or pbrt_iq_* (a probe flag in the block)"""
+    if not tables and method == "das":
+        return das, "das"
+    par, family = ((_capi.ScanParams(), "scan") if tables else (_capi.IqParams(), "iq") if method == "iq" else (_capi.BfParams(), "bf"))
+    par.das, par.probe = das, int(bool(probe))
+    if family in ("scan", "bf"):
+        par.method, par.p = _METHODS[method], float(p)
+    if family in ("scan", "iq"):
+        par.demod_freq = float(demod_freq or 0.0)
+    return par, family
+
+
+def _checked_demod_freq(demod_freq) -> float:
+    if demod_freq is None or not (math.isfinite(float(demod_freq)) and float(demod_freq) >= 0.0):
+        raise ValueError(f"demod_freq must be finite and >= 0, got {demod_freq}")
+    return float(demod_freq)
+
+
+def _first_arrival(tx_delays, elem, gx, gz, tables, sound_speed, out):
+    """das_first_arrival (axes) and scan_first_arrival (pixel tables): uploads what is on the host, validates `out`, queues
+    pbrt_{das,scan}_first_arrival[_probe]_dev and keeps what the kernel reads alive with the table"""
+    cx = next((a.ctx for a in (tx_delays, elem, gx, gz) if _is_dev(a)), None) or _capi.default_context()
+    d_tx = tx_delays if _is_dev(tx_delays) else _arg(cx, np.atleast_2d(np.asarray(tx_delays)))
+    A, E = d_tx.shape
+    elem, probe, eshape = _elem_arg(elem, E)
+    d_ex = _arg(cx, elem, eshape)
+    d_gx, d_gz, (n0, n1) = _pixels(cx, gx, gz, tables, True)
+    par, family = _block(_das_params(A, E, 2, n0, n1, 1.0, sound_speed, 0.0, 0.0, "linear", "sum"), tables, "das", 2.0, None, probe)
+    tab = out if out is not None else _capi.DeviceBuffer(cx, (A, n0, n1), np.float64)
+    if tab.nbytes != A * n0 * n1 * 8:
+        raise ValueError(f"out must hold n_angles * {'n0 * n1' if tables else 'nx * nz'} float64")
+    name = f"pbrt_{family}_first_arrival" + ("_probe" if probe and family == "das" else "") + "_dev"
+    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), d_tx.ptr, d_ex.ptr, d_gx.ptr, d_gz.ptr, tab.ptr), name)
+    tab._keep = (d_tx, d_ex, d_gx, d_gz)
+    return tab
 
 
 def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
     """first-arrival table of a scan, [n_angles, nx, nz] float64 in HBM: t_tx(a; x, z) = min_e (tx_delays[a, e] + distance to element e / c)
     (pbrt_das_first_arrival_dev; elem_x an element table [n_elements, 4]: pbrt_das_first_arrival_probe_dev).  It depends on the delays and the grid only: a loop that changes neither (USMain.py:262-289) makes it
     once and hands it to every das_beamform(..., table=...) call, which then skips its pass over all elements (same image bit for bit)."""
-    cx = next((a.ctx for a in (tx_delays, elem_x, x, z) if _is_dev(a)), None) or _capi.default_context()
-    d_tx = tx_delays if _is_dev(tx_delays) else _to_dev(cx, np.atleast_2d(np.asarray(tx_delays)))
-    A, E = d_tx.shape
-    elem_x, probe, eshape = _elem_arg(elem_x, E)
-    d_ex = _to_dev(cx, elem_x, eshape)
-    d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
-    d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
-    nx, nz = d_x.shape[0], d_z.shape[0]
-    p = _das_params(A, E, 2, nx, nz, 1.0, sound_speed, 0.0, 0.0, "linear", "sum")
-    tab = out if out is not None else _capi.DeviceBuffer(cx, (A, nx, nz), np.float64)
-    if tab.nbytes != A * nx * nz * 8:
-        raise ValueError("out must hold n_angles * nx * nz float64")
-    name = "pbrt_das_first_arrival_probe_dev" if probe else "pbrt_das_first_arrival_dev"
-    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(p), d_tx.ptr, d_ex.ptr, d_x.ptr, d_z.ptr, tab.ptr), name)
-    tab._keep = (d_tx, d_ex, d_x, d_z)
-    return tab
+    return _first_arrival(tx_delays, elem_x, x, z, False, sound_speed, out)
 
 
-def _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, *, t0, f_number, interpolation, compound, out, table, method=None,
-              p=2.0, demod_freq=None):
-    """das_beamform (method None), nonlinear_beamform and iq_beamform (demod_freq set): shapes and uploads the arguments, validates
-    `out` and `table`, selects the entry point -- pbrt_das_beamform[_table][_probe][_dev], or pbrt_bf_beamform[_table][_dev] /
-    pbrt_iq_beamform[_table][_dev] with the probe flag in their parameters -- and keeps what the queued kernel reads alive with its
-    result.  I/Q: data and result are complex64."""
+def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method, p=2.0, demod_freq=None, t0, f_number, interpolation,
+              compound, out, table):
+    """One beamform request, from every public call to its entry point: `data` by `method` ("das", "pdas" with p, "fdmas", or "iq"
+    with demod_freq: data and result complex64) on the pixels gx, gz -- the axes x, z, or (`tables`) two pixel tables.  Shapes the
+    arguments, holds RF against I/Q, uploads the small tables where the data is a DeviceBuffer, validates `out` and `table`, selects
+    the parameter block and the entry point (_block; [_table] with a first-arrival table, [_dev] for data in HBM), calls it and keeps
+    what a queued kernel reads alive with its result.  Host arrays in: a host array out, `out` and `table` are not read."""
     dev = _is_dev(data)
-    iq = demod_freq is not None
-    dtype, width = (np.complex64, 8) if iq else (np.float32, 4)
+    iq = method == "iq"
+    dtype = np.dtype(np.complex64 if iq else np.float32)
     cx = data.ctx if dev else _capi.default_context()
     if not dev:
-        data = np.ascontiguousarray(data, dtype=dtype)
+        data, out, table = np.ascontiguousarray(data, dtype=dtype), None, None
     elif iq != (data.dtype.kind == "c"):
         raise ValueError(f"the channel data must be {'complex64 (I/Q)' if iq else 'float32 (RF)'}, got a {data.dtype} DeviceBuffer")
     if len(data.shape) != 3:
         raise ValueError("data must be [n_angles, n_elements, time_samples]")
     A, E, T = data.shape
+    elem, probe, eshape = _elem_arg(elem, E)
+    tx, ex = _arg(cx, tx_delays, (A, E), dev), _arg(cx, elem, eshape, dev)
+    gx, gz, (n0, n1) = _pixels(cx, gx, gz, tables, dev)
+    par, family = _block(_das_params(A, E, T, n0, n1, fs, sound_speed, t0, f_number, interpolation, compound), tables, method, p,
+                         demod_freq, probe)
+    d0, d1 = ("n0", "n1") if tables else ("nx", "nz")
+    res = out if out is not None else _capi.DeviceBuffer(cx, (n0, n1), dtype) if dev else np.empty((n0, n1), dtype)
+    if res.nbytes != n0 * n1 * dtype.itemsize:
+        raise ValueError(f"out must hold {d0} * {d1} {dtype.name}")
+    if table is not None and table.nbytes != A * n0 * n1 * 8:   # the first-arrival times of this scan, made once
+        raise ValueError(f"table must be the [n_angles, {d0}, {d1}] float64 buffer of {'scan' if tables else 'das'}_first_arrival for this scan")
+    name = (f"pbrt_{family}_beamform" + ("_table" if table is not None else "") + ("_probe" if probe and family == "das" else "")
+            + ("_dev" if dev else ""))
+    args = (data, tx if table is None else table, ex, gx, gz, res)
+    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), *[a.ptr if dev else a.ctypes.data for a in args]), name)
     if dev:
-        elem_x, probe, eshape = _elem_arg(elem_x, E)
-        d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem_x, eshape)
-        d_x = x if _is_dev(x) else _to_dev(cx, np.asarray(x).ravel())
-        d_z = z if _is_dev(z) else _to_dev(cx, np.asarray(z).ravel())
-        nx, nz = d_x.shape[0], d_z.shape[0]
-    else:
-        tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
-        elem_x, probe, eshape = _elem_arg(elem_x, E)
-        ex = _capi.f32(np.asarray(elem_x).reshape(eshape))
-        gx, gz = _capi.f32(np.asarray(x).ravel()), _capi.f32(np.asarray(z).ravel())
-        nx, nz = len(gx), len(gz)
-    par = _das_params(A, E, T, nx, nz, fs, sound_speed, t0, f_number, interpolation, compound)
-    name = "pbrt_das_beamform"
-    if method is not None:
-        par, name = _bf_params(par, method, p, probe), "pbrt_bf_beamform"
-    elif iq:
-        par, name = _iq_params(par, demod_freq, probe), "pbrt_iq_beamform"
-    flag_in_params = method is not None or iq   # (their parameter blocks carry the probe flag: no *_probe names)
-    if not dev:
-        name += "_probe" if probe and not flag_in_params else ""
-        res = np.empty((nx, nz), dtype=dtype)
-        cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
-                                       _capi.addr(gz), _capi.addr(res)), name)
-        return res
-    d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz), dtype)
-    if d_out.nbytes != nx * nz * width:
-        raise ValueError(f"out must hold nx * nz {np.dtype(dtype).name}")
-    if table is not None:   # the first-arrival times of this scan, made once (das_first_arrival)
-        if table.nbytes != A * nx * nz * 8:
-            raise ValueError("table must be the [n_angles, nx, nz] float64 buffer of das_first_arrival for this scan")
-        name += "_table"
-    name += ("_probe" if probe and not flag_in_params else "") + "_dev"
-    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(par), data.ptr, (d_tx if table is None else table).ptr, d_ex.ptr, d_x.ptr,
-                                   d_z.ptr, d_out.ptr), name)
-    d_out._keep = (d_tx, d_ex, d_x, d_z, table)  # the queued kernel reads them: they live as long as its result
-    return d_out
+        res._keep = (tx, ex, gx, gz, table)  # the queued kernel reads them: they live as long as its result
+    return res
 
 
 def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_number=1.0, interpolation="linear",
@@ -151,16 +183,8 @@ def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_numbe
     times from das_first_arrival (pbrt_das_beamform_table_dev).
     elem_x [n_elements, 4] = (x, z, nx, nz): the element table of a curved probe; the same calls with `_probe` in their names
     (distances to (x_e, z_e), the f-number aperture in the element's frame: include/pbrt_hip.h)."""
-    return _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
-                     compound=compound, out=out, table=table)
-
-
-def _bf_params(das, method, p, probe) -> "_capi.BfParams":
-    bp = _capi.BfParams()
-    bp.das = das
-    bp.method = {"pdas": _capi.BF_PDAS, "fdmas": _capi.BF_FDMAS}[method]
-    bp.p, bp.probe = float(p), int(bool(probe))
-    return bp
+    return _beamform(data, tx_delays, elem_x, x, z, False, fs, sound_speed, method="das", t0=t0, f_number=f_number,
+                     interpolation=interpolation, compound=compound, out=out, table=table)
 
 
 def nonlinear_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, method="fdmas", p=2.0, t0=0.0, f_number=1.0,
@@ -171,15 +195,8 @@ def nonlinear_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, method="f
     das_first_arrival), queued, a DeviceBuffer out.  elem_x [n_elements] or the element table [n_elements, 4]."""
     if method not in ("pdas", "fdmas"):
         raise ValueError(f"method must be 'pdas' or 'fdmas', got {method!r}")
-    return _beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
-                     compound=compound, out=out, table=table, method=method, p=p)
-
-
-def _iq_params(das, demod_freq, probe) -> "_capi.IqParams":
-    ip = _capi.IqParams()
-    ip.das = das
-    ip.demod_freq, ip.probe = float(demod_freq), int(bool(probe))
-    return ip
+    return _beamform(data, tx_delays, elem_x, x, z, False, fs, sound_speed, method=method, p=p, t0=t0, f_number=f_number,
+                     interpolation=interpolation, compound=compound, out=out, table=table)
 
 
 def iq_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, t0=0.0, f_number=1.0, interpolation="linear",
@@ -190,56 +207,18 @@ def iq_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, t0=0.
     Arguments and the host / DeviceBuffer rule as das_beamform: host arrays in -> pbrt_iq_beamform and a host array out; `iq` a complex
     DeviceBuffer -> pbrt_iq_beamform_dev (or _table_dev with `table` from das_first_arrival), queued, a complex DeviceBuffer out.
     elem [n_elements] or the element table [n_elements, 4]."""
-    demod_freq = float(demod_freq)
-    if not (np.isfinite(demod_freq) and demod_freq >= 0.0):
-        raise ValueError(f"demod_freq must be finite and >= 0, got {demod_freq}")
-    return _beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, t0=t0, f_number=f_number, interpolation=interpolation,
-                     compound=compound, out=out, table=table, demod_freq=demod_freq)
+    return _beamform(iq, tx_delays, elem, x, z, False, fs_iq, sound_speed, method="iq", demod_freq=_checked_demod_freq(float(demod_freq)),
+                     t0=t0, f_number=f_number, interpolation=interpolation, compound=compound, out=out, table=table)
 
 
 _SCAN_METHODS = ("das", "pdas", "fdmas", "iq")
-
-
-def _scan_params(das, method, p, demod_freq, probe) -> "_capi.ScanParams":
-    sp = _capi.ScanParams()
-    sp.das = das
-    sp.method = {"das": _capi.SCAN_DAS, "pdas": _capi.BF_PDAS, "fdmas": _capi.BF_FDMAS, "iq": _capi.SCAN_IQ}[method]
-    sp.p, sp.demod_freq, sp.probe = float(p), float(demod_freq or 0.0), int(bool(probe))
-    return sp
-
-
-def _pixel_tables(cx, px, pz, dev):
-    """the two pixel tables [n0, n1] of a scan as they are handed on (host float32 arrays, or DeviceBuffers), and (n0, n1)"""
-    if _is_dev(px) != _is_dev(pz):
-        raise ValueError("px and pz must both be host arrays or both DeviceBuffers")
-    if not _is_dev(px):
-        px, pz = _capi.f32(np.asarray(px)), _capi.f32(np.asarray(pz))
-    if len(px.shape) != 2 or tuple(px.shape) != tuple(pz.shape):
-        raise ValueError(f"px and pz must be two tables of one shape [n0, n1], got {list(px.shape)} and {list(pz.shape)}")
-    shape = tuple(int(v) for v in px.shape)
-    if dev and not _is_dev(px):
-        px, pz = _capi.DeviceBuffer.from_host(cx, px), _capi.DeviceBuffer.from_host(cx, pz)
-    return px, pz, shape
 
 
 def scan_first_arrival(tx_delays, elem, px, pz, sound_speed, out=None):
     """das_first_arrival for a scan given as pixel tables px, pz [n0, n1] (metres, the probe's frame): [n_angles, n0, n1] float64 in
     HBM, t_tx(a; pixel) = min_e (tx_delays[a, e] + distance to element e / c) (pbrt_scan_first_arrival_dev).  elem [n_elements] or
     the element table [n_elements, 4].  On the tables of a separable scan it equals das_first_arrival bit for bit."""
-    cx = next((a.ctx for a in (tx_delays, elem, px, pz) if _is_dev(a)), None) or _capi.default_context()
-    d_tx = tx_delays if _is_dev(tx_delays) else _to_dev(cx, np.atleast_2d(np.asarray(tx_delays)))
-    A, E = d_tx.shape
-    elem, probe, eshape = _elem_arg(elem, E)
-    d_ex = _to_dev(cx, elem, eshape)
-    d_px, d_pz, (n0, n1) = _pixel_tables(cx, px, pz, True)
-    sp = _scan_params(_das_params(A, E, 2, n0, n1, 1.0, sound_speed, 0.0, 0.0, "linear", "sum"), "das", 2.0, None, probe)
-    tab = out if out is not None else _capi.DeviceBuffer(cx, (A, n0, n1), np.float64)
-    if tab.nbytes != A * n0 * n1 * 8:
-        raise ValueError("out must hold n_angles * n0 * n1 float64")
-    cx.check(cx.lib.pbrt_scan_first_arrival_dev(cx.handle, C.byref(sp), d_tx.ptr, d_ex.ptr, d_px.ptr, d_pz.ptr, tab.ptr),
-             "pbrt_scan_first_arrival_dev")
-    tab._keep = (d_tx, d_ex, d_px, d_pz)
-    return tab
+    return _first_arrival(tx_delays, elem, px, pz, True, sound_speed, out)
 
 
 def scan_beamform(data, tx_delays, elem, px, pz, fs, sound_speed, method="das", p=2.0, demod_freq=None, t0=0.0, f_number=1.0,
@@ -253,43 +232,36 @@ def scan_beamform(data, tx_delays, elem, px, pz, fs, sound_speed, method="das", 
     scan_first_arrival -> pbrt_scan_beamform_table_dev.  elem [n_elements] or the element table [n_elements, 4]."""
     if method not in _SCAN_METHODS:
         raise ValueError(f"method must be one of {_SCAN_METHODS}, got {method!r}")
-    iq = method == "iq"
-    if iq:
-        if demod_freq is None or not (np.isfinite(float(demod_freq)) and float(demod_freq) >= 0.0):
-            raise ValueError(f"demod_freq must be finite and >= 0, got {demod_freq}")
-    dev = _is_dev(data)
-    dtype, width = (np.complex64, 8) if iq else (np.float32, 4)
-    cx = data.ctx if dev else _capi.default_context()
-    if not dev:
-        data = np.ascontiguousarray(data, dtype=dtype)
-    elif iq != (data.dtype.kind == "c"):
-        raise ValueError(f"the channel data must be {'complex64 (I/Q)' if iq else 'float32 (RF)'}, got a {data.dtype} DeviceBuffer")
-    if len(data.shape) != 3:
-        raise ValueError("data must be [n_angles, n_elements, time_samples]")
-    A, E, T = data.shape
-    elem, probe, eshape = _elem_arg(elem, E)
-    gx, gz, (n0, n1) = _pixel_tables(cx, px, pz, dev)
-    sp = _scan_params(_das_params(A, E, T, n0, n1, fs, sound_speed, t0, f_number, interpolation, compound), method, p, demod_freq, probe)
-    if not dev:
-        tx = _capi.f32(np.asarray(tx_delays).reshape(A, E))
-        ex = _capi.f32(np.asarray(elem).reshape(eshape))
-        res = np.empty((n0, n1), dtype=dtype)
-        cx.check(cx.lib.pbrt_scan_beamform(cx.handle, C.byref(sp), _capi.addr(data), _capi.addr(tx), _capi.addr(ex), _capi.addr(gx),
-                                           _capi.addr(gz), _capi.addr(res)), "pbrt_scan_beamform")
+    if method == "iq":
+        _checked_demod_freq(demod_freq)
+    return _beamform(data, tx_delays, elem, px, pz, True, fs, sound_speed, method=method, p=p, demod_freq=demod_freq, t0=t0,
+                     f_number=f_number, interpolation=interpolation, compound=compound, out=out, table=table)
+
+
+def _step(stem, src, args, shape, dtype, out, message=None):
+    """One step around the beamformer in its host or its device form.  src: the input that decides -- a host array -> the entry
+    point `stem`, a host array of `shape` and `dtype` out; a DeviceBuffer -> stem + "_dev", queued, the result `out` (which must
+    hold `shape`: ValueError(message), where the step has one) or a new DeviceBuffer, which keeps src and the other buffers alive.
+    args: what the entry point takes between the context and the output -- scalars, and buffers that are all of src's kind."""
+    if not isinstance(src, _capi.DeviceBuffer):
+        cx, res = _capi.default_context(), np.empty(shape, dtype)
+        cx.check(getattr(cx.lib, stem)(cx.handle, *[a.ctypes.data if isinstance(a, np.ndarray) else a for a in args], res.ctypes.data), stem)
         return res
-    d_tx, d_ex = _to_dev(cx, tx_delays, (A, E)), _to_dev(cx, elem, eshape)
-    d_out = out if out is not None else _capi.DeviceBuffer(cx, (n0, n1), dtype)
-    if d_out.nbytes != n0 * n1 * width:
-        raise ValueError(f"out must hold n0 * n1 {np.dtype(dtype).name}")
-    name = "pbrt_scan_beamform_dev"
-    if table is not None:   # the first-arrival times of this scan, made once (scan_first_arrival)
-        if table.nbytes != A * n0 * n1 * 8:
-            raise ValueError("table must be the [n_angles, n0, n1] float64 buffer of scan_first_arrival for this scan")
-        name = "pbrt_scan_beamform_table_dev"
-    cx.check(getattr(cx.lib, name)(cx.handle, C.byref(sp), data.ptr, (d_tx if table is None else table).ptr, d_ex.ptr, gx.ptr, gz.ptr,
-                                   d_out.ptr), name)
-    d_out._keep = (d_tx, d_ex, gx, gz, table)  # the queued kernel reads them: they live as long as its result
-    return d_out
+    cx, name = src.ctx, stem + "_dev"
+    res = out if out is not None else _capi.DeviceBuffer(cx, shape, dtype)
+    if message is not None and res.nbytes != math.prod(shape) * np.dtype(dtype).itemsize:
+        raise ValueError(message)
+    ptrs, keep = [], [src]
+    for a in args:   # (one pass: this runs once per queued step of every us_render call)
+        if isinstance(a, _capi.DeviceBuffer):
+            ptrs.append(a.ptr)
+            if a is not src:
+                keep.append(a)
+        else:
+            ptrs.append(a)
+    cx.check(getattr(cx.lib, name)(cx.handle, *ptrs, res.ptr), name)
+    res._keep = tuple(keep)
+    return res
 
 
 def scan_convert(img, scan, x_axis, z_axis, fill=0.0, out=None):
@@ -304,27 +276,14 @@ def scan_convert(img, scan, x_axis, z_axis, fill=0.0, out=None):
         raise ValueError(f"the image must have the scan's shape {list(scan.shape)} = [n_theta, n_rho], got {list(img.shape)}")
     if dev and img.dtype != np.float32:
         raise ValueError(f"scan_convert takes a float32 image (an envelope), got a {img.dtype} DeviceBuffer")
-    nx = x_axis.shape[0] if _is_dev(x_axis) else np.asarray(x_axis).size
-    nz = z_axis.shape[0] if _is_dev(z_axis) else np.asarray(z_axis).size
+    gx, gz, (nx, nz) = _pixels(cx, x_axis, z_axis, False, dev)
     sc = _capi.ScanConvertParams()
     sc.n_theta, sc.n_rho, sc.nx, sc.nz = scan.shape[0], scan.shape[1], int(nx), int(nz)
     sc.theta0, sc.dtheta = float(scan.thetas[0]), float((scan.thetas[-1] - scan.thetas[0]) / (len(scan.thetas) - 1))
     sc.rho0, sc.drho = float(scan.rhos[0]), float((scan.rhos[-1] - scan.rhos[0]) / (len(scan.rhos) - 1))
     sc.ox, sc.oz = scan.origin
     sc.fill = float(fill)
-    if dev:
-        d_x, d_z = _to_dev(cx, x_axis, (nx,)), _to_dev(cx, z_axis, (nz,))
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, (nx, nz))
-        if d_out.nbytes != nx * nz * 4:
-            raise ValueError("out must hold nx * nz float32")
-        cx.check(cx.lib.pbrt_scan_convert_dev(cx.handle, C.byref(sc), img.ptr, d_x.ptr, d_z.ptr, d_out.ptr), "pbrt_scan_convert_dev")
-        d_out._keep = (img, d_x, d_z)
-        return d_out
-    gx, gz = _capi.f32(np.asarray(x_axis).ravel()), _capi.f32(np.asarray(z_axis).ravel())
-    res = np.empty((nx, nz), np.float32)
-    cx.check(cx.lib.pbrt_scan_convert(cx.handle, C.byref(sc), _capi.addr(img), _capi.addr(gx), _capi.addr(gz), _capi.addr(res)),
-             "pbrt_scan_convert")
-    return res
+    return _step("pbrt_scan_convert", img, (C.byref(sc), img, gx, gz), (nx, nz), np.float32, out, "out must hold nx * nz float32")
 
 
 RF2IQ_MAX_DECIMATION = 8
@@ -379,24 +338,20 @@ def rf2iq(data, central_freq, sampling_freq, t0=0.0, bandwidth=100, decimation=1
         if np.iscomplexobj(data):
             raise ValueError("rf2iq takes real RF traces, got complex data")
         x = _capi.f32(np.asarray(data))
-    cx = data.ctx if dev else _capi.default_context()
     shape = tuple(x.shape)
     T = shape[-1]
     n_traces = int(np.prod(shape[:-1], dtype=np.int64))
     oshape = shape[:-1] + (-(-T // D),)
-    args = (n_traces, T, fs, float(t0), fc, D, K)
-    if dev:
-        d_taps = taps if _is_dev(taps) else _capi.DeviceBuffer.from_host(cx, _capi.f32(np.asarray(taps).ravel()))
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, oshape, np.complex64)
-        if d_out.nbytes != int(np.prod(oshape, dtype=np.int64)) * 8:
-            raise ValueError(f"out must hold {list(oshape)} complex64")
-        cx.check(cx.lib.pbrt_rf2iq_dev(cx.handle, *args, d_taps.ptr, x.ptr, d_out.ptr), "pbrt_rf2iq_dev")
-        d_out._keep = (x, d_taps)
-        return d_out
-    h = _capi.f32(np.asarray(taps).ravel())
-    res = np.empty(oshape, np.complex64)
-    cx.check(cx.lib.pbrt_rf2iq(cx.handle, *args, _capi.addr(h), _capi.addr(x), _capi.addr(res)), "pbrt_rf2iq")
-    return res
+    h = _arg(x.ctx if dev else None, taps, (-1,), dev)
+    return _step("pbrt_rf2iq", x, (n_traces, T, fs, float(t0), fc, D, K, h, x), oshape, np.complex64, out,
+                 f"out must hold {list(oshape)} complex64")
+
+
+def _columns(rf):
+    """an image [nx, nz], or one column [nz], as the axial steps take it (a host array: float32 [nx, nz]), and (nx, nz)"""
+    if not _is_dev(rf):
+        rf = _capi.f32(np.atleast_2d(np.asarray(rf)))
+    return rf, (rf.shape if len(rf.shape) == 2 else (1, rf.shape[0]))
 
 
 def iq_envelope(iq, out=None):
@@ -405,20 +360,11 @@ def iq_envelope(iq, out=None):
     if _is_dev(iq):
         if iq.dtype.kind != "c":
             raise ValueError(f"iq_envelope takes complex64 data, got a {iq.dtype} DeviceBuffer")
-        cx, n = iq.ctx, iq.nbytes // 8
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, iq.shape)
-        if d_out.nbytes != n * 4:
-            raise ValueError("out must hold one float32 per pixel")
-        cx.check(cx.lib.pbrt_iq_envelope_dev(cx.handle, n, iq.ptr, d_out.ptr), "pbrt_iq_envelope_dev")
-        d_out._keep = (iq,)
-        return d_out
-    if not np.iscomplexobj(iq):
+    elif not np.iscomplexobj(iq):
         raise ValueError("iq_envelope takes complex data")
-    cx = _capi.default_context()
-    a = np.ascontiguousarray(iq, dtype=np.complex64)
-    res = np.empty(a.shape, np.float32)
-    cx.check(cx.lib.pbrt_iq_envelope(cx.handle, a.size, _capi.addr(a), _capi.addr(res)), "pbrt_iq_envelope")
-    return res
+    else:
+        iq = np.ascontiguousarray(iq, dtype=np.complex64)
+    return _step("pbrt_iq_envelope", iq, (iq.nbytes // 8, iq), iq.shape, np.float32, out, "out must hold one float32 per pixel")
 
 
 def axial_fir(rf, taps, out=None):
@@ -428,23 +374,10 @@ def axial_fir(rf, taps, out=None):
     n_taps = taps.shape[0] if _is_dev(taps) else np.asarray(taps).size
     if n_taps % 2 != 1:
         raise ValueError("taps must be [2 K + 1]")
-    K = n_taps // 2
-    cx = rf.ctx if _is_dev(rf) else _capi.default_context()
-    if _is_dev(rf):
-        nx, nz = (rf.shape if len(rf.shape) == 2 else (1, rf.shape[0]))
-        d_taps = _to_dev(cx, taps, (n_taps,))
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, rf.shape)
-        if d_out.nbytes != nx * nz * 4:
-            raise ValueError("out must hold nx * nz float32")
-        cx.check(cx.lib.pbrt_axial_fir_dev(cx.handle, nx, nz, K, d_taps.ptr, rf.ptr, d_out.ptr), "pbrt_axial_fir_dev")
-        d_out._keep = (rf, d_taps)
-        return d_out
-    rf = _capi.f32(np.atleast_2d(np.asarray(rf)))
-    h = _capi.f32(np.asarray(taps).ravel())
-    nx, nz = rf.shape
-    res = np.empty_like(rf)
-    cx.check(cx.lib.pbrt_axial_fir(cx.handle, nx, nz, K, _capi.addr(h), _capi.addr(rf), _capi.addr(res)), "pbrt_axial_fir")
-    return res
+    dev = _is_dev(rf)
+    rf, (nx, nz) = _columns(rf)
+    h = _arg(rf.ctx if dev else None, taps, (n_taps,), dev)
+    return _step("pbrt_axial_fir", rf, (nx, nz, n_taps // 2, h, rf), rf.shape, np.float32, out, "out must hold nx * nz float32")
 
 
 FIR_MAX_K = 1024
@@ -491,53 +424,25 @@ def bandpass_taps(f_lo, f_hi, fs_ax, K=None) -> np.ndarray:
 def envelope(rf, out=None):
     """|analytic signal| along the last (axial) axis of a [nx, nz] RF image (pbrt_envelope; a DeviceBuffer in gives a
     DeviceBuffer out, queued on the context's stream)."""
-    cx = rf.ctx if _is_dev(rf) else _capi.default_context()
-    if _is_dev(rf):
-        nx, nz = (rf.shape if len(rf.shape) == 2 else (1, rf.shape[0]))
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, rf.shape)
-        cx.check(cx.lib.pbrt_envelope_dev(cx.handle, nx, nz, rf.ptr, d_out.ptr), "pbrt_envelope_dev")
-        d_out._keep = (rf,)
-        return d_out
-    rf = _capi.f32(np.atleast_2d(np.asarray(rf)))
-    nx, nz = rf.shape
-    res = np.empty_like(rf)
-    cx.check(cx.lib.pbrt_envelope(cx.handle, nx, nz, _capi.addr(rf), _capi.addr(res)), "pbrt_envelope")
-    return res
+    rf, (nx, nz) = _columns(rf)
+    return _step("pbrt_envelope", rf, (nx, nz, rf), rf.shape, np.float32, out)
 
 
 def log_compress(env, dynamic_range=60.0, out=None):
     """USMain.py:210-218: 20 log10(env + 1e-12) clipped to the top `dynamic_range` dB, mapped to [0, 1]."""
-    cx = env.ctx if _is_dev(env) else _capi.default_context()
-    if _is_dev(env):
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, env.shape)
-        n = env.nbytes // 4
-        cx.check(cx.lib.pbrt_log_compress_dev(cx.handle, n, env.ptr, float(dynamic_range), d_out.ptr), "pbrt_log_compress_dev")
-        d_out._keep = (env,)
-        return d_out
-    env = _capi.f32(np.asarray(env))
-    res = np.empty_like(env)
-    cx.check(cx.lib.pbrt_log_compress(cx.handle, env.size, _capi.addr(env), float(dynamic_range), _capi.addr(res)),
-             "pbrt_log_compress")
-    return res
+    if not _is_dev(env):
+        env = _capi.f32(np.asarray(env))
+    return _step("pbrt_log_compress", env, (env.nbytes // 4, env, float(dynamic_range)), env.shape, np.float32, out)
 
 
 def apply_pulse(traces, fs, frequency, sigma, out=None):
     """SURVEY f-3 pulse model (RayTracingV0.py:194-204): every trace (last axis) convolved with
     h[k] = sin(2 pi f k / fs) exp(-(k / fs)^2 / sigma^2)  (pbrt_us_apply_pulse; DeviceBuffer in -> DeviceBuffer out)."""
-    cx = traces.ctx if _is_dev(traces) else _capi.default_context()
-    if _is_dev(traces):
-        T = traces.shape[-1]
-        d_out = out if out is not None else _capi.DeviceBuffer(cx, traces.shape)
-        cx.check(cx.lib.pbrt_us_apply_pulse_dev(cx.handle, (traces.nbytes // 4) // T, T, float(fs), float(frequency), float(sigma),
-                                                traces.ptr, d_out.ptr), "pbrt_us_apply_pulse_dev")
-        d_out._keep = (traces,)
-        return d_out
-    x = _capi.f32(np.asarray(traces))
-    T = x.shape[-1]
-    res = np.empty_like(x)
-    cx.check(cx.lib.pbrt_us_apply_pulse(cx.handle, x.size // T, T, float(fs), float(frequency), float(sigma), _capi.addr(x),
-                                        _capi.addr(res)), "pbrt_us_apply_pulse")
-    return res
+    if not _is_dev(traces):
+        traces = _capi.f32(np.asarray(traces))
+    T = traces.shape[-1]
+    return _step("pbrt_us_apply_pulse", traces, ((traces.nbytes // 4) // T, T, float(fs), float(frequency), float(sigma), traces),
+                 traces.shape, np.float32, out)
 
 
 # ---- ultraspy-shaped front end (USMain.py:126-205) ---------------------------------------------------------------
@@ -693,6 +598,8 @@ def polar_n_theta(rho_max, theta_range, step) -> int:
 
 
 class DelayAndSum:
+    _method = "das"
+
     def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", is_iq=False):
         self.on_gpu = on_gpu  # accepted for compatibility; the beamformer has no CPU path
         # is_iq: the data are I/Q samples (complex64) at the rate acquisition_info['sampling_freq'], demodulated at `demod_freq`
@@ -728,36 +635,34 @@ class DelayAndSum:
         f = self.setups["demod_freq"]
         return float(self.probe.central_freq if f is None else f)
 
-    def beamform(self, d_data, scan, out=None, table=None):
-        """host array in -> host array out; a DeviceBuffer in (the channel buffer left in HBM) -> a DeviceBuffer out, queued.
-        is_iq: complex64 in (host, or a complex DeviceBuffer), complex out."""
-        ai = self.acquisition_info
-        if ai is None or self.probe is None:
-            raise RuntimeError("DelayAndSum.automatic_setup(acquisition_info, probe) has not been called")
+    def _checked(self, d_data):
+        """the data as they go on: a DeviceBuffer, or the host array without its frame axis.  RuntimeError before automatic_setup;
+        ValueError where real or complex data meet the wrong is_iq."""
+        if self.acquisition_info is None or self.probe is None:
+            raise RuntimeError(f"{type(self).__name__}.automatic_setup(acquisition_info, probe) has not been called")
         data = d_data
         if not _is_dev(data):
             data = np.asarray(d_data)
             if data.ndim == 4:      # (frames, n_angles, n_elements, T): USMain passes reader.data[0]
                 data = data[0]
         _check_iq(self, data)
+        return data
+
+    def _request(self, data, scan, out, table):
+        """the beamform request acquisition_info, the probe, the setups and the scan make up, by the class's method and p"""
+        ai, su, iq, dev = self.acquisition_info, self.setups, self.is_iq, _is_dev(data)
         # tables that already sit in HBM (us_render keeps them there between calls) are used where the data is a DeviceBuffer
-        dev = _is_dev(data)
         ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
-        polar, gx, gz = _scan_tables(scan, dev)
-        if polar:   # a PolarScan: the same arithmetic on its pixel tables (DESIGN D21)
-            return scan_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"],
-                                 method="iq" if self.is_iq else "das", demod_freq=self.demod_freq() if self.is_iq else None,
-                                 t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
-                                 interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out,
-                                 table=table if dev else None)
-        if self.is_iq:
-            return iq_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], self.demod_freq(),
-                               t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
-                               interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out,
-                               table=table if dev else None)
-        return das_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], t0=ai.get("t0", 0.0) or 0.0,
-                            f_number=self.setups["f_number"], interpolation=self.setups["interpolation"],
-                            compound=self.setups["compound"], out=out, table=table if dev else None)
+        polar, gx, gz = _scan_tables(scan, dev)   # (a PolarScan: the same arithmetic on its pixel tables, DESIGN D21)
+        return _beamform(data, ai["delays"], ex, gx, gz, polar, ai["sampling_freq"], ai["sound_speed"],
+                         method="iq" if iq else self._method, p=su.get("p", 2.0),
+                         demod_freq=_checked_demod_freq(self.demod_freq()) if iq else None, t0=ai.get("t0", 0.0) or 0.0,
+                         f_number=su["f_number"], interpolation=su["interpolation"], compound=su["compound"], out=out, table=table)
+
+    def beamform(self, d_data, scan, out=None, table=None):
+        """host array in -> host array out; a DeviceBuffer in (the channel buffer left in HBM) -> a DeviceBuffer out, queued.
+        is_iq: complex64 in (host, or a complex DeviceBuffer), complex out."""
+        return self._request(self._checked(d_data), scan, out, table)
 
     def compute_envelope(self, d_output, scan=None, out=None):
         if self.is_iq:
@@ -781,7 +686,6 @@ class _NonlinearBeamformer(DelayAndSum):
     """p-DAS / F-DMAS in the shape of DelayAndSum (DESIGN D19): beamform() runs the non-linear kernel and, unless the setup `band`
     is None, the axial band-pass.  Setup keys: DelayAndSum's, `band` ("default": centre (1 -+ probe.bandwidth / 200) around
     `_centre` x probe.central_freq; (f_lo, f_hi) in Hz; None: no filter) and `taps_half_length` (None: bandpass_taps' default)."""
-    _method = None
     _centre = 1.0   # band centre in units of the probe's central frequency
 
     def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", band="default", taps_half_length=None,
@@ -829,42 +733,20 @@ class _NonlinearBeamformer(DelayAndSum):
                 f"{c / (4.0 * f_hi):.4g} m would fit -- pass step= to us_render (DESIGN D19)")
         return bandpass_taps(f_lo, f_hi, fs_ax, self.setups["taps_half_length"])
 
-    def _raw(self, data, ai, ex, gx, gz, out, table, polar=False):
-        if polar:   # gx, gz are the pixel tables of a PolarScan (DESIGN D21)
-            return scan_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], method=self._method,
-                                 p=self.setups.get("p", 2.0), t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
-                                 interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out, table=table)
-        return nonlinear_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], method=self._method,
-                                  p=self.setups.get("p", 2.0), t0=ai.get("t0", 0.0) or 0.0, f_number=self.setups["f_number"],
-                                  interpolation=self.setups["interpolation"], compound=self.setups["compound"], out=out, table=table)
-
     def beamform(self, d_data, scan, out=None, table=None):
         """host array in -> host array out; a DeviceBuffer in -> a DeviceBuffer out, queued (kernel, then the band-pass)"""
-        ai = self.acquisition_info
-        if ai is None or self.probe is None:
-            raise RuntimeError(f"{type(self).__name__}.automatic_setup(acquisition_info, probe) has not been called")
-        data = d_data
-        if not _is_dev(data):
-            data = np.asarray(d_data)
-            if data.ndim == 4:
-                data = data[0]
-        _check_iq(self, data)
-        dev = _is_dev(data)
-        ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
-        polar, gx, gz = _scan_tables(scan, dev)
-        taps = self.filter_taps(scan, ai["sound_speed"])
+        data = self._checked(d_data)
+        taps = self.filter_taps(scan, self.acquisition_info["sound_speed"])
         if taps is None:
-            return self._raw(data, ai, ex, gx, gz, out, table if dev else None, polar)
-        if not dev:
-            return axial_fir(self._raw(data, ai, ex, gx, gz, None, None, polar), taps)
+            return self._request(data, scan, out, table)
+        if not _is_dev(data):
+            return axial_fir(self._request(data, scan, None, None), taps)
         # the taps in HBM: uploaded once per change (us_render puts its plan's copy here, with the buffer of the unfiltered image)
         key = taps.tobytes()
         if self._taps_cache[0] != key or self._taps_cache[1].ctx is not data.ctx:
             self._taps_cache = (key, _capi.DeviceBuffer.from_host(data.ctx, taps))
-        d_taps = self._taps_cache[1]
-        raw = self._raw(data, ai, ex, gx, gz, self.scratch_dev if self.scratch_dev is not None and self.scratch_dev.shape == scan.shape else None,
-                        table, polar)
-        return axial_fir(raw, d_taps, out=out)
+        scratch = self.scratch_dev if self.scratch_dev is not None and self.scratch_dev.shape == scan.shape else None
+        return axial_fir(self._request(data, scan, scratch, table), self._taps_cache[1], out=out)
 
     def __str__(self):
         return f"{type(self).__name__}(MI355X, {self.setups})"

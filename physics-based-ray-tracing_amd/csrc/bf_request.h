@@ -1,0 +1,65 @@
+// One beamform request: "beamform this channel data on these pixels by this method", as every pbrt_das_* / pbrt_bf_* / pbrt_iq_* /
+// pbrt_scan_* entry point hands it to the launch (pbrt_api.hip beamform_host, beamform_dev, first_arrival_dev, das_enqueue), and
+// the rules its four public parameter blocks must keep -- each written once.  Plain host code (no HIP), so that
+// tests/native/bf_request_check.cpp can build it on its own.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/pbrt_hip.h"
+
+#define DAS_TILE 8u
+#define DAS_XCDS 8u
+#define DAS_BANDS (2u * DAS_XCDS)
+
+struct BfRequest {
+    const pbrt_das_params *das;
+    uint32_t method;  // one numbering everywhere: PBRT_SCAN_DAS (0), PBRT_BF_PDAS, PBRT_BF_FDMAS, PBRT_SCAN_IQ
+    float pw;         // the launch argument of the method: p (p-DAS, F-DMAS does not read it), the demodulation frequency (I/Q), else 0
+    bool probe;       // the elements are a table [n_elements][4] of pbrt_us_array_elements, not positions [n_elements]
+    bool tab;         // the pixels are two tables [nx][nz] (pbrt_scan_*), not the axes x[nx], z[nz]
+};
+
+// tiles of DAS_TILE pixels along an axis of n
+static inline uint32_t das_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + DAS_TILE - 1u) / DAS_TILE); }
+
+// a rule of the makers below: its own text is the refusal
+#define BF_RULE(cond)              \
+    do {                           \
+        if (!(cond)) return #cond; \
+    } while (0)
+
+// -> nullptr and *rq filled, or the text of the first rule that failed.  `p` is read by PBRT_BF_PDAS only, `demod_freq` by PBRT_SCAN_IQ only.
+static inline const char *bf_request(BfRequest *rq, const pbrt_das_params *das, uint32_t method, float p, float demod_freq, uint32_t probe,
+                                     bool tab) {
+    BF_RULE(das != nullptr);
+    BF_RULE(method == PBRT_SCAN_DAS || method == PBRT_BF_PDAS || method == PBRT_BF_FDMAS || method == PBRT_SCAN_IQ);
+    BF_RULE(probe <= 1u);
+    BF_RULE(method != PBRT_BF_PDAS || (std::isfinite(p) && p >= 1.0f && p <= 8.0f));
+    BF_RULE(method != PBRT_SCAN_IQ || (std::isfinite(demod_freq) && demod_freq >= 0.0f));
+    BF_RULE(das->n_angles > 0 && das->n_elements > 0 && das->time_samples > 1 && das->fs > 0.0f && das->sound_speed > 0.0f);
+    BF_RULE(das->interpolation <= PBRT_DAS_LINEAR && das->f_number >= 0.0f);
+    BF_RULE(das->nx > 0 && das->nz > 0 && (uint64_t)das->nx * das->nz < 0xffffffffull);
+    // (the launch grid of das_enqueue: every XCD gets the z-tiles of the largest share, at most all of them and one per band)
+    BF_RULE((uint64_t)das_tiles(das->nx) * (das_tiles(das->nz) + DAS_BANDS) * DAS_XCDS < 0x7fffffffull);
+    *rq = BfRequest{das, method, method == PBRT_SCAN_IQ ? demod_freq : method == PBRT_SCAN_DAS ? 0.0f : p, probe != 0u, tab};
+    return nullptr;
+}
+
+// the four public blocks: the methods each admits, then the rules above
+static inline const char *bf_request(BfRequest *rq, const pbrt_das_params *p, bool probe) {  // pbrt_das_*[_probe]
+    return bf_request(rq, p, PBRT_SCAN_DAS, 0.0f, 0.0f, probe ? 1u : 0u, false);
+}
+static inline const char *bf_request(BfRequest *rq, const pbrt_bf_params *p) {  // (plain delay-and-sum has its own calls)
+    BF_RULE(p != nullptr);
+    BF_RULE(p->method == PBRT_BF_PDAS || p->method == PBRT_BF_FDMAS);
+    return bf_request(rq, &p->das, p->method, p->p, 0.0f, p->probe, false);
+}
+static inline const char *bf_request(BfRequest *rq, const pbrt_iq_params *p) {
+    BF_RULE(p != nullptr);
+    return bf_request(rq, &p->das, PBRT_SCAN_IQ, 0.0f, p->demod_freq, p->probe, false);
+}
+static inline const char *bf_request(BfRequest *rq, const pbrt_scan_params *p) {
+    BF_RULE(p != nullptr);
+    return bf_request(rq, &p->das, p->method, p->p, p->demod_freq, p->probe, true);
+}

@@ -4,6 +4,7 @@
 // here): the arithmetic below is this build's own definition (include/pbrt_hip.h), restated in oracle/beamform.py.
 #pragma once
 #include "../../include/pbrt_hip.h"
+#include "bf_request.h"
 #include "device_math.h"
 
 // ---- delay and sum --------------------------------------------------------------------------------------------------------
@@ -37,9 +38,6 @@
 #ifndef DAS_SPLIT
 #define DAS_SPLIT 4  // waves that share the elements of one tile (1, 2, 4 or 8)
 #endif
-#define DAS_TILE 8u
-#define DAS_XCDS 8u
-#define DAS_BANDS (2u * DAS_XCDS)
 
 // Which tile does workgroup b take?  Workgroup b runs on XCD b % 8, and every XCD has its own 4 MB L2: the z-tiles are cut into 16
 // bands and XCD k takes the bands k and 15 - k -- an XCD then reads one eighth of the samples (a pixel at depth z reads around
@@ -148,7 +146,8 @@ __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, ui
 //   q_a = sum_{e in U(a)} rot_e s_{a,e},  out = sum_a rot_a q_a  (/ n_angles)
 // Wave w = e % DAS_SPLIT keeps its share of q_a (re in q[j], im in b[j]: the two register rows per angle F-DMAS has), the shares meet
 // in LDS in wave order, wave 0 applies rot_a and adds in angle order.  A pixel that uses no element is exactly (0, 0).
-#define BF_IQ 3u
+#define BF_IQ PBRT_SCAN_IQ
+static_assert(BF_IQ == PBRT_SCAN_IQ && BF_IQ != BF_DAS && BF_IQ != PBRT_BF_PDAS && BF_IQ != PBRT_BF_FDMAS, "one method numbering (bf_request.h)");
 template <uint32_t METHOD>
 struct DasSample {
     typedef float type;

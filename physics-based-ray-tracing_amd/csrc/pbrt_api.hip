@@ -14,6 +14,7 @@
 
 #include "bvh_build.h"
 #include "prim_runs.h"
+#include "bf_request.h"
 #include "kernels_us.h"
 #include "kernels_wavefront.h"
 #include "kernels_us_wavefront.h"
@@ -2517,44 +2518,39 @@ struct ImgTimer {
     }
 };
 
-static int das_check(pbrt_ctx *ctx, const pbrt_das_params *p) {
-    NEED(ctx, p->n_angles > 0 && p->n_elements > 0 && p->time_samples > 1 && p->fs > 0.0f && p->sound_speed > 0.0f);
-    NEED(ctx, p->interpolation <= PBRT_DAS_LINEAR && p->f_number >= 0.0f);
-    NEED(ctx, p->nx > 0 && p->nz > 0 && (uint64_t)p->nx * p->nz < 0xffffffffull);
-    NEED(ctx, (uint64_t)div_up(p->nx, DAS_TILE) * (div_up(p->nz, DAS_TILE) + DAS_BANDS) * DAS_XCDS < 0x7fffffffull);
-    return PBRT_OK;
-}
-// de: element positions [n_elements], or (probe) the element table [n_elements][4] of pbrt_us_array_elements
-static int das_enqueue(pbrt_ctx *c, const pbrt_das_params *p, const float *dd, const float *dt, const float *de, const float *dx,
-                       const float *dz, float *dout, const double *ttx = nullptr, bool probe = false, uint32_t method = 0u, float pw = 0.0f,
-                       bool tab = false) {
+// ---- one beamform request (bf_request.h: the request, and the rules of the four parameter blocks) from the entry points to the launch ----
+// de: element positions [n_elements], or (rq.probe) the element table [n_elements][4]; dx, dz: the axes, or (rq.tab) the pixel tables;
+// dt, ttx: the transmit delays, and the first-arrival table of this scan or null
+static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const float *dt, const float *de, const float *dx, const float *dz,
+                       float *dout, const double *ttx) {
+    const pbrt_das_params *p = rq.das;
     ImgTimer tm(c, IMG_DAS);
     DasGrid g;
-    g.tab = tab ? 1u : 0u;  // dx, dz are the pixel tables [nx][nz] of a pbrt_scan_* call
-    g.ntx = div_up(p->nx, DAS_TILE);
-    g.ntz = div_up(p->nz, DAS_TILE);
+    g.tab = rq.tab ? 1u : 0u;
+    g.ntx = das_tiles(p->nx);
+    g.ntz = das_tiles(p->nz);
     // z-tiles of the largest XCD share (bands k and 15 - k, kernels_beamform.h das_tile_of); the grid gives every XCD that many slots
     g.m = 0;
     auto lo = [&](uint32_t band) { return das_band_lo(band, g.ntz); };
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    if (method == BF_IQ) {  // I/Q delay-and-sum (pbrt_iq_*): dd and dout hold (re, im) pairs, pw is the demodulation frequency
+    if (rq.method == PBRT_SCAN_IQ) {  // I/Q delay-and-sum: dd and dout hold (re, im) pairs, pw is the demodulation frequency
         const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_iq_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe);
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
         hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
-                           reinterpret_cast<float2 *>(dout), pw);
-    } else if (method) {  // p-DAS / F-DMAS (pbrt_bf_*): the same tiles, the method's arithmetic compiled in, p a launch argument
+                           reinterpret_cast<float2 *>(dout), rq.pw);
+    } else if (rq.method != PBRT_SCAN_DAS) {  // p-DAS / F-DMAS: the same tiles, the method's arithmetic compiled in, p a launch argument
         const auto kernel = with_flags([](auto L, auto T, auto X, auto F) {
             return &k_nl_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), F() ? PBRT_BF_FDMAS : PBRT_BF_PDAS>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe, method == PBRT_BF_FDMAS);
-        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout, pw);
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe, rq.method == PBRT_BF_FDMAS);
+        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout, rq.pw);
     } else {
         const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_das_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, probe);
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
         hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
     }
-    c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * (method == BF_IQ ? 8 : 4);
+    c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * (rq.method == PBRT_SCAN_IQ ? 8 : 4);
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
 }
@@ -2618,63 +2614,72 @@ static int pulse_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, uint32_t K,
     return PBRT_OK;
 }
 
-// the four DAS entry points and their *_probe twins (element table instead of positions): one body each
+// The three bodies behind the 17 beamform and first-arrival entry points.  Each entry point makes its request first (BF_REQUEST below):
+// a null context is PBRT_E_INVALID and touches nothing, a refused block is PBRT_E_INVALID with the text of the rule.
 // (d_tx_delays or d_table: the plain form passes its delays, the table form its first-arrival table, and the other one null)
-static int das_beamform_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_table,
-                                 const void *d_elem_x, const void *d_x, const void *d_z, void *d_out, bool probe, uint32_t method = 0u,
-                                 float pw = 0.0f, bool tab = false) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && d_data && (d_tx_delays || d_table) && d_elem_x && d_x && d_z && d_out);
-    int rc = das_check(ctx, p);
-    if (rc) return rc;
+static int beamform_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_data, const void *d_elem, const void *d_x, const void *d_z,
+                        void *d_out, const void *d_tx_delays, const void *d_table) {
+    NEED(ctx, d_data && (d_tx_delays || d_table) && d_elem && d_x && d_z && d_out);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return das_enqueue(ctx, p, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x,
-                       (const float *)d_z, (float *)d_out, (const double *)d_table, probe, method, pw, tab);
+    return das_enqueue(ctx, rq, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem, (const float *)d_x,
+                       (const float *)d_z, (float *)d_out, (const double *)d_table);
 }
 
-static int das_first_arrival_dev_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
-                                      const void *d_z, void *d_table, bool probe, bool tab = false) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && d_tx_delays && d_elem_x && d_x && d_z && d_table);
-    int rc = das_check(ctx, p);
-    if (rc) return rc;
+static int first_arrival_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_tx_delays, const void *d_elem, const void *d_x, const void *d_z,
+                             void *d_table) {
+    NEED(ctx, d_tx_delays && d_elem && d_x && d_z && d_table);
+    const pbrt_das_params *p = rq.das;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(probe ? k_das_first_arrival<true> : k_das_first_arrival<false>, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256), 0,
-                       ctx->stream, *p, tab ? 1u : 0u, (const float *)d_tx_delays, (const float *)d_elem_x, (const float *)d_x, (const float *)d_z,
-                       (double *)d_table);
+    hipLaunchKernelGGL(rq.probe ? k_das_first_arrival<true> : k_das_first_arrival<false>, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256),
+                       0, ctx->stream, *p, rq.tab ? 1u : 0u, (const float *)d_tx_delays, (const float *)d_elem, (const float *)d_x,
+                       (const float *)d_z, (double *)d_table);
     HIPCHK(ctx, hipGetLastError());
     return PBRT_OK;
 }
 
-static int das_beamform_impl(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays, const float *elem_x,
-                             const float *x, const float *z, float *out, bool probe, uint32_t method = 0u, float pw = 0.0f,
-                             bool tab = false) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && data && tx_delays && elem_x && x && z && out);
-    int rc = das_check(ctx, p);
-    if (rc) return rc;
-    const size_t width = method == BF_IQ ? 2u : 1u;  // floats per sample and per pixel
+static int beamform_host(pbrt_ctx *ctx, const BfRequest &rq, const float *data, const float *tx_delays, const float *elem, const float *x,
+                         const float *z, float *out) {
+    NEED(ctx, data && tx_delays && elem && x && z && out);
+    const pbrt_das_params *p = rq.das;
+    const size_t width = rq.method == PBRT_SCAN_IQ ? 2u : 1u;  // floats per sample and per pixel
     const size_t nd = (size_t)p->n_angles * p->n_elements * p->time_samples * width, ne = (size_t)p->n_angles * p->n_elements;
     const uint32_t n = p->nx * p->nz;
-    const size_t nel = (size_t)p->n_elements * (probe ? 4u : 1u);
-    const size_t ngx = tab ? (size_t)n : p->nx, ngz = tab ? (size_t)n : p->nz;  // axes, or the two pixel tables
+    const size_t nel = (size_t)p->n_elements * (rq.probe ? 4u : 1u);
+    const size_t ngx = rq.tab ? (size_t)n : p->nx, ngz = rq.tab ? (size_t)n : p->nz;  // axes, or the two pixel tables
     STAGED_BEGIN(ctx, (nd + ne + nel + ngx + ngz + (size_t)n * width) * 4 + 256);
-    float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem_x, nel);
+    float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem, nel);
     float *dx = S.in(x, ngx), *dz = S.in(z, ngz);
     float *dout = S.out<float>(n * width);
-    if ((rc = das_enqueue(c, p, dd, dt, de, dx, dz, dout, nullptr, probe, method, pw, tab)) != 0) return rc;
+    if (int rc = das_enqueue(c, rq, dd, dt, de, dx, dz, dout, nullptr)) return rc;
     S.back(out, dout, n * width);
     return S.finish();
 }
+// entering a beamform entry point: declares rq, the request of its parameter block (bf_request.h)
+#define BF_REQUEST(...)                      \
+    BfRequest rq;                            \
+    if (!ctx) return PBRT_E_INVALID;         \
+    if (const char *why = bf_request(&rq, __VA_ARGS__)) return ctx->fail(PBRT_E_INVALID, "invalid argument: %s", why)
 
-// p-DAS / F-DMAS: what pbrt_bf_params adds to das_check; the entry points then take the DAS path with a method
-static int bf_check(pbrt_ctx *ctx, const pbrt_bf_params *p) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && (p->method == PBRT_BF_PDAS || p->method == PBRT_BF_FDMAS) && p->probe <= 1u);
-    NEED(ctx, p->method != PBRT_BF_PDAS || (std::isfinite(p->p) && p->p >= 1.0f && p->p <= 8.0f));
+// ---- the argument rules of the steps around the beamformer: one *_check each, called by the host form and by the _dev form ----
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+// (no overlap rule here: pbrt_envelope stages rf and env separately and so takes rf == env; pbrt_envelope_dev refuses overlap itself)
+static int env_check(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *rf, const void *env) {
+    NEED(ctx, rf && env && nz <= ENV_MAX_N && (uint64_t)nx * nz < 0xffffffffull);
     return PBRT_OK;
 }
-static int fir_check(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K) {
+static int log_check(pbrt_ctx *ctx, const void *env, float dynamic_range_db, const void *out) {
+    NEED(ctx, env && out && dynamic_range_db > 0.0f);
+    return PBRT_OK;
+}
+static int iq_env_check(pbrt_ctx *ctx, uint32_t n, const void *iq, const void *env) {
+    NEED(ctx, iq && env && !ranges_overlap(iq, (size_t)n * 8, env, (size_t)n * 4));
+    return PBRT_OK;
+}
+static int fir_check(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *taps, const void *in, const void *out) {
+    NEED(ctx, taps && in && out && !ranges_overlap(in, (size_t)nx * nz * 4, out, (size_t)nx * nz * 4));
     NEED(ctx, K <= FIR_MAX_K && nz > 0);
     NEED(ctx, (uint64_t)nx * nz < 0xffffffffull && (uint64_t)nx * div_up(nz, 256) < 0x7fffffffull);
     return PBRT_OK;
@@ -2687,28 +2692,6 @@ static int fir_enqueue(pbrt_ctx *c, uint32_t nx, uint32_t nz, uint32_t K, const 
     return PBRT_OK;
 }
 
-// I/Q (DESIGN D20): what pbrt_iq_params adds to das_check; the entry points then take the DAS path with the method BF_IQ
-static int iq_check(pbrt_ctx *ctx, const pbrt_iq_params *p) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && p->probe <= 1u);
-    NEED(ctx, std::isfinite(p->demod_freq) && p->demod_freq >= 0.0f);
-    return PBRT_OK;
-}
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-// pixel-table scans (DESIGN D21): what pbrt_scan_params adds to das_check -- bf_check's and iq_check's rules for the method it names;
-// the entry points then take the DAS path with that method and the table flag.  -> the launch argument pw (p, or the demodulation frequency)
-static int scan_check(pbrt_ctx *ctx, const pbrt_scan_params *p, float *pw) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && p->probe <= 1u);
-    NEED(ctx, p->method == PBRT_SCAN_DAS || p->method == PBRT_BF_PDAS || p->method == PBRT_BF_FDMAS || p->method == PBRT_SCAN_IQ);
-    NEED(ctx, p->method != PBRT_BF_PDAS || (std::isfinite(p->p) && p->p >= 1.0f && p->p <= 8.0f));
-    NEED(ctx, p->method != PBRT_SCAN_IQ || (std::isfinite(p->demod_freq) && p->demod_freq >= 0.0f));
-    *pw = p->method == PBRT_SCAN_IQ ? p->demod_freq : p->method == PBRT_SCAN_DAS ? 0.0f : p->p;
-    return PBRT_OK;
-}
 static int scan_convert_check(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *src, const void *dst) {
     NEED(ctx, p->n_theta >= 2u && p->n_rho >= 2u && p->nx > 0 && p->nz > 0);
     NEED(ctx, (uint64_t)p->n_theta * p->n_rho < 0xffffffffull && (uint64_t)p->nx * p->nz < 0xffffffffull);
@@ -2752,27 +2735,23 @@ extern "C" {
 
 int pbrt_scan_beamform(pbrt_ctx *ctx, const pbrt_scan_params *p, const float *data, const float *tx_delays, const float *elem,
                        const float *px, const float *pz, float *out) {
-    float pw;
-    int rc = scan_check(ctx, p, &pw);
-    return rc ? rc : das_beamform_impl(ctx, &p->das, data, tx_delays, elem, px, pz, out, p->probe != 0u, p->method, pw, true);
+    BF_REQUEST(p);
+    return beamform_host(ctx, rq, data, tx_delays, elem, px, pz, out);
 }
 int pbrt_scan_beamform_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
                            const void *d_px, const void *d_pz, void *d_out) {
-    float pw;
-    int rc = scan_check(ctx, p, &pw);
-    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, d_tx_delays, nullptr, d_elem, d_px, d_pz, d_out, p->probe != 0u, p->method, pw, true);
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_px, d_pz, d_out, d_tx_delays, nullptr);
 }
 int pbrt_scan_beamform_table_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_data, const void *d_table, const void *d_elem,
                                  const void *d_px, const void *d_pz, void *d_out) {
-    float pw;
-    int rc = scan_check(ctx, p, &pw);
-    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, nullptr, d_table, d_elem, d_px, d_pz, d_out, p->probe != 0u, p->method, pw, true);
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_px, d_pz, d_out, nullptr, d_table);
 }
 int pbrt_scan_first_arrival_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_tx_delays, const void *d_elem, const void *d_px,
                                 const void *d_pz, void *d_table) {
-    float pw;
-    int rc = scan_check(ctx, p, &pw);
-    return rc ? rc : das_first_arrival_dev_impl(ctx, &p->das, d_tx_delays, d_elem, d_px, d_pz, d_table, p->probe != 0u, true);
+    BF_REQUEST(p);
+    return first_arrival_dev(ctx, rq, d_tx_delays, d_elem, d_px, d_pz, d_table);
 }
 int pbrt_scan_convert_dev(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *d_src, const void *d_x, const void *d_z,
                           void *d_dst) {
@@ -2799,18 +2778,18 @@ int pbrt_scan_convert(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const fl
 
 int pbrt_iq_beamform_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem,
                          const void *d_x, const void *d_z, void *d_out) {
-    int rc = iq_check(ctx, p);
-    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_iq, d_tx_delays, nullptr, d_elem, d_x, d_z, d_out, p->probe != 0u, BF_IQ, p->demod_freq);
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_iq, d_elem, d_x, d_z, d_out, d_tx_delays, nullptr);
 }
 int pbrt_iq_beamform_table_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_table, const void *d_elem,
                                const void *d_x, const void *d_z, void *d_out) {
-    int rc = iq_check(ctx, p);
-    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_iq, nullptr, d_table, d_elem, d_x, d_z, d_out, p->probe != 0u, BF_IQ, p->demod_freq);
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_iq, d_elem, d_x, d_z, d_out, nullptr, d_table);
 }
 int pbrt_iq_beamform(pbrt_ctx *ctx, const pbrt_iq_params *p, const float *iq, const float *tx_delays, const float *elem,
                      const float *x, const float *z, float *out) {
-    int rc = iq_check(ctx, p);
-    return rc ? rc : das_beamform_impl(ctx, &p->das, iq, tx_delays, elem, x, z, out, p->probe != 0u, BF_IQ, p->demod_freq);
+    BF_REQUEST(p);
+    return beamform_host(ctx, rq, iq, tx_delays, elem, x, z, out);
 }
 int pbrt_rf2iq_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float t0, float demod_freq,
                    uint32_t decimation, uint32_t K, const void *d_taps, const void *d_in, void *d_out) {
@@ -2839,95 +2818,98 @@ int pbrt_rf2iq(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs
 }
 int pbrt_iq_envelope_dev(pbrt_ctx *ctx, uint32_t n, const void *d_iq, void *d_env) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_iq && d_env && !ranges_overlap(d_iq, (size_t)n * 8, d_env, (size_t)n * 4));
+    if (int rc = iq_env_check(ctx, n, d_iq, d_env)) return rc;
     if (n == 0) return PBRT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return iq_env_enqueue(ctx, n, (const float *)d_iq, (float *)d_env);
 }
 int pbrt_iq_envelope(pbrt_ctx *ctx, uint32_t n, const float *iq, float *env) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, iq && env && !ranges_overlap(iq, (size_t)n * 8, env, (size_t)n * 4));
+    if (int rc = iq_env_check(ctx, n, iq, env)) return rc;
     STAGED_BEGIN(ctx, (size_t)n * 12 + 64);
     float *din = S.in(iq, 2 * (size_t)n), *dout = S.out<float>(n);
-    int rc = iq_env_enqueue(c, n, din, dout);
-    if (rc) return rc;
+    if (int rc = iq_env_enqueue(c, n, din, dout)) return rc;
     S.back(env, dout, n);
     return S.finish();
 }
 
 int pbrt_bf_beamform_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
                          const void *d_x, const void *d_z, void *d_out) {
-    int rc = bf_check(ctx, p);
-    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, d_tx_delays, nullptr, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_x, d_z, d_out, d_tx_delays, nullptr);
 }
 int pbrt_bf_beamform_table_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_table, const void *d_elem,
                                const void *d_x, const void *d_z, void *d_out) {
-    int rc = bf_check(ctx, p);
-    return rc ? rc : das_beamform_dev_impl(ctx, &p->das, d_data, nullptr, d_table, d_elem, d_x, d_z, d_out, p->probe != 0u, p->method, p->p);
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_x, d_z, d_out, nullptr, d_table);
 }
 int pbrt_bf_beamform(pbrt_ctx *ctx, const pbrt_bf_params *p, const float *data, const float *tx_delays, const float *elem,
                      const float *x, const float *z, float *out) {
-    int rc = bf_check(ctx, p);
-    return rc ? rc : das_beamform_impl(ctx, &p->das, data, tx_delays, elem, x, z, out, p->probe != 0u, p->method, p->p);
+    BF_REQUEST(p);
+    return beamform_host(ctx, rq, data, tx_delays, elem, x, z, out);
 }
 int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *d_taps, const void *d_in, void *d_out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_taps && d_in && d_out && !ranges_overlap(d_in, (size_t)nx * nz * 4, d_out, (size_t)nx * nz * 4));
-    int rc = fir_check(ctx, nx, nz, K);
-    if (rc) return rc;
+    if (int rc = fir_check(ctx, nx, nz, K, d_taps, d_in, d_out)) return rc;
     if (nx == 0) return PBRT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return fir_enqueue(ctx, nx, nz, K, (const float *)d_taps, (const float *)d_in, (float *)d_out);
 }
 int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const float *taps, const float *in, float *out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, taps && in && out && !ranges_overlap(in, (size_t)nx * nz * 4, out, (size_t)nx * nz * 4));
-    int rc = fir_check(ctx, nx, nz, K);
-    if (rc) return rc;
+    if (int rc = fir_check(ctx, nx, nz, K, taps, in, out)) return rc;
     const uint32_t n = nx * nz;
     STAGED_BEGIN(ctx, (size_t)n * 8 + (size_t)(2 * K + 1) * 4 + 128);
     float *dh = S.in(taps, 2 * (size_t)K + 1), *din = S.in(in, n), *dout = S.out<float>(n);
-    if ((rc = fir_enqueue(c, nx, nz, K, dh, din, dout)) != 0) return rc;
+    if (int rc = fir_enqueue(c, nx, nz, K, dh, din, dout)) return rc;
     S.back(out, dout, n);
     return S.finish();
 }
 
 int pbrt_das_beamform_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
                           const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, nullptr, d_elem_x, d_x, d_z, d_out, false);
+    BF_REQUEST(p, false);
+    return beamform_dev(ctx, rq, d_data, d_elem_x, d_x, d_z, d_out, d_tx_delays, nullptr);
 }
 int pbrt_das_beamform_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
                                 const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_dev_impl(ctx, p, d_data, d_tx_delays, nullptr, d_elem, d_x, d_z, d_out, true);
+    BF_REQUEST(p, true);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_x, d_z, d_out, d_tx_delays, nullptr);
 }
 int pbrt_das_first_arrival_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem_x, const void *d_x,
                                const void *d_z, void *d_table) {
-    return das_first_arrival_dev_impl(ctx, p, d_tx_delays, d_elem_x, d_x, d_z, d_table, false);
+    BF_REQUEST(p, false);
+    return first_arrival_dev(ctx, rq, d_tx_delays, d_elem_x, d_x, d_z, d_table);
 }
 int pbrt_das_first_arrival_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_tx_delays, const void *d_elem, const void *d_x,
                                      const void *d_z, void *d_table) {
-    return das_first_arrival_dev_impl(ctx, p, d_tx_delays, d_elem, d_x, d_z, d_table, true);
+    BF_REQUEST(p, true);
+    return first_arrival_dev(ctx, rq, d_tx_delays, d_elem, d_x, d_z, d_table);
 }
 int pbrt_das_beamform_table_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem_x,
                                 const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_dev_impl(ctx, p, d_data, nullptr, d_table, d_elem_x, d_x, d_z, d_out, false);
+    BF_REQUEST(p, false);
+    return beamform_dev(ctx, rq, d_data, d_elem_x, d_x, d_z, d_out, nullptr, d_table);
 }
 int pbrt_das_beamform_table_probe_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_table, const void *d_elem,
                                       const void *d_x, const void *d_z, void *d_out) {
-    return das_beamform_dev_impl(ctx, p, d_data, nullptr, d_table, d_elem, d_x, d_z, d_out, true);
+    BF_REQUEST(p, true);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_x, d_z, d_out, nullptr, d_table);
 }
 int pbrt_das_beamform(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
                       const float *elem_x, const float *x, const float *z, float *out) {
-    return das_beamform_impl(ctx, p, data, tx_delays, elem_x, x, z, out, false);
+    BF_REQUEST(p, false);
+    return beamform_host(ctx, rq, data, tx_delays, elem_x, x, z, out);
 }
 int pbrt_das_beamform_probe(pbrt_ctx *ctx, const pbrt_das_params *p, const float *data, const float *tx_delays,
                             const float *elem, const float *x, const float *z, float *out) {
-    return das_beamform_impl(ctx, p, data, tx_delays, elem, x, z, out, true);
+    BF_REQUEST(p, true);
+    return beamform_host(ctx, rq, data, tx_delays, elem, x, z, out);
 }
 
 int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf, void *d_env) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_rf && d_env && nz <= ENV_MAX_N && (uint64_t)nx * nz < 0xffffffffull);
+    if (int rc = env_check(ctx, nx, nz, d_rf, d_env)) return rc;
     NEED(ctx, !ranges_overlap(d_rf, (size_t)nx * nz * 4, d_env, (size_t)nx * nz * 4));
     if (nx == 0 || nz == 0) return PBRT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2936,20 +2918,18 @@ int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf,
 
 int pbrt_envelope(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const float *rf, float *env) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, rf && env && nz <= ENV_MAX_N);
+    if (int rc = env_check(ctx, nx, nz, rf, env)) return rc;
     const uint32_t n = nx * nz;
-    NEED(ctx, (uint64_t)nx * nz < 0xffffffffull);
     STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
     float *din = S.in(rf, n), *dout = S.out<float>(n);
-    int rc = env_enqueue(c, nx, nz, din, dout);
-    if (rc) return rc;
+    if (int rc = env_enqueue(c, nx, nz, din, dout)) return rc;
     S.back(env, dout, n);
     return S.finish();
 }
 
 int pbrt_log_compress_dev(pbrt_ctx *ctx, uint32_t n, const void *d_env, float dynamic_range_db, void *d_out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_env && d_out && dynamic_range_db > 0.0f);
+    if (int rc = log_check(ctx, d_env, dynamic_range_db, d_out)) return rc;
     if (n == 0) return PBRT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return log_enqueue(ctx, n, (const float *)d_env, dynamic_range_db, (float *)d_out);
@@ -2957,11 +2937,10 @@ int pbrt_log_compress_dev(pbrt_ctx *ctx, uint32_t n, const void *d_env, float dy
 
 int pbrt_log_compress(pbrt_ctx *ctx, uint32_t n, const float *env, float dynamic_range_db, float *out) {
     if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, env && out && dynamic_range_db > 0.0f);
+    if (int rc = log_check(ctx, env, dynamic_range_db, out)) return rc;
     STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
     float *din = S.in(env, n), *dout = S.out<float>(n);
-    int rc = log_enqueue(c, n, din, dynamic_range_db, dout);
-    if (rc) return rc;
+    if (int rc = log_enqueue(c, n, din, dynamic_range_db, dout)) return rc;
     S.back(out, dout, n);
     return S.finish();
 }

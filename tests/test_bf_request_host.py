@@ -1,0 +1,47 @@
+"""Host-side check of the beamform request (csrc/bf_request.h): the four makers that turn a pbrt_das_params (with a probe flag), a
+pbrt_bf_params, a pbrt_iq_params or a pbrt_scan_params into the request every beamform entry point hands to the launch, and the
+argument rules they keep, each written once.  No GPU: the header is plain C++, and tests/native/bf_request_check.cpp holds the rule
+table -- every valid block gives the expected (method, pw, probe, tab), every single violation is refused (counts, rates,
+interpolation, f-number, nx = 0, nx * nz >= 2^32 - 1, the launch-grid limit, the methods each block admits, probe = 2, p outside
+[1, 8] for p-DAS only, demod_freq not finite or negative for I/Q only, -0.0 taken).  The program is built with the address and
+undefined-behaviour sanitizers and run on its own."""
+import json
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+SRC = os.path.join(ROOT, "tests", "native", "bf_request_check.cpp")
+CSRC = os.path.join(ROOT, "physics-based-ray-tracing_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def report(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("bf_request") / "bf_request_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", CSRC, "-o", exe, SRC])
+    return subprocess.run([exe], capture_output=True, text=True, timeout=120)
+
+
+def test_the_makers_keep_the_rule_table(report):
+    assert report.returncode == 0, report.stderr
+    assert "ERROR: AddressSanitizer" not in report.stderr and "runtime error" not in report.stderr, report.stderr
+    rep = json.loads(report.stdout.strip().splitlines()[-1])
+    assert rep["failures"] == 0 and rep["checks"] >= 200
+
+
+def test_the_header_includes_nothing_of_hip():
+    text = open(os.path.join(CSRC, "bf_request.h")).read()
+    assert "#include <hip" not in text and "hip_runtime" not in text
+    includes = [line.split()[1] for line in text.splitlines() if line.startswith("#include")]
+    assert includes == ["<cmath>", "<cstdint>", '"../../include/pbrt_hip.h"']
+
+
+def test_the_kernels_and_the_host_share_the_header():
+    """the tile constants and the method numbering have one definition: kernels_beamform.h takes them from bf_request.h"""
+    text = open(os.path.join(CSRC, "kernels_beamform.h")).read()
+    assert '#include "bf_request.h"' in text
+    assert "#define DAS_TILE" not in text and "#define DAS_XCDS" not in text and "#define DAS_BANDS" not in text
+    assert "static_assert(BF_IQ == PBRT_SCAN_IQ" in text or "#define BF_IQ PBRT_SCAN_IQ" in text
