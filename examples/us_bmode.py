@@ -2,7 +2,8 @@
 """The reference's ultrasound driver flow on this library: scene dict -> acquisition -> delay-and-sum -> envelope ->
 log compression -> finite-difference roughness loop (what USMain.py does at :26-90, :93-224, :257-289), without the
 plotting.  Writes the B-mode image and the channel buffer as .npy.
-    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [--iq [--decimation D]] [--polar] [out_dir]
+    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [--iq [--decimation D]] [--polar]
+                                  [--apodization {boxcar,tukey,hann,hamming} [--alpha A]] [out_dir]
 --convex: the same flow under a curved (abdominal) array -- 64 elements on a 40 mm arc of 40 degrees (DESIGN D18); the sensor
 transform puts the apex where the linear array sits, and the scan is given in the sensor's frame, whose origin is the centre of
 curvature.
@@ -14,7 +15,9 @@ frequency AT the carrier, so the example picks lambda / 8 for p-DAS and lambda /
 example then scans at lambda / 2 axially.  Delay-and-sum only.
 --polar: the beamformer runs on a sector (PolarScan, DESIGN D21) -- rays over the opening angle of the curved array, or over the x-range
 seen from the deepest z under the linear one -- the envelope is taken along the rays, and the scan conversion brings it onto the Cartesian
-grid of the other runs.  Combines with every option above; --profile prints the device time of each step (HIP events)."""
+grid of the other runs.  Combines with every option above.
+--apodization: the receive window on the f-number aperture of every pixel (DESIGN D22) -- boxcar (default), tukey (--alpha, default 0.5),
+hann or hamming: lower side lobes around the specular plate for a wider main lobe.  Combines with every option above.  --profile prints the device time of each step (HIP events)."""
 import argparse
 import os
 import sys
@@ -34,6 +37,8 @@ ap.add_argument("--p", type=float, default=2.0)
 ap.add_argument("--iq", action="store_true")
 ap.add_argument("--decimation", type=int, default=4)
 ap.add_argument("--polar", action="store_true")
+ap.add_argument("--apodization", choices=("boxcar", "tukey", "hann", "hamming"), default="boxcar")
+ap.add_argument("--alpha", type=float, default=0.5)
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("out_dir", nargs="?", default=".")
 args = ap.parse_args()
@@ -63,8 +68,9 @@ scene = mi.load_dict({
 
 integ = scene.integrator()
 lam = integ.sound_speed / integ.frequency
-beamformer = {"das": lambda: mi.DelayAndSum(), "pdas": lambda: mi.PDelayAndSum(p=args.p),
-              "fdmas": lambda: mi.FilteredDelayMultiplyAndSum()}[args.beamformer]()
+window = dict(rx_apodization=args.apodization, rx_apodization_alpha=args.alpha)
+beamformer = {"das": lambda: mi.DelayAndSum(**window), "pdas": lambda: mi.PDelayAndSum(p=args.p, **window),
+              "fdmas": lambda: mi.FilteredDelayMultiplyAndSum(**window)}[args.beamformer]()
 step = {"das": lam / 4, "pdas": lam / 8, "fdmas": lam / 16}[args.beamformer]
 RENDER = dict(x_range=(-0.02, 0.02), z_range=Z_RANGE, step=step, beamformer=beamformer)
 if args.iq:

@@ -722,6 +722,50 @@ int pbrt_scan_convert(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const fl
 int pbrt_scan_convert_dev(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *d_src, const void *d_x, const void *d_z,
                           void *d_dst);
 
+/* ---- receive apodisation: a window on the f-number aperture of every beamformer -----------------------------------
+ * replaces: ultraspy's DelayAndSum setups `rx_apodization` ('boxcar' / 'tukey') and `rx_apodization_alpha` (absent here as above, so
+ * this is the build's own definition).  Every call above weighs the elements inside a pixel's f-number aperture with 1.  Here the
+ * delayed sample s_{a,e} of a pixel whose element e lies inside the aperture is replaced by w_e * s_{a,e} (one f32 product; both
+ * components of an I/Q sample, before rot_e) before anything else happens to it: delay-and-sum adds it, p-DAS and F-DMAS take the signed
+ * root of the weighted sample (and F-DMAS' sum |s_e| is of weighted samples), I/Q turns it.  Nothing else differs from the call the
+ * method names; the weight depends on the pixel and the element only, not on the transmission.
+ *   u, the element's distance from the aperture's centre over the aperture's half width, in f64 from the doubles of the aperture test:
+ *        line of elements:  u = |x - x_e| * (1 / (z / (2 f#)))     (one reciprocal per pixel)
+ *        element table:     u = 2 f# |d_t| * (1 / d_n)             (one reciprocal per element)
+ *   t = min(max((u - (1 - alpha)) * (1 / alpha), 0), 1) in f64 (alpha widened from its float; a NaN u -- z = 0 -- gives 0), rounded once to f32
+ *   w = fmaf(1 - a0, cospif(t), a0) in f32, 1 - a0 one f32 subtraction
+ *        PBRT_APOD_BOXCAR   w = 1: the kernels of the calls above, which hold no weight code -- the same image bit for bit
+ *        PBRT_APOD_TUKEY    a0 = 1/2, alpha the caller's: 1 for u <= 1 - alpha, a raised cosine down to 0 at u = 1
+ *        PBRT_APOD_HANN     a0 = 1/2, alpha = 1: Tukey(1), bit for bit
+ *        PBRT_APOD_HAMMING  a0 = 0.54f, alpha = 1
+ *   Error of a weight against its value in exact arithmetic: at most 4 * 2^-24 -- 2^-25 pi / 2 from rounding t (|dw/dt| <= pi / 2), 4 ulp
+ *   of cospif on a value <= 1 times 1 - a0 <= 1/2, half an ulp of the fmaf (u and t in f64 add 1e-15 / alpha).
+ * A weight of exactly 0 (Hann at u = 1) still multiplies: a non-finite sample there gives NaN.  A pixel that uses no element stays exactly
+ * 0, the tiles no element sees are left as before, and the first-arrival table does not depend on the window: pbrt_das_first_arrival_dev
+ * (tables = 0; _probe for scan.probe = 1) or pbrt_scan_first_arrival_dev (tables = 1) make it.
+ * One block carries the whole request: scan keeps every rule of pbrt_scan_params (every method, probe), `tables` says whether the pixel
+ * arguments are the axes x[nx], z[nz] or two pixel tables.  Refused with PBRT_E_INVALID besides: tables > 1, an unknown window,
+ * PBRT_APOD_TUKEY with alpha not finite or outside (0, 1] (alpha is read by PBRT_APOD_TUKEY only), and a window other than boxcar with
+ * das.f_number <= 0: there is no aperture to be a window of.  The three calls take the arguments of their pbrt_scan_* twins; the _dev forms
+ * are queued on the context's stream and recordable, the table form is bit-equal to the direct form, and so is tables = 1 on the tables of
+ * a separable scan to tables = 0. */
+#define PBRT_APOD_BOXCAR 0u
+#define PBRT_APOD_TUKEY 1u
+#define PBRT_APOD_HANN 2u
+#define PBRT_APOD_HAMMING 3u
+typedef struct pbrt_apod_params {
+    pbrt_scan_params scan; /* das, method (all four), p, demod_freq, probe: every rule of pbrt_scan_params */
+    uint32_t tables;       /* 0: the axes x[nx], z[nz]; 1: two pixel tables [nx][nz] */
+    uint32_t window;       /* PBRT_APOD_* */
+    float alpha;           /* PBRT_APOD_TUKEY: finite, 0 < alpha <= 1 */
+} pbrt_apod_params;
+int pbrt_apod_beamform(pbrt_ctx *ctx, const pbrt_apod_params *p, const float *data, const float *tx_delays, const float *elem,
+                       const float *px, const float *pz, float *out);
+int pbrt_apod_beamform_dev(pbrt_ctx *ctx, const pbrt_apod_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
+                           const void *d_px, const void *d_pz, void *d_out);
+int pbrt_apod_beamform_table_dev(pbrt_ctx *ctx, const pbrt_apod_params *p, const void *d_data, const void *d_table, const void *d_elem,
+                                 const void *d_px, const void *d_pz, void *d_out);
+
 /* waits for everything queued on the context's stream */
 int pbrt_ctx_synchronize(pbrt_ctx *ctx);
 /* Device buffers for a caller without a GPU library of its own (the reference's driver is NumPy: USMain.py:103-121).
@@ -751,6 +795,7 @@ int pbrt_get_image_stats(pbrt_ctx *ctx, pbrt_image_stats *out);
  * pbrt_das_beamform_dev, pbrt_das_beamform_table_dev, pbrt_bf_beamform_dev, pbrt_bf_beamform_table_dev, pbrt_axial_fir_dev,
  * pbrt_rf2iq_dev, pbrt_iq_beamform_dev, pbrt_iq_beamform_table_dev, pbrt_iq_envelope_dev,
  * pbrt_scan_beamform_dev, pbrt_scan_beamform_table_dev, pbrt_scan_first_arrival_dev, pbrt_scan_convert_dev,
+ * pbrt_apod_beamform_dev, pbrt_apod_beamform_table_dev,
  * pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
  * stream instead of run; pbrt_graph_launch replays the recording in one submission and returns without waiting, exactly as if
  * the recorded calls had just been made: same kernels, same arguments, same results bit for bit, the acquisition's statistics

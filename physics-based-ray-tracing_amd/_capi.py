@@ -156,6 +156,15 @@ class ScanParams(C.Structure):
 SCAN_DAS, SCAN_IQ = 0, 3
 
 
+class ApodParams(C.Structure):
+    """pbrt_apod_params: a whole beamform request with a receive window (DESIGN D22)"""
+    _fields_ = [("scan", ScanParams), ("tables", C.c_uint32), ("window", C.c_uint32), ("alpha", C.c_float)]
+
+
+APOD_BOXCAR, APOD_TUKEY, APOD_HANN, APOD_HAMMING = 0, 1, 2, 3
+PBRT_APOD_BOXCAR, PBRT_APOD_TUKEY, PBRT_APOD_HANN, PBRT_APOD_HAMMING = APOD_BOXCAR, APOD_TUKEY, APOD_HANN, APOD_HAMMING
+
+
 class ScanConvertParams(C.Structure):
     _fields_ = [("n_theta", C.c_uint32), ("n_rho", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32), ("theta0", C.c_double),
                 ("dtheta", C.c_double), ("rho0", C.c_double), ("drho", C.c_double), ("ox", C.c_double), ("oz", C.c_double),
@@ -246,6 +255,9 @@ SIGNATURES = {
     "pbrt_scan_beamform_dev": (C.c_int, [_P, C.POINTER(ScanParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_scan_beamform_table_dev": (C.c_int, [_P, C.POINTER(ScanParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_scan_first_arrival_dev": (C.c_int, [_P, C.POINTER(ScanParams), _P, _P, _P, _P, _P]),
+    "pbrt_apod_beamform": (C.c_int, [_P, C.POINTER(ApodParams), _F, _F, _F, _F, _F, _F]),
+    "pbrt_apod_beamform_dev": (C.c_int, [_P, C.POINTER(ApodParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_apod_beamform_table_dev": (C.c_int, [_P, C.POINTER(ApodParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_scan_convert": (C.c_int, [_P, C.POINTER(ScanConvertParams), _F, _F, _F, _F]),
     "pbrt_scan_convert_dev": (C.c_int, [_P, C.POINTER(ScanConvertParams), _P, _P, _P, _P]),
     "pbrt_ctx_synchronize": (C.c_int, [_P]),

@@ -87,11 +87,38 @@ def _pixels(cx, gx, gz, tables, dev):
 
 
 _METHODS = {"das": _capi.SCAN_DAS, "pdas": _capi.BF_PDAS, "fdmas": _capi.BF_FDMAS, "iq": _capi.SCAN_IQ}
+_WINDOWS = {"boxcar": _capi.APOD_BOXCAR, "tukey": _capi.APOD_TUKEY, "hann": _capi.APOD_HANN, "hamming": _capi.APOD_HAMMING}
 
 
-def _block(das, tables, method, p, demod_freq, probe):
+def _checked_window(rx_apodization, rx_apodization_alpha, f_number):
+    """(window, alpha) of a request as the library takes them; ValueError for what it would refuse: an unknown window, a Tukey alpha
+    outside (0, 1], and a window other than boxcar without an f-number (there is no aperture to be a window of).  alpha is read by
+    "tukey" only."""
+    if not isinstance(rx_apodization, str) or rx_apodization not in _WINDOWS:
+        raise ValueError(f"rx_apodization must be one of {tuple(_WINDOWS)}, got {rx_apodization!r}")
+    alpha = 1.0
+    if rx_apodization == "tukey":
+        try:
+            alpha = float(rx_apodization_alpha)
+        except (TypeError, ValueError):
+            alpha = float("nan")
+        if not (math.isfinite(alpha) and 0.0 < alpha <= 1.0):
+            raise ValueError(f"rx_apodization_alpha must lie in (0, 1] for a Tukey window, got {rx_apodization_alpha!r}")
+    if rx_apodization != "boxcar" and not (f_number is not None and float(f_number) > 0.0):
+        raise ValueError(f"rx_apodization={rx_apodization!r} is a window on the f-number aperture: it needs f_number > 0, got {f_number!r}")
+    return _WINDOWS[rx_apodization], alpha
+
+
+def _block(das, tables, method, p, demod_freq, probe, window=_capi.APOD_BOXCAR, alpha=1.0):
     """the parameter block of a request and the family of entry points that takes it: pbrt_scan_* for pixel tables (one block for
-    every method); on axes pbrt_das_* (the element table is in the NAME: *_probe), pbrt_bf_* or pbrt_iq_* (a probe flag in the block)"""
+    every method); on axes pbrt_das_* (the element table is in the NAME: *_probe), pbrt_bf_* or pbrt_iq_* (a probe flag in the block);
+    with a receive window other than boxcar pbrt_apod_* (one block for every method, probe and scan kind, DESIGN D22)"""
+    if window != _capi.APOD_BOXCAR:
+        par = _capi.ApodParams()
+        par.scan.das, par.scan.probe, par.scan.method, par.scan.p = das, int(bool(probe)), _METHODS[method], float(p)
+        par.scan.demod_freq = float(demod_freq or 0.0)
+        par.tables, par.window, par.alpha = int(bool(tables)), int(window), float(alpha)
+        return par, "apod"
     if not tables and method == "das":
         return das, "das"
     par, family = ((_capi.ScanParams(), "scan") if tables else (_capi.IqParams(), "iq") if method == "iq" else (_capi.BfParams(), "bf"))
@@ -136,12 +163,15 @@ def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
 
 
 def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method, p=2.0, demod_freq=None, t0, f_number, interpolation,
-              compound, out, table):
+              compound, out, table, rx_apodization="boxcar", rx_apodization_alpha=0.5):
     """One beamform request, from every public call to its entry point: `data` by `method` ("das", "pdas" with p, "fdmas", or "iq"
     with demod_freq: data and result complex64) on the pixels gx, gz -- the axes x, z, or (`tables`) two pixel tables.  Shapes the
     arguments, holds RF against I/Q, uploads the small tables where the data is a DeviceBuffer, validates `out` and `table`, selects
     the parameter block and the entry point (_block; [_table] with a first-arrival table, [_dev] for data in HBM), calls it and keeps
-    what a queued kernel reads alive with its result.  Host arrays in: a host array out, `out` and `table` are not read."""
+    what a queued kernel reads alive with its result.  Host arrays in: a host array out, `out` and `table` are not read.
+    rx_apodization: the receive window on the f-number aperture, "boxcar" (today's entry points), "tukey" (with rx_apodization_alpha),
+    "hann" or "hamming" (pbrt_apod_*, DESIGN D22); validated before a context is made."""
+    window, alpha = _checked_window(rx_apodization, rx_apodization_alpha, f_number)
     dev = _is_dev(data)
     iq = method == "iq"
     dtype = np.dtype(np.complex64 if iq else np.float32)
@@ -157,7 +187,7 @@ def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method,
     tx, ex = _arg(cx, tx_delays, (A, E), dev), _arg(cx, elem, eshape, dev)
     gx, gz, (n0, n1) = _pixels(cx, gx, gz, tables, dev)
     par, family = _block(_das_params(A, E, T, n0, n1, fs, sound_speed, t0, f_number, interpolation, compound), tables, method, p,
-                         demod_freq, probe)
+                         demod_freq, probe, window, alpha)
     d0, d1 = ("n0", "n1") if tables else ("nx", "nz")
     res = out if out is not None else _capi.DeviceBuffer(cx, (n0, n1), dtype) if dev else np.empty((n0, n1), dtype)
     if res.nbytes != n0 * n1 * dtype.itemsize:
@@ -174,7 +204,7 @@ def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method,
 
 
 def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_number=1.0, interpolation="linear",
-                 compound="sum", out=None, table=None):
+                 compound="sum", out=None, table=None, rx_apodization="boxcar", rx_apodization_alpha=0.5):
     """data [n_angles, n_elements, T] f32, tx_delays [n_angles, n_elements] (s), elem_x [n_elements] (m),
     grid x [nx], z [nz] (m)  ->  beamformed RF image [nx, nz].
     Host arrays in: pbrt_das_beamform, a host array out.  `data` a DeviceBuffer (the channel buffer of an acquisition that
@@ -182,33 +212,41 @@ def das_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, t0=0.0, f_numbe
     the context's stream and the result is a DeviceBuffer (`out`, or a new one); nothing waits.  table: the scan's first-arrival
     times from das_first_arrival (pbrt_das_beamform_table_dev).
     elem_x [n_elements, 4] = (x, z, nx, nz): the element table of a curved probe; the same calls with `_probe` in their names
-    (distances to (x_e, z_e), the f-number aperture in the element's frame: include/pbrt_hip.h)."""
+    (distances to (x_e, z_e), the f-number aperture in the element's frame: include/pbrt_hip.h).
+    rx_apodization: "boxcar" (the default: every element inside the f-number aperture weighs 1), "tukey" (rx_apodization_alpha in
+    (0, 1]), "hann" or "hamming" -- a window on the aperture of every pixel (DESIGN D22, pbrt_apod_beamform*); it needs f_number > 0."""
     return _beamform(data, tx_delays, elem_x, x, z, False, fs, sound_speed, method="das", t0=t0, f_number=f_number,
-                     interpolation=interpolation, compound=compound, out=out, table=table)
+                     interpolation=interpolation, compound=compound, out=out, table=table, rx_apodization=rx_apodization,
+                     rx_apodization_alpha=rx_apodization_alpha)
 
 
 def nonlinear_beamform(data, tx_delays, elem_x, x, z, fs, sound_speed, method="fdmas", p=2.0, t0=0.0, f_number=1.0,
-                       interpolation="linear", compound="sum", out=None, table=None):
+                       interpolation="linear", compound="sum", out=None, table=None, rx_apodization="boxcar",
+                       rx_apodization_alpha=0.5):
     """p-DAS (method="pdas", 1 <= p <= 8) or F-DMAS (method="fdmas") of the channel buffer, BEFORE the axial band-pass both need
     (axial_fir; DESIGN D19, include/pbrt_hip.h).  Arguments and the host / DeviceBuffer rule as das_beamform: host arrays in ->
     pbrt_bf_beamform and a host array out; `data` a DeviceBuffer -> pbrt_bf_beamform_dev (or _table_dev with `table` from
-    das_first_arrival), queued, a DeviceBuffer out.  elem_x [n_elements] or the element table [n_elements, 4]."""
+    das_first_arrival), queued, a DeviceBuffer out.  elem_x [n_elements] or the element table [n_elements, 4].
+    rx_apodization, rx_apodization_alpha: the receive window of das_beamform; the roots are taken of the weighted samples."""
     if method not in ("pdas", "fdmas"):
         raise ValueError(f"method must be 'pdas' or 'fdmas', got {method!r}")
     return _beamform(data, tx_delays, elem_x, x, z, False, fs, sound_speed, method=method, p=p, t0=t0, f_number=f_number,
-                     interpolation=interpolation, compound=compound, out=out, table=table)
+                     interpolation=interpolation, compound=compound, out=out, table=table, rx_apodization=rx_apodization,
+                     rx_apodization_alpha=rx_apodization_alpha)
 
 
 def iq_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, t0=0.0, f_number=1.0, interpolation="linear",
-                compound="sum", out=None, table=None):
+                compound="sum", out=None, table=None, rx_apodization="boxcar", rx_apodization_alpha=0.5):
     """Delay-and-sum of I/Q channel data (DESIGN D20, include/pbrt_hip.h): iq [n_angles, n_elements, T] complex64 at the rate fs_iq,
     demodulated at demod_freq (rf2iq), sample m at t0 + m / fs_iq  ->  complex64 image [nx, nz].  The delayed samples are
     das_beamform's (same delays, aperture and interpolation, on complex samples), each turned back by the carrier phase of its delay.
     Arguments and the host / DeviceBuffer rule as das_beamform: host arrays in -> pbrt_iq_beamform and a host array out; `iq` a complex
     DeviceBuffer -> pbrt_iq_beamform_dev (or _table_dev with `table` from das_first_arrival), queued, a complex DeviceBuffer out.
-    elem [n_elements] or the element table [n_elements, 4]."""
+    elem [n_elements] or the element table [n_elements, 4].
+    rx_apodization, rx_apodization_alpha: the receive window of das_beamform, on both components of a sample."""
     return _beamform(iq, tx_delays, elem, x, z, False, fs_iq, sound_speed, method="iq", demod_freq=_checked_demod_freq(float(demod_freq)),
-                     t0=t0, f_number=f_number, interpolation=interpolation, compound=compound, out=out, table=table)
+                     t0=t0, f_number=f_number, interpolation=interpolation, compound=compound, out=out, table=table,
+                     rx_apodization=rx_apodization, rx_apodization_alpha=rx_apodization_alpha)
 
 
 _SCAN_METHODS = ("das", "pdas", "fdmas", "iq")
@@ -222,20 +260,22 @@ def scan_first_arrival(tx_delays, elem, px, pz, sound_speed, out=None):
 
 
 def scan_beamform(data, tx_delays, elem, px, pz, fs, sound_speed, method="das", p=2.0, demod_freq=None, t0=0.0, f_number=1.0,
-                  interpolation="linear", compound="sum", out=None, table=None):
+                  interpolation="linear", compound="sum", out=None, table=None, rx_apodization="boxcar", rx_apodization_alpha=0.5):
     """Beamforming on a scan given as two pixel tables px, pz [n0, n1] (metres, the probe's frame; a PolarScan's .pixels(), or any
     other list of pixels) -> image [n0, n1] (DESIGN D21, pbrt_scan_beamform).  method: "das" (das_beamform's arithmetic), "pdas" (with
     p) / "fdmas" (nonlinear_beamform's, BEFORE the axial band-pass) or "iq" (iq_beamform's: complex64 data at the rate fs, demodulated
     at demod_freq, a complex64 image).  On np.meshgrid(x, z, indexing="ij") the result is that call's on the axes x, z, bit for bit.
     The host / DeviceBuffer rule is das_beamform's: host arrays in -> a host array out; `data` a DeviceBuffer ->
     pbrt_scan_beamform_dev, queued, a DeviceBuffer out (`out`, or a new one; host tables are uploaded), with `table` from
-    scan_first_arrival -> pbrt_scan_beamform_table_dev.  elem [n_elements] or the element table [n_elements, 4]."""
+    scan_first_arrival -> pbrt_scan_beamform_table_dev.  elem [n_elements] or the element table [n_elements, 4].
+    rx_apodization, rx_apodization_alpha: the receive window of das_beamform (pbrt_apod_beamform* with tables = 1)."""
     if method not in _SCAN_METHODS:
         raise ValueError(f"method must be one of {_SCAN_METHODS}, got {method!r}")
     if method == "iq":
         _checked_demod_freq(demod_freq)
     return _beamform(data, tx_delays, elem, px, pz, True, fs, sound_speed, method=method, p=p, demod_freq=demod_freq, t0=t0,
-                     f_number=f_number, interpolation=interpolation, compound=compound, out=out, table=table)
+                     f_number=f_number, interpolation=interpolation, compound=compound, out=out, table=table,
+                     rx_apodization=rx_apodization, rx_apodization_alpha=rx_apodization_alpha)
 
 
 def _step(stem, src, args, shape, dtype, out, message=None):
@@ -598,13 +638,20 @@ def polar_n_theta(rho_max, theta_range, step) -> int:
 
 
 class DelayAndSum:
+    """ultraspy's DelayAndSum in the call shapes USMain.py uses.  Setups: f_number, interpolation, compound, is_iq, demod_freq, and the
+    receive window rx_apodization ("boxcar", "tukey", "hann", "hamming") with rx_apodization_alpha (read by "tukey" only; DESIGN D22).
+    `ultraspy` is absent: the names rx_apodization / rx_apodization_alpha and the values 'boxcar' / 'tukey' are ultraspy's from memory,
+    and parity with it is unpinned, as everywhere in this file.  A setup that cannot be beamformed (an unknown window, an alpha outside
+    (0, 1], a window with f_number 0) is a ValueError of beamform()."""
     _method = "das"
 
-    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", is_iq=False):
+    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", is_iq=False, rx_apodization="boxcar",
+                 rx_apodization_alpha=0.5):
         self.on_gpu = on_gpu  # accepted for compatibility; the beamformer has no CPU path
         # is_iq: the data are I/Q samples (complex64) at the rate acquisition_info['sampling_freq'], demodulated at `demod_freq`
         # (None: probe.central_freq)
-        self.setups = {"f_number": f_number, "interpolation": interpolation, "compound": compound, "is_iq": False, "demod_freq": None}
+        self.setups = {"f_number": f_number, "interpolation": interpolation, "compound": compound, "is_iq": False, "demod_freq": None,
+                       "rx_apodization": rx_apodization, "rx_apodization_alpha": rx_apodization_alpha}
         self.set_is_iq(is_iq)
         self.acquisition_info = None
         self.probe = None
@@ -657,7 +704,8 @@ class DelayAndSum:
         return _beamform(data, ai["delays"], ex, gx, gz, polar, ai["sampling_freq"], ai["sound_speed"],
                          method="iq" if iq else self._method, p=su.get("p", 2.0),
                          demod_freq=_checked_demod_freq(self.demod_freq()) if iq else None, t0=ai.get("t0", 0.0) or 0.0,
-                         f_number=su["f_number"], interpolation=su["interpolation"], compound=su["compound"], out=out, table=table)
+                         f_number=su["f_number"], interpolation=su["interpolation"], compound=su["compound"], out=out, table=table,
+                         rx_apodization=su["rx_apodization"], rx_apodization_alpha=su["rx_apodization_alpha"])
 
     def beamform(self, d_data, scan, out=None, table=None):
         """host array in -> host array out; a DeviceBuffer in (the channel buffer left in HBM) -> a DeviceBuffer out, queued.
@@ -689,8 +737,9 @@ class _NonlinearBeamformer(DelayAndSum):
     _centre = 1.0   # band centre in units of the probe's central frequency
 
     def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", band="default", taps_half_length=None,
-                 is_iq=False):
-        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound, is_iq=is_iq)
+                 is_iq=False, rx_apodization="boxcar", rx_apodization_alpha=0.5):
+        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound, is_iq=is_iq,
+                         rx_apodization=rx_apodization, rx_apodization_alpha=rx_apodization_alpha)
         self.setups.update(band=band, taps_half_length=taps_half_length)
         self.scratch_dev = None           # a buffer for the unfiltered image (set by us_render)
         self._taps_cache = (None, None)   # (the taps' bytes, the taps as a DeviceBuffer)

@@ -18,6 +18,10 @@ struct BfRequest {
     float pw;         // the launch argument of the method: p (p-DAS, F-DMAS does not read it), the demodulation frequency (I/Q), else 0
     bool probe;       // the elements are a table [n_elements][4] of pbrt_us_array_elements, not positions [n_elements]
     bool tab;         // the pixels are two tables [nx][nz] (pbrt_scan_*), not the axes x[nx], z[nz]
+    // the receive window (pbrt_apod_*, DESIGN D22): PBRT_APOD_*, and what the kernel reads of it, w = a0 + (1 - a0) cos(pi t(u; alpha)).
+    // PBRT_APOD_BOXCAR (every other block): a0 = 1, alpha = 1, which no kernel reads
+    uint32_t window;
+    float a0, alpha;
 };
 
 // tiles of DAS_TILE pixels along an axis of n
@@ -42,11 +46,12 @@ static inline const char *bf_request(BfRequest *rq, const pbrt_das_params *das, 
     BF_RULE(das->nx > 0 && das->nz > 0 && (uint64_t)das->nx * das->nz < 0xffffffffull);
     // (the launch grid of das_enqueue: every XCD gets the z-tiles of the largest share, at most all of them and one per band)
     BF_RULE((uint64_t)das_tiles(das->nx) * (das_tiles(das->nz) + DAS_BANDS) * DAS_XCDS < 0x7fffffffull);
-    *rq = BfRequest{das, method, method == PBRT_SCAN_IQ ? demod_freq : method == PBRT_SCAN_DAS ? 0.0f : p, probe != 0u, tab};
+    *rq = BfRequest{das, method, method == PBRT_SCAN_IQ ? demod_freq : method == PBRT_SCAN_DAS ? 0.0f : p, probe != 0u, tab,
+                    PBRT_APOD_BOXCAR, 1.0f, 1.0f};
     return nullptr;
 }
 
-// the four public blocks: the methods each admits, then the rules above
+// the five public blocks: the methods each admits, then the rules above (the first four make a boxcar request)
 static inline const char *bf_request(BfRequest *rq, const pbrt_das_params *p, bool probe) {  // pbrt_das_*[_probe]
     return bf_request(rq, p, PBRT_SCAN_DAS, 0.0f, 0.0f, probe ? 1u : 0u, false);
 }
@@ -62,4 +67,17 @@ static inline const char *bf_request(BfRequest *rq, const pbrt_iq_params *p) {
 static inline const char *bf_request(BfRequest *rq, const pbrt_scan_params *p) {
     BF_RULE(p != nullptr);
     return bf_request(rq, &p->das, p->method, p->p, p->demod_freq, p->probe, true);
+}
+// the block with a receive window: the window's own rules, then every rule of its pbrt_scan_params
+static inline const char *bf_request(BfRequest *rq, const pbrt_apod_params *p) {
+    BF_RULE(p != nullptr);
+    BF_RULE(p->tables <= 1u);
+    BF_RULE(p->window == PBRT_APOD_BOXCAR || p->window == PBRT_APOD_TUKEY || p->window == PBRT_APOD_HANN || p->window == PBRT_APOD_HAMMING);
+    BF_RULE(p->window != PBRT_APOD_TUKEY || (std::isfinite(p->alpha) && p->alpha > 0.0f && p->alpha <= 1.0f));
+    BF_RULE(p->window == PBRT_APOD_BOXCAR || p->scan.das.f_number > 0.0f);  // (no aperture, nothing to be a window of)
+    if (const char *why = bf_request(rq, &p->scan.das, p->scan.method, p->scan.p, p->scan.demod_freq, p->scan.probe, p->tables != 0u)) return why;
+    rq->window = p->window;
+    rq->a0 = p->window == PBRT_APOD_BOXCAR ? 1.0f : p->window == PBRT_APOD_HAMMING ? 0.54f : 0.5f;
+    rq->alpha = p->window == PBRT_APOD_TUKEY ? p->alpha : 1.0f;
+    return nullptr;
 }

@@ -189,11 +189,19 @@ DEV float nl_root(float v, bool square, float inv_p) {
 // per call; the rest of the walk, and every bit of its result, is the same.
 // CONVEX: the element table of a curved array (above); its four columns are held in lanes and picked with v_readlane like elem_x.
 // pw: the power p of p-DAS; BF_IQ: the demodulation frequency f_d.  The samples and the pixels are float2 (re, im) for BF_IQ.
-template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD>
+// APOD (DESIGN D22, include/pbrt_hip.h "receive apodisation"): a delayed sample of an element inside the aperture is multiplied by the
+// window's weight w_e before the method sees it.  u = the element's distance from the centre of the pixel's aperture over the
+// aperture's half width, in f64 from the doubles of the aperture test (line: |dx| times ONE reciprocal of half_ap per pixel; table:
+// 2 f# |d_t| times one reciprocal of d_n per element); t = clamp((u - (1 - alpha)) / alpha, 0, 1) in f64 (a NaN u -- z = 0 -- gives 0),
+// rounded once to f32; w = fmaf(1 - a0, cospif(t), a0) in f32.  Once per (pixel, element), outside the loop over the angles.  Without
+// APOD a0 and alpha are not read and no instruction of the walk changes (profiles/rx_apodization.md).
+DEV float das_weigh(float w, float s) { return w * s; }
+DEV float2 das_weigh(float w, float2 s) { return make_float2(w * s.x, w * s.y); }
+template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD, bool APOD = false>
 DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename DasSample<METHOD>::type *__restrict__ data,
                   const float *__restrict__ tx, const float *__restrict__ elem_x, const float *__restrict__ gx,
                   const float *__restrict__ gz, const double *__restrict__ ttx, typename DasSample<METHOD>::type *__restrict__ out,
-                  float pw) {
+                  float pw, [[maybe_unused]] float apod_a0 = 1.0f, [[maybe_unused]] float alpha = 1.0f) {
     typedef typename DasSample<METHOD>::type Sample;
     // rows of a wave's share: the partial sum (BF_DAS), or per angle of a trip q_a, then (F-DMAS) sum |s_e|, (BF_IQ) the imaginary part
     constexpr uint32_t ROWS = METHOD == BF_DAS ? 1u : (METHOD == PBRT_BF_FDMAS || METHOD == BF_IQ) ? 2u * DAS_ANG : DAS_ANG;
@@ -212,6 +220,10 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
     const double zz = z * z;
     const bool square = pw == 2.0f;
     const float inv_p = 1.0f / pw;
+    // APOD: 1 / half_ap once per pixel (a window needs f# > 0: bf_request.h), 1 - alpha and 1 / alpha once per lane, 1 - a0 in f32
+    [[maybe_unused]] const double inv_half_ap = APOD ? 1.0 / half_ap : 0.0;
+    [[maybe_unused]] const double flat = APOD ? 1.0 - (double)alpha : 0.0, inv_alpha = APOD ? 1.0 / (double)alpha : 0.0;
+    [[maybe_unused]] const float apod_a1 = 1.0f - apod_a0;  // (a0 is the first angle of a trip below)
     // Element positions and transmit delays are tables of the launch, indexed by the (wave-uniform) element: as scalar loads they
     // put a trip to the scalar cache (or to L2) in front of every element of every loop -- a wave alone on its CU took 100 us for
     // 7 600 VALU instructions.  Instead lane l of the wave holds entry l of the current block of 64 elements, as doubles, and an
@@ -306,15 +318,23 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
                 const double dx = x - das_lane_f64(ex_l, el);
                 double dz = 0.0;
                 bool in_ap;
+                [[maybe_unused]] double u = 0.0;  // (APOD) distance from the aperture's centre over its half width
                 if (CONVEX) {
                     dz = z - das_lane_f64(ez_l, el);
                     const double enx = das_lane_f64(nx_l, el), enz = das_lane_f64(nz_l, el);
                     const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
                     in_ap = any && (p.f_number > 0.0f ? (dn > 0.0 && two_f * fabs(dt) <= dn) : true);
+                    if constexpr (APOD) u = two_f * fabs(dt) * (1.0 / dn);
                 } else {
                     in_ap = any && fabs(dx) <= half_ap;
+                    if constexpr (APOD) u = fabs(dx) * inv_half_ap;
                 }
                 if (__ballot(in_ap) == 0ull) continue;
+                [[maybe_unused]] float w_e = 1.0f;
+                if constexpr (APOD) {
+                    const float t = (float)fmin(fmax((u - flat) * inv_alpha, 0.0), 1.0);
+                    w_e = fma_(apod_a1, cospif(t), apod_a0);
+                }
                 const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
                 const DasPos dp = INTERP == PBRT_DAS_LINEAR ? das_split(d * fs) : DasPos{0, 0.0f};
                 [[maybe_unused]] float2 rot_e = make_float2(1.0f, 0.0f);
@@ -328,6 +348,7 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
                     [[maybe_unused]] bool use = false;  // (p-DAS only)
                     [[maybe_unused]] float v = 0.0f;
                     const auto take = [&](Sample s) {
+                        if constexpr (APOD) s = das_weigh(w_e, s);
                         if constexpr (METHOD == BF_DAS) {
                             acc += s;
                         } else if constexpr (METHOD == BF_IQ) {
@@ -430,6 +451,19 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_iq_beamform(pbrt_das_params 
                                                                 const float *__restrict__ gx, const float *__restrict__ gz,
                                                                 const double *__restrict__ ttx, float2 *__restrict__ out, float f_d) {
     das_walk<INTERP, TABLE, CONVEX, BF_IQ>(p, grid, data, tx, elem_x, gx, gz, ttx, out, f_d);
+}
+
+// the walk with a receive window (APOD above): every method, and the two launch arguments of the window -- a template of its own for the
+// reason k_nl_beamform is one.  data and out are float2 (re, im) pairs for BF_IQ, as DasSample says; pw as in k_nl_beamform / k_iq_beamform.
+template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t METHOD>
+__global__ __launch_bounds__(64 * DAS_SPLIT) void k_apod_beamform(pbrt_das_params p, DasGrid grid,
+                                                                  const typename DasSample<METHOD>::type *__restrict__ data,
+                                                                  const float *__restrict__ tx, const float *__restrict__ elem_x,
+                                                                  const float *__restrict__ gx, const float *__restrict__ gz,
+                                                                  const double *__restrict__ ttx,
+                                                                  typename DasSample<METHOD>::type *__restrict__ out, float pw, float a0,
+                                                                  float alpha) {
+    das_walk<INTERP, TABLE, CONVEX, METHOD, true>(p, grid, data, tx, elem_x, gx, gz, ttx, out, pw, a0, alpha);
 }
 
 // What k_axial_fir and k_apply_pulse share: one workgroup makes the 256 outputs n0 .. n0 + 255 of one row of N samples,

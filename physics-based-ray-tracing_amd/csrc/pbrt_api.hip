@@ -2535,7 +2535,18 @@ static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const 
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    if (rq.method == PBRT_SCAN_IQ) {  // I/Q delay-and-sum: dd and dout hold (re, im) pairs, pw is the demodulation frequency
+    if (rq.window != PBRT_APOD_BOXCAR && rq.method == PBRT_SCAN_IQ) {  // a receive window (D22): the walk with the weight arm, a0 and alpha
+        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_apod_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), BF_IQ>; },
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
+        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
+                           reinterpret_cast<float2 *>(dout), rq.pw, rq.a0, rq.alpha);
+    } else if (rq.window != PBRT_APOD_BOXCAR) {
+        const auto kernel = with_flags([](auto L, auto T, auto X, auto F, auto P) {
+            return &k_apod_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), F() ? PBRT_BF_FDMAS : P() ? PBRT_BF_PDAS : BF_DAS>; },
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe, rq.method == PBRT_BF_FDMAS,
+                                       rq.method == PBRT_BF_PDAS);
+        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout, rq.pw, rq.a0, rq.alpha);
+    } else if (rq.method == PBRT_SCAN_IQ) {  // I/Q delay-and-sum: dd and dout hold (re, im) pairs, pw is the demodulation frequency
         const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_iq_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
                                        p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
         hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
@@ -2614,7 +2625,7 @@ static int pulse_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, uint32_t K,
     return PBRT_OK;
 }
 
-// The three bodies behind the 17 beamform and first-arrival entry points.  Each entry point makes its request first (BF_REQUEST below):
+// The three bodies behind the 20 beamform and first-arrival entry points.  Each entry point makes its request first (BF_REQUEST below):
 // a null context is PBRT_E_INVALID and touches nothing, a refused block is PBRT_E_INVALID with the text of the rule.
 // (d_tx_delays or d_table: the plain form passes its delays, the table form its first-arrival table, and the other one null)
 static int beamform_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_data, const void *d_elem, const void *d_x, const void *d_z,
@@ -2744,6 +2755,21 @@ int pbrt_scan_beamform_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void 
     return beamform_dev(ctx, rq, d_data, d_elem, d_px, d_pz, d_out, d_tx_delays, nullptr);
 }
 int pbrt_scan_beamform_table_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_data, const void *d_table, const void *d_elem,
+                                 const void *d_px, const void *d_pz, void *d_out) {
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_px, d_pz, d_out, nullptr, d_table);
+}
+int pbrt_apod_beamform(pbrt_ctx *ctx, const pbrt_apod_params *p, const float *data, const float *tx_delays, const float *elem,
+                       const float *px, const float *pz, float *out) {
+    BF_REQUEST(p);
+    return beamform_host(ctx, rq, data, tx_delays, elem, px, pz, out);
+}
+int pbrt_apod_beamform_dev(pbrt_ctx *ctx, const pbrt_apod_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
+                           const void *d_px, const void *d_pz, void *d_out) {
+    BF_REQUEST(p);
+    return beamform_dev(ctx, rq, d_data, d_elem, d_px, d_pz, d_out, d_tx_delays, nullptr);
+}
+int pbrt_apod_beamform_table_dev(pbrt_ctx *ctx, const pbrt_apod_params *p, const void *d_data, const void *d_table, const void *d_elem,
                                  const void *d_px, const void *d_pz, void *d_out) {
     BF_REQUEST(p);
     return beamform_dev(ctx, rq, d_data, d_elem, d_px, d_pz, d_out, nullptr, d_table);

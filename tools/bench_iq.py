@@ -3,8 +3,15 @@
 modulus on the same grid at decimation 1 and 4; the I/Q chain on a lambda / 2 axial grid.  Beamformer and envelope by HIP events on the
 library's stream (pbrt_ctx_set_profiling), N = 10, without and with the first-arrival table.  rf2iq has no event slot in
 pbrt_image_stats (ABI 5 stays as it is): it is timed by wall clock over a queue of 50 launches, so the chain totals add two kinds of
-time and say so.  A last block times rf2iq alone at D = 1, 2, 4, 8: its LDS reads are D words apart from lane to lane."""
+time and say so.  A last block times rf2iq alone at D = 1, 2, 4, 8: its LDS reads are D words apart from lane to lane.
+--apodization {boxcar,tukey,hann,hamming} [--alpha A]: the receive window of both beamformers (DESIGN D22; boxcar: today's kernels)."""
 import os, sys, time
+import argparse
+_ap = argparse.ArgumentParser()
+_ap.add_argument("--apodization", choices=("boxcar", "tukey", "hann", "hamming"), default="boxcar")   # the receive window (DESIGN D22)
+_ap.add_argument("--alpha", type=float, default=0.5)
+_a = _ap.parse_args()
+WIN = dict(rx_apodization=_a.apodization, rx_apodization_alpha=_a.alpha) if _a.apodization != "boxcar" else {}
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pbrt_amd as mi
@@ -55,7 +62,7 @@ def rf_chain(step_z, name):
     x, z, d_x, d_z, tab = grid(step_z)
     bf, env = mi.DeviceBuffer(cx, (len(x), len(z))), mi.DeviceBuffer(cx, (len(x), len(z)))
     for label, t in (("", None), (", first-arrival table", tab)):
-        das, e = events(lambda: (mi.das_beamform(d_data, d_tx, d_ex, d_x, d_z, fs, c, out=bf, table=t), mi.envelope(bf, out=env)))
+        das, e = events(lambda: (mi.das_beamform(d_data, d_tx, d_ex, d_x, d_z, fs, c, out=bf, table=t, **WIN), mi.envelope(bf, out=env)))
         print(f"RF  {name} {len(x)} x {len(z)}{label}: DAS {das:7.1f} us + Hilbert envelope {e:6.1f} us = {das + e:7.1f} us", flush=True)
 
 
@@ -66,11 +73,12 @@ def iq_chain(step_z, name, D):
     t_demod = wall(lambda: mi.rf2iq(d_data, fc, fs, decimation=D, taps=taps, out=iq))
     bf, env = mi.DeviceBuffer(cx, (len(x), len(z)), np.complex64), mi.DeviceBuffer(cx, (len(x), len(z)))
     for label, t in (("", None), (", first-arrival table", tab)):
-        das, e = events(lambda: (mi.iq_beamform(iq, d_tx, d_ex, d_x, d_z, fs / D, c, fc, out=bf, table=t), mi.iq_envelope(bf, out=env)))
+        das, e = events(lambda: (mi.iq_beamform(iq, d_tx, d_ex, d_x, d_z, fs / D, c, fc, out=bf, table=t, **WIN), mi.iq_envelope(bf, out=env)))
         print(f"I/Q {name} {len(x)} x {len(z)} D = {D}{label}: rf2iq (K = {taps.shape[0] // 2}, wall clock) {t_demod:6.1f} us + I/Q DAS {das:7.1f} us "
               f"+ modulus {e:5.1f} us = {t_demod + das + e:7.1f} us (events + wall clock)", flush=True)
 
 
+print(f"receive window: {_a.apodization}" + (f" alpha = {_a.alpha:g}" if _a.apodization == "tukey" else ""), flush=True)
 rf_chain(lam / 4, "lambda/4")
 for D in (1, 4):
     iq_chain(lam / 4, "lambda/4", D)
