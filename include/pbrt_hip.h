@@ -178,7 +178,8 @@ typedef struct pbrt_film_desc {
 #define PBRT_FILM_RAW_ACCUM 1u /* output 4 floats/pixel (sum w*rgb, sum w) un-normalised: \
                                   for sample-sharded multi-GPU reduction */
 /* The flags marked DIAGNOSTIC BUILD select launch structures that lost their A/B: the product library does not carry their kernels
- * and refuses them with PBRT_E_UNSUPPORTED; libpbrt_hip_diag.so (make -C csrc diag, -DPBRT_DIAG) has them.  Same film either way. */
+ * and refuses them with PBRT_E_UNSUPPORTED; libpbrt_hip_diag.so (make -C csrc diag, -DPBRT_DIAG) has them (kernels: csrc/kernels_diag.h,
+ * host side: csrc/diag_driver.h).  Same film either way. */
 #define PBRT_FILM_NO_REPACK 2u /* DIAGNOSTIC BUILD, with PBRT_FILM_NO_HIT_POOL: do not re-densify the live paths before bounces >= 2 */
 #define PBRT_FILM_FUSE_PLAN_SET 0x80u /* bits 8..15 of flags hold the fuse plan: bit d set = the launch that walks bounce d goes on \
                                         with bounce d + 1 of its paths in registers, up to 6 bounces per launch (brute-force \

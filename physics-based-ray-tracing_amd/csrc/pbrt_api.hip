@@ -19,6 +19,9 @@
 #include "kernels_wavefront.h"
 #include "kernels_us_wavefront.h"
 #include "kernels_beamform.h"
+#ifdef PBRT_DIAG
+#include "kernels_diag.h"  // the kernels only the diagnostic build launches
+#endif
 #include "workspace.h"
 
 static std::string g_ctxless_error;
@@ -616,9 +619,9 @@ int pbrt_scene_destroy(pbrt_scene *s) {
 //   PBRT_US_EMIT_FUSED            0: emitter rays through k_us_emit_init and the later-bounce instance         per call (us_impl)
 //   PBRT_US_EMIT_PERMUTE          0: workgroup b walks region b; k > 1: another stride of the permutation     per call (us_impl)
 //   PBRT_ENV_GENERAL              1: every column length through k_hilbert_env                                per call (env_enqueue)
-//   diagnostic build (-DPBRT_DIAG) only:
-//   PBRT_PAIR_MERGE               k: k_chain_pair with merge bounce k instead of the k_bounce chain           per call (render_impl)
-//   PBRT_US_FUSED_BVH             1: BVH scenes through the fused ultrasound bounce, not the streams          per call (us_impl)
+//   diagnostic build (-DPBRT_DIAG) only, read in diag_driver.h and not part of Switches:
+//   PBRT_PAIR_MERGE               k: k_chain_pair with merge bounce k instead of the k_bounce chain           per call (diag_selected)
+//   PBRT_US_FUSED_BVH             1: BVH scenes through the fused ultrasound bounce, not the streams          per call (diag_us_fused_bvh)
 //   -DPBRT_CU_MASK_PROBE only:
 //   PBRT_CU_MASK                  even | odd | low | pairs | ...: the CUs the context's stream runs on        pbrt_ctx_create
 //
@@ -628,10 +631,6 @@ struct Switches {
     uint32_t wf_split_s = 0, wf_split_parts = 1;  // s = 0: off
     bool us_generic_kernel = false, us_emit_fused = true, env_general = false;
     int us_emit_permute = 1;  // 0: off, 1: the library's stride, > 1: that stride
-#ifdef PBRT_DIAG
-    uint32_t pair_merge = 0;  // 0: off
-    bool us_fused_bvh = false;
-#endif
 };
 static Switches read_switches() {
     static const Switches once = [] {  // the two that hold for the process
@@ -654,10 +653,6 @@ static Switches read_switches() {
     w.us_emit_fused = flag("PBRT_US_EMIT_FUSED", true);
     w.env_general = flag("PBRT_ENV_GENERAL", false);
     if (const char *e = getenv("PBRT_US_EMIT_PERMUTE")) w.us_emit_permute = atoi(e);
-#ifdef PBRT_DIAG
-    if (const char *e = getenv("PBRT_PAIR_MERGE")) w.pair_merge = (uint32_t)atoi(e);
-    w.us_fused_bvh = flag("PBRT_US_FUSED_BVH", false);
-#endif
     return w;
 }
 
@@ -670,26 +665,12 @@ static Switches read_switches() {
 #ifndef PBRT_DEFAULT_FUSE_PLAN
 #define PBRT_DEFAULT_FUSE_PLAN 0x15u
 #endif
-// Depth from which one launch walks every remaining bounce of a pass (k_walk; 0xff: never).  PBRT_FILM_WALK_FROM overrides.
-#ifndef PBRT_DEFAULT_WALK_FROM
-#define PBRT_DEFAULT_WALK_FROM 0xffu
-#endif
 
 // The fused bounce kernel of a launch that walks nb bounces (>= 2: the multi-bounce variants of the brute-force kernels,
-// kernels_radiance.h; a.nb = nb) -- or, walk (diagnostic build), every remaining bounce of the pass (k_walk).  Glossy brute-force
-// scenes have instances of their own.  nullptr: BVH scenes run k_trace / k_shade (wf_bounces); their fused bounce
-// (PBRT_FILM_NO_HIT_POOL) exists in the diagnostic build only.
-static RadKern bounce_kernel(const pbrt_scene *s, bool first, uint32_t nb, bool walk = false) {
+// kernels_radiance.h; a.nb = nb).  Glossy brute-force scenes have instances of their own.  nullptr: BVH scenes run k_trace /
+// k_shade (wf_bounces); their fused bounce (PBRT_FILM_NO_HIT_POOL) and k_walk exist in the diagnostic build only (diag_driver.h).
+static RadKern bounce_kernel(const pbrt_scene *s, bool first, uint32_t nb) {
     const bool two = nb >= 2;
-#ifdef PBRT_DIAG
-    if (walk)
-        return with_flags(
-            [](auto F, auto B, auto N) -> RadKern { return &k_walk<F(), B() ? ACCEL_K_BRUTE_BIG : ACCEL_K_BRUTE, N() ? 2 : 1>; }, first,
-            s->accel_kernel != ACCEL_K_BRUTE, nb == 2);
-    if (s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS)
-        return with_flags([](auto F, auto L) -> RadKern { return &k_bounce<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL>; }, first,
-                          s->accel_kernel == ACCEL_K_BVH_LDS);
-#endif
     switch (s->accel_kernel) {
         case ACCEL_K_BRUTE:
             return with_flags([](auto F, auto N) -> RadKern { return &k_bounce<F(), ACCEL_K_BRUTE, N() ? 2 : 1>; }, first, two);
@@ -700,11 +681,10 @@ static RadKern bounce_kernel(const pbrt_scene *s, bool first, uint32_t nb, bool 
             return nullptr;
     }
 }
-static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool first, uint32_t nb = 1, bool walk = false) {
-    const RadKern k = bounce_kernel(s, first, nb, walk);
+static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool first, uint32_t nb = 1) {
+    const RadKern k = bounce_kernel(s, first, nb);
     if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_bounce: no fused bounce kernel for accelerator %d in this build", s->accel_kernel);
-    const bool lds = s->accel_kernel == ACCEL_K_BVH_LDS;
-    hipLaunchKernelGGL(k, dim3(nseg), dim3(seg_threads(s->accel_kernel)), lds ? s->lds_bytes : 0u, s->ctx->stream, a);
+    hipLaunchKernelGGL(k, dim3(nseg), dim3(seg_threads(s->accel_kernel)), 0u, s->ctx->stream, a);
     return PBRT_OK;
 }
 
@@ -712,7 +692,7 @@ static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool fi
 // ACCEL_K_BRUTE with a compiled-in quirk set (the kernels of BASELINE config 3, both readings, and of the reference's own loop)
 // has its table mode compiled in too: -1 on later bounces, 0 for emitter rays (never any tables).  Everything else reads both at
 // run time.  nullptr: BVH scenes run k_trace / k_us_shade (us_wf_pass); their fused bounce (PBRT_US_FUSED_BVH=1, no emitter rays)
-// exists in the diagnostic build only.
+// exists in the diagnostic build only (diag_driver.h; launch_us takes it from there).
 // convex (PBRT_US_ARRAY_CONVEX, D18): the curved array has the generic instances only (quirks and tables read at run time).
 static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint32_t q, int tab, bool convex = false) {
     if (!first) tab = -1;
@@ -732,24 +712,8 @@ static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint3
             return with_flags([](auto F, auto E, auto X) -> UsKern {
                 return &k_us_bounce<F(), ACCEL_K_BRUTE_BIG, E(), US_Q_RUNTIME, -1, X()>; }, first, emit, convex);
         default:
-#ifdef PBRT_DIAG
-            if (!emit)
-                return with_flags([](auto F, auto L, auto X) -> UsKern {
-                    return &k_us_bounce<F(), L() ? ACCEL_K_BVH_LDS : ACCEL_K_BVH_GLOBAL, false, US_Q_RUNTIME, -1, X()>; },
-                                  first, s->accel_kernel == ACCEL_K_BVH_LDS, convex);
-#endif
             return nullptr;
     }
-}
-// Scenes whose tree is in LDS: the LDS limit of their fused kernels (the diagnostic build has them; nullptr: not in this build)
-static int set_lds_attr(pbrt_scene *s) {
-    if (s->accel_kernel != ACCEL_K_BVH_LDS) return PBRT_OK;
-    for (bool first : {true, false}) {
-        if (const RadKern k = bounce_kernel(s, first, 1)) HIPCHK(s->ctx, set_max_lds(k, s->lds_bytes));
-        for (bool convex : {false, true})
-            if (const UsKern k = us_bounce_kernel(s, first, false, US_Q_RUNTIME, -1, convex)) HIPCHK(s->ctx, set_max_lds(k, s->lds_bytes));
-    }
-    return PBRT_OK;
 }
 
 // Fuse plan: bit d set = the launch that walks bounce d goes on with bounce d + 1 in registers (at most MAX_CHAIN bounces per
@@ -773,15 +737,6 @@ static uint32_t plan_from_survival(const unsigned long long *live, uint32_t max_
     }
     return plan;
 }
-
-// k_chain_pair (two tiles per wave, kernels_radiance.h; lost its A/B): diagnostic builds launch it instead of the k_bounce chain
-// when PBRT_PAIR_MERGE=k names the merge bounce and the plan walks the whole path in one launch.
-#ifdef PBRT_DIAG
-static uint32_t pair_merge_bounce(uint32_t k, uint32_t plan, uint32_t max_depth) {
-    if (max_depth > MAX_CHAIN || max_depth < 2 || chain_len(plan, 0, max_depth) < max_depth) return 0;
-    return k < max_depth ? k : 0u;
-}
-#endif
 
 // Byte model of the radiance path (DESIGN.md "Algorithmic bytes").  live[d] = paths entering depth d.
 // A launch that walks two bounces (fuse plan bit d) keeps its paths in registers between them: the survivors of bounce d
@@ -1322,8 +1277,47 @@ static int probe_plan(pbrt_ctx *c, unsigned long long *segstats, uint32_t n_rows
     return PBRT_OK;
 }
 
-static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_desc *f, void *d_out) {
-    pbrt_ctx *c = s->ctx;
+// What the stages of a radiance render share.  render_impl calls the stages in order; each fills its own group of members.
+namespace {
+struct Render {
+    pbrt_scene *s;
+    pbrt_ctx *c;
+    const pbrt_camera *cam;
+    const pbrt_film_desc *f;
+    void *d_out;
+    // render_check: the launch structure and the rendered region (the crop and the margin its filter reads)
+    bool brute = false, wavefront = false;
+    Switches sw;
+    uint32_t rx0 = 0, ry0 = 0, rw = 0, rh = 0;
+    uint64_t npix_r = 0, film_px = 0;
+    // render_buffers: the shape of a full pass and the buffers of the call
+    uint32_t region = 0, s_pass = 0, cap = 0, nseg = 0;
+    uint32_t n_own = 0, n_rows = 0, stat_rows = 0, hit_rows = 0;  // live counters; statistics rows per counter, counters in use, k_shade's hit rows
+    WfBufs wfb{};
+    WfPlan wfp;
+    float *Lhome = nullptr, *acc = nullptr;
+    uint32_t *segA = nullptr, *segB = nullptr;
+    unsigned long long *dstats = nullptr, *segstats = nullptr;
+    // render_args: the arguments of every pass
+    RadArgs base{};
+    FilmArgs fa{};
+    // the pass loop
+    PassTimer timer{};
+    uint32_t passes = 0, launches = 0, plan = 0;
+    bool probe = false, plan_was_learnt = false;
+};
+}  // namespace
+// First render of a brute-force scene with the plan left to the library: the first PROBE_SPP samples are a pass of their own,
+// their path survival is read back (probe_plan) and decides the plan of all the other passes.  The film does not depend on how
+// the samples are split into passes, nor on the plan.
+constexpr uint32_t PROBE_SPP = 2;
+
+// Check and geometry: the argument rules, the launch structure of the scene, the rendered region.
+static int render_check(Render &r) {
+    pbrt_ctx *c = r.c;
+    const pbrt_camera *cam = r.cam;
+    const pbrt_film_desc *f = r.f;
+    void *d_out = r.d_out;
     if (int rcs = ctx_settle(c)) return rcs;
     NEED(c, cam && f && d_out);
     const uint32_t W = cam->film_w, H = cam->film_h;
@@ -1334,24 +1328,28 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     HIPCHK(c, hipSetDevice(c->device));
     // Brute-force scenes, or BVH scenes: these run intersection and shading as separate streams (kernels_wavefront.h);
     // PBRT_FILM_NO_HIT_POOL keeps the fused k_bounce (one launch per bounce, shading in the lanes the traversal leaves) as the A/B
-    // reference
-    const bool brute = s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG;
-    const bool wavefront = !brute && !(f->flags & PBRT_FILM_NO_HIT_POOL);
-    const Switches sw = read_switches();
-#ifndef PBRT_DIAG
-    // launch structures that lost their A/B live in the diagnostic build only (make -C csrc diag -> libpbrt_hip_diag.so)
-    if ((f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || (!brute && (f->flags & PBRT_FILM_NO_HIT_POOL)))
-        return c->fail(PBRT_E_UNSUPPORTED, "PBRT_FILM_REGEN / PBRT_FILM_WALK_FROM / PBRT_FILM_NO_HIT_POOL select diagnostic launch "
-                                           "structures: build libpbrt_hip_diag.so (make -C csrc diag)");
-#endif
-    int rc = set_lds_attr(s);
-    if (rc) return rc;
+    // reference -- in the diagnostic build (diag_driver.h)
+    r.brute = r.s->accel_kernel == ACCEL_K_BRUTE || r.s->accel_kernel == ACCEL_K_BRUTE_BIG;
+    r.wavefront = !r.brute && !(f->flags & PBRT_FILM_NO_HIT_POOL);
+    r.sw = read_switches();
     const uint32_t R = f->filter == PBRT_FILTER_BOX ? 0 : (f->filter == PBRT_FILTER_TENT ? 1 : 2);
-    const uint32_t rx0 = f->crop_x > R ? f->crop_x - R : 0, ry0 = f->crop_y > R ? f->crop_y - R : 0;
+    r.rx0 = f->crop_x > R ? f->crop_x - R : 0;
+    r.ry0 = f->crop_y > R ? f->crop_y - R : 0;
     const uint32_t rx1 = std::min(f->crop_x + f->crop_w + R, W), ry1 = std::min(f->crop_y + f->crop_h + R, H);
-    const uint32_t rw = rx1 - rx0, rh = ry1 - ry0;
-    const uint64_t npix_r = (uint64_t)rw * rh;
-    const uint64_t film_px = (uint64_t)f->crop_w * f->crop_h;
+    r.rw = rx1 - r.rx0;
+    r.rh = ry1 - r.ry0;
+    r.npix_r = (uint64_t)r.rw * r.rh;
+    r.film_px = (uint64_t)f->crop_w * f->crop_h;
+    return PBRT_OK;
+}
+
+// Pass sizing and buffers: the paths in flight per pass, the buffers whose size follows it, the counters, the film accumulator and
+// the statistics rows, all cleared; the launch plan of the call.
+static int render_buffers(Render &r) {
+    pbrt_scene *s = r.s;
+    pbrt_ctx *c = r.c;
+    const pbrt_film_desc *f = r.f;
+    const bool brute = r.brute, wavefront = r.wavefront;
     // default paths in flight per pass, measured on cbox 512^2 x 256 (one box): 2 / 4 / 8 / 16 / 32 / 64 Mi -> 9.55 / 8.56 / 8.14 / 7.92 /
     // 8.13 / 8.20 ms (fewer launch tails against cache residency of the ping-pong state)
     // round 2, fused first launch: 2 / 4 / 8 / 16 / 32 / 64 Mi -> 9.09 / 8.07 / 7.65 / 7.37 / 7.31 / 7.39 ms; BVH scenes keep 16 Mi
@@ -1371,72 +1369,62 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
     const uint64_t pass_paths = f->pass_paths ? f->pass_paths
                                               : default_pass_paths(c, wavefront, brute ? (64u << 20) : (16u << 20), 16 + 2 * N_STATE * 4);
     static_assert(WF_REGION == REGION_SEGS_BVH * SEG_BVH, "both BVH launch structures cut a pass into the same regions");
-    const uint32_t REGION = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
-    WfBufs wfb{};
-    float *Lhome = nullptr;
+    r.region = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
     auto alloc_pass = [&](uint32_t cap, uint32_t nseg) -> int {
         NEED(c, wavefront || (uint64_t)cap * N_STATE * 4 < 0xffffffffull);  // the tiled state arrays are addressed through 32-bit buffer offsets
         if (wavefront) NEED(c, cap < WF_DEAD);  // ray records are addressed with two flag bits on top
-        Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
-        return Lhome && (!wavefront || wf_alloc(c, cap, nseg, &wfb)) ? PBRT_OK : PBRT_E_NOMEM;
+        r.Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
+        return r.Lhome && (!wavefront || wf_alloc(c, cap, nseg, &r.wfb)) ? PBRT_OK : PBRT_E_NOMEM;
     };
     PassShape ps;
-    if ((rc = size_pass(c, pass_paths, f->pass_paths != 0, f->spp, npix_r, REGION, true, alloc_pass, &ps)) != 0) return rc;
-    const uint32_t s_pass = ps.per_pass, cap = ps.cap, nseg = ps.nseg;
-    WfPlan wfp;
+    int rc;
+    if ((rc = size_pass(c, pass_paths, f->pass_paths != 0, f->spp, r.npix_r, r.region, true, alloc_pass, &ps)) != 0) return rc;
+    r.s_pass = ps.per_pass;
+    r.cap = ps.cap;
+    r.nseg = ps.nseg;
     if (wavefront) {
-        wfp = wf_plan(s, sw);
-        if ((rc = wf_set_attr(s, wfp)) != 0) return rc;
+        r.wfp = wf_plan(s, r.sw);
+        if ((rc = wf_set_attr(s, r.wfp)) != 0) return rc;
     }
-    // Brute-force scenes: the ping-pong path state (2 x 60 B per slot, 8 GB at 64 Mi paths) is only touched by a pass that needs
-    // more than one bounce launch; with the plan that walks every bounce in one launch (the Cornell box) it is never written, so it
-    // is allocated per pass, for the paths of THAT pass, when its plan says so (state_for below).
-    float *stA = wavefront ? (float *)wfb.stA : nullptr;
-    float *stB = wavefront ? (float *)wfb.stB : nullptr;
-    // fused BVH kernels: the live paths are made dense again before every bounce of depth >= 2 (k_scan_owners / k_repack_copy)
-    const bool repack = !brute && !wavefront && rad_wave_private(s->accel_kernel) && !(f->flags & PBRT_FILM_NO_REPACK);
-    float *stC = repack ? (float *)c->buf("stateC", (size_t)cap * N_STATE * 4) : nullptr;
     // live counters and statistics rows: one per region, or one per wave of it (BVH kernels: wave-private compaction)
-    const uint32_t n_own = nseg * rad_owners_per_region(s->accel_kernel);
-    uint32_t *segA = (uint32_t *)c->buf("segA", (size_t)n_own * 4);
-    uint32_t *segB = (uint32_t *)c->buf("segB", (size_t)n_own * 4);
-    uint32_t *segC = repack ? (uint32_t *)c->buf("segC", (size_t)n_own * 4) : nullptr;
-    uint32_t *offs = repack ? (uint32_t *)c->buf("seg_offs", (size_t)n_own * 4) : nullptr;
-    uint32_t *quota = repack ? (uint32_t *)c->buf("seg_quota", 64) : nullptr;
-    float *acc = (float *)c->buf("film_acc", film_px * 16);
-    unsigned long long *dstats = (unsigned long long *)c->buf("stats", (2 + 2 * MAX_DEPTH_STATS) * 8);
-    const uint32_t n_rows = nseg * (wavefront ? WF_SHADE_THREADS / 64u : rad_rows_per_region(s->accel_kernel));  // statistics rows
+    r.n_own = r.nseg * rad_owners_per_region(s->accel_kernel);
+    r.segA = (uint32_t *)c->buf("segA", (size_t)r.n_own * 4);
+    r.segB = (uint32_t *)c->buf("segB", (size_t)r.n_own * 4);
+    r.acc = (float *)c->buf("film_acc", r.film_px * 16);
+    r.dstats = (unsigned long long *)c->buf("stats", (2 + 2 * MAX_DEPTH_STATS) * 8);
+    r.n_rows = r.nseg * (wavefront ? WF_SHADE_THREADS / 64u : rad_rows_per_region(s->accel_kernel));  // statistics rows
     // statistics rows in use: segments, shadow rays, one per depth (cleared and reduced per call: keep it to what the call touches)
-    const uint32_t stat_rows = 2 + (uint32_t)std::min<uint64_t>(f->max_depth, MAX_DEPTH_STATS);
-    const size_t segstats_bytes = (size_t)stat_rows * n_rows * 8;  // reduced at the end
-    unsigned long long *segstats = (unsigned long long *)c->buf("segstats", (size_t)(2 + 2 * MAX_DEPTH_STATS) * n_rows * 8);
-    if (!segstats) return PBRT_E_NOMEM;
-    if (!Lhome || !segA || !segB || !acc || !dstats) return PBRT_E_NOMEM;
+    r.stat_rows = 2 + (uint32_t)std::min<uint64_t>(f->max_depth, MAX_DEPTH_STATS);
+    const size_t segstats_bytes = (size_t)r.stat_rows * r.n_rows * 8;  // reduced at the end
+    r.segstats = (unsigned long long *)c->buf("segstats", (size_t)(2 + 2 * MAX_DEPTH_STATS) * r.n_rows * 8);
+    if (!r.segstats) return PBRT_E_NOMEM;
+    if (!r.Lhome || !r.segA || !r.segB || !r.acc || !r.dstats) return PBRT_E_NOMEM;
     // k_shade counts the rays of every depth that hit something (rows HIT_ROW0 + d, for the byte model)
-    const uint32_t hit_rows = wavefront ? stat_rows - 2 : 0;
-    if (repack && (!stC || !segC || !offs || !quota)) return PBRT_E_NOMEM;
+    r.hit_rows = wavefront ? r.stat_rows - 2 : 0;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemsetAsync(acc, 0, film_px * 16, st));
-    HIPCHK(c, hipMemsetAsync(dstats, 0, (2 + 2 * MAX_DEPTH_STATS) * 8, st));
-    HIPCHK(c, hipMemsetAsync(segstats, 0, segstats_bytes, st));
-    if (hit_rows) HIPCHK(c, hipMemsetAsync(segstats + (size_t)HIT_ROW0 * n_rows, 0, (size_t)hit_rows * n_rows * 8, st));
+    HIPCHK(c, hipMemsetAsync(r.acc, 0, r.film_px * 16, st));
+    HIPCHK(c, hipMemsetAsync(r.dstats, 0, (2 + 2 * MAX_DEPTH_STATS) * 8, st));
+    HIPCHK(c, hipMemsetAsync(r.segstats, 0, segstats_bytes, st));
+    if (r.hit_rows) HIPCHK(c, hipMemsetAsync(r.segstats + (size_t)HIT_ROW0 * r.n_rows, 0, (size_t)r.hit_rows * r.n_rows * 8, st));
     HIPCHK(c, hipEventRecord(c->ev0, st));
-    PassTimer timer{c};
-    uint32_t passes = 0, launches = 0;
+    r.timer = PassTimer{c};
     // the fuse plan of this call: the caller's, or the one learnt from the last render of this scene, or the library default
-    const bool plan_was_learnt = brute && s->plan_hint_valid;
-    uint32_t plan = !brute ? 0u
-                    : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? ((f->flags >> 8) & 0xffu)
-                    : (s->plan_hint_valid ? s->plan_hint : PBRT_DEFAULT_FUSE_PLAN);
-    // First render of a brute-force scene with the plan left to the library: the first PROBE_SPP samples are a pass of their own,
-    // their path survival is read back (probe_plan) and decides the plan of all the other passes.  The film does not depend on how
-    // the samples are split into passes, nor on the plan.
-    constexpr uint32_t PROBE_SPP = 2;
-    const bool probe = brute && !s->plan_hint_valid && f->spp >= 8 * PROBE_SPP && s_pass >= PROBE_SPP &&
-                       !(f->flags & (PBRT_FILM_FUSE_PLAN_SET | PBRT_FILM_WALK_SET | PBRT_FILM_REGEN));
-    const uint32_t walk_from = (f->flags & PBRT_FILM_WALK_SET) ? ((f->flags >> 17) & 0xffu) : PBRT_DEFAULT_WALK_FROM;
-    // the arguments of every pass (key_mode 0: home -> (pixel of the rendered region, sample s_first + home / npix_r))
-    RadArgs base{};
+    r.plan_was_learnt = brute && s->plan_hint_valid;
+    r.plan = !brute ? 0u
+             : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? ((f->flags >> 8) & 0xffu)
+             : (s->plan_hint_valid ? s->plan_hint : PBRT_DEFAULT_FUSE_PLAN);
+    r.probe = brute && !s->plan_hint_valid && f->spp >= 8 * PROBE_SPP && r.s_pass >= PROBE_SPP && !(f->flags & PBRT_FILM_FUSE_PLAN_SET);
+    return PBRT_OK;
+}
+
+// Argument blocks: what every pass hands its bounce kernels (key_mode 0: home -> (pixel of the rendered region, sample s_first +
+// home / npix_r)) and the film gather.
+static int render_args(Render &r) {
+    pbrt_scene *s = r.s;
+    pbrt_ctx *c = r.c;
+    const pbrt_film_desc *f = r.f;
+    const uint32_t rw = r.rw, cap = r.cap;
+    RadArgs &base = r.base;
     base.sc = s->ds;
     if ((f->flags & PBRT_FILM_NO_OCCLUDER_PRUNING) && base.sc.occ_prims) {  // diagnostic: shadow segments walk every primitive
         base.sc.occ_prims = base.sc.prims;
@@ -1444,180 +1432,169 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
         base.sc.occ_runs = base.sc.prim_runs;
         base.sc.n_occ_runs = base.sc.n_prim_runs;
     }
-    base.cam = *cam;
-    base.Lhome = Lhome;
-    base.stats = segstats;
-    base.stat_stride = n_rows;
+    base.cam = *r.cam;
+    base.Lhome = r.Lhome;
+    base.stats = r.segstats;
+    base.stat_stride = r.n_rows;
     base.cap = cap;
     base.state_cap = cap;
     base.max_depth = f->max_depth;
     base.rr_depth = f->rr_depth;
     base.seed = f->seed;
     base.key_mode = 0;
-    base.rx0 = rx0;
-    base.ry0 = ry0;
+    base.rx0 = r.rx0;
+    base.ry0 = r.ry0;
     base.rw = rw;
-    base.npix_r = (uint32_t)npix_r;
-    base.tile_rows = rh & ~7u;
+    base.npix_r = (uint32_t)r.npix_r;
+    base.tile_rows = r.rh & ~7u;
     base.div_npix = make_fastdiv(base.npix_r);
     base.div_rw = make_fastdiv(rw);
     const std::initializer_list<uint32_t> probes = {0u, 1u, rw - 1, rw, rw + 1, base.npix_r - 1, base.npix_r, base.npix_r + 1, cap - 1, cap, 0xffffffffu};
     NEED(c, fastdiv_exact(base.div_npix, base.npix_r, probes) && fastdiv_exact(base.div_rw, rw, probes));
-    base.film_w = W;
-    base.film_h = H;
+    base.film_w = r.cam->film_w;
+    base.film_h = r.cam->film_h;
     base.lds_bytes = s->lds_bytes;
-    FilmArgs fa{};
-    fa.Lhome = Lhome;
-    fa.acc = acc;
+    FilmArgs &fa = r.fa;
+    fa.Lhome = r.Lhome;
+    fa.acc = r.acc;
     fa.cap = cap;
     fa.cx0 = f->crop_x;
     fa.cy0 = f->crop_y;
     fa.cw = f->crop_w;
     fa.ch = f->crop_h;
-    fa.rx0 = rx0;
-    fa.ry0 = ry0;
+    fa.rx0 = r.rx0;
+    fa.ry0 = r.ry0;
     fa.rw = rw;
-    fa.rh = rh;
-    fa.npix_r = (uint32_t)npix_r;
+    fa.rh = r.rh;
+    fa.npix_r = (uint32_t)r.npix_r;
     fa.tile_rows = base.tile_rows;
-    fa.film_w = W;
-    fa.film_h = H;
+    fa.film_w = r.cam->film_w;
+    fa.film_h = r.cam->film_h;
     fa.filter = f->filter;
     fa.seed = f->seed;
-    uint32_t s_step = s_pass;  // samples of a regular pass
-    for (uint32_t s0 = 0; s0 < f->spp; ++passes) {
-        const uint32_t sc = (probe && passes == 0) ? PROBE_SPP : std::min(s_step, f->spp - s0);
-        RadArgs a = base;
-        a.n_paths = (uint32_t)(npix_r * sc);
+    return PBRT_OK;
+}
+
+// The bounces of one pass of a brute-force scene: the launches of the fuse plan, each walking chain_len bounces.
+// The ping-pong path state (2 x 60 B per slot, 8 GB at 64 Mi paths) is only touched by a pass that needs more than one bounce
+// launch; with the plan that walks every bounce in one launch (the Cornell box) it is never written, so it is allocated per pass, for
+// the paths of THAT pass, when its plan says so.
+// A pass walks at most PASS_MAX_BOUNCES bounces whatever max_depth says (Mitsuba's -1 arrives as 0xffffffff) and drops the paths
+// that are still alive then.  An unbounded render relies on it: poll_live sums the n_own counters of a FULL pass, and a shorter
+// pass (the probe pass, a short last pass) leaves those of the regions it did not launch as an earlier call wrote them -- the
+// survivors of a bounded render, for one -- so the sum may never reach 0 although every path of the pass has ended.  The launches
+// up to the bound then find their regions empty.
+constexpr uint32_t PASS_MAX_BOUNCES = 256;
+static int brute_pass(Render &r, RadArgs a, uint32_t nseg_pass) {
+    pbrt_ctx *c = r.c;
+    const uint32_t max_depth = r.f->max_depth;
+    const bool one_launch = chain_len(r.plan, 0, max_depth) >= max_depth;
+    const size_t need = one_launch ? (size_t)r.region : (size_t)nseg_pass * r.region;
+    float *in = (float *)c->buf("stateA", need * N_STATE * 4), *out = (float *)c->buf("stateB", need * N_STATE * 4);
+    if (!in || !out) return PBRT_E_NOMEM;
+    a.state_cap = (uint32_t)need;
+    uint32_t *sin = r.segA, *sout = r.segB;
+    int rc;
+    if ((rc = r.timer.begin()) != 0) return rc;
+    for (uint32_t depth = 0; depth < max_depth && depth < PASS_MAX_BOUNCES;) {
+        // bounces this launch walks: 2 at the depths of the fuse plan (the last bounce of a path only looks for emitters, so it
+        // is never worth a launch slot of its own either)
+        const uint32_t nb = chain_len(r.plan, depth, max_depth);
+        a.depth = depth;
+        a.nb = nb;
+        a.in = in;
+        a.out = out;
+        a.seg_in = sin;
+        a.seg_out = sout;
+        if ((rc = launch_bounce(r.s, a, nseg_pass, depth == 0, nb)) != 0) return rc;
+        HIPCHK(c, hipGetLastError());
+        ++r.launches;
+        std::swap(in, out);
+        std::swap(sin, sout);
+        const uint32_t depth_before = depth;
+        depth += nb;
+        bool dead;
+        if ((rc = poll_live(c, max_depth, depth_before, depth, sin, r.n_own, &dead)) != 0) return rc;
+        if (dead) break;
+    }
+    return PBRT_OK;
+}
+
+// Pass loop: the samples in passes of s_pass (the probe pass first, if the plan is to be learnt), each through the bounces of its
+// launch structure and into the film accumulator.
+static int render_passes(Render &r) {
+    pbrt_ctx *c = r.c;
+    const pbrt_film_desc *f = r.f;
+    int rc;
+    uint32_t s_step = r.s_pass;  // samples of a regular pass
+    for (uint32_t s0 = 0; s0 < f->spp; ++r.passes) {
+        const bool probing = r.probe && r.passes == 0;
+        const uint32_t sc = probing ? PROBE_SPP : std::min(s_step, f->spp - s0);
+        RadArgs a = r.base;
+        a.n_paths = (uint32_t)(r.npix_r * sc);
         a.s_first = f->sample_offset + s0;
-        const uint32_t nseg_pass = div_up(a.n_paths, REGION);
-        if (!wavefront) {  // state for this pass: none if one launch walks all its bounces
-            const bool one_launch = brute && !(f->flags & (PBRT_FILM_WALK_SET | PBRT_FILM_REGEN)) &&
-                                    chain_len(plan, 0, f->max_depth) >= f->max_depth;
-            const size_t need = one_launch ? (size_t)REGION : (size_t)nseg_pass * REGION;
-            stA = (float *)c->buf("stateA", need * N_STATE * 4);
-            stB = (float *)c->buf("stateB", need * N_STATE * 4);
-            if (!stA || !stB) return PBRT_E_NOMEM;
-            a.state_cap = (uint32_t)need;
+        const uint32_t nseg_pass = div_up(a.n_paths, r.region);
+        if (r.wavefront) {
+            if ((rc = r.timer.begin()) != 0) return rc;
+            rc = wf_bounces(r.s, wf_args(a), r.wfb, r.wfp, nseg_pass, true, &r.launches);
+        } else {
+            rc = brute_pass(r, a, nseg_pass);
         }
-        float *in = stA, *out = stB;
-        uint32_t *sin = segA, *sout = segB;
-        if (wavefront) {
-            if ((rc = timer.begin()) != 0) return rc;
-            if ((rc = wf_bounces(s, wf_args(a), wfb, wfp, nseg_pass, true, &launches)) != 0) return rc;
-        }
-#ifdef PBRT_DIAG
-        else if (brute && (f->flags & PBRT_FILM_REGEN)) {
-            // persistent waves with path regeneration (k_regen): one launch per pass, as many workgroups as the GPU holds at once
-            int per_cu = 0;
-            const void *fn = s->accel_kernel == ACCEL_K_BRUTE ? reinterpret_cast<const void *>(&k_regen<ACCEL_K_BRUTE>)
-                                                              : reinterpret_cast<const void *>(&k_regen<ACCEL_K_BRUTE_BIG>);
-            HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, REGEN_WG, 0));
-            const uint32_t wpw = REGEN_WG / 64;
-            uint32_t grid = (uint32_t)std::max(per_cu, 1) * (uint32_t)c->n_cu;
-            grid = std::min(grid, std::max(1u, n_rows / wpw));            // one statistics row per wave
-            grid = std::min(grid, div_up(a.n_paths, REGEN_WG));
-            a.depth = 0;
-            if ((rc = timer.begin()) != 0) return rc;
-            if (s->accel_kernel == ACCEL_K_BRUTE)
-                hipLaunchKernelGGL(k_regen<ACCEL_K_BRUTE>, dim3(grid), dim3(REGEN_WG), 0, st, a);
-            else
-                hipLaunchKernelGGL(k_regen<ACCEL_K_BRUTE_BIG>, dim3(grid), dim3(REGEN_WG), 0, st, a);
-            HIPCHK(c, hipGetLastError());
-            ++launches;
-        }
-#endif
-        else
-        for (uint32_t depth = 0; depth < f->max_depth;) {
-            // bounces this launch walks: 2 at the depths of the fuse plan (brute-force kernels; the last bounce of a
-            // path only looks for emitters, so it is never worth a launch slot of its own either)
-            const uint32_t nb = brute ? chain_len(plan, depth, f->max_depth) : 1u;
-            a.depth = depth;
-            a.nb = nb;
-            a.in = in;
-            a.out = out;
-            a.seg_in = sin;
-            a.seg_out = sout;
-#ifdef PBRT_DIAG
-            if (repack && depth >= 2) {
-                // Only the regions THIS pass launched take part: a short last pass (spp not a multiple of the pass size)
-                // launches nseg_pass < nseg workgroups, so paths dealt to regions >= nseg_pass would never be traced, and
-                // the counters of those regions are left over from the previous pass.
-                const uint32_t owners = rad_owners_per_region(s->accel_kernel), wreg = REGION / owners;
-                const uint32_t n_own_pass = nseg_pass * owners;
-                hipLaunchKernelGGL(k_scan_owners, dim3(1), dim3(1024), 0, st, sin, n_own_pass, wreg, owners, (uint32_t)c->n_cu, offs,
-                                   segC, quota);
-                hipLaunchKernelGGL(k_repack_copy, dim3(n_own_pass), dim3(256), 0, st, in, stC, sin, offs, quota, n_own_pass, wreg);
-                a.in = stC;
-                a.seg_in = segC;
-            }
-#endif
-            if (depth == 0 && (rc = timer.begin()) != 0) return rc;
-            const bool walk = brute && depth >= walk_from;  // this launch walks every remaining bounce of the pass
-#ifdef PBRT_DIAG
-            const uint32_t pair_m = (brute && depth == 0 && !walk) ? pair_merge_bounce(sw.pair_merge, plan, f->max_depth) : 0u;
-            if (pair_m) {  // the whole path in one launch, two tiles per wave
-                a.merge_at = pair_m;
-                const uint32_t g2 = div_up(a.n_paths, 2u * SEG_BRUTE);
-                if (s->accel_kernel == ACCEL_K_BRUTE)
-                    hipLaunchKernelGGL(k_chain_pair<ACCEL_K_BRUTE>, dim3(g2), dim3(SEG_BRUTE), 0, st, a);
-                else
-                    hipLaunchKernelGGL(k_chain_pair<ACCEL_K_BRUTE_BIG>, dim3(g2), dim3(SEG_BRUTE), 0, st, a);
-            } else
-#endif
-            if ((rc = launch_bounce(s, a, nseg_pass, depth == 0, nb, walk)) != 0) return rc;
-            HIPCHK(c, hipGetLastError());
-            ++launches;
-            if (walk) break;
-            std::swap(in, out);
-            std::swap(sin, sout);
-            const uint32_t depth_before = depth;
-            depth += nb;
-            bool dead;
-            if ((rc = poll_live(c, f->max_depth, depth_before, depth, sin, n_own, &dead)) != 0) return rc;
-            if (dead) break;
-        }
-        if ((rc = timer.end()) != 0) return rc;
-        fa.s_first = a.s_first;
-        fa.s_count = sc;
-        film_accum(c, fa);
+        if (rc) return rc;
+        if ((rc = r.timer.end()) != 0) return rc;
+        r.fa.s_first = a.s_first;
+        r.fa.s_count = sc;
+        film_accum(c, r.fa);
         HIPCHK(c, hipGetLastError());
         s0 += sc;
-        if (probe && passes == 0) {  // learn the plan from the probe pass
-            if ((rc = probe_plan(c, segstats, n_rows, stat_rows, dstats, f->max_depth, &plan)) != 0) return rc;
+        if (probing) {  // learn the plan from the probe pass
+            if ((rc = probe_plan(c, r.segstats, r.n_rows, r.stat_rows, r.dstats, f->max_depth, &r.plan)) != 0) return rc;
             const uint32_t rem = f->spp - s0;
-            s_step = div_up(rem, div_up(rem, s_pass));  // equal passes for what is left
+            s_step = div_up(rem, div_up(rem, r.s_pass));  // equal passes for what is left
         }
     }
-    hipLaunchKernelGGL(k_film_resolve, dim3(div_up(film_px, 256)), dim3(256), 0, st, acc, (float *)d_out, (uint32_t)film_px,
+    return PBRT_OK;
+}
+
+// Finish: the film resolved into d_out, the statistics rows reduced and read back with the guard words, pbrt_stats filled (the plan
+// that ran and where it came from, the byte model), and the plan this scene's next render starts from.
+static int render_finish(Render &r) {
+    pbrt_scene *s = r.s;
+    pbrt_ctx *c = r.c;
+    const pbrt_film_desc *f = r.f;
+    const bool wavefront = r.wavefront;
+    const uint32_t n_rows = r.n_rows;
+    hipStream_t st = c->stream;
+    int rc;
+    hipLaunchKernelGGL(k_film_resolve, dim3(div_up(r.film_px, 256)), dim3(256), 0, st, r.acc, (float *)r.d_out, (uint32_t)r.film_px,
                        (uint32_t)((f->flags & PBRT_FILM_RAW_ACCUM) ? 1 : 0));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev1, st));
     unsigned long long hstats[2 + 2 * MAX_DEPTH_STATS];
-    hipLaunchKernelGGL(k_reduce_stats, dim3(stat_rows, REDUCE_SLICES), dim3(256), 0, st, segstats, n_rows, (size_t)n_rows, dstats);
-    if (hit_rows)
-        hipLaunchKernelGGL(k_reduce_stats, dim3(hit_rows, REDUCE_SLICES), dim3(256), 0, st, segstats + (size_t)HIT_ROW0 * n_rows, n_rows,
-                           (size_t)n_rows, dstats + HIT_ROW0);
+    hipLaunchKernelGGL(k_reduce_stats, dim3(r.stat_rows, REDUCE_SLICES), dim3(256), 0, st, r.segstats, n_rows, (size_t)n_rows, r.dstats);
+    if (r.hit_rows)
+        hipLaunchKernelGGL(k_reduce_stats, dim3(r.hit_rows, REDUCE_SLICES), dim3(256), 0, st, r.segstats + (size_t)HIT_ROW0 * n_rows, n_rows,
+                           (size_t)n_rows, r.dstats + HIT_ROW0);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hstats, dstats, sizeof hstats, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hstats, r.dstats, sizeof hstats, hipMemcpyDeviceToHost, st));
     uint32_t hguard[WF_GUARD_WORDS] = {0};
     if (wavefront && (rc = wf_guard_fetch(c, hguard)) != 0) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     if (wavefront && (rc = wf_check_guard(c, hguard)) != 0) return rc;
-    if ((rc = call_stats(c, hstats, npix_r * f->spp, launches, passes, true, timer.n_ev)) != 0) return rc;
+    if ((rc = call_stats(c, hstats, r.npix_r * f->spp, r.launches, r.passes, true, r.timer.n_ev)) != 0) return rc;
     pbrt_stats &S = c->stats;
-    S.fuse_plan = plan;
+    S.fuse_plan = r.plan;
     S.plan_source = wavefront ? PBRT_PLAN_STREAMS
                     : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? PBRT_PLAN_CALLER
-                    : probe ? PBRT_PLAN_PROBED
-                    : plan_was_learnt ? PBRT_PLAN_LEARNT : PBRT_PLAN_DEFAULT;
-    S.pass_paths = (uint64_t)npix_r * s_pass;
-    if (brute && hstats[2] > 0) {  // remember what this scene's paths do for the next render of it
+                    : r.probe ? PBRT_PLAN_PROBED
+                    : r.plan_was_learnt ? PBRT_PLAN_LEARNT : PBRT_PLAN_DEFAULT;
+    S.pass_paths = (uint64_t)r.npix_r * r.s_pass;
+    if (r.brute && hstats[2] > 0) {  // remember what this scene's paths do for the next render of it
         s->plan_hint = plan_from_survival(hstats + 2, (uint32_t)std::min<uint64_t>(f->max_depth, MAX_DEPTH_STATS));
         s->plan_hint_valid = true;
     }
     uint64_t tot, bb;
-    radiance_model_bytes(hstats + 2, MAX_DEPTH_STATS, S.samples, film_px, passes, plan, f->max_depth,
+    radiance_model_bytes(hstats + 2, MAX_DEPTH_STATS, S.samples, r.film_px, r.passes, r.plan, f->max_depth,
                          wavefront ? hstats + HIT_ROW0 : nullptr, &tot, &bb);
     if (wavefront) {
         tot -= bb;
@@ -1626,14 +1603,31 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
         tot += bb;
         S.trace_model_bytes = trb;
     }
-    if (brute && (f->flags & PBRT_FILM_REGEN)) {  // k_regen keeps the paths in registers: only the radiance records are written
-        tot -= bb;
-        bb = S.samples * 12;
-        tot += bb;
-    }
     S.model_bytes = tot;
     S.bounce_model_bytes = bb;
     return PBRT_OK;
+}
+
+#ifdef PBRT_DIAG
+#include "diag_driver.h"  // diag_selected, diag_render: the launch structures only the diagnostic build carries
+#endif
+
+static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_desc *f, void *d_out) {
+    Render r{s, s->ctx, cam, f, d_out};
+    int rc;
+    if ((rc = render_check(r)) != 0) return rc;
+    // launch structures that lost their A/B live in the diagnostic build only (make -C csrc diag -> libpbrt_hip_diag.so)
+#ifdef PBRT_DIAG
+    if (diag_selected(r)) return diag_render(r);
+#else
+    if ((f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || (!r.brute && (f->flags & PBRT_FILM_NO_HIT_POOL)))
+        return r.c->fail(PBRT_E_UNSUPPORTED, "PBRT_FILM_REGEN / PBRT_FILM_WALK_FROM / PBRT_FILM_NO_HIT_POOL select diagnostic launch "
+                                             "structures: build libpbrt_hip_diag.so (make -C csrc diag)");
+#endif
+    if ((rc = render_buffers(r)) != 0) return rc;
+    if ((rc = render_args(r)) != 0) return rc;
+    if ((rc = render_passes(r)) != 0) return rc;
+    return render_finish(r);
 }
 
 #ifdef PBRT_BVH_PROBE  // diagnostic builds only (tools/bvh_probe.py); not part of the ABI
@@ -1679,8 +1673,7 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
     if (n == 0) return PBRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rcs = ctx_settle(c)) return rcs;
-    int rc = set_lds_attr(s);
-    if (rc) return rc;
+    int rc;
     ++c->call_seq;
     const Switches sw = read_switches();
     const uint32_t REGION = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
@@ -1860,7 +1853,10 @@ static uint32_t us_kernel_quirks(const UsArgs &a, bool generic) {
 static int launch_us(pbrt_scene *s, const UsArgs &a, uint32_t nseg, bool first, bool generic, bool convex) {
     const bool emit = a.p.primary == PBRT_US_PRIMARY_EMITTER;  // primary rays from CustomEmitter.sample_ray, echoes times the ray's weight
     const int tab = (a.first_hit && a.first_rx) ? 1 : (!a.first_hit && !a.first_rx) ? 0 : -1;
-    const UsKern k = us_bounce_kernel(s, first, emit, us_kernel_quirks(a, generic), tab, convex);
+    UsKern k = us_bounce_kernel(s, first, emit, us_kernel_quirks(a, generic), tab, convex);
+#ifdef PBRT_DIAG
+    if (!k && !emit) k = diag_us_bvh_kernel(s, first, convex);
+#endif
     if (!k && emit)
         return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: emitter primary rays on BVH scenes run as streams (us_wf_pass)");
     if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_us: no fused ultrasound bounce for accelerator %d in this build", s->accel_kernel);
@@ -1975,8 +1971,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
         NEED(c, E.number_of_elements == p->n_elements);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = set_lds_attr(s);
-    if (rc) return rc;
+    int rc;
     const Switches sw = read_switches();
     const uint32_t NA = p->n_angles, NE = p->n_elements, T = p->time_samples;
     const uint32_t n_rays = NA * NE;
@@ -2017,7 +2012,7 @@ static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32
     const bool bvh_scene = s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS;
     bool streams = bvh_scene;
 #ifdef PBRT_DIAG
-    streams = streams && !sw.us_fused_bvh;
+    if ((rc = diag_us_fused_bvh(s, &streams)) != 0) return rc;
 #endif
     // paths in flight per pass.  Streams: 2 x 10 launches per pass whatever is still alive, so passes as large as the radiance
     // streams take (wf_default_pass_paths; the shared trace / shade workspace).  The fused kernels: the pass buffers must fit the
