@@ -199,6 +199,8 @@ typedef struct pbrt_film_desc {
 #define PBRT_FILM_NO_OCCLUDER_PRUNING 4u /* diagnostic: next-event shadow segments of brute-force scenes walk EVERY primitive \
                                            instead of the occluder list (DESIGN D11: primitives on the scene's convex hull \
                                            and the lone area light are left out of it) -- same film if the pruning is right */
+#define PBRT_FILM_NO_TILE_CULL 0x20u /* diagnostic: the camera rays of brute-force scenes walk EVERY primitive instead of the ones the \
+                                        keep word of their 8 x 8 pixel tile leaves (csrc/tile_cull.h) -- same film if the culling is right */
 
 /* ---- ultrasound (acoustic) mode ----------------------------------------------------------- */
 /* Parameter block of UltraIntegrator (CustomIntegrator.py:13-48) plus the sensor transform

@@ -341,37 +341,42 @@ DEV bool brute_take(BruteBest &b, bool ok, float num, float den, float us, float
     b.bp = better ? i : b.bp;
     return false;
 }
+// one triangle (TRI) or parallelogram record: primitive i of the list
+template <bool ANY, bool TRI>
+DEV bool brute_planar_one(const pbrt_prim *p, uint32_t i, V3 o, V3 d, float tmax, BruteBest &b) {
+    typedef float __attribute__((ext_vector_type(8))) f32x8;
+    const f32x8 g = load_uniform<f32x8>(p->g);
+    const float g8 = load_uniform<float>(p->g + 8);
+    V3 v0 = {g[0], g[1], g[2]}, e1 = {g[3], g[4], g[5]}, e2 = {g[6], g[7], g8};
+    V3 pvec = cross(d, e2);
+    float det = dot(e1, pvec);
+    V3 tvec = o - v0;
+    V3 qvec = cross(tvec, e1);
+    float us = dot(tvec, pvec);
+    float vs = dot(d, qvec);
+    float ts = dot(e2, qvec);
+    const bool neg = det < 0.0f;
+    det = neg ? -det : det;
+    us = neg ? -us : us;
+    vs = neg ? -vs : vs;
+    ts = neg ? -ts : ts;
+    // (us >= 0 & vs >= 0 & ts >= 0) folded into min3: two compares less per primitive.  min3 drops a NaN (a ray with an
+    // infinite component), which the oracle's three compares reject; every NaN fails one of the tests that follow --
+    // ts in the range test, us or vs in the sum of the triangle, in its own upper bound for the parallelogram (which
+    // is why that bound is two compares and not max(us, vs) <= det) -- so the truth value is the oracle's for every input
+    bool ok = (det > 0.0f) & (fminf(fminf(us, vs), ts) >= 0.0f) & (ts <= tmax * det);
+    if (TRI)
+        ok = ok & (us + vs <= det);
+    else
+        ok = ok & (us <= det) & (vs <= det);
+    return brute_take<ANY>(b, ok, ts, det, us, vs, i);
+}
 // cnt >= 1 records of triangles (TRI) or parallelograms from p on; p and the primitive index i end behind the run
 template <bool ANY, bool TRI>
 DEV bool brute_planar_run(const pbrt_prim *&p, uint32_t &i, uint32_t cnt, V3 o, V3 d, float tmax, BruteBest &b) {
-    typedef float __attribute__((ext_vector_type(8))) f32x8;
     const pbrt_prim *const pend = p + cnt;
     do {
-        const f32x8 g = load_uniform<f32x8>(p->g);
-        const float g8 = load_uniform<float>(p->g + 8);
-        V3 v0 = {g[0], g[1], g[2]}, e1 = {g[3], g[4], g[5]}, e2 = {g[6], g[7], g8};
-        V3 pvec = cross(d, e2);
-        float det = dot(e1, pvec);
-        V3 tvec = o - v0;
-        V3 qvec = cross(tvec, e1);
-        float us = dot(tvec, pvec);
-        float vs = dot(d, qvec);
-        float ts = dot(e2, qvec);
-        const bool neg = det < 0.0f;
-        det = neg ? -det : det;
-        us = neg ? -us : us;
-        vs = neg ? -vs : vs;
-        ts = neg ? -ts : ts;
-        // (us >= 0 & vs >= 0 & ts >= 0) folded into min3: two compares less per primitive.  min3 drops a NaN (a ray with an
-        // infinite component), which the oracle's three compares reject; every NaN fails one of the tests that follow --
-        // ts in the range test, us or vs in the sum of the triangle, in its own upper bound for the parallelogram (which
-        // is why that bound is two compares and not max(us, vs) <= det) -- so the truth value is the oracle's for every input
-        bool ok = (det > 0.0f) & (fminf(fminf(us, vs), ts) >= 0.0f) & (ts <= tmax * det);
-        if (TRI)
-            ok = ok & (us + vs <= det);
-        else
-            ok = ok & (us <= det) & (vs <= det);
-        const bool stop = brute_take<ANY>(b, ok, ts, det, us, vs, i);
+        const bool stop = brute_planar_one<ANY, TRI>(p, i, o, d, tmax, b);
         ++p;
         ++i;
         if (ANY && stop) return true;
@@ -409,15 +414,52 @@ DEV bool brute_curved_run(const pbrt_prim *&p, uint32_t &i, uint32_t cnt, V3 o, 
 // because the cone branch costs the
 // 64-VGPR brute-force radiance kernel 9 VGPRs and puts it into scratch (measured: 54 / 60 -> 63 VGPRs + 4 spilled);
 // small scenes with a cone or a cylinder run the ACCEL_K_BRUTE_BIG variant instead (pbrt_api.hip).
+//
+// keep: the closest-hit walk of a list of <= 32 primitives without quadrics may leave out the primitives whose bit is clear: the
+// keep word of a camera tile (csrc/tile_cull.h; kernels_radiance.h k_tile_keep), wave-uniform in an SGPR.  All ones (every other
+// walk, as a constant: the masked loops then fold away) goes straight to the plain loops and pays nothing.  The masked loops visit
+// the set bits of a planar run in rising order -- a scalar find-first-set per kept primitive, nothing per skipped one, a run
+// without a set bit is stepped over whole -- so indices, list order and the tie rule are those of the plain walk.  A run of spheres
+// has no masked loop of its own (a second copy of sphere_hit would be one more IEEE division in the kernel): without a set bit it
+// is stepped over, with one the plain loops take the walk over from that run on, and test what is left of the list unmasked.
 template <bool ANY, bool SEGMENT = false, bool CONES = true>
-DEV bool brute_intersect(const DevScene &sc, V3 o, V3 d, float tmax, Hit *h) {
+DEV bool brute_intersect(const DevScene &sc, V3 o, V3 d, float tmax, Hit *h, uint32_t keep = 0xffffffffu) {
     BruteBest b = {0.0f, 1.0f, 0.0f, 0.0f, 0xffffffffu, false};
     constexpr bool OCC = ANY && SEGMENT;
     const pbrt_prim *p = OCC ? sc.occ_prims : sc.prims;
     const uint32_t *runs = OCC ? sc.occ_runs : sc.prim_runs;
     const uint32_t n_runs = (uint32_t)__builtin_amdgcn_readfirstlane((int)(OCC ? sc.n_occ_runs : sc.n_prim_runs));
-    uint32_t i = 0;
-    for (uint32_t r = 0; r < n_runs; ++r) {
+    uint32_t i = 0, r = 0;
+    if (!ANY && !CONES && keep != 0xffffffffu) {
+        for (; r < n_runs && i < 32u; ++r) {
+            const uint32_t w = load_uniform<uint32_t>(runs + r);
+            const uint32_t cnt = w >> 2, cls = w & 3u;
+            uint32_t bits = keep >> i;
+            if (cnt < 32u) bits &= (1u << cnt) - 1u;
+            auto next = [&bits]() {  // the lowest set bit, taken
+                const uint32_t k = (uint32_t)__builtin_ctz(bits);
+                bits &= bits - 1u;
+                return k;
+            };
+            if (bits == 0u) {  // nothing of this run is seen
+            } else if (cls == PRIM_RUN_QUAD) {
+                do {
+                    const uint32_t k = next();
+                    brute_planar_one<false, false>(p + k, i + k, o, d, tmax, b);
+                } while (bits);
+            } else if (cls == PRIM_RUN_TRI) {
+                do {
+                    const uint32_t k = next();
+                    brute_planar_one<false, true>(p + k, i + k, o, d, tmax, b);
+                } while (bits);
+            } else {
+                break;
+            }
+            p += cnt;
+            i += cnt;
+        }
+    }
+    for (; r < n_runs; ++r) {
         const uint32_t w = load_uniform<uint32_t>(runs + r);  // wave-uniform: count << 2 | class
         const uint32_t cnt = w >> 2, cls = w & 3u;
         bool stop;

@@ -14,6 +14,7 @@
 // the path-state data path; paths that end write their radiance once to Lhome[home].
 #pragma once
 #include "device_scene.h"
+#include "tile_cull.h"
 
 // slots per compaction segment == threads per workgroup (seg_threads(ACCEL) below).  Measured on MI355X, cbox
 // 512^2 x 256 spp (current kernel): 128 / 256 / 512 / 1024 -> 10.5 / 9.0 / 8.6 / 9.9 ms; the LDS-staged BVH wants
@@ -131,6 +132,8 @@ struct RadArgs {
     // key mode 1 (Integrator.sample on caller rays): key = (index_offset + home, sample_index)
     uint32_t index_offset, sample_index;
     uint32_t lds_bytes;  // ACCEL_K_BVH_LDS: bytes of nodes + prims + ids staged per workgroup
+    // key mode 0, ACCEL_K_BRUTE, npix_r % 64 == 0: the keep words of the camera tiles, [npix_r / 64] (k_tile_keep); nullptr: none
+    const uint32_t *tile_keep;
 };
 
 // Path state is tiled SoA: 64 consecutive slots (one wave) form a tile of N_STATE rows x 64 lanes = 3840 contiguous
@@ -225,9 +228,9 @@ __host__ __device__ constexpr uint32_t ilog2_c(uint32_t v) { return v <= 1u ? 0u
 // SEGMENT: the ray is a segment between two points of the scene (next-event shadow ray): brute-force
 // scenes then only walk the primitives that can occlude such a segment (DevScene::occ_prims).
 template <int ACCEL, bool ANY, bool SEGMENT = false>
-DEV bool scene_intersect(const DevScene &sc, const LdsScene &ls, V3 o, V3 d, float tmax, Hit *h) {
+DEV bool scene_intersect(const DevScene &sc, const LdsScene &ls, V3 o, V3 d, float tmax, Hit *h, uint32_t keep = 0xffffffffu) {
     if (ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG)
-        return brute_intersect<ANY, SEGMENT, ACCEL != ACCEL_K_BRUTE>(sc, o, d, tmax, h);
+        return brute_intersect<ANY, SEGMENT, ACCEL != ACCEL_K_BRUTE>(sc, o, d, tmax, h, keep);
     if (ACCEL == ACCEL_K_BVH_GLOBAL) return bvh_intersect<ANY>(TreeGlobal{sc.nodes, sc.lprims}, sc.prims, ls.stk, o, d, tmax, h);
     return bvh_intersect<ANY>(ls.tree, sc.prims, ls.stk, o, d, tmax, h);
 }
@@ -378,16 +381,17 @@ DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka
 // One bounce of one path (the body shared by k_bounce and k_walk): closest hit, the surface interaction, shade_step with its
 // shadow segment traced at once.  Returns whether the path goes on; a path that ends writes its radiance to Lhome[home].
 // HAVE_HIT: the closest hit was found earlier (k_bounce_pool) and comes in through h_in; the step starts at the shading.
+// keep: the primitives the closest-hit walk may leave out (device_scene.h brute_intersect); the shadow walk sees them all.
 // GLOSSY: as shade_step.  Only k_bounce of the brute-force scenes has instances without it: every other kernel that comes through
 // here (the diagnostic build's launch structures, on the _BIG tables) always carries the arms.
 template <int ACCEL, bool HAVE_HIT = false, bool GLOSSY = ACCEL != ACCEL_K_BRUTE>
 DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsrc r_L, uint32_t depth, uint32_t ka, uint32_t kb,
                      uint32_t home, float tmax, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, bool &did_seg,
-                     bool &did_shadow, const Hit *h_in = nullptr) {
+                     bool &did_shadow, const Hit *h_in = nullptr, uint32_t keep = 0xffffffffu) {
     bool survive = false;
     Hit h;
     if (HAVE_HIT) h = *h_in;
-    if (HAVE_HIT || scene_intersect<ACCEL, false>(a.sc, ls, o, d, tmax, &h)) {
+    if (HAVE_HIT || scene_intersect<ACCEL, false>(a.sc, ls, o, d, tmax, &h, keep)) {
         did_seg = true;
         const pbrt_prim &P = tb.prims_by_slot[h.slot];
         const SI si = make_si<ACCEL != ACCEL_K_BRUTE>(P, o, d, h.t, h.u, h.v, a.sc.vnormals, h.slot);
@@ -571,6 +575,14 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
     if (ACCEL == ACCEL_K_BRUTE && !FIRST && !DYN && it0 == 0) fill_tables_lds(a.sc, tab_lds, live_threads);
     if (alive && !FIRST) path_key<TILED>(a, home, &ka, &kb, &px, &py);
     bool live = alive;                        // the lane still carries a path
+    // the wave's camera rays are the 8 x 8 tile of one sample (or, on a region whose width is no multiple of 8, a few tiles): the
+    // closest-hit walk of bounce 0 leaves out what the keep word of its 64 region indices rules out (one scalar load)
+    uint32_t keep = 0xffffffffu;
+    if (FIRST && ACCEL == ACCEL_K_BRUTE && !DYN && a.tile_keep) {
+        const uint32_t home0 = base + ((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u);
+        const uint32_t blk = (home0 - udiv_fast(home0, a.div_npix) * a.npix_r) >> 6;
+        keep = load_uniform<uint32_t>(a.tile_keep + min(blk, (a.npix_r >> 6) - 1u));
+    }
     uint32_t nseg_w = 0, nshd_w = 0, nmid_w = 0, nmid_hi_w = 0;  // wave-uniform counts over the launch's bounces
 #pragma unroll 1
     for (uint32_t bounce = 0; bounce < nb_run; ++bounce) {
@@ -596,8 +608,10 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
             if (probe == 12345.678f) o.x = probe;  // never true; keeps the chain alive
         }
 #endif
-        survive = bounce_step<ACCEL, false, GL>(a, tb, ls, r_L, depth, ka, kb, home, tmax, o, d, thr, L, eta, prev_pdf, did_seg, did_shadow);
+        survive = bounce_step<ACCEL, false, GL>(a, tb, ls, r_L, depth, ka, kb, home, tmax, o, d, thr, L, eta, prev_pdf, did_seg, did_shadow,
+                                                nullptr, keep);
     }
+    keep = 0xffffffffu;  // the later bounces of the launch are no camera rays
     live = survive;
     nseg_w += (uint32_t)__popcll(__ballot(did_seg));
     nshd_w += (uint32_t)__popcll(__ballot(did_shadow));
@@ -696,6 +710,43 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
                 row[(2 + min(a.depth + k, (uint32_t)MAX_DEPTH_STATS - 1)) * stride] += n_on;
             }
     }
+}
+
+// The keep table of a radiance render of an ACCEL_K_BRUTE scene (RadArgs::tile_keep): word b = which of the <= 32 primitives the
+// camera rays of region indices [64 b, 64 b + 63] can meet, bit i = primitive i of sc.prims (tile_cull.h decides, in double; a
+// cleared bit is a proof that the float test rejects).  The rectangle of a block is the bounding box of its 64 pixels through
+// the inverse of region_index: one 8 x 8 tile when the region's width is a multiple of 8, a few tiles or a piece of the row-major
+// tail otherwise.  One thread per word; a render runs it once, ahead of its first pass (microseconds).
+struct TileKeepArgs {
+    const pbrt_prim *prims;
+    uint32_t n_prims;  // <= 32
+    pbrt_camera cam;
+    uint32_t rx0, ry0, rw, tile_rows, n_blocks;
+    FastDiv div_rw;
+    uint32_t *keep;  // [n_blocks]
+};
+__global__ __launch_bounds__(64) void k_tile_keep(const TileKeepArgs a) {
+    const uint32_t blk = blockIdx.x * 64u + threadIdx.x;
+    if (blk >= a.n_blocks) return;
+    uint32_t x0 = 0xffffffffu, y0 = 0xffffffffu, x1 = 0, y1 = 0;
+    for (uint32_t k = 0; k < 64u; ++k) {
+        const uint32_t pr = blk * 64u + k;  // as path_key<TILED>
+        const bool tiled = pr < a.tile_rows * a.rw;
+        const uint32_t num = tiled ? pr >> 3 : pr;
+        const uint32_t q = udiv_fast(num, a.div_rw);
+        const uint32_t rx = num - q * a.rw, ry = tiled ? (q << 3) + (pr & 7u) : q;
+        x0 = min(x0, rx);
+        x1 = max(x1, rx);
+        y0 = min(y0, ry);
+        y1 = max(y1, ry);
+    }
+    uint32_t word = 0;
+    for (uint32_t i = 0; i < a.n_prims && i < 32u; ++i) {
+        const pbrt_prim P = load_prim_uniform(a.prims + i);
+        if (tile_cull_keep(a.cam, a.rx0 + x0, a.ry0 + y0, a.rx0 + x1, a.ry0 + y1, P)) word |= 1u << i;
+    }
+    word |= a.n_prims < 32u ? ~0u << a.n_prims : 0u;  // bits without a primitive stay set: a full word means "nothing culled"
+    a.keep[blk] = word;
 }
 
 // column sums of the per-segment statistics: out[k] += sum_seg stats[k][seg].  grid (rows, REDUCE_SLICES): every block sums

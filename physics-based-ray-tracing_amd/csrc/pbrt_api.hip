@@ -3,6 +3,7 @@
 // uploaded once and stay resident; every entry point is synchronous on return.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -92,6 +93,14 @@ struct pbrt_ctx {
     uint32_t env_taps_n = 0;  // column length the context's tap table (workspace "env_taps") was made for ...
     uint64_t env_taps_gen = 0;  // ... in this allocation of it
     uint64_t wf_guard_gen = 0;  // the allocation of workspace "wf_guard" that was cleared
+    // the keep words of the camera tiles (workspace "tile_keep") as the last render of a brute-force scene left them: a render of the
+    // same scene with the same camera and region that finds the same allocation (its generation; 0: none) skips k_tile_keep -- a
+    // progressive render calls with nothing but the sample offset changed, and the kernel is 20 us of a 6 ms Cornell box step
+    struct TileKeepKey {
+        uint64_t gen = 0, scene = 0;
+        pbrt_camera cam{};
+        uint32_t rx0 = 0, ry0 = 0, rw = 0, rh = 0;
+    } tile_keep_key;
     bool img_event(int i) { return img_ev[i] || hipEventCreate(&img_ev[i]) == hipSuccess; }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint32_t lds_limit = 0;
@@ -155,6 +164,7 @@ struct pbrt_scene {
     // fuse plan learnt from the path survival of the last render of this scene (brute-force kernels; 0: none yet)
     uint32_t plan_hint = 0;
     bool plan_hint_valid = false;
+    uint64_t serial = 0;  // unique per scene of the process (never 0): what a context remembers a scene by (pbrt_ctx::tile_keep_key)
 };
 
 #define HIPCHK(ctx, call)                                                                              \
@@ -482,6 +492,8 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
             if (!std::isfinite(d->vertex_normals[i])) return c->fail(PBRT_E_INVALID, "vertex_normals: entry %zu is not finite", i);
     HIPCHK(c, hipSetDevice(c->device));
     pbrt_scene *s = new pbrt_scene();
+    static std::atomic<uint64_t> scene_serial{0};
+    s->serial = ++scene_serial;
     s->ctx = c;
     int rc;
     const pbrt_prim *d_prims_by_id = nullptr;
@@ -1454,6 +1466,39 @@ static int render_args(Render &r) {
     base.film_w = r.cam->film_w;
     base.film_h = r.cam->film_h;
     base.lds_bytes = s->lds_bytes;
+    // the keep words of the camera tiles (kernels_radiance.h k_tile_keep): the waves of the first bounce are whole blocks of 64 region
+    // indices only if the region's pixel count is a multiple of 64; rebuilt per render (camera and crop are the call's)
+    base.tile_keep = nullptr;
+    if (s->accel_kernel == ACCEL_K_BRUTE && s->ds.n_prims <= 32 && base.npix_r % 64 == 0 && !(f->flags & PBRT_FILM_NO_TILE_CULL)) {
+        TileKeepArgs ta;
+        ta.prims = s->ds.prims;
+        ta.n_prims = s->ds.n_prims;
+        ta.cam = *r.cam;
+        ta.rx0 = r.rx0;
+        ta.ry0 = r.ry0;
+        ta.rw = rw;
+        ta.tile_rows = base.tile_rows;
+        ta.n_blocks = base.npix_r / 64;
+        ta.div_rw = base.div_rw;
+        ta.keep = (uint32_t *)c->buf("tile_keep", (size_t)ta.n_blocks * 4);
+        if (!ta.keep) return PBRT_E_NOMEM;
+        pbrt_ctx::TileKeepKey &key = c->tile_keep_key;
+        const uint64_t gen = c->work.generation("tile_keep");
+        const bool same = key.gen == gen && key.scene == s->serial && memcmp(&key.cam, r.cam, sizeof(pbrt_camera)) == 0 && key.rx0 == r.rx0 &&
+                          key.ry0 == r.ry0 && key.rw == rw && key.rh == r.rh;
+        if (!same) {
+            hipLaunchKernelGGL(k_tile_keep, dim3(div_up(ta.n_blocks, 64)), dim3(64), 0, c->stream, ta);
+            HIPCHK(c, hipGetLastError());
+            key.gen = gen;
+            key.scene = s->serial;
+            key.cam = *r.cam;
+            key.rx0 = r.rx0;
+            key.ry0 = r.ry0;
+            key.rw = rw;
+            key.rh = r.rh;
+        }
+        base.tile_keep = ta.keep;
+    }
     FilmArgs &fa = r.fa;
     fa.Lhome = r.Lhome;
     fa.acc = r.acc;
