@@ -791,6 +791,21 @@ typedef struct pbrt_image_stats {
 int pbrt_ctx_set_profiling(pbrt_ctx *ctx, int on);
 int pbrt_get_image_stats(pbrt_ctx *ctx, pbrt_image_stats *out);
 
+/* The keep table of the LAST radiance render of the context (csrc/tile_cull.h; PBRT_FILM_NO_TILE_CULL), for tests and diagnosis:
+ * whether that render walked its first bounce with one, the region of the film it was built for, and the words themselves --
+ * word b, bit i: primitive i can be met by the camera rays of region indices [64 b, 64 b + 63].  n_blocks == 0: that render had no
+ * table (a BVH scene, more than 32 primitives, a region whose pixel count is no multiple of 64, PBRT_FILM_NO_TILE_CULL), or the
+ * context has not rendered yet; the region is then 0.  builds counts the launches of the kernel that fills the table since the
+ * context was made: a render that repeats scene, camera and region leaves it alone.  Waits for the context's stream, then copies
+ * min(n_blocks, capacity) words to `words` (may be NULL with capacity 0).  Refused while a recording is open. */
+typedef struct pbrt_tile_keep_info {
+    uint32_t n_blocks;         /* words of the table: rw * rh / 64, or 0 */
+    uint32_t rx0, ry0, rw, rh; /* the rendered region in film pixels: the crop widened by the filter's reach, clipped to the film */
+    uint32_t pad;
+    uint64_t builds;
+} pbrt_tile_keep_info;
+int pbrt_ctx_tile_keep(pbrt_ctx *ctx, pbrt_tile_keep_info *info, uint32_t *words, uint32_t capacity);
+
 /* ---- the queued chain as ONE submission (hipGraph) ---------------------------------------------------------------------
  * At the reference's own size (320 rays x 1 path, USMain.py:36) the chain above is eight small kernels, three fills and a copy:
  * the host spends as long queueing them as the device spends running them, 100 times per script.  Between

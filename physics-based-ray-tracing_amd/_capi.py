@@ -190,6 +190,11 @@ class ImageStats(C.Structure):
                 ("das_model_bytes", C.c_uint64), ("measured", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class TileKeepInfo(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint32), ("rx0", C.c_uint32), ("ry0", C.c_uint32), ("rw", C.c_uint32), ("rh", C.c_uint32),
+                ("pad", C.c_uint32), ("builds", C.c_uint64)]
+
+
 _P = C.c_void_p
 _F = C.c_void_p  # float* passed as raw address of a numpy buffer
 
@@ -268,6 +273,7 @@ SIGNATURES = {
     "pbrt_dev_download": (C.c_int, [_P, _F, _P, C.c_uint64]),
     "pbrt_ctx_set_profiling": (C.c_int, [_P, C.c_int]),
     "pbrt_get_image_stats": (C.c_int, [_P, C.POINTER(ImageStats)]),
+    "pbrt_ctx_tile_keep": (C.c_int, [_P, C.POINTER(TileKeepInfo), _P, C.c_uint32]),
     "pbrt_ctx_record_begin": (C.c_int, [_P]),
     "pbrt_ctx_record_end": (C.c_int, [_P, C.POINTER(_P)]),
     "pbrt_graph_launch": (C.c_int, [_P]),
@@ -418,6 +424,18 @@ class Context:
         st = ImageStats()
         self.check(self.lib.pbrt_get_image_stats(self.handle, C.byref(st)), "pbrt_get_image_stats")
         return {k: getattr(st, k) for k, _ in st._fields_ if k != "pad"}
+
+    def tile_keep(self) -> dict:
+        """the keep table of the last radiance render of this context (pbrt_ctx_tile_keep): used, the region (rx0, ry0, rw, rh) it
+        was built for, n_blocks, words [n_blocks] uint32 and builds, the launches of k_tile_keep so far; n_blocks == 0: no table"""
+        info = TileKeepInfo()
+        self.check(self.lib.pbrt_ctx_tile_keep(self.handle, C.byref(info), None, 0), "pbrt_ctx_tile_keep")
+        words = np.zeros(info.n_blocks, np.uint32)
+        if info.n_blocks:
+            self.check(self.lib.pbrt_ctx_tile_keep(self.handle, C.byref(info), addr(words), len(words)), "pbrt_ctx_tile_keep")
+        d = {k: int(getattr(info, k)) for k, _ in info._fields_ if k != "pad"}
+        d.update(used=info.n_blocks > 0, words=words)
+        return d
 
     def record(self) -> "Recording":
         """with ctx.record() as rec: <queueing calls> -- the calls are recorded instead of run (pbrt_ctx_record_begin / _end);

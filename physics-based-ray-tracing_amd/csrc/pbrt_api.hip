@@ -101,6 +101,11 @@ struct pbrt_ctx {
         pbrt_camera cam{};
         uint32_t rx0 = 0, ry0 = 0, rw = 0, rh = 0;
     } tile_keep_key;
+    // what pbrt_ctx_tile_keep reports: whether the LAST radiance render carried a table (the key outlives a later render without
+    // one), and how often k_tile_keep has been launched
+    bool tile_keep_last = false;
+    const uint32_t *tile_keep_words = nullptr;  // that render's table: good while the workspace buffer is allocation tile_keep_key.gen
+    uint64_t tile_keep_builds = 0;
     bool img_event(int i) { return img_ev[i] || hipEventCreate(&img_ev[i]) == hipSuccess; }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint32_t lds_limit = 0;
@@ -420,6 +425,29 @@ int pbrt_get_stats(pbrt_ctx *c, pbrt_stats *out) {
     if (!c || !out) return PBRT_E_INVALID;
     if (int rc = ctx_settle(c)) return rc;  // (a queued acquisition: its counters arrive now)
     *out = c->stats;
+    return PBRT_OK;
+}
+
+// the keep table of the last radiance render (render_args): read back for tests and diagnosis, launches nothing
+int pbrt_ctx_tile_keep(pbrt_ctx *c, pbrt_tile_keep_info *info, uint32_t *words, uint32_t capacity) {
+    if (!c) return PBRT_E_INVALID;
+    NEED(c, info && (words || capacity == 0));
+    if (int rc = ctx_settle(c)) return rc;
+    *info = pbrt_tile_keep_info{};
+    info->builds = c->tile_keep_builds;
+    if (!c->tile_keep_last) return PBRT_OK;
+    const pbrt_ctx::TileKeepKey &key = c->tile_keep_key;
+    if (key.gen == 0 || c->work.generation("tile_keep") != key.gen)
+        return c->fail(PBRT_E_INVALID, "the keep table of the last render has left the workspace (pbrt_ctx_trim or the workspace limit after another call)");
+    info->n_blocks = (uint32_t)((uint64_t)key.rw * key.rh / 64);
+    info->rx0 = key.rx0;
+    info->ry0 = key.ry0;
+    info->rw = key.rw;
+    info->rh = key.rh;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t n = std::min(info->n_blocks, capacity);
+    if (n) HIPCHK(c, hipMemcpy(words, c->tile_keep_words, (size_t)n * 4, hipMemcpyDeviceToHost));
     return PBRT_OK;
 }
 
@@ -1469,6 +1497,7 @@ static int render_args(Render &r) {
     // the keep words of the camera tiles (kernels_radiance.h k_tile_keep): the waves of the first bounce are whole blocks of 64 region
     // indices only if the region's pixel count is a multiple of 64; rebuilt per render (camera and crop are the call's)
     base.tile_keep = nullptr;
+    c->tile_keep_last = false;
     if (s->accel_kernel == ACCEL_K_BRUTE && s->ds.n_prims <= 32 && base.npix_r % 64 == 0 && !(f->flags & PBRT_FILM_NO_TILE_CULL)) {
         TileKeepArgs ta;
         ta.prims = s->ds.prims;
@@ -1489,6 +1518,7 @@ static int render_args(Render &r) {
         if (!same) {
             hipLaunchKernelGGL(k_tile_keep, dim3(div_up(ta.n_blocks, 64)), dim3(64), 0, c->stream, ta);
             HIPCHK(c, hipGetLastError());
+            ++c->tile_keep_builds;
             key.gen = gen;
             key.scene = s->serial;
             key.cam = *r.cam;
@@ -1498,6 +1528,8 @@ static int render_args(Render &r) {
             key.rh = r.rh;
         }
         base.tile_keep = ta.keep;
+        c->tile_keep_last = true;
+        c->tile_keep_words = ta.keep;
     }
     FilmArgs &fa = r.fa;
     fa.Lhome = r.Lhome;

@@ -4,17 +4,30 @@
 //   {"cases": {name: {"cam": [17 numbers], "prims": [[type, 12 numbers], ...], "blocks": [[x0, y0, x1, y1, word], ...]}},
 //    "bits": all (block, primitive) bits, "cleared": how many of them are clear, "cleared_share": their share}
 // The test casts the oracle's camera rays against the oracle's primitive tests and holds every cleared bit to them.
+//
+// With one argument the cases come from that file instead (tests/tile_cull_util.py write_cases: the camera, the primitives and the
+// block rectangles of a render on the device, whose keep words tests/test_gpu_tile_keep_words.py compares with the ones printed
+// here), as whitespace-separated tokens, floats as %.9g so that the float32 values are exact:
+//   case NAME  cam <12 matrix entries> tan_half_fov_x near far film_w film_h  prims N <N x (type, 12 numbers)>
+//   rects M <M x (x0 y0 x1 y1)>  -- absolute film pixels, inclusive
+// and the output has the same shape, one word per rectangle.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
+#include <fstream>
 #include <string>
 #include <vector>
 
 #include "tile_cull.h"
 
+struct Rect {
+    uint32_t x0, y0, x1, y1;
+};
 struct Case {
     std::string name;
     pbrt_camera cam;
     std::vector<pbrt_prim> prims;
+    std::vector<Rect> rects;  // empty: the blocks of the whole film (block_rects)
 };
 
 static pbrt_prim planar(uint32_t type, float x, float y, float z, float e1x, float e1y, float e1z, float e2x, float e2y, float e2z) {
@@ -87,7 +100,26 @@ static void pixel_of(uint32_t pr, uint32_t rw, uint32_t tile_rows, uint32_t *x, 
     *y = tiled ? (q << 3) + (pr & 7u) : q;
 }
 
-int main() {
+// the blocks of 64 region indices of a region that is the whole film: the bounding box of the 64 pixels of each
+static std::vector<Rect> block_rects(uint32_t rw, uint32_t rh) {
+    const uint32_t tile_rows = rh & ~7u, n_blocks = rw * rh / 64;
+    std::vector<Rect> out;
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        Rect r = {~0u, ~0u, 0, 0};
+        for (uint32_t k = 0; k < 64; ++k) {
+            uint32_t x, y;
+            pixel_of(b * 64 + k, rw, tile_rows, &x, &y);
+            r.x0 = x < r.x0 ? x : r.x0;
+            r.x1 = x > r.x1 ? x : r.x1;
+            r.y0 = y < r.y0 ? y : r.y0;
+            r.y1 = y > r.y1 ? y : r.y1;
+        }
+        out.push_back(r);
+    }
+    return out;
+}
+
+static std::vector<Case> builtin_cases() {
     std::vector<Case> cases;
     cases.push_back({"cbox_64", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 64, 64), cbox()});
     cases.push_back({"cbox_48x80", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 48, 80), cbox()});
@@ -110,12 +142,77 @@ int main() {
     cases.push_back({"behind_camera", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 32, 32),
                      {quad(-1, -1, 6, 2, 0, 0, 0, 2, 0), sphere(0, 0, 7, 1), sphere(0, 0, 4.6f, 0.5f), tri(-1, -1, 4.01f, 2, 0, 0, 0, 2, 0),
                       quad(-3, -1, 5, 6, 0, -2, 0, 2, 0), sphere(0.3f, 0.2f, 0, 0.4f)}});
+    // regions with a row-major tail below the last full 8-row band, or with no band at all (tile_rows == 0)
+    cases.push_back({"cbox_16x12", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 16, 12), cbox()});  // two 8 x 8 blocks and one 16 x 4 tail block
+    cases.push_back({"cbox_32x10", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 32, 10), cbox()});  // four 8 x 8 blocks and one 32 x 2 tail block
+    cases.push_back({"cbox_64x9", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 64, 9), cbox()});    // the tail is a single row
+    cases.push_back({"cbox_48x4", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 48, 4), cbox()});    // no band; the middle block spans two rows
+    cases.push_back({"cbox_128x1", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 128, 1), cbox()});  // no band; two blocks
+    cases.push_back({"cbox_20x16", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 20, 16), cbox()});  // width no multiple of 8; no tail
+    cases.push_back({"cbox_4x16", look_at(0, 0, 4, 0, 0, 0, 0, 1, 0, 4, 16), cbox()});    // one block: the whole region
+    return cases;
+}
+
+// the cases of a file (the format is at the top); false: the file does not parse
+static bool read_cases(const char *path, std::vector<Case> *cases) {
+    std::ifstream in(path);
+    std::string tok;
+    auto word = [&](const char *want) { return (in >> tok) && tok == want; };
+    auto real = [&](float *v) {
+        if (!(in >> tok)) return false;
+        char *end = nullptr;
+        *v = std::strtof(tok.c_str(), &end);
+        return end != tok.c_str() && *end == 0;
+    };
+    auto count = [&](uint32_t *v) {
+        if (!(in >> tok)) return false;
+        char *end = nullptr;
+        const unsigned long long u = std::strtoull(tok.c_str(), &end, 10);
+        *v = (uint32_t)u;
+        return end != tok.c_str() && *end == 0 && u <= 0xffffffffull;
+    };
+    while (in >> tok) {
+        Case c = {};
+        if (tok != "case" || !(in >> c.name) || !word("cam")) return false;
+        for (int k = 0; k < 12; ++k)
+            if (!real(&c.cam.to_world[k])) return false;
+        if (!real(&c.cam.tan_half_fov_x) || !real(&c.cam.near_clip) || !real(&c.cam.far_clip) || !count(&c.cam.film_w) || !count(&c.cam.film_h))
+            return false;
+        uint32_t n = 0;
+        if (!word("prims") || !count(&n) || n > 32) return false;
+        for (uint32_t i = 0; i < n; ++i) {
+            pbrt_prim P = {};
+            P.emitter = -1;
+            if (!count(&P.type)) return false;
+            for (int k = 0; k < 12; ++k)
+                if (!real(&P.g[k])) return false;
+            c.prims.push_back(P);
+        }
+        if (!word("rects") || !count(&n) || n == 0 || n > (1u << 20)) return false;
+        for (uint32_t i = 0; i < n; ++i) {
+            Rect r;
+            if (!count(&r.x0) || !count(&r.y0) || !count(&r.x1) || !count(&r.y1)) return false;
+            c.rects.push_back(r);
+        }
+        cases->push_back(c);
+    }
+    return !cases->empty();
+}
+
+int main(int argc, char **argv) {
+    std::vector<Case> cases;
+    if (argc > 2 || (argc == 2 && !read_cases(argv[1], &cases))) {
+        std::fprintf(stderr, "usage: %s [case file]; %s\n", argv[0], argc == 2 ? "the file does not parse" : "one argument at the most");
+        return 2;
+    }
+    if (argc < 2) cases = builtin_cases();
 
     unsigned long long bits = 0, cleared = 0;
     std::printf("{\"cases\": {");
     for (size_t ci = 0; ci < cases.size(); ++ci) {
         const Case &c = cases[ci];
-        const uint32_t rw = c.cam.film_w, rh = c.cam.film_h, tile_rows = rh & ~7u, n_blocks = rw * rh / 64;
+        const uint32_t rw = c.cam.film_w, rh = c.cam.film_h;
+        const std::vector<Rect> rects = c.rects.empty() ? block_rects(rw, rh) : c.rects;
         std::printf("%s\"%s\": {\"cam\": [", ci ? ", " : "", c.name.c_str());
         for (int k = 0; k < 12; ++k) std::printf("%.9g, ", c.cam.to_world[k]);
         std::printf("%.9g, %.9g, %.9g, %u, %u], \"prims\": [", c.cam.tan_half_fov_x, c.cam.near_clip, c.cam.far_clip, rw, rh);
@@ -125,24 +222,16 @@ int main() {
             std::printf("]");
         }
         std::printf("], \"blocks\": [");
-        for (uint32_t b = 0; b < n_blocks; ++b) {
-            uint32_t x0 = ~0u, y0 = ~0u, x1 = 0, y1 = 0;
-            for (uint32_t k = 0; k < 64; ++k) {
-                uint32_t x, y;
-                pixel_of(b * 64 + k, rw, tile_rows, &x, &y);
-                x0 = x < x0 ? x : x0;
-                x1 = x > x1 ? x : x1;
-                y0 = y < y0 ? y : y0;
-                y1 = y > y1 ? y : y1;
-            }
+        for (size_t b = 0; b < rects.size(); ++b) {
+            const Rect &r = rects[b];
             uint32_t word = 0;
             for (size_t i = 0; i < c.prims.size(); ++i) {
-                const bool keep = tile_cull_keep(c.cam, x0, y0, x1, y1, c.prims[i]);
+                const bool keep = tile_cull_keep(c.cam, r.x0, r.y0, r.x1, r.y1, c.prims[i]);
                 word |= (keep ? 1u : 0u) << i;
                 ++bits;
                 cleared += keep ? 0 : 1;
             }
-            std::printf("%s[%u, %u, %u, %u, %u]", b ? ", " : "", x0, y0, x1, y1, word);
+            std::printf("%s[%u, %u, %u, %u, %u]", b ? ", " : "", r.x0, r.y0, r.x1, r.y1, word);
         }
         std::printf("]}");
     }

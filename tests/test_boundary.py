@@ -37,7 +37,8 @@ def test_struct_layouts_match_the_header(capi):
              "pbrt_film_desc": C.sizeof(capi.FilmDesc), "pbrt_us_params": C.sizeof(capi.UsParams),
              "pbrt_us_sensor": C.sizeof(capi.UsSensor), "pbrt_us_emitter": C.sizeof(capi.UsEmitter),
              "pbrt_us_receiver": C.sizeof(capi.UsReceiver), "pbrt_stats": C.sizeof(capi.Stats),
-             "pbrt_das_params": C.sizeof(capi.DasParams), "pbrt_image_stats": C.sizeof(capi.ImageStats)}
+             "pbrt_das_params": C.sizeof(capi.DasParams), "pbrt_image_stats": C.sizeof(capi.ImageStats),
+             "pbrt_tile_keep_info": C.sizeof(capi.TileKeepInfo)}
     prog = '#include <stdio.h>\n#include "pbrt_hip.h"\nint main(){' + "".join(
         f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
     exe = os.path.join(ROOT, "oracle", "_build", "abi_sizes")
@@ -95,6 +96,7 @@ def test_invalid_arguments_return_error_codes(capi):
     assert lib.pbrt_render_radiance(None, None, None, None) == -1
     assert lib.pbrt_ray_intersect(None, 0, None, None, None, None, None, None, None) == -1
     assert lib.pbrt_ctx_set_workspace_limit(None, 0) == -1 and lib.pbrt_ctx_trim(None, None) == -1
+    assert lib.pbrt_ctx_tile_keep(None, None, None, 0) == -1
     assert lib.pbrt_ctx_destroy(None) == 0 and lib.pbrt_scene_destroy(None) == 0
 
 
