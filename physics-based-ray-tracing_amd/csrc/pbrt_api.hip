@@ -16,6 +16,7 @@
 #include "bvh_build.h"
 #include "prim_runs.h"
 #include "bf_request.h"
+#include "us_request.h"
 #include "kernels_us.h"
 #include "kernels_wavefront.h"
 #include "kernels_us_wavefront.h"
@@ -1214,6 +1215,13 @@ static int call_stats(pbrt_ctx *c, const unsigned long long *hstats, uint64_t sa
 // about to give the memory to someone else); the message of the failed request stands.  Any other code from alloc is returned as is.
 // equal: passes of equal size instead of full ones plus a small remainder.
 static const uint64_t PASS_MIN_PATHS = 1u << 20;
+#ifndef US_PASS_PATHS
+// an acquisition's paths in flight per pass.  Config 3 (268 M paths), one launch per bounce: 8 / 16 / 32 / 64 Mi -> 13.1 / 12.7 / 13.0 /
+// 13.2 ms; with all bounces of a pass in one launch the survivors are re-read while still cached and smaller passes
+// win: 2 / 4 / 6 / 8 / 12 / 16 / 32 / 64 Mi -> 13.1 / 9.8 / 8.4 / 8.1 / 8.2 / 8.5 / 9.0 / 8.7 ms.  Later in round 2 (Mitsuba's
+// shading frame: 1.96 segments per path; three workgroups per CU): 4 / 8 / 16 / 32 Mi -> 13.26 / 11.89 / 11.61 / 12.20 ms
+#define US_PASS_PATHS (16u << 20)
+#endif
 struct PassShape {
     uint32_t per_pass = 1, cap = 0, nseg = 0;
 };
@@ -1846,23 +1854,11 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
 // ------------------------------------------------------------------------------------------------
 // ultrasound mode driver
 // ------------------------------------------------------------------------------------------------
-static inline float host_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-// :248 float32 elem_x = pitch * (arange_f32 - (N-1)/2)
-static inline float us_elem_x(const pbrt_us_params *p, uint32_t e) {
-    return (float)((double)p->pitch * ((double)(float)e - ((double)p->n_elements - 1.0) / 2.0));
-}
-
 // The curved array (PBRT_US_ARRAY_CONVEX, DESIGN D18).  The geometry is CustomEmitter's (CustomEmmitter.py:41-47), evaluated with the
 // float statements of kernels_us.h us_emitter_ray, so that the position an emitter ray starts from and the position the receive
 // connection aims at are the same floats (sin / cos: kernels_us.h emit_sincos itself, compiled for the host -- the polynomial of
 // device_math.h sincos_pi4 up to 45 degrees; beyond, the host's sinf / cosf where the kernel calls the device library's, which agree
-// to a few ulp).
-static bool us_convex(const pbrt_us_params *p) { return (p->primary & PBRT_US_ARRAY_CONVEX) != 0; }
-static bool us_convex_valid(const pbrt_us_params *p) {
-    const pbrt_us_emitter &E = p->emitter;
-    return std::isfinite(E.radius) && E.radius > 0.0f && std::isfinite(E.opening_angle) && E.opening_angle > 0.0f &&
-           E.opening_angle < 180.0f && E.number_of_elements == p->n_elements;
-}
+// to a few ulp).  Its rules: us_request.h us_array_rules.
 // element e of the array: (x, z, nx, nz) in the sensor's frame
 static void us_array_element(const pbrt_us_params *p, uint32_t e, float *out) {
     if (!us_convex(p)) {
@@ -1886,7 +1882,7 @@ static void us_array_element(const pbrt_us_params *p, uint32_t e, float *out) {
 
 int pbrt_us_array_elements(const pbrt_us_params *p, float *elem) {
     if (!p || !elem || p->n_elements == 0) return PBRT_E_INVALID;
-    if (us_convex(p) && !us_convex_valid(p)) return PBRT_E_INVALID;
+    if (us_convex(p) && us_array_rules(p)) return PBRT_E_INVALID;
     for (uint32_t e = 0; e < p->n_elements; ++e) us_array_element(p, e, elem + 4 * (size_t)e);
     return PBRT_OK;
 }
@@ -1894,7 +1890,7 @@ int pbrt_us_array_elements(const pbrt_us_params *p, float *elem) {
 int pbrt_us_tx_delays(const pbrt_us_params *p, float *tx) {
     if (!p || !tx || p->n_angles > PBRT_US_MAX_ANGLES || p->n_angles == 0 || p->n_elements == 0) return PBRT_E_INVALID;
     if (us_convex(p)) {  // the plane wave along (sin a, 0, cos a), referenced to the apex (0, 0, R): (x_e sin a + (z_e - R) cos a) / c
-        if (!us_convex_valid(p)) return PBRT_E_INVALID;
+        if (us_array_rules(p)) return PBRT_E_INVALID;
         for (uint32_t a = 0; a < p->n_angles; ++a) {
             const double ar = (double)p->angles_deg[a] * (M_PI / 180.0);
             for (uint32_t e = 0; e < p->n_elements; ++e) {
@@ -2012,278 +2008,275 @@ static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p,
     return PBRT_OK;
 }
 
-extern "C" {
+// What the stages of an acquisition share.  us_impl calls the stages in order; each fills its own group of members.
+namespace {
+struct Acquire {
+    pbrt_scene *s;
+    pbrt_ctx *c;
+    const pbrt_us_params *p;
+    uint32_t seed, ppr, path_offset, norm_paths;
+    float *d_channel, *tx_host;
+    bool wait;
+    // us_check: the request (us_request.h: the rules, the derived facts, the host's constants), the switches, the launch structure
+    UsRequest rq;
+    bool timed = true;  // (event pairs recorded into a graph cannot be read back)
+    Switches sw;
+    bool streams = false;  // k_trace / k_us_shade streams (us_wf_pass), not the fused k_us_bounce
+    // us_buffers: the shape of a full pass (n_own: its live counters / statistics rows) and the buffers of the call
+    uint32_t region = 0, n_own = 0;
+    PassShape ps;
+    WfBufs wfb{};
+    WfPlan wfp;
+    float *stA = nullptr, *stB = nullptr;
+    uint32_t *segA = nullptr, *segB = nullptr;
+    unsigned long long *segstats = nullptr;
+    size_t segstats_bytes = 0;
+    float *tabs = nullptr;  // transmit delays [n_rays], primary directions [3 n_angles], elements [n_ex]; filled by us_tables
+    // us_args: the arguments every pass shares (us_passes sets those of a pass, us_fused_pass those of a launch)
+    UsArgs a{};
+    // us_passes
+    PassTimer timer{};
+    uint32_t passes = 0, launches = 0;
+};
+// the buffers whose size follows the pass (size_pass: again with half the paths after a failed allocation)
+struct UsAllocPass {
+    Acquire &q;
+    int operator()(uint32_t cap, uint32_t nseg) const {
+        pbrt_ctx *c = q.c;
+        NEED(c, q.streams || (uint64_t)cap * US_N_STATE * 4 < 0xffffffffull);  // the state tiles are addressed through 32-bit buffer offsets
+        NEED(c, !q.streams || cap < WF_DEAD);
+        if (q.streams) return wf_alloc(c, cap, nseg, &q.wfb) ? PBRT_OK : PBRT_E_NOMEM;
+        q.stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
+        q.stB = q.stA ? (float *)c->buf("stateB", (size_t)cap * N_STATE * 4) : nullptr;
+        return q.stA && q.stB ? PBRT_OK : PBRT_E_NOMEM;
+    }
+};
+}  // namespace
 
-static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32_t ppr, uint32_t path_offset,
-                   uint32_t norm_paths, float *d_channel, float *tx_host, bool wait = true) {
-    pbrt_ctx *c = s->ctx;
+// Check: what a recording admits, the argument rules and what follows from the block (us_request.h), the switches, the launch structure.
+static int us_check(Acquire &q) {
+    pbrt_ctx *c = q.c;
     if (c->recording) {  // recorded, not run: the queueing form only, one acquisition per recording
-        if (wait || c->pend.active) return c->fail(PBRT_E_INVALID, "recording: one pbrt_us_acquire_queue_dev per recording, and no call that waits");
+        if (q.wait || c->pend.active) return c->fail(PBRT_E_INVALID, "recording: one pbrt_us_acquire_queue_dev per recording, and no call that waits");
     } else if (int rcs = ctx_settle(c)) {
         return rcs;
     }
-    const bool timed = !c->recording;  // (event pairs recorded into a graph cannot be read back)
-    NEED(c, p && d_channel);
-    NEED(c, p->n_angles > 0 && p->n_angles <= PBRT_US_MAX_ANGLES && p->n_elements > 0 && p->time_samples > 0);
-    NEED(c, (uint64_t)p->n_angles * p->n_elements * p->time_samples < 0xffffffffull);  // channel index is 32-bit (echo bins)
-    NEED(c, p->max_depth > 0 && ppr > 0 && p->sound_speed > 0 && p->fs > 0);
-    NEED(c, p->max_depth < 0x40000000u);  // RNG block = bounce index; bit 30 marks a path's second block of a bounce, bit 31 the emitter's
-    const bool convex = us_convex(p);  // the curved array (DESIGN D18): geometry from p->emitter, kernels of their own
-    const uint32_t primary = p->primary & ~PBRT_US_ARRAY_CONVEX;
-    NEED(c, primary <= PBRT_US_PRIMARY_EMITTER);
-    const bool emit = primary == PBRT_US_PRIMARY_EMITTER;
-    if (emit) {  // CustomEmitter as the source of the primary rays: its elements are the acquisition's (include/pbrt_hip.h)
-        const pbrt_us_emitter &E = p->emitter;
-        NEED(c, E.number_of_elements == p->n_elements && E.number_of_rays_per_element > 0 && E.speed_of_sound > 0.0f);
-        NEED(c, std::isfinite(E.pitch) && std::isfinite(E.element_width) && std::isfinite(E.element_height) && std::isfinite(E.radius));
-        NEED(c, std::isfinite(E.steering_angle_min) && std::isfinite(E.steering_angle_max) && std::isfinite(E.opening_angle));
-        // an emitter on an arc and receivers on a line: never defined (D18) -- the curved array is asked for with PBRT_US_ARRAY_CONVEX
-        if (!convex && E.radius != 0.0f)
-            return c->fail(PBRT_E_UNSUPPORTED, "emitter.radius != 0 transmits from an arc: set PBRT_US_ARRAY_CONVEX in pbrt_us_params.primary");
-    }
-    if (convex) {
-        const pbrt_us_emitter &E = p->emitter;
-        NEED(c, std::isfinite(E.radius) && E.radius > 0.0f);
-        NEED(c, std::isfinite(E.opening_angle) && E.opening_angle > 0.0f && E.opening_angle < 180.0f);
-        NEED(c, E.number_of_elements == p->n_elements);
-    }
+    q.timed = !c->recording;
+    if (const char *why = us_request(&q.rq, q.p, q.ppr, q.d_channel != nullptr))
+        return q.rq.code == PBRT_E_INVALID ? c->fail(PBRT_E_INVALID, "invalid argument: %s", why) : c->fail(q.rq.code, "%s", why);
     HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    const Switches sw = read_switches();
-    const uint32_t NA = p->n_angles, NE = p->n_elements, T = p->time_samples;
-    const uint32_t n_rays = NA * NE;
-    const uint32_t n_ex = convex ? 4u * NE : NE;  // element positions, or the curved array's (x, z, nx, nz) table
-    std::vector<float> tx(n_rays), dir0(3 * NA), ex(n_ex);
-    pbrt_us_tx_delays(p, tx.data());
-    if (tx_host) std::memcpy(tx_host, tx.data(), tx.size() * 4);
-    const float *M = p->sensor_to_world;
-    auto xfv = [&](float x, float y, float z, float *o) {
-        o[0] = host_fma(M[0], x, host_fma(M[1], y, M[2] * z));
-        o[1] = host_fma(M[4], x, host_fma(M[5], y, M[6] * z));
-        o[2] = host_fma(M[8], x, host_fma(M[9], y, M[10] * z));
-    };
-    auto nrm = [&](float *v) {
-        float inv = 1.0f / std::sqrt(host_fma(v[0], v[0], host_fma(v[1], v[1], v[2] * v[2])));
-        v[0] *= inv;
-        v[1] *= inv;
-        v[2] *= inv;
-    };
-    for (uint32_t a = 0; a < NA; ++a) {  // CustomIntegrator.py:265,271,273
-        float ar = (float)((double)p->angles_deg[a] * (M_PI / 180.0));
-        xfv(sinf(ar), 0.0f, cosf(ar), &dir0[3 * a]);
-        nrm(&dir0[3 * a]);
-    }
-    if (convex)
-        pbrt_us_array_elements(p, ex.data());
-    else
-        for (uint32_t e = 0; e < NE; ++e) ex[e] = us_elem_x(p, e);
-#ifndef US_PASS_PATHS
-// paths in flight per pass.  Config 3 (268 M paths), one launch per bounce: 8 / 16 / 32 / 64 Mi -> 13.1 / 12.7 / 13.0 /
-// 13.2 ms; with all bounces of a pass in one launch the survivors are re-read while still cached and smaller passes
-// win: 2 / 4 / 6 / 8 / 12 / 16 / 32 / 64 Mi -> 13.1 / 9.8 / 8.4 / 8.1 / 8.2 / 8.5 / 9.0 / 8.7 ms.  Later in round 2 (Mitsuba's
-// shading frame: 1.96 segments per path; three workgroups per CU): 4 / 8 / 16 / 32 Mi -> 13.26 / 11.89 / 11.61 / 12.20 ms
-#define US_PASS_PATHS (16u << 20)
-#endif
+    q.sw = read_switches();
     // BVH scenes (tessellated phantoms, meshes) run as k_trace / k_us_shade streams (us_wf_pass); the diagnostic build keeps the
     // fused bounce behind PBRT_US_FUSED_BVH=1 for the A/B
-    const bool bvh_scene = s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS;
-    bool streams = bvh_scene;
+    q.streams = q.s->accel_kernel == ACCEL_K_BVH_GLOBAL || q.s->accel_kernel == ACCEL_K_BVH_LDS;
 #ifdef PBRT_DIAG
-    if ((rc = diag_us_fused_bvh(s, &streams)) != 0) return rc;
+    if (int rc = diag_us_fused_bvh(q.s, &q.streams)) return rc;
 #endif
+    return PBRT_OK;
+}
+
+// Pass sizing and buffers: the paths in flight per pass and the buffers whose size follows it, the launch plan of the streams, the
+// live counters, the counter rows and the buffer of the small tables.
+static int us_buffers(Acquire &q) {
+    pbrt_scene *s = q.s;
+    pbrt_ctx *c = q.c;
+    const bool streams = q.streams;
+    int rc;
     // paths in flight per pass.  Streams: 2 x 10 launches per pass whatever is still alive, so passes as large as the radiance
     // streams take (wf_default_pass_paths; the shared trace / shade workspace).  The fused kernels: the pass buffers must fit the
     // context's workspace limit.  A failed allocation halves the pass (size_pass); the echoes do not depend on the pass size.
-    const uint32_t REGION = streams ? WF_REGION : us_region_segs(s->accel_kernel, emit) * seg_threads(s->accel_kernel);
-    WfBufs wfb{};
-    float *stA = nullptr, *stB = nullptr;
-    uint32_t *segA = nullptr, *segB = nullptr;
-    auto alloc_pass = [&](uint32_t cap, uint32_t nseg) -> int {
-        NEED(c, streams || (uint64_t)cap * US_N_STATE * 4 < 0xffffffffull);  // the state tiles are addressed through 32-bit buffer offsets
-        NEED(c, !streams || cap < WF_DEAD);
-        if (streams) return wf_alloc(c, cap, nseg, &wfb) ? PBRT_OK : PBRT_E_NOMEM;
-        stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
-        stB = stA ? (float *)c->buf("stateB", (size_t)cap * N_STATE * 4) : nullptr;
-        return stA && stB ? PBRT_OK : PBRT_E_NOMEM;
-    };
+    q.region = streams ? WF_REGION : us_region_segs(s->accel_kernel, q.rq.emit) * seg_threads(s->accel_kernel);
     const uint64_t pass_paths = default_pass_paths(c, streams, US_PASS_PATHS, 2 * N_STATE * 4);
-    PassShape ps;
-    if ((rc = size_pass(c, pass_paths, false, ppr, n_rays, REGION, false, alloc_pass, &ps)) != 0) return rc;
-    const uint32_t ppr_pass = ps.per_pass, cap = ps.cap, nseg = ps.nseg;
-    WfPlan wfp;
+    if ((rc = size_pass(c, pass_paths, false, q.ppr, q.rq.n_rays, q.region, false, UsAllocPass{q}, &q.ps)) != 0) return rc;
     if (streams) {
-        wfp = wf_plan(s, sw);
-        wfp.packet = false;
-        if ((rc = wf_set_attr(s, wfp)) != 0) return rc;
+        q.wfp = wf_plan(s, q.sw);
+        q.wfp.packet = false;
+        if ((rc = wf_set_attr(s, q.wfp)) != 0) return rc;
     }
     // live counters / statistics rows: per region, per wave of a region for the BVH kernels
-    const uint32_t n_own = nseg * (streams ? WF_SHADE_THREADS / 64u : us_owners_per_region(s->accel_kernel));
+    q.n_own = q.ps.nseg * (streams ? WF_SHADE_THREADS / 64u : us_owners_per_region(s->accel_kernel));
     if (!streams) {
-        segA = (uint32_t *)c->buf("segA", (size_t)n_own * 4);
-        segB = (uint32_t *)c->buf("segB", (size_t)n_own * 4);
+        q.segA = (uint32_t *)c->buf("segA", (size_t)q.n_own * 4);
+        q.segB = (uint32_t *)c->buf("segB", (size_t)q.n_own * 4);
     }
     // the counter rows: summed into the pinned page and zeroed again by k_us_reduce_stats at the end of the call
-    const size_t segstats_bytes = (size_t)(2 + MAX_DEPTH_STATS) * n_own * 8;
-    unsigned long long *dstats = (unsigned long long *)c->buf("us_stats", segstats_bytes);
-    if (!dstats) return PBRT_E_NOMEM;
-    unsigned long long *segstats = dstats;
-    float *tabs = (float *)c->buf("us_tables", ((size_t)n_rays + 3 * NA + n_ex) * 4);
-    if ((!streams && (!segA || !segB)) || !dstats || !tabs) return PBRT_E_NOMEM;
+    q.segstats_bytes = (size_t)(2 + MAX_DEPTH_STATS) * q.n_own * 8;
+    q.segstats = (unsigned long long *)c->buf("us_stats", q.segstats_bytes);
+    if (!q.segstats) return PBRT_E_NOMEM;
+    q.tabs = (float *)c->buf("us_tables", ((size_t)q.rq.n_rays + 3 * q.rq.NA + q.rq.n_ex) * 4);
+    if ((!streams && (!q.segA || !q.segB)) || !q.tabs) return PBRT_E_NOMEM;
+    return PBRT_OK;
+}
+
+// The three small tables in one host image, uploaded only when they differ from what the device copy already holds, and what the
+// call clears: the channel buffer, the counter rows unless they are clean.  (A recording can neither upload nor fill.)
+static int us_tables(Acquire &q) {
+    pbrt_ctx *c = q.c;
+    const UsRequest &rq = q.rq;
     hipStream_t st = c->stream;
-    float *d_tx = tabs, *d_dir = tabs + n_rays, *d_ex = d_dir + 3 * NA;
-    // emitter rays are drawn inside the first-bounce instance (the EMIT instances of k_us_bounce: 17.1 against 18.4 ms since the echo table
-    // grew); PBRT_US_EMIT_FUSED=0 (A/B, test) writes them into the path state first (k_us_emit_init) and walks every bounce with the
-    // later-bounce instance.  (Two default bench runs of this form showed steps of 38 - 43 ms; host stalls of that size hit the
-    // two-kernel form as well and went away when bench.py took Python's cyclic collector out of its timed steps: three runs of
-    // either form clean since.)
-    // the three small tables in one host image; uploaded only when they differ from what the device copy already holds
-    {
-        std::vector<float> img((size_t)n_rays + 3 * NA + n_ex);
-        if (emit)  // the ray's own emission time rides in its time of flight (CustomEmmitter.py:93-94); t0 of :329 is 0
-            std::fill(img.begin(), img.begin() + n_rays, 0.0f);
-        else
-            std::copy(tx.begin(), tx.end(), img.begin());
-        std::copy(dir0.begin(), dir0.end(), img.begin() + n_rays);
-        std::copy(ex.begin(), ex.end(), img.begin() + n_rays + 3 * NA);
-        const uint64_t gen = c->work.generation("us_tables");
-        if (c->us_tab_gen != gen || c->us_tab_host != img) {
-            if (c->recording) return c->fail(PBRT_E_INVALID, "recording: the acquisition's tables are not on the device yet -- run the chain once before recording it");
-            c->work.invalidate_recordings();  // (a finished recording was made with the tables that are replaced now)
-            HIPCHK(c, hipMemcpyAsync(tabs, img.data(), img.size() * 4, hipMemcpyHostToDevice, st));
-            c->us_tab_host.swap(img);
-            c->us_tab_gen = gen;
-        }
+    std::vector<float> img((size_t)rq.n_rays + 3 * rq.NA + rq.n_ex);
+    float *tx = img.data(), *dir0 = tx + rq.n_rays, *ex = dir0 + 3 * rq.NA;
+    pbrt_us_tx_delays(q.p, tx);
+    if (q.tx_host) std::memcpy(q.tx_host, tx, (size_t)rq.n_rays * 4);
+    if (rq.emit)  // the ray's own emission time rides in its time of flight (CustomEmmitter.py:93-94); t0 of :329 is 0
+        std::fill(tx, tx + rq.n_rays, 0.0f);
+    std::copy(rq.dir0, rq.dir0 + 3 * rq.NA, dir0);
+    if (rq.convex)
+        pbrt_us_array_elements(q.p, ex);
+    else
+        for (uint32_t e = 0; e < rq.NE; ++e) ex[e] = us_elem_x(q.p, e);
+    const uint64_t gen = c->work.generation("us_tables");
+    if (c->us_tab_gen != gen || c->us_tab_host != img) {
+        if (c->recording) return c->fail(PBRT_E_INVALID, "recording: the acquisition's tables are not on the device yet -- run the chain once before recording it");
+        c->work.invalidate_recordings();  // (a finished recording was made with the tables that are replaced now)
+        HIPCHK(c, hipMemcpyAsync(q.tabs, img.data(), img.size() * 4, hipMemcpyHostToDevice, st));
+        c->us_tab_host.swap(img);
+        c->us_tab_gen = gen;
     }
-    const size_t nchan = (size_t)n_rays * T;
-    HIPCHK(c, hipMemsetAsync(d_channel, 0, nchan * 4, st));
+    HIPCHK(c, hipMemsetAsync(q.d_channel, 0, rq.nchan * 4, st));
     // (the rows are clean if the last acquisition's reduction has swept exactly this allocation; anything else -- a fresh or resized
     // buffer, a call that failed half-way -- gets the fill)
-    if (c->us_rows_gen != c->work.generation("us_stats") || c->us_rows_bytes != segstats_bytes) {
+    if (c->us_rows_gen != c->work.generation("us_stats") || c->us_rows_bytes != q.segstats_bytes) {
         if (c->recording) return c->fail(PBRT_E_INVALID, "recording: the acquisition's counters are not clean yet -- run the chain once before recording it");
-        HIPCHK(c, hipMemsetAsync(dstats, 0, segstats_bytes, st));
+        HIPCHK(c, hipMemsetAsync(q.segstats, 0, q.segstats_bytes, st));
     }
     c->us_rows_gen = 0;
-    if (timed) HIPCHK(c, hipEventRecord(c->ev0, st));
-    UsArgs a{};
+    if (q.timed) HIPCHK(c, hipEventRecord(c->ev0, st));
+    return PBRT_OK;
+}
+
+// Argument block: what every pass hands its kernels, and the first-bounce tables made with it (k_us_first).
+static int us_args(Acquire &q) {
+    pbrt_scene *s = q.s;
+    pbrt_ctx *c = q.c;
+    const UsRequest &rq = q.rq;
+    const uint32_t NE = rq.NE, n_rays = rq.n_rays;
+    UsArgs &a = q.a;
+    us_request_args(rq, &a);  // the block with primary without the array bit, tn, am .. inv_c, fuse
     a.sc = s->ds;
-    a.p = *p;
-    a.p.primary = primary;  // (the kernels compare it with PBRT_US_PRIMARY_*; the array is a template switch of theirs)
-    a.stats = segstats;
-    a.stat_stride = n_own;
-    a.channel = d_channel;
-    a.tx = d_tx;
-    a.dir0 = d_dir;
-    a.elem_x = d_ex;
-    float tn[3];
-    xfv(0.0f, 0.0f, 1.0f, tn);
-    nrm(tn);
-    a.tn[0] = tn[0];
-    a.tn[1] = tn[1];
-    a.tn[2] = tn[2];
-    a.am = p->main_beam_angle * (K_PI / 180.0f);
-    a.ac = p->cutoff_angle * (K_PI / 180.0f);
-    a.cos_min = cosf(a.ac);                                                           // :370
-    a.katt = (float)(-(double)p->attenuation * (double)p->frequency * 1e-6);          // :328
-    a.two_pi_f = (float)(2.0 * M_PI * (double)p->frequency);                          // :330
-    a.inv_c = 1.0f / p->sound_speed;
-    a.cap = cap;
-    a.seed = seed;
+    a.stats = q.segstats;
+    a.stat_stride = q.n_own;
+    a.channel = q.d_channel;
+    a.tx = q.tabs;
+    a.dir0 = q.tabs + n_rays;
+    a.elem_x = q.tabs + n_rays + 3 * rq.NA;
+    a.cap = q.ps.cap;
+    a.seed = q.seed;
     a.lds_bytes = s->lds_bytes;
-    a.fuse = (p->quirks & PBRT_USQ_NO_FUSED_BOUNCES) ? 0u : 1u;
     a.div_ne = make_fastdiv(NE);
     NEED(c, fastdiv_exact(a.div_ne, NE, {0u, 1u, NE - 1, NE, NE + 1, n_rays - 1, n_rays}));
-    // first-bounce tables (kernels_us.h k_us_first): worth it once a ray has more paths than receive elements
-    if (ppr >= NE && !(p->quirks & PBRT_USQ_NO_FIRST_TABLES) && !emit) {  // (emitter rays: every path has its own origin)
+    if (rq.tables) {
         float4 *fh = (float4 *)c->buf("us_first_hit", (size_t)n_rays * 16);
         float4 *fv = (float4 *)c->buf("us_first_rx", (size_t)n_rays * NE * 16);
         if (!fh || !fv) return PBRT_E_NOMEM;
         const dim3 g(div_up((uint64_t)n_rays * NE, 256)), b(256);
-        hipLaunchKernelGGL(us_first_kernel(s, convex), g, b, 0, st, a, n_rays, fh, fv);
+        hipLaunchKernelGGL(us_first_kernel(s, rq.convex), g, b, 0, c->stream, a, n_rays, fh, fv);
         HIPCHK(c, hipGetLastError());
         a.first_hit = fh;
         a.first_rx = fv;
     }
-    PassTimer timer{c, timed};
-    uint32_t passes = 0, launches = 0;
-    for (uint32_t k0 = 0; k0 < ppr; k0 += ppr_pass, ++passes) {
-        const uint32_t kc = std::min(ppr_pass, ppr - k0);
+    return PBRT_OK;
+}
+
+// Brute-force scenes: the bounces of one ultrasound pass through the fused k_us_bounce, in one launch (a.fuse) or one per bounce.
+// Emitter rays are drawn inside the first-bounce instance (the EMIT instances of k_us_bounce: 17.1 against 18.4 ms since the echo table
+// grew); PBRT_US_EMIT_FUSED=0 (A/B, test) writes them into the path state first (k_us_emit_init) and walks every bounce with the
+// later-bounce instance.  (Two default bench runs of this form showed steps of 38 - 43 ms; host stalls of that size hit the
+// two-kernel form as well and went away when bench.py took Python's cyclic collector out of its timed steps: three runs of
+// either form clean since.)
+static int us_fused_pass(Acquire &q, uint32_t nseg_pass) {
+    pbrt_ctx *c = q.c;
+    UsArgs &a = q.a;
+    int rc;
+    float *in = q.stA, *out = q.stB;
+    uint32_t *sin = q.segA, *sout = q.segB;
+    // step 0 of the two-kernel form: the primary rays into the state (k_us_emit_init writes a.out / a.seg_out), then the later-bounce
+    // instance from depth 0
+    const bool emit_init = q.rq.emit && !q.sw.us_emit_fused;
+    for (uint32_t depth = 0, step = 0; depth < q.p->max_depth; ++step) {
+        a.depth = depth;
+        a.in = in;
+        a.out = out;
+        a.seg_in = sin;
+        a.seg_out = sout;
+        if (emit_init && step == 0) {
+            hipLaunchKernelGGL(k_us_emit_init, dim3(div_up(std::max(a.n_paths, nseg_pass), 256)), dim3(256), 0, c->stream, a, q.region, nseg_pass);
+        } else {
+            if ((rc = launch_us(q.s, a, nseg_pass, step == 0, q.sw.us_generic_kernel, q.rq.convex)) != 0) return rc;
+            HIPCHK(c, hipGetLastError());
+            ++q.launches;
+            if (a.fuse) break;  // that launch walked every bounce (kernels_us.h)
+            ++depth;
+        }
+        std::swap(in, out);
+        std::swap(sin, sout);
+    }
+    return PBRT_OK;
+}
+
+// The pass loop: the paths of a ray in passes of ps.per_pass, each between the events of its own pair.
+static int us_passes(Acquire &q) {
+    pbrt_ctx *c = q.c;
+    UsArgs &a = q.a;
+    const uint32_t n_rays = q.rq.n_rays;
+    int rc;
+    q.timer = PassTimer{c, q.timed};
+    for (uint32_t k0 = 0; k0 < q.ppr; k0 += q.ps.per_pass, ++q.passes) {
+        const uint32_t kc = std::min(q.ps.per_pass, q.ppr - k0);
         a.ppr_pass = kc;
         a.div_ppr = make_fastdiv(kc);
         NEED(c, fastdiv_exact(a.div_ppr, kc, {0u, 1u, kc - 1, kc, kc + 1, n_rays * kc - 1, n_rays * kc, 0xfffffbffu}));
-        a.path_first = path_offset + k0;
+        a.path_first = q.path_offset + k0;
         a.n_paths = n_rays * kc;
-        const uint32_t nseg_pass = div_up(a.n_paths, REGION);
-        a.blk_mul = 0;
-        if (emit && !streams && nseg_pass > 2u * NA && sw.us_emit_permute != 0) {  // (PBRT_US_EMIT_PERMUTE=0, A/B and test: workgroup b stays on region b)
-            uint32_t m = (nseg_pass / NA) | 1u;
-            if (sw.us_emit_permute > 1) m = (uint32_t)sw.us_emit_permute | 1u;  // (A/B: another stride)
-            while (std::gcd(m, nseg_pass) != 1u) m += 2u;
-            a.blk_mul = m % nseg_pass;
-        }
-        if (streams) {
-            if ((rc = timer.begin()) != 0) return rc;
-            if ((rc = us_wf_pass(s, a, wfb, wfp, nseg_pass, convex, &launches)) != 0) return rc;
-            if ((rc = timer.end()) != 0) return rc;
-            continue;
-        }
-        float *in = stA, *out = stB;
-        uint32_t *sin = segA, *sout = segB;
-        for (uint32_t depth = 0; depth < p->max_depth; ++depth) {
-            a.depth = depth;
-            a.in = in;
-            a.out = out;
-            a.seg_in = sin;
-            a.seg_out = sout;
-            if (depth == 0 && (rc = timer.begin()) != 0) return rc;
-            bool first_kernel = depth == 0;
-            if (depth == 0 && emit && !sw.us_emit_fused) {
-                // emitter rays: the primary rays into the state (k_us_emit_init writes a.out / a.seg_out), then the later-bounce
-                // instance from depth 0
-                hipLaunchKernelGGL(k_us_emit_init, dim3(div_up(std::max(a.n_paths, nseg_pass), 256)), dim3(256), 0, st, a, REGION, nseg_pass);
-                std::swap(in, out);
-                std::swap(sin, sout);
-                a.in = in;
-                a.out = out;
-                a.seg_in = sin;
-                a.seg_out = sout;
-                first_kernel = false;
-            }
-            if ((rc = launch_us(s, a, nseg_pass, first_kernel, sw.us_generic_kernel, convex)) != 0) return rc;
-            HIPCHK(c, hipGetLastError());
-            ++launches;
-            if (a.fuse) break;  // that launch walked every bounce (kernels_us.h)
-            std::swap(in, out);
-            std::swap(sin, sout);
-        }
-        if ((rc = timer.end()) != 0) return rc;
+        const uint32_t nseg_pass = div_up(a.n_paths, q.region);
+        a.blk_mul = q.rq.emit && !q.streams ? us_emit_blk_mul(nseg_pass, q.rq.NA, q.sw.us_emit_permute) : 0u;
+        if ((rc = q.timer.begin()) != 0) return rc;
+        rc = q.streams ? us_wf_pass(q.s, a, q.wfb, q.wfp, nseg_pass, q.rq.convex, &q.launches) : us_fused_pass(q, nseg_pass);
+        if (rc != 0) return rc;
+        if ((rc = q.timer.end()) != 0) return rc;
     }
-    const float inv_norm = 1.0f / (float)(norm_paths ? norm_paths : 1);
-    // (one path per ray, the reference's own setting (USMain.py:36): the factor is exactly 1 and the pass over the buffer changes no bit)
-    if (inv_norm != 1.0f) hipLaunchKernelGGL(k_scale, dim3(div_up(nchan, 256)), dim3(256), 0, st, d_channel, nchan, inv_norm);
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventRecord(c->ev1, st));
-    // counters into the context's pinned page (partial sums, written by the kernel; the rows are zero again behind it), guard words by
-    // a queued copy; both are read by us_finish once the stream has drained
-    hipLaunchKernelGGL(k_us_reduce_stats, dim3(2 + MAX_DEPTH_STATS, REDUCE_SLICES), dim3(256), 0, st, segstats, n_own, (size_t)n_own, c->pin_stats());
-    HIPCHK(c, hipGetLastError());
-    c->us_rows_gen = c->work.generation("us_stats");
-    c->us_rows_bytes = segstats_bytes;
-    if (streams && (rc = wf_guard_fetch(c, c->pin_guard())) != 0) return rc;
-    pbrt_ctx::PendingAcq &P = c->pend;
-    P.active = true;
-    P.timed = timed;
-    P.scaled = inv_norm != 1.0f;
-    P.streams = streams;
-    P.tab0 = a.first_hit != nullptr;
-    P.n_ev = timer.n_ev;
-    P.passes = passes;
-    P.launches = launches;
-    P.samples = (uint64_t)n_rays * ppr;
-    P.nchan = nchan;
-    return wait ? us_finish(c) : PBRT_OK;
+    return PBRT_OK;
 }
 
-}  // extern "C"
+// The end of the queued chain: normalisation, the counters into the context's pinned page, and what us_finish needs to turn them
+// into pbrt_stats once the stream has drained.
+static int us_queue_finish(Acquire &q) {
+    pbrt_ctx *c = q.c;
+    hipStream_t st = c->stream;
+    const uint64_t nchan = q.rq.nchan;
+    const float inv_norm = 1.0f / (float)(q.norm_paths ? q.norm_paths : 1);
+    // (one path per ray, the reference's own setting (USMain.py:36): the factor is exactly 1 and the pass over the buffer changes no bit)
+    if (inv_norm != 1.0f) hipLaunchKernelGGL(k_scale, dim3(div_up(nchan, 256)), dim3(256), 0, st, q.d_channel, nchan, inv_norm);
+    HIPCHK(c, hipGetLastError());
+    if (q.timed) HIPCHK(c, hipEventRecord(c->ev1, st));
+    // counters into the context's pinned page (partial sums, written by the kernel; the rows are zero again behind it), guard words by
+    // a queued copy; both are read by us_finish once the stream has drained
+    hipLaunchKernelGGL(k_us_reduce_stats, dim3(2 + MAX_DEPTH_STATS, REDUCE_SLICES), dim3(256), 0, st, q.segstats, q.n_own, (size_t)q.n_own, c->pin_stats());
+    HIPCHK(c, hipGetLastError());
+    c->us_rows_gen = c->work.generation("us_stats");
+    c->us_rows_bytes = q.segstats_bytes;
+    if (int rc = q.streams ? wf_guard_fetch(c, c->pin_guard()) : PBRT_OK) return rc;
+    pbrt_ctx::PendingAcq &P = c->pend;
+    P.active = true;
+    P.timed = q.timed;
+    P.scaled = inv_norm != 1.0f;
+    P.streams = q.streams;
+    P.tab0 = q.a.first_hit != nullptr;
+    P.n_ev = q.timer.n_ev;
+    P.passes = q.passes;
+    P.launches = q.launches;
+    P.samples = (uint64_t)q.rq.n_rays * q.ppr;
+    P.nchan = nchan;
+    return PBRT_OK;
+}
+
+static int us_impl(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint32_t ppr, uint32_t path_offset,
+                   uint32_t norm_paths, float *d_channel, float *tx_host, bool wait = true) {
+    Acquire q{s, s->ctx, p, seed, ppr, path_offset, norm_paths, d_channel, tx_host, wait};
+    for (auto stage : {us_check, us_buffers, us_tables, us_args, us_passes, us_queue_finish})
+        if (int rc = stage(q)) return rc;
+    return wait ? us_finish(q.c) : PBRT_OK;
+}
 
 static int us_finish(pbrt_ctx *c) {
     pbrt_ctx::PendingAcq P = c->pend;
