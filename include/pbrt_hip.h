@@ -201,6 +201,9 @@ typedef struct pbrt_film_desc {
                                            and the lone area light are left out of it) -- same film if the pruning is right */
 #define PBRT_FILM_NO_TILE_CULL 0x20u /* diagnostic: the camera rays of brute-force scenes walk EVERY primitive instead of the ones the \
                                         keep word of their 8 x 8 pixel tile leaves (csrc/tile_cull.h) -- same film if the culling is right */
+#define PBRT_FILM_NO_ORDERED_WALK 0x40u /* diagnostic: a brute-force scene whose primitive lists are class-ordered (parallelograms, then \
+                                           triangles, then curved records) is rendered through the kernels that walk the run tables \
+                                           (csrc/prim_runs.h) -- same film, same statistics */
 
 /* ---- ultrasound (acoustic) mode ----------------------------------------------------------- */
 /* Parameter block of UltraIntegrator (CustomIntegrator.py:13-48) plus the sensor transform

@@ -130,6 +130,7 @@ struct DevScene {
     // mode, pbrt_ray_test) always walk the full list.
     const pbrt_prim *occ_prims;
     uint32_t n_occ;
+    uint32_t occ_ord;  // (see prim_ord)
     // BRUTE only: prims and occ_prims cut into maximal runs of one primitive class, in list order; a run is count << 2 | class
     // (prim_runs.h).  brute_intersect walks a list run by run, one straight-line loop per class.
     const uint32_t *prim_runs, *occ_runs;
@@ -137,6 +138,11 @@ struct DevScene {
     // optional: the vertex normals of mesh primitives, [n_prims][9], caller order (indexed by Hit::slot); nullptr: face normals
     const float *vnormals;
     uint32_t n_prims, n_nodes, n_emitters, n_mats, n_light_prims;
+    // BRUTE only, non-zero on an ordered scene: BOTH lists are class-ordered (prim_runs.h prim_runs_ordered: parallelograms, then
+    // triangles, then curved records).  prim_ord and occ_ord hold the counts (nq, nt, nc) of prims and of occ_prims, packed by
+    // prim_ord_pack; brute_intersect ORDERED walks the lists by them and reads no run table.  (One word each, in the two padding
+    // words of this struct: its size and the offset of every other kernel argument stay what they were.)
+    uint32_t prim_ord;
 };
 
 struct Hit {
@@ -409,6 +415,21 @@ DEV bool brute_curved_run(const pbrt_prim *&p, uint32_t &i, uint32_t cnt, V3 o, 
     } while (p != pend);
     return false;
 }
+// the end of a walk: any-hit: is this lane occluded; closest hit: the one division of the best candidate
+template <bool ANY>
+DEV bool brute_finish(const BruteBest &b, Hit *h) {
+    if (ANY) return b.found;
+    const bool found = b.bp != 0xffffffffu;
+    if (found) {
+        float inv = 1.0f / b.bd;
+        h->t = b.bn * inv;
+        h->u = b.bu * inv;
+        h->v = b.bv * inv;
+        h->prim = b.bp;
+        h->slot = b.bp;
+    }
+    return found;
+}
 
 // CONES: the kernel variant understands the analytic quadrics, PBRT_PRIM_CONE and PBRT_PRIM_CYLINDER records.  Compile-time,
 // because the cone branch costs the
@@ -422,11 +443,52 @@ DEV bool brute_curved_run(const pbrt_prim *&p, uint32_t &i, uint32_t cnt, V3 o, 
 // without a set bit is stepped over whole -- so indices, list order and the tie rule are those of the plain walk.  A run of spheres
 // has no masked loop of its own (a second copy of sphere_hit would be one more IEEE division in the kernel): without a set bit it
 // is stepped over, with one the plain loops take the walk over from that run on, and test what is left of the list unmasked.
-template <bool ANY, bool SEGMENT = false, bool CONES = true>
+//
+// ORDERED: the list is class-ordered (DevScene::prim_ord, the host's promise): at most one run per class, parallelograms, then
+// triangles, then curved records.  The walk is then the three loops one after the other over the counts of DevScene::prim_ord /
+// occ_ord -- no table word, no dispatch loop, and no copies of the best candidate between a dispatch loop and the loops of the
+// classes.  Same loops, same indices, same list order as the table walk, so the same result for every input.  With a keep word
+// the set bits of the parallelogram range are visited in rising order, then those of the triangle range (a list of <= 32
+// primitives: the host builds keep words for no other), and the ONE curved loop both paths share runs if a bit of its range is set.
+template <bool ANY, bool SEGMENT = false, bool CONES = true, bool ORDERED = false>
 DEV bool brute_intersect(const DevScene &sc, V3 o, V3 d, float tmax, Hit *h, uint32_t keep = 0xffffffffu) {
     BruteBest b = {0.0f, 1.0f, 0.0f, 0.0f, 0xffffffffu, false};
     constexpr bool OCC = ANY && SEGMENT;
     const pbrt_prim *p = OCC ? sc.occ_prims : sc.prims;
+    if constexpr (ORDERED) {
+        // prim_ord_pack; a kernel argument: wave-uniform, in an SGPR.  (No readfirstlane, and no barrier that would keep the unpacking
+        // inside the walk: either form spills twice the SGPRs in k_bounce<true, ., 2>, and the second was measured slower than the
+        // table walk, profiles/ordered_walk.md.)
+        const uint32_t w = OCC ? sc.occ_ord : sc.prim_ord;
+        const uint32_t nq = w & PRIM_ORD_MASK, nt = (w >> PRIM_ORD_BITS) & PRIM_ORD_MASK, nc = (w >> (2u * PRIM_ORD_BITS)) & PRIM_ORD_MASK;
+        uint32_t i = 0;
+        bool curved = nc != 0u;
+        if (!ANY && !CONES && keep != 0xffffffffu) {
+            // (64-bit shifts: nq, nq + nt <= 32 may be 32)
+            uint32_t bits = keep & (uint32_t)((1ull << nq) - 1ull);
+            while (bits) {
+                const uint32_t k = (uint32_t)__builtin_ctz(bits);
+                bits &= bits - 1u;
+                brute_planar_one<false, false>(p + k, k, o, d, tmax, b);
+            }
+            bits = (uint32_t)((unsigned long long)keep >> nq) & (uint32_t)((1ull << nt) - 1ull);
+            while (bits) {
+                const uint32_t k = (uint32_t)__builtin_ctz(bits);
+                bits &= bits - 1u;
+                brute_planar_one<false, true>(p + nq + k, nq + k, o, d, tmax, b);
+            }
+            p += nq + nt;
+            i = nq + nt;
+            curved = curved & ((uint32_t)((unsigned long long)keep >> i) != 0u);
+        } else {
+            bool stop = false;
+            if (nq) stop = brute_planar_run<ANY, false>(p, i, nq, o, d, tmax, b);
+            if (!(ANY && stop) && nt) stop = brute_planar_run<ANY, true>(p, i, nt, o, d, tmax, b);
+            if (ANY && stop) curved = false;
+        }
+        if (curved) brute_curved_run<ANY, CONES>(p, i, nc, o, d, tmax, b);
+        return brute_finish<ANY>(b, h);
+    }
     const uint32_t *runs = OCC ? sc.occ_runs : sc.prim_runs;
     const uint32_t n_runs = (uint32_t)__builtin_amdgcn_readfirstlane((int)(OCC ? sc.n_occ_runs : sc.n_prim_runs));
     uint32_t i = 0, r = 0;
@@ -471,17 +533,7 @@ DEV bool brute_intersect(const DevScene &sc, V3 o, V3 d, float tmax, Hit *h, uin
             stop = brute_curved_run<ANY, CONES>(p, i, cnt, o, d, tmax, b);
         if (ANY && stop) break;
     }
-    if (ANY) return b.found;
-    const bool found = b.bp != 0xffffffffu;
-    if (found) {
-        float inv = 1.0f / b.bd;
-        h->t = b.bn * inv;
-        h->u = b.bu * inv;
-        h->v = b.bv * inv;
-        h->prim = b.bp;
-        h->slot = b.bp;
-    }
-    return found;
+    return brute_finish<ANY>(b, h);
 }
 
 // ---- BVH4 traversal; NodeP / PrimP are global or LDS pointers ------------------------------------

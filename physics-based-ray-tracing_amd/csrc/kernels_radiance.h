@@ -64,7 +64,12 @@ enum { ACCEL_K_BRUTE = 0, ACCEL_K_BVH_GLOBAL = 1, ACCEL_K_BVH_LDS = 2, ACCEL_K_B
 // k_bounce only: ACCEL_K_BRUTE_BIG with the rough / Fresnel conductor code (scenes that hold such a material).  A template
 // argument of that kernel, never a pbrt_scene::accel_kernel: inside the kernel it is ACCEL_K_BRUTE_BIG + GLOSSY.
 enum { ACCEL_K_BRUTE_GLOSSY = 4 };
-__host__ __device__ constexpr int accel_base(int accel) { return accel == ACCEL_K_BRUTE_GLOSSY ? ACCEL_K_BRUTE_BIG : accel; }
+// k_bounce only: ACCEL_K_BRUTE on a scene whose two primitive lists are class-ordered (DevScene::prim_ord): the walks read no run
+// table (device_scene.h brute_intersect ORDERED).  Like _GLOSSY a template argument only; inside the kernel it is ACCEL_K_BRUTE.
+enum { ACCEL_K_BRUTE_ORDERED = 5 };
+__host__ __device__ constexpr int accel_base(int accel) {
+    return accel == ACCEL_K_BRUTE_GLOSSY ? ACCEL_K_BRUTE_BIG : accel == ACCEL_K_BRUTE_ORDERED ? ACCEL_K_BRUTE : accel;
+}
 __host__ __device__ constexpr uint32_t rad_region_segs(int accel) {
     return (accel == ACCEL_K_BVH_GLOBAL || accel == ACCEL_K_BVH_LDS) ? REGION_SEGS_BVH : REGION_SEGS_BRUTE;
 }
@@ -227,10 +232,12 @@ __host__ __device__ constexpr uint32_t ilog2_c(uint32_t v) { return v <= 1u ? 0u
 
 // SEGMENT: the ray is a segment between two points of the scene (next-event shadow ray): brute-force
 // scenes then only walk the primitives that can occlude such a segment (DevScene::occ_prims).
-template <int ACCEL, bool ANY, bool SEGMENT = false>
+// ORDERED: brute-force scenes whose lists are class-ordered (DevScene::prim_ord) walk them without the run tables.
+template <int ACCEL, bool ANY, bool SEGMENT = false, bool ORDERED = false>
 DEV bool scene_intersect(const DevScene &sc, const LdsScene &ls, V3 o, V3 d, float tmax, Hit *h, uint32_t keep = 0xffffffffu) {
+    static_assert(!ORDERED || ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG, "ordered walk: brute-force kernels only");
     if (ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG)
-        return brute_intersect<ANY, SEGMENT, ACCEL != ACCEL_K_BRUTE>(sc, o, d, tmax, h, keep);
+        return brute_intersect<ANY, SEGMENT, ACCEL != ACCEL_K_BRUTE, ORDERED>(sc, o, d, tmax, h, keep);
     if (ACCEL == ACCEL_K_BVH_GLOBAL) return bvh_intersect<ANY>(TreeGlobal{sc.nodes, sc.lprims}, sc.prims, ls.stk, o, d, tmax, h);
     return bvh_intersect<ANY>(ls.tree, sc.prims, ls.stk, o, d, tmax, h);
 }
@@ -384,14 +391,15 @@ DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka
 // keep: the primitives the closest-hit walk may leave out (device_scene.h brute_intersect); the shadow walk sees them all.
 // GLOSSY: as shade_step.  Only k_bounce of the brute-force scenes has instances without it: every other kernel that comes through
 // here (the diagnostic build's launch structures, on the _BIG tables) always carries the arms.
-template <int ACCEL, bool HAVE_HIT = false, bool GLOSSY = ACCEL != ACCEL_K_BRUTE>
+// ORDERED: as scene_intersect (the ACCEL_K_BRUTE_ORDERED instances of k_bounce).
+template <int ACCEL, bool HAVE_HIT = false, bool GLOSSY = ACCEL != ACCEL_K_BRUTE, bool ORDERED = false>
 DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsrc r_L, uint32_t depth, uint32_t ka, uint32_t kb,
                      uint32_t home, float tmax, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, bool &did_seg,
                      bool &did_shadow, const Hit *h_in = nullptr, uint32_t keep = 0xffffffffu) {
     bool survive = false;
     Hit h;
     if (HAVE_HIT) h = *h_in;
-    if (HAVE_HIT || scene_intersect<ACCEL, false>(a.sc, ls, o, d, tmax, &h, keep)) {
+    if (HAVE_HIT || scene_intersect<ACCEL, false, false, ORDERED>(a.sc, ls, o, d, tmax, &h, keep)) {
         did_seg = true;
         const pbrt_prim &P = tb.prims_by_slot[h.slot];
         const SI si = make_si<ACCEL != ACCEL_K_BRUTE>(P, o, d, h.t, h.u, h.v, a.sc.vnormals, h.slot);
@@ -403,7 +411,7 @@ DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsr
                 return smax > 0.0f;
 #else
                 Hit hs;
-                return !scene_intersect<ACCEL, true, true>(a.sc, ls, so, sdir, smax, &hs);
+                return !scene_intersect<ACCEL, true, true, ORDERED>(a.sc, ls, so, sdir, smax, &hs);
 #endif
             },
             [&](V3 A, V3 B) { L = {fma_(A.x, B.x, L.x), fma_(A.y, B.y, L.y), fma_(A.z, B.z, L.z)}; });
@@ -425,7 +433,8 @@ DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsr
 // per bounce, same RNG keys: the film does not change.  Which depths start a two-bounce launch is the host's fuse plan
 // (pbrt_api.hip PBRT_DEFAULT_FUSE_PLAN: every pair).
 // ACCEL_T: ACCEL_K_*, or ACCEL_K_BRUTE_GLOSSY for the instances of brute-force scenes with a ROUGHCONDUCTOR / CONDUCTOR_FRESNEL
-// material; the fused BVH bounce of the diagnostic build always carries those arms.
+// material; the fused BVH bounce of the diagnostic build always carries those arms.  ACCEL_K_BRUTE_ORDERED: the instances of
+// ACCEL_K_BRUTE scenes with class-ordered lists.
 template <bool FIRST, int ACCEL_T, int NB = 1>
 // two-bounce variants of ACCEL_K_BRUTE at the 64-register budget: 8 waves per SIMD with ONE spilled VGPR (a 4-byte scratch store
 // and load per bounce).  Without the budget the kernel takes 67 VGPRs = 7 waves, i.e. three 512-thread workgroups per CU instead of
@@ -441,10 +450,11 @@ template <bool FIRST, int ACCEL_T, int NB = 1>
 #ifndef GLOSSY_WAVES_PER_EU
 #define GLOSSY_WAVES_PER_EU 4
 #endif
-__global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_K_BRUTE_GLOSSY ? GLOSSY_WAVES_PER_EU : NB > 1 ? (ACCEL_T == ACCEL_K_BRUTE ? FUSED_WAVES_PER_EU : BIG_WAVES_PER_EU) : seg_waves_per_eu(ACCEL_T)) void k_bounce(const RadArgs a) {
+__global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_K_BRUTE_GLOSSY ? GLOSSY_WAVES_PER_EU : NB > 1 ? (accel_base(ACCEL_T) == ACCEL_K_BRUTE ? FUSED_WAVES_PER_EU : BIG_WAVES_PER_EU) : seg_waves_per_eu(accel_base(ACCEL_T))) void k_bounce(const RadArgs a) {
     constexpr int ACCEL = accel_base(ACCEL_T);
     static_assert(NB == 1 || ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG, "fused bounces: brute-force kernels only");
     constexpr bool GL = ACCEL_T == ACCEL_K_BRUTE_GLOSSY || ACCEL == ACCEL_K_BVH_GLOBAL || ACCEL == ACCEL_K_BVH_LDS;
+    constexpr bool ORD = ACCEL_T == ACCEL_K_BRUTE_ORDERED;
     // the per-bounce survivor counts of a chain are packed 10 bits each per WORKGROUP and summed by thread 0: one segment per region,
     // workgroup-level compaction (a -DREGION_SEGS_BRUTE build would silently lose them)
     static_assert(NB == 1 || (rad_region_segs(ACCEL) == 1 && !rad_wave_private(ACCEL) && seg_threads(ACCEL) <= 1023),
@@ -608,7 +618,7 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
             if (probe == 12345.678f) o.x = probe;  // never true; keeps the chain alive
         }
 #endif
-        survive = bounce_step<ACCEL, false, GL>(a, tb, ls, r_L, depth, ka, kb, home, tmax, o, d, thr, L, eta, prev_pdf, did_seg, did_shadow,
+        survive = bounce_step<ACCEL, false, GL, ORD>(a, tb, ls, r_L, depth, ka, kb, home, tmax, o, d, thr, L, eta, prev_pdf, did_seg, did_shadow,
                                                 nullptr, keep);
     }
     keep = 0xffffffffu;  // the later bounces of the launch are no camera rays

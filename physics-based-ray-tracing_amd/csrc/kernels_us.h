@@ -686,8 +686,11 @@ __global__ __launch_bounds__(256) void k_ray_intersect(DevScene sc, uint32_t n, 
     BVH_STACK_LDS(ACCEL, 256);
     LdsScene ls = {NO_TREE_LDS, MAKE_BVH_STACK(bvh_stk_lds, 256)};
     Hit h;
-    bool f = scene_intersect<ACCEL, false>(sc, ls, v3(o[i], o[n + i], o[2 * n + i]), v3(d[i], d[n + i], d[2 * n + i]),
-                                           tmax[i], &h);
+    const V3 ro = v3(o[i], o[n + i], o[2 * n + i]), rd = v3(d[i], d[n + i], d[2 * n + i]);
+    constexpr bool BRUTE = ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG;
+    // (a uniform branch, not an instance: a class-ordered brute-force scene is walked without its run tables)
+    bool f = BRUTE && sc.prim_ord ? scene_intersect<ACCEL, false, false, BRUTE>(sc, ls, ro, rd, tmax[i], &h)
+                                 : scene_intersect<ACCEL, false>(sc, ls, ro, rd, tmax[i], &h);
     t[i] = f ? h.t : K_INF;
     prim[i] = f ? h.prim : 0xffffffffu;
     u[i] = f ? h.u : 0.0f;
@@ -702,10 +705,11 @@ __global__ __launch_bounds__(256) void k_ray_test(DevScene sc, uint32_t n, const
     BVH_STACK_LDS(ACCEL, 256);
     LdsScene ls = {NO_TREE_LDS, MAKE_BVH_STACK(bvh_stk_lds, 256)};
     Hit h;
-    hit[i] = scene_intersect<ACCEL, true>(sc, ls, v3(o[i], o[n + i], o[2 * n + i]), v3(d[i], d[n + i], d[2 * n + i]),
-                                          tmax[i], &h)
-                 ? 1
-                 : 0;
+    const V3 ro = v3(o[i], o[n + i], o[2 * n + i]), rd = v3(d[i], d[n + i], d[2 * n + i]);
+    constexpr bool BRUTE = ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG;
+    const bool f = BRUTE && sc.prim_ord ? scene_intersect<ACCEL, true, false, BRUTE>(sc, ls, ro, rd, tmax[i], &h)
+                                       : scene_intersect<ACCEL, true>(sc, ls, ro, rd, tmax[i], &h);
+    hit[i] = f ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void k_bsdf_sample(pbrt_material m, uint32_t quirks, uint32_t n, const float *wi,

@@ -570,6 +570,12 @@ int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
         s->ds.n_prim_runs = (uint32_t)runs.size();
         UP(upload(s, occ_runs.data(), occ_runs.size(), &s->ds.occ_runs));
         s->ds.n_occ_runs = (uint32_t)occ_runs.size();
+        // an ordered scene: BOTH lists class-ordered (the occluders are a sub-sequence of the primitives, checked all the same)
+        uint32_t cnt[3], occ_cnt[3];
+        if (prim_runs_ordered(runs, cnt) && prim_runs_ordered(occ_runs, occ_cnt) && prim_ord_pack(cnt) && prim_ord_pack(occ_cnt)) {
+            s->ds.prim_ord = prim_ord_pack(cnt);
+            s->ds.occ_ord = prim_ord_pack(occ_cnt);
+        }
     } else {
         HostBvh bvh;
         // (a tree whose leaf records alone exceed the LDS stays in global memory whatever its shape: the SAH constant of those trees)
@@ -710,11 +716,14 @@ static Switches read_switches() {
 // The fused bounce kernel of a launch that walks nb bounces (>= 2: the multi-bounce variants of the brute-force kernels,
 // kernels_radiance.h; a.nb = nb).  Glossy brute-force scenes have instances of their own.  nullptr: BVH scenes run k_trace /
 // k_shade (wf_bounces); their fused bounce (PBRT_FILM_NO_HIT_POOL) and k_walk exist in the diagnostic build only (diag_driver.h).
-static RadKern bounce_kernel(const pbrt_scene *s, bool first, uint32_t nb) {
+// ordered: the launch's lists are class-ordered (RadArgs::sc.prim_ord != 0: the scene's, unless PBRT_FILM_NO_ORDERED_WALK took it back):
+// ACCEL_K_BRUTE then runs the instances that walk them without the run tables; the _BIG / glossy instances keep the table walk.
+static RadKern bounce_kernel(const pbrt_scene *s, bool first, uint32_t nb, bool ordered) {
     const bool two = nb >= 2;
     switch (s->accel_kernel) {
         case ACCEL_K_BRUTE:
-            return with_flags([](auto F, auto N) -> RadKern { return &k_bounce<F(), ACCEL_K_BRUTE, N() ? 2 : 1>; }, first, two);
+            return with_flags([](auto F, auto O, auto N) -> RadKern {
+                return &k_bounce<F(), O() ? ACCEL_K_BRUTE_ORDERED : ACCEL_K_BRUTE, N() ? 2 : 1>; }, first, ordered, two);
         case ACCEL_K_BRUTE_BIG:
             return with_flags([](auto F, auto G, auto N) -> RadKern {
                 return &k_bounce<F(), G() ? ACCEL_K_BRUTE_GLOSSY : ACCEL_K_BRUTE_BIG, N() ? 2 : 1>; }, first, s->glossy, two);
@@ -723,7 +732,7 @@ static RadKern bounce_kernel(const pbrt_scene *s, bool first, uint32_t nb) {
     }
 }
 static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool first, uint32_t nb = 1) {
-    const RadKern k = bounce_kernel(s, first, nb);
+    const RadKern k = bounce_kernel(s, first, nb, a.sc.prim_ord != 0u);
     if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_bounce: no fused bounce kernel for accelerator %d in this build", s->accel_kernel);
     hipLaunchKernelGGL(k, dim3(nseg), dim3(seg_threads(s->accel_kernel)), 0u, s->ctx->stream, a);
     return PBRT_OK;
@@ -1479,7 +1488,9 @@ static int render_args(Render &r) {
         base.sc.n_occ = base.sc.n_prims;
         base.sc.occ_runs = base.sc.prim_runs;
         base.sc.n_occ_runs = base.sc.n_prim_runs;
+        base.sc.occ_ord = base.sc.prim_ord;
     }
+    if (f->flags & PBRT_FILM_NO_ORDERED_WALK) base.sc.prim_ord = base.sc.occ_ord = 0u;  // diagnostic: the table-walk instances (launch_bounce)
     base.cam = *r.cam;
     base.Lhome = r.Lhome;
     base.stats = r.segstats;
