@@ -23,7 +23,9 @@ from __future__ import annotations
 
 import ctypes as C
 import copy
+import dataclasses
 import math
+import time
 
 import numpy as np
 
@@ -817,28 +819,198 @@ class FilteredDelayMultiplyAndSum(_NonlinearBeamformer):
     _method, _centre = "fdmas", 2.0
 
 
-class _RenderPlan:
-    """Device buffers of one us_render configuration (acquisition shape, scan grid): allocated once, reused by every call of the
-    reference's loop (USMain.py:262-289 calls us_render 50 times on one scene)."""
+# ---- us_render in stages: a request record, one statement of the chain, a plan that owns its buffers and its recording ------------
+@dataclasses.dataclass
+class _UsRenderRequest:
+    """One us_render call as its stages read it: the integrator, the arguments and what follows from them alone.  Made by
+    _us_render_request without a device; every ValueError of us_render is raised there."""
+    integ: object
+    A: int
+    E: int
+    T: int
+    x_scan: np.ndarray          # the axes of the display image                                        (USMain.py:193-194)
+    z_scan: np.ndarray
+    scan: object                # what the beamformer runs on: a GridScan on the axes, or the PolarScan of scan="polar"
+    polar: bool
+    theta_range: tuple          # (polar) the sector's angles as floats, else None
+    probe: Probe
+    bf: DelayAndSum             # the beamformer that runs: the caller's, a copy of it that beamforms I/Q data, or a DelayAndSum
+    iq: bool
+    D: int                      # decimation (1 without iq)
+    f_demod: float              # (iq) the frequency rf2iq demodulates at, else None
+    lp: np.ndarray              # (iq) rf2iq's low-pass taps, else None
+    taps: np.ndarray            # (p-DAS / F-DMAS with a band) the band-pass taps of this scan, else None
+    fs_img: float               # the rate of the data the beamformer is given
+    gaussian: bool              # the pulse is applied after the acquisition (pulse_model 'gaussian')
+    seq: dict
+    seed: object
+    paths_per_ray: object
+    dynamic_range: float
 
-    def __init__(self, cx, A, E, T, elem_x, x_scan, z_scan, gaussian, taps=None, iq=None, polar=None):
-        self.key = None
-        self.cx = cx
+    def info(self, delays):
+        """the acquisition_info of the beamformer (USMain.py:138-172) for delays on the host or in HBM"""
+        return {"sampling_freq": self.fs_img, "t0": 0, "prf": None, "signal_duration": None, "delays": delays,
+                "sound_speed": self.integ.sound_speed, "sequence_elements": self.seq}
+
+    def plan_key(self, cx):
+        """what the buffers of a _RenderPlan and their constant contents depend on"""
+        return (self.A, self.E, self.T,                                  # the shapes of d_channel, d_rf, d_tx, d_iq and d_table
+                float(self.integ.pitch),                                 # d_ex: the element positions of a linear array
+                self.x_scan.tobytes(), self.z_scan.tobytes(),            # d_x, d_z and the shapes of d_bf, d_env, d_img
+                self.gaussian,                                           # d_rf exists
+                id(cx),                                                  # the context that owns the memory
+                self.probe.geometry_type, self.probe.radius, self.probe.opening_angle,   # d_ex: positions, or an arc's element table
+                None if self.taps is None else self.taps.tobytes(),      # d_taps, and d_nl exists
+                self.iq, self.D if self.iq else 1,                       # d_iq, d_bf_iq exist; the decimated length of d_iq
+                None if self.lp is None else self.lp.tobytes(),          # d_iq_taps
+                self.theta_range if self.polar else None,                # d_px, d_pz: the sector's angles ...
+                len(self.scan.thetas) if self.polar else None)           # ... and their count: the shapes of d_bf, d_env_sec
+
+    def graph_key(self, scene):
+        """what the queued calls depend on besides the CONTENTS of device memory: a recording of them stands for exactly this key.
+        (The reference's loop, USMain.py:262-289, repeats one key 100 times and changes a material's roughness in between:
+        pbrt_scene_update_material writes device memory, the replay sees it.)"""
+        integ, h = self.integ, scene.device().handle
+        return (bytes(integ.us_params(scene, integ.quirks)),             # the acquisition's parameter block, by value in the launch
+                getattr(h, "value", h),                                  # the device scene it traces
+                int(integ.seed if self.seed is None else self.seed) & 0xFFFFFFFF,   # an argument of the acquisition
+                int(self.paths_per_ray if self.paths_per_ray is not None else integ.paths_per_ray),   # one more
+                float(self.dynamic_range),                               # an argument of the log compression
+                type(self.bf).__name__,                                  # which beamform kernel runs, and whether a band-pass follows
+                tuple(sorted(self.bf.setups.items())),                   # its parameter block: f-number, interpolation, window, p, band
+                float(integ.pulse_sigma) if self.gaussian else None,     # an argument of apply_pulse
+                (self.D, self.f_demod) if self.iq else None,             # arguments of rf2iq and of the I/Q beamformer
+                (self.theta_range, self.scan.shape) if self.polar else None)   # the parameter block of scan_convert
+
+
+def _request_scan(x_range, z_range, step, scan, theta_range, convex, opening_angle):
+    """(x_scan, z_scan, the scan the beamformer runs on, theta_range as floats or None) of a us_render call"""
+    x_scan = np.arange(x_range[0], x_range[1] + step, step)                                            # :193
+    z_scan = np.arange(z_range[0], z_range[1] + step, step)                                            # :194
+    if scan not in ("grid", "polar"):
+        raise ValueError(f"us_render: scan must be 'grid' or 'polar', got {scan!r}")
+    if scan == "grid":
+        if theta_range is not None:
+            raise ValueError("us_render: theta_range belongs to scan='polar'")
+        return x_scan, z_scan, GridScan(x_scan, z_scan), None
+    if theta_range is None and convex:      # the arc's own opening angle
+        theta_range = (-np.radians(float(opening_angle)) / 2.0, np.radians(float(opening_angle)) / 2.0)
+    elif theta_range is None:               # the x-range seen from the deepest z
+        theta_range = (np.arctan(x_range[0] / z_range[1]), np.arctan(x_range[1] / z_range[1]))
+    theta_range = (float(theta_range[0]), float(theta_range[1]))
+    rhos = z_scan   # measured from the origin of the probe's frame, as the scan's z is
+    return x_scan, z_scan, PolarScan(rhos, np.linspace(theta_range[0], theta_range[1], polar_n_theta(rhos[-1], theta_range, step))), theta_range
+
+
+def _request_iq(integ, bf, iq, decimation):
+    """(the beamformer that runs, iq, D, f_demod, lp): the rules of the I/Q chain (DESIGN D20)"""
+    iq, D = bool(iq) or bf.is_iq, int(decimation)      # (a beamformer that has is_iq set selects the I/Q chain by itself)
+    if not iq:
+        if D != 1:
+            raise ValueError("us_render: decimation belongs to the I/Q chain (iq=True)")
+        return bf, False, D, None, None
+    if not bf.is_iq:
+        # the caller's beamformer keeps its setups: this call works on a copy of it that beamforms I/Q data (p-DAS / F-DMAS:
+        # NotImplementedError)
+        bf = copy.copy(bf)
+        bf.setups = dict(bf.setups)
+        bf.set_is_iq(True)
+    # the frequency rf2iq demodulates at is the one the walk turns back by: the setup `demod_freq`, else the integrator's
+    f_demod = float(integ.frequency if bf.setups["demod_freq"] is None else bf.setups["demod_freq"])
+    if not 1 <= D <= RF2IQ_MAX_DECIMATION or D != decimation:
+        raise ValueError(f"us_render: decimation must be an integer in [1, {RF2IQ_MAX_DECIMATION}], got {decimation}")
+    if -(-integ.time_samples // D) < 2:
+        raise ValueError(f"us_render: {integ.time_samples} samples decimated by {D} leave fewer than two")
+    # rf2iq's default low-pass (bandwidth = 100): refused here, before anything is acquired, when the decimation does not fit
+    return bf, True, D, f_demod, _rf2iq_lowpass(f_demod, float(integ.fs), 100, D)
+
+
+def _us_render_request(integ, x_range, z_range, dynamic_range, step, seed, paths_per_ray, beamformer, iq, decimation, scan, theta_range):
+    """the request of a us_render call; its refusals in the order scan, probe, I/Q rules, band"""
+    A, E, T = integ.n_angles, integ.n_elements, integ.time_samples
+    lam = integ.sound_speed / integ.frequency
+    step = step or lam / 4                                                                             # :189-191
+    convex = float(getattr(integ, "radius", 0.0)) != 0.0
+    x_scan, z_scan, scan, theta_range = _request_scan(x_range, z_range, step, scan, theta_range, convex, getattr(integ, "opening_angle", 0.0))
+    if convex:  # the curved array (DESIGN D18): element table instead of positions, the *_probe beamformer
+        probe = build_probe("convex", E, integ.pitch, integ.frequency, 70, radius=integ.radius, opening_angle=integ.opening_angle)
+    else:
+        probe = build_probe("linear", E, integ.pitch, integ.frequency, 70)                             # :130-136
+    bf, iq, D, f_demod, lp = _request_iq(integ, beamformer or DelayAndSum(on_gpu=True), iq, decimation)
+    # (p-DAS / F-DMAS: the band-pass taps of this scan -- refused here, before anything is acquired, when the band does not fit
+    # under the Nyquist frequency of the depth step: the reference's lambda / 4 grid puts that AT the carrier, DESIGN D19)
+    taps = bf.filter_taps(scan, integ.sound_speed, probe) if isinstance(bf, _NonlinearBeamformer) else None
+    seq = {"emitted": np.tile(np.arange(E), (A, 1)), "received": np.tile(np.arange(E), (A, 1))}
+    return _UsRenderRequest(integ=integ, A=A, E=E, T=T, x_scan=x_scan, z_scan=z_scan, scan=scan, polar=isinstance(scan, PolarScan),
+                            theta_range=theta_range, probe=probe, bf=bf, iq=iq, D=D, f_demod=f_demod, lp=lp, taps=taps,
+                            fs_img=integ.fs / D if iq else integ.fs, gaussian=integ.pulse_model == "gaussian", seq=seq, seed=seed,
+                            paths_per_ray=paths_per_ray, dynamic_range=dynamic_range)
+
+
+class _HostBuffers:
+    """the buffers of the chain in its host form: none -- every step hands back a host array of its own"""
+    d_rf = d_iq_taps = d_iq = d_bf = d_bf_iq = d_table = d_env_sec = d_env = d_img = d_x = d_z = None
+
+
+def _form_image(rq, data, delays, b):
+    """The image-formation chain of us_render, stated once: channel data -> [pulse] -> [rf2iq] -> beamform -> envelope or modulus ->
+    [scan_convert] -> log compression -> (display image [nx, nz], envelope [nx, nz]).  data and delays in HBM: the device forms, queued,
+    on the buffers `b` of a _RenderPlan.  On the host (b: _HostBuffers) the host-pointer forms: the pulse was applied inside the
+    acquisition, the data get the frame axis USMain.py hands on (reader.data) and the envelope is brought to float32."""
+    dev, integ, bf, scan = _is_dev(data), rq.integ, rq.bf, rq.scan
+    if rq.gaussian and dev:                                                                            # f-3: carrier on the device
+        data = apply_pulse(data, integ.fs, integ.frequency, integ.pulse_sigma, out=b.d_rf)
+    bf.automatic_setup(rq.info(delays), rq.probe)                                                      # :175
+    if rq.iq:                                                                                          # D20: baseband, then complex DAS
+        data = rf2iq(data, rq.f_demod, integ.fs, decimation=rq.D, taps=b.d_iq_taps if dev else rq.lp, out=b.d_iq)
+    img = bf.beamform(data if dev else data[np.newaxis], scan, out=b.d_bf_iq if rq.iq else b.d_bf, table=b.d_table)      # :204
+    env = bf.compute_envelope(img, scan, out=b.d_env_sec if rq.polar else b.d_env)                     # :205 (I/Q: the modulus)
+    if not dev:
+        env = env.astype(np.float32)                                                                   # :207
+    if rq.polar:                                                                                       # D21: sector -> the grid
+        env = scan_convert(env, scan, *((b.d_x, b.d_z) if dev else (rq.x_scan, rq.z_scan)), fill=0.0, out=b.d_env)
+    return log_compress(env, rq.dynamic_range, out=b.d_img), env                                       # :210-218
+
+
+def _render_host(scene, rq):
+    """device_resident=False: the acquisition and every step of the chain through the host-pointer entry points"""
+    integ = rq.integ
+    if rq.seed is not None or rq.paths_per_ray is not None:
+        integ.channel_buf = integ._acquire(scene, integ.quirks, paths_per_ray=rq.paths_per_ray, seed=rq.seed)
+    else:
+        integ.simulate_acquisition_parallel(scene)                                                     # :99
+    data = np.asarray(integ.channel_buf, dtype=np.float32).reshape(rq.A, rq.E, rq.T)                   # :118
+    delays = np.asarray(integ.transmission_delays_buf, dtype=np.float32).reshape(rq.A, rq.E)           # :121
+    display, bmode = _form_image(rq, data, delays, _HostBuffers)
+    return display.T, bmode, (rq.x_scan, rq.z_scan)                                                    # :221
+
+
+class _RenderPlan:
+    """Device buffers of one us_render configuration (_UsRenderRequest.plan_key: acquisition shape, scan grid, chain): allocated once,
+    reused by every call of the reference's loop (USMain.py:262-289 calls us_render 50 times on one scene), with the state that goes
+    with their contents -- the delays and the sound speed d_tx and d_table were made with, and the recording.
+    The recording: from the third call in a row with one _UsRenderRequest.graph_key on, the queued calls are replayed from it
+    (pbrt_ctx_record_begin / pbrt_graph_launch: one submission instead of eleven; same kernels, same bits).  A call runs replay(), and
+    queue() where that says no; queue() records the chain at the second call in a row with a key, when the workspace is warm.
+    graph_key: the key `graph` stands for; warm_key: that of the last queued call; no_graph_key: one whose chain cannot be recorded."""
+
+    def __init__(self, cx, rq, key):
+        A, E, T = rq.A, rq.E, rq.T
+        self.key, self.cx = key, cx
         self.d_channel = _capi.DeviceBuffer(cx, (A, E, T))
-        self.d_rf = _capi.DeviceBuffer(cx, (A, E, T)) if gaussian else None
+        self.d_rf = _capi.DeviceBuffer(cx, (A, E, T)) if rq.gaussian else None
         self.d_tx = _capi.DeviceBuffer(cx, (A, E))
-        self.tx_host = None
-        self.table_c = None   # the sound speed d_table was made with
-        self.d_ex = _capi.DeviceBuffer.from_host(cx, _capi.f32(elem_x))
-        self.d_x = _capi.DeviceBuffer.from_host(cx, _capi.f32(x_scan))
-        self.d_z = _capi.DeviceBuffer.from_host(cx, _capi.f32(z_scan))
+        self.tx_host = self.table_c = None   # the delays d_tx holds, the sound speed d_table was made with
+        self.d_ex = _capi.DeviceBuffer.from_host(cx, _capi.f32(rq.probe.das_elements))
+        self.d_x = _capi.DeviceBuffer.from_host(cx, _capi.f32(rq.x_scan))
+        self.d_z = _capi.DeviceBuffer.from_host(cx, _capi.f32(rq.z_scan))
         # polar (a PolarScan, DESIGN D21): the beamformer's buffers have the sector's shape, d_px / d_pz are its pixel tables, d_env_sec
         # its envelope; d_env is then the scan-converted envelope on the Cartesian grid, which d_img always has
         self.d_px = self.d_pz = self.d_env_sec = None
-        gx, gz = len(x_scan), len(z_scan)
-        nx, nz = (gx, gz) if polar is None else polar.shape
-        if polar is not None:
-            px, pz = polar.pixels()
+        gx, gz = len(rq.x_scan), len(rq.z_scan)
+        nx, nz = rq.scan.shape
+        if rq.polar:
+            px, pz = rq.scan.pixels()
             self.d_px, self.d_pz = _capi.DeviceBuffer.from_host(cx, px), _capi.DeviceBuffer.from_host(cx, pz)
             self.d_env_sec = _capi.DeviceBuffer(cx, (nx, nz))
         self.d_bf = _capi.DeviceBuffer(cx, (nx, nz))
@@ -846,17 +1018,96 @@ class _RenderPlan:
         self.d_img = _capi.DeviceBuffer(cx, (gx, gz))
         self.d_table = _capi.DeviceBuffer(cx, (A, nx, nz), np.float64)   # first-arrival times of this scan (das_first_arrival)
         # p-DAS / F-DMAS with a band: the band-pass taps, and the image before the filter
-        self.d_taps = _capi.DeviceBuffer.from_host(cx, taps) if taps is not None else None
-        self.d_nl = _capi.DeviceBuffer(cx, (nx, nz)) if taps is not None else None
-        # the I/Q chain (iq = (decimation, low-pass taps)): the taps, the demodulated channel data and the complex image
+        self.d_taps = _capi.DeviceBuffer.from_host(cx, rq.taps) if rq.taps is not None else None
+        self.d_nl = _capi.DeviceBuffer(cx, (nx, nz)) if rq.taps is not None else None
+        # the I/Q chain: the low-pass taps, the demodulated channel data and the complex image
         self.d_iq_taps = self.d_iq = self.d_bf_iq = None
-        if iq is not None:
-            D, lp = iq
-            self.d_iq_taps = _capi.DeviceBuffer.from_host(cx, lp)
-            self.d_iq = _capi.DeviceBuffer(cx, (A, E, -(-T // D)), np.complex64)
+        if rq.iq:
+            self.d_iq_taps = _capi.DeviceBuffer.from_host(cx, rq.lp)
+            self.d_iq = _capi.DeviceBuffer(cx, (A, E, -(-T // rq.D)), np.complex64)
             self.d_bf_iq = _capi.DeviceBuffer(cx, (nx, nz), np.complex64)
-        # the queued chain of one key as a recording (pbrt_graph), made at the second call in a row with that key
         self.graph = self.graph_key = self.warm_key = self.no_graph_key = None
+
+    @classmethod
+    def of(cls, cx, rq):
+        """the plan the integrator keeps, or a new one where the request's plan key is another; bound to the request"""
+        key = rq.plan_key(cx)
+        plan = getattr(rq.integ, "_render_plan", None)
+        if plan is None or plan.key != key:
+            plan = rq.integ._render_plan = cls(cx, rq, key)
+        plan.bind(rq)
+        return plan
+
+    def bind(self, rq):
+        """the tables this plan holds in HBM, handed to the request's scan and beamformer, which use them where the data is in HBM"""
+        if rq.polar:
+            rq.scan.d_px, rq.scan.d_pz = self.d_px, self.d_pz
+        else:
+            rq.scan.d_x, rq.scan.d_z = self.d_x, self.d_z
+        rq.bf.probe_dev = self.d_ex
+        if isinstance(rq.bf, _NonlinearBeamformer):
+            rq.bf.scratch_dev = self.d_nl
+            if rq.taps is not None:
+                rq.bf._taps_cache = (rq.taps.tobytes(), self.d_taps)
+
+    def refresh_delays(self, delays, sound_speed):
+        """d_tx and d_table for the delays [A, E] an acquisition handed back and the integrator's sound speed.  The scan's first-arrival
+        times follow the delays, the sound speed and the grid: made again only when those change (never, in the loop of
+        USMain.py:262-289; a single 0 degree angle has zero delays at every sound speed), and the recording, which reads both, is
+        dropped with them."""
+        if self.tx_host is not None and np.array_equal(self.tx_host, delays) and self.table_c == float(sound_speed):
+            return
+        self.d_tx.upload(delays)
+        self.tx_host, self.table_c = delays.copy(), float(sound_speed)
+        if self.d_px is not None:
+            scan_first_arrival(self.d_tx, self.d_ex, self.d_px, self.d_pz, sound_speed, out=self.d_table)
+        else:
+            das_first_arrival(self.d_tx, self.d_ex, self.d_x, self.d_z, sound_speed, out=self.d_table)
+        self.graph = self.graph_key = self.warm_key = None
+
+    def replay(self, rq, gkey) -> bool:
+        """launch the recording if it stands for gkey, and leave on the integrator and the beamformer what the queued calls would have;
+        False: nothing was submitted"""
+        if gkey is None or self.graph is None or self.graph_key != gkey:
+            return False
+        try:
+            self.graph.launch()
+        except RuntimeError:
+            # stale (the context freed or replaced memory the recording refers to): the caller queues the chain the plain way.
+            # ADVICE.md finding 1: every failure of the launch lands here, a deferred device error of the queued work included.
+            self.graph = self.graph_key = None
+            return False
+        rq.integ.transmission_delays_buf = self.tx_host.reshape(-1).copy()
+        rq.integ._ray_count = None
+        rq.integ._stats_ctx = self.cx
+        rq.bf.automatic_setup(rq.info(self.d_tx), rq.probe)
+        return True
+
+    def _acquire(self, scene, rq):
+        integ = rq.integ
+        integ._acquire(scene, integ.quirks, paths_per_ray=rq.paths_per_ray, seed=rq.seed, out_dev=self.d_channel.ptr, pulse=False,
+                       queue=True)                                                                     # :99 (queued, not waited for)
+
+    def queue(self, scene, rq, gkey) -> float:
+        """queue the acquisition and the chain call by call -> the time at which the acquisition was queued.  At the second call in a
+        row with gkey the chain is queued once more inside a recording, for the calls that follow."""
+        self._acquire(scene, rq)
+        t1 = time.perf_counter()
+        self.refresh_delays(np.asarray(rq.integ.transmission_delays_buf, dtype=np.float32).reshape(rq.A, rq.E), rq.integ.sound_speed)   # :121
+        _form_image(rq, self.d_channel, self.d_tx, self)
+        if gkey is not None and self.warm_key == gkey and self.no_graph_key != gkey:
+            try:
+                with self.cx.record() as rec:
+                    self._acquire(scene, rq)
+                    _form_image(rq, self.d_channel, self.d_tx, self)
+                self.graph, self.graph_key = rec.graph, gkey
+            except RuntimeError:
+                # (a chain that cannot be recorded -- e.g. a pass whose size follows the free device memory of the moment -- is
+                # queued call by call from now on, not tried again at every call)
+                self.graph = self.graph_key = None
+                self.no_graph_key = gkey
+        self.warm_key = gkey
+        return t1
 
 
 def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range=60.0, step=None, seed=None,
@@ -872,8 +1123,8 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     device_resident=False is round 4's path through the host-pointer entry points (every step up and down PCIe), kept for the
     A/B and the bit-for-bit test.  timing: a dict that receives host wall-clock seconds (acquire, queue, wait_copy).
     graph (default): from the third call in a row with the same arguments on, the queued calls are replayed from a recording
-    (pbrt_ctx_record_begin / pbrt_graph_launch: one submission instead of eleven; same kernels, same bits); graph=False, or a
-    context that profiles (Context.set_profiling), queues them one by one.
+    (_RenderPlan: one submission, same kernels, same bits); graph=False, or a context that profiles (Context.set_profiling), queues
+    them one by one.
     on_device: nothing is copied and nothing waits -- the display image and the envelope come back as DeviceBuffers [nx, nz] (the
     reference's display image is their transpose), still being written by the queued kernels; a caller that keeps its loss on
     the GPU (USMain.py:5 imports torch: `torch.as_tensor(buf, device="cuda")` through __cuda_array_interface__) calls
@@ -890,185 +1141,23 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     (polar_n_theta); the envelope (or modulus) is taken along rho, the propagation direction of every ray, and scan_convert brings it
     onto the Cartesian grid of "grid" (0 outside the sector) before the log compression.  The display image, the returned envelope
     and the axes have the shapes "grid" gives; every path above runs this chain."""
-    import time as _time
-    integ = scene.integrator()
-    A, E, T = integ.n_angles, integ.n_elements, integ.time_samples
-    lam = integ.sound_speed / integ.frequency
-    step = step or lam / 4                                                                             # :189-191
-    x_scan = np.arange(x_range[0], x_range[1] + step, step)                                            # :193
-    z_scan = np.arange(z_range[0], z_range[1] + step, step)                                            # :194
-    if scan not in ("grid", "polar"):
-        raise ValueError(f"us_render: scan must be 'grid' or 'polar', got {scan!r}")
-    polar = scan == "polar"
-    if theta_range is not None and not polar:
-        raise ValueError("us_render: theta_range belongs to scan='polar'")
-    convex = float(getattr(integ, "radius", 0.0)) != 0.0
-    scan = GridScan(x_scan, z_scan)
-    if polar:
-        if theta_range is None and convex:      # the arc's own opening angle
-            theta_range = (-np.radians(float(integ.opening_angle)) / 2.0, np.radians(float(integ.opening_angle)) / 2.0)
-        elif theta_range is None:               # the x-range seen from the deepest z
-            theta_range = (np.arctan(x_range[0] / z_range[1]), np.arctan(x_range[1] / z_range[1]))
-        theta_range = (float(theta_range[0]), float(theta_range[1]))
-        rhos = z_scan   # measured from the origin of the probe's frame, as the scan's z is
-        scan = PolarScan(rhos, np.linspace(theta_range[0], theta_range[1], polar_n_theta(rhos[-1], theta_range, step)))
-    if convex:  # the curved array (DESIGN D18): element table instead of positions, the *_probe beamformer
-        probe = build_probe("convex", E, integ.pitch, integ.frequency, 70, radius=integ.radius, opening_angle=integ.opening_angle)
-    else:
-        probe = build_probe("linear", E, integ.pitch, integ.frequency, 70)                             # :130-136
-    bf = beamformer or DelayAndSum(on_gpu=True)
-    iq, D = bool(iq) or bf.is_iq, int(decimation)      # (a beamformer that has is_iq set selects the I/Q chain by itself)
-    if iq and not bf.is_iq:
-        # the caller's beamformer keeps its setups: this call works on a copy of it that beamforms I/Q data (p-DAS / F-DMAS:
-        # NotImplementedError)
-        bf = copy.copy(bf)
-        bf.setups = dict(bf.setups)
-        bf.set_is_iq(True)
-    lp = None
-    f_demod = None
-    if iq:   # the frequency rf2iq demodulates at is the one the walk turns back by: the setup `demod_freq`, else the integrator's
-        f_demod = float(integ.frequency if bf.setups["demod_freq"] is None else bf.setups["demod_freq"])
-    if iq:
-        if not 1 <= D <= RF2IQ_MAX_DECIMATION or D != decimation:
-            raise ValueError(f"us_render: decimation must be an integer in [1, {RF2IQ_MAX_DECIMATION}], got {decimation}")
-        if -(-T // D) < 2:
-            raise ValueError(f"us_render: {T} samples decimated by {D} leave fewer than two")
-        # rf2iq's default low-pass (bandwidth = 100): refused here, before anything is acquired, when the decimation does not fit
-        lp = _rf2iq_lowpass(f_demod, float(integ.fs), 100, D)
-    elif D != 1:
-        raise ValueError("us_render: decimation belongs to the I/Q chain (iq=True)")
-    fs_img = integ.fs / D if iq else integ.fs   # the rate of the data the beamformer is given
-    # (p-DAS / F-DMAS: the band-pass taps of this scan -- refused here, before anything is acquired, when the band does not fit
-    # under the Nyquist frequency of the depth step: the reference's lambda / 4 grid puts that AT the carrier, DESIGN D19)
-    taps = bf.filter_taps(scan, integ.sound_speed, probe) if isinstance(bf, _NonlinearBeamformer) else None
-    seq = {"emitted": np.tile(np.arange(E), (A, 1)), "received": np.tile(np.arange(E), (A, 1))}
-
-    def info(delays):
-        return {"sampling_freq": fs_img, "t0": 0, "prf": None, "signal_duration": None, "delays": delays,
-                "sound_speed": integ.sound_speed, "sequence_elements": seq}
-
+    rq = _us_render_request(scene.integrator(), x_range, z_range, dynamic_range, step, seed, paths_per_ray, beamformer, iq, decimation,
+                            scan, theta_range)
     if not device_resident:
-        if seed is not None or paths_per_ray is not None:
-            integ.channel_buf = integ._acquire(scene, integ.quirks, paths_per_ray=paths_per_ray, seed=seed)
-        else:
-            integ.simulate_acquisition_parallel(scene)                                                 # :99
-        data = np.asarray(integ.channel_buf, dtype=np.float32).reshape(A, E, T)                        # :118
-        delays = np.asarray(integ.transmission_delays_buf, dtype=np.float32).reshape(A, E)             # :121
-        bf.automatic_setup(info(delays), probe)                                                        # :175
-        if iq:
-            data = rf2iq(data, f_demod, integ.fs, decimation=D, taps=lp)
-        bmode = bf.compute_envelope(bf.beamform(data[np.newaxis], scan), scan).astype(np.float32)      # :204-207
-        if polar:
-            bmode = scan_convert(bmode, scan, x_scan, z_scan, fill=0.0)
-        display = log_compress(bmode, dynamic_range).T                                                 # :210-221
-        return display, bmode, (x_scan, z_scan)
-
+        return _render_host(scene, rq)
     cx = scene.device().ctx
-    gaussian = integ.pulse_model == "gaussian"
-    key = (A, E, T, float(integ.pitch), x_scan.tobytes(), z_scan.tobytes(), gaussian, id(cx), probe.geometry_type, probe.radius,
-           probe.opening_angle, None if taps is None else taps.tobytes(), iq, D if iq else 1, None if lp is None else lp.tobytes(),
-           theta_range if polar else None, len(scan.thetas) if polar else None)
-    plan = getattr(integ, "_render_plan", None)
-    if plan is None or plan.key != key:
-        plan = _RenderPlan(cx, A, E, T, probe.das_elements, x_scan, z_scan, gaussian, taps, (D, lp) if iq else None,
-                           scan if polar else None)
-        plan.key = key
-        integ._render_plan = plan
-    rf = plan.d_rf if gaussian else plan.d_channel
-    if polar:
-        scan.d_px, scan.d_pz = plan.d_px, plan.d_pz
-    else:
-        scan.d_x, scan.d_z = plan.d_x, plan.d_z
-    d_env_bf = plan.d_env_sec if polar else plan.d_env   # the envelope on the scan the beamformer ran on
-    bf.probe_dev = plan.d_ex
-    if isinstance(bf, _NonlinearBeamformer):
-        bf.scratch_dev = plan.d_nl
-        if taps is not None:
-            bf._taps_cache = (taps.tobytes(), plan.d_taps)
-
-    def queue_acquisition():
-        integ._acquire(scene, integ.quirks, paths_per_ray=paths_per_ray, seed=seed, out_dev=plan.d_channel.ptr, pulse=False,
-                       queue=True)                                                                      # :99 (queued, not waited for)
-
-    def queue_image_formation():
-        if gaussian:                                                                                   # f-3: carrier on the device
-            apply_pulse(plan.d_channel, integ.fs, integ.frequency, integ.pulse_sigma, out=plan.d_rf)
-        bf.automatic_setup(info(plan.d_tx), probe)                                                     # :175
-        if iq:                                                                                         # D20: baseband, then complex DAS
-            rf2iq(rf, f_demod, integ.fs, decimation=D, taps=plan.d_iq_taps, out=plan.d_iq)
-            bf.beamform(plan.d_iq, scan, out=plan.d_bf_iq, table=plan.d_table)
-            bf.compute_envelope(plan.d_bf_iq, scan, out=d_env_bf)                                      # the modulus
-        else:
-            bf.beamform(rf, scan, out=plan.d_bf, table=plan.d_table)                                   # :204
-            bf.compute_envelope(plan.d_bf, scan, out=d_env_bf)                                         # :205
-        if polar:                                                                                      # D21: sector -> the grid
-            scan_convert(plan.d_env_sec, scan, plan.d_x, plan.d_z, fill=0.0, out=plan.d_env)
-        log_compress(plan.d_env, dynamic_range, out=plan.d_img)                                        # :210-218
-
-    # What the queued calls depend on besides the CONTENTS of device memory: a recording of them (pbrt_ctx_record_begin, one
-    # hipGraph) stands for exactly this key.  The reference's loop (USMain.py:262-289) repeats one key 100 times and changes a
-    # material's roughness in between (pbrt_scene_update_material writes device memory: the replay sees it).
-    t0 = _time.perf_counter()
-    gkey = None
-    if graph and not getattr(cx, "profiling", False):
-        h = scene.device().handle
-        gkey = (bytes(integ.us_params(scene, integ.quirks)), getattr(h, "value", h),
-                int(integ.seed if seed is None else seed) & 0xFFFFFFFF,
-                int(paths_per_ray if paths_per_ray is not None else integ.paths_per_ray), float(dynamic_range),
-                type(bf).__name__, tuple(sorted(bf.setups.items())), float(integ.pulse_sigma) if gaussian else None,
-                (D, f_demod) if iq else None, (theta_range, scan.shape) if polar else None)
-    replayed = False
-    if gkey is not None and plan.graph is not None and plan.graph_key == gkey:
-        try:
-            plan.graph.launch()
-            replayed = True
-        except RuntimeError:        # stale (the context freed or replaced memory the recording refers to): queue it the plain way
-            plan.graph = plan.graph_key = None
-    if replayed:
-        integ.transmission_delays_buf = plan.tx_host.reshape(-1).copy()
-        integ._ray_count = None
-        integ._stats_ctx = cx
-        bf.automatic_setup(info(plan.d_tx), probe)
-        t1 = _time.perf_counter()
-    else:
-        queue_acquisition()
-        t1 = _time.perf_counter()
-        delays = np.asarray(integ.transmission_delays_buf, dtype=np.float32).reshape(A, E)             # :121
-        if plan.tx_host is None or not np.array_equal(plan.tx_host, delays) or plan.table_c != float(integ.sound_speed):
-            plan.d_tx.upload(delays)
-            plan.tx_host = delays.copy()
-            plan.table_c = float(integ.sound_speed)
-            # the scan's first-arrival times follow the delays, the sound speed and the grid: made again only when those change
-            # (never, in the loop of USMain.py:262-289).  (A single 0 degree angle has zero delays at every sound speed.)
-            if polar:
-                scan_first_arrival(plan.d_tx, plan.d_ex, plan.d_px, plan.d_pz, integ.sound_speed, out=plan.d_table)
-            else:
-                das_first_arrival(plan.d_tx, plan.d_ex, plan.d_x, plan.d_z, integ.sound_speed, out=plan.d_table)
-            plan.graph = plan.graph_key = plan.warm_key = None
-        queue_image_formation()
-        if gkey is not None and plan.warm_key == gkey and plan.no_graph_key != gkey:
-            # the second call in a row with this key: the workspace is warm, record the chain for the calls that follow
-            try:
-                with cx.record() as rec:
-                    queue_acquisition()
-                    queue_image_formation()
-                plan.graph, plan.graph_key = rec.graph, gkey
-            except RuntimeError:
-                # (a chain that cannot be recorded -- e.g. a pass whose size follows the free device memory of the moment -- is
-                # queued call by call from now on, not tried again at every call)
-                plan.graph = plan.graph_key = None
-                plan.no_graph_key = gkey
-        plan.warm_key = gkey
-    integ._set_device_channel(rf)
-    d_env, d_img = plan.d_env, plan.d_img
-    t2 = _time.perf_counter()
+    plan = _RenderPlan.of(cx, rq)
+    t0 = time.perf_counter()
+    gkey = rq.graph_key(scene) if graph and not getattr(cx, "profiling", False) else None
+    replayed = plan.replay(rq, gkey)
+    t1 = time.perf_counter() if replayed else plan.queue(scene, rq, gkey)
+    rq.integ._set_device_channel(plan.d_rf if rq.gaussian else plan.d_channel)
+    t2 = time.perf_counter()
     if on_device:
-        if timing is not None:
-            timing.update(acquire=t1 - t0, queue=t2 - t1, wait_copy=0.0, replayed=replayed)
-        return d_img, (d_env if return_bmode else None), (x_scan, z_scan)
-    display = d_img.numpy().T                                                                          # :221  (the one copy)
-    bmode = d_env.numpy() if return_bmode else None
-    t3 = _time.perf_counter()
+        display, bmode = plan.d_img, (plan.d_env if return_bmode else None)
+    else:
+        display = plan.d_img.numpy().T                                                                 # :221  (the one copy)
+        bmode = plan.d_env.numpy() if return_bmode else None
     if timing is not None:
-        timing.update(acquire=t1 - t0, queue=t2 - t1, wait_copy=t3 - t2, replayed=replayed)
-    return display, bmode, (x_scan, z_scan)
+        timing.update(acquire=t1 - t0, queue=t2 - t1, wait_copy=0.0 if on_device else time.perf_counter() - t2, replayed=replayed)
+    return display, bmode, (rq.x_scan, rq.z_scan)

@@ -6,15 +6,17 @@ the shape and dtype of its result and the members of `_keep`.
 Covered: das_beamform / nonlinear_beamform / iq_beamform on axes and scan_beamform on pixel tables (host and DeviceBuffer data,
 elements [E] and [E, 4], with and without a first-arrival table), the two first-arrival functions, DelayAndSum (RF and I/Q),
 PDelayAndSum and FilteredDelayMultiplyAndSum on a GridScan and a PolarScan (the sequence kernel, band-pass), and the seven step
-wrappers.  (DelayAndSum has no `band` setup: its cases have no band-pass.)  Shapes: A = 2, E = 3, T = 16, 5 x 7 pixels."""
-import ctypes as C
+wrappers.  (DelayAndSum has no `band` setup: its cases have no band-pass.)  Shapes: A = 2, E = 3, T = 16, 5 x 7 pixels.
+us_render, which drives these calls from a render plan, is held the same way in test_us_render_dispatch.py; the stand-in itself is
+dispatch_util.py."""
 import importlib
 import itertools
 
 import numpy as np
 import pytest
 
-capi = importlib.import_module("physics-based-ray-tracing_amd._capi")
+from dispatch_util import capi, cx, dev, fields, held  # noqa: F401  (cx is the fixture)
+
 bf = importlib.import_module("physics-based-ray-tracing_amd.beamform")
 
 A, E, T, NX, NZ = 2, 3, 16, 5, 7
@@ -29,66 +31,6 @@ ETAB = np.stack([EX, np.zeros(E), np.zeros(E), np.ones(E)], axis=1).astype(np.fl
 X = np.linspace(-2e-4, 2e-4, NX).astype(np.float32)
 Z = (1e-3 + 1e-4 * np.arange(NZ)).astype(np.float32)
 PX, PZ = np.meshgrid(X, Z, indexing="ij")
-
-
-class RecordingLib:
-    """every pbrt_* attribute is a function that records (name, parameter block, arguments) and returns 0"""
-
-    def __init__(self):
-        self.calls, self.mem, self.peek, self.top = [], {}, {}, 0x10000
-
-    def __getattr__(self, name):
-        if not name.startswith("pbrt_"):
-            raise AttributeError(name)
-
-        def call(*args):
-            if name == "pbrt_dev_alloc":      # (handle, bytes, byref(void *)): a distinct fake address
-                self.top += 0x1000
-                args[2]._obj.value = self.top
-                return 0
-            if name == "pbrt_dev_upload":     # (handle, dst, src, bytes): the bytes that went up
-                self.mem[args[1].value] = C.string_at(args[2], args[3].value)
-                return 0
-            block = next((a._obj for a in args if hasattr(a, "_obj")), None)
-            rest = [a for a in args[1:] if not hasattr(a, "_obj")]
-            # host forms: the bytes behind the pointer arguments the test named (self.peek[name] = {position in rest: bytes})
-            seen = {i: C.string_at(rest[i], n) for i, n in self.peek.get(name, {}).items()}
-            self.calls.append((name, type(block), bytes(block) if block is not None else b"", rest, seen))
-            return 0
-        return call
-
-
-class StandInContext(capi.Context):
-    def __init__(self):
-        self.lib, self.handle, self.device = RecordingLib(), None, 0   # (no handle: nothing is destroyed or freed)
-
-
-@pytest.fixture
-def cx():
-    saved = dict(capi._default_ctx)
-    ctx = StandInContext()
-    capi._default_ctx.clear()
-    capi._default_ctx[0] = ctx
-    try:
-        yield ctx
-    finally:
-        capi._default_ctx.clear()
-        capi._default_ctx.update(saved)
-
-
-def dev(cx, a):
-    return capi.DeviceBuffer.from_host(cx, a)
-
-
-def fields(call):
-    """the parameter block of a recorded call as a flat dict (the embedded das block under its own field names)"""
-    _, typ, raw, _, _ = call
-    blk = typ.from_buffer_copy(raw)
-    out = {}
-    for k, _ in typ._fields_:
-        v = getattr(blk, k)
-        out.update({n: getattr(v, n) for n, _ in v._fields_} if isinstance(v, C.Structure) else {k: v})
-    return out
 
 
 def das_fields(nx=NX, nz=NZ):
