@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/pbrt_hip.h"
 #include "bf_request.h"
+#include "img_request.h"  // the limits of the image steps: FIR_MAX_K, RF2IQ_MAX_D, ENV_MAX_N, ENV_MAX_BLOCKS, PULSE_MAX_K, env_even_len
 #include "device_math.h"
 
 // ---- delay and sum --------------------------------------------------------------------------------------------------------
@@ -490,7 +491,6 @@ DEV void fir_256(uint32_t N, uint32_t K, uint32_t n0, const float *__restrict__ 
 
 // Axial FIR (the band-pass both methods need, D19): out[ix][n] = sum_{k = -K .. K} h[k] in[ix][n - k] along a column.  The taps
 // h [2K + 1] come from the caller (beamform.bandpass_taps designs them).  One workgroup per 256 outputs of one column.
-#define FIR_MAX_K 1024
 __global__ __launch_bounds__(256) void k_axial_fir(uint32_t nz, uint32_t K, uint32_t blocks_per_col, const float *__restrict__ taps,
                                                    const float *__restrict__ in, float *__restrict__ out) {
     const uint32_t col = blockIdx.x / blocks_per_col, n0 = (blockIdx.x - col * blocks_per_col) * 256u;
@@ -505,7 +505,6 @@ __global__ __launch_bounds__(256) void k_axial_fir(uint32_t nz, uint32_t K, uint
 // structure with the mix applied while staging: one workgroup makes 256 outputs of one trace from the 256 D + 2K mixed samples
 // (two planes) and the taps in LDS, (2K + 1) + 2 (256 D + 2K) floats of dynamic LDS -- 40 KB at D = 8, K = 1024.  A sibling of
 // fir_256, not a generalisation: k_axial_fir and k_apply_pulse keep their instructions.
-#define RF2IQ_MAX_D 8
 __global__ __launch_bounds__(256) void k_rf2iq(uint32_t T, uint32_t Td, uint32_t K, uint32_t D, uint32_t blocks_per_trace, float fs,
                                                float t0, float f_d, const float *__restrict__ taps, const float *__restrict__ in,
                                                float2 *__restrict__ out) {
@@ -597,13 +596,11 @@ __global__ __launch_bounds__(256) void k_scan_convert(pbrt_scan_convert_params p
 // neighbouring LDS words (ds_read_b128, conflict-free), the column is a broadcast read, and a thread carries four outputs
 // over four inputs per trip: 16 multiply-adds per three 16-byte LDS reads.  Taps in f64 (sincospi, k_hilbert_taps), sums in f32.
 // One 256-thread workgroup per column, N <= ENV_MAX_N.  LDS: column [Np] + taps [2 Np + 8], Np = N rounded up to 4.
-#define ENV_MAX_N 4096
 // the tap table of a column length N, g[C + k] = h[k] for 0 < k < N, -h[-k] for -N < k < 0, 0 elsewhere (C = Np + 4, 2 Np + 8 entries):
 // computed once per N and kept by the context -- every column of every image of a loop uses the same one, and the f64 sincospi and
 // division per tap were most of the kernel when each workgroup made its own copy (47 -> 2x us at 1040 columns of 638)
 // (even N: followed, at ENV_TAPS_EVEN floats from the start, by the four compact tables of k_hilbert_env_even in the layout of its LDS)
 #define ENV_TAPS_EVEN (2u * ENV_MAX_N + 8u)
-__host__ DEV uint32_t env_even_len(uint32_t Mp) { return 2u * Mp + 16u; }  // entries of one compact table of k_hilbert_env_even
 #define ENV_TAPS_FLOATS (ENV_TAPS_EVEN + 4u * (ENV_MAX_N + 16u))
 // Non-finite input: the analytic signal of a column that holds a NaN or an infinity is NaN at every sample (the FFT of the definition
 // spreads it over the whole column).  Both kernels note, during the copy of the column into LDS, whether a thread copied such a value;
@@ -816,7 +813,6 @@ __global__ __launch_bounds__(256) void k_hilbert_env_even(uint32_t nz, const flo
 // Non-finite input as USMain.py:213-218 has it, where np.max propagates NaN: a value whose log is NaN (NaN itself, or e + 1e-12 < 0)
 // makes the maximum NaN, and with it every pixel of the image.  fmaxf alone would drop the NaN, so each block also ORs a flag and
 // writes NaN as its maximum; the floor at 0 stays for finite input.  (+inf needs nothing: max_db = min_db = inf, inf - inf = NaN.)
-#define ENV_MAX_BLOCKS 256u
 DEV bool log_nan(float e) { return !(e + 1e-12f >= 0.0f); }  // 20 log10f(e + 1e-12f) is NaN
 __global__ __launch_bounds__(256) void k_env_max(uint32_t n, const float *__restrict__ env, float *__restrict__ block_max) {
     __shared__ float part[4];
@@ -881,7 +877,6 @@ __global__ __launch_bounds__(256) void k_log_compress(uint32_t n, const float *_
 // Pulse model (SURVEY f-3; RayTracingV0.py:194-204): every trace convolved with the Gaussian-windowed carrier
 // h[k] = sin(2 pi fc k / fs) * exp(-(k / fs)^2 / sigma^2), |k| <= K (fir_256 above).  One workgroup per 256 output samples of one
 // trace.  HBM-bound (4 B in, 4 B out per sample).
-#define PULSE_MAX_K 1024
 __global__ __launch_bounds__(256) void k_apply_pulse(uint32_t T, uint32_t K, float fs, float fc, float sigma,
                                                      const float *__restrict__ in, float *__restrict__ out) {
     const size_t row = (size_t)blockIdx.y * T;

@@ -11,6 +11,7 @@
 #include <map>
 #include <numeric>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "bvh_build.h"
@@ -24,6 +25,7 @@
 #ifdef PBRT_DIAG
 #include "kernels_diag.h"  // the kernels only the diagnostic build launches
 #endif
+#include "stage_layout.h"
 #include "workspace.h"
 
 static std::string g_ctxless_error;
@@ -665,7 +667,7 @@ int pbrt_scene_destroy(pbrt_scene *s) {
 //   PBRT_US_GENERIC_KERNEL        1: the k_us_bounce instance that reads the quirks at run time              per call (us_impl)
 //   PBRT_US_EMIT_FUSED            0: emitter rays through k_us_emit_init and the later-bounce instance         per call (us_impl)
 //   PBRT_US_EMIT_PERMUTE          0: workgroup b walks region b; k > 1: another stride of the permutation     per call (us_impl)
-//   PBRT_ENV_GENERAL              1: every column length through k_hilbert_env                                per call (env_enqueue)
+//   PBRT_ENV_GENERAL              1: every column length through k_hilbert_env                                per call (pbrt_envelope*)
 //   diagnostic build (-DPBRT_DIAG) only, read in diag_driver.h and not part of Switches:
 //   PBRT_PAIR_MERGE               k: k_chain_pair with merge bounce k instead of the k_bounce chain           per call (diag_selected)
 //   PBRT_US_FUSED_BVH             1: BVH scenes through the fused ultrasound bounce, not the streams          per call (diag_us_fused_bvh)
@@ -1799,13 +1801,14 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
     const uint32_t n_rows = nseg * (streams ? WF_SHADE_THREADS / 64u : rad_rows_per_region(s->accel_kernel));
     const size_t rows_bytes = (size_t)(2 + (streams ? 2 : 1) * MAX_DEPTH_STATS) * n_rows * 8;  // statistics rows (k_shade: and its hit rows)
     unsigned long long *rows = (unsigned long long *)c->buf("segstats", rows_bytes);
-    float *io = (float *)c->buf("leaf_io", (size_t)n * 7 * 4);
+    const auto io_at = stage_layout(stage_in(o, 3 * (size_t)n), stage_in(d, 3 * (size_t)n), stage_in(tmax, n));
+    char *io = (char *)c->buf("leaf_io", io_at.total);
     if (!Lhome || !rows || !io) return PBRT_E_NOMEM;
-    const float *dO = io, *dD = io + 3 * (size_t)n, *dT = io + 6 * (size_t)n;
+    float *dO = (float *)(io + io_at.offset[0]), *dD = (float *)(io + io_at.offset[1]), *dT = (float *)(io + io_at.offset[2]);
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(io, o, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(io + 3 * (size_t)n, d, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(io + 6 * (size_t)n, tmax, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dO, o, (size_t)n * 12, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dD, d, (size_t)n * 12, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dT, tmax, (size_t)n * 4, hipMemcpyHostToDevice, st));
     if (dstats) HIPCHK(c, hipMemsetAsync(dstats, 0, (2 + MAX_DEPTH_STATS) * 8, st));
     HIPCHK(c, hipMemsetAsync(rows, 0, rows_bytes, st));
     HIPCHK(c, hipMemsetAsync(Lhome, 0, (size_t)cap * 16, st));
@@ -2376,37 +2379,36 @@ int pbrt_us_acquire(pbrt_scene *s, const pbrt_us_params *p, uint32_t seed, uint3
 // ------------------------------------------------------------------------------------------------
 }  // extern "C"
 
+// The staging area of one call (stage_layout.h): arrays() takes the call's arrays, each named once, asks the workspace for what their
+// layout needs, uploads the inputs and returns the device pointers; finish() downloads the outputs and waits (both in argument order)
 struct Stage {
     pbrt_ctx *c;
-    char *base = nullptr;
-    size_t off = 0, cap = 0;
-    int rc = PBRT_OK;
-    Stage(pbrt_ctx *ctx, const char *name, size_t bytes) : c(ctx) {
+    int rc = PBRT_OK;  // looked at after arrays(): PBRT_E_NOMEM, or a failed upload
+    struct Back { void *h; const void *d; size_t bytes; } backs[16] = {};  // the outputs, for finish()
+    size_t n_back = 0;
+    template <class... T>
+    std::tuple<T *...> arrays(const StageArray<T> &...a) {
+        static_assert(sizeof...(T) <= sizeof(backs) / sizeof(backs[0]), "more arrays than a staged call can download");
+        const auto L = stage_layout(a...);
         ++c->call_seq;
-        base = (char *)c->buf(name, bytes + 1024);
-        cap = bytes + 1024;
+        char *base = (char *)c->buf("leaf_io", L.total);
         if (!base) rc = PBRT_E_NOMEM;
+        size_t i = 0;
+        return std::tuple<T *...>{place(base, L.offset[i++], a)...};  // (a braced list: evaluated left to right)
     }
-    template <typename T>
-    T *in(const T *h, size_t n) {
+    template <class T>
+    T *place(char *base, size_t off, const StageArray<T> &a) {
+        if (!base || (a.input && !a.src)) return nullptr;
         T *d = reinterpret_cast<T *>(base + off);
-        off += (n * sizeof(T) + 15) & ~size_t(15);
-        if (h && rc == PBRT_OK && hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        if (a.input && rc == PBRT_OK && hipMemcpyAsync(d, a.src, a.bytes(), hipMemcpyHostToDevice, c->stream) != hipSuccess)
             rc = c->fail(PBRT_E_DEVICE, "leaf upload failed");
-        return h ? d : nullptr;
-    }
-    template <typename T>
-    T *out(size_t n) {
-        T *d = reinterpret_cast<T *>(base + off);
-        off += (n * sizeof(T) + 15) & ~size_t(15);
+        if (a.dst) backs[n_back++] = Back{a.dst, d, a.bytes()};
         return d;
     }
-    template <typename T>
-    void back(T *h, const T *d, size_t n) {
-        if (rc == PBRT_OK && hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-            rc = c->fail(PBRT_E_DEVICE, "leaf download failed");
-    }
     int finish() {
+        for (size_t i = 0; i < n_back && rc == PBRT_OK; ++i)
+            if (hipMemcpyAsync(backs[i].h, backs[i].d, backs[i].bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+                rc = c->fail(PBRT_E_DEVICE, "leaf download failed");
         if (rc != PBRT_OK) return rc;
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -2417,43 +2419,39 @@ struct Stage {
 
 extern "C" {
 
-// entering a call that stages host arrays of n items through the workspace: declares c and S
-#define STAGED_BEGIN(ctxp, total_bytes)        \
-    pbrt_ctx *c = (ctxp);                      \
-    if (!c) return PBRT_E_INVALID;             \
-    if (n == 0) return PBRT_OK;                \
-    NOT_RECORDING(c);                          \
-    HIPCHK(c, hipSetDevice(c->device));        \
-    Stage S(c, "leaf_io", (total_bytes));      \
-    if (S.rc) return S.rc;
-// the launch of a leaf operator: one thread per item
-#define LEAF_LAUNCH(kernel, ...) hipLaunchKernelGGL(kernel, dim3(div_up(n, 256)), dim3(256), 0, c->stream, __VA_ARGS__)
+// entering a call that stages host arrays through the workspace (`empty`: it has nothing to do): declares S
+#define STAGED_BEGIN(c, empty)             \
+    if (empty) return PBRT_OK;             \
+    NOT_RECORDING(c);                      \
+    HIPCHK(c, hipSetDevice((c)->device));  \
+    Stage S{c}
+// the rest of a staged call: nothing more if S.arrays() failed, the queueing function (its failure returns before any download or wait), finish()
+#define STAGED_RUN(S, enqueue)               \
+    if ((S).rc) return (S).rc;               \
+    if (int rc_ = (enqueue)) return rc_;     \
+    return (S).finish()
+// the same for a leaf operator on n items: its launch is one thread per item
+#define LEAF_RUN(S, n, kernel, ...)                                                                              \
+    if ((S).rc) return (S).rc;                                                                                   \
+    hipLaunchKernelGGL(kernel, dim3(div_up(n, 256)), dim3(256), 0, (S).c->stream, __VA_ARGS__);                  \
+    return (S).finish()
 
 int pbrt_ray_intersect(pbrt_scene *s, uint32_t n, const float *o, const float *d, const float *tmax, float *t,
                        uint32_t *prim, float *u, float *v) {
     if (!s) return PBRT_E_INVALID;
     NEED(s->ctx, o && d && tmax && t && prim && u && v);
-    STAGED_BEGIN(s->ctx, (size_t)n * 4 * 12);
-    float *dO = S.in(o, 3 * (size_t)n), *dD = S.in(d, 3 * (size_t)n), *dT = S.in(tmax, n);
-    float *rt = S.out<float>(n), *ru = S.out<float>(n), *rv = S.out<float>(n);
-    uint32_t *rp = S.out<uint32_t>(n);
-    LEAF_LAUNCH(ray_intersect_kernel(s), s->ds, n, dO, dD, dT, rt, rp, ru, rv);
-    S.back(t, rt, n);
-    S.back(prim, rp, n);
-    S.back(u, ru, n);
-    S.back(v, rv, n);
-    return S.finish();
+    STAGED_BEGIN(s->ctx, n == 0);
+    auto [dO, dD, dT, rt, rp, ru, rv] = S.arrays(stage_in(o, 3 * (size_t)n), stage_in(d, 3 * (size_t)n), stage_in(tmax, n), stage_out(t, n),
+                                                 stage_out(prim, n), stage_out(u, n), stage_out(v, n));
+    LEAF_RUN(S, n, ray_intersect_kernel(s), s->ds, n, dO, dD, dT, rt, rp, ru, rv);
 }
 
 int pbrt_ray_test(pbrt_scene *s, uint32_t n, const float *o, const float *d, const float *tmax, uint8_t *hit) {
     if (!s) return PBRT_E_INVALID;
     NEED(s->ctx, o && d && tmax && hit);
-    STAGED_BEGIN(s->ctx, (size_t)n * 4 * 9);
-    float *dO = S.in(o, 3 * (size_t)n), *dD = S.in(d, 3 * (size_t)n), *dT = S.in(tmax, n);
-    uint8_t *rh = S.out<uint8_t>(n);
-    LEAF_LAUNCH(ray_test_kernel(s), s->ds, n, dO, dD, dT, rh);
-    S.back(hit, rh, n);
-    return S.finish();
+    STAGED_BEGIN(s->ctx, n == 0);
+    auto [dO, dD, dT, rh] = S.arrays(stage_in(o, 3 * (size_t)n), stage_in(d, 3 * (size_t)n), stage_in(tmax, n), stage_out(hit, n));
+    LEAF_RUN(S, n, ray_test_kernel(s), s->ds, n, dO, dD, dT, rh);
 }
 
 int pbrt_bsdf_sample(pbrt_ctx *ctx, const pbrt_material *m, uint32_t quirks, uint32_t n, const float *wi,
@@ -2462,18 +2460,12 @@ int pbrt_bsdf_sample(pbrt_ctx *ctx, const pbrt_material *m, uint32_t quirks, uin
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && s1 && s2 && wo && pdf && weight && sampled);
     if (int rc = check_material(ctx, *m, 0)) return rc;
-    STAGED_BEGIN(ctx, (size_t)n * 4 * 25);
-    float *dwi = S.in(wi, 3 * (size_t)n), *dng = S.in(n_geo, 3 * (size_t)n), *dns = S.in(n_sh, 3 * (size_t)n);
-    float *dss = S.in(sh_s, 3 * (size_t)n);
-    float *d1 = S.in(s1, n), *d2 = S.in(s2, 2 * (size_t)n);
-    float *rwo = S.out<float>(3 * (size_t)n), *rpdf = S.out<float>(n), *rw = S.out<float>(3 * (size_t)n);
-    uint32_t *rs = S.out<uint32_t>(n);
-    LEAF_LAUNCH(k_bsdf_sample, *m, quirks, n, dwi, dng, dns, dss, d1, d2, rwo, rpdf, rw, rs);
-    S.back(wo, rwo, 3 * (size_t)n);
-    S.back(pdf, rpdf, n);
-    S.back(weight, rw, 3 * (size_t)n);
-    S.back(sampled, rs, n);
-    return S.finish();
+    STAGED_BEGIN(ctx, n == 0);
+    const size_t n3 = 3 * (size_t)n;  // (n_geo, n_sh, sh_s may be null: the slot stays, the kernel gets a null pointer)
+    auto [dwi, dng, dns, dss, d1, d2, rwo, rpdf, rw, rs] =
+        S.arrays(stage_in(wi, n3), stage_in(n_geo, n3), stage_in(n_sh, n3), stage_in(sh_s, n3), stage_in(s1, n), stage_in(s2, 2 * (size_t)n),
+                 stage_out(wo, n3), stage_out(pdf, n), stage_out(weight, n3), stage_out(sampled, n));
+    LEAF_RUN(S, n, k_bsdf_sample, *m, quirks, n, dwi, dng, dns, dss, d1, d2, rwo, rpdf, rw, rs);
 }
 
 int pbrt_bsdf_eval_pdf(pbrt_ctx *ctx, const pbrt_material *m, uint32_t n, const float *wi, const float *wo, float *f,
@@ -2481,46 +2473,30 @@ int pbrt_bsdf_eval_pdf(pbrt_ctx *ctx, const pbrt_material *m, uint32_t n, const 
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && wo && f && pdf);
     if (int rc = check_material(ctx, *m, 0)) return rc;
-    STAGED_BEGIN(ctx, (size_t)n * 4 * 12);
-    float *dwi = S.in(wi, 3 * (size_t)n), *dwo = S.in(wo, 3 * (size_t)n);
-    float *rf = S.out<float>(3 * (size_t)n), *rp = S.out<float>(n);
-    LEAF_LAUNCH(k_bsdf_eval_pdf, *m, n, dwi, dwo, rf, rp);
-    S.back(f, rf, 3 * (size_t)n);
-    S.back(pdf, rp, n);
-    return S.finish();
+    STAGED_BEGIN(ctx, n == 0);
+    const size_t n3 = 3 * (size_t)n;
+    auto [dwi, dwo, rf, rp] = S.arrays(stage_in(wi, n3), stage_in(wo, n3), stage_out(f, n3), stage_out(pdf, n));
+    LEAF_RUN(S, n, k_bsdf_eval_pdf, *m, n, dwi, dwo, rf, rp);
 }
 
 int pbrt_emitter_sample_direction(pbrt_scene *s, uint32_t n, const float *p, const float *u, float *d, float *dist,
                                   float *pdf, float *weight, float *q, uint32_t *emitter) {
     if (!s) return PBRT_E_INVALID;
     NEED(s->ctx, p && u && d && dist && pdf && weight && q && emitter);
-    STAGED_BEGIN(s->ctx, (size_t)n * 4 * 22);
-    float *dp = S.in(p, 3 * (size_t)n), *du = S.in(u, 4 * (size_t)n);
-    float *rd = S.out<float>(3 * (size_t)n), *rdist = S.out<float>(n), *rpdf = S.out<float>(n);
-    float *rw = S.out<float>(3 * (size_t)n), *rq = S.out<float>(3 * (size_t)n);
-    uint32_t *re = S.out<uint32_t>(n);
-    LEAF_LAUNCH(k_emitter_sample, s->ds, n, dp, du, rd, rdist, rpdf, rw, rq, re);
-    S.back(d, rd, 3 * (size_t)n);
-    S.back(dist, rdist, n);
-    S.back(pdf, rpdf, n);
-    S.back(weight, rw, 3 * (size_t)n);
-    S.back(q, rq, 3 * (size_t)n);
-    S.back(emitter, re, n);
-    return S.finish();
+    STAGED_BEGIN(s->ctx, n == 0);
+    const size_t n3 = 3 * (size_t)n;
+    auto [dp, du, rd, rdist, rpdf, rw, rq, re] = S.arrays(stage_in(p, n3), stage_in(u, 4 * (size_t)n), stage_out(d, n3), stage_out(dist, n),
+                                                          stage_out(pdf, n), stage_out(weight, n3), stage_out(q, n3), stage_out(emitter, n));
+    LEAF_RUN(S, n, k_emitter_sample, s->ds, n, dp, du, rd, rdist, rpdf, rw, rq, re);
 }
 
 int pbrt_sensor_sample_ray(pbrt_ctx *ctx, const pbrt_camera *cam, uint32_t n, const float *pos, float *o, float *d,
                            float *tmax) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, cam && pos && o && d && tmax);
-    STAGED_BEGIN(ctx, (size_t)n * 4 * 10);
-    float *dp = S.in(pos, 2 * (size_t)n);
-    float *ro = S.out<float>(3 * (size_t)n), *rd = S.out<float>(3 * (size_t)n), *rt = S.out<float>(n);
-    LEAF_LAUNCH(k_sensor_sample_ray, *cam, n, dp, ro, rd, rt);
-    S.back(o, ro, 3 * (size_t)n);
-    S.back(d, rd, 3 * (size_t)n);
-    S.back(tmax, rt, n);
-    return S.finish();
+    STAGED_BEGIN(ctx, n == 0);
+    auto [dp, ro, rd, rt] = S.arrays(stage_in(pos, 2 * (size_t)n), stage_out(o, 3 * (size_t)n), stage_out(d, 3 * (size_t)n), stage_out(tmax, n));
+    LEAF_RUN(S, n, k_sensor_sample_ray, *cam, n, dp, ro, rd, rt);
 }
 
 int pbrt_us_sensor_sample_ray(pbrt_ctx *ctx, const pbrt_us_sensor *sn, int use_hemisphere_warp, uint32_t n,
@@ -2528,15 +2504,11 @@ int pbrt_us_sensor_sample_ray(pbrt_ctx *ctx, const pbrt_us_sensor *sn, int use_h
                               const float *aperture_sample, float *o, float *d, float *weight) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, sn && time && wavelength_sample && position_sample && aperture_sample && o && d && weight);
-    STAGED_BEGIN(ctx, (size_t)n * 4 * 14);
-    float *dt = S.in(time, n), *dw = S.in(wavelength_sample, n), *dp = S.in(position_sample, 2 * (size_t)n),
-          *da = S.in(aperture_sample, 2 * (size_t)n);
-    float *ro = S.out<float>(3 * (size_t)n), *rd = S.out<float>(3 * (size_t)n), *rw = S.out<float>(n);
-    LEAF_LAUNCH(k_us_sensor_sample_ray, *sn, use_hemisphere_warp, n, dt, dw, dp, da, ro, rd, rw);
-    S.back(o, ro, 3 * (size_t)n);
-    S.back(d, rd, 3 * (size_t)n);
-    S.back(weight, rw, n);
-    return S.finish();
+    STAGED_BEGIN(ctx, n == 0);
+    auto [dt, dw, dp, da, ro, rd, rw] =
+        S.arrays(stage_in(time, n), stage_in(wavelength_sample, n), stage_in(position_sample, 2 * (size_t)n),
+                 stage_in(aperture_sample, 2 * (size_t)n), stage_out(o, 3 * (size_t)n), stage_out(d, 3 * (size_t)n), stage_out(weight, n));
+    LEAF_RUN(S, n, k_us_sensor_sample_ray, *sn, use_hemisphere_warp, n, dt, dw, dp, da, ro, rd, rw);
 }
 
 int pbrt_us_emitter_sample_ray(pbrt_ctx *ctx, const pbrt_us_emitter *e, uint32_t n, const float *time, const float *s1,
@@ -2544,37 +2516,29 @@ int pbrt_us_emitter_sample_ray(pbrt_ctx *ctx, const pbrt_us_emitter *e, uint32_t
                                float *pdf_pos) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, e && time && s1 && s2 && s3 && o && d && ray_time && weight && pdf_pos);
-    STAGED_BEGIN(ctx, (size_t)n * 4 * 16);
-    float *dt = S.in(time, n), *d1 = S.in(s1, n), *d2 = S.in(s2, 2 * (size_t)n), *d3 = S.in(s3, n);
-    float *ro = S.out<float>(3 * (size_t)n), *rd = S.out<float>(3 * (size_t)n), *rt = S.out<float>(n),
-          *rw = S.out<float>(n), *rp = S.out<float>(n);
-    LEAF_LAUNCH(k_us_emitter_sample_ray, *e, n, dt, d1, d2, d3, ro, rd, rt, rw, rp);
-    S.back(o, ro, 3 * (size_t)n);
-    S.back(d, rd, 3 * (size_t)n);
-    S.back(ray_time, rt, n);
-    S.back(weight, rw, n);
-    S.back(pdf_pos, rp, n);
-    return S.finish();
+    STAGED_BEGIN(ctx, n == 0);
+    auto [dt, d1, d2, d3, ro, rd, rt, rw, rp] =
+        S.arrays(stage_in(time, n), stage_in(s1, n), stage_in(s2, 2 * (size_t)n), stage_in(s3, n), stage_out(o, 3 * (size_t)n),
+                 stage_out(d, 3 * (size_t)n), stage_out(ray_time, n), stage_out(weight, n), stage_out(pdf_pos, n));
+    LEAF_RUN(S, n, k_us_emitter_sample_ray, *e, n, dt, d1, d2, d3, ro, rd, rt, rw, rp);
 }
 
 int pbrt_us_put_data(pbrt_ctx *ctx, const pbrt_us_receiver *r, uint32_t n, const float *ox, const float *time,
                      const float *d, const float *amplitude, float *channel_buffer) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, r && ox && time && d && amplitude && channel_buffer);
-    const size_t nb = (size_t)r->number_of_elements * r->time_samples;
-    STAGED_BEGIN(ctx, (size_t)n * 4 * 7 + nb * 4);
-    float *dx = S.in(ox, n), *dt = S.in(time, n), *dd = S.in(d, 3 * (size_t)n), *da = S.in(amplitude, n);
-    float *db = S.in(channel_buffer, nb);
-    LEAF_LAUNCH(k_us_put_data, *r, n, dx, dt, dd, da, db);
-    S.back(channel_buffer, db, nb);
-    return S.finish();
+    STAGED_BEGIN(ctx, n == 0);
+    auto [dx, dt, dd, da, db] = S.arrays(stage_in(ox, n), stage_in(time, n), stage_in(d, 3 * (size_t)n), stage_in(amplitude, n),
+                                         stage_inout(channel_buffer, (size_t)r->number_of_elements * r->time_samples));
+    LEAF_RUN(S, n, k_us_put_data, *r, n, dx, dt, dd, da, db);
 }
 
 // ------------------------------------------------------------------------------------------------
 // image formation behind the hot path: (pulse ->) beamform -> envelope -> log compression.
 // The *_dev entry points queue their kernels on the context's stream and return (ABI 5): the reference's us_render loop
 // (USMain.py:92-252, 51 x per run) stays in HBM from the acquisition to the display image.  The host-pointer forms stage
-// their arguments and call the same queueing functions.
+// their arguments and call the same queueing functions.  The rules of the seven steps around the beamformer, what makes a call of theirs
+// empty and the shape of every launch are in img_request.h (host only): an entry point makes its request, *_enqueue adds what needs the device.
 // ------------------------------------------------------------------------------------------------
 }  // extern "C"
 
@@ -2594,6 +2558,10 @@ struct ImgTimer {
     }
 };
 
+static int launched(pbrt_ctx *c) {  // the end of every function that queues kernels
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
 // ---- one beamform request (bf_request.h: the request, and the rules of the four parameter blocks) from the entry points to the launch ----
 // de: element positions [n_elements], or (rq.probe) the element table [n_elements][4]; dx, dz: the axes, or (rq.tab) the pixel tables;
 // dt, ttx: the transmit delays, and the first-arrival table of this scan or null
@@ -2638,67 +2606,61 @@ static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const 
         hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
     }
     c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * (rq.method == PBRT_SCAN_IQ ? 8 : 4);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
+    return launched(c);
 }
-static int env_enqueue(pbrt_ctx *c, uint32_t nx, uint32_t nz, const float *din, float *dout) {
-    const uint32_t np = (nz + 3u) & ~3u, G = 2u * np + 8u;
+// the launch of an image step as its request shapes it (img_request.h ImgLaunch: grid, block, dynamic LDS bytes)
+#define IMG_LAUNCH(c, L, kernel, ...) hipLaunchKernelGGL(kernel, dim3((L).gx, (L).gy), dim3((L).block), (L).lds, (c)->stream, __VA_ARGS__)
+
+static int env_enqueue(pbrt_ctx *c, const EnvRequest &rq, const float *din, float *dout) {
     // the tap table of this column length: made once, kept while the workspace buffer lives (pbrt_ctx_trim may take it)
     float *taps = (float *)c->buf("env_taps", (size_t)ENV_TAPS_FLOATS * 4);
     if (!taps) return PBRT_E_NOMEM;
     const uint64_t gen = c->work.generation("env_taps");
-    const Switches sw = read_switches();
     ImgTimer tm(c, IMG_ENV);
-    if (gen != c->env_taps_gen || c->env_taps_n != nz) {
+    if (gen != c->env_taps_gen || c->env_taps_n != rq.nz) {
         c->work.invalidate_recordings();  // (a finished recording holds no launch of this kernel: its taps are replaced now)
-        hipLaunchKernelGGL(k_hilbert_taps, dim3(div_up(G + 4u * env_even_len(((nz >> 1) + 3u) & ~3u), 256)), dim3(256), 0, c->stream, nz, taps);
-        c->env_taps_n = nz;
+        IMG_LAUNCH(c, rq.taps_launch, k_hilbert_taps, rq.nz, taps);
+        c->env_taps_n = rq.nz;
         c->env_taps_gen = gen;
     }
-    // even column lengths: half of the taps are zero, k_hilbert_env_even leaves their multiply-adds out (kernels_beamform.h)
-    const uint32_t mp = ((nz >> 1) + 3u) & ~3u;
-    const size_t lds_even = (size_t)(2u * mp + 4u * env_even_len(mp)) * 4;  // (its four tap tables: 3.3 x the column; 80 KB at 4096 samples)
-    // (PBRT_ENV_GENERAL=1, A/B and test: every column length through k_hilbert_env)
-    const bool even = (nz & 1u) == 0u && nz >= 8u && lds_even <= (c->lds_limit ? c->lds_limit : 65536u) && !sw.env_general;
-    const size_t lds = even ? lds_even : (size_t)(3u * np + 8u) * 4;
-    if (lds > c->env_lds_attr) {
+    if (const size_t lds = rq.launch.lds; lds > c->env_lds_attr) {
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hilbert_env), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hilbert_env_even), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         c->env_lds_attr = lds;
     }
-    // a thread carries four outputs: whole waves for the quads of a column (638 samples: 160 quads, three waves)
-    const uint32_t threads = std::min(256u, div_up(div_up(nz, 4u), 64u) * 64u);
-    if (even)
-        hipLaunchKernelGGL(k_hilbert_env_even, dim3(nx), dim3(threads), lds, c->stream, nz, din, taps, dout);
-    else
-        hipLaunchKernelGGL(k_hilbert_env, dim3(nx), dim3(threads), lds, c->stream, nz, din, taps, dout);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
+    IMG_LAUNCH(c, rq.launch, rq.even ? k_hilbert_env_even : k_hilbert_env, rq.nz, din, taps, dout);
+    return launched(c);
 }
-static int log_enqueue(pbrt_ctx *c, uint32_t n, const float *din, float dr, float *dout) {
+static int log_enqueue(pbrt_ctx *c, const LogRequest &rq, const float *din, float *dout) {
     float *mx = (float *)c->buf("img_max", ENV_MAX_BLOCKS * 4);
     if (!mx) return PBRT_E_NOMEM;
     ImgTimer tm(c, IMG_LOG);
-    const uint32_t nb = std::max(1u, std::min<uint32_t>(div_up(n, 1024), ENV_MAX_BLOCKS));
-    hipLaunchKernelGGL(k_env_max, dim3(nb), dim3(256), 0, c->stream, n, din, mx);
-    hipLaunchKernelGGL(k_log_compress, dim3(div_up(n, 256)), dim3(256), 0, c->stream, n, din, mx, nb, dr, dout);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
+    IMG_LAUNCH(c, rq.max_launch, k_env_max, rq.n, din, mx);
+    IMG_LAUNCH(c, rq.launch, k_log_compress, rq.n, din, mx, rq.nb, rq.dynamic_range_db, dout);
+    return launched(c);
 }
-static int pulse_check(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma, uint32_t *K) {
-    NEED(ctx, fs > 0.0f && frequency > 0.0f && sigma > 0.0f);
-    NEED(ctx, (uint64_t)n_traces * time_samples < 0xffffffffull && n_traces <= 65535u);
-    *K = (uint32_t)std::ceil(2.5 * (double)sigma * (double)fs);
-    NEED(ctx, *K <= PULSE_MAX_K);
-    return PBRT_OK;
-}
-static int pulse_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, uint32_t K, float fs, float fc, float sigma, const float *din,
-                         float *dout) {
+static int pulse_enqueue(pbrt_ctx *c, const PulseRequest &rq, const float *din, float *dout) {
     ImgTimer tm(c, IMG_PULSE);
-    const size_t lds = (size_t)(2 * K + 1 + 256 + 2 * K) * 4;
-    hipLaunchKernelGGL(k_apply_pulse, dim3(div_up(T, 256), n_traces), dim3(256), lds, c->stream, T, K, fs, fc, sigma, din, dout);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
+    IMG_LAUNCH(c, rq.launch, k_apply_pulse, rq.T, rq.K, rq.fs, rq.frequency, rq.sigma, din, dout);
+    return launched(c);
+}
+static int fir_enqueue(pbrt_ctx *c, const FirRequest &rq, const float *dtaps, const float *din, float *dout) {
+    IMG_LAUNCH(c, rq.launch, k_axial_fir, rq.nz, rq.K, rq.per_col, dtaps, din, dout);
+    return launched(c);
+}
+static int scan_convert_enqueue(pbrt_ctx *c, const ScanConvertRequest &rq, const float *dsrc, const float *dx, const float *dz, float *ddst) {
+    IMG_LAUNCH(c, rq.launch, k_scan_convert, *rq.p, dsrc, dx, dz, ddst);
+    return launched(c);
+}
+static int rf2iq_enqueue(pbrt_ctx *c, const Rf2iqRequest &rq, const float *dtaps, const float *din, float *dout) {
+    IMG_LAUNCH(c, rq.launch, k_rf2iq, rq.T, rq.Td, rq.K, rq.D, rq.per_trace, rq.fs, rq.t0, rq.demod_freq, dtaps, din,
+               reinterpret_cast<float2 *>(dout));
+    return launched(c);
+}
+static int iq_env_enqueue(pbrt_ctx *c, const IqEnvRequest &rq, const float *din, float *dout) {
+    ImgTimer tm(c, IMG_ENV);
+    IMG_LAUNCH(c, rq.launch, k_iq_modulus, rq.n, reinterpret_cast<const float2 *>(din), dout);
+    return launched(c);
 }
 
 // The three bodies behind the 20 beamform and first-arrival entry points.  Each entry point makes its request first (BF_REQUEST below):
@@ -2720,8 +2682,7 @@ static int first_arrival_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_t
     hipLaunchKernelGGL(rq.probe ? k_das_first_arrival<true> : k_das_first_arrival<false>, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256),
                        0, ctx->stream, *p, rq.tab ? 1u : 0u, (const float *)d_tx_delays, (const float *)d_elem, (const float *)d_x,
                        (const float *)d_z, (double *)d_table);
-    HIPCHK(ctx, hipGetLastError());
-    return PBRT_OK;
+    return launched(ctx);
 }
 
 static int beamform_host(pbrt_ctx *ctx, const BfRequest &rq, const float *data, const float *tx_delays, const float *elem, const float *x,
@@ -2733,90 +2694,27 @@ static int beamform_host(pbrt_ctx *ctx, const BfRequest &rq, const float *data, 
     const uint32_t n = p->nx * p->nz;
     const size_t nel = (size_t)p->n_elements * (rq.probe ? 4u : 1u);
     const size_t ngx = rq.tab ? (size_t)n : p->nx, ngz = rq.tab ? (size_t)n : p->nz;  // axes, or the two pixel tables
-    STAGED_BEGIN(ctx, (nd + ne + nel + ngx + ngz + (size_t)n * width) * 4 + 256);
-    float *dd = S.in(data, nd), *dt = S.in(tx_delays, ne), *de = S.in(elem, nel);
-    float *dx = S.in(x, ngx), *dz = S.in(z, ngz);
-    float *dout = S.out<float>(n * width);
-    if (int rc = das_enqueue(c, rq, dd, dt, de, dx, dz, dout, nullptr)) return rc;
-    S.back(out, dout, n * width);
-    return S.finish();
+    STAGED_BEGIN(ctx, n == 0);
+    auto [dd, dt, de, dx, dz, dout] =
+        S.arrays(stage_in(data, nd), stage_in(tx_delays, ne), stage_in(elem, nel), stage_in(x, ngx), stage_in(z, ngz), stage_out(out, n * width));
+    STAGED_RUN(S, das_enqueue(ctx, rq, dd, dt, de, dx, dz, dout, nullptr));
 }
-// entering a beamform entry point: declares rq, the request of its parameter block (bf_request.h)
-#define BF_REQUEST(...)                      \
-    BfRequest rq;                            \
-    if (!ctx) return PBRT_E_INVALID;         \
-    if (const char *why = bf_request(&rq, __VA_ARGS__)) return ctx->fail(PBRT_E_INVALID, "invalid argument: %s", why)
-
-// ---- the argument rules of the steps around the beamformer: one *_check each, called by the host form and by the _dev form ----
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-// (no overlap rule here: pbrt_envelope stages rf and env separately and so takes rf == env; pbrt_envelope_dev refuses overlap itself)
-static int env_check(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *rf, const void *env) {
-    NEED(ctx, rf && env && nz <= ENV_MAX_N && (uint64_t)nx * nz < 0xffffffffull);
-    return PBRT_OK;
-}
-static int log_check(pbrt_ctx *ctx, const void *env, float dynamic_range_db, const void *out) {
-    NEED(ctx, env && out && dynamic_range_db > 0.0f);
-    return PBRT_OK;
-}
-static int iq_env_check(pbrt_ctx *ctx, uint32_t n, const void *iq, const void *env) {
-    NEED(ctx, iq && env && !ranges_overlap(iq, (size_t)n * 8, env, (size_t)n * 4));
-    return PBRT_OK;
-}
-static int fir_check(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *taps, const void *in, const void *out) {
-    NEED(ctx, taps && in && out && !ranges_overlap(in, (size_t)nx * nz * 4, out, (size_t)nx * nz * 4));
-    NEED(ctx, K <= FIR_MAX_K && nz > 0);
-    NEED(ctx, (uint64_t)nx * nz < 0xffffffffull && (uint64_t)nx * div_up(nz, 256) < 0x7fffffffull);
-    return PBRT_OK;
-}
-static int fir_enqueue(pbrt_ctx *c, uint32_t nx, uint32_t nz, uint32_t K, const float *dtaps, const float *din, float *dout) {
-    const size_t lds = (size_t)(2 * K + 1 + 256 + 2 * K) * 4;
-    const uint32_t per_col = div_up(nz, 256);
-    hipLaunchKernelGGL(k_axial_fir, dim3(nx * per_col), dim3(256), lds, c->stream, nz, K, per_col, dtaps, din, dout);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-static int scan_convert_check(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *src, const void *dst) {
-    NEED(ctx, p->n_theta >= 2u && p->n_rho >= 2u && p->nx > 0 && p->nz > 0);
-    NEED(ctx, (uint64_t)p->n_theta * p->n_rho < 0xffffffffull && (uint64_t)p->nx * p->nz < 0xffffffffull);
-    NEED(ctx, std::isfinite(p->theta0) && std::isfinite(p->dtheta) && std::isfinite(p->rho0) && std::isfinite(p->drho));
-    NEED(ctx, std::isfinite(p->ox) && std::isfinite(p->oz) && p->dtheta != 0.0 && p->drho != 0.0);
-    NEED(ctx, !ranges_overlap(src, (size_t)p->n_theta * p->n_rho * 4, dst, (size_t)p->nx * p->nz * 4));
-    return PBRT_OK;
-}
-static int scan_convert_enqueue(pbrt_ctx *c, const pbrt_scan_convert_params *p, const float *dsrc, const float *dx, const float *dz,
-                                float *ddst) {
-    hipLaunchKernelGGL(k_scan_convert, dim3(div_up((uint64_t)p->nx * p->nz, 256)), dim3(256), 0, c->stream, *p, dsrc, dx, dz, ddst);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-static int rf2iq_check(pbrt_ctx *ctx, uint32_t n_traces, uint32_t T, float fs, float t0, float f_d, uint32_t D, uint32_t K, const void *in,
-                       const void *out) {
-    NEED(ctx, T > 0 && D >= 1u && D <= RF2IQ_MAX_D && K <= FIR_MAX_K);
-    NEED(ctx, std::isfinite(fs) && fs > 0.0f && std::isfinite(t0));
-    NEED(ctx, std::isfinite(f_d) && f_d >= 0.0f);
-    NEED(ctx, (uint64_t)n_traces * T < 0xffffffffull && (uint64_t)n_traces * div_up(div_up(T, D), 256) < 0x7fffffffull);
-    NEED(ctx, !ranges_overlap(in, (size_t)n_traces * T * 4, out, (size_t)n_traces * div_up(T, D) * 8));
-    return PBRT_OK;
-}
-static int rf2iq_enqueue(pbrt_ctx *c, uint32_t n_traces, uint32_t T, float fs, float t0, float f_d, uint32_t D, uint32_t K,
-                         const float *dtaps, const float *din, float *dout) {
-    const uint32_t Td = div_up(T, D), per_trace = div_up(Td, 256);
-    const size_t lds = (size_t)(2 * K + 1 + 2 * (256 * D + 2 * K)) * 4;  // <= 40 KB
-    hipLaunchKernelGGL(k_rf2iq, dim3(n_traces * per_trace), dim3(256), lds, c->stream, T, Td, K, D, per_trace, fs, t0, f_d, dtaps, din,
-                       reinterpret_cast<float2 *>(dout));
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-static int iq_env_enqueue(pbrt_ctx *c, uint32_t n, const float *din, float *dout) {
-    ImgTimer tm(c, IMG_ENV);
-    hipLaunchKernelGGL(k_iq_modulus, dim3(div_up(n, 256)), dim3(256), 0, c->stream, n, reinterpret_cast<const float2 *>(din), dout);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
+// entering an entry point of the image chain: declares rq, the request its maker fills (bf_request.h, img_request.h)
+#define MAKE_REQUEST(ctx, Request, maker, ...) \
+    Request rq;                                \
+    if (!(ctx)) return PBRT_E_INVALID;         \
+    if (const char *why = maker(&rq, __VA_ARGS__)) return (ctx)->fail(PBRT_E_INVALID, "invalid argument: %s", why)
+#define BF_REQUEST(...) MAKE_REQUEST(ctx, BfRequest, bf_request, __VA_ARGS__)
+// The two sequences of the fourteen image-step entry points, each stated once.  A _dev form: null context -> request -> refused ->
+// empty -> hipSetDevice, then it queues.  A host form: ... -> empty -> not while recording -> hipSetDevice (STAGED_BEGIN, which
+// declares S), then it stages, queues, downloads and waits (STAGED_RUN).
+#define IMG_QUEUED(ctx, Request, maker, ...)        \
+    MAKE_REQUEST(ctx, Request, maker, __VA_ARGS__); \
+    if (rq.empty) return PBRT_OK;                   \
+    HIPCHK(ctx, hipSetDevice((ctx)->device))
+#define IMG_STAGED(ctx, Request, maker, ...)        \
+    MAKE_REQUEST(ctx, Request, maker, __VA_ARGS__); \
+    STAGED_BEGIN(ctx, rq.empty)
 
 extern "C" {
 
@@ -2857,25 +2755,13 @@ int pbrt_scan_first_arrival_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const 
 }
 int pbrt_scan_convert_dev(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const void *d_src, const void *d_x, const void *d_z,
                           void *d_dst) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && d_src && d_x && d_z && d_dst);
-    int rc = scan_convert_check(ctx, p, d_src, d_dst);
-    if (rc) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return scan_convert_enqueue(ctx, p, (const float *)d_src, (const float *)d_x, (const float *)d_z, (float *)d_dst);
+    IMG_QUEUED(ctx, ScanConvertRequest, scan_convert_request, p, d_src, d_x, d_z, d_dst);
+    return scan_convert_enqueue(ctx, rq, (const float *)d_src, (const float *)d_x, (const float *)d_z, (float *)d_dst);
 }
 int pbrt_scan_convert(pbrt_ctx *ctx, const pbrt_scan_convert_params *p, const float *src, const float *x, const float *z, float *dst) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, p && src && x && z && dst);
-    int rc = scan_convert_check(ctx, p, src, dst);
-    if (rc) return rc;
-    const size_t ns = (size_t)p->n_theta * p->n_rho, nd = (size_t)p->nx * p->nz;
-    const uint32_t n = p->nx * p->nz;
-    STAGED_BEGIN(ctx, (ns + nd + p->nx + p->nz) * 4 + 256);
-    float *dsrc = S.in(src, ns), *dx = S.in(x, p->nx), *dz = S.in(z, p->nz), *ddst = S.out<float>(nd);
-    if ((rc = scan_convert_enqueue(c, p, dsrc, dx, dz, ddst)) != 0) return rc;
-    S.back(dst, ddst, nd);
-    return S.finish();
+    IMG_STAGED(ctx, ScanConvertRequest, scan_convert_request, p, src, x, z, dst);
+    auto [dsrc, dx, dz, ddst] = S.arrays(stage_in(src, rq.n_src), stage_in(x, p->nx), stage_in(z, p->nz), stage_out(dst, rq.n_dst));
+    STAGED_RUN(S, scan_convert_enqueue(ctx, rq, dsrc, dx, dz, ddst));
 }
 
 int pbrt_iq_beamform_dev(pbrt_ctx *ctx, const pbrt_iq_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem,
@@ -2895,44 +2781,24 @@ int pbrt_iq_beamform(pbrt_ctx *ctx, const pbrt_iq_params *p, const float *iq, co
 }
 int pbrt_rf2iq_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float t0, float demod_freq,
                    uint32_t decimation, uint32_t K, const void *d_taps, const void *d_in, void *d_out) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_taps && d_in && d_out);
-    int rc = rf2iq_check(ctx, n_traces, time_samples, fs, t0, demod_freq, decimation, K, d_in, d_out);
-    if (rc) return rc;
-    if (n_traces == 0) return PBRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return rf2iq_enqueue(ctx, n_traces, time_samples, fs, t0, demod_freq, decimation, K, (const float *)d_taps, (const float *)d_in,
-                         (float *)d_out);
+    IMG_QUEUED(ctx, Rf2iqRequest, rf2iq_request, n_traces, time_samples, fs, t0, demod_freq, decimation, K, d_taps, d_in, d_out);
+    return rf2iq_enqueue(ctx, rq, (const float *)d_taps, (const float *)d_in, (float *)d_out);
 }
 int pbrt_rf2iq(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float t0, float demod_freq, uint32_t decimation,
                uint32_t K, const float *taps, const float *in, float *out) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, taps && in && out);
-    int rc = rf2iq_check(ctx, n_traces, time_samples, fs, t0, demod_freq, decimation, K, in, out);
-    if (rc) return rc;
-    const uint32_t n = n_traces * time_samples;
-    const size_t n_out = (size_t)n_traces * div_up(time_samples, decimation) * 2;
-    STAGED_BEGIN(ctx, ((size_t)n + n_out + 2 * (size_t)K + 1) * 4 + 128);
-    float *dh = S.in(taps, 2 * (size_t)K + 1), *din = S.in(in, n), *dout = S.out<float>(n_out);
-    if ((rc = rf2iq_enqueue(c, n_traces, time_samples, fs, t0, demod_freq, decimation, K, dh, din, dout)) != 0) return rc;
-    S.back(out, dout, n_out);
-    return S.finish();
+    IMG_STAGED(ctx, Rf2iqRequest, rf2iq_request, n_traces, time_samples, fs, t0, demod_freq, decimation, K, taps, in, out);
+    auto [dh, din, dout] = S.arrays(stage_in(taps, 2 * (size_t)K + 1), stage_in(in, (size_t)n_traces * time_samples),
+                                    stage_out(out, (size_t)n_traces * rq.Td * 2));
+    STAGED_RUN(S, rf2iq_enqueue(ctx, rq, dh, din, dout));
 }
 int pbrt_iq_envelope_dev(pbrt_ctx *ctx, uint32_t n, const void *d_iq, void *d_env) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = iq_env_check(ctx, n, d_iq, d_env)) return rc;
-    if (n == 0) return PBRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return iq_env_enqueue(ctx, n, (const float *)d_iq, (float *)d_env);
+    IMG_QUEUED(ctx, IqEnvRequest, iq_env_request, n, d_iq, d_env);
+    return iq_env_enqueue(ctx, rq, (const float *)d_iq, (float *)d_env);
 }
 int pbrt_iq_envelope(pbrt_ctx *ctx, uint32_t n, const float *iq, float *env) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = iq_env_check(ctx, n, iq, env)) return rc;
-    STAGED_BEGIN(ctx, (size_t)n * 12 + 64);
-    float *din = S.in(iq, 2 * (size_t)n), *dout = S.out<float>(n);
-    if (int rc = iq_env_enqueue(c, n, din, dout)) return rc;
-    S.back(env, dout, n);
-    return S.finish();
+    IMG_STAGED(ctx, IqEnvRequest, iq_env_request, n, iq, env);
+    auto [din, dout] = S.arrays(stage_in(iq, 2 * (size_t)n), stage_out(env, n));
+    STAGED_RUN(S, iq_env_enqueue(ctx, rq, din, dout));
 }
 
 int pbrt_bf_beamform_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
@@ -2951,21 +2817,13 @@ int pbrt_bf_beamform(pbrt_ctx *ctx, const pbrt_bf_params *p, const float *data, 
     return beamform_host(ctx, rq, data, tx_delays, elem, x, z, out);
 }
 int pbrt_axial_fir_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const void *d_taps, const void *d_in, void *d_out) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = fir_check(ctx, nx, nz, K, d_taps, d_in, d_out)) return rc;
-    if (nx == 0) return PBRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return fir_enqueue(ctx, nx, nz, K, (const float *)d_taps, (const float *)d_in, (float *)d_out);
+    IMG_QUEUED(ctx, FirRequest, fir_request, nx, nz, K, d_taps, d_in, d_out);
+    return fir_enqueue(ctx, rq, (const float *)d_taps, (const float *)d_in, (float *)d_out);
 }
 int pbrt_axial_fir(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, uint32_t K, const float *taps, const float *in, float *out) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = fir_check(ctx, nx, nz, K, taps, in, out)) return rc;
-    const uint32_t n = nx * nz;
-    STAGED_BEGIN(ctx, (size_t)n * 8 + (size_t)(2 * K + 1) * 4 + 128);
-    float *dh = S.in(taps, 2 * (size_t)K + 1), *din = S.in(in, n), *dout = S.out<float>(n);
-    if (int rc = fir_enqueue(c, nx, nz, K, dh, din, dout)) return rc;
-    S.back(out, dout, n);
-    return S.finish();
+    IMG_STAGED(ctx, FirRequest, fir_request, nx, nz, K, taps, in, out);
+    auto [dh, din, dout] = S.arrays(stage_in(taps, 2 * (size_t)K + 1), stage_in(in, (size_t)nx * nz), stage_out(out, (size_t)nx * nz));
+    STAGED_RUN(S, fir_enqueue(ctx, rq, dh, din, dout));
 }
 
 int pbrt_das_beamform_dev(pbrt_ctx *ctx, const pbrt_das_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem_x,
@@ -3010,68 +2868,33 @@ int pbrt_das_beamform_probe(pbrt_ctx *ctx, const pbrt_das_params *p, const float
 }
 
 int pbrt_envelope_dev(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const void *d_rf, void *d_env) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = env_check(ctx, nx, nz, d_rf, d_env)) return rc;
-    NEED(ctx, !ranges_overlap(d_rf, (size_t)nx * nz * 4, d_env, (size_t)nx * nz * 4));
-    if (nx == 0 || nz == 0) return PBRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return env_enqueue(ctx, nx, nz, (const float *)d_rf, (float *)d_env);
+    IMG_QUEUED(ctx, EnvRequest, env_request, IMG_FORM_DEV, nx, nz, d_rf, d_env, ctx->lds_limit, read_switches().env_general);
+    return env_enqueue(ctx, rq, (const float *)d_rf, (float *)d_env);
 }
-
 int pbrt_envelope(pbrt_ctx *ctx, uint32_t nx, uint32_t nz, const float *rf, float *env) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = env_check(ctx, nx, nz, rf, env)) return rc;
-    const uint32_t n = nx * nz;
-    STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
-    float *din = S.in(rf, n), *dout = S.out<float>(n);
-    if (int rc = env_enqueue(c, nx, nz, din, dout)) return rc;
-    S.back(env, dout, n);
-    return S.finish();
+    IMG_STAGED(ctx, EnvRequest, env_request, IMG_FORM_HOST, nx, nz, rf, env, ctx->lds_limit, read_switches().env_general);
+    auto [din, dout] = S.arrays(stage_in(rf, (size_t)nx * nz), stage_out(env, (size_t)nx * nz));
+    STAGED_RUN(S, env_enqueue(ctx, rq, din, dout));
 }
-
 int pbrt_log_compress_dev(pbrt_ctx *ctx, uint32_t n, const void *d_env, float dynamic_range_db, void *d_out) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = log_check(ctx, d_env, dynamic_range_db, d_out)) return rc;
-    if (n == 0) return PBRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return log_enqueue(ctx, n, (const float *)d_env, dynamic_range_db, (float *)d_out);
+    IMG_QUEUED(ctx, LogRequest, log_request, n, d_env, dynamic_range_db, d_out);
+    return log_enqueue(ctx, rq, (const float *)d_env, (float *)d_out);
 }
-
 int pbrt_log_compress(pbrt_ctx *ctx, uint32_t n, const float *env, float dynamic_range_db, float *out) {
-    if (!ctx) return PBRT_E_INVALID;
-    if (int rc = log_check(ctx, env, dynamic_range_db, out)) return rc;
-    STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
-    float *din = S.in(env, n), *dout = S.out<float>(n);
-    if (int rc = log_enqueue(c, n, din, dynamic_range_db, dout)) return rc;
-    S.back(out, dout, n);
-    return S.finish();
+    IMG_STAGED(ctx, LogRequest, log_request, n, env, dynamic_range_db, out);
+    auto [din, dout] = S.arrays(stage_in(env, n), stage_out(out, n));
+    STAGED_RUN(S, log_enqueue(ctx, rq, din, dout));
 }
-
 int pbrt_us_apply_pulse_dev(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,
                             const void *d_in, void *d_out) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, d_in && d_out && !ranges_overlap(d_in, (size_t)n_traces * time_samples * 4, d_out, (size_t)n_traces * time_samples * 4));
-    uint32_t K = 0;
-    int rc = pulse_check(ctx, n_traces, time_samples, fs, frequency, sigma, &K);
-    if (rc) return rc;
-    if (n_traces == 0 || time_samples == 0) return PBRT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return pulse_enqueue(ctx, n_traces, time_samples, K, fs, frequency, sigma, (const float *)d_in, (float *)d_out);
+    IMG_QUEUED(ctx, PulseRequest, pulse_request, n_traces, time_samples, fs, frequency, sigma, d_in, d_out);
+    return pulse_enqueue(ctx, rq, (const float *)d_in, (float *)d_out);
 }
-
 int pbrt_us_apply_pulse(pbrt_ctx *ctx, uint32_t n_traces, uint32_t time_samples, float fs, float frequency, float sigma,
                         const float *in, float *out) {
-    if (!ctx) return PBRT_E_INVALID;
-    NEED(ctx, in && out && !ranges_overlap(in, (size_t)n_traces * time_samples * 4, out, (size_t)n_traces * time_samples * 4));
-    uint32_t K = 0;
-    int rc = pulse_check(ctx, n_traces, time_samples, fs, frequency, sigma, &K);
-    if (rc) return rc;
-    const uint32_t n = n_traces * time_samples;
-    STAGED_BEGIN(ctx, (size_t)n * 8 + 64);
-    float *din = S.in(in, n), *dout = S.out<float>(n);
-    if ((rc = pulse_enqueue(c, n_traces, time_samples, K, fs, frequency, sigma, din, dout)) != 0) return rc;
-    S.back(out, dout, n);
-    return S.finish();
+    IMG_STAGED(ctx, PulseRequest, pulse_request, n_traces, time_samples, fs, frequency, sigma, in, out);
+    auto [din, dout] = S.arrays(stage_in(in, (size_t)n_traces * time_samples), stage_out(out, (size_t)n_traces * time_samples));
+    STAGED_RUN(S, pulse_enqueue(ctx, rq, din, dout));
 }
 
 // ---- device buffers and the stream (ABI 5): what a caller needs to keep the us_render loop in HBM without another GPU library ----

@@ -1,5 +1,7 @@
 """GPU parity of the batched leaf operators of include/pbrt_hip.h against the oracle: bit-exact for
 indices / lobes and for arithmetic inside the numeric contract; a few ulp where ocml meets libm."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -228,3 +230,38 @@ def test_put_data_k6_on_device(mi, known):
     assert s.channel_data()[0, 10] == pytest.approx(1.5)
     s.clear()
     assert not s.channel_data().any()
+
+
+@pytest.mark.parametrize("n", [1, 3, 5, 67])
+def test_small_batches_equal_the_head_of_a_larger_one(mi, capi, n):
+    """batch sizes at which no staged array is a multiple of 16 bytes long (the staging area rounds every array up to 16): one-byte
+    outputs (pbrt_ray_test), seven arrays (pbrt_ray_intersect), null optional inputs between staged ones (pbrt_bsdf_sample without
+    n_geo, n_sh, sh_s) -- every output is, bit for bit, the first n entries of the same call on 128 items"""
+    N = 128
+    sc = mi.load_file(scene_path("cbox.xml"), res=8)
+    dev = sc.device()
+    lib, A = dev.ctx.lib, capi.addr
+    o, d = _rays(N, 11, -0.95, 0.95)
+    tmax = np.where(np.arange(N) % 3 == 0, 0.9, np.inf).astype(np.float32)
+    rng = np.random.default_rng(12)
+    wi = rng.normal(size=(N, 3))
+    wi = (wi / np.linalg.norm(wi, axis=1, keepdims=True)).astype(np.float32)
+    s1, s2 = rng.random(N, dtype=np.float32), rng.random((N, 2), dtype=np.float32)
+    mat = mi.DiffuseBSDF(mi.Properties("diffuse", dict(reflectance=[0.2, 0.5, 0.8])))._material()
+
+    def run(k):
+        os_, ds_, tm = capi.f32(o[:k].T), capi.f32(d[:k].T), capi.f32(tmax[:k])
+        t, prim, u, v = np.empty(k, np.float32), np.empty(k, np.uint32), np.empty(k, np.float32), np.empty(k, np.float32)
+        assert lib.pbrt_ray_intersect(dev.handle, k, A(os_), A(ds_), A(tm), A(t), A(prim), A(u), A(v)) == 0
+        hit = np.full(k, 0xAA, np.uint8)
+        assert lib.pbrt_ray_test(dev.handle, k, A(os_), A(ds_), A(tm), A(hit)) == 0
+        wis, a1, a2 = capi.f32(wi[:k].T), capi.f32(s1[:k]), capi.f32(s2[:k].T)
+        wo, w, pdf, lobe = np.empty((3, k), np.float32), np.empty((3, k), np.float32), np.empty(k, np.float32), np.empty(k, np.uint32)
+        assert lib.pbrt_bsdf_sample(dev.ctx.handle, C.byref(mat), 0, k, A(wis), None, None, None, A(a1), A(a2), A(wo), A(pdf), A(w),
+                                    A(lobe)) == 0
+        return dict(t=t, prim=prim, u=u, v=v, hit=hit, wo=wo, w=w, pdf=pdf, lobe=lobe)
+
+    full, got = run(N), run(n)
+    assert 0 < full["hit"].sum() and set(np.unique(full["hit"])) <= {0, 1} and (full["lobe"] != 0xFFFFFFFF).any()
+    for k, a in got.items():
+        assert a.tobytes() == np.ascontiguousarray(full[k][..., :n]).tobytes(), k
