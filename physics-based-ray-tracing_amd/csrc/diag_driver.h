@@ -76,8 +76,8 @@ static uint32_t diag_pair_merge() {
 }
 // Does this call select a diagnostic launch structure?  (BVH scenes without PBRT_FILM_NO_HIT_POOL run as streams whatever else is set.)
 static bool diag_selected(const Render &r) {
-    if (r.wavefront) return false;
-    return !r.brute || (r.f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || diag_pair_merge() != 0 || PBRT_DEFAULT_WALK_FROM != 0xffu;
+    if (r.rq.wavefront) return false;
+    return !r.rq.brute || (r.f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || diag_pair_merge() != 0 || PBRT_DEFAULT_WALK_FROM != 0xffu;
 }
 
 // The bounces of one pass through a diagnostic launch structure: k_regen, or the chain of the plan with k_walk from walk_from on,
@@ -86,12 +86,13 @@ static int diag_pass(Render &r, const DiagRender &dg, RadArgs a, uint32_t nseg_p
     pbrt_scene *s = r.s;
     pbrt_ctx *c = r.c;
     const pbrt_film_desc *f = r.f;
-    const bool brute = r.brute;
+    const bool brute = r.rq.brute;
+    const uint32_t region = r.rq.launch.region;
     hipStream_t st = c->stream;
     int rc;
     // state for this pass: none if one launch walks all its bounces
-    const bool one_launch = brute && !(f->flags & (PBRT_FILM_WALK_SET | PBRT_FILM_REGEN)) && chain_len(r.plan, 0, f->max_depth) >= f->max_depth;
-    const size_t need = one_launch ? (size_t)r.region : (size_t)nseg_pass * r.region;
+    const bool one_launch = brute && !(f->flags & (PBRT_FILM_WALK_SET | PBRT_FILM_REGEN)) && chain_len(r.fp.plan, 0, f->max_depth) >= f->max_depth;
+    const size_t need = one_launch ? (size_t)region : (size_t)nseg_pass * region;
     float *in = (float *)c->buf("stateA", need * N_STATE * 4), *out = (float *)c->buf("stateB", need * N_STATE * 4);
     if (!in || !out) return PBRT_E_NOMEM;
     a.state_cap = (uint32_t)need;
@@ -117,7 +118,7 @@ static int diag_pass(Render &r, const DiagRender &dg, RadArgs a, uint32_t nseg_p
         return PBRT_OK;
     }
     for (uint32_t depth = 0; depth < f->max_depth;) {
-        const uint32_t nb = brute ? chain_len(r.plan, depth, f->max_depth) : 1u;
+        const uint32_t nb = brute ? chain_len(r.fp.plan, depth, f->max_depth) : 1u;
         a.depth = depth;
         a.nb = nb;
         a.in = in;
@@ -128,7 +129,7 @@ static int diag_pass(Render &r, const DiagRender &dg, RadArgs a, uint32_t nseg_p
             // Only the regions THIS pass launched take part: a short last pass (spp not a multiple of the pass size)
             // launches nseg_pass < nseg workgroups, so paths dealt to regions >= nseg_pass would never be traced, and
             // the counters of those regions are left over from the previous pass.
-            const uint32_t owners = rad_owners_per_region(s->accel_kernel), wreg = r.region / owners;
+            const uint32_t owners = rad_owners_per_region(s->accel_kernel), wreg = region / owners;
             const uint32_t n_own_pass = nseg_pass * owners;
             hipLaunchKernelGGL(k_scan_owners, dim3(1), dim3(1024), 0, st, sin, n_own_pass, wreg, owners, (uint32_t)c->n_cu, dg.offs,
                                dg.segC, dg.quota);
@@ -138,7 +139,7 @@ static int diag_pass(Render &r, const DiagRender &dg, RadArgs a, uint32_t nseg_p
         }
         if (depth == 0 && (rc = r.timer.begin()) != 0) return rc;
         const bool walk = brute && depth >= dg.walk_from;  // this launch walks every remaining bounce of the pass
-        const uint32_t pair_m = (brute && depth == 0 && !walk) ? pair_merge_bounce(dg.pair_merge, r.plan, f->max_depth) : 0u;
+        const uint32_t pair_m = (brute && depth == 0 && !walk) ? pair_merge_bounce(dg.pair_merge, r.fp.plan, f->max_depth) : 0u;
         if (pair_m) {  // the whole path in one launch, two tiles per wave
             a.merge_at = pair_m;
             const uint32_t g2 = div_up(a.n_paths, 2u * SEG_BRUTE);
@@ -172,44 +173,42 @@ static int diag_pass(Render &r, const DiagRender &dg, RadArgs a, uint32_t nseg_p
 static int diag_render(Render &r) {
     pbrt_ctx *c = r.c;
     const pbrt_film_desc *f = r.f;
+    const bool brute = r.rq.brute;
     int rc;
-    if (!r.brute && (rc = diag_lds_attr(r.s, false)) != 0) return rc;
+    if (!brute && (rc = diag_lds_attr(r.s, false)) != 0) return rc;
     if ((rc = render_buffers(r)) != 0) return rc;
-    if (f->flags & (PBRT_FILM_WALK_SET | PBRT_FILM_REGEN)) r.probe = false;
+    if ((rc = render_clear(r)) != 0) return rc;
+    render_plan(r, !(f->flags & (PBRT_FILM_WALK_SET | PBRT_FILM_REGEN)));
     DiagRender dg;
     dg.pair_merge = diag_pair_merge();
     if (f->flags & PBRT_FILM_WALK_SET) dg.walk_from = (f->flags >> 17) & 0xffu;
-    dg.repack = !r.brute && rad_wave_private(r.s->accel_kernel) && !(f->flags & PBRT_FILM_NO_REPACK);
+    dg.repack = !brute && rad_wave_private(r.s->accel_kernel) && !(f->flags & PBRT_FILM_NO_REPACK);
     if (dg.repack) {
-        dg.stC = (float *)c->buf("stateC", (size_t)r.cap * N_STATE * 4);
+        dg.stC = (float *)c->buf("stateC", (size_t)r.ps.cap * N_STATE * 4);
         dg.segC = (uint32_t *)c->buf("segC", (size_t)r.n_own * 4);
         dg.offs = (uint32_t *)c->buf("seg_offs", (size_t)r.n_own * 4);
         dg.quota = (uint32_t *)c->buf("seg_quota", 64);
         if (!dg.stC || !dg.segC || !dg.offs || !dg.quota) return PBRT_E_NOMEM;
     }
     if ((rc = render_args(r)) != 0) return rc;
-    uint32_t s_step = r.s_pass;  // samples of a regular pass
-    for (uint32_t s0 = 0; s0 < f->spp; ++r.passes) {
-        const bool probing = r.probe && r.passes == 0;
-        const uint32_t sc = probing ? PROBE_SPP : std::min(s_step, f->spp - s0);
+    if ((rc = render_tile_keep(r)) != 0) return rc;
+    render_film(r);
+    for (PassSchedule p{f->spp, r.ps.per_pass, r.fp.probe}; p.next(); ++r.passes) {
         RadArgs a = r.base;
-        a.n_paths = (uint32_t)(r.npix_r * sc);
-        a.s_first = f->sample_offset + s0;
-        if ((rc = diag_pass(r, dg, a, div_up(a.n_paths, r.region))) != 0) return rc;
+        a.n_paths = (uint32_t)(r.rq.npix_r * p.sc);
+        a.s_first = f->sample_offset + p.s0;
+        if ((rc = diag_pass(r, dg, a, div_up(a.n_paths, r.rq.launch.region))) != 0) return rc;
         if ((rc = r.timer.end()) != 0) return rc;
         r.fa.s_first = a.s_first;
-        r.fa.s_count = sc;
+        r.fa.s_count = p.sc;
         film_accum(c, r.fa);
         HIPCHK(c, hipGetLastError());
-        s0 += sc;
-        if (probing) {  // learn the plan from the probe pass
-            if ((rc = probe_plan(c, r.segstats, r.n_rows, r.stat_rows, r.dstats, f->max_depth, &r.plan)) != 0) return rc;
-            const uint32_t rem = f->spp - s0;
-            s_step = div_up(rem, div_up(rem, r.s_pass));  // equal passes for what is left
-        }
+        // learn the plan from the probe pass
+        if (p.probing() && (rc = probe_plan(c, r.segstats, r.n_rows, r.rq.stat_rows, r.dstats, f->max_depth, &r.fp.plan)) != 0) return rc;
     }
     if ((rc = render_finish(r)) != 0) return rc;
-    if (r.brute && (f->flags & PBRT_FILM_REGEN)) {  // k_regen keeps the paths in registers: only the radiance records are written
+    if ((rc = render_stats(r)) != 0) return rc;
+    if (brute && (f->flags & PBRT_FILM_REGEN)) {  // k_regen keeps the paths in registers: only the radiance records are written
         pbrt_stats &S = c->stats;
         S.model_bytes = S.model_bytes - S.bounce_model_bytes + S.samples * 12;
         S.bounce_model_bytes = S.samples * 12;

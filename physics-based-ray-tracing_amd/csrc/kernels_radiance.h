@@ -14,6 +14,7 @@
 // the path-state data path; paths that end write their radiance once to Lhome[home].
 #pragma once
 #include "device_scene.h"
+#include "render_request.h"  // N_STATE, MAX_DEPTH_STATS, MAX_CHAIN, HIT_ROW0: the constants the host arithmetic shares with the kernels
 #include "tile_cull.h"
 
 // slots per compaction segment == threads per workgroup (seg_threads(ACCEL) below).  Measured on MI355X, cbox
@@ -50,10 +51,6 @@ __host__ __device__ constexpr uint32_t rad_region_segs(int accel);
 #define REGION_SEGS_US_EMIT 16
 #endif
 __host__ __device__ constexpr uint32_t us_region_segs(int, bool emit = false) { return emit ? REGION_SEGS_US_EMIT : REGION_SEGS_US; }
-#define N_STATE 15
-#define MAX_DEPTH_STATS 62
-#define MAX_CHAIN 6  // bounces one launch of the multi-bounce kernels walks at most (the per-bounce counts are packed 10 bits each)
-#define HIT_ROW0 (2 + MAX_DEPTH_STATS)  // k_bounce_pool: statistics rows HIT_ROW0 + d = rays of depth d that hit something
 
 // ACCEL_K_BRUTE      uniform primitive loop (scalar loads) + shading tables staged in LDS; every table <= 32 entries,
 //                    no analytic cones (device_scene.h brute_intersect CONES)

@@ -103,6 +103,9 @@ struct pbrt_ctx {
         uint64_t gen = 0, scene = 0;
         pbrt_camera cam{};
         uint32_t rx0 = 0, ry0 = 0, rw = 0, rh = 0;
+        bool operator==(const TileKeepKey &o) const {
+            return gen == o.gen && scene == o.scene && memcmp(&cam, &o.cam, sizeof cam) == 0 && rx0 == o.rx0 && ry0 == o.ry0 && rw == o.rw && rh == o.rh;
+        }
     } tile_keep_key;
     // what pbrt_ctx_tile_keep reports: whether the LAST radiance render carried a table (the key outlives a later render without
     // one), and how often k_tile_keep has been launched
@@ -212,7 +215,6 @@ static int upload(pbrt_scene *s, const T *src, size_t n, const T **dst) {
     return PBRT_OK;
 }
 
-static inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // Runtime flags as template arguments: with_flags(f, a, b, ...) calls the generic lambda f with one std::true_type / std::false_type
 // per flag and returns what f returns.  Every kernel family has ONE selector built on it (bounce_kernel, trace_kernel, ...), which
@@ -431,7 +433,7 @@ int pbrt_get_stats(pbrt_ctx *c, pbrt_stats *out) {
     return PBRT_OK;
 }
 
-// the keep table of the last radiance render (render_args): read back for tests and diagnosis, launches nothing
+// the keep table of the last radiance render (render_tile_keep): read back for tests and diagnosis, launches nothing
 int pbrt_ctx_tile_keep(pbrt_ctx *c, pbrt_tile_keep_info *info, uint32_t *words, uint32_t capacity) {
     if (!c) return PBRT_E_INVALID;
     NEED(c, info && (words || capacity == 0));
@@ -708,13 +710,8 @@ static Switches read_switches() {
 // ------------------------------------------------------------------------------------------------
 // radiance mode driver
 // ------------------------------------------------------------------------------------------------
-// Depths at which a launch of the brute-force kernels walks two bounces (bit d: bounces d and d + 1).  Measured on the
-// Cornell box (0x1 while the two-bounce kernels ran at 6 - 7 waves per SIMD, every pair since they run
-// at 8); pbrt_film_desc.flags can override it per call (PBRT_FILM_FUSE_PLAN).
-#ifndef PBRT_DEFAULT_FUSE_PLAN
-#define PBRT_DEFAULT_FUSE_PLAN 0x15u
-#endif
-
+// What the driver decides on the host -- the argument rules, the rendered region, the shape of a pass, the fuse plan, the pass
+// schedule, the stream grids, the byte models -- is render_request.h; the stages below talk to the device.
 // The fused bounce kernel of a launch that walks nb bounces (>= 2: the multi-bounce variants of the brute-force kernels,
 // kernels_radiance.h; a.nb = nb).  Glossy brute-force scenes have instances of their own.  nullptr: BVH scenes run k_trace /
 // k_shade (wf_bounces); their fused bounce (PBRT_FILM_NO_HIT_POOL) and k_walk exist in the diagnostic build only (diag_driver.h).
@@ -768,53 +765,6 @@ static UsKern us_bounce_kernel(const pbrt_scene *s, bool first, bool emit, uint3
     }
 }
 
-// Fuse plan: bit d set = the launch that walks bounce d goes on with bounce d + 1 in registers (at most MAX_CHAIN bounces per
-// launch).  0 = one launch per bounce, 0x15 = pairs, all ones = as many bounces per launch as MAX_CHAIN allows.
-static uint32_t chain_len(uint32_t plan, uint32_t depth, uint32_t max_depth) {
-    uint32_t nb = 1;
-    while (nb < MAX_CHAIN && depth + nb < max_depth && depth + nb - 1 < 32 && ((plan >> (depth + nb - 1)) & 1u)) ++nb;
-    return nb;
-}
-// The plan that pays for a scene follows from how many paths survive each bounce: walking bounce d + 1 in the same launch saves
-// the state round trip of the survivors and costs the idle lanes of the others.  Measured (cbox, survival 0.87 / 0.77 / 0.83 /
-// 0.85 / 0.20: ONE launch for all six bounces 6.23 ms, triples 6.30, pairs 6.58; open scenes with survival 0.37 - 0.49 / 0.29 /
-// 0.33: pairs 2.11 / 4.52 ms, triples 2.11 / 4.84, one launch 2.47 / 5.70): go on while at least 45 % of the paths do; the last
-// bounce of a path only looks for emitters and is always taken along.  Any plan renders the same film.
-static uint32_t plan_from_survival(const unsigned long long *live, uint32_t max_depth) {
-    uint32_t plan = 0;
-    for (uint32_t d = 0; d + 1 < max_depth && d < 31; ++d) {
-        const bool last = d + 2 == max_depth;
-        if (live[d] == 0) break;
-        if (last || (double)live[d + 1] >= 0.45 * (double)live[d]) plan |= 1u << d;
-    }
-    return plan;
-}
-
-// Byte model of the radiance path (DESIGN.md "Algorithmic bytes").  live[d] = paths entering depth d.
-// A launch that walks two bounces (fuse plan bit d) keeps its paths in registers between them: the survivors of bounce d
-// are neither written nor read back, only the survivors of bounce d + 1 are.
-// hits (k_bounce_pool launches, BVH scenes, bounces >= 1; else nullptr): hits[d] = rays of depth d that hit something.  Every ray
-// reads its origin and direction (24 B), a path that hit something reads its full state.
-static void radiance_model_bytes(const unsigned long long *live, uint32_t nd, uint64_t samples, uint64_t film_px,
-                                 uint32_t passes, uint32_t fuse_plan, uint32_t max_depth, const unsigned long long *hits,
-                                 uint64_t *total, uint64_t *bounce) {
-    uint64_t b = 0;
-    for (uint32_t d = 0; d < nd;) {
-        const uint32_t nb = std::min(chain_len(fuse_plan, d, max_depth), nd - d);
-        uint64_t in = live[d], next = (d + nb < nd) ? live[d + nb] : 0;
-        if (d > 0 && hits)
-            b += in * 24 + hits[d] * (N_STATE * 4);
-        else if (d > 0)
-            b += in * (N_STATE * 4);  // state read
-        b += next * (N_STATE * 4);            // compacted survivors written
-        b += (in - next) * 12;                // radiance of the paths that ended (at either bounce of the launch)
-        d += nb;
-    }
-    *bounce = b;
-    *total = b + samples * 12 /* film gather reads Lhome once */ + film_px * 32ull * passes /* accumulator RMW */ +
-             film_px * 28 /* resolve */;
-}
-
 
 // ---- BVH scenes: intersection and shading as separate streams (kernels_wavefront.h) -------------------------------------------
 struct WfPlan {
@@ -824,26 +774,16 @@ struct WfPlan {
     size_t lds = 0;
     uint32_t split_s = 0, split_parts = 1;  // PBRT_WF_SPLIT (wf_bounces); s = 0: off
 };
-// Workgroup shape of k_trace: the image plus (rows + 1) stack rows per workgroup; two 1024-thread workgroups per CU when both fit
-// (8 waves per SIMD at <= 64 VGPRs), else one.
+// Workgroup shape of k_trace (render_request.h wf_shape) and the switches of the call
 static WfPlan wf_plan(const pbrt_scene *s, const Switches &sw) {
     WfPlan p;
-    const uint32_t limit = s->ctx->lds_limit ? s->ctx->lds_limit : 65536u;
-    const uint32_t image = s->accel_kernel == ACCEL_K_BVH_LDS ? s->lds_bytes : 0u;
-    // 1024-thread workgroups for trees in global memory as well: what counts is the size of the queue a workgroup's waves share
-    // (bunny.ply 1024^2 x 64: 256 / 512 / 1024 threads 38.5 / 31.6 / 30.2 ms), not the LDS -- a copy of the top of the tree (the
-    // first 16 .. 1008 nodes in breadth-first order) in LDS on top of that was worth 1 - 2 %: the vector caches hold those nodes anyway
-    p.threads = 1024u;
-    const uint32_t statics = 1024;  // queue words and the segment table, with slack
-    uint32_t budget = limit / 2;     // two workgroups per CU
-    if (image + statics + 3u * p.threads * 4u > budget) budget = limit;
-    const uint32_t rows_fit = (budget - image - statics) / (p.threads * 4u);
-    p.rows = std::max(2u, std::min(rows_fit, 8u));
-    p.packet = sw.wf_packet;
+    const WfShape w = wf_shape(s->ctx->lds_limit, s->accel_kernel == ACCEL_K_BVH_LDS ? s->lds_bytes : 0u, s->bvh_depth, sw.wf_packet);
+    p.threads = w.threads;
+    p.rows = w.rows;
+    p.lds = w.lds;
+    p.packet = w.packet;
     p.split_s = sw.wf_split_s;
     p.split_parts = sw.wf_split_parts;
-    if (3u * s->bvh_depth > 64u) p.packet = false;  // the wave's stack is the 64 lanes of one register (bvh_packet_closest)
-    p.lds = (size_t)image + (size_t)p.rows * p.threads * 4u;
     return p;
 }
 // The intersection kernel of a bounce with its workgroup size and dynamic LDS: camera rays as packets (k_trace_primary), else
@@ -965,10 +905,6 @@ static void wf_launch_trace(pbrt_scene *s, const WfArgs &a, const WfPlan &p, uin
     const TraceLaunch t = trace_kernel(s, p, first);
     hipLaunchKernelGGL(t.kernel, dim3(G), dim3(t.threads), t.lds, st, a);
 }
-// workgroups of a k_trace launch over nr regions: at least nr / WF_KMAX (a workgroup walks at most WF_KMAX regions), else `mult` per CU
-static uint32_t wf_trace_grid(uint32_t nr, uint32_t mult, uint32_t cus) {
-    return std::min(nr, std::max(div_up(nr, WF_KMAX), std::max(1u, mult * cus)));
-}
 
 // k_shade with or without the cylinder code (the instance without it is the one every other scene runs), or with the rough /
 // Fresnel conductor code on top of it (GLOSSY, always with CYL); the small shading tables in LDS when they fit (wf_tables_lds)
@@ -1014,10 +950,7 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
     const uint32_t cu_trace = split ? 256u - 32u * p.split_s : (uint32_t)c->n_cu;
     hipStream_t st_t = split ? c->st_trace : c->stream, st_s = split ? c->st_shade : c->stream;
     uint32_t reg0[8], regn[8];
-    for (uint32_t h = 0; h < parts; ++h) {
-        reg0[h] = (uint32_t)((uint64_t)nreg * h / parts);
-        regn[h] = (uint32_t)((uint64_t)nreg * (h + 1) / parts) - reg0[h];
-    }
+    for (uint32_t h = 0; h < parts; ++h) wf_part(nreg, parts, h, &reg0[h], &regn[h]);
     // events of the split pipeline: [part][0] = its last k_trace, [part][1] = its last k_shade (a wait captures the record that
     // precedes it, so one event per part and kind serves every depth)
     if (split)
@@ -1035,7 +968,7 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
         fill(depth, have_shadows, h);
         const uint32_t nr = regn[h];
         const uint32_t mult = depth >= 2 ? p.grid_deep : p.grid_mult;
-        wf_launch_trace(s, a, p, wf_trace_grid(nr, mult, cu_trace), first, st_t);
+        wf_launch_trace(s, a, p, wf_trace_grid(nr, mult, cu_trace, WF_KMAX), first, st_t);
         ++*launches;
     };
     auto shade = [&](uint32_t depth, bool first, bool have_shadows, uint32_t h) {
@@ -1083,22 +1016,14 @@ static int wf_bounces(pbrt_scene *s, WfArgs a, const WfBufs &b, const WfPlan &p,
         for (uint32_t h = 0; h < parts; ++h) HIPCHK(c, hipStreamWaitEvent(c->stream, c->sync_ev[2u * h + 1u], 0));
     return PBRT_OK;
 }
-// Default paths in flight per pass of the trace / shade streams: the largest power of two (min_pass .. 512 Mi) whose workspace
-// (WF_BYTES_PER_PATH each) fits two thirds of the free device memory -- what this context already holds for these buffers is
-// re-used, not allocated on top --, one half of the device's total memory, and the context's workspace limit.
-static uint64_t wf_default_pass_paths(pbrt_ctx *c, uint64_t min_pass) {
+// Default paths in flight per pass of the trace / shade streams (render_request.h stream_default_pass_paths) from what the device
+// has free now and what this context already holds for the buffers of a pass
+static uint64_t wf_default_pass_paths(pbrt_ctx *c) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
     size_t held = 0;
     for (const char *nm : {"wf_stateA", "wf_stateB", "wf_shadowA", "wf_shadowB", "wf_hit_id", "Lhome"}) held += c->work.bytes(nm);
-    // two thirds of what is free, and never more than half of the device: a tenant that arrives second (torch beside the renderer,
-    // USMain.py:5) still finds room, and the pass size depends less on who allocated first.  A caller that owns the device asks
-    // for more per call (pbrt_film_desc.pass_paths) -- bench.py does for BASELINE config 4.
-    double budget = std::min((2.0 / 3.0) * (double)(free_b + held), 0.5 * (double)total_b);
-    if (c->work.limit) budget = std::min(budget, (double)c->work.limit - (double)(c->work.total() - held) - 64e6 /* the small buffers */);
-    uint64_t pass_paths = min_pass;
-    while (pass_paths < (512u << 20) && 2.0 * (double)pass_paths * WF_BYTES_PER_PATH <= budget) pass_paths *= 2;
-    return pass_paths;
+    return stream_default_pass_paths(free_b, total_b, held, c->work.limit, c->work.total(), WF_BYTES_PER_PATH);
 }
 
 // The guard words of the context come back with the statistics of a call (wf_guard_fetch queues the copy on the call's stream,
@@ -1135,34 +1060,6 @@ static int wf_check_guard(pbrt_ctx *c, const uint32_t *g) {
                    "shift %u nodes %u)",
                    g[0], g[1], g[2], g[3], g[4], g[6], g[7], g[8], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17],
                    g[19], g[20], f[0], f[1], f[2], f[3], f[4], f[5], f[6], g[28], g[29], g[30]);
-}
-
-// Byte model of the two-launch bounce, the bytes the algorithm NEEDS, per depth d with live[d] rays of which
-// hits[d] hit something (both counted on the device), S = shadow rays of the render:
-//   k_trace (k_trace_primary at depth 0: the camera rays are generated in registers)
-//       32 B per continuation ray (origin, direction planes; depth >= 1), 4 B hit index written (the primitive, or none)
-//       per shadow ray: 32 B read + 4 B visibility written
-//   k_shade
-//       4 B hit index per ray ((t, u, v) are recomputed from the primitive's record, not read)
-//       depth >= 1: the state of a path once -- 48 B (L / A / B planes) if its ray left the scene, all six planes (96 B) if it hit
-//       16 B radiance record per path that ends, 96 B per survivor, 32 B per shadow ray it emits
-// (the 64-byte primitive record and the vertex normals of a hit come from tables that stay in L2: 0 B.)  What the kernels move on
-// top of that -- the 48 bytes k_shade reads twice for a path that hit, whole 128-byte lines for sparse gathers -- is traffic, not
-// model: profiles/pmc_traffic.json has the ratio.  *trace = the part of the total that is k_trace's.
-static uint64_t wavefront_model_bytes(const unsigned long long *live, const unsigned long long *hits, uint32_t nd, uint64_t shadows,
-                                      uint64_t *trace) {
-    uint64_t tr = 0, sh = 0;
-    for (uint32_t d = 0; d < nd; ++d) {
-        const uint64_t in = live[d], next = d + 1 < nd ? live[d + 1] : 0, h = std::min<uint64_t>(hits[d], in);
-        if (!in) break;
-        tr += (d > 0 ? in * 32 : 0) + in * 4;
-        sh += in * 4 + (d > 0 ? (in - h) * 48 + h * 96 : 0);
-        sh += (in - next) * 16 + next * 96;
-    }
-    tr += shadows * 36;
-    sh += shadows * 32;
-    if (trace) *trace = tr;
-    return tr + sh;
 }
 
 // ---- pass handling of the radiance and ultrasound drivers ---------------------------------------------------------------------
@@ -1218,14 +1115,6 @@ static int call_stats(pbrt_ctx *c, const unsigned long long *hstats, uint64_t sa
     return PBRT_OK;
 }
 
-// Sizing a pass: `per_call` units (samples of a film region of `unit` pixels, paths per ray of `unit` rays) in passes of at most
-// pass_paths paths, rounded up to whole regions.  The free-memory figure behind a default pass_paths is a snapshot (torch or another
-// process may allocate between the query and the hipMalloc): alloc(cap, nseg) returns PBRT_E_NOMEM when the pass buffers do not fit,
-// and then they go back, the pass is halved and tried again -- the result does not depend on the pass size (global path keys).  A
-// caller-fixed pass size (fixed) gives up at once.  What did fit goes back too when even the smallest pass does not (the caller may be
-// about to give the memory to someone else); the message of the failed request stands.  Any other code from alloc is returned as is.
-// equal: passes of equal size instead of full ones plus a small remainder.
-static const uint64_t PASS_MIN_PATHS = 1u << 20;
 #ifndef US_PASS_PATHS
 // an acquisition's paths in flight per pass.  Config 3 (268 M paths), one launch per bounce: 8 / 16 / 32 / 64 Mi -> 13.1 / 12.7 / 13.0 /
 // 13.2 ms; with all bounces of a pass in one launch the survivors are re-read while still cached and smaller passes
@@ -1233,33 +1122,36 @@ static const uint64_t PASS_MIN_PATHS = 1u << 20;
 // shading frame: 1.96 segments per path; three workgroups per CU): 4 / 8 / 16 / 32 Mi -> 13.26 / 11.89 / 11.61 / 12.20 ms
 #define US_PASS_PATHS (16u << 20)
 #endif
-struct PassShape {
-    uint32_t per_pass = 1, cap = 0, nseg = 0;
-};
+// Sizing a pass (render_request.h pass_shape: the shape, pass_addressing: what the kernels can address, pass_halve: the next size).
+// The free-memory figure behind a default pass_paths is a snapshot (torch or another process may allocate between the query and the
+// hipMalloc): alloc(ps) returns PBRT_E_NOMEM when the pass buffers do not fit, and then they go back, the pass is halved and tried
+// again -- the result does not depend on the pass size (global path keys).  A caller-fixed pass size (fixed) gives up at once.  What
+// did fit goes back too when even the smallest pass does not (the caller may be about to give the memory to someone else); the
+// message of the failed request stands.  Any other code from alloc is returned as is.  rows: dwords per slot of the fused kernels'
+// state.
+#define RULE_TEXT(c, why) (c)->fail(PBRT_E_INVALID, "invalid argument: %s", why)
+// one pass of a fixed size: its shape, held to what the kernels can address
+static int one_pass(pbrt_ctx *c, uint64_t pass_paths, uint32_t per_call, uint64_t unit, uint32_t region, bool equal, bool streams,
+                    uint32_t rows, PassShape *ps) {
+    if (const char *why = pass_shape(ps, pass_paths, per_call, unit, region, equal)) return RULE_TEXT(c, why);
+    if (const char *why = pass_addressing(ps->cap, streams, rows, WF_DEAD)) return RULE_TEXT(c, why);
+    return PBRT_OK;
+}
 template <typename Alloc>
 static int size_pass(pbrt_ctx *c, uint64_t pass_paths, bool fixed, uint32_t per_call, uint64_t unit, uint32_t region, bool equal,
-                     Alloc alloc, PassShape *ps) {
+                     bool streams, uint32_t rows, Alloc alloc, PassShape *ps) {
     for (;;) {
-        uint32_t k = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(per_call, pass_paths / std::max<uint64_t>(unit, 1)));
-        if (equal) k = div_up(per_call, div_up(per_call, k));
-        NEED(c, unit * k < 0xfffffc00ull);
-        ps->per_pass = k;
-        ps->cap = div_up(unit * k, region) * region;
-        ps->nseg = ps->cap / region;  // regions (one workgroup each)
-        const int rc = alloc(ps->cap, ps->nseg);
+        if (int rc = one_pass(c, pass_paths, per_call, unit, region, equal, streams, rows, ps)) return rc;
+        const int rc = alloc(*ps);
         if (rc != PBRT_E_NOMEM) return rc;
         release_pass_buffers(c);
-        if (fixed || k <= 1 || pass_paths <= PASS_MIN_PATHS) return PBRT_E_NOMEM;
-        pass_paths = std::max<uint64_t>(PASS_MIN_PATHS, std::min<uint64_t>(pass_paths, unit * k) / 2);
+        if (!pass_halve(&pass_paths, fixed, *ps, unit)) return PBRT_E_NOMEM;
     }
 }
 // Default paths in flight per pass: the trace / shade streams size it from the free device memory (wf_default_pass_paths); the fused
-// kernels take `paths`, halved under a workspace limit until bytes_per_path of each fit it (the small buffers: 64 MB)
+// kernels take `paths`, halved under a workspace limit until bytes_per_path of each fit it
 static uint64_t default_pass_paths(pbrt_ctx *c, bool streams, uint64_t paths, uint32_t bytes_per_path) {
-    if (streams) return wf_default_pass_paths(c, PASS_MIN_PATHS);
-    if (c->work.limit)
-        while (paths > PASS_MIN_PATHS && (double)paths * (double)bytes_per_path > (double)c->work.limit - 64e6) paths /= 2;
-    return paths;
+    return streams ? wf_default_pass_paths(c) : fused_default_pass_paths(paths, bytes_per_path, c->work.limit);
 }
 
 // self-check of a fast divisor (device_math.h make_fastdiv) against `/` at the probe values of its caller
@@ -1344,71 +1236,64 @@ struct Render {
     const pbrt_camera *cam;
     const pbrt_film_desc *f;
     void *d_out;
-    // render_check: the launch structure and the rendered region (the crop and the margin its filter reads)
-    bool brute = false, wavefront = false;
+    // render_check: the request (render_request.h: the rules, the launch structure, the rendered region, the row counts), the switches
+    RenderRequest rq;
     Switches sw;
-    uint32_t rx0 = 0, ry0 = 0, rw = 0, rh = 0;
-    uint64_t npix_r = 0, film_px = 0;
-    // render_buffers: the shape of a full pass and the buffers of the call
-    uint32_t region = 0, s_pass = 0, cap = 0, nseg = 0;
-    uint32_t n_own = 0, n_rows = 0, stat_rows = 0, hit_rows = 0;  // live counters; statistics rows per counter, counters in use, k_shade's hit rows
+    // render_buffers: the shape of a full pass (n_own: its live counters, n_rows: its statistics rows) and the buffers of the call
+    PassShape ps;
+    uint32_t n_own = 0, n_rows = 0;
     WfBufs wfb{};
     WfPlan wfp;
     float *Lhome = nullptr, *acc = nullptr;
     uint32_t *segA = nullptr, *segB = nullptr;
     unsigned long long *dstats = nullptr, *segstats = nullptr;
+    // render_plan: the fuse plan of the call (plan: of the passes after the probe pass, once that has run)
+    FusePlan fp;
     // render_args: the arguments of every pass
     RadArgs base{};
     FilmArgs fa{};
     // the pass loop
     PassTimer timer{};
-    uint32_t passes = 0, launches = 0, plan = 0;
-    bool probe = false, plan_was_learnt = false;
+    uint32_t passes = 0, launches = 0;
+    // render_finish: the reduced statistics rows and the guard words of the call, read back
+    unsigned long long hstats[2 + 2 * MAX_DEPTH_STATS];
+    uint32_t hguard[WF_GUARD_WORDS] = {0};
 };
 }  // namespace
-// First render of a brute-force scene with the plan left to the library: the first PROBE_SPP samples are a pass of their own,
-// their path survival is read back (probe_plan) and decides the plan of all the other passes.  The film does not depend on how
-// the samples are split into passes, nor on the plan.
-constexpr uint32_t PROBE_SPP = 2;
 
-// Check and geometry: the argument rules, the launch structure of the scene, the rendered region.
+// What the scene's accelerator decides for a request (render_request.h RenderLaunch)
+static RenderLaunch render_launch(const pbrt_scene *s) {
+    static_assert(WF_REGION == REGION_SEGS_BVH * SEG_BVH, "both BVH launch structures cut a pass into the same regions");
+    const int k = s->accel_kernel;
+    RenderLaunch l;
+    l.brute = k == ACCEL_K_BRUTE || k == ACCEL_K_BRUTE_BIG;
+    l.keep = k == ACCEL_K_BRUTE && s->ds.n_prims <= 32;
+    l.region = rad_region_segs(k) * seg_threads(k);
+    l.owners = rad_owners_per_region(k);
+    l.rows_fused = rad_rows_per_region(k);
+    l.rows_streams = WF_SHADE_THREADS / 64u;
+    return l;
+}
+
+// Check: the context settled, the request made (the argument rules, the launch structure of the scene, the rendered region), the
+// device, the switches.
 static int render_check(Render &r) {
     pbrt_ctx *c = r.c;
-    const pbrt_camera *cam = r.cam;
-    const pbrt_film_desc *f = r.f;
-    void *d_out = r.d_out;
     if (int rcs = ctx_settle(c)) return rcs;
-    NEED(c, cam && f && d_out);
-    const uint32_t W = cam->film_w, H = cam->film_h;
-    NEED(c, W > 0 && H > 0 && f->crop_w > 0 && f->crop_h > 0);
-    NEED(c, (uint64_t)f->crop_x + f->crop_w <= W && (uint64_t)f->crop_y + f->crop_h <= H);
-    NEED(c, f->spp > 0 && f->max_depth > 0 && f->filter <= PBRT_FILTER_GAUSSIAN);
-    NEED(c, (uint64_t)W * H <= 0xffffffffull);
+    if (const char *why = render_request(&r.rq, r.cam, r.f, r.d_out != nullptr, render_launch(r.s))) return RULE_TEXT(c, why);
     HIPCHK(c, hipSetDevice(c->device));
-    // Brute-force scenes, or BVH scenes: these run intersection and shading as separate streams (kernels_wavefront.h);
-    // PBRT_FILM_NO_HIT_POOL keeps the fused k_bounce (one launch per bounce, shading in the lanes the traversal leaves) as the A/B
-    // reference -- in the diagnostic build (diag_driver.h)
-    r.brute = r.s->accel_kernel == ACCEL_K_BRUTE || r.s->accel_kernel == ACCEL_K_BRUTE_BIG;
-    r.wavefront = !r.brute && !(f->flags & PBRT_FILM_NO_HIT_POOL);
     r.sw = read_switches();
-    const uint32_t R = f->filter == PBRT_FILTER_BOX ? 0 : (f->filter == PBRT_FILTER_TENT ? 1 : 2);
-    r.rx0 = f->crop_x > R ? f->crop_x - R : 0;
-    r.ry0 = f->crop_y > R ? f->crop_y - R : 0;
-    const uint32_t rx1 = std::min(f->crop_x + f->crop_w + R, W), ry1 = std::min(f->crop_y + f->crop_h + R, H);
-    r.rw = rx1 - r.rx0;
-    r.rh = ry1 - r.ry0;
-    r.npix_r = (uint64_t)r.rw * r.rh;
-    r.film_px = (uint64_t)f->crop_w * f->crop_h;
     return PBRT_OK;
 }
 
 // Pass sizing and buffers: the paths in flight per pass, the buffers whose size follows it, the counters, the film accumulator and
-// the statistics rows, all cleared; the launch plan of the call.
+// the statistics rows; the launch shape of the streams.
 static int render_buffers(Render &r) {
     pbrt_scene *s = r.s;
     pbrt_ctx *c = r.c;
     const pbrt_film_desc *f = r.f;
-    const bool brute = r.brute, wavefront = r.wavefront;
+    const RenderRequest &rq = r.rq;
+    const bool wavefront = rq.wavefront;
     // default paths in flight per pass, measured on cbox 512^2 x 256 (one box): 2 / 4 / 8 / 16 / 32 / 64 Mi -> 9.55 / 8.56 / 8.14 / 7.92 /
     // 8.13 / 8.20 ms (fewer launch tails against cache residency of the ping-pong state)
     // round 2, fused first launch: 2 / 4 / 8 / 16 / 32 / 64 Mi -> 9.09 / 8.07 / 7.65 / 7.37 / 7.31 / 7.39 ms; BVH scenes keep 16 Mi
@@ -1426,63 +1311,55 @@ static int render_buffers(Render &r) {
     // launch plan turns out to need it.
     // (pbrt_ctx::call_seq was bumped by the entry point, before its first workspace request.)
     const uint64_t pass_paths = f->pass_paths ? f->pass_paths
-                                              : default_pass_paths(c, wavefront, brute ? (64u << 20) : (16u << 20), 16 + 2 * N_STATE * 4);
-    static_assert(WF_REGION == REGION_SEGS_BVH * SEG_BVH, "both BVH launch structures cut a pass into the same regions");
-    r.region = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
-    auto alloc_pass = [&](uint32_t cap, uint32_t nseg) -> int {
-        NEED(c, wavefront || (uint64_t)cap * N_STATE * 4 < 0xffffffffull);  // the tiled state arrays are addressed through 32-bit buffer offsets
-        if (wavefront) NEED(c, cap < WF_DEAD);  // ray records are addressed with two flag bits on top
-        r.Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
-        return r.Lhome && (!wavefront || wf_alloc(c, cap, nseg, &r.wfb)) ? PBRT_OK : PBRT_E_NOMEM;
+                                              : default_pass_paths(c, wavefront, rq.brute ? (64u << 20) : (16u << 20), 16 + 2 * N_STATE * 4);
+    auto alloc_pass = [&](const PassShape &ps) -> int {
+        r.Lhome = (float *)c->buf("Lhome", (size_t)ps.cap * 16);  // float4 (r, g, b, 0) per home
+        return r.Lhome && (!wavefront || wf_alloc(c, ps.cap, ps.nseg, &r.wfb)) ? PBRT_OK : PBRT_E_NOMEM;
     };
-    PassShape ps;
-    int rc;
-    if ((rc = size_pass(c, pass_paths, f->pass_paths != 0, f->spp, r.npix_r, r.region, true, alloc_pass, &ps)) != 0) return rc;
-    r.s_pass = ps.per_pass;
-    r.cap = ps.cap;
-    r.nseg = ps.nseg;
+    int rc = size_pass(c, pass_paths, f->pass_paths != 0, f->spp, rq.npix_r, rq.launch.region, true, wavefront, N_STATE, alloc_pass, &r.ps);
+    if (rc) return rc;
     if (wavefront) {
         r.wfp = wf_plan(s, r.sw);
         if ((rc = wf_set_attr(s, r.wfp)) != 0) return rc;
     }
     // live counters and statistics rows: one per region, or one per wave of it (BVH kernels: wave-private compaction)
-    r.n_own = r.nseg * rad_owners_per_region(s->accel_kernel);
+    r.n_own = r.ps.nseg * rq.launch.owners;
+    r.n_rows = r.ps.nseg * rq.rows_per_region();
     r.segA = (uint32_t *)c->buf("segA", (size_t)r.n_own * 4);
     r.segB = (uint32_t *)c->buf("segB", (size_t)r.n_own * 4);
-    r.acc = (float *)c->buf("film_acc", r.film_px * 16);
+    r.acc = (float *)c->buf("film_acc", rq.film_px * 16);
     r.dstats = (unsigned long long *)c->buf("stats", (2 + 2 * MAX_DEPTH_STATS) * 8);
-    r.n_rows = r.nseg * (wavefront ? WF_SHADE_THREADS / 64u : rad_rows_per_region(s->accel_kernel));  // statistics rows
-    // statistics rows in use: segments, shadow rays, one per depth (cleared and reduced per call: keep it to what the call touches)
-    r.stat_rows = 2 + (uint32_t)std::min<uint64_t>(f->max_depth, MAX_DEPTH_STATS);
-    const size_t segstats_bytes = (size_t)r.stat_rows * r.n_rows * 8;  // reduced at the end
     r.segstats = (unsigned long long *)c->buf("segstats", (size_t)(2 + 2 * MAX_DEPTH_STATS) * r.n_rows * 8);
     if (!r.segstats) return PBRT_E_NOMEM;
-    if (!r.Lhome || !r.segA || !r.segB || !r.acc || !r.dstats) return PBRT_E_NOMEM;
-    // k_shade counts the rays of every depth that hit something (rows HIT_ROW0 + d, for the byte model)
-    r.hit_rows = wavefront ? r.stat_rows - 2 : 0;
+    return r.Lhome && r.segA && r.segB && r.acc && r.dstats ? PBRT_OK : PBRT_E_NOMEM;
+}
+
+// What the call clears -- the film accumulator, the reduction target, the statistics rows in use (cleared and reduced per call:
+// kept to what the call touches) -- and the start of its clock.
+static int render_clear(Render &r) {
+    pbrt_ctx *c = r.c;
+    const RenderRequest &rq = r.rq;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemsetAsync(r.acc, 0, r.film_px * 16, st));
+    HIPCHK(c, hipMemsetAsync(r.acc, 0, rq.film_px * 16, st));
     HIPCHK(c, hipMemsetAsync(r.dstats, 0, (2 + 2 * MAX_DEPTH_STATS) * 8, st));
-    HIPCHK(c, hipMemsetAsync(r.segstats, 0, segstats_bytes, st));
-    if (r.hit_rows) HIPCHK(c, hipMemsetAsync(r.segstats + (size_t)HIT_ROW0 * r.n_rows, 0, (size_t)r.hit_rows * r.n_rows * 8, st));
+    HIPCHK(c, hipMemsetAsync(r.segstats, 0, (size_t)rq.stat_rows * r.n_rows * 8, st));
+    if (rq.hit_rows) HIPCHK(c, hipMemsetAsync(r.segstats + (size_t)HIT_ROW0 * r.n_rows, 0, (size_t)rq.hit_rows * r.n_rows * 8, st));
     HIPCHK(c, hipEventRecord(c->ev0, st));
     r.timer = PassTimer{c};
-    // the fuse plan of this call: the caller's, or the one learnt from the last render of this scene, or the library default
-    r.plan_was_learnt = brute && s->plan_hint_valid;
-    r.plan = !brute ? 0u
-             : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? ((f->flags >> 8) & 0xffu)
-             : (s->plan_hint_valid ? s->plan_hint : PBRT_DEFAULT_FUSE_PLAN);
-    r.probe = brute && !s->plan_hint_valid && f->spp >= 8 * PROBE_SPP && r.s_pass >= PROBE_SPP && !(f->flags & PBRT_FILM_FUSE_PLAN_SET);
     return PBRT_OK;
+}
+
+// The fuse plan of this call and whether a probe pass is to learn it (render_request.h fuse_plan)
+static void render_plan(Render &r, bool may_probe = true) {
+    r.fp = fuse_plan(r.rq, r.s->plan_hint_valid, r.s->plan_hint, r.ps.per_pass, may_probe);
 }
 
 // Argument blocks: what every pass hands its bounce kernels (key_mode 0: home -> (pixel of the rendered region, sample s_first +
 // home / npix_r)) and the film gather.
 static int render_args(Render &r) {
     pbrt_scene *s = r.s;
-    pbrt_ctx *c = r.c;
     const pbrt_film_desc *f = r.f;
-    const uint32_t rw = r.rw, cap = r.cap;
+    const uint32_t rw = r.rq.rw, cap = r.ps.cap;
     RadArgs &base = r.base;
     base.sc = s->ds;
     if ((f->flags & PBRT_FILM_NO_OCCLUDER_PRUNING) && base.sc.occ_prims) {  // diagnostic: shadow segments walk every primitive
@@ -1503,77 +1380,92 @@ static int render_args(Render &r) {
     base.rr_depth = f->rr_depth;
     base.seed = f->seed;
     base.key_mode = 0;
-    base.rx0 = r.rx0;
-    base.ry0 = r.ry0;
-    base.rw = rw;
-    base.npix_r = (uint32_t)r.npix_r;
-    base.tile_rows = r.rh & ~7u;
+    render_film_args(r.rq, &base);
     base.div_npix = make_fastdiv(base.npix_r);
     base.div_rw = make_fastdiv(rw);
     const std::initializer_list<uint32_t> probes = {0u, 1u, rw - 1, rw, rw + 1, base.npix_r - 1, base.npix_r, base.npix_r + 1, cap - 1, cap, 0xffffffffu};
-    NEED(c, fastdiv_exact(base.div_npix, base.npix_r, probes) && fastdiv_exact(base.div_rw, rw, probes));
-    base.film_w = r.cam->film_w;
-    base.film_h = r.cam->film_h;
+    NEED(r.c, fastdiv_exact(base.div_npix, base.npix_r, probes) && fastdiv_exact(base.div_rw, rw, probes));
     base.lds_bytes = s->lds_bytes;
-    // the keep words of the camera tiles (kernels_radiance.h k_tile_keep): the waves of the first bounce are whole blocks of 64 region
-    // indices only if the region's pixel count is a multiple of 64; rebuilt per render (camera and crop are the call's)
     base.tile_keep = nullptr;
-    c->tile_keep_last = false;
-    if (s->accel_kernel == ACCEL_K_BRUTE && s->ds.n_prims <= 32 && base.npix_r % 64 == 0 && !(f->flags & PBRT_FILM_NO_TILE_CULL)) {
-        TileKeepArgs ta;
-        ta.prims = s->ds.prims;
-        ta.n_prims = s->ds.n_prims;
-        ta.cam = *r.cam;
-        ta.rx0 = r.rx0;
-        ta.ry0 = r.ry0;
-        ta.rw = rw;
-        ta.tile_rows = base.tile_rows;
-        ta.n_blocks = base.npix_r / 64;
-        ta.div_rw = base.div_rw;
-        ta.keep = (uint32_t *)c->buf("tile_keep", (size_t)ta.n_blocks * 4);
-        if (!ta.keep) return PBRT_E_NOMEM;
-        pbrt_ctx::TileKeepKey &key = c->tile_keep_key;
-        const uint64_t gen = c->work.generation("tile_keep");
-        const bool same = key.gen == gen && key.scene == s->serial && memcmp(&key.cam, r.cam, sizeof(pbrt_camera)) == 0 && key.rx0 == r.rx0 &&
-                          key.ry0 == r.ry0 && key.rw == rw && key.rh == r.rh;
-        if (!same) {
-            hipLaunchKernelGGL(k_tile_keep, dim3(div_up(ta.n_blocks, 64)), dim3(64), 0, c->stream, ta);
-            HIPCHK(c, hipGetLastError());
-            ++c->tile_keep_builds;
-            key.gen = gen;
-            key.scene = s->serial;
-            key.cam = *r.cam;
-            key.rx0 = r.rx0;
-            key.ry0 = r.ry0;
-            key.rw = rw;
-            key.rh = r.rh;
-        }
-        base.tile_keep = ta.keep;
-        c->tile_keep_last = true;
-        c->tile_keep_words = ta.keep;
-    }
+    return PBRT_OK;
+}
+// ... and the film gather
+static void render_film(Render &r) {
+    const pbrt_film_desc *f = r.f;
     FilmArgs &fa = r.fa;
     fa.Lhome = r.Lhome;
     fa.acc = r.acc;
-    fa.cap = cap;
+    fa.cap = r.ps.cap;
     fa.cx0 = f->crop_x;
     fa.cy0 = f->crop_y;
     fa.cw = f->crop_w;
     fa.ch = f->crop_h;
-    fa.rx0 = r.rx0;
-    fa.ry0 = r.ry0;
-    fa.rw = rw;
-    fa.rh = r.rh;
-    fa.npix_r = (uint32_t)r.npix_r;
-    fa.tile_rows = base.tile_rows;
-    fa.film_w = r.cam->film_w;
-    fa.film_h = r.cam->film_h;
+    render_film_args(r.rq, &fa);
+    fa.rh = r.rq.rh;
     fa.filter = f->filter;
     fa.seed = f->seed;
+}
+
+// The keep words of the camera tiles (kernels_radiance.h k_tile_keep) for the requests that may carry them: built when the scene,
+// the camera, the region or the buffer is not what the context's table was built for (camera and crop are the call's)
+static int render_tile_keep(Render &r) {
+    pbrt_ctx *c = r.c;
+    c->tile_keep_last = false;
+    if (!r.rq.tile_keep) return PBRT_OK;
+    TileKeepArgs ta;
+    ta.prims = r.s->ds.prims;
+    ta.n_prims = r.s->ds.n_prims;
+    ta.cam = *r.cam;
+    render_region_args(r.rq, &ta);
+    ta.n_blocks = r.base.npix_r / 64;
+    ta.div_rw = r.base.div_rw;
+    ta.keep = (uint32_t *)c->buf("tile_keep", (size_t)ta.n_blocks * 4);
+    if (!ta.keep) return PBRT_E_NOMEM;
+    const pbrt_ctx::TileKeepKey key{c->work.generation("tile_keep"), r.s->serial, *r.cam, r.rq.rx0, r.rq.ry0, r.rq.rw, r.rq.rh};
+    if (!(key == c->tile_keep_key)) {
+        hipLaunchKernelGGL(k_tile_keep, dim3(div_up(ta.n_blocks, 64)), dim3(64), 0, c->stream, ta);
+        HIPCHK(c, hipGetLastError());
+        ++c->tile_keep_builds;
+        c->tile_keep_key = key;
+    }
+    r.base.tile_keep = ta.keep;
+    c->tile_keep_last = true;
+    c->tile_keep_words = ta.keep;
     return PBRT_OK;
 }
 
-// The bounces of one pass of a brute-force scene: the launches of the fuse plan, each walking chain_len bounces.
+// The bounce launches of the fused brute-force kernels over nseg_pass regions: the launches of the fuse plan, each walking chain_len
+// bounces, between the state sets in / out and the counters sin / sout (n_own of them).  camera: depth 0 generates its rays from the
+// film keys (else the rays are in `in` / sin).  At most `bound` bounces, whatever a.max_depth says.
+static int brute_bounces(pbrt_scene *s, RadArgs a, uint32_t plan, uint32_t nseg_pass, bool camera, uint32_t bound, float *in, float *out,
+                         uint32_t *sin, uint32_t *sout, uint32_t n_own, uint32_t *launches) {
+    pbrt_ctx *c = s->ctx;
+    int rc;
+    for (uint32_t depth = 0; depth < a.max_depth && depth < bound;) {
+        // bounces this launch walks: 2 at the depths of the fuse plan (the last bounce of a path only looks for emitters, so it
+        // is never worth a launch slot of its own either)
+        const uint32_t nb = chain_len(plan, depth, a.max_depth);
+        a.depth = depth;
+        a.nb = nb;
+        a.in = in;
+        a.out = out;
+        a.seg_in = sin;
+        a.seg_out = sout;
+        if ((rc = launch_bounce(s, a, nseg_pass, camera && depth == 0, nb)) != 0) return rc;
+        HIPCHK(c, hipGetLastError());
+        ++*launches;
+        std::swap(in, out);
+        std::swap(sin, sout);
+        const uint32_t depth_before = depth;
+        depth += nb;
+        bool dead;
+        if ((rc = poll_live(c, a.max_depth, depth_before, depth, sin, n_own, &dead)) != 0) return rc;
+        if (dead) break;
+    }
+    return PBRT_OK;
+}
+
+// The bounces of one pass of a brute-force scene.
 // The ping-pong path state (2 x 60 B per slot, 8 GB at 64 Mi paths) is only touched by a pass that needs more than one bounce
 // launch; with the plan that walks every bounce in one launch (the Cornell box) it is never written, so it is allocated per pass, for
 // the paths of THAT pass, when its plan says so.
@@ -1585,54 +1477,28 @@ static int render_args(Render &r) {
 constexpr uint32_t PASS_MAX_BOUNCES = 256;
 static int brute_pass(Render &r, RadArgs a, uint32_t nseg_pass) {
     pbrt_ctx *c = r.c;
-    const uint32_t max_depth = r.f->max_depth;
-    const bool one_launch = chain_len(r.plan, 0, max_depth) >= max_depth;
-    const size_t need = one_launch ? (size_t)r.region : (size_t)nseg_pass * r.region;
+    const uint32_t region = r.rq.launch.region;
+    const bool one_launch = chain_len(r.fp.plan, 0, a.max_depth) >= a.max_depth;
+    const size_t need = one_launch ? (size_t)region : (size_t)nseg_pass * region;
     float *in = (float *)c->buf("stateA", need * N_STATE * 4), *out = (float *)c->buf("stateB", need * N_STATE * 4);
     if (!in || !out) return PBRT_E_NOMEM;
     a.state_cap = (uint32_t)need;
-    uint32_t *sin = r.segA, *sout = r.segB;
-    int rc;
-    if ((rc = r.timer.begin()) != 0) return rc;
-    for (uint32_t depth = 0; depth < max_depth && depth < PASS_MAX_BOUNCES;) {
-        // bounces this launch walks: 2 at the depths of the fuse plan (the last bounce of a path only looks for emitters, so it
-        // is never worth a launch slot of its own either)
-        const uint32_t nb = chain_len(r.plan, depth, max_depth);
-        a.depth = depth;
-        a.nb = nb;
-        a.in = in;
-        a.out = out;
-        a.seg_in = sin;
-        a.seg_out = sout;
-        if ((rc = launch_bounce(r.s, a, nseg_pass, depth == 0, nb)) != 0) return rc;
-        HIPCHK(c, hipGetLastError());
-        ++r.launches;
-        std::swap(in, out);
-        std::swap(sin, sout);
-        const uint32_t depth_before = depth;
-        depth += nb;
-        bool dead;
-        if ((rc = poll_live(c, max_depth, depth_before, depth, sin, r.n_own, &dead)) != 0) return rc;
-        if (dead) break;
-    }
-    return PBRT_OK;
+    if (int rc = r.timer.begin()) return rc;
+    return brute_bounces(r.s, a, r.fp.plan, nseg_pass, true, PASS_MAX_BOUNCES, in, out, r.segA, r.segB, r.n_own, &r.launches);
 }
 
-// Pass loop: the samples in passes of s_pass (the probe pass first, if the plan is to be learnt), each through the bounces of its
-// launch structure and into the film accumulator.
+// Pass loop: the samples in the passes of the schedule (render_request.h PassSchedule: the probe pass first, if the plan is to be
+// learnt), each through the bounces of its launch structure and into the film accumulator.
 static int render_passes(Render &r) {
     pbrt_ctx *c = r.c;
     const pbrt_film_desc *f = r.f;
     int rc;
-    uint32_t s_step = r.s_pass;  // samples of a regular pass
-    for (uint32_t s0 = 0; s0 < f->spp; ++r.passes) {
-        const bool probing = r.probe && r.passes == 0;
-        const uint32_t sc = probing ? PROBE_SPP : std::min(s_step, f->spp - s0);
+    for (PassSchedule p{f->spp, r.ps.per_pass, r.fp.probe}; p.next(); ++r.passes) {
         RadArgs a = r.base;
-        a.n_paths = (uint32_t)(r.npix_r * sc);
-        a.s_first = f->sample_offset + s0;
-        const uint32_t nseg_pass = div_up(a.n_paths, r.region);
-        if (r.wavefront) {
+        a.n_paths = (uint32_t)(r.rq.npix_r * p.sc);
+        a.s_first = f->sample_offset + p.s0;
+        const uint32_t nseg_pass = div_up(a.n_paths, r.rq.launch.region);
+        if (r.rq.wavefront) {
             if ((rc = r.timer.begin()) != 0) return rc;
             rc = wf_bounces(r.s, wf_args(a), r.wfb, r.wfp, nseg_pass, true, &r.launches);
         } else {
@@ -1641,68 +1507,54 @@ static int render_passes(Render &r) {
         if (rc) return rc;
         if ((rc = r.timer.end()) != 0) return rc;
         r.fa.s_first = a.s_first;
-        r.fa.s_count = sc;
+        r.fa.s_count = p.sc;
         film_accum(c, r.fa);
         HIPCHK(c, hipGetLastError());
-        s0 += sc;
-        if (probing) {  // learn the plan from the probe pass
-            if ((rc = probe_plan(c, r.segstats, r.n_rows, r.stat_rows, r.dstats, f->max_depth, &r.plan)) != 0) return rc;
-            const uint32_t rem = f->spp - s0;
-            s_step = div_up(rem, div_up(rem, r.s_pass));  // equal passes for what is left
-        }
+        // learn the plan from the probe pass
+        if (p.probing() && (rc = probe_plan(c, r.segstats, r.n_rows, r.rq.stat_rows, r.dstats, f->max_depth, &r.fp.plan)) != 0) return rc;
     }
     return PBRT_OK;
 }
 
-// Finish: the film resolved into d_out, the statistics rows reduced and read back with the guard words, pbrt_stats filled (the plan
-// that ran and where it came from, the byte model), and the plan this scene's next render starts from.
+// Finish: the film resolved into d_out, the statistics rows reduced and read back with the guard words.
 static int render_finish(Render &r) {
-    pbrt_scene *s = r.s;
     pbrt_ctx *c = r.c;
-    const pbrt_film_desc *f = r.f;
-    const bool wavefront = r.wavefront;
+    const RenderRequest &rq = r.rq;
     const uint32_t n_rows = r.n_rows;
     hipStream_t st = c->stream;
     int rc;
-    hipLaunchKernelGGL(k_film_resolve, dim3(div_up(r.film_px, 256)), dim3(256), 0, st, r.acc, (float *)r.d_out, (uint32_t)r.film_px,
-                       (uint32_t)((f->flags & PBRT_FILM_RAW_ACCUM) ? 1 : 0));
+    hipLaunchKernelGGL(k_film_resolve, dim3(div_up(rq.film_px, 256)), dim3(256), 0, st, r.acc, (float *)r.d_out, (uint32_t)rq.film_px,
+                       (uint32_t)(rq.out_floats == 4 ? 1 : 0));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev1, st));
-    unsigned long long hstats[2 + 2 * MAX_DEPTH_STATS];
-    hipLaunchKernelGGL(k_reduce_stats, dim3(r.stat_rows, REDUCE_SLICES), dim3(256), 0, st, r.segstats, n_rows, (size_t)n_rows, r.dstats);
-    if (r.hit_rows)
-        hipLaunchKernelGGL(k_reduce_stats, dim3(r.hit_rows, REDUCE_SLICES), dim3(256), 0, st, r.segstats + (size_t)HIT_ROW0 * n_rows, n_rows,
+    hipLaunchKernelGGL(k_reduce_stats, dim3(rq.stat_rows, REDUCE_SLICES), dim3(256), 0, st, r.segstats, n_rows, (size_t)n_rows, r.dstats);
+    if (rq.hit_rows)
+        hipLaunchKernelGGL(k_reduce_stats, dim3(rq.hit_rows, REDUCE_SLICES), dim3(256), 0, st, r.segstats + (size_t)HIT_ROW0 * n_rows, n_rows,
                            (size_t)n_rows, r.dstats + HIT_ROW0);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hstats, r.dstats, sizeof hstats, hipMemcpyDeviceToHost, st));
-    uint32_t hguard[WF_GUARD_WORDS] = {0};
-    if (wavefront && (rc = wf_guard_fetch(c, hguard)) != 0) return rc;
+    HIPCHK(c, hipMemcpyAsync(r.hstats, r.dstats, sizeof r.hstats, hipMemcpyDeviceToHost, st));
+    if (rq.wavefront && (rc = wf_guard_fetch(c, r.hguard)) != 0) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
-    if (wavefront && (rc = wf_check_guard(c, hguard)) != 0) return rc;
-    if ((rc = call_stats(c, hstats, r.npix_r * f->spp, r.launches, r.passes, true, r.timer.n_ev)) != 0) return rc;
+    return rq.wavefront ? wf_check_guard(c, r.hguard) : PBRT_OK;
+}
+
+// pbrt_stats filled (the plan that ran and where it came from, the byte model), and the plan this scene's next render starts from.
+static int render_stats(Render &r) {
+    pbrt_ctx *c = r.c;
+    const unsigned long long *hstats = r.hstats;
+    if (int rc = call_stats(c, hstats, r.rq.npix_r * r.f->spp, r.launches, r.passes, true, r.timer.n_ev)) return rc;
     pbrt_stats &S = c->stats;
-    S.fuse_plan = r.plan;
-    S.plan_source = wavefront ? PBRT_PLAN_STREAMS
-                    : (f->flags & PBRT_FILM_FUSE_PLAN_SET) ? PBRT_PLAN_CALLER
-                    : r.probe ? PBRT_PLAN_PROBED
-                    : r.plan_was_learnt ? PBRT_PLAN_LEARNT : PBRT_PLAN_DEFAULT;
-    S.pass_paths = (uint64_t)r.npix_r * r.s_pass;
-    if (r.brute && hstats[2] > 0) {  // remember what this scene's paths do for the next render of it
-        s->plan_hint = plan_from_survival(hstats + 2, (uint32_t)std::min<uint64_t>(f->max_depth, MAX_DEPTH_STATS));
-        s->plan_hint_valid = true;
+    S.fuse_plan = r.fp.plan;
+    S.plan_source = r.fp.source;
+    S.pass_paths = (uint64_t)r.rq.npix_r * r.ps.per_pass;
+    if (r.rq.brute && hstats[2] > 0) {  // remember what this scene's paths do for the next render of it
+        r.s->plan_hint = plan_from_survival(hstats + 2, (uint32_t)std::min<uint64_t>(r.f->max_depth, MAX_DEPTH_STATS));
+        r.s->plan_hint_valid = true;
     }
-    uint64_t tot, bb;
-    radiance_model_bytes(hstats + 2, MAX_DEPTH_STATS, S.samples, r.film_px, r.passes, r.plan, f->max_depth,
-                         wavefront ? hstats + HIT_ROW0 : nullptr, &tot, &bb);
-    if (wavefront) {
-        tot -= bb;
-        uint64_t trb = 0;
-        bb = wavefront_model_bytes(hstats + 2, hstats + HIT_ROW0, MAX_DEPTH_STATS, S.shadow_rays, &trb);
-        tot += bb;
-        S.trace_model_bytes = trb;
-    }
-    S.model_bytes = tot;
-    S.bounce_model_bytes = bb;
+    const ModelBytes m = render_model_bytes(r.rq, hstats, S.samples, r.passes, r.fp.plan);
+    S.model_bytes = m.total;
+    S.bounce_model_bytes = m.bounce;
+    if (r.rq.wavefront) S.trace_model_bytes = m.trace;
     return PBRT_OK;
 }
 
@@ -1718,14 +1570,19 @@ static int render_impl(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_de
 #ifdef PBRT_DIAG
     if (diag_selected(r)) return diag_render(r);
 #else
-    if ((f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || (!r.brute && (f->flags & PBRT_FILM_NO_HIT_POOL)))
+    if ((f->flags & (PBRT_FILM_REGEN | PBRT_FILM_WALK_SET)) || (!r.rq.brute && (f->flags & PBRT_FILM_NO_HIT_POOL)))
         return r.c->fail(PBRT_E_UNSUPPORTED, "PBRT_FILM_REGEN / PBRT_FILM_WALK_FROM / PBRT_FILM_NO_HIT_POOL select diagnostic launch "
                                              "structures: build libpbrt_hip_diag.so (make -C csrc diag)");
 #endif
     if ((rc = render_buffers(r)) != 0) return rc;
+    if ((rc = render_clear(r)) != 0) return rc;
+    render_plan(r);
     if ((rc = render_args(r)) != 0) return rc;
+    if ((rc = render_tile_keep(r)) != 0) return rc;
+    render_film(r);
     if ((rc = render_passes(r)) != 0) return rc;
-    return render_finish(r);
+    if ((rc = render_finish(r)) != 0) return rc;
+    return render_stats(r);
 }
 
 #ifdef PBRT_BVH_PROBE  // diagnostic builds only (tools/bvh_probe.py); not part of the ABI
@@ -1739,6 +1596,143 @@ extern "C" int pbrt_debug_bvh_probe(unsigned long long *out, int reset) {
 }
 #endif
 
+// ---- pbrt_integrator_sample: radiance along the caller's rays, on the pieces of a render ------------------------------------------
+// One pass of n paths (no halving) whose first bounce reads the rays from the state instead of generating them; key_mode 1: the key
+// of ray i is (index_offset + i, sample_index).
+namespace {
+struct SampleCall {
+    pbrt_scene *s;
+    pbrt_ctx *c;
+    uint32_t n;
+    const float *o, *d, *tmax;
+    uint32_t index_offset, sample_index, seed, max_depth, rr_depth;
+    float *rgb;
+    // sample_check
+    Switches sw;
+    RenderLaunch launch;
+    bool streams = false;  // trace / shade streams
+    // sample_buffers: the pass, its counters and rows, what differs between the two launch structures (path state and live counters),
+    // the radiance records, the statistics rows (k_shade: and its hit rows), the caller's rays on the device
+    PassShape ps;
+    uint32_t n_own = 0, n_rows = 0;
+    WfBufs wfb{};
+    WfPlan wfp;
+    float *stA = nullptr, *stB = nullptr, *Lhome = nullptr, *dO = nullptr, *dD = nullptr, *dT = nullptr;
+    uint32_t *segA = nullptr, *segB = nullptr;
+    unsigned long long *dstats = nullptr, *rows = nullptr;
+    size_t rows_bytes = 0;
+    RadArgs a{};
+    uint32_t hguard[WF_GUARD_WORDS] = {0};
+};
+}  // namespace
+
+static int sample_check(SampleCall &q) {
+    pbrt_ctx *c = q.c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rcs = ctx_settle(c)) return rcs;
+    ++c->call_seq;
+    q.sw = read_switches();
+    q.launch = render_launch(q.s);
+    q.streams = !q.launch.brute;
+    return one_pass(c, q.n, 1, q.n, q.launch.region, false, q.streams, N_STATE, &q.ps);
+}
+
+static int sample_buffers(SampleCall &q) {
+    pbrt_scene *s = q.s;
+    pbrt_ctx *c = q.c;
+    const uint32_t cap = q.ps.cap, nseg = q.ps.nseg;
+    q.n_own = nseg * q.launch.owners;
+    if (q.streams) {
+        if (!wf_alloc(c, cap, nseg, &q.wfb)) return PBRT_E_NOMEM;
+        q.wfp = wf_plan(s, q.sw);
+        if (int rc = wf_set_attr(s, q.wfp)) return rc;
+    } else {
+        q.stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
+        q.stB = (float *)c->buf("stateB", (size_t)cap * N_STATE * 4);
+        q.segA = (uint32_t *)c->buf("segA", (size_t)q.n_own * 4);
+        q.segB = (uint32_t *)c->buf("segB", (size_t)q.n_own * 4);
+        q.dstats = (unsigned long long *)c->buf("stats", (2 + MAX_DEPTH_STATS) * 8);
+        if (!q.stA || !q.stB || !q.segA || !q.segB || !q.dstats) return PBRT_E_NOMEM;
+    }
+    q.Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
+    q.n_rows = nseg * (q.streams ? q.launch.rows_streams : q.launch.rows_fused);
+    q.rows_bytes = (size_t)(2 + (q.streams ? 2 : 1) * MAX_DEPTH_STATS) * q.n_rows * 8;
+    q.rows = (unsigned long long *)c->buf("segstats", q.rows_bytes);
+    const size_t n = q.n;
+    const auto io_at = stage_layout(stage_in(q.o, 3 * n), stage_in(q.d, 3 * n), stage_in(q.tmax, n));
+    char *io = (char *)c->buf("leaf_io", io_at.total);
+    if (!q.Lhome || !q.rows || !io) return PBRT_E_NOMEM;
+    q.dO = (float *)(io + io_at.offset[0]);
+    q.dD = (float *)(io + io_at.offset[1]);
+    q.dT = (float *)(io + io_at.offset[2]);
+    return PBRT_OK;
+}
+
+// the rays uploaded, and what the call clears
+static int sample_upload(SampleCall &q) {
+    pbrt_ctx *c = q.c;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(q.dO, q.o, (size_t)q.n * 12, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(q.dD, q.d, (size_t)q.n * 12, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(q.dT, q.tmax, (size_t)q.n * 4, hipMemcpyHostToDevice, st));
+    if (q.dstats) HIPCHK(c, hipMemsetAsync(q.dstats, 0, (2 + MAX_DEPTH_STATS) * 8, st));
+    HIPCHK(c, hipMemsetAsync(q.rows, 0, q.rows_bytes, st));
+    HIPCHK(c, hipMemsetAsync(q.Lhome, 0, (size_t)q.ps.cap * 16, st));
+    return PBRT_OK;
+}
+
+// key_mode 1: key = (index_offset + home, sample_index) for the caller's n rays
+static void sample_args(SampleCall &q) {
+    RadArgs &a = q.a;
+    a.sc = q.s->ds;
+    a.Lhome = q.Lhome;
+    a.stats = q.rows;
+    a.stat_stride = q.n_rows;
+    a.cap = q.ps.cap;
+    a.state_cap = q.ps.cap;
+    a.n_paths = q.n;
+    a.max_depth = q.max_depth;
+    a.rr_depth = q.rr_depth;
+    a.seed = q.seed;
+    a.key_mode = 1;
+    a.npix_r = 1;
+    a.rw = 1;
+    a.div_npix = a.div_rw = make_fastdiv(1);
+    a.index_offset = q.index_offset;
+    a.sample_index = q.sample_index;
+    a.lds_bytes = q.s->lds_bytes;
+}
+
+// the rays into the state of their launch structure, and its bounces: the streams', or the fused kernels' with one launch per bounce
+// and as many bounces as the paths live (a single full pass: every counter poll_live sums is this call's)
+static int sample_bounces(SampleCall &q) {
+    pbrt_scene *s = q.s;
+    const uint32_t n = q.n, cap = q.ps.cap, nseg = q.ps.nseg, n_own = q.n_own;
+    hipStream_t st = q.c->stream;
+    uint32_t launches = 0;
+    if (q.streams) {
+        hipLaunchKernelGGL(k_init_rays_wf, dim3(div_up(std::max(n, nseg), 256)), dim3(256), 0, st, q.wfb.stA, cap, q.wfb.segA, nseg, n, q.dO, q.dD, q.dT);
+        if (int rc = wf_bounces(s, wf_args(q.a), q.wfb, q.wfp, nseg, false, &launches)) return rc;
+        return wf_guard_fetch(q.c, q.hguard);
+    }
+    hipLaunchKernelGGL(k_init_rays, dim3(div_up(std::max(n, n_own), 256)), dim3(256), 0, st, q.stA, q.segA, n_own,
+                       q.launch.region / q.launch.owners, n, q.dO, q.dD, q.dT);
+    return brute_bounces(s, q.a, 0u, nseg, false, q.max_depth, q.stA, q.stB, q.segA, q.segB, n_own, &launches);
+}
+
+static int sample_read(SampleCall &q) {
+    pbrt_ctx *c = q.c;
+    const uint32_t n = q.n;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (q.streams)
+        if (int rc = wf_check_guard(c, q.hguard)) return rc;
+    std::vector<float> rec((size_t)n * 4);
+    HIPCHK(c, hipMemcpy(rec.data(), q.Lhome, (size_t)n * 16, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) q.rgb[(size_t)k * n + i] = rec[(size_t)i * 4 + k];
+    return PBRT_OK;
+}
+
 extern "C" {
 
 int pbrt_render_radiance_dev(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_desc *f, void *d_out) {
@@ -1747,13 +1741,16 @@ int pbrt_render_radiance_dev(pbrt_scene *s, const pbrt_camera *cam, const pbrt_f
     return render_impl(s, cam, f, d_out);
 }
 
+// (the request is made here as well, before anything is asked of the workspace: film_out takes its size from it)
 int pbrt_render_radiance(pbrt_scene *s, const pbrt_camera *cam, const pbrt_film_desc *f, float *out) {
     if (!s) return PBRT_E_INVALID;
     pbrt_ctx *c = s->ctx;
     NEED(c, cam && f && out);
+    RenderRequest rq;
+    if (const char *why = render_request(&rq, cam, f, true, render_launch(s))) return RULE_TEXT(c, why);
     HIPCHK(c, hipSetDevice(c->device));
     ++c->call_seq;
-    const size_t n = (size_t)f->crop_w * f->crop_h * ((f->flags & PBRT_FILM_RAW_ACCUM) ? 4 : 3);
+    const size_t n = (size_t)rq.film_px * rq.out_floats;
     void *d = c->buf("film_out", n * 4);
     if (!d) return PBRT_E_NOMEM;
     int rc = render_impl(s, cam, f, d);
@@ -1766,103 +1763,16 @@ int pbrt_integrator_sample(pbrt_scene *s, uint32_t n, const float *o, const floa
                            uint32_t index_offset, uint32_t sample_index, uint32_t seed, uint32_t max_depth,
                            uint32_t rr_depth, float *rgb) {
     if (!s) return PBRT_E_INVALID;
-    pbrt_ctx *c = s->ctx;
-    NEED(c, o && d && tmax && rgb && max_depth > 0);
+    NEED(s->ctx, o && d && tmax && rgb && max_depth > 0);
     if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rcs = ctx_settle(c)) return rcs;
+    SampleCall q{s, s->ctx, n, o, d, tmax, index_offset, sample_index, seed, max_depth, rr_depth, rgb};
     int rc;
-    ++c->call_seq;
-    const Switches sw = read_switches();
-    const uint32_t REGION = rad_region_segs(s->accel_kernel) * seg_threads(s->accel_kernel);
-    const uint32_t cap = div_up(n, REGION) * REGION, nseg = cap / REGION;
-    const bool streams = s->accel_kernel == ACCEL_K_BVH_GLOBAL || s->accel_kernel == ACCEL_K_BVH_LDS;  // trace / shade streams
-    // what differs: the path state and live counters of the two launch structures
-    WfBufs wfb{};
-    WfPlan wfp;
-    float *stA = nullptr, *stB = nullptr;
-    uint32_t *segA = nullptr, *segB = nullptr;
-    unsigned long long *dstats = nullptr;
-    const uint32_t owners = rad_owners_per_region(s->accel_kernel), n_own = nseg * owners;  // see render_impl
-    if (streams) {
-        NEED(c, cap < WF_DEAD);
-        if (!wf_alloc(c, cap, nseg, &wfb)) return PBRT_E_NOMEM;
-        wfp = wf_plan(s, sw);
-        if ((rc = wf_set_attr(s, wfp)) != 0) return rc;
-    } else {
-        stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
-        stB = (float *)c->buf("stateB", (size_t)cap * N_STATE * 4);
-        segA = (uint32_t *)c->buf("segA", (size_t)n_own * 4);
-        segB = (uint32_t *)c->buf("segB", (size_t)n_own * 4);
-        dstats = (unsigned long long *)c->buf("stats", (2 + MAX_DEPTH_STATS) * 8);
-        if (!stA || !stB || !segA || !segB || !dstats) return PBRT_E_NOMEM;
-    }
-    float *Lhome = (float *)c->buf("Lhome", (size_t)cap * 16);  // float4 (r, g, b, 0) per home
-    const uint32_t n_rows = nseg * (streams ? WF_SHADE_THREADS / 64u : rad_rows_per_region(s->accel_kernel));
-    const size_t rows_bytes = (size_t)(2 + (streams ? 2 : 1) * MAX_DEPTH_STATS) * n_rows * 8;  // statistics rows (k_shade: and its hit rows)
-    unsigned long long *rows = (unsigned long long *)c->buf("segstats", rows_bytes);
-    const auto io_at = stage_layout(stage_in(o, 3 * (size_t)n), stage_in(d, 3 * (size_t)n), stage_in(tmax, n));
-    char *io = (char *)c->buf("leaf_io", io_at.total);
-    if (!Lhome || !rows || !io) return PBRT_E_NOMEM;
-    float *dO = (float *)(io + io_at.offset[0]), *dD = (float *)(io + io_at.offset[1]), *dT = (float *)(io + io_at.offset[2]);
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(dO, o, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(dD, d, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(dT, tmax, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (dstats) HIPCHK(c, hipMemsetAsync(dstats, 0, (2 + MAX_DEPTH_STATS) * 8, st));
-    HIPCHK(c, hipMemsetAsync(rows, 0, rows_bytes, st));
-    HIPCHK(c, hipMemsetAsync(Lhome, 0, (size_t)cap * 16, st));
-    // key_mode 1: key = (index_offset + home, sample_index) for the caller's n rays
-    RadArgs a{};
-    a.sc = s->ds;
-    a.Lhome = Lhome;
-    a.stats = rows;
-    a.stat_stride = n_rows;
-    a.cap = cap;
-    a.state_cap = cap;
-    a.n_paths = n;
-    a.max_depth = max_depth;
-    a.rr_depth = rr_depth;
-    a.seed = seed;
-    a.key_mode = 1;
-    a.npix_r = 1;
-    a.rw = 1;
-    a.div_npix = a.div_rw = make_fastdiv(1);
-    a.index_offset = index_offset;
-    a.sample_index = sample_index;
-    a.lds_bytes = s->lds_bytes;
-    uint32_t hguard[WF_GUARD_WORDS] = {0};
-    if (streams) {
-        hipLaunchKernelGGL(k_init_rays_wf, dim3(div_up(std::max(n, nseg), 256)), dim3(256), 0, st, wfb.stA, cap, wfb.segA, nseg, n, dO, dD, dT);
-        uint32_t launches = 0;
-        if ((rc = wf_bounces(s, wf_args(a), wfb, wfp, nseg, false, &launches)) != 0) return rc;
-        if ((rc = wf_guard_fetch(c, hguard)) != 0) return rc;
-    } else {
-        hipLaunchKernelGGL(k_init_rays, dim3(div_up(std::max(n, n_own), 256)), dim3(256), 0, st, stA, segA, n_own, REGION / owners, n, dO, dD, dT);
-        float *in = stA, *out = stB;
-        uint32_t *sin = segA, *sout = segB;
-        for (uint32_t depth = 0; depth < max_depth; ++depth) {
-            a.depth = depth;
-            a.in = in;
-            a.out = out;
-            a.seg_in = sin;
-            a.seg_out = sout;
-            if ((rc = launch_bounce(s, a, nseg, false)) != 0) return rc;
-            HIPCHK(c, hipGetLastError());
-            std::swap(in, out);
-            std::swap(sin, sout);
-            bool dead;
-            if ((rc = poll_live(c, max_depth, depth, depth + 1, sin, n_own, &dead)) != 0) return rc;
-            if (dead) break;
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (streams && (rc = wf_check_guard(c, hguard)) != 0) return rc;
-    std::vector<float> rec((size_t)n * 4);
-    HIPCHK(c, hipMemcpy(rec.data(), Lhome, (size_t)n * 16, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) rgb[(size_t)k * n + i] = rec[(size_t)i * 4 + k];
-    return PBRT_OK;
+    if ((rc = sample_check(q)) != 0) return rc;
+    if ((rc = sample_buffers(q)) != 0) return rc;
+    if ((rc = sample_upload(q)) != 0) return rc;
+    sample_args(q);
+    if ((rc = sample_bounces(q)) != 0) return rc;
+    return sample_read(q);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1988,7 +1898,7 @@ static int us_wf_pass(pbrt_scene *s, UsArgs a, const WfBufs &b, const WfPlan &p,
     auto trace = [&](uint32_t depth, bool have_shadows) {
         t.depth = depth;
         pp.bind(t, b, have_shadows, 0, nreg);
-        wf_launch_trace(s, t, p, wf_trace_grid(nreg, depth >= 2 ? p.grid_deep : p.grid_mult, (uint32_t)c->n_cu), false, st);
+        wf_launch_trace(s, t, p, wf_trace_grid(nreg, depth >= 2 ? p.grid_deep : p.grid_mult, (uint32_t)c->n_cu, WF_KMAX), false, st);
         ++*launches;
     };
     auto shade = [&](uint32_t depth, bool tab, bool have_shadows) {
@@ -2055,13 +1965,11 @@ struct Acquire {
 // the buffers whose size follows the pass (size_pass: again with half the paths after a failed allocation)
 struct UsAllocPass {
     Acquire &q;
-    int operator()(uint32_t cap, uint32_t nseg) const {
+    int operator()(const PassShape &ps) const {
         pbrt_ctx *c = q.c;
-        NEED(c, q.streams || (uint64_t)cap * US_N_STATE * 4 < 0xffffffffull);  // the state tiles are addressed through 32-bit buffer offsets
-        NEED(c, !q.streams || cap < WF_DEAD);
-        if (q.streams) return wf_alloc(c, cap, nseg, &q.wfb) ? PBRT_OK : PBRT_E_NOMEM;
-        q.stA = (float *)c->buf("stateA", (size_t)cap * N_STATE * 4);
-        q.stB = q.stA ? (float *)c->buf("stateB", (size_t)cap * N_STATE * 4) : nullptr;
+        if (q.streams) return wf_alloc(c, ps.cap, ps.nseg, &q.wfb) ? PBRT_OK : PBRT_E_NOMEM;
+        q.stA = (float *)c->buf("stateA", (size_t)ps.cap * N_STATE * 4);
+        q.stB = q.stA ? (float *)c->buf("stateB", (size_t)ps.cap * N_STATE * 4) : nullptr;
         return q.stA && q.stB ? PBRT_OK : PBRT_E_NOMEM;
     }
 };
@@ -2101,7 +2009,8 @@ static int us_buffers(Acquire &q) {
     // context's workspace limit.  A failed allocation halves the pass (size_pass); the echoes do not depend on the pass size.
     q.region = streams ? WF_REGION : us_region_segs(s->accel_kernel, q.rq.emit) * seg_threads(s->accel_kernel);
     const uint64_t pass_paths = default_pass_paths(c, streams, US_PASS_PATHS, 2 * N_STATE * 4);
-    if ((rc = size_pass(c, pass_paths, false, q.ppr, q.rq.n_rays, q.region, false, UsAllocPass{q}, &q.ps)) != 0) return rc;
+    // (the fused ultrasound kernels address US_N_STATE dwords per slot of the state tiles)
+    if ((rc = size_pass(c, pass_paths, false, q.ppr, q.rq.n_rays, q.region, false, streams, US_N_STATE, UsAllocPass{q}, &q.ps)) != 0) return rc;
     if (streams) {
         q.wfp = wf_plan(s, q.sw);
         q.wfp.packet = false;
