@@ -5,6 +5,7 @@
 #include "../../include/pbrt_hip.h"
 #include "device_math.h"
 #include "prim_runs.h"
+#include "scene_request.h"  // ACCEL_K_*, TAB_MAX, LDS_IMAGE_NODE_BYTES, BVH_STK_OVF / _MAX: the constants scene creation shares with the kernels
 
 // BVH4 inner node, 64 bytes (bvh_build.h HostNode4): lower corner of the node's box, a power-of-two grid step per axis and
 // the boxes of FOUR children on that 8-bit grid, rounded outward -- one node read decides four descents.
@@ -110,7 +111,6 @@ struct TreeLds {
         return {q[0], q[1], q[2], q[3], q[4]};
     }
 };
-#define LDS_IMAGE_NODE_BYTES 56u
 #define BVH_LEAF 0x80000000u
 #define BVH_SENT 0xffffffffu  // bottom of the traversal stack
 
@@ -126,7 +126,7 @@ struct DevScene {
     // BRUTE only: the primitives that can occlude a SEGMENT between two points of the scene (copies, any
     // order).  Planar primitives on a supporting plane of the scene's convex hull (all other geometry and
     // every point emitter on one side) can never be crossed by such a segment and are left out, e.g. the
-    // five walls of the Cornell box (pbrt_api.hip: find_occluders).  Unbounded occlusion rays (ultrasound
+    // five walls of the Cornell box (scene_request.h: find_occluders).  Unbounded occlusion rays (ultrasound
     // mode, pbrt_ray_test) always walk the full list.
     const pbrt_prim *occ_prims;
     uint32_t n_occ;
@@ -567,9 +567,7 @@ DEV BoxRay make_box_ray(V3 o, V3 d) {
 // anything deeper goes to a private array in scratch memory.  The two live in different address spaces BY TYPE (LDS_AS /
 // PRIV_AS): the rows can only be reached by ds_* instructions, the overflow only by scratch_* ones, and no pointer can stand
 // for both.  The bottom of the stack is BVH_SENT: the first push stores it in row 0, the last pop brings it back.  The host
-// checks depth <= BVH_STK_MAX and nodes < 2^24.
-#define BVH_STK_OVF 30
-#define BVH_STK_MAX (BVH_STK_OVF + 2)  // guaranteed capacity whatever n_rows is (>= 2 rows are always there)
+// checks depth <= BVH_STK_MAX and nodes < 2^24 (scene_request.h tree_placement, where BVH_STK_OVF and BVH_STK_MAX are defined).
 struct BvhStack {
     LDS_AS uint32_t *col;  // this thread's column: entry of row r at col[r << shift]; nullptr: brute-force kernels
     uint32_t shift;        // log2(threads of the workgroup)

@@ -52,12 +52,7 @@ __host__ __device__ constexpr uint32_t rad_region_segs(int accel);
 #endif
 __host__ __device__ constexpr uint32_t us_region_segs(int, bool emit = false) { return emit ? REGION_SEGS_US_EMIT : REGION_SEGS_US; }
 
-// ACCEL_K_BRUTE      uniform primitive loop (scalar loads) + shading tables staged in LDS; every table <= 32 entries,
-//                    no analytic cones (device_scene.h brute_intersect CONES)
-// ACCEL_K_BVH_GLOBAL stackless BVH, nodes / primitives through the vector caches (scene larger than LDS)
-// ACCEL_K_BVH_LDS    stackless BVH, nodes + primitives + ids staged in LDS per workgroup
-// ACCEL_K_BRUTE_BIG  uniform primitive loop, tables in global memory (brute force forced on a large scene)
-enum { ACCEL_K_BRUTE = 0, ACCEL_K_BVH_GLOBAL = 1, ACCEL_K_BVH_LDS = 2, ACCEL_K_BRUTE_BIG = 3 };
+// (ACCEL_K_BRUTE, _BVH_GLOBAL, _BVH_LDS, _BRUTE_BIG: scene_request.h, where a scene's is chosen)
 // k_bounce only: ACCEL_K_BRUTE_BIG with the rough / Fresnel conductor code (scenes that hold such a material).  A template
 // argument of that kernel, never a pbrt_scene::accel_kernel: inside the kernel it is ACCEL_K_BRUTE_BIG + GLOSSY.
 enum { ACCEL_K_BRUTE_GLOSSY = 4 };
@@ -106,7 +101,6 @@ __host__ __device__ constexpr uint32_t rad_owners_per_region(int) {
 __host__ __device__ constexpr uint32_t rad_rows_per_region(int accel) {
     return rad_wave_private(accel) ? seg_threads(accel) / 64 : 1;
 }
-#define TAB_MAX 32
 #define TAB_DW (TAB_MAX * 16 + TAB_MAX * 8 + TAB_MAX * 12 + TAB_MAX + TAB_MAX)
 
 struct RadArgs {

@@ -14,8 +14,7 @@
 #include <tuple>
 #include <vector>
 
-#include "bvh_build.h"
-#include "prim_runs.h"
+#include "scene_request.h"
 #include "bf_request.h"
 #include "us_request.h"
 #include "kernels_us.h"
@@ -156,19 +155,9 @@ struct pbrt_ctx {
     }
 };
 
-struct pbrt_scene {
+struct pbrt_scene : SceneFacts {  // (scene_request.h: accel_kernel, lds_bytes, bvh_depth, curved, cylinders, glossy, small_tables, mat_types)
     pbrt_ctx *ctx = nullptr;
     DevScene ds{};
-    int accel_kernel = ACCEL_K_BRUTE;
-    uint32_t lds_bytes = 0;
-    uint32_t bvh_depth = 0;  // levels of inner nodes of the BVH4
-    bool curved = true;      // the scene holds spheres, cones or cylinders (else the BVH stream kernels run without their tests)
-    bool cylinders = false;  // the scene holds cylinders (else the stream shading kernels run without their code)
-    // a material is a ROUGHCONDUCTOR or CONDUCTOR_FRESNEL (else the bounce and the stream shading kernels run the instances
-    // without their code); follows pbrt_scene_update_material through mat_types
-    bool glossy = false;
-    bool small_tables = false;  // brute-force scenes: everything the ACCEL_K_BRUTE variant needs holds (tables <= 32 entries, no quadrics, no vertex normals)
-    std::vector<uint32_t> mat_types;
     std::vector<void *> allocs;
     pbrt_material *d_mats = nullptr;
     uint32_t n_mats = 0;
@@ -186,6 +175,12 @@ struct pbrt_scene {
 #define NEED(ctx, cond)                                                        \
     do {                                                                       \
         if (!(cond)) return (ctx)->fail(PBRT_E_INVALID, "invalid argument: %s", #cond); \
+    } while (0)
+// the material rule (scene_request.h) as an entry point reports it
+#define MATERIAL_RULE(ctx, m, index)                                                                    \
+    do {                                                                                                \
+        Refusal why_;                                                                                   \
+        if (int rc_ = material_rule(m, index, &why_)) return (ctx)->fail(rc_, "%s", why_.text);         \
     } while (0)
 
 // entry points that wait, copy from host memory or free: not while the context's stream records (pbrt_ctx_record_begin)
@@ -238,77 +233,6 @@ using UsWfKern = void (*)(UsWfArgs);
 using UsFirstKern = void (*)(UsArgs, uint32_t, float4 *, float4 *);
 using RayIntersectKern = void (*)(DevScene, uint32_t, const float *, const float *, const float *, float *, uint32_t *, float *, float *);
 using RayTestKern = void (*)(DevScene, uint32_t, const float *, const float *, const float *, uint8_t *);
-
-// Primitives that can occlude a segment between two points of the scene (DevScene::occ_prims).  A planar
-// primitive is dropped when all OTHER geometry and every point emitter lie in one closed half-space of its
-// plane: it then sits on the boundary of the scene's convex hull and a segment whose end points are in the
-// hull cannot cross it.  Exact comparisons (>= 0 in f64 on the f32 data), so nearly-coplanar scenes just
-// keep their primitives.
-
-static std::vector<pbrt_prim> find_occluders(const pbrt_scene_desc *d) {
-    std::vector<pbrt_prim> occ;
-    for (uint32_t i = 0; i < d->n_prims; ++i) {
-        const pbrt_prim &P = d->prims[i];
-        bool keep = true;
-        if (P.type == PBRT_PRIM_TRIANGLE || P.type == PBRT_PRIM_PARALLELOGRAM) {
-            const double n[3] = {P.g[9], P.g[10], P.g[11]}, p0[3] = {P.g[0], P.g[1], P.g[2]};
-            double lo = INFINITY, hi = -INFINITY;
-            auto side = [&](double x, double y, double z) {
-                return n[0] * (x - p0[0]) + n[1] * (y - p0[1]) + n[2] * (z - p0[2]);
-            };
-            auto acc = [&](double s) {
-                lo = std::min(lo, s);
-                hi = std::max(hi, s);
-            };
-            for (uint32_t j = 0; j < d->n_prims; ++j) {
-                if (j == i) continue;
-                const pbrt_prim &Q = d->prims[j];
-                if (Q.type == PBRT_PRIM_SPHERE) {
-                    double s = side(Q.g[0], Q.g[1], Q.g[2]);
-                    acc(s - (double)Q.g[3]);
-                    acc(s + (double)Q.g[3]);
-                } else if (Q.type == PBRT_PRIM_CONE) {  // extent of the base ellipse along n, and the apex
-                    double cc[3], ca[3], cb[3], cx[3];
-                    cone_world_frame(Q, cc, ca, cb, cx);
-                    const double s = side(cc[0], cc[1], cc[2]);
-                    const double an = n[0] * ca[0] + n[1] * ca[1] + n[2] * ca[2], bn = n[0] * cb[0] + n[1] * cb[1] + n[2] * cb[2];
-                    const double r = std::sqrt(an * an + bn * bn) * (1.0 + 1e-12);
-                    acc(s - r);
-                    acc(s + r);
-                    acc(side(cx[0], cx[1], cx[2]));
-                } else if (Q.type == PBRT_PRIM_CYLINDER) {  // extent of both end ellipses along n
-                    double c0[3], c1[3], ca[3], cb[3];
-                    cylinder_world_frame(Q, c0, c1, ca, cb);
-                    const double an = n[0] * ca[0] + n[1] * ca[1] + n[2] * ca[2], bn = n[0] * cb[0] + n[1] * cb[1] + n[2] * cb[2];
-                    const double r = std::sqrt(an * an + bn * bn) * (1.0 + 1e-12);
-                    const double s0 = side(c0[0], c0[1], c0[2]), s1 = side(c1[0], c1[1], c1[2]);
-                    acc(s0 - r);
-                    acc(s0 + r);
-                    acc(s1 - r);
-                    acc(s1 + r);
-                } else {
-                    const double v0[3] = {Q.g[0], Q.g[1], Q.g[2]}, e1[3] = {Q.g[3], Q.g[4], Q.g[5]}, e2[3] = {Q.g[6], Q.g[7], Q.g[8]};
-                    acc(side(v0[0], v0[1], v0[2]));
-                    acc(side(v0[0] + e1[0], v0[1] + e1[1], v0[2] + e1[2]));
-                    acc(side(v0[0] + e2[0], v0[1] + e2[1], v0[2] + e2[2]));
-                    if (Q.type == PBRT_PRIM_PARALLELOGRAM)
-                        acc(side(v0[0] + e1[0] + e2[0], v0[1] + e1[1] + e2[1], v0[2] + e1[2] + e2[2]));
-                }
-            }
-            for (uint32_t e = 0; e < d->n_emitters; ++e)
-                if (d->emitters[e].type == PBRT_EMIT_POINT)
-                    acc(side(d->emitters[e].pos[0], d->emitters[e].pos[1], d->emitters[e].pos[2]));
-            if (lo >= 0.0 || hi <= 0.0) keep = false;
-            // a scene lit by ONE single-primitive area light: every shadow segment ends (1 - ShadowEpsilon)
-            // short of that primitive's plane, so the light itself never occludes
-            if (d->n_emitters == 1 && d->emitters[0].type == PBRT_EMIT_AREA && d->emitters[0].count == 1 &&
-                d->light_prims[d->emitters[0].first] == i)
-                keep = false;
-        }
-        if (keep) occ.push_back(P);
-    }
-    return occ;
-}
 
 extern "C" {
 
@@ -458,172 +382,95 @@ int pbrt_ctx_tile_keep(pbrt_ctx *c, pbrt_tile_keep_info *info, uint32_t *words, 
 
 }  // extern "C"
 
-// ROUGHCONDUCTOR / CONDUCTOR_FRESNEL records (include/pbrt_hip.h): alpha finite and > 0, eta and k finite and >= 0
-static bool material_is_glossy(uint32_t type) { return type == PBRT_MAT_ROUGHCONDUCTOR || type == PBRT_MAT_CONDUCTOR_FRESNEL; }
-static int check_material(pbrt_ctx *c, const pbrt_material &m, uint32_t index) {
-    if (!material_is_glossy(m.type)) return PBRT_OK;
-    if (m.type == PBRT_MAT_ROUGHCONDUCTOR && !(std::isfinite(m.p[0]) && m.p[0] > 0.0f))
-        return c->fail(PBRT_E_INVALID, "material %u: roughconductor alpha must be finite and > 0", index);
-    for (int k = 1; k < 7; ++k)
-        if (!(std::isfinite(m.p[k]) && m.p[k] >= 0.0f))
-            return c->fail(PBRT_E_INVALID, "material %u: conductor %s must be finite and >= 0", index, k < 4 ? "eta" : "k");
+// ---- pbrt_scene_create: check -> host tables -> placement -> upload -> publish ----------------------------------------------------
+// What creation decides on the host -- the rules, the accelerator and its kernel variant, the occluder list, the run tables, the tree
+// and where it goes -- is scene_request.h; every refusal but a failed device call comes before the first allocation.
+namespace {
+struct SceneCall {
+    pbrt_ctx *c;
+    const pbrt_scene_desc *d;
+    pbrt_scene **out;
+    SceneRequest rq;          // scene_check; scene_placed finishes its facts
+    SceneTables tab;          // scene_tables (scene_request.h)
+    pbrt_scene *s = nullptr;  // scene_upload
+};
+}  // namespace
+
+static int scene_check(SceneCall &q) {
+    if (scene_request(&q.rq, q.d, q.out != nullptr, q.c->lds_limit, BVH_STK_DW(SEG_BVH) * 4)) return q.c->fail(q.rq.why.code, "%s", q.rq.why.text);
     return PBRT_OK;
 }
-// the kernel variant of a brute-force scene: only ACCEL_K_BRUTE_BIG carries the rough / Fresnel conductor code
-static void scene_set_glossy(pbrt_scene *s) {
-    s->glossy = false;
-    for (uint32_t t : s->mat_types) s->glossy = s->glossy || material_is_glossy(t);
-    if (s->accel_kernel == ACCEL_K_BRUTE || s->accel_kernel == ACCEL_K_BRUTE_BIG)
-        s->accel_kernel = s->small_tables && !s->glossy ? ACCEL_K_BRUTE : ACCEL_K_BRUTE_BIG;
+
+static int scene_placed(SceneCall &q) {
+    static_assert(sizeof(HostLeafPrim) == sizeof(DevLeafPrim) && sizeof(DevLeafPrim) == 40, "leaf record layout");
+    static_assert(sizeof(HostNode4) == sizeof(DevNode4) && sizeof(DevNode4) == 64, "node layout");
+    if (scene_place(&q.rq, q.tab)) return q.c->fail(q.rq.why.code, "%s", q.rq.why.text);
+    return PBRT_OK;
+}
+
+// one allocation and one copy per table, in the order they always had; a failure leaves what was allocated in q.s->allocs
+static int scene_upload(SceneCall &q) {
+    const pbrt_scene_desc *d = q.d;
+    const SceneTables &t = q.tab;
+    HIPCHK(q.c, hipSetDevice(q.c->device));
+    pbrt_scene *s = q.s = new pbrt_scene();
+    s->ctx = q.c;
+    DevScene &ds = s->ds;
+    int rc = upload(s, d->prims, d->n_prims, &ds.prims_by_id);
+    if (!rc) rc = upload(s, d->materials, d->n_materials, &ds.mats);
+    if (!rc) rc = upload(s, d->emitters, d->n_emitters, &ds.emitters);
+    if (!rc) rc = upload(s, d->light_prims, d->n_light_prims, &ds.light_prims);
+    if (!rc) rc = upload(s, d->light_cdf, d->n_light_prims, &ds.light_cdf);
+    if (!rc && q.rq.want_bvh) rc = upload(s, reinterpret_cast<const DevLeafPrim *>(t.leaves.data()), t.leaves.size(), &ds.lprims);
+    if (!rc && d->vertex_normals) rc = upload(s, d->vertex_normals, (size_t)d->n_prims * 9, &ds.vnormals);
+    if (!rc && q.rq.want_bvh) rc = upload(s, reinterpret_cast<const DevNode4 *>(t.b4.nodes.data()), t.b4.nodes.size(), &ds.nodes);
+    if (!rc && !q.rq.want_bvh) rc = upload(s, t.occ.data(), t.occ.size(), &ds.occ_prims);
+    if (!rc && !q.rq.want_bvh) rc = upload(s, t.runs.data(), t.runs.size(), &ds.prim_runs);
+    if (!rc && !q.rq.want_bvh) rc = upload(s, t.occ_runs.data(), t.occ_runs.size(), &ds.occ_runs);
+    ds.prims = ds.prims_by_id;  // Hit::slot is the caller's index
+    ds.n_prims = d->n_prims;
+    ds.n_mats = d->n_materials;
+    ds.n_emitters = d->n_emitters;
+    ds.n_light_prims = d->n_light_prims;
+    ds.n_nodes = (uint32_t)t.b4.nodes.size();
+    ds.n_occ = (uint32_t)t.occ.size();
+    ds.n_prim_runs = (uint32_t)t.runs.size();
+    ds.n_occ_runs = (uint32_t)t.occ_runs.size();
+    ds.prim_ord = t.prim_ord;
+    ds.occ_ord = t.occ_ord;
+    return rc;
+}
+
+// A scene that was never handed out: nothing queued and no recording can refer to its memory, so there is no acquisition to settle,
+// no stream to wait for and no recording to mark stale (pbrt_scene_destroy does all three for a scene a caller has seen).
+static int scene_discard(pbrt_scene *s, int rc) {
+    for (void *p : s->allocs) (void)hipFree(p);
+    delete s;
+    return rc;
+}
+
+static void scene_publish(SceneCall &q) {
+    static std::atomic<uint64_t> scene_serial{0};
+    pbrt_scene *s = q.s;
+    static_cast<SceneFacts &>(*s) = q.rq.facts;
+    s->serial = ++scene_serial;
+    s->d_mats = const_cast<pbrt_material *>(s->ds.mats);
+    s->n_mats = q.d->n_materials;
+    *q.out = s;
 }
 
 extern "C" {
 
 int pbrt_scene_create(pbrt_ctx *c, const pbrt_scene_desc *d, pbrt_scene **out) {
     if (!c) return PBRT_E_INVALID;
-    NEED(c, d && out);
-    NOT_RECORDING(c);
-    NEED(c, d->n_prims > 0 && d->prims && d->n_materials > 0 && d->materials);
-    NEED(c, d->n_emitters == 0 || d->emitters);
-    NEED(c, d->n_light_prims == 0 || (d->light_prims && d->light_cdf));
-    for (uint32_t i = 0; i < d->n_prims; ++i) {
-        const pbrt_prim &p = d->prims[i];
-        if (p.type > PBRT_PRIM_CYLINDER) return c->fail(PBRT_E_UNSUPPORTED, "primitive %u: type %u is not supported", i, p.type);
-        if (p.type == PBRT_PRIM_CONE) {
-            double cc[3], ca[3], cb[3], cx[3];
-            if (!cone_world_frame(p, cc, ca, cb, cx))
-                return c->fail(PBRT_E_INVALID, "primitive %u: cone needs an invertible, finite world -> object matrix", i);
-        }
-        if (p.type == PBRT_PRIM_CYLINDER) {
-            double c0[3], c1[3], ca[3], cb[3];
-            if (!cylinder_world_frame(p, c0, c1, ca, cb))
-                return c->fail(PBRT_E_INVALID, "primitive %u: cylinder needs an invertible, finite world -> object matrix", i);
-        }
-        if (p.material >= d->n_materials) return c->fail(PBRT_E_INVALID, "primitive %u: material out of range", i);
-        if (p.emitter >= 0 && (uint32_t)p.emitter >= d->n_emitters)
-            return c->fail(PBRT_E_INVALID, "primitive %u: emitter out of range", i);
-    }
-    for (uint32_t i = 0; i < d->n_materials; ++i)
-        if (int rc = check_material(c, d->materials[i], i)) return rc;
-    for (uint32_t i = 0; i < d->n_emitters; ++i) {
-        const pbrt_emitter &e = d->emitters[i];
-        if (e.type == PBRT_EMIT_AREA) {
-            if (e.count == 0 || e.first + e.count > d->n_light_prims)
-                return c->fail(PBRT_E_INVALID, "emitter %u: light primitive range out of bounds", i);
-            for (uint32_t k = 0; k < e.count; ++k) {
-                uint32_t pi = d->light_prims[e.first + k];
-                if (pi >= d->n_prims || d->prims[pi].type == PBRT_PRIM_SPHERE || d->prims[pi].type == PBRT_PRIM_CONE ||
-                    d->prims[pi].type == PBRT_PRIM_CYLINDER)
-                    return c->fail(PBRT_E_UNSUPPORTED, "emitter %u: area lights need triangle/parallelogram primitives", i);
-            }
-        } else if (e.type != PBRT_EMIT_POINT) {
-            return c->fail(PBRT_E_INVALID, "emitter %u: unknown type", i);
-        }
-    }
-    if (d->vertex_normals)
-        for (size_t i = 0; i < (size_t)d->n_prims * 9; ++i)
-            if (!std::isfinite(d->vertex_normals[i])) return c->fail(PBRT_E_INVALID, "vertex_normals: entry %zu is not finite", i);
-    HIPCHK(c, hipSetDevice(c->device));
-    pbrt_scene *s = new pbrt_scene();
-    static std::atomic<uint64_t> scene_serial{0};
-    s->serial = ++scene_serial;
-    s->ctx = c;
+    if (d && out) NOT_RECORDING(c);  // (behind the null rule, which scene_check reports)
+    SceneCall q{c, d, out};
     int rc;
-    const pbrt_prim *d_prims_by_id = nullptr;
-#define UP(call)               \
-    if ((rc = (call)) != 0) {  \
-        pbrt_scene_destroy(s); \
-        return rc;             \
-    }
-    UP(upload(s, d->prims, d->n_prims, &d_prims_by_id));
-    s->ds.prims_by_id = d_prims_by_id;
-    s->ds.n_prims = d->n_prims;
-    const pbrt_material *dm = nullptr;
-    UP(upload(s, d->materials, d->n_materials, &dm));
-    s->ds.mats = dm;
-    s->d_mats = const_cast<pbrt_material *>(dm);
-    s->n_mats = s->ds.n_mats = d->n_materials;
-    for (uint32_t i = 0; i < d->n_materials; ++i) s->mat_types.push_back(d->materials[i].type);
-    UP(upload(s, d->emitters, d->n_emitters, &s->ds.emitters));
-    s->ds.n_emitters = d->n_emitters;
-    UP(upload(s, d->light_prims, d->n_light_prims, &s->ds.light_prims));
-    UP(upload(s, d->light_cdf, d->n_light_prims, &s->ds.light_cdf));
-    s->ds.n_light_prims = d->n_light_prims;
-    NEED(c, d->accel <= PBRT_ACCEL_BVH_GLOBAL);
-    const bool want_bvh = d->accel == PBRT_ACCEL_BVH || d->accel == PBRT_ACCEL_BVH_GLOBAL ||
-                          (d->accel == PBRT_ACCEL_AUTO && d->n_prims > 32);
-    if (!want_bvh) {
-        s->ds.prims = d_prims_by_id;
-        s->ds.lprims = nullptr;
-        s->ds.nodes = nullptr;
-        s->ds.n_nodes = 0;
-        bool small = d->n_prims <= TAB_MAX && d->n_materials <= TAB_MAX && d->n_emitters <= TAB_MAX;
-        for (uint32_t i = 0; i < d->n_prims; ++i)
-            if (d->prims[i].type == PBRT_PRIM_CONE || d->prims[i].type == PBRT_PRIM_CYLINDER)
-                small = false;  // only the _BIG variant carries the cone / cylinder code
-        if (d->vertex_normals) small = false;                      // ... and the shading-normal code
-        if (d->vertex_normals) UP(upload(s, d->vertex_normals, (size_t)d->n_prims * 9, &s->ds.vnormals));
-        s->small_tables = small;
-        s->accel_kernel = small ? ACCEL_K_BRUTE : ACCEL_K_BRUTE_BIG;
-        std::vector<pbrt_prim> occ = find_occluders(d);
-        UP(upload(s, occ.data(), occ.size(), &s->ds.occ_prims));
-        s->ds.n_occ = (uint32_t)occ.size();
-        // both lists cut into runs of one primitive class, in list order (prim_runs.h; brute_intersect walks them run by run)
-        const std::vector<uint32_t> runs = cut_prim_runs(d->prims, d->n_prims), occ_runs = cut_prim_runs(occ.data(), occ.size());
-        UP(upload(s, runs.data(), runs.size(), &s->ds.prim_runs));
-        s->ds.n_prim_runs = (uint32_t)runs.size();
-        UP(upload(s, occ_runs.data(), occ_runs.size(), &s->ds.occ_runs));
-        s->ds.n_occ_runs = (uint32_t)occ_runs.size();
-        // an ordered scene: BOTH lists class-ordered (the occluders are a sub-sequence of the primitives, checked all the same)
-        uint32_t cnt[3], occ_cnt[3];
-        if (prim_runs_ordered(runs, cnt) && prim_runs_ordered(occ_runs, occ_cnt) && prim_ord_pack(cnt) && prim_ord_pack(occ_cnt)) {
-            s->ds.prim_ord = prim_ord_pack(cnt);
-            s->ds.occ_ord = prim_ord_pack(occ_cnt);
-        }
-    } else {
-        HostBvh bvh;
-        // (a tree whose leaf records alone exceed the LDS stays in global memory whatever its shape: the SAH constant of those trees)
-        const bool sure_global = !c->lds_limit || (size_t)d->n_prims * sizeof(DevLeafPrim) > c->lds_limit || d->accel == PBRT_ACCEL_BVH_GLOBAL;
-        build_bvh(d->prims, d->n_prims, &bvh, sure_global ? BVH_CTRAV_GLOBAL : BVH_CTRAV);
-        HostBvh4 b4;
-        to_bvh4(bvh, &b4);
-        // traversal stack: one entry per level of inner nodes, 24-bit node indices (device_scene.h BvhStack)
-        if (b4.depth > BVH_STK_MAX || b4.nodes.size() >= (1u << 24) - 1u || d->n_prims >= (1u << 27)) {
-            pbrt_scene_destroy(s);
-            return c->fail(PBRT_E_UNSUPPORTED, "BVH depth %u / %zu nodes exceed the traversal state", b4.depth, b4.nodes.size());
-        }
-        std::vector<HostLeafPrim> lp;
-        make_leaf_prims(d->prims, bvh.order, &lp);
-        static_assert(sizeof(HostLeafPrim) == sizeof(DevLeafPrim) && sizeof(DevLeafPrim) == 40, "leaf record layout");
-        static_assert(sizeof(HostNode4) == sizeof(DevNode4) && sizeof(DevNode4) == 64, "node layout");
-        s->ds.prims = d_prims_by_id;  // Hit::slot is the caller's index
-        const DevLeafPrim *dl = nullptr;
-        UP(upload(s, reinterpret_cast<const DevLeafPrim *>(lp.data()), lp.size(), &dl));
-        s->ds.lprims = dl;
-        if (d->vertex_normals) UP(upload(s, d->vertex_normals, (size_t)d->n_prims * 9, &s->ds.vnormals));
-        const DevNode4 *dn = nullptr;
-        UP(upload(s, reinterpret_cast<const DevNode4 *>(b4.nodes.data()), b4.nodes.size(), &dn));
-        s->ds.nodes = dn;
-        s->ds.n_nodes = (uint32_t)b4.nodes.size();
-        s->bvh_depth = b4.depth;
-        s->curved = false;
-        for (uint32_t i = 0; i < d->n_prims; ++i) {
-            if (d->prims[i].type != PBRT_PRIM_TRIANGLE && d->prims[i].type != PBRT_PRIM_PARALLELOGRAM) s->curved = true;
-            if (d->prims[i].type == PBRT_PRIM_CYLINDER) s->cylinders = true;
-        }
-        // the LDS image: 56 bytes per node (planes, device_scene.h TreeLds) + the leaf records
-        const size_t lds = b4.nodes.size() * LDS_IMAGE_NODE_BYTES + (size_t)d->n_prims * sizeof(DevLeafPrim);
-        // beside the image: the traversal stacks of a 1024-thread workgroup and the kernels' small static arrays (1 KiB of slack)
-        if (c->lds_limit && lds + BVH_STK_DW(SEG_BVH) * 4 + 1024 <= c->lds_limit && d->accel != PBRT_ACCEL_BVH_GLOBAL) {
-            s->accel_kernel = ACCEL_K_BVH_LDS;
-            s->lds_bytes = (uint32_t)((lds + 15) & ~size_t(15));
-        } else {
-            s->accel_kernel = ACCEL_K_BVH_GLOBAL;
-        }
-    }
-#undef UP
-    scene_set_glossy(s);
-    *out = s;
+    if ((rc = scene_check(q)) != 0) return rc;
+    scene_tables(q.rq, &q.tab);
+    if ((rc = scene_placed(q)) != 0) return rc;
+    if ((rc = scene_upload(q)) != 0) return q.s ? scene_discard(q.s, rc) : rc;
+    scene_publish(q);
     return PBRT_OK;
 }
 
@@ -632,13 +479,13 @@ int pbrt_scene_update_material(pbrt_scene *s, uint32_t index, const pbrt_materia
     pbrt_ctx *c = s->ctx;
     NEED(c, m && index < s->n_mats);
     NOT_RECORDING(c);  // (a recorded copy would replay the bytes of THIS call's host block)
-    if (int rc = check_material(c, *m, index)) return rc;
+    MATERIAL_RULE(c, *m, index);
     HIPCHK(c, hipSetDevice(c->device));
     // in the order of the context's stream: behind an acquisition that is still queued, ahead of the next one (the 32 bytes are
     // staged before the call returns)
     HIPCHK(c, hipMemcpyAsync(s->d_mats + index, m, sizeof *m, hipMemcpyHostToDevice, c->stream));
     s->mat_types[index] = m->type;
-    scene_set_glossy(s);  // the launches queued from now on
+    scene_set_glossy(s);  // glossy and the brute-force variant again, as creation derived them: the launches queued from now on
     return PBRT_OK;
 }
 
@@ -2368,7 +2215,7 @@ int pbrt_bsdf_sample(pbrt_ctx *ctx, const pbrt_material *m, uint32_t quirks, uin
                      float *pdf, float *weight, uint32_t *sampled) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && s1 && s2 && wo && pdf && weight && sampled);
-    if (int rc = check_material(ctx, *m, 0)) return rc;
+    MATERIAL_RULE(ctx, *m, 0);
     STAGED_BEGIN(ctx, n == 0);
     const size_t n3 = 3 * (size_t)n;  // (n_geo, n_sh, sh_s may be null: the slot stays, the kernel gets a null pointer)
     auto [dwi, dng, dns, dss, d1, d2, rwo, rpdf, rw, rs] =
@@ -2381,7 +2228,7 @@ int pbrt_bsdf_eval_pdf(pbrt_ctx *ctx, const pbrt_material *m, uint32_t n, const 
                        float *pdf) {
     if (!ctx) return PBRT_E_INVALID;
     NEED(ctx, m && wi && wo && f && pdf);
-    if (int rc = check_material(ctx, *m, 0)) return rc;
+    MATERIAL_RULE(ctx, *m, 0);
     STAGED_BEGIN(ctx, n == 0);
     const size_t n3 = 3 * (size_t)n;
     auto [dwi, dwo, rf, rp] = S.arrays(stage_in(wi, n3), stage_in(wo, n3), stage_out(f, n3), stage_out(pdf, n));
