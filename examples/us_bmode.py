@@ -2,14 +2,17 @@
 """The reference's ultrasound driver flow on this library: scene dict -> acquisition -> delay-and-sum -> envelope ->
 log compression -> finite-difference roughness loop (what USMain.py does at :26-90, :93-224, :257-289), without the
 plotting.  Writes the B-mode image and the channel buffer as .npy.
-    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas}] [--p P] [--iq [--decimation D]] [--polar]
-                                  [--apodization {boxcar,tukey,hann,hamming} [--alpha A]] [out_dir]
+    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas,capon}] [--p P] [--l-prop X] [--delta-l D]
+                                  [--iq [--decimation D]] [--polar] [--apodization {boxcar,tukey,hann,hamming} [--alpha A]] [out_dir]
 --convex: the same flow under a curved (abdominal) array -- 64 elements on a 40 mm arc of 40 degrees (DESIGN D18); the sensor
 transform puts the apex where the linear array sits, and the scan is given in the sensor's frame, whose origin is the centre of
 curvature.
 --beamformer: delay-and-sum (default), p-DAS (--p, default 2) or F-DMAS (DESIGN D19).  The non-linear beamformers band-pass their
 image along z, around the carrier (p-DAS) or twice the carrier (F-DMAS): the reference's lambda / 4 grid puts the axial Nyquist
 frequency AT the carrier, so the example picks lambda / 8 for p-DAS and lambda / 16 for F-DMAS itself and says so.
+--beamformer capon: the minimum-variance beamformer (DESIGN D23) with subarrays of --l-prop (default 0.5) of the elements a pixel uses
+and a diagonal loading of --delta-l (default 0.01).  It works on I/Q data, so it implies --iq, and it makes its own weights: no
+--apodization.
 --iq: the I/Q chain (DESIGN D20) -- the channel data are demodulated at the carrier and decimated by --decimation (default 4: 50 MHz ->
 12.5 MHz), delay-and-sum runs on complex samples and the envelope is the modulus of each pixel, which needs no carrier on the grid: the
 example then scans at lambda / 2 axially.  Delay-and-sum only.
@@ -32,8 +35,10 @@ import pbrt_amd.drjit_compat as dr          # was: import drjit as dr
 mi.set_variant("llvm_ad_mono")              # accepted; the one backend is HIP on gfx950
 ap = argparse.ArgumentParser()
 ap.add_argument("--convex", action="store_true")
-ap.add_argument("--beamformer", choices=("das", "pdas", "fdmas"), default="das")
+ap.add_argument("--beamformer", choices=("das", "pdas", "fdmas", "capon"), default="das")
 ap.add_argument("--p", type=float, default=2.0)
+ap.add_argument("--l-prop", type=float, default=0.5)
+ap.add_argument("--delta-l", type=float, default=0.01)
 ap.add_argument("--iq", action="store_true")
 ap.add_argument("--decimation", type=int, default=4)
 ap.add_argument("--polar", action="store_true")
@@ -42,8 +47,12 @@ ap.add_argument("--alpha", type=float, default=0.5)
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("out_dir", nargs="?", default=".")
 args = ap.parse_args()
-if args.iq and args.beamformer != "das":
-    ap.error("--iq takes delay-and-sum: the non-linear beamformers are defined on RF data (DESIGN D19)")
+if args.beamformer == "capon":
+    if args.apodization != "boxcar":
+        ap.error("--beamformer capon makes its own weights: no --apodization (DESIGN D23)")
+    args.iq = True
+if args.iq and args.beamformer not in ("das", "capon"):
+    ap.error("--iq takes delay-and-sum or Capon: the non-linear beamformers are defined on RF data (DESIGN D19)")
 convex, out_dir = args.convex, args.out_dir
 T = mi.ScalarTransform4f
 RADIUS = 0.04 if convex else 0.0            # centre of curvature RADIUS behind the apex; the scan's z is measured from it
@@ -70,8 +79,9 @@ integ = scene.integrator()
 lam = integ.sound_speed / integ.frequency
 window = dict(rx_apodization=args.apodization, rx_apodization_alpha=args.alpha)
 beamformer = {"das": lambda: mi.DelayAndSum(**window), "pdas": lambda: mi.PDelayAndSum(p=args.p, **window),
-              "fdmas": lambda: mi.FilteredDelayMultiplyAndSum(**window)}[args.beamformer]()
-step = {"das": lam / 4, "pdas": lam / 8, "fdmas": lam / 16}[args.beamformer]
+              "fdmas": lambda: mi.FilteredDelayMultiplyAndSum(**window),
+              "capon": lambda: mi.Capon(l_prop=args.l_prop, delta_l=args.delta_l)}[args.beamformer]()
+step = {"das": lam / 4, "pdas": lam / 8, "fdmas": lam / 16, "capon": lam / 2}[args.beamformer]
 RENDER = dict(x_range=(-0.02, 0.02), z_range=Z_RANGE, step=step, beamformer=beamformer)
 if args.iq:
     RENDER.update(iq=True, decimation=args.decimation, step=lam / 2)
@@ -79,7 +89,7 @@ if args.iq:
           f"scan step lambda / 2 = {lam / 2 * 1e6:.0f} um (the Hilbert envelope of the RF chain needs lambda / 4 or finer)")
 if args.polar:
     RENDER.update(scan="polar")
-if args.beamformer != "das":
+if args.beamformer in ("pdas", "fdmas"):
     f_lo, f_hi = beamformer.band(mi.build_probe("linear", 64, 1.2e-4, integ.frequency, 70))
     print(f"{beamformer}: band {f_lo / 1e6:.2f} - {f_hi / 1e6:.2f} MHz needs an axial rate c / (2 step) above {2 * f_hi / 1e6:.2f} MHz; "
           f"scan step lambda / {lam / step:.0f} = {step * 1e6:.1f} um gives {integ.sound_speed / (2 * step) / 1e6:.2f} MHz "

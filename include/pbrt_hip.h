@@ -772,6 +772,60 @@ int pbrt_apod_beamform_dev(pbrt_ctx *ctx, const pbrt_apod_params *p, const void 
 int pbrt_apod_beamform_table_dev(pbrt_ctx *ctx, const pbrt_apod_params *p, const void *d_data, const void *d_table, const void *d_elem,
                                  const void *d_px, const void *d_pz, void *d_out);
 
+/* ---- Capon: the minimum-variance beamformer on I/Q data --------------------------------------------------------------
+ * replaces: ultraspy's Capon beamformer (absent here as above, so this is the build's own definition, after Synnevag, Austeng and Holm,
+ * "Adaptive beamforming applied to medical ultrasound imaging", 2007, and "Benefits of minimum-variance beamforming in medical ultrasound
+ * imaging", 2009).  Every call above weighs the elements by a rule fixed in advance; this one solves a small Hermitian system per pixel
+ * and transmission.  data [n_angles][n_elements][time_samples] PAIRS, exactly as pbrt_iq_beamform takes them.  Per pixel and
+ * transmission a, all in f32:
+ *   U(a)   the elements pbrt_iq_beamform adds for that pixel and transmission -- the same first arrival, f64 position, range rules,
+ *          f-number aperture of the line (probe = 0) or of the element table (probe = 1), nearest / linear interpolation -- taken in
+ *          index order, N = |U(a)|
+ *   v_k    (k = 0 .. N - 1) the delayed sample of the k-th element of U(a) turned by its receive rotation, v_k = rot_e * s_{a,e}, rot_e
+ *          and the complex product as in pbrt_iq_beamform
+ *   L = min(max(1, (uint32) floorf(l_prop * (float) N)), 32),  M = N - L + 1,  the subarrays x_l = (v_l .. v_{l+L-1}), l = 0 .. M - 1
+ *   R = sum_l x_l x_l^H (L x L Hermitian, a sum and not a mean),  xbar = sum_l x_l,  tr = sum_i Re R_ii
+ *   N == 0, or the comparison tr == 0 true:  y_a = (0, 0) exactly
+ *   otherwise eps = delta_l * tr / (float) L, R' = R + eps I, u solves R' u = 1 by Cholesky (R' = G G^H, forward then backward
+ *          substitution), y_a = ((float) N / (float) M) * (u^H xbar) / (sum_i Re u_i)
+ *          -- in exact arithmetic N w^H mean_l(x_l) with w = R'^-1 1 / (1^H R'^-1 1).
+ *   out = sum_a rot_a * y_a, rot_a as in pbrt_iq_beamform, added in order of a, divided by n_angles when compound_mean is set.
+ * The scale of the data: y_a is homogeneous in the v_k, their squares are not.  Before the sums the v_k of a pixel and transmission are
+ * multiplied by the power of two 2^(127 - e), e the biased exponent of max_k max(|Re v_k|, |Im v_k|) (a NaN is no maximum) clamped to
+ * [1, 253], and y_a by 2^(e - 127) at the end: both exact, so no bit differs from the formulas above unless a square would have left the
+ * range of f32 -- and data times a power of two give the image times that power, bit for bit.
+ * The order of the sums as built (one wave per pixel and transmission, lanes share the entries):
+ *   R_ij (i >= j) = sum over l ascending of v_{l+i} conj(v_{l+j}): re = fmaf(a.x, b.x, fmaf(a.y, b.y, re)), im = fmaf(a.y, b.x,
+ *          fmaf(-a.x, b.y, im)); xbar_i = sum over l ascending; tr over i ascending; eps = delta_l * tr / L (product, then quotient)
+ *   Cholesky by columns j ascending: t = R_ij (+ eps on the diagonal, added first) minus G_ik conj(G_jk) over k ascending, one fmaf per
+ *          real product; G_jj = sqrtf(Re t), G_ij = t / G_jj (two f32 divisions)
+ *   forward: t_i = 1 minus G_ik y_k over k ascending, y_i = t_i / G_ii; backward: t_i = y_i minus conj(G_ki) u_k over k DEscending,
+ *          u_i = t_i / G_ii
+ *   u^H xbar and sum Re u_i: the L terms (zeros up to 64) added as a butterfly (lane i with lane i ^ 32, ^ 16, .. ^ 1);
+ *          y_a = (((float) N / (float) M) * num) / den per component
+ * Non-finite samples get no special treatment: a pixel that reads one is non-finite in at least one component and no other pixel
+ * changes by a bit.  A pixel that uses no element is exactly (0, 0), and the tiles no element of a line sees are left as before.
+ * Facts that follow: L = 1 (l_prop = 0) gives y_a = sum_k v_k, pbrt_iq_beamform's image in another order of operations; if every v_k of
+ * a pixel equals v then y_a = N v for every l_prop and delta_l.
+ * `tables` says whether the pixel arguments are the axes x[nx], z[nz] or two pixel tables, as in pbrt_apod_params.  There is no receive
+ * window: the method makes its own weights.  Refused with PBRT_E_INVALID: everything pbrt_scan_params refuses, scan.method !=
+ * PBRT_SCAN_IQ, tables > 1, l_prop not finite or outside [0, 0.5], delta_l not finite, <= 0 or > 1e3, das.n_elements > 256.
+ * pbrt_capon_beamform takes host pointers; the _dev forms take device pointers, are queued on the context's stream and recordable; the
+ * table is the one pbrt_das_first_arrival[_probe]_dev / pbrt_scan_first_arrival_dev write, the table form is bit-equal to the direct
+ * form, and so is tables = 1 on the tables of a separable scan to tables = 0. */
+typedef struct pbrt_capon_params {
+    pbrt_scan_params scan; /* das, method (PBRT_SCAN_IQ only), demod_freq, probe: every rule of pbrt_scan_params */
+    uint32_t tables;       /* 0: the axes x[nx], z[nz]; 1: two pixel tables [nx][nz] */
+    float l_prop;          /* subarray length over the aperture's element count: finite, 0 <= l_prop <= 0.5 */
+    float delta_l;         /* diagonal loading over the mean diagonal entry of R: finite, 0 < delta_l <= 1e3 */
+} pbrt_capon_params;
+int pbrt_capon_beamform(pbrt_ctx *ctx, const pbrt_capon_params *p, const float *iq, const float *tx_delays, const float *elem,
+                        const float *px, const float *pz, float *out);
+int pbrt_capon_beamform_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem,
+                            const void *d_px, const void *d_pz, void *d_out);
+int pbrt_capon_beamform_table_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const void *d_iq, const void *d_table, const void *d_elem,
+                                  const void *d_px, const void *d_pz, void *d_out);
+
 /* waits for everything queued on the context's stream */
 int pbrt_ctx_synchronize(pbrt_ctx *ctx);
 /* Device buffers for a caller without a GPU library of its own (the reference's driver is NumPy: USMain.py:103-121).
@@ -816,7 +870,7 @@ int pbrt_ctx_tile_keep(pbrt_ctx *ctx, pbrt_tile_keep_info *info, uint32_t *words
  * pbrt_das_beamform_dev, pbrt_das_beamform_table_dev, pbrt_bf_beamform_dev, pbrt_bf_beamform_table_dev, pbrt_axial_fir_dev,
  * pbrt_rf2iq_dev, pbrt_iq_beamform_dev, pbrt_iq_beamform_table_dev, pbrt_iq_envelope_dev,
  * pbrt_scan_beamform_dev, pbrt_scan_beamform_table_dev, pbrt_scan_first_arrival_dev, pbrt_scan_convert_dev,
- * pbrt_apod_beamform_dev, pbrt_apod_beamform_table_dev,
+ * pbrt_apod_beamform_dev, pbrt_apod_beamform_table_dev, pbrt_capon_beamform_dev, pbrt_capon_beamform_table_dev,
  * pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
  * stream instead of run; pbrt_graph_launch replays the recording in one submission and returns without waiting, exactly as if
  * the recorded calls had just been made: same kernels, same arguments, same results bit for bit, the acquisition's statistics

@@ -167,6 +167,14 @@ APOD_BOXCAR, APOD_TUKEY, APOD_HANN, APOD_HAMMING = 0, 1, 2, 3
 PBRT_APOD_BOXCAR, PBRT_APOD_TUKEY, PBRT_APOD_HANN, PBRT_APOD_HAMMING = APOD_BOXCAR, APOD_TUKEY, APOD_HANN, APOD_HAMMING
 
 
+class CaponParams(C.Structure):
+    """pbrt_capon_params: a whole Capon request on I/Q data (DESIGN D23)"""
+    _fields_ = [("scan", ScanParams), ("tables", C.c_uint32), ("l_prop", C.c_float), ("delta_l", C.c_float)]
+
+
+CAPON_MAX_L, CAPON_MAX_E = 32, 256
+
+
 class ScanConvertParams(C.Structure):
     _fields_ = [("n_theta", C.c_uint32), ("n_rho", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32), ("theta0", C.c_double),
                 ("dtheta", C.c_double), ("rho0", C.c_double), ("drho", C.c_double), ("ox", C.c_double), ("oz", C.c_double),
@@ -265,6 +273,9 @@ SIGNATURES = {
     "pbrt_apod_beamform": (C.c_int, [_P, C.POINTER(ApodParams), _F, _F, _F, _F, _F, _F]),
     "pbrt_apod_beamform_dev": (C.c_int, [_P, C.POINTER(ApodParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_apod_beamform_table_dev": (C.c_int, [_P, C.POINTER(ApodParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_capon_beamform": (C.c_int, [_P, C.POINTER(CaponParams), _F, _F, _F, _F, _F, _F]),
+    "pbrt_capon_beamform_dev": (C.c_int, [_P, C.POINTER(CaponParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_capon_beamform_table_dev": (C.c_int, [_P, C.POINTER(CaponParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_scan_convert": (C.c_int, [_P, C.POINTER(ScanConvertParams), _F, _F, _F, _F]),
     "pbrt_scan_convert_dev": (C.c_int, [_P, C.POINTER(ScanConvertParams), _P, _P, _P, _P]),
     "pbrt_ctx_synchronize": (C.c_int, [_P]),

@@ -18,6 +18,9 @@ samples, and the envelope of an I/Q image is its modulus (iq_envelope) -- DESIGN
 Sector scans: PolarScan beside GridScan, scan_beamform / scan_first_arrival on pixel tables (every method above),
 scan_convert from the sector onto a Cartesian grid, us_render(scan="polar").
 
+Capon: ultraspy's fourth beamformer, minimum-variance weights per pixel and transmission on I/Q data -- capon_beamform
+and the class Capon, on both kinds of scan; us_render(beamformer=Capon()) runs the I/Q chain with it.
+
 All work runs on the GPU through libpbrt_hip.so (no CPU fallback; `on_gpu` is accepted for compatibility)."""
 from __future__ import annotations
 
@@ -111,10 +114,17 @@ def _checked_window(rx_apodization, rx_apodization_alpha, f_number):
     return _WINDOWS[rx_apodization], alpha
 
 
-def _block(das, tables, method, p, demod_freq, probe, window=_capi.APOD_BOXCAR, alpha=1.0):
+def _block(das, tables, method, p, demod_freq, probe, window=_capi.APOD_BOXCAR, alpha=1.0, capon=None):
     """the parameter block of a request and the family of entry points that takes it: pbrt_scan_* for pixel tables (one block for
     every method); on axes pbrt_das_* (the element table is in the NAME: *_probe), pbrt_bf_* or pbrt_iq_* (a probe flag in the block);
-    with a receive window other than boxcar pbrt_apod_* (one block for every method, probe and scan kind, DESIGN D22)"""
+    with a receive window other than boxcar pbrt_apod_* (one block for every method, probe and scan kind, DESIGN D22); capon =
+    (l_prop, delta_l): pbrt_capon_* (I/Q data, every probe and scan kind, DESIGN D23)"""
+    if capon is not None:
+        par = _capi.CaponParams()
+        par.scan.das, par.scan.probe, par.scan.method, par.scan.p = das, int(bool(probe)), _METHODS[method], float(p)
+        par.scan.demod_freq = float(demod_freq or 0.0)
+        par.tables, par.l_prop, par.delta_l = int(bool(tables)), float(capon[0]), float(capon[1])
+        return par, "capon"
     if window != _capi.APOD_BOXCAR:
         par = _capi.ApodParams()
         par.scan.das, par.scan.probe, par.scan.method, par.scan.p = das, int(bool(probe)), _METHODS[method], float(p)
@@ -165,15 +175,18 @@ def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
 
 
 def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method, p=2.0, demod_freq=None, t0, f_number, interpolation,
-              compound, out, table, rx_apodization="boxcar", rx_apodization_alpha=0.5):
+              compound, out, table, rx_apodization="boxcar", rx_apodization_alpha=0.5, capon=None):
     """One beamform request, from every public call to its entry point: `data` by `method` ("das", "pdas" with p, "fdmas", or "iq"
     with demod_freq: data and result complex64) on the pixels gx, gz -- the axes x, z, or (`tables`) two pixel tables.  Shapes the
     arguments, holds RF against I/Q, uploads the small tables where the data is a DeviceBuffer, validates `out` and `table`, selects
     the parameter block and the entry point (_block; [_table] with a first-arrival table, [_dev] for data in HBM), calls it and keeps
     what a queued kernel reads alive with its result.  Host arrays in: a host array out, `out` and `table` are not read.
     rx_apodization: the receive window on the f-number aperture, "boxcar" (today's entry points), "tukey" (with rx_apodization_alpha),
-    "hann" or "hamming" (pbrt_apod_*, DESIGN D22); validated before a context is made."""
+    "hann" or "hamming" (pbrt_apod_*, DESIGN D22); validated before a context is made.
+    capon: (l_prop, delta_l) -- the I/Q data go through pbrt_capon_* (DESIGN D23), which has no receive window."""
     window, alpha = _checked_window(rx_apodization, rx_apodization_alpha, f_number)
+    if capon is not None and (method != "iq" or window != _capi.APOD_BOXCAR):
+        raise ValueError("Capon beamforms I/Q data and makes its own weights: method 'iq' and rx_apodization='boxcar'")
     dev = _is_dev(data)
     iq = method == "iq"
     dtype = np.dtype(np.complex64 if iq else np.float32)
@@ -189,7 +202,7 @@ def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method,
     tx, ex = _arg(cx, tx_delays, (A, E), dev), _arg(cx, elem, eshape, dev)
     gx, gz, (n0, n1) = _pixels(cx, gx, gz, tables, dev)
     par, family = _block(_das_params(A, E, T, n0, n1, fs, sound_speed, t0, f_number, interpolation, compound), tables, method, p,
-                         demod_freq, probe, window, alpha)
+                         demod_freq, probe, window, alpha, capon)
     d0, d1 = ("n0", "n1") if tables else ("nx", "nz")
     res = out if out is not None else _capi.DeviceBuffer(cx, (n0, n1), dtype) if dev else np.empty((n0, n1), dtype)
     if res.nbytes != n0 * n1 * dtype.itemsize:
@@ -249,6 +262,39 @@ def iq_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, t0=0.
     return _beamform(iq, tx_delays, elem, x, z, False, fs_iq, sound_speed, method="iq", demod_freq=_checked_demod_freq(float(demod_freq)),
                      t0=t0, f_number=f_number, interpolation=interpolation, compound=compound, out=out, table=table,
                      rx_apodization=rx_apodization, rx_apodization_alpha=rx_apodization_alpha)
+
+
+def _checked_capon(l_prop, delta_l, E):
+    """(l_prop, delta_l) as the library takes them; ValueError for what it would refuse (include/pbrt_hip.h "Capon")"""
+    try:
+        lp, dl = float(l_prop), float(delta_l)
+    except (TypeError, ValueError):
+        lp = dl = float("nan")
+    if not (math.isfinite(lp) and 0.0 <= lp <= 0.5):
+        raise ValueError(f"l_prop must lie in [0, 0.5], got {l_prop!r}")
+    if not (math.isfinite(dl) and 0.0 < dl <= 1e3):
+        raise ValueError(f"delta_l must lie in (0, 1e3], got {delta_l!r}")
+    if E > _capi.CAPON_MAX_E:
+        raise ValueError(f"Capon takes at most {_capi.CAPON_MAX_E} elements, got {E}")
+    return lp, dl
+
+
+def capon_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, l_prop=0.5, delta_l=0.01, t0=0.0, f_number=1.0,
+                   interpolation="linear", compound="sum", out=None, table=None, tables=False):
+    """Capon (minimum-variance) beamforming of I/Q channel data (DESIGN D23, include/pbrt_hip.h): the delayed and turned samples of
+    iq_beamform -- same delays, aperture and interpolation -- are not added with weights fixed in advance: per pixel and transmission
+    the covariance of the subarrays of L = floor(l_prop N) elements (1 <= L <= 32) of the N elements in use is formed, loaded with
+    delta_l times its mean diagonal and solved for the minimum-variance weights.  l_prop in [0, 0.5] (0: iq_beamform's image in
+    another order of operations), delta_l in (0, 1e3], at most 256 elements.  Arguments and the host / DeviceBuffer rule as
+    iq_beamform: host arrays in -> pbrt_capon_beamform and a host array out; `iq` a complex DeviceBuffer -> pbrt_capon_beamform_dev
+    (or _table_dev with `table` from das_first_arrival / scan_first_arrival), queued, a complex DeviceBuffer out.  elem [n_elements] or
+    the element table [n_elements, 4]; tables: x, z are two pixel tables [n0, n1] (scan_beamform's), not the axes.  There is no
+    receive window: the method makes its own weights."""
+    shape = tuple(iq.shape) if _is_dev(iq) else np.shape(iq)
+    E = shape[1] if len(shape) == 3 else 0   # (any other shape is _beamform's ValueError)
+    return _beamform(iq, tx_delays, elem, x, z, bool(tables), fs_iq, sound_speed, method="iq",
+                     demod_freq=_checked_demod_freq(float(demod_freq)), t0=t0, f_number=f_number, interpolation=interpolation,
+                     compound=compound, out=out, table=table, capon=_checked_capon(l_prop, delta_l, int(E)))
 
 
 _SCAN_METHODS = ("das", "pdas", "fdmas", "iq")
@@ -801,6 +847,40 @@ class _NonlinearBeamformer(DelayAndSum):
 
     def __str__(self):
         return f"{type(self).__name__}(MI355X, {self.setups})"
+
+
+class Capon(DelayAndSum):
+    """ultraspy's Capon in the shape of DelayAndSum (DESIGN D23): the minimum-variance beamformer on I/Q data.  Setups: DelayAndSum's,
+    `l_prop` (the subarray length over the number of elements a pixel uses, [0, 0.5]) and `delta_l` (the diagonal loading over the mean
+    diagonal entry of the covariance, (0, 1e3]).  `ultraspy` is absent: the two names are ultraspy's from memory, the arithmetic is this
+    build's own definition (include/pbrt_hip.h, after Synnevag, Austeng and Holm 2007 / 2009), and parity with it is unpinned.  Always
+    I/Q: set_is_iq(False) raises NotImplementedError; a receive window other than 'boxcar' is a ValueError of beamform() -- the method
+    makes its own weights.  It takes a GridScan or a PolarScan, and compute_envelope is the modulus."""
+
+    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", l_prop=0.5, delta_l=0.01, is_iq=True,
+                 rx_apodization="boxcar", rx_apodization_alpha=0.5):
+        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound, is_iq=is_iq,
+                         rx_apodization=rx_apodization, rx_apodization_alpha=rx_apodization_alpha)
+        self.setups.update(l_prop=l_prop, delta_l=delta_l)
+
+    def set_is_iq(self, flag):
+        if not flag:
+            raise NotImplementedError("Capon: RF (real) data are not built -- the covariance is defined on I/Q samples (DESIGN D23); "
+                                      "demodulate them first (rf2iq)")
+        self.setups["is_iq"] = True
+
+    def _request(self, data, scan, out, table):
+        ai, su, dev = self.acquisition_info, self.setups, _is_dev(data)
+        if su["rx_apodization"] != "boxcar":
+            raise ValueError(f"Capon makes its own weights: rx_apodization must be 'boxcar', got {su['rx_apodization']!r}")
+        ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
+        polar, gx, gz = _scan_tables(scan, dev)
+        return capon_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], self.demod_freq(),
+                              l_prop=su["l_prop"], delta_l=su["delta_l"], t0=ai.get("t0", 0.0) or 0.0, f_number=su["f_number"],
+                              interpolation=su["interpolation"], compound=su["compound"], out=out, table=table, tables=polar)
+
+    def __str__(self):
+        return f"Capon(MI355X, {self.setups})"
 
 
 class PDelayAndSum(_NonlinearBeamformer):

@@ -5,7 +5,8 @@
 #pragma once
 #include "../../include/pbrt_hip.h"
 #include "bf_request.h"
-#include "img_request.h"  // the limits of the image steps: FIR_MAX_K, RF2IQ_MAX_D, ENV_MAX_N, ENV_MAX_BLOCKS, PULSE_MAX_K, env_even_len
+#include "capon_request.h"  // the limits of Capon and the subarray rule: CAPON_MAX_L, CAPON_MAX_E, capon_lm
+#include "img_request.h" // the limits of the image steps: FIR_MAX_K, RF2IQ_MAX_D, ENV_MAX_N, ENV_MAX_BLOCKS, PULSE_MAX_K, env_even_len
 #include "device_math.h"
 
 // ---- delay and sum --------------------------------------------------------------------------------------------------------
@@ -465,6 +466,269 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_apod_beamform(pbrt_das_param
                                                                   typename DasSample<METHOD>::type *__restrict__ out, float pw, float a0,
                                                                   float alpha) {
     das_walk<INTERP, TABLE, CONVEX, METHOD, true>(p, grid, data, tx, elem_x, gx, gz, ttx, out, pw, a0, alpha);
+}
+
+// ---- Capon: the minimum-variance beamformer on I/Q data (DESIGN D23; the definition and the order of the sums: include/pbrt_hip.h) ----
+// Not a METHOD of das_walk: there a lane is a pixel and the elements pass by; here a pixel and transmission needs an L x L Hermitian
+// system solved, L <= 32, so a WAVE owns the pixel and its lanes are elements, then entries of R, then rows of the factor.  Kept from the
+// walk: the tile map (das_tile_of, DasGrid: 8 x 8 tiles, axes or tables), das_split / DasPos, iq_rot, das_lerp, and the early-out for the
+// tiles of a line of elements that no element sees.  A workgroup is four waves on one tile; wave w takes the pixels w, w + 4, ... of the
+// tile, one after the other, and the waves never meet: no s_barrier anywhere, every loop bound is wave-uniform.
+//   gather      lanes are elements in blocks of 64: distance and aperture test per lane; the first arrival from the table, or the
+//               wave-wide minimum over ALL elements (f64 fmin: exact, whatever the order -- the table form is bit-equal); the sample is
+//               gathered, turned by rot_e and written to the wave's row s_v at its rank in U(a) (ballot and prefix count)
+//   covariance  lane i < L sums xbar_i (kept in a register); the L (L + 1) / 2 entries of the lower triangle of R are dealt to the lanes
+//   solve       in place in LDS: column j of the factor is made by the lanes i >= j from the columns before it (row i is the lane's
+//               own, row j lane j's: one capon_wave_sync per column); the two substitutions keep t_i in a register and pass y_k / u_k
+//               on by a shuffle from lane k -- no LDS write, no register array indexed by the column
+// LDS: 2 KB of samples and 4.1 KB of matrix (the lower triangle alone, 528 pairs) per wave, 24.5 KB per workgroup: room for six
+// workgroups per CU, of which 92 - 104 VGPRs allow five (a line of elements) or four (an element table).  profiles/capon.md: the full
+// 32 x 33 matrix, three workgroups per CU, with the LDS loops not unrolled took 11.4 ms where this form takes 10.0 ms; what remains is
+// the LDS traffic of the covariance and the columns.
+#define CAPON_TRI (CAPON_MAX_L * (CAPON_MAX_L + 1u) / 2u)
+// entry (i, j), j <= i, of the lower triangle: 2 (i (i + 1) / 2) mod 64 is a different bank for each of the 32 rows
+DEV uint32_t capon_at(uint32_t i, uint32_t j) { return i * (i + 1u) / 2u + j; }
+// what a lane wrote to LDS is read by other lanes of ITS wave: the LDS runs a wave's instructions in order, so the wave needs no
+// s_barrier, but the compiler must neither keep the value in a register nor move the read up, and the write must have left the wave
+DEV void capon_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+template <uint32_t INTERP, bool TABLE, bool CONVEX>
+__global__ __launch_bounds__(64 * DAS_SPLIT) void k_capon_beamform(pbrt_das_params p, DasGrid grid, const float2 *__restrict__ data,
+                                                                   const float *__restrict__ tx, const float *__restrict__ elem_x,
+                                                                   const float *__restrict__ gx, const float *__restrict__ gz,
+                                                                   const double *__restrict__ ttx, float2 *__restrict__ out, float f_d,
+                                                                   float l_prop, float delta_l) {
+    __shared__ float2 s_v[DAS_SPLIT][CAPON_MAX_E];
+    __shared__ float2 s_g[DAS_SPLIT][CAPON_TRI];
+    uint32_t tile_x, tile_z;
+    if (!das_tile_of(grid, blockIdx.x, &tile_x, &tile_z)) return;
+    const uint32_t A = p.n_angles, E = p.n_elements, T = p.time_samples;
+    if (E > CAPON_MAX_E) return;  // (capon_request refuses it: a rank never leaves the row)
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    float2 *sv = s_v[wave], *G = s_g[wave];
+    const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0, last = (double)(T - 1u);
+    const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;
+    // lane = pixel of the tile, as in the walk: its position, and whether it sees an element of a line at all
+    uint64_t seen;
+    double x_l, z_l;
+    {
+        const uint32_t ix = tile_x * DAS_TILE + (lane >> 3), iz = tile_z * DAS_TILE + (lane & 7u);
+        const bool valid = ix < p.nx && iz < p.nz;
+        const uint32_t cx = min(ix, p.nx - 1u), cz = min(iz, p.nz - 1u), cpix = cx * p.nz + cz;
+        x_l = (double)gx[das_px_index(grid.tab, cx, cpix)];
+        z_l = (double)gz[das_px_index(grid.tab, cz, cpix)];
+        const double half_ap = p.f_number > 0.0f ? z_l / (2.0 * (double)p.f_number) : 1e300;
+        float ex_lo = 3.0e38f, ex_hi = -3.0e38f;
+        for (uint32_t eb = 0; !CONVEX && eb < E; eb += 64u) {
+            const float v = elem_x[eb + min(lane, E - eb - 1u)];
+            ex_lo = fminf(ex_lo, v);
+            ex_hi = fmaxf(ex_hi, v);
+        }
+        if (!CONVEX) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
+                ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
+            }
+        }
+        seen = __ballot(valid && (CONVEX || (x_l + half_ap >= (double)ex_lo && x_l - half_ap <= (double)ex_hi)));
+        if (seen == 0ull) {  // a tile outside the span of a linear array writes exact zeros
+            if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = float2{};
+            return;
+        }
+    }
+    for (uint32_t px = wave; px < DAS_TILE * DAS_TILE; px += DAS_SPLIT) {
+        const uint32_t ix = tile_x * DAS_TILE + (px >> 3), iz = tile_z * DAS_TILE + (px & 7u);
+        if (ix >= p.nx || iz >= p.nz) continue;
+        const size_t pix = (size_t)ix * p.nz + iz;
+        if (!((seen >> px) & 1ull)) {  // no element of the line reaches it
+            if (lane == 0) out[pix] = float2{};
+            continue;
+        }
+        const double x = das_lane_f64(x_l, px), z = das_lane_f64(z_l, px), zz = z * z;
+        const double half_ap = p.f_number > 0.0f ? z / (2.0 * (double)p.f_number) : 1e300;
+        float acc = 0.0f, acc_im = 0.0f;
+        for (uint32_t a = 0; a < A; ++a) {
+            // first arrival of the emitted wavefront at the pixel
+            double tmin = 1e300;
+            if (TABLE) {
+                tmin = ttx[(size_t)a * p.nx * p.nz + pix];
+            } else {
+                for (uint32_t eb = 0; eb < E; eb += 64u) {
+                    const uint32_t e = min(eb + lane, E - 1u);  // (a lane beyond the last element repeats it: the minimum is the same)
+                    const double dx = x - (double)elem_x[CONVEX ? 4u * e : e];
+                    const double dz = CONVEX ? z - (double)elem_x[4u * e + 1u] : 0.0;
+                    tmin = fmin(tmin, (double)tx[(size_t)a * E + e] + sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c);
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) tmin = fmin(tmin, __shfl_xor(tmin, off));
+            }
+            const DasPos tp = INTERP == PBRT_DAS_LINEAR ? das_split((tmin - t0) * fs) : DasPos{0, 0.0f};
+            capon_wave_sync();  // the reads of the transmission before are behind the writes below
+            // gather: v_k = rot_e s_{a,e} at the rank k of e in U(a)
+            uint32_t N = 0;
+            for (uint32_t eb = 0; eb < E; eb += 64u) {
+                const uint32_t e = eb + lane, ec = min(e, E - 1u);
+                const double dx = x - (double)elem_x[CONVEX ? 4u * ec : ec];
+                double dz = 0.0;
+                bool in_ap;
+                if (CONVEX) {
+                    dz = z - (double)elem_x[4u * ec + 1u];
+                    const double enx = (double)elem_x[4u * ec + 2u], enz = (double)elem_x[4u * ec + 3u];
+                    const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
+                    in_ap = p.f_number > 0.0f ? (dn > 0.0 && two_f * fabs(dt) <= dn) : true;
+                } else {
+                    in_ap = fabs(dx) <= half_ap;
+                }
+                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
+                bool use = false;
+                float2 s = float2{};
+                if (e < E && in_ap) {
+                    const float2 *trace = data + ((size_t)a * E + e) * T;
+                    if (INTERP == PBRT_DAS_NEAREST) {
+                        const double r = rint((tmin + d - t0) * fs);
+                        if (r >= 0.0 && r <= last) {
+                            s = trace[(uint32_t)r];
+                            use = true;
+                        }
+                    } else {
+                        const DasPos dp = das_split(d * fs);
+                        const float fr = tp.f + dp.f;  // [0, 2)
+                        const float fl = floorf(fr);
+                        const float w = fr - fl;
+                        const uint32_t i0 = (uint32_t)(tp.i + dp.i + (int32_t)fl);
+                        if (i0 < T - 1u) {
+                            s = das_lerp(w, trace[i0], trace[i0 + 1]);
+                            use = true;
+                        } else if (i0 == T - 1u && w == 0.0f) {  // exactly the last sample
+                            s = trace[T - 1u];
+                            use = true;
+                        }
+                    }
+                }
+                const uint64_t users = __ballot(use);
+                if (use) {
+                    const float2 rot_e = iq_rot((double)f_d * d);
+                    sv[N + (uint32_t)__popcll(users & ((1ull << lane) - 1ull))] =
+                        make_float2(fma_(rot_e.x, s.x, -(rot_e.y * s.y)), fma_(rot_e.x, s.y, rot_e.y * s.x));
+                }
+                N += (uint32_t)__popcll(users);
+            }
+            if (N == 0u) continue;  // y_a = (0, 0)
+            const CaponLM lm = capon_lm(N, l_prop);
+            const uint32_t L = lm.L, M = lm.M;
+            capon_wave_sync();
+            // y_a is homogeneous in the samples, their squares are not: channel data of 1e-20 (the tail of a low-pass behind a sparse
+            // acquisition) would lose R in the subnormals.  So the v_k are brought to order 1 by a power of two -- exact, and undone on
+            // y_a: no bit changes unless a square would have left the range of f32.  Every lane rescales the entries it read.
+            float big = 0.0f;
+            for (uint32_t k = lane; k < N; k += 64u) big = fmaxf(big, fmaxf(__builtin_fabsf(sv[k].x), __builtin_fabsf(sv[k].y)));
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) big = fmaxf(big, __shfl_xor(big, off));
+            const uint32_t ex = min(max((__float_as_uint(big) >> 23) & 0xffu, 1u), 253u);  // (a NaN is no maximum; an infinity stays one)
+            const float down = __uint_as_float((254u - ex) << 23), up = __uint_as_float(ex << 23);
+            for (uint32_t k = lane; k < N; k += 64u) sv[k] = make_float2(sv[k].x * down, sv[k].y * down);
+            capon_wave_sync();
+            // covariance: xbar_i in lane i, the lower triangle of R = sum_l x_l x_l^H in G
+            float2 xb = float2{};
+            if (lane < L) {
+#pragma unroll 4
+                for (uint32_t l = 0; l < M; ++l) {
+                    const float2 v = sv[l + lane];
+                    xb.x += v.x;
+                    xb.y += v.y;
+                }
+            }
+            for (uint32_t idx = lane; idx < L * (L + 1u) / 2u; idx += 64u) {
+                uint32_t i = (uint32_t)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);  // the row of entry idx, then made exact
+                while (i * (i + 1u) / 2u > idx) --i;
+                while ((i + 1u) * (i + 2u) / 2u <= idx) ++i;
+                const uint32_t j = idx - i * (i + 1u) / 2u;
+                float re = 0.0f, im = 0.0f;
+#pragma unroll 4
+                for (uint32_t l = 0; l < M; ++l) {
+                    const float2 u = sv[l + i], v = sv[l + j];
+                    re = fma_(u.x, v.x, fma_(u.y, v.y, re));
+                    im = fma_(u.y, v.x, fma_(-u.x, v.y, im));
+                }
+                G[idx] = make_float2(re, im);  // idx == capon_at(i, j)
+            }
+            capon_wave_sync();
+            float tr = 0.0f;
+            for (uint32_t i = 0; i < L; ++i) tr += G[capon_at(i, i)].x;
+            if (tr == 0.0f) continue;  // y_a = (0, 0); a NaN trace goes on and comes out as NaN
+            const float eps = delta_l * tr / (float)L;
+            // R + eps I = G G^H, column by column; the diagonal stays in lane j's register
+            float dg = 1.0f;
+            for (uint32_t j = 0; j < L; ++j) {
+                const bool mine = lane >= j && lane < L;
+                float2 t = float2{};
+                if (mine) {
+                    const uint32_t row = capon_at(lane, 0), row_j = capon_at(j, 0);
+                    t = G[row + j];
+                    if (lane == j) t.x += eps;
+#pragma unroll 4
+                    for (uint32_t k = 0; k < j; ++k) {
+                        const float2 g = G[row + k], h = G[row_j + k];
+                        t.x = fma_(-g.x, h.x, t.x);
+                        t.x = fma_(-g.y, h.y, t.x);
+                        t.y = fma_(-g.y, h.x, t.y);
+                        t.y = fma_(g.x, h.y, t.y);
+                    }
+                }
+                const float d = sqrtf(__shfl(t.x, (int)j));
+                if (mine) {
+                    if (lane == j)
+                        dg = d;
+                    else
+                        G[capon_at(lane, j)] = make_float2(t.x / d, t.y / d);
+                }
+                capon_wave_sync();
+            }
+            // G y = 1, then G^H u = y: t_i in lane i, y_k and u_k handed on from lane k
+            float2 t = make_float2(lane < L ? 1.0f : 0.0f, 0.0f), yv = float2{}, u = float2{};
+            for (uint32_t k = 0; k < L; ++k) {
+                const float2 yk = make_float2(__shfl(t.x / dg, (int)k), __shfl(t.y / dg, (int)k));
+                if (lane == k) yv = yk;
+                if (lane > k && lane < L) {
+                    const float2 g = G[capon_at(lane, k)];
+                    t.x = fma_(-g.x, yk.x, t.x);
+                    t.x = fma_(g.y, yk.y, t.x);
+                    t.y = fma_(-g.x, yk.y, t.y);
+                    t.y = fma_(-g.y, yk.x, t.y);
+                }
+            }
+            t = yv;
+            for (uint32_t k = L; k-- > 0u;) {
+                const float2 uk = make_float2(__shfl(t.x / dg, (int)k), __shfl(t.y / dg, (int)k));
+                if (lane == k) u = uk;
+                if (lane < k) {
+                    const float2 g = G[capon_at(k, lane)];  // conj(G_ki) u_k
+                    t.x = fma_(-g.x, uk.x, t.x);
+                    t.x = fma_(-g.y, uk.y, t.x);
+                    t.y = fma_(-g.x, uk.y, t.y);
+                    t.y = fma_(g.y, uk.x, t.y);
+                }
+            }
+            // y_a = (N / M) (u^H xbar) / sum_i Re u_i: the lanes' terms (0 from L on) meet in a butterfly
+            float nr = fma_(u.x, xb.x, u.y * xb.y), ni = fma_(u.x, xb.y, -(u.y * xb.x)), den = u.x;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                nr += __shfl_xor(nr, off);
+                ni += __shfl_xor(ni, off);
+                den += __shfl_xor(den, off);
+            }
+            const float scale = (float)N / (float)M;
+            const float yr = scale * nr / den * up, yi = scale * ni / den * up;
+            const float2 rot_a = iq_rot((double)f_d * tmin);
+            acc += fma_(rot_a.x, yr, -(rot_a.y * yi));
+            acc_im += fma_(rot_a.x, yi, rot_a.y * yr);
+        }
+        if (lane == 0) out[pix] = p.compound_mean ? make_float2(acc / (float)A, acc_im / (float)A) : make_float2(acc, acc_im);
+    }
 }
 
 // What k_axial_fir and k_apply_pulse share: one workgroup makes the 256 outputs n0 .. n0 + 255 of one row of N samples,

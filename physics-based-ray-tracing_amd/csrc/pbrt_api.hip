@@ -2322,7 +2322,7 @@ static int launched(pbrt_ctx *c) {  // the end of every function that queues ker
 // de: element positions [n_elements], or (rq.probe) the element table [n_elements][4]; dx, dz: the axes, or (rq.tab) the pixel tables;
 // dt, ttx: the transmit delays, and the first-arrival table of this scan or null
 static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const float *dt, const float *de, const float *dx, const float *dz,
-                       float *dout, const double *ttx) {
+                       float *dout, const double *ttx, const CaponRequest *capon = nullptr) {
     const pbrt_das_params *p = rq.das;
     ImgTimer tm(c, IMG_DAS);
     DasGrid g;
@@ -2335,7 +2335,12 @@ static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const 
     for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
     const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
     const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    if (rq.window != PBRT_APOD_BOXCAR && rq.method == PBRT_SCAN_IQ) {  // a receive window (D22): the walk with the weight arm, a0 and alpha
+    if (capon) {  // Capon (D23): the tiles of the walk, a wave per pixel; I/Q data and pixels, l_prop and delta_l launch arguments
+        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_capon_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
+                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
+        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
+                           reinterpret_cast<float2 *>(dout), rq.pw, capon->l_prop, capon->delta_l);
+    } else if (rq.window != PBRT_APOD_BOXCAR && rq.method == PBRT_SCAN_IQ) {  // a receive window (D22): the walk with the weight arm, a0 and alpha
         const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_apod_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), BF_IQ>; },
                                        p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
         hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
@@ -2419,15 +2424,15 @@ static int iq_env_enqueue(pbrt_ctx *c, const IqEnvRequest &rq, const float *din,
     return launched(c);
 }
 
-// The three bodies behind the 20 beamform and first-arrival entry points.  Each entry point makes its request first (BF_REQUEST below):
+// The three bodies behind the 23 beamform and first-arrival entry points (capon: the request of pbrt_capon_*, else null).  Each entry point makes its request first (BF_REQUEST below):
 // a null context is PBRT_E_INVALID and touches nothing, a refused block is PBRT_E_INVALID with the text of the rule.
 // (d_tx_delays or d_table: the plain form passes its delays, the table form its first-arrival table, and the other one null)
 static int beamform_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_data, const void *d_elem, const void *d_x, const void *d_z,
-                        void *d_out, const void *d_tx_delays, const void *d_table) {
+                        void *d_out, const void *d_tx_delays, const void *d_table, const CaponRequest *capon = nullptr) {
     NEED(ctx, d_data && (d_tx_delays || d_table) && d_elem && d_x && d_z && d_out);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, rq, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem, (const float *)d_x,
-                       (const float *)d_z, (float *)d_out, (const double *)d_table);
+                       (const float *)d_z, (float *)d_out, (const double *)d_table, capon);
 }
 
 static int first_arrival_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_tx_delays, const void *d_elem, const void *d_x, const void *d_z,
@@ -2442,7 +2447,7 @@ static int first_arrival_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_t
 }
 
 static int beamform_host(pbrt_ctx *ctx, const BfRequest &rq, const float *data, const float *tx_delays, const float *elem, const float *x,
-                         const float *z, float *out) {
+                         const float *z, float *out, const CaponRequest *capon = nullptr) {
     NEED(ctx, data && tx_delays && elem && x && z && out);
     const pbrt_das_params *p = rq.das;
     const size_t width = rq.method == PBRT_SCAN_IQ ? 2u : 1u;  // floats per sample and per pixel
@@ -2453,7 +2458,7 @@ static int beamform_host(pbrt_ctx *ctx, const BfRequest &rq, const float *data, 
     STAGED_BEGIN(ctx, n == 0);
     auto [dd, dt, de, dx, dz, dout] =
         S.arrays(stage_in(data, nd), stage_in(tx_delays, ne), stage_in(elem, nel), stage_in(x, ngx), stage_in(z, ngz), stage_out(out, n * width));
-    STAGED_RUN(S, das_enqueue(ctx, rq, dd, dt, de, dx, dz, dout, nullptr));
+    STAGED_RUN(S, das_enqueue(ctx, rq, dd, dt, de, dx, dz, dout, nullptr, capon));
 }
 // entering an entry point of the image chain: declares rq, the request its maker fills (bf_request.h, img_request.h)
 #define MAKE_REQUEST(ctx, Request, maker, ...) \
@@ -2503,6 +2508,21 @@ int pbrt_apod_beamform_table_dev(pbrt_ctx *ctx, const pbrt_apod_params *p, const
                                  const void *d_px, const void *d_pz, void *d_out) {
     BF_REQUEST(p);
     return beamform_dev(ctx, rq, d_data, d_elem, d_px, d_pz, d_out, nullptr, d_table);
+}
+int pbrt_capon_beamform(pbrt_ctx *ctx, const pbrt_capon_params *p, const float *iq, const float *tx_delays, const float *elem,
+                        const float *px, const float *pz, float *out) {
+    MAKE_REQUEST(ctx, CaponRequest, capon_request, p);
+    return beamform_host(ctx, rq.bf, iq, tx_delays, elem, px, pz, out, &rq);
+}
+int pbrt_capon_beamform_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem,
+                            const void *d_px, const void *d_pz, void *d_out) {
+    MAKE_REQUEST(ctx, CaponRequest, capon_request, p);
+    return beamform_dev(ctx, rq.bf, d_iq, d_elem, d_px, d_pz, d_out, d_tx_delays, nullptr, &rq);
+}
+int pbrt_capon_beamform_table_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const void *d_iq, const void *d_table, const void *d_elem,
+                                  const void *d_px, const void *d_pz, void *d_out) {
+    MAKE_REQUEST(ctx, CaponRequest, capon_request, p);
+    return beamform_dev(ctx, rq.bf, d_iq, d_elem, d_px, d_pz, d_out, nullptr, d_table, &rq);
 }
 int pbrt_scan_first_arrival_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_tx_delays, const void *d_elem, const void *d_px,
                                 const void *d_pz, void *d_table) {
