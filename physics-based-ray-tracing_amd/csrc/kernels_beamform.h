@@ -41,29 +41,9 @@
 #define DAS_SPLIT 4  // waves that share the elements of one tile (1, 2, 4 or 8)
 #endif
 
-// Which tile does workgroup b take?  Workgroup b runs on XCD b % 8, and every XCD has its own 4 MB L2: the z-tiles are cut into 16
-// bands and XCD k takes the bands k and 15 - k -- an XCD then reads one eighth of the samples (a pixel at depth z reads around
-// sample 2 z fs / c), and, the receive cone widening linearly with depth, a shallow band and its deep mirror together always hold
-// the same number of pixels that see an element: the same work on every XCD.  (Measured neutral at the sizes of USMain.py, 151
-// against 148 us: the 4.2 MB that are read at all stay cached either way; kept for larger acquisitions.)
-// -> (tx, tz), or false for a slot beyond the XCD's share.  m = z-tiles of the largest share.
-// tab: the scan is a pair of pixel tables px[nx][nz], pz[nx][nz] (the pbrt_scan_* entry points, DESIGN D21) instead of the axes
-// x[nx], z[nz] -- the strides (1, 0) / (0, 1) of the axes against (nz, 1) of the tables differ in this one bit: pixel (ix, iz) reads
-// entry tab ? ix * nz + iz : ix of gx and tab ? ix * nz + iz : iz of gz, once per lane, and everything after that is per pixel already.
-struct DasGrid {
-    uint32_t ntx, ntz, m, tab;
-};
+// The tile a workgroup takes (DasGrid, das_tile_of) is bf_request.h's: the host sizes the launch from the same text.
+// pixel (ix, iz) reads entry tab ? ix * nz + iz : ix of gx and tab ? ix * nz + iz : iz of gz (DasGrid::tab: pixel tables instead of axes)
 DEV uint32_t das_px_index(uint32_t tab, uint32_t i, uint32_t pix) { return tab ? pix : i; }
-__host__ DEV uint32_t das_band_lo(uint32_t band, uint32_t ntz) { return (band * ntz + DAS_BANDS - 1u) / DAS_BANDS; }
-DEV bool das_tile_of(const DasGrid g, uint32_t b, uint32_t *tx, uint32_t *tz) {
-    const uint32_t xcd = b % DAS_XCDS, i = b / DAS_XCDS;
-    const uint32_t lo1 = das_band_lo(xcd, g.ntz), n1 = das_band_lo(xcd + 1u, g.ntz) - lo1;
-    const uint32_t lo2 = das_band_lo(DAS_BANDS - 1u - xcd, g.ntz), n2 = das_band_lo(DAS_BANDS - xcd, g.ntz) - lo2;
-    const uint32_t t = i / g.m, r = i - t * g.m;
-    *tx = t;
-    *tz = r < n1 ? lo1 + r : lo2 + (r - n1);
-    return t < g.ntx && r < n1 + n2;
-}
 
 // A sample position as whole samples + a fraction in [0, 1): the sum of two positions is an integer add, an f32 add and the carry
 // (v_fract / v_floor) -- 2-cycle instructions -- where the f64 form needs add, multiply, floor / convert, subtract, convert at 4
@@ -102,9 +82,15 @@ DEV double das_lane_f64(double v, uint32_t e) {
 // distance of pixel (x, z) to an element: dx = x - x_e, and zz = z * z (linear) or dz = z - z_e (CONVEX)
 template <bool CONVEX>
 DEV double das_dist2(double dx, double zz, double dz) { return CONVEX ? dx * dx + dz * dz : dx * dx + zz; }
+// The travel time of transmission a by way of element e is tx[a][e] + |pixel - element| / c.  It is stated in two steps because the
+// flight time d does not depend on the angle (one square root serves DAS_ANG angles, and the receive side reads d alone); with
+// -ffp-contract=off `tx + d` is the one expression tx + sqrt(...) * inv_c.  Every kernel that makes or uses a first arrival calls both.
+template <bool CONVEX>
+DEV double das_flight(double dx, double zz, double dz, double inv_c) { return sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c; }
+DEV double das_first(double tmin, double tx, double d) { return fmin(tmin, tx + d); }
 
-// first-arrival table of a scan: ttx[a][ix][iz] = min_e (tx[a][e] + |(x, z) - (x_e, 0)| / c), the statement of k_das_beamform's first
-// pass (same operands, same operations: the same doubles).  One thread per pixel, z fastest.  tab: gx, gz are pixel tables (DasGrid).
+// first-arrival table of a scan: ttx[a][ix][iz] = min_e (tx[a][e] + |(x, z) - (x_e, 0)| / c), by the two functions above like the
+// walk's first pass: the same doubles.  One thread per pixel, z fastest.  tab: gx, gz are pixel tables (DasGrid).
 template <bool CONVEX = false>
 __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, uint32_t tab, const float *__restrict__ tx,
                                                            const float *__restrict__ elem_x, const float *__restrict__ gx,
@@ -124,10 +110,10 @@ __global__ __launch_bounds__(256) void k_das_first_arrival(pbrt_das_params p, ui
         for (uint32_t e = 0; e < E; ++e) {
             const double dx = x - (double)elem_x[CONVEX ? 4u * e : e];
             const double dz = CONVEX ? z - (double)elem_x[4u * e + 1u] : 0.0;
-            const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
+            const double d = das_flight<CONVEX>(dx, zz, dz, inv_c);
 #pragma unroll
             for (uint32_t j = 0; j < DAS_ANG; ++j)
-                if (j < na) tmin[j] = fmin(tmin[j], (double)tx[(size_t)(a0 + j) * E + e] + d);
+                if (j < na) tmin[j] = das_first(tmin[j], (double)tx[(size_t)(a0 + j) * E + e], d);
         }
 #pragma unroll
         for (uint32_t j = 0; j < DAS_ANG; ++j)
@@ -168,6 +154,95 @@ DEV float2 iq_rot(double cycles) {
     sincospif(2.0f * ph, &sn, &cs);
     return make_float2(cs, sn);
 }
+// a sample (or a sum of samples) turned by a rotation: rot * s
+DEV float2 iq_turn(float2 rot, float2 s) { return make_float2(fma_(rot.x, s.x, -(rot.y * s.y)), fma_(rot.x, s.y, rot.y * s.x)); }
+
+// ---- what every beamformer shares: the pixel of a lane, the aperture and the delayed sample, each stated once ----
+// Lane l of a wave is pixel (l >> 3, l & 7) of its 8 x 8 tile.  Lanes beyond the scan read its edge (the clamped pixel) and are
+// not `valid`.  `sees`: the pixel is valid and its aperture reaches into the span of a LINE of elements -- exact when the elements lie
+// between their extremes, as those of every probe do, and conservative otherwise (a pixel that passes without an element in its
+// aperture just adds nothing; the loop over all elements this replaces was a fifth of a wave's instruction stream).  CONVEX: every
+// valid lane -- the apertures of a curved array fan out, the span of the x_e bounds nothing.  -> the ballot of `sees`: 0 means that
+// the tile is exactly zero, which the caller stores.
+struct DasPixel {
+    uint32_t ix, iz;
+    bool valid, sees;
+    double x, z, half_ap;  // half_ap: half the width of the pixel's aperture on a line of elements, z / (2 f#)
+};
+DEV double das_half_ap(float f_number, double z) { return f_number > 0.0f ? z / (2.0 * (double)f_number) : 1e300; }
+template <bool CONVEX>
+DEV uint64_t das_tile_pixel(const pbrt_das_params &p, uint32_t tab, uint32_t tile_x, uint32_t tile_z, uint32_t lane,
+                            const float *__restrict__ elem_x, const float *__restrict__ gx, const float *__restrict__ gz, DasPixel *px) {
+    const uint32_t ix = tile_x * DAS_TILE + (lane >> 3), iz = tile_z * DAS_TILE + (lane & 7u), E = p.n_elements;
+    const bool valid = ix < p.nx && iz < p.nz;
+    const uint32_t cx = min(ix, p.nx - 1u), cz = min(iz, p.nz - 1u), cpix = cx * p.nz + cz;
+    const double x = (double)gx[das_px_index(tab, cx, cpix)], z = (double)gz[das_px_index(tab, cz, cpix)];
+    const double half_ap = das_half_ap(p.f_number, z);
+    float ex_lo = 3.0e38f, ex_hi = -3.0e38f;
+    for (uint32_t eb = 0; !CONVEX && eb < E; eb += 64u) {
+        const float v = elem_x[eb + min(lane, E - eb - 1u)];
+        ex_lo = fminf(ex_lo, v);
+        ex_hi = fmaxf(ex_hi, v);
+    }
+    if (!CONVEX) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
+            ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
+        }
+    }
+    const bool sees = valid && (CONVEX || (x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi));
+    *px = DasPixel{ix, iz, valid, sees, x, z, half_ap};
+    return __ballot(sees);
+}
+
+// The receive aperture of a pixel, from values: dx = x - x_e and, CONVEX, dz = z - z_e and the element's normal (enx, enz) -- the rule
+// of the CONVEX comment above, and |dx| <= half_ap on a line.  f# <= 0 (half_ap = 1e300, not `open`): every element receives every
+// pixel.  APOD: *u = the element's distance from the centre of the aperture over its half width (the APOD comment below).
+struct DasAperture {
+    bool open;  // f# > 0
+    double half_ap, two_f, inv_half_ap;
+};
+template <bool APOD>
+DEV DasAperture das_aperture_of(float f_number, double half_ap) {
+    return DasAperture{f_number > 0.0f, half_ap, f_number > 0.0f ? 2.0 * (double)f_number : 0.0, APOD ? 1.0 / half_ap : 0.0};
+}
+template <bool CONVEX, bool APOD>
+DEV bool das_in_aperture(const DasAperture &ap, double dx, double dz, double enx, double enz, [[maybe_unused]] double *u) {
+    if (CONVEX) {
+        const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
+        if constexpr (APOD) *u = ap.two_f * fabs(dt) * (1.0 / dn);
+        return ap.open ? (dn > 0.0 && ap.two_f * fabs(dt) <= dn) : true;
+    }
+    if constexpr (APOD) *u = fabs(dx) * ap.inv_half_ap;
+    return fabs(dx) <= ap.half_ap;
+}
+
+// The delayed sample s_{a,e} of a trace of T samples, handed to `take` in the branch that gathered it; nothing is taken outside the
+// aperture or the trace.  Nearest: the sample at rint((tmin + d - t0) fs), if that is one of 0 .. T - 1.  Linear: the position is
+// tp + dp (DasPos of (tmin - t0) fs and of d fs): between two samples their das_lerp, exactly on the last sample that sample, nothing
+// beyond it.  A macro, not a function: a function that calls `take` is optimised on its own first, with the caller's sums behind
+// references, and the compiler folds the two linear arms into one site (the form profiles/one_beamformer_walk.md measured 2 % slower
+// for F-DMAS; it cost a linear I/Q instance a wave per SIMD); a function that returns where the sample lies, with the branches at the
+// call, evaluates the conditions of both arms at once and was 2 - 4 % slower in the walk (profiles/shared_beamform_steps.md).
+// The arguments are evaluated more than once: pass values and names, nothing with a side effect; `take` is a callable's name.
+#define DAS_DELAYED(INTERP, trace, T, in_ap, tmin, d, t0, fs, tp, dp, take)                                  \
+    do {                                                                                                     \
+        if (INTERP == PBRT_DAS_NEAREST) {                                                                    \
+            const double r_ = rint(((tmin) + (d) - (t0)) * (fs));                                            \
+            if ((in_ap) && r_ >= 0.0 && r_ <= (double)((T) - 1u)) take((trace)[(uint32_t)r_]);              \
+        } else {                                                                                             \
+            const float fr_ = (tp).f + (dp).f;                                                               \
+            const float fl_ = floorf(fr_);                                                                   \
+            const float w_ = fr_ - fl_;                                                                      \
+            const uint32_t i0_ = (uint32_t)((tp).i + (dp).i + (int32_t)fl_);                                 \
+            if ((in_ap) && i0_ < (T) - 1u) {                                                                 \
+                take(das_lerp(w_, (trace)[i0_], (trace)[i0_ + 1]));                                          \
+            } else if ((in_ap) && i0_ == (T) - 1u && w_ == 0.0f) {                                           \
+                take((trace)[(T) - 1u]);                                                                     \
+            }                                                                                                \
+        }                                                                                                    \
+    } while (0)
 // p-DAS and F-DMAS (DESIGN D19).  The non-linear members of the beamformer family (`ultraspy` ships them beside DelayAndSum; absent here, so the arithmetic is this
 // build's own definition, include/pbrt_hip.h, taken from Polichetti et al. 2018 and Matrone et al. 2015).  The delayed sample s_e of
 // transmission a and element e at a pixel is exactly the term delay-and-sum adds; per transmission
@@ -212,51 +287,29 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
     uint32_t tile_x, tile_z;
     if (!das_tile_of(grid, blockIdx.x, &tile_x, &tile_z)) return;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t ix = tile_x * DAS_TILE + (lane >> 3), iz = tile_z * DAS_TILE + (lane & 7u);
-    const bool valid = ix < p.nx && iz < p.nz;
-    const uint32_t cx = min(ix, p.nx - 1u), cz = min(iz, p.nz - 1u), cpix = cx * p.nz + cz;  // (clamped: lanes beyond the scan read its edge)
-    const double x = (double)gx[das_px_index(grid.tab, cx, cpix)], z = (double)gz[das_px_index(grid.tab, cz, cpix)];
+    // which pixels of the tile see an element at all?  (every wave of the workgroup finds the same answer)
+    DasPixel px;
+    if (das_tile_pixel<CONVEX>(p, grid.tab, tile_x, tile_z, lane, elem_x, gx, gz, &px) == 0ull) {  // exact zeros
+        if (px.valid && wave == 0) out[(size_t)px.ix * p.nz + px.iz] = Sample{};
+        return;
+    }
+    const uint32_t ix = px.ix, iz = px.iz;
+    const bool valid = px.valid, any = px.sees;
+    const double x = px.x, z = px.z, zz = z * z;
     const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0;
     const uint32_t A = p.n_angles, E = p.n_elements, T = p.time_samples;
-    const double half_ap = p.f_number > 0.0f ? z / (2.0 * (double)p.f_number) : 1e300;
-    const double zz = z * z;
     const bool square = pw == 2.0f;
     const float inv_p = 1.0f / pw;
     // APOD: 1 / half_ap once per pixel (a window needs f# > 0: bf_request.h), 1 - alpha and 1 / alpha once per lane, 1 - a0 in f32
-    [[maybe_unused]] const double inv_half_ap = APOD ? 1.0 / half_ap : 0.0;
+    const DasAperture ap = das_aperture_of<APOD>(p.f_number, px.half_ap);
     [[maybe_unused]] const double flat = APOD ? 1.0 - (double)alpha : 0.0, inv_alpha = APOD ? 1.0 / (double)alpha : 0.0;
     [[maybe_unused]] const float apod_a1 = 1.0f - apod_a0;  // (a0 is the first angle of a trip below)
     // Element positions and transmit delays are tables of the launch, indexed by the (wave-uniform) element: as scalar loads they
     // put a trip to the scalar cache (or to L2) in front of every element of every loop -- a wave alone on its CU took 100 us for
     // 7 600 VALU instructions.  Instead lane l of the wave holds entry l of the current block of 64 elements, as doubles, and an
     // element is picked with v_readlane: no memory access inside the loops at all.
-    // which pixels of the tile see an element at all?  (every wave of the workgroup finds the same answer)
-    // (a test against the span of the array: exact when the elements lie between their extremes, as those of every probe do, and
-    // conservative otherwise -- a tile that passes without an element in any aperture just adds nothing.  The loop over all
-    // elements this replaces was a fifth of a wave's instruction stream.)
-    float ex_lo = 3.0e38f, ex_hi = -3.0e38f;
-    for (uint32_t eb = 0; !CONVEX && eb < E; eb += 64u) {
-        const float v = elem_x[eb + min(lane, E - eb - 1u)];
-        ex_lo = fminf(ex_lo, v);
-        ex_hi = fmaxf(ex_hi, v);
-    }
-    if (!CONVEX) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
-            ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
-        }
-    }
-    // (CONVEX: no early-out -- the apertures of a curved array fan out, the span of the x_e bounds nothing)
-    bool any = valid && (CONVEX || (x + half_ap >= (double)ex_lo && x - half_ap <= (double)ex_hi));
-    if (__ballot(any) == 0ull) {  // a tile outside the span of a linear array writes exact zeros
-        if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = Sample{};
-        return;
-    }
-    const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;  // CONVEX: 2 f# |d_t| <= d_n
     float acc = 0.0f;  // BF_DAS: this wave's partial sum; else, in wave 0: the y_a so far
     [[maybe_unused]] float acc_im = 0.0f;  // (BF_IQ: acc is the real part)
-    const double last = (double)(T - 1u);
     for (uint32_t a0 = 0; a0 < A; a0 += DAS_ANG) {
         const uint32_t na = min((uint32_t)DAS_ANG, A - a0);
         // first arrival of the emitted wavefront at the pixel, for the angles of this trip: this wave's share of the elements ...
@@ -264,6 +317,8 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
 #pragma unroll
         for (uint32_t j = 0; j < DAS_ANG; ++j) tmin[j] = 1e300;
         if (TABLE) {
+            // (the clamped pixel once more, as a 64-bit index of its own: with das_tile_pixel's 32-bit one handed on, three figures of the
+            // table form left the parent's range by 0.7 - 1.4 %, profiles/shared_beamform_steps.md)
             const size_t pix = (size_t)min(ix, p.nx - 1u) * p.nz + min(iz, p.nz - 1u), plane = (size_t)p.nx * p.nz;
 #pragma unroll
             for (uint32_t j = 0; j < DAS_ANG; ++j)
@@ -279,10 +334,10 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
             for (uint32_t e = wave; e < ne; e += DAS_SPLIT) {
                 const double dx = x - das_lane_f64(ex_l, e);
                 const double dz = CONVEX ? z - das_lane_f64(ez_l, e) : 0.0;
-                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
+                const double d = das_flight<CONVEX>(dx, zz, dz, inv_c);
 #pragma unroll
                 for (uint32_t j = 0; j < DAS_ANG; ++j)
-                    if (j < na) tmin[j] = fmin(tmin[j], das_lane_f64(tx_l[j], e) + d);
+                    if (j < na) tmin[j] = das_first(tmin[j], das_lane_f64(tx_l[j], e), d);
             }
         }
         // ... and the minimum over the waves
@@ -318,26 +373,18 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
             for (uint32_t el = wave; el < ne; el += DAS_SPLIT) {
                 const uint32_t e = eb + el;
                 const double dx = x - das_lane_f64(ex_l, el);
-                double dz = 0.0;
-                bool in_ap;
+                const double dz = CONVEX ? z - das_lane_f64(ez_l, el) : 0.0;
+                const double enx = CONVEX ? das_lane_f64(nx_l, el) : 0.0, enz = CONVEX ? das_lane_f64(nz_l, el) : 0.0;
                 [[maybe_unused]] double u = 0.0;  // (APOD) distance from the aperture's centre over its half width
-                if (CONVEX) {
-                    dz = z - das_lane_f64(ez_l, el);
-                    const double enx = das_lane_f64(nx_l, el), enz = das_lane_f64(nz_l, el);
-                    const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
-                    in_ap = any && (p.f_number > 0.0f ? (dn > 0.0 && two_f * fabs(dt) <= dn) : true);
-                    if constexpr (APOD) u = two_f * fabs(dt) * (1.0 / dn);
-                } else {
-                    in_ap = any && fabs(dx) <= half_ap;
-                    if constexpr (APOD) u = fabs(dx) * inv_half_ap;
-                }
+                const bool reached = das_in_aperture<CONVEX, APOD>(ap, dx, dz, enx, enz, &u);  // (unconditionally: u is no select on `any`)
+                const bool in_ap = any && reached;
                 if (__ballot(in_ap) == 0ull) continue;
                 [[maybe_unused]] float w_e = 1.0f;
                 if constexpr (APOD) {
                     const float t = (float)fmin(fmax((u - flat) * inv_alpha, 0.0), 1.0);
                     w_e = fma_(apod_a1, cospif(t), apod_a0);
                 }
-                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
+                const double d = das_flight<CONVEX>(dx, zz, dz, inv_c);
                 const DasPos dp = INTERP == PBRT_DAS_LINEAR ? das_split(d * fs) : DasPos{0, 0.0f};
                 [[maybe_unused]] float2 rot_e = make_float2(1.0f, 0.0f);
                 if constexpr (METHOD == BF_IQ) rot_e = iq_rot((double)pw * d);
@@ -354,8 +401,9 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
                         if constexpr (METHOD == BF_DAS) {
                             acc += s;
                         } else if constexpr (METHOD == BF_IQ) {
-                            q[j] += fma_(rot_e.x, s.x, -(rot_e.y * s.y));
-                            b[j] += fma_(rot_e.x, s.y, rot_e.y * s.x);
+                            const float2 v_e = iq_turn(rot_e, s);
+                            q[j] += v_e.x;
+                            b[j] += v_e.y;
                         } else if constexpr (METHOD == PBRT_BF_FDMAS) {
                             q[j] += nl_root<METHOD>(s, square, inv_p);
                             b[j] += __builtin_fabsf(s);
@@ -364,21 +412,7 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
                             use = true;
                         }
                     };
-                    if (INTERP == PBRT_DAS_NEAREST) {
-                        const double r = rint((tmin[j] + d - t0) * fs);
-                        if (in_ap && r >= 0.0 && r <= last) take(trace[(uint32_t)r]);
-                    } else {
-                        const float fr = tp[j].f + dp.f;  // [0, 2)
-                        const float fl = floorf(fr);
-                        const float w = fr - fl;
-                        const uint32_t i0 = (uint32_t)(tp[j].i + dp.i + (int32_t)fl);
-                        if (in_ap && i0 < T - 1u) {
-                            const Sample v0 = trace[i0], v1 = trace[i0 + 1];
-                            take(das_lerp(w, v0, v1));
-                        } else if (in_ap && i0 == T - 1u && w == 0.0f) {  // exactly the last sample
-                            take(trace[T - 1u]);
-                        }
-                    }
+                    DAS_DELAYED(INTERP, trace, T, in_ap, tmin[j], d, t0, fs, tp[j], dp, take);
                     if constexpr (METHOD == PBRT_BF_PDAS) {
                         if (use) q[j] += nl_root<METHOD>(v, square, inv_p);
                     }
@@ -404,9 +438,9 @@ DEV void das_walk(const pbrt_das_params &p, const DasGrid grid, const typename D
                 if constexpr (METHOD == BF_IQ) {
                     float ba = s_sum[0][DAS_ANG + j][lane];
                     for (uint32_t w = 1; w < DAS_SPLIT; ++w) ba += s_sum[w][DAS_ANG + j][lane];
-                    const float2 rot_a = iq_rot((double)pw * tmin[j]);
-                    acc += fma_(rot_a.x, qa, -(rot_a.y * ba));
-                    acc_im += fma_(rot_a.x, ba, rot_a.y * qa);
+                    const float2 y_a = iq_turn(iq_rot((double)pw * tmin[j]), make_float2(qa, ba));
+                    acc += y_a.x;
+                    acc_im += y_a.y;
                 } else if (METHOD == PBRT_BF_FDMAS) {
                     float ba = s_sum[0][DAS_ANG + j][lane];
                     for (uint32_t w = 1; w < DAS_SPLIT; ++w) ba += s_sum[w][DAS_ANG + j][lane];
@@ -470,9 +504,10 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_apod_beamform(pbrt_das_param
 
 // ---- Capon: the minimum-variance beamformer on I/Q data (DESIGN D23; the definition and the order of the sums: include/pbrt_hip.h) ----
 // Not a METHOD of das_walk: there a lane is a pixel and the elements pass by; here a pixel and transmission needs an L x L Hermitian
-// system solved, L <= 32, so a WAVE owns the pixel and its lanes are elements, then entries of R, then rows of the factor.  Kept from the
-// walk: the tile map (das_tile_of, DasGrid: 8 x 8 tiles, axes or tables), das_split / DasPos, iq_rot, das_lerp, and the early-out for the
-// tiles of a line of elements that no element sees.  A workgroup is four waves on one tile; wave w takes the pixels w, w + 4, ... of the
+// system solved, L <= 32, so a WAVE owns the pixel and its lanes are elements, then entries of R, then rows of the factor.  Called, as
+// the walk calls them: das_tile_of (the tile of a workgroup), das_tile_pixel (the 64 pixels of the tile and which of them a line of
+// elements sees), das_flight / das_first (travel times), das_aperture_of / das_in_aperture, DAS_DELAYED (the delayed sample: das_split,
+// das_lerp and the range rules) and iq_rot / iq_turn.  A workgroup is four waves on one tile; wave w takes the pixels w, w + 4, ... of the
 // tile, one after the other, and the waves never meet: no s_barrier anywhere, every loop bound is wave-uniform.
 //   gather      lanes are elements in blocks of 64: distance and aperture test per lane; the first arrival from the table, or the
 //               wave-wide minimum over ALL elements (f64 fmin: exact, whatever the order -- the table form is bit-equal); the sample is
@@ -509,37 +544,15 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_capon_beamform(pbrt_das_para
     if (E > CAPON_MAX_E) return;  // (capon_request refuses it: a rank never leaves the row)
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     float2 *sv = s_v[wave], *G = s_g[wave];
-    const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0, last = (double)(T - 1u);
-    const double two_f = p.f_number > 0.0f ? 2.0 * (double)p.f_number : 0.0;
-    // lane = pixel of the tile, as in the walk: its position, and whether it sees an element of a line at all
-    uint64_t seen;
-    double x_l, z_l;
-    {
-        const uint32_t ix = tile_x * DAS_TILE + (lane >> 3), iz = tile_z * DAS_TILE + (lane & 7u);
-        const bool valid = ix < p.nx && iz < p.nz;
-        const uint32_t cx = min(ix, p.nx - 1u), cz = min(iz, p.nz - 1u), cpix = cx * p.nz + cz;
-        x_l = (double)gx[das_px_index(grid.tab, cx, cpix)];
-        z_l = (double)gz[das_px_index(grid.tab, cz, cpix)];
-        const double half_ap = p.f_number > 0.0f ? z_l / (2.0 * (double)p.f_number) : 1e300;
-        float ex_lo = 3.0e38f, ex_hi = -3.0e38f;
-        for (uint32_t eb = 0; !CONVEX && eb < E; eb += 64u) {
-            const float v = elem_x[eb + min(lane, E - eb - 1u)];
-            ex_lo = fminf(ex_lo, v);
-            ex_hi = fmaxf(ex_hi, v);
-        }
-        if (!CONVEX) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                ex_lo = fminf(ex_lo, __shfl_xor(ex_lo, off));
-                ex_hi = fmaxf(ex_hi, __shfl_xor(ex_hi, off));
-            }
-        }
-        seen = __ballot(valid && (CONVEX || (x_l + half_ap >= (double)ex_lo && x_l - half_ap <= (double)ex_hi)));
-        if (seen == 0ull) {  // a tile outside the span of a linear array writes exact zeros
-            if (valid && wave == 0) out[(size_t)ix * p.nz + iz] = float2{};
-            return;
-        }
+    const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0;
+    // first the lanes are the pixels of the tile: the positions stay in lanes, `seen` says which pixels have a system to solve at all
+    DasPixel lp;
+    const uint64_t seen = das_tile_pixel<CONVEX>(p, grid.tab, tile_x, tile_z, lane, elem_x, gx, gz, &lp);
+    if (seen == 0ull) {  // exact zeros
+        if (lp.valid && wave == 0) out[(size_t)lp.ix * p.nz + lp.iz] = float2{};
+        return;
     }
+    const double x_l = lp.x, z_l = lp.z;
     for (uint32_t px = wave; px < DAS_TILE * DAS_TILE; px += DAS_SPLIT) {
         const uint32_t ix = tile_x * DAS_TILE + (px >> 3), iz = tile_z * DAS_TILE + (px & 7u);
         if (ix >= p.nx || iz >= p.nz) continue;
@@ -549,7 +562,7 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_capon_beamform(pbrt_das_para
             continue;
         }
         const double x = das_lane_f64(x_l, px), z = das_lane_f64(z_l, px), zz = z * z;
-        const double half_ap = p.f_number > 0.0f ? z / (2.0 * (double)p.f_number) : 1e300;
+        const DasAperture ap = das_aperture_of<false>(p.f_number, das_half_ap(p.f_number, z));
         float acc = 0.0f, acc_im = 0.0f;
         for (uint32_t a = 0; a < A; ++a) {
             // first arrival of the emitted wavefront at the pixel
@@ -561,7 +574,7 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_capon_beamform(pbrt_das_para
                     const uint32_t e = min(eb + lane, E - 1u);  // (a lane beyond the last element repeats it: the minimum is the same)
                     const double dx = x - (double)elem_x[CONVEX ? 4u * e : e];
                     const double dz = CONVEX ? z - (double)elem_x[4u * e + 1u] : 0.0;
-                    tmin = fmin(tmin, (double)tx[(size_t)a * E + e] + sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c);
+                    tmin = das_first(tmin, (double)tx[(size_t)a * E + e], das_flight<CONVEX>(dx, zz, dz, inv_c));
                 }
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) tmin = fmin(tmin, __shfl_xor(tmin, off));
@@ -573,48 +586,21 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_capon_beamform(pbrt_das_para
             for (uint32_t eb = 0; eb < E; eb += 64u) {
                 const uint32_t e = eb + lane, ec = min(e, E - 1u);
                 const double dx = x - (double)elem_x[CONVEX ? 4u * ec : ec];
-                double dz = 0.0;
-                bool in_ap;
-                if (CONVEX) {
-                    dz = z - (double)elem_x[4u * ec + 1u];
-                    const double enx = (double)elem_x[4u * ec + 2u], enz = (double)elem_x[4u * ec + 3u];
-                    const double dn = dx * enx + dz * enz, dt = dx * enz - dz * enx;
-                    in_ap = p.f_number > 0.0f ? (dn > 0.0 && two_f * fabs(dt) <= dn) : true;
-                } else {
-                    in_ap = fabs(dx) <= half_ap;
-                }
-                const double d = sqrt(das_dist2<CONVEX>(dx, zz, dz)) * inv_c;
+                const double dz = CONVEX ? z - (double)elem_x[4u * ec + 1u] : 0.0;
+                const double enx = CONVEX ? (double)elem_x[4u * ec + 2u] : 0.0, enz = CONVEX ? (double)elem_x[4u * ec + 3u] : 0.0;
+                const bool in_ap = e < E && das_in_aperture<CONVEX, false>(ap, dx, dz, enx, enz, nullptr);
+                const double d = das_flight<CONVEX>(dx, zz, dz, inv_c);
+                const DasPos dp = INTERP == PBRT_DAS_LINEAR ? das_split(d * fs) : DasPos{0, 0.0f};
                 bool use = false;
                 float2 s = float2{};
-                if (e < E && in_ap) {
-                    const float2 *trace = data + ((size_t)a * E + e) * T;
-                    if (INTERP == PBRT_DAS_NEAREST) {
-                        const double r = rint((tmin + d - t0) * fs);
-                        if (r >= 0.0 && r <= last) {
-                            s = trace[(uint32_t)r];
-                            use = true;
-                        }
-                    } else {
-                        const DasPos dp = das_split(d * fs);
-                        const float fr = tp.f + dp.f;  // [0, 2)
-                        const float fl = floorf(fr);
-                        const float w = fr - fl;
-                        const uint32_t i0 = (uint32_t)(tp.i + dp.i + (int32_t)fl);
-                        if (i0 < T - 1u) {
-                            s = das_lerp(w, trace[i0], trace[i0 + 1]);
-                            use = true;
-                        } else if (i0 == T - 1u && w == 0.0f) {  // exactly the last sample
-                            s = trace[T - 1u];
-                            use = true;
-                        }
-                    }
-                }
+                const float2 *trace = data + ((size_t)a * E + ec) * T;
+                const auto take = [&](float2 v) {
+                    s = v;
+                    use = true;
+                };
+                DAS_DELAYED(INTERP, trace, T, in_ap, tmin, d, t0, fs, tp, dp, take);
                 const uint64_t users = __ballot(use);
-                if (use) {
-                    const float2 rot_e = iq_rot((double)f_d * d);
-                    sv[N + (uint32_t)__popcll(users & ((1ull << lane) - 1ull))] =
-                        make_float2(fma_(rot_e.x, s.x, -(rot_e.y * s.y)), fma_(rot_e.x, s.y, rot_e.y * s.x));
-                }
+                if (use) sv[N + (uint32_t)__popcll(users & ((1ull << lane) - 1ull))] = iq_turn(iq_rot((double)f_d * d), s);
                 N += (uint32_t)__popcll(users);
             }
             if (N == 0u) continue;  // y_a = (0, 0)
@@ -723,9 +709,9 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_capon_beamform(pbrt_das_para
             }
             const float scale = (float)N / (float)M;
             const float yr = scale * nr / den * up, yi = scale * ni / den * up;
-            const float2 rot_a = iq_rot((double)f_d * tmin);
-            acc += fma_(rot_a.x, yr, -(rot_a.y * yi));
-            acc_im += fma_(rot_a.x, yi, rot_a.y * yr);
+            const float2 y_a = iq_turn(iq_rot((double)f_d * tmin), make_float2(yr, yi));
+            acc += y_a.x;
+            acc_im += y_a.y;
         }
         if (lane == 0) out[pix] = p.compound_mean ? make_float2(acc / (float)A, acc_im / (float)A) : make_float2(acc, acc_im);
     }

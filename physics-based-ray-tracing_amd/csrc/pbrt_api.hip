@@ -2321,50 +2321,44 @@ static int launched(pbrt_ctx *c) {  // the end of every function that queues ker
 // ---- one beamform request (bf_request.h: the request, and the rules of the four parameter blocks) from the entry points to the launch ----
 // de: element positions [n_elements], or (rq.probe) the element table [n_elements][4]; dx, dz: the axes, or (rq.tab) the pixel tables;
 // dt, ttx: the transmit delays, and the first-arrival table of this scan or null
+// DAS_PICK(k<I, T, X ...>): the selector of a beamform family for with_flags(linear interpolation, first-arrival table, element table)
+#define DAS_PICK(...)                                                                    \
+    [](auto L, auto Tab, auto Probe) {                                                   \
+        constexpr uint32_t I = L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST;                 \
+        constexpr bool T = Tab(), X = Probe();                                           \
+        return &__VA_ARGS__;                                                             \
+    }
 static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const float *dt, const float *de, const float *dx, const float *dz,
                        float *dout, const double *ttx, const CaponRequest *capon = nullptr) {
     const pbrt_das_params *p = rq.das;
     ImgTimer tm(c, IMG_DAS);
     DasGrid g;
-    g.tab = rq.tab ? 1u : 0u;
-    g.ntx = das_tiles(p->nx);
-    g.ntz = das_tiles(p->nz);
-    // z-tiles of the largest XCD share (bands k and 15 - k, kernels_beamform.h das_tile_of); the grid gives every XCD that many slots
-    g.m = 0;
-    auto lo = [&](uint32_t band) { return das_band_lo(band, g.ntz); };
-    for (uint32_t k = 0; k < DAS_XCDS; ++k) g.m = std::max(g.m, (lo(k + 1) - lo(k)) + (lo(DAS_BANDS - k) - lo(DAS_BANDS - 1u - k)));
-    const uint32_t blocks = DAS_XCDS * g.ntx * std::max(g.m, 1u);
-    const dim3 grid(blocks), block(64 * DAS_SPLIT);
-    if (capon) {  // Capon (D23): the tiles of the walk, a wave per pixel; I/Q data and pixels, l_prop and delta_l launch arguments
-        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_capon_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
-        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
-                           reinterpret_cast<float2 *>(dout), rq.pw, capon->l_prop, capon->delta_l);
-    } else if (rq.window != PBRT_APOD_BOXCAR && rq.method == PBRT_SCAN_IQ) {  // a receive window (D22): the walk with the weight arm, a0 and alpha
-        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_apod_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), BF_IQ>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
-        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
-                           reinterpret_cast<float2 *>(dout), rq.pw, rq.a0, rq.alpha);
-    } else if (rq.window != PBRT_APOD_BOXCAR) {
-        const auto kernel = with_flags([](auto L, auto T, auto X, auto F, auto P) {
-            return &k_apod_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), F() ? PBRT_BF_FDMAS : P() ? PBRT_BF_PDAS : BF_DAS>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe, rq.method == PBRT_BF_FDMAS,
-                                       rq.method == PBRT_BF_PDAS);
-        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout, rq.pw, rq.a0, rq.alpha);
-    } else if (rq.method == PBRT_SCAN_IQ) {  // I/Q delay-and-sum: dd and dout hold (re, im) pairs, pw is the demodulation frequency
-        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_iq_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
-        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, reinterpret_cast<const float2 *>(dd), dt, de, dx, dz, ttx,
-                           reinterpret_cast<float2 *>(dout), rq.pw);
-    } else if (rq.method != PBRT_SCAN_DAS) {  // p-DAS / F-DMAS: the same tiles, the method's arithmetic compiled in, p a launch argument
-        const auto kernel = with_flags([](auto L, auto T, auto X, auto F) {
-            return &k_nl_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X(), F() ? PBRT_BF_FDMAS : PBRT_BF_PDAS>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe, rq.method == PBRT_BF_FDMAS);
-        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout, rq.pw);
-    } else {
-        const auto kernel = with_flags([](auto L, auto T, auto X) { return &k_das_beamform<L() ? PBRT_DAS_LINEAR : PBRT_DAS_NEAREST, T(), X()>; },
-                                       p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
-        hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, *p, g, dd, dt, de, dx, dz, ttx, dout);
+    const uint32_t blocks = das_grid(&g, p->nx, p->nz, rq.tab);
+    // The one launch: `pick` names a family's instance for <INTERP, TABLE, CONVEX>, the nine arguments every family takes follow (the
+    // samples and the pixels as the method's type, kernels_beamform.h DasSample), then the family's own.
+    const auto family = [&](auto method) {
+        constexpr uint32_t M = decltype(method)::value;
+        typedef typename DasSample<M>::type Sample;
+        const auto launch = [&](auto pick, auto... own) {
+            hipLaunchKernelGGL(with_flags(pick, p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe), dim3(blocks), dim3(64 * DAS_SPLIT),
+                               0, c->stream, *p, g, reinterpret_cast<const Sample *>(dd), dt, de, dx, dz, ttx, reinterpret_cast<Sample *>(dout), own...);
+        };
+        //  the request                                    its kernel                              the kernel's own arguments
+        if constexpr (M == BF_IQ) {  // (Capon's samples are I/Q pairs: the switch below sends every Capon request here)
+            if (capon)                              return launch(DAS_PICK(k_capon_beamform<I, T, X>),    rq.pw, capon->l_prop, capon->delta_l);  // (D23)
+        }
+        if (rq.window != PBRT_APOD_BOXCAR)          return launch(DAS_PICK(k_apod_beamform<I, T, X, M>),  rq.pw, rq.a0, rq.alpha);                // (D22)
+        if constexpr (M == BF_IQ)                   return launch(DAS_PICK(k_iq_beamform<I, T, X>),       rq.pw);  // pw: the demodulation frequency
+        else if constexpr (M == BF_DAS)             return launch(DAS_PICK(k_das_beamform<I, T, X>));
+        else                                        return launch(DAS_PICK(k_nl_beamform<I, T, X, M>),    rq.pw);  // pw: p
+    };
+    // (bf_request admits four methods and capon_request I/Q alone; what they would refuse goes where it went before this table was one:
+    // a Capon request to Capon whatever its method, an unknown method to p-DAS)
+    switch (capon ? (uint32_t)PBRT_SCAN_IQ : rq.method) {
+        case PBRT_SCAN_IQ: family(std::integral_constant<uint32_t, BF_IQ>{}); break;
+        case PBRT_BF_FDMAS: family(std::integral_constant<uint32_t, PBRT_BF_FDMAS>{}); break;
+        default: family(std::integral_constant<uint32_t, PBRT_BF_PDAS>{}); break;
+        case PBRT_SCAN_DAS: family(std::integral_constant<uint32_t, BF_DAS>{}); break;
     }
     c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * (rq.method == PBRT_SCAN_IQ ? 8 : 4);
     return launched(c);

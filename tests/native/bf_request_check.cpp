@@ -2,12 +2,15 @@
 // valid parameter block into the request (method, pw, probe, tab) the launch reads, and refuse every single violation of the rules
 // the entry points kept before the header existed -- those of a pbrt_das_params (counts, rates, interpolation, f-number, the pixel
 // count and the launch grid), the methods each block admits, probe <= 1, 1 <= p <= 8 for p-DAS only, demod_freq finite and >= 0 for I/Q only.
+// And the launch grid the host and the kernels share: over 12 x 12 scan sizes, axes and tables, the slots 0 .. blocks - 1 of das_grid give,
+// through das_tile_of, every tile of the scan exactly once and nothing else.
 // Prints one JSON line: {"checks": N, "failures": M}.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
 #include <limits>
+#include <vector>
 
 #include "bf_request.h"
 
@@ -172,6 +175,32 @@ int main() {
         pbrt_scan_params s{d, PBRT_SCAN_IQ, NaN, f, 0u};   // (p is not read)
         CHECK(is(bf_request(&rq, &s), rq, &s.das, PBRT_SCAN_IQ, f, false, true));
     }
+
+    // ---- the launch grid: das_grid's slots, walked through das_tile_of as the kernels walk them, hand every tile out exactly once ----
+    const uint32_t sizes[] = {1, 7, 8, 9, 64, 121, 127, 128, 129, 135, 1040, 2547};  // 1, 2, 8, 9, 16, 17 tiles ... and the bench shape
+    for (uint32_t nx : sizes)
+        for (uint32_t nz : sizes)
+            for (uint32_t tab = 0; tab <= 1; ++tab) {
+                DasGrid g;
+                const uint32_t blocks = das_grid(&g, nx, nz, tab != 0);
+                CHECK(g.ntx == das_tiles(nx) && g.ntz == das_tiles(nz) && g.tab == tab && g.m >= 1 && g.m <= g.ntz);
+                CHECK(blocks == DAS_XCDS * g.ntx * g.m);
+                std::vector<uint8_t> given((size_t)g.ntx * g.ntz, 0);
+                uint32_t taken = 0, outside = 0, twice = 0;
+                for (uint32_t b = 0; b < blocks; ++b) {
+                    uint32_t tx = 0, tz = 0;
+                    if (!das_tile_of(g, b, &tx, &tz)) continue;
+                    ++taken;
+                    if (tx >= g.ntx || tz >= g.ntz) {
+                        ++outside;
+                    } else if (given[(size_t)tx * g.ntz + tz]++) {
+                        ++twice;
+                    }
+                }
+                // (every slot that is taken names a tile of the scan, no tile twice, and as many as there are tiles: each exactly once,
+                // and every other slot is refused)
+                CHECK(outside == 0 && twice == 0 && taken == g.ntx * g.ntz);
+            }
 
     std::printf("{\"checks\": %d, \"failures\": %d}\n", checks, failures);
     return failures ? 1 : 0;

@@ -45,3 +45,10 @@ def test_the_kernels_and_the_host_share_the_header():
     assert '#include "bf_request.h"' in text
     assert "#define DAS_TILE" not in text and "#define DAS_XCDS" not in text and "#define DAS_BANDS" not in text
     assert "static_assert(BF_IQ == PBRT_SCAN_IQ" in text or "#define BF_IQ PBRT_SCAN_IQ" in text
+    # the launch grid too: the struct, the band split and the tile of a workgroup are the header's, and the host sizes its launch there
+    request = open(os.path.join(CSRC, "bf_request.h")).read()
+    for name in ("struct DasGrid", "uint32_t das_band_lo(", "bool das_tile_of(", "uint32_t das_grid("):
+        assert name in request and name not in text, name
+    assert "das_tile_of(grid, blockIdx.x" in text
+    host = open(os.path.join(CSRC, "pbrt_api.hip")).read()
+    assert "das_grid(&g" in host and "das_band_lo" not in host
