@@ -204,6 +204,10 @@ typedef struct pbrt_film_desc {
 #define PBRT_FILM_NO_ORDERED_WALK 0x40u /* diagnostic: a brute-force scene whose primitive lists are class-ordered (parallelograms, then \
                                            triangles, then curved records) is rendered through the kernels that walk the run tables \
                                            (csrc/prim_runs.h) -- same film, same statistics */
+#define PBRT_FILM_NO_PATH_KERNEL 0x2000000u /* diagnostic: a pass of camera paths whose every bounce one launch walks (brute-force \
+                                               scenes without glossy materials, max_depth <= 6) goes through the bounce kernel with \
+                                               its survivor compaction instead of k_path (csrc/kernels_radiance.h) -- same film, \
+                                               same statistics */
 
 /* ---- ultrasound (acoustic) mode ----------------------------------------------------------- */
 /* Parameter block of UltraIntegrator (CustomIntegrator.py:13-48) plus the sensor transform

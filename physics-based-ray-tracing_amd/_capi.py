@@ -30,6 +30,7 @@ FILM_NO_REPACK = 2
 FILM_NO_OCCLUDER_PRUNING = 4
 FILM_NO_TILE_CULL = 0x20  # diagnostic: camera rays of brute-force scenes walk every primitive (no keep words per pixel tile)
 FILM_NO_ORDERED_WALK = 0x40  # diagnostic: class-ordered brute-force scenes through the kernels that walk the run tables
+FILM_NO_PATH_KERNEL = 0x2000000  # diagnostic: one-launch passes of camera paths through k_bounce instead of k_path
 FILM_NO_HIT_POOL = 0x10  # diagnostic: BVH scenes without k_bounce_pool
 FILM_REGEN = 8  # diagnostic: brute-force scenes, persistent waves with path regeneration, one launch per pass (k_regen)
 FILM_FUSE_PLAN_SET = 0x80

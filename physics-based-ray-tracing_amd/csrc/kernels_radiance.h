@@ -176,8 +176,9 @@ DEV uint32_t xcd_swizzle(uint32_t b, uint32_t n) {
     return (b & ~7u) | ((b + rot) & 7u);
 }
 
-template <bool TILED>
-DEV void path_key(const RadArgs &a, uint32_t home, uint32_t *ka, uint32_t *kb, uint32_t *px, uint32_t *py) {
+// Args: RadArgs, or PathArgs (k_path: key mode 0 as a constant)
+template <bool TILED, class Args>
+DEV void path_key(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, uint32_t *px, uint32_t *py) {
     if (a.key_mode == 0) {
         uint32_t sl = udiv_fast(home, a.div_npix), pr = home - sl * a.npix_r;
         uint32_t rx, ry;
@@ -383,8 +384,10 @@ DEV bool shade_step(const Args &a, const Tables &tb, uint32_t depth, uint32_t ka
 // GLOSSY: as shade_step.  Only k_bounce of the brute-force scenes has instances without it: every other kernel that comes through
 // here (the diagnostic build's launch structures, on the _BIG tables) always carries the arms.
 // ORDERED: as scene_intersect (the ACCEL_K_BRUTE_ORDERED instances of k_bounce).
-template <int ACCEL, bool HAVE_HIT = false, bool GLOSSY = ACCEL != ACCEL_K_BRUTE, bool ORDERED = false>
-DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsrc r_L, uint32_t depth, uint32_t ka, uint32_t kb,
+// STORE: a path that ends writes its record here; without it the caller does, from the L the lane keeps (k_path: r_L is not read).
+// Args: RadArgs, or PathArgs (k_path).
+template <int ACCEL, bool HAVE_HIT = false, bool GLOSSY = ACCEL != ACCEL_K_BRUTE, bool ORDERED = false, bool STORE = true, class Args>
+DEV bool bounce_step(const Args &a, const Tables &tb, const LdsScene &ls, Rsrc r_L, uint32_t depth, uint32_t ka, uint32_t kb,
                      uint32_t home, float tmax, V3 &o, V3 &d, V3 &thr, V3 &L, float &eta, float &prev_pdf, bool &did_seg,
                      bool &did_shadow, const Hit *h_in = nullptr, uint32_t keep = 0xffffffffu) {
     bool survive = false;
@@ -407,7 +410,7 @@ DEV bool bounce_step(const RadArgs &a, const Tables &tb, const LdsScene &ls, Rsr
             },
             [&](V3 A, V3 B) { L = {fma_(A.x, B.x, L.x), fma_(A.y, B.y, L.y), fma_(A.z, B.z, L.z)}; });
     }
-    if (!survive) {
+    if (STORE && !survive) {
         // one 16-byte record per finished path: three 4-byte row stores at a scattered `home` cost three
         // 32-byte HBM sectors (measured: k_bounce WRITE_SIZE 1.23 x algorithmic), one dwordx4 store costs one
         typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
@@ -710,6 +713,153 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
                 const uint32_t n_on = k <= 3 ? (mid_acc >> (10u * (k - 1u))) & 1023u : (mid_acc_hi >> (10u * (k - 4u))) & 1023u;
                 row[(2 + min(a.depth + k, (uint32_t)MAX_DEPTH_STATS - 1)) * stride] += n_on;
             }
+    }
+}
+
+// ---- k_path: camera paths of an ACCEL_K_BRUTE scene walked to their end in ONE launch --------------------------------------------
+// When the fuse plan walks every bounce of a pass in one launch (max_depth <= MAX_CHAIN) no path outlives the launch: there is
+// nothing to compact, no state to write and no survivor count to publish.  k_path is that launch without the machinery: the same
+// camera start, keep word, bounce_step and RNG keys as k_bounce<true, .., 2> in the same order (same film, bit for bit), but
+//   * no barrier after the one that ends the table staging: the waves of a workgroup end on their own, and their slots are free
+//     for the next workgroup's waves at once;
+//   * a lane keeps L when its path ends and the wave stores its 64 records after the bounce loop, 1 KiB contiguous;
+//   * the waves add their counts to workgroup counters in LDS and the last one to arrive adds them to the workgroup's statistics
+//     row (row = workgroup of the launch: stat_stride >= gridDim.x);
+//   * an argument block of its own.  (DevScene stays whole -- brute_intersect takes it -- but its BVH members are never loaded.)
+// THREADS: the workgroup size (PATH_THREADS is what the host launches); the pass is cut into workgroups of THREADS consecutive homes.
+// Measured on MI355X, cbox 512^2 x 256 spp (profiles/path_kernel.md): 5.88 -> 5.70 ms per step against k_bounce<true, 5, 2>, the store
+// after the loop alone 0.14 ms of it; 512 / 256 / 128 / 64 threads -> 5.71 / 5.71 / 5.98 / 6.04 ms (the table staging per workgroup).
+#ifndef PATH_THREADS
+#define PATH_THREADS 512
+#endif
+static_assert(SEG_BRUTE % PATH_THREADS == 0 && PATH_THREADS % 64 == 0, "a region of the brute-force kernels is whole k_path workgroups");
+// k_path workgroups (and statistics rows) per region of the brute-force kernels
+__host__ __device__ constexpr uint32_t path_groups_per_region() { return SEG_BRUTE / PATH_THREADS; }
+struct PathArgs {
+    DevScene sc;
+    pbrt_camera cam;
+    float *Lhome;               // [cap] float4 records (r, g, b, 0) indexed by home
+    unsigned long long *stats;  // as RadArgs::stats; one row per workgroup of the launch
+    const uint32_t *tile_keep;  // as RadArgs::tile_keep
+    uint32_t stat_stride, cap, n_paths, max_depth, rr_depth, seed;
+    uint32_t rx0, ry0, rw, npix_r, s_first, film_w, film_h, tile_rows;
+    FastDiv div_npix, div_rw;
+    static constexpr uint32_t key_mode = 0, index_offset = 0, sample_index = 0;  // (path_key)
+};
+// what k_path reads of the arguments of a bounce launch (host)
+static inline PathArgs path_args(const RadArgs &a) {
+    PathArgs p;
+    p.sc = a.sc;
+    p.cam = a.cam;
+    p.Lhome = a.Lhome;
+    p.stats = a.stats;
+    p.tile_keep = a.tile_keep;
+    p.stat_stride = a.stat_stride;
+    p.cap = a.cap;
+    p.n_paths = a.n_paths;
+    p.max_depth = a.max_depth;
+    p.rr_depth = a.rr_depth;
+    p.seed = a.seed;
+    p.rx0 = a.rx0;
+    p.ry0 = a.ry0;
+    p.rw = a.rw;
+    p.npix_r = a.npix_r;
+    p.s_first = a.s_first;
+    p.film_w = a.film_w;
+    p.film_h = a.film_h;
+    p.tile_rows = a.tile_rows;
+    p.div_npix = a.div_npix;
+    p.div_rw = a.div_rw;
+    return p;
+}
+template <int ACCEL_T, int THREADS>
+__global__ __launch_bounds__(THREADS, FUSED_WAVES_PER_EU) void k_path(const PathArgs a) {
+    static_assert(ACCEL_T == ACCEL_K_BRUTE || ACCEL_T == ACCEL_K_BRUTE_ORDERED, "k_path: ACCEL_K_BRUTE scenes without glossy materials");
+    constexpr bool ORD = ACCEL_T == ACCEL_K_BRUTE_ORDERED;
+    constexpr uint32_t W = THREADS / 64;
+    __shared__ uint32_t tab_lds[TAB_DW];
+    __shared__ uint32_t wg_cnt[2 + MAX_CHAIN];  // segments, shadow rays, paths that went on to bounce 1 .. MAX_CHAIN - 1; [1 + MAX_CHAIN]: waves done
+    const uint32_t wg = xcd_swizzle(blockIdx.x, gridDim.x);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t base = wg * THREADS;
+    if (base >= a.n_paths) return;  // uniform across the workgroup; its row gets nothing
+    const uint32_t cnt_in = min(a.n_paths - base, (uint32_t)THREADS);
+    if (tid < 2 + MAX_CHAIN) wg_cnt[tid] = 0;
+    const LdsScene ls = NO_LDS_SCENE;
+    const Tables tb = stage_tables_lds(a.sc, tab_lds);
+    fill_tables_lds(a.sc, tab_lds, THREADS);  // ends with the only barrier of the kernel
+
+    const bool alive = tid < cnt_in;
+    const uint32_t home = base + tid;
+    V3 o = {0, 0, 0}, d = {0, 0, 1}, thr = {1, 1, 1}, L = {0, 0, 0};
+    float eta = 1.0f, prev_pdf = -1.0f, tmax = K_INF;
+    uint32_t ka = 0, kb = 0, px = 0, py = 0;
+    if (alive) {
+        path_key<true>(a, home, &ka, &kb, &px, &py);
+        F4 uj = rng4(ka, kb, 0, a.seed);
+        float fx = (float)px + uj.x, fy = (float)py + uj.y;
+        camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
+    }
+    uint32_t keep = 0xffffffffu;  // as k_bounce: the keep word of the wave's 64 region indices
+    if (a.tile_keep) {
+        const uint32_t home0 = base + ((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u);
+        const uint32_t blk = (home0 - udiv_fast(home0, a.div_npix) * a.npix_r) >> 6;
+        keep = load_uniform<uint32_t>(a.tile_keep + min(blk, (a.npix_r >> 6) - 1u));
+    }
+    bool live = alive;
+    uint32_t nseg_w = 0, nshd_w = 0;
+    unsigned long long non_w = 0;  // paths of the wave that went on to bounce k (1 .. MAX_CHAIN - 1): 8 bits each
+    static_assert(8 * (MAX_CHAIN - 1) <= 64, "the per-bounce counts of a wave (<= 64 each) are packed 8 bits each");
+    const uint32_t nb_run = min(a.max_depth, (uint32_t)MAX_CHAIN);
+#pragma unroll 1
+    for (uint32_t depth = 0; depth < nb_run; ++depth) {
+        if (depth > 0) {
+            const uint32_t n_on = (uint32_t)__popcll(__ballot(live));
+            if (n_on == 0) break;  // uniform: every path of the wave has ended
+            non_w += (unsigned long long)n_on << (8u * (depth - 1u));
+            tmax = K_INF;
+        }
+        bool did_seg = false, did_shadow = false, survive = false;
+        if (live)
+            survive = bounce_step<ACCEL_K_BRUTE, false, false, ORD, false>(a, tb, ls, Rsrc(), depth, ka, kb, home, tmax, o, d, thr, L, eta, prev_pdf,
+                                                                           did_seg, did_shadow, nullptr, keep);
+        keep = 0xffffffffu;  // the later bounces are no camera rays
+        live = survive;
+        nseg_w += (uint32_t)__popcll(__ballot(did_seg));
+        nshd_w += (uint32_t)__popcll(__ballot(did_shadow));
+    }
+    // one record per path, 64 consecutive homes per wave
+    if (alive) {
+        typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
+        const u32x4 rec = {__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u};
+        __builtin_amdgcn_raw_buffer_store_b128(rec, make_rsrc(a.Lhome, a.cap * 16u), home * 16u, 0, 0);
+    }
+    // statistics: every wave adds its counts to the workgroup's, the last one to arrive adds those to the row (LDS atomics of one
+    // CU are ordered, as the q_done of k_bounce's chunk queue relies on); nobody waits
+    if ((tid & 63u) == 0) {
+        if (nseg_w) atomicAdd(&wg_cnt[0], nseg_w);
+        if (nshd_w) atomicAdd(&wg_cnt[1], nshd_w);
+#pragma unroll
+        for (uint32_t k = 1; k < MAX_CHAIN; ++k) {
+            const uint32_t n_on = (uint32_t)(non_w >> (8u * (k - 1u))) & 255u;
+            if (n_on) atomicAdd(&wg_cnt[1 + k], n_on);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        if (atomicAdd(&wg_cnt[1 + MAX_CHAIN], 1u) == W - 1) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            unsigned long long *row = a.stats + wg;
+            const size_t stride = a.stat_stride;
+            unsigned long long v[2 + MAX_CHAIN];
+            uint32_t add[2 + MAX_CHAIN];
+#pragma unroll
+            for (uint32_t k = 0; k < 2 + MAX_CHAIN; ++k) {  // rows 0, 1: segments, shadow rays; 2 + dpt: paths entering depth dpt
+                add[k] = k == 2 ? cnt_in : atomicAdd(&wg_cnt[k < 2 ? k : k - 1], 0u);
+                if (k < 2 + nb_run) v[k] = row[k * stride];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 2 + MAX_CHAIN; ++k)
+                if (k < 2 + nb_run) row[k * stride] = v[k] + add[k];
+        }
     }
 }
 

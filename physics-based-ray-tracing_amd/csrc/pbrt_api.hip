@@ -227,6 +227,7 @@ static hipError_t set_max_lds(K kernel, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 using RadKern = void (*)(RadArgs);
+using PathKern = void (*)(PathArgs);
 using WfKern = void (*)(WfArgs);
 using UsKern = void (*)(UsArgs);
 using UsWfKern = void (*)(UsWfArgs);
@@ -581,6 +582,22 @@ static int launch_bounce(pbrt_scene *s, const RadArgs &a, uint32_t nseg, bool fi
     const RadKern k = bounce_kernel(s, first, nb, a.sc.prim_ord != 0u);
     if (!k) return s->ctx->fail(PBRT_E_UNSUPPORTED, "launch_bounce: no fused bounce kernel for accelerator %d in this build", s->accel_kernel);
     hipLaunchKernelGGL(k, dim3(nseg), dim3(seg_threads(s->accel_kernel)), 0u, s->ctx->stream, a);
+    return PBRT_OK;
+}
+// k_path (kernels_radiance.h): the launch of a pass of camera paths whose every bounce one launch walks, for ACCEL_K_BRUTE scenes
+// (none of which is glossy: those are _BIG).  nullptr: the pass takes k_bounce.
+static PathKern path_kernel(const pbrt_scene *s, bool ordered) {
+    if (s->accel_kernel != ACCEL_K_BRUTE || s->glossy) return nullptr;
+    return with_flags([](auto O) -> PathKern { return &k_path<O() ? ACCEL_K_BRUTE_ORDERED : ACCEL_K_BRUTE, PATH_THREADS>; }, ordered);
+}
+// The launch over the nseg regions of a pass: path_groups_per_region workgroups each, one statistics row per workgroup (the rows a
+// render of such a scene has, render_launch).  No path survives it: the regions' survivor counts are cleared as k_bounce leaves them.
+static int launch_path(pbrt_scene *s, PathKern k, const RadArgs &a, uint32_t nseg) {
+    pbrt_ctx *c = s->ctx;
+    const uint32_t groups = nseg * path_groups_per_region();
+    NEED(c, a.key_mode == 0 && a.depth == 0 && a.max_depth <= MAX_CHAIN && a.stat_stride >= groups && (uint64_t)groups * PATH_THREADS <= a.cap);
+    HIPCHK(c, hipMemsetAsync(a.seg_out, 0, (size_t)nseg * 4, c->stream));
+    hipLaunchKernelGGL(k, dim3(groups), dim3(PATH_THREADS), 0u, c->stream, path_args(a));
     return PBRT_OK;
 }
 
@@ -1117,7 +1134,7 @@ static RenderLaunch render_launch(const pbrt_scene *s) {
     l.keep = k == ACCEL_K_BRUTE && s->ds.n_prims <= 32;
     l.region = rad_region_segs(k) * seg_threads(k);
     l.owners = rad_owners_per_region(k);
-    l.rows_fused = rad_rows_per_region(k);
+    l.rows_fused = k == ACCEL_K_BRUTE ? std::max(rad_rows_per_region(k), path_groups_per_region()) : rad_rows_per_region(k);  // (launch_path)
     l.rows_streams = WF_SHADE_THREADS / 64u;
     return l;
 }
@@ -1284,8 +1301,9 @@ static int render_tile_keep(Render &r) {
 // The bounce launches of the fused brute-force kernels over nseg_pass regions: the launches of the fuse plan, each walking chain_len
 // bounces, between the state sets in / out and the counters sin / sout (n_own of them).  camera: depth 0 generates its rays from the
 // film keys (else the rays are in `in` / sin).  At most `bound` bounces, whatever a.max_depth says.
+// path_ok: a launch of camera paths that walks every bounce of the pass may be k_path's (launch_path; PBRT_FILM_NO_PATH_KERNEL says no).
 static int brute_bounces(pbrt_scene *s, RadArgs a, uint32_t plan, uint32_t nseg_pass, bool camera, uint32_t bound, float *in, float *out,
-                         uint32_t *sin, uint32_t *sout, uint32_t n_own, uint32_t *launches) {
+                         uint32_t *sin, uint32_t *sout, uint32_t n_own, uint32_t *launches, bool path_ok = false) {
     pbrt_ctx *c = s->ctx;
     int rc;
     for (uint32_t depth = 0; depth < a.max_depth && depth < bound;) {
@@ -1298,7 +1316,8 @@ static int brute_bounces(pbrt_scene *s, RadArgs a, uint32_t plan, uint32_t nseg_
         a.out = out;
         a.seg_in = sin;
         a.seg_out = sout;
-        if ((rc = launch_bounce(s, a, nseg_pass, camera && depth == 0, nb)) != 0) return rc;
+        const PathKern whole = path_ok && camera && depth == 0 && nb >= a.max_depth ? path_kernel(s, a.sc.prim_ord != 0u) : nullptr;
+        if ((rc = whole ? launch_path(s, whole, a, nseg_pass) : launch_bounce(s, a, nseg_pass, camera && depth == 0, nb)) != 0) return rc;
         HIPCHK(c, hipGetLastError());
         ++*launches;
         std::swap(in, out);
@@ -1331,7 +1350,8 @@ static int brute_pass(Render &r, RadArgs a, uint32_t nseg_pass) {
     if (!in || !out) return PBRT_E_NOMEM;
     a.state_cap = (uint32_t)need;
     if (int rc = r.timer.begin()) return rc;
-    return brute_bounces(r.s, a, r.fp.plan, nseg_pass, true, PASS_MAX_BOUNCES, in, out, r.segA, r.segB, r.n_own, &r.launches);
+    return brute_bounces(r.s, a, r.fp.plan, nseg_pass, true, PASS_MAX_BOUNCES, in, out, r.segA, r.segB, r.n_own, &r.launches,
+                         !(r.f->flags & PBRT_FILM_NO_PATH_KERNEL));
 }
 
 // Pass loop: the samples in the passes of the schedule (render_request.h PassSchedule: the probe pass first, if the plan is to be
