@@ -830,6 +830,63 @@ int pbrt_capon_beamform_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const voi
 int pbrt_capon_beamform_table_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const void *d_iq, const void *d_table, const void *d_elem,
                                   const void *d_px, const void *d_pz, void *d_out);
 
+/* ---- colour and power Doppler on an ensemble of beamformed I/Q frames ----------------------------------------------
+ * replaces: ultraspy's Doppler module (apply_wall_filter, get_color_doppler_map, get_power_doppler_map; absent here as above, so this
+ * is the build's own definition, the lag-one autocorrelation estimator of Kasai et al. 1985).  frames [n_frames][nx][nz] are (re, im)
+ * float pairs, each frame an image as pbrt_iq_beamform writes it; frame n is pulse n, at slow time n / prf.  Two steps, one block.
+ *
+ * pbrt_doppler_autocorr: frames and the wall-filter basis -> acf [3][nx][nz] floats, the planes Re R1, Im R1, R0.  Per pixel, with
+ * x_n its sample in frame n, N = n_frames, all in f32:
+ *   wall (clutter) filter, the polynomial regression filter of degree d = wall_degree: y = x - Q^T (Q x).  q [d + 1][N] floats is the
+ *          caller's table, row k the k-th member of an orthonormal basis of the polynomials of degree <= d on the points 0 .. N - 1
+ *          (the library does not make it; d = 0 is mean removal).  The ensemble is first referred to its first frame, u_n = x_n - x_0
+ *          (one f32 subtraction per component): a constant lies in the span of every basis, so y does not change, but what does not
+ *          move from pulse to pulse -- the clutter the filter is there for -- is gone before anything is summed, and N identical
+ *          frames give y = 0, and so acf = 0, exactly.  Then the coefficients, each component by itself:
+ *              c_k = sum over n ascending of q[k][n] * u_n          (c = fmaf(q[k][n], u_n, c), from 0)
+ *          then, per frame, y_n = u_n minus q[k][n] * c_k over k ascending   (y = fmaf(-q[k][n], c_k, y), from u_n).
+ *          PBRT_DOPPLER_WALL_NONE: y_n = x_n, and q is not read (it may be NULL).
+ *   lag zero: r0 = sum over n ascending of |y_n|^2, r0 = fmaf(y.re, y.re, fmaf(y.im, y.im, r0)) from 0;  R0 = r0 / (float) N
+ *   lag one:  R1 = sum over n = 1 .. N - 1 ascending of y_n conj(y_{n-1}), with a = y_n, b = y_{n-1}:
+ *              re = fmaf(a.re, b.re, fmaf(a.im, b.im, re)),   im = fmaf(a.im, b.re, fmaf(-a.re, b.im, im)),   both from 0
+ *   The frames are swept twice (coefficients, then filter and correlation), once with PBRT_DOPPLER_WALL_NONE.
+ *
+ * pbrt_doppler_maps: acf -> velocity [nx][nz] and amplitude [nx][nz].  Each plane of acf is smoothed by a separable window of kx x kz
+ * pixels (both odd), hx = kx / 2, hz = kz / 2, pixels outside the image zero (a 'same' convolution), in f32:
+ *   weights w[0 .. k) of a k-point window, in f64 and rounded once to f32: PBRT_DOPPLER_BOXCAR 1 / k; PBRT_DOPPLER_HAMMING
+ *          h_i / (h_0 + h_1 + .. + h_{k-1}) (added in that order) with h_i = 0.54 - 0.46 cos(2 pi i / (k - 1)), and 1 for k = 1
+ *   along z first: t[ix][iz] = sum over j = 0 .. kz - 1 ascending of wz[j] * a[ix][iz + j - hz]    (t = fmaf(wz[j], a, t), from 0)
+ *   then along x:  s[ix][iz] = sum over i = 0 .. kx - 1 ascending of wx[i] * t[ix + i - hx][iz],   rows outside the image zero
+ *   velocity = (float) (nyquist_velocity / pi) * atan2f(s_Im, s_Re), the factor from the doubles, rounded once; a pixel whose smoothed
+ *          R1 compares equal to (0, 0) has velocity exactly 0
+ *   amplitude = sqrtf(s_R0): the root of a power, so that pbrt_log_compress of it is the power-Doppler display
+ *          (20 log10 of an amplitude = 10 log10 of a power)
+ *   A 1 x 1 window (weight 1) leaves every plane as it is, bit for bit.
+ * Sign: pbrt_rf2iq mixes with exp(-i 2 pi f t) and the beamformer turns a pixel back by the phase of its own delay, so a target that
+ * moves AWAY from the probe (its echo arrives later from pulse to pulse) gives a NEGATIVE velocity, one that moves towards it a
+ * positive one: velocity = -v_z for nyquist_velocity = c prf / (4 f), |v_z| below it.
+ * The frames must come from a pulse whose carrier moves with the target (pulse_model 'gaussian' of the acquisition); the 'impulse'
+ * model ties the carrier to absolute time, and a moving target then shifts no phase.
+ * Each step reads the fields named for it and holds only those to their rules.  PBRT_E_INVALID: a null pointer (q may be NULL with
+ * PBRT_DOPPLER_WALL_NONE only); n_frames outside [2, 64]; wall_degree neither PBRT_DOPPLER_WALL_NONE nor <= 3, or wall_degree + 1 >=
+ * n_frames; kx or kz even or outside [1, 15]; an unknown window; nyquist_velocity not finite or <= 0; n_frames * nx * nz, nx * nz or a
+ * grid dimension outside 32 bits; input and output overlapping.  nx * nz == 0 does nothing.  The _dev forms take device pointers (q
+ * included), are queued on the context's stream and recordable like their neighbours. */
+#define PBRT_DOPPLER_WALL_NONE 0xffffffffu
+#define PBRT_DOPPLER_BOXCAR 0u
+#define PBRT_DOPPLER_HAMMING 1u
+typedef struct pbrt_doppler_params {
+    uint32_t n_frames, nx, nz; /* the ensemble [n_frames][nx][nz]; n_frames is read by pbrt_doppler_autocorr only */
+    uint32_t wall_degree;      /* autocorr: 0 .. 3, or PBRT_DOPPLER_WALL_NONE */
+    uint32_t kx, kz;           /* maps: the smoothing window in pixels, odd, 1 .. 15 */
+    uint32_t window;           /* maps: PBRT_DOPPLER_BOXCAR / PBRT_DOPPLER_HAMMING */
+    float nyquist_velocity;    /* maps: m/s, finite and > 0: the velocity of a phase step of pi between two pulses */
+} pbrt_doppler_params;
+int pbrt_doppler_autocorr(pbrt_ctx *ctx, const pbrt_doppler_params *p, const float *frames, const float *q, float *acf);
+int pbrt_doppler_autocorr_dev(pbrt_ctx *ctx, const pbrt_doppler_params *p, const void *d_frames, const void *d_q, void *d_acf);
+int pbrt_doppler_maps(pbrt_ctx *ctx, const pbrt_doppler_params *p, const float *acf, float *velocity, float *amplitude);
+int pbrt_doppler_maps_dev(pbrt_ctx *ctx, const pbrt_doppler_params *p, const void *d_acf, void *d_velocity, void *d_amplitude);
+
 /* waits for everything queued on the context's stream */
 int pbrt_ctx_synchronize(pbrt_ctx *ctx);
 /* Device buffers for a caller without a GPU library of its own (the reference's driver is NumPy: USMain.py:103-121).
@@ -875,7 +932,7 @@ int pbrt_ctx_tile_keep(pbrt_ctx *ctx, pbrt_tile_keep_info *info, uint32_t *words
  * pbrt_rf2iq_dev, pbrt_iq_beamform_dev, pbrt_iq_beamform_table_dev, pbrt_iq_envelope_dev,
  * pbrt_scan_beamform_dev, pbrt_scan_beamform_table_dev, pbrt_scan_first_arrival_dev, pbrt_scan_convert_dev,
  * pbrt_apod_beamform_dev, pbrt_apod_beamform_table_dev, pbrt_capon_beamform_dev, pbrt_capon_beamform_table_dev,
- * pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
+ * pbrt_doppler_autocorr_dev, pbrt_doppler_maps_dev, pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
  * stream instead of run; pbrt_graph_launch replays the recording in one submission and returns without waiting, exactly as if
  * the recorded calls had just been made: same kernels, same arguments, same results bit for bit, the acquisition's statistics
  * arrive with the next call that waits (kernel_ms / bounce_ms are 0: a replay carries no event pairs).

@@ -31,6 +31,8 @@ from .beamform import (Capon, DelayAndSum, FilteredDelayMultiplyAndSum, GridScan
                        bandpass_taps, build_probe, capon_beamform, das_beamform, das_first_arrival, envelope, iq_beamform, iq_envelope, log_compress,
                        lowpass_taps, nonlinear_beamform, polar_n_theta, rf2iq, scan_beamform, scan_convert, scan_first_arrival,
                        us_render)
+from .beamform import (doppler_autocorr, doppler_maps, doppler_render, get_color_doppler_map, get_power_doppler_map,
+                       nyquist_velocity, wall_basis)
 
 # NB: the receive-side accumulator class `CustomSensor` is reached as pbrt_amd.CustomSensor.CustomSensor (module of
 # the same name, like the reference's CustomSensor.py) or pbrt_amd.plugins.CustomSensor.

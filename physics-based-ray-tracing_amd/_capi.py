@@ -176,6 +176,17 @@ class CaponParams(C.Structure):
 CAPON_MAX_L, CAPON_MAX_E = 32, 256
 
 
+class DopplerParams(C.Structure):
+    """pbrt_doppler_params: the one block of the two Doppler steps (DESIGN D24)"""
+    _fields_ = [("n_frames", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32), ("wall_degree", C.c_uint32), ("kx", C.c_uint32),
+                ("kz", C.c_uint32), ("window", C.c_uint32), ("nyquist_velocity", C.c_float)]
+
+
+DOPPLER_WALL_NONE = 0xFFFFFFFF
+DOPPLER_BOXCAR, DOPPLER_HAMMING = 0, 1
+DOPPLER_MAX_FRAMES, DOPPLER_MAX_DEGREE, DOPPLER_MAX_K = 64, 3, 15
+
+
 class ScanConvertParams(C.Structure):
     _fields_ = [("n_theta", C.c_uint32), ("n_rho", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32), ("theta0", C.c_double),
                 ("dtheta", C.c_double), ("rho0", C.c_double), ("drho", C.c_double), ("ox", C.c_double), ("oz", C.c_double),
@@ -277,6 +288,11 @@ SIGNATURES = {
     "pbrt_capon_beamform": (C.c_int, [_P, C.POINTER(CaponParams), _F, _F, _F, _F, _F, _F]),
     "pbrt_capon_beamform_dev": (C.c_int, [_P, C.POINTER(CaponParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_capon_beamform_table_dev": (C.c_int, [_P, C.POINTER(CaponParams), _P, _P, _P, _P, _P, _P]),
+    # colour and power Doppler on an ensemble of I/Q frames (DESIGN D24)
+    "pbrt_doppler_autocorr": (C.c_int, [_P, C.POINTER(DopplerParams), _F, _F, _F]),
+    "pbrt_doppler_autocorr_dev": (C.c_int, [_P, C.POINTER(DopplerParams), _P, _P, _P]),
+    "pbrt_doppler_maps": (C.c_int, [_P, C.POINTER(DopplerParams), _F, _F, _F]),
+    "pbrt_doppler_maps_dev": (C.c_int, [_P, C.POINTER(DopplerParams), _P, _P, _P]),
     "pbrt_scan_convert": (C.c_int, [_P, C.POINTER(ScanConvertParams), _F, _F, _F, _F]),
     "pbrt_scan_convert_dev": (C.c_int, [_P, C.POINTER(ScanConvertParams), _P, _P, _P, _P]),
     "pbrt_ctx_synchronize": (C.c_int, [_P]),
@@ -552,7 +568,26 @@ class DeviceBuffer:
         self.ctx.check(self.ctx.lib.pbrt_dev_download(self.ctx.handle, addr(out), _P(self.ptr), C.c_uint64(self.nbytes)), "pbrt_dev_download")
         return out
 
+    def view(self, offset: int, shape, dtype=None) -> "DeviceBuffer":
+        """A non-owning view of a contiguous part of this buffer: `shape` elements of `dtype` (default: this buffer's) starting
+        `offset` elements of that dtype in -- frame n of an ensemble [N, nx, nz] is ens.view(n * nx * nz, (nx, nz)), and can be the
+        `out=` of a beamform call.  The view keeps its parent alive and never frees; ValueError where it would leave the buffer."""
+        v = object.__new__(DeviceBuffer)
+        v.ctx = self.ctx
+        v.shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        v.dtype = np.dtype(self.dtype if dtype is None else dtype)
+        v.nbytes = int(np.prod(v.shape, dtype=np.int64)) * v.dtype.itemsize
+        start = int(offset) * v.dtype.itemsize
+        if self.ptr is None or int(offset) < 0 or min(v.shape, default=0) < 0 or start + v.nbytes > self.nbytes:
+            raise ValueError(f"a view of {v.nbytes} bytes at byte {start} does not lie inside a buffer of {self.nbytes}")
+        v.parent = self
+        v.ptr = self.ptr + start
+        return v
+
     def close(self):
+        if getattr(self, "parent", None) is not None:   # a view: the memory is its parent's
+            self.ptr = self.parent = None
+            return
         if getattr(self, "ptr", None) and getattr(self.ctx, "handle", None):
             self.ctx.lib.pbrt_dev_free(self.ctx.handle, _P(self.ptr))
         self.ptr = None

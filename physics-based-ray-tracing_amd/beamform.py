@@ -760,6 +760,55 @@ class DelayAndSum:
         is_iq: complex64 in (host, or a complex DeviceBuffer), complex out."""
         return self._request(self._checked(d_data), scan, out, table)
 
+    def beamform_packet(self, d_data, scan, out=None):
+        """An ensemble of pulses, one image per frame (DESIGN D24; ultraspy's packet beamforming from memory, parity unpinned): host
+        data [frames, n_angles, n_elements, T] complex64 -> a host array [frames, nx, nz] complex64; a list of complex DeviceBuffers
+        [n_angles, n_elements, T] -> a complex DeviceBuffer [frames, nx, nz] (`out`, or a new one), queued.  The first-arrival table
+        of the scan is made once and every frame goes through the _table_dev entry point of this beamformer into its part of the
+        ensemble (DeviceBuffer.view): frame n equals beamform() of that frame bit for bit.  I/Q data only: ValueError without is_iq."""
+        if self.acquisition_info is None or self.probe is None:
+            raise RuntimeError(f"{type(self).__name__}.automatic_setup(acquisition_info, probe) has not been called")
+        if not self.is_iq:
+            raise ValueError(f"{type(self).__name__}.beamform_packet takes I/Q data: set_is_iq(True) and demodulate the frames (rf2iq)")
+        host = not isinstance(d_data, (list, tuple))
+        if host:
+            data = np.asarray(d_data)
+            if data.ndim != 4:
+                raise ValueError(f"beamform_packet takes [frames, n_angles, n_elements, T], got {list(data.shape)}")
+            _check_iq(self, data)
+            cx = _capi.default_context()
+            frames = [_capi.DeviceBuffer.from_host(cx, np.ascontiguousarray(f, dtype=np.complex64)) for f in data]
+        else:
+            frames = list(d_data)
+            if not all(_is_dev(f) for f in frames):
+                raise ValueError("beamform_packet takes a host array, or a list of DeviceBuffers")
+            for f in frames:
+                _check_iq(self, f)
+        if not frames or any(tuple(f.shape) != tuple(frames[0].shape) or f.ctx is not frames[0].ctx for f in frames):
+            raise ValueError("beamform_packet needs one frame at least, all of one shape and on one context")
+        cx, N, (n0, n1) = frames[0].ctx, len(frames), scan.shape
+        ens = out if out is not None else _capi.DeviceBuffer(cx, (N, n0, n1), np.complex64)
+        if not _is_dev(ens) or ens.nbytes != N * n0 * n1 * 8:
+            raise ValueError("out must be a DeviceBuffer that holds frames * nx * nz complex64")
+        ai = self.acquisition_info
+        polar, gx, gz = _scan_tables(scan, True)
+        table = _first_arrival(ai["delays"], self.probe_dev if self.probe_dev is not None else self.probe.das_elements, gx, gz, polar,
+                               ai["sound_speed"], None)
+        # the small tables the table's kernel read sit in HBM now: every frame's call takes them from there
+        d_tx, d_ex, d_gx, d_gz = table._keep
+        names = ("d_px", "d_pz") if polar else ("d_x", "d_z")
+        saved = (self.acquisition_info, self.probe_dev, getattr(scan, names[0], None), getattr(scan, names[1], None))
+        self.acquisition_info, self.probe_dev = dict(ai, delays=d_tx), d_ex
+        setattr(scan, names[0], d_gx), setattr(scan, names[1], d_gz)
+        try:
+            for n, f in enumerate(frames):
+                self._request(f, scan, ens.view(n * n0 * n1, (n0, n1)), table)
+        finally:
+            self.acquisition_info, self.probe_dev = saved[0], saved[1]
+            setattr(scan, names[0], saved[2]), setattr(scan, names[1], saved[3])
+        ens._keep = (tuple(frames), table)
+        return ens.numpy() if host else ens
+
     def compute_envelope(self, d_output, scan=None, out=None):
         if self.is_iq:
             return iq_envelope(d_output, out=out)
@@ -1241,3 +1290,237 @@ def us_render(scene, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), dynamic_range
     if timing is not None:
         timing.update(acquire=t1 - t0, queue=t2 - t1, wait_copy=0.0 if on_device else time.perf_counter() - t2, replayed=replayed)
     return display, bmode, (rq.x_scan, rq.z_scan)
+
+
+# ---- colour and power Doppler on an ensemble of I/Q frames (DESIGN D24, include/pbrt_hip.h) -----------------------------------------
+# `ultraspy` is absent, as everywhere in this file: the names follow its Doppler module from memory (apply_wall_filter,
+# get_color_doppler_map, get_power_doppler_map), the arithmetic is this build's own definition and parity with it is unpinned.
+DOPPLER_MAX_FRAMES, DOPPLER_MAX_DEGREE, DOPPLER_MAX_K = _capi.DOPPLER_MAX_FRAMES, _capi.DOPPLER_MAX_DEGREE, _capi.DOPPLER_MAX_K
+_SMOOTHING = {"boxcar": _capi.DOPPLER_BOXCAR, "hamming": _capi.DOPPLER_HAMMING}
+
+
+def nyquist_velocity(sound_speed, prf, demod_freq) -> float:
+    """c prf / (4 f): the axial velocity whose echo turns by pi between two pulses, the largest a colour map can tell from its alias"""
+    c, prf, f = float(sound_speed), float(prf), float(demod_freq)
+    if not (math.isfinite(c * prf / f if f else math.nan) and c > 0.0 and prf > 0.0 and f > 0.0):
+        raise ValueError(f"nyquist_velocity needs sound_speed, prf and demod_freq finite and > 0, got {sound_speed}, {prf}, {demod_freq}")
+    return c * prf / (4.0 * f)
+
+
+def _checked_ensemble_length(n_frames) -> int:
+    N = int(n_frames)
+    if N != n_frames or not 2 <= N <= DOPPLER_MAX_FRAMES:
+        raise ValueError(f"an ensemble has 2 to {DOPPLER_MAX_FRAMES} frames, got {n_frames}")
+    return N
+
+
+def _wall_degree(wall_filter, degree, N):
+    """the degree of the polynomial regression filter a call names, None for "none"; ValueError for what the library would refuse"""
+    if wall_filter not in ("none", "mean", "poly"):
+        raise ValueError(f"wall_filter must be 'none', 'mean' or 'poly', got {wall_filter!r}")
+    if wall_filter == "none":
+        return None
+    d = 0 if wall_filter == "mean" else degree
+    if isinstance(d, bool) or int(d) != d or not 0 <= int(d) <= DOPPLER_MAX_DEGREE:
+        raise ValueError(f"the degree of the wall filter must be an integer in [0, {DOPPLER_MAX_DEGREE}], got {degree!r}")
+    if int(d) + 1 >= N:
+        raise ValueError(f"a wall filter of degree {int(d)} leaves nothing of {N} frames: degree + 1 < frames is required")
+    return int(d)
+
+
+def wall_basis(n_frames, degree) -> np.ndarray:
+    """The table pbrt_doppler_autocorr takes: float32 [degree + 1, n_frames], row k the k-th member of the orthonormal basis of the
+    polynomials of degree <= `degree` on the slow-time points 0 .. n_frames - 1 (row 0 constant; the leading coefficient of every row
+    positive), made in float64 -- a QR factorisation of the centred Vandermonde matrix -- and rounded once.  The wall filter is
+    y = x - Q^T (Q x); degree 0 is mean removal."""
+    N = _checked_ensemble_length(n_frames)
+    d = _wall_degree("poly", degree, N)
+    t = (np.arange(N, dtype=np.float64) - (N - 1) / 2.0) / ((N - 1) / 2.0)
+    q, r = np.linalg.qr(np.vander(t, d + 1, increasing=True))
+    return np.ascontiguousarray((q * np.sign(np.diag(r))[None, :]).T.astype(np.float32))
+
+
+def _wall_basis_dev(cx, N, d):
+    """wall_basis(N, d) in HBM, uploaded once per context: a queued call neither allocates nor waits"""
+    cache = cx.__dict__.setdefault("_wall_basis_dev", {})
+    if (N, d) not in cache:
+        cache[(N, d)] = _capi.DeviceBuffer.from_host(cx, wall_basis(N, d))
+    return cache[(N, d)]
+
+
+def _checked_smoothing(smoothing, kernel):
+    if smoothing not in _SMOOTHING:
+        raise ValueError(f"smoothing must be one of {tuple(_SMOOTHING)}, got {smoothing!r}")
+    try:
+        kx, kz = kernel
+        ok = all(not isinstance(k, bool) and int(k) == k and 1 <= int(k) <= DOPPLER_MAX_K and int(k) % 2 == 1 for k in (kx, kz))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"kernel must be two odd sizes (kx, kz) in [1, {DOPPLER_MAX_K}], got {kernel!r}")
+    return _SMOOTHING[smoothing], int(kx), int(kz)
+
+
+def _checked_ensemble(frames):
+    """an ensemble [frames, nx, nz] as the autocorrelation takes it: a complex DeviceBuffer, or a host array as complex64"""
+    if _is_dev(frames):
+        if frames.dtype.kind != "c":
+            raise ValueError(f"the ensemble must be complex64 (beamformed I/Q frames), got a {frames.dtype} DeviceBuffer")
+    elif not np.iscomplexobj(frames):
+        raise ValueError("the ensemble must be complex (beamformed I/Q frames)")
+    else:
+        frames = np.ascontiguousarray(frames, dtype=np.complex64)
+    if len(frames.shape) != 3:
+        raise ValueError(f"the ensemble must be [frames, nx, nz], got {list(frames.shape)}")
+    _checked_ensemble_length(frames.shape[0])
+    return frames
+
+
+def doppler_autocorr(frames, wall_filter="none", degree=1, out=None):
+    """Slow-time autocorrelation of an ensemble frames [N, nx, nz] complex64 (frame n = pulse n; beamform_packet makes one) ->
+    acf [3, nx, nz] float32, the planes Re R1, Im R1 and R0 (pbrt_doppler_autocorr, DESIGN D24): R1 = sum_n y[n + 1] conj(y[n]),
+    R0 = mean |y[n]|^2 of the wall-filtered samples y.  wall_filter: "none", "mean" (the slow-time mean is removed: ultraspy's 'mean')
+    or "poly" (the polynomial regression filter of `degree` 0 .. 3; degree + 1 < N).  The filter is part of this step and not one of
+    its own (ultraspy's apply_wall_filter): the filtered ensemble is never written.  A host array in gives a host array out; a complex
+    DeviceBuffer in gives a DeviceBuffer out (`out`, or a new one), queued."""
+    frames = _checked_ensemble(frames)
+    N, nx, nz = (int(v) for v in frames.shape)
+    d = _wall_degree(wall_filter, degree, N)
+    par = _capi.DopplerParams()
+    par.n_frames, par.nx, par.nz = N, nx, nz
+    par.wall_degree = _capi.DOPPLER_WALL_NONE if d is None else d
+    par.kx = par.kz = 1
+    par.window, par.nyquist_velocity = _capi.DOPPLER_BOXCAR, 1.0
+    q = None if d is None else _wall_basis_dev(frames.ctx, N, d) if _is_dev(frames) else wall_basis(N, d)
+    return _step("pbrt_doppler_autocorr", frames, (C.byref(par), frames, q), (3, nx, nz), np.float32, out, "out must hold 3 * nx * nz float32")
+
+
+def doppler_maps(acf, nyquist_velocity, smoothing="hamming", kernel=(1, 1), out=None):
+    """acf [3, nx, nz] (doppler_autocorr) -> (velocity [nx, nz], amplitude [nx, nz]) float32 (pbrt_doppler_maps, DESIGN D24): the
+    three planes smoothed by a separable `smoothing` window ("boxcar" / "hamming") of kernel = (kx, kz) pixels, odd and at most 15,
+    zero outside the image; velocity = nyquist_velocity * arg(R1) / pi -- NEGATIVE for a target that moves away from the probe --
+    and amplitude = sqrt(R0).  A host array in gives host arrays out; a DeviceBuffer in gives DeviceBuffers out (`out` = (velocity,
+    amplitude), or new ones), queued."""
+    window, kx, kz = _checked_smoothing(smoothing, kernel)
+    nyq = float(nyquist_velocity)
+    if not (math.isfinite(nyq) and nyq > 0.0):
+        raise ValueError(f"nyquist_velocity must be finite and > 0, got {nyquist_velocity!r}")
+    dev = _is_dev(acf)
+    if not dev:
+        acf = _capi.f32(np.asarray(acf))
+    if len(acf.shape) != 3 or acf.shape[0] != 3 or (dev and acf.dtype != np.float32):
+        raise ValueError(f"acf must be float32 [3, nx, nz], got {acf.dtype} {list(acf.shape)}")
+    nx, nz = int(acf.shape[1]), int(acf.shape[2])
+    par = _capi.DopplerParams()
+    par.n_frames, par.nx, par.nz, par.wall_degree = 2, nx, nz, _capi.DOPPLER_WALL_NONE
+    par.kx, par.kz, par.window, par.nyquist_velocity = kx, kz, window, nyq
+    if not dev:
+        cx, vel, amp = _capi.default_context(), np.empty((nx, nz), np.float32), np.empty((nx, nz), np.float32)
+        cx.check(cx.lib.pbrt_doppler_maps(cx.handle, C.byref(par), acf.ctypes.data, vel.ctypes.data, amp.ctypes.data), "pbrt_doppler_maps")
+        return vel, amp
+    cx = acf.ctx
+    vel, amp = out if out is not None else (_capi.DeviceBuffer(cx, (nx, nz)), _capi.DeviceBuffer(cx, (nx, nz)))
+    if not (_is_dev(vel) and _is_dev(amp)) or vel.nbytes != nx * nz * 4 or amp.nbytes != nx * nz * 4:
+        raise ValueError("out must be two DeviceBuffers that hold nx * nz float32 each")
+    cx.check(cx.lib.pbrt_doppler_maps_dev(cx.handle, C.byref(par), acf.ptr, vel.ptr, amp.ptr), "pbrt_doppler_maps_dev")
+    vel._keep = amp._keep = (acf,)
+    return vel, amp
+
+
+def get_color_doppler_map(frames, nyquist_velocity, wall_filter="none", degree=1, smoothing="hamming", kernel=(1, 1)):
+    """Colour-flow velocity map [nx, nz] (m/s) of an ensemble frames [N, nx, nz] complex64: doppler_autocorr, then doppler_maps.
+    nyquist_velocity: nyquist_velocity(sound_speed, prf, demod_freq).  Negative: away from the probe.  Host in, host out; a
+    DeviceBuffer in gives a DeviceBuffer out, queued."""
+    _checked_smoothing(smoothing, kernel)
+    return doppler_maps(doppler_autocorr(frames, wall_filter, degree), nyquist_velocity, smoothing, kernel)[0]
+
+
+def get_power_doppler_map(frames, wall_filter="none", degree=1, smoothing="hamming", kernel=(1, 1), dynamic_range=None):
+    """Power-Doppler map [nx, nz] of an ensemble: the amplitude sqrt(R0) of the wall-filtered, smoothed lag-zero autocorrelation; with
+    dynamic_range (dB) the display log_compress makes of it -- 20 log10 of an amplitude is 10 log10 of a power -- in [0, 1].  It does
+    not depend on a velocity scale, so it takes none.  Host in, host out; a DeviceBuffer in gives a DeviceBuffer out, queued."""
+    _checked_smoothing(smoothing, kernel)
+    amp = doppler_maps(doppler_autocorr(frames, wall_filter, degree), 1.0, smoothing, kernel)[1]
+    return amp if dynamic_range is None else log_compress(amp, dynamic_range)
+
+
+def _acquisition_key(integ, scene):
+    """everything of an integrator that an acquisition and its pulse read"""
+    return (bytes(integ.us_params(scene, integ.quirks)), int(integ.seed), int(integ.paths_per_ray), integ.pulse_model,
+            float(integ.pulse_sigma), float(integ.fs))
+
+
+def _doppler_render_request(scenes, prf, x_range, z_range, step, seed, paths_per_ray, decimation, beamformer, wall_filter, degree,
+                            smoothing, kernel, dynamic_range):
+    """the checks of doppler_render, all of them before any device work -> (scenes, the us_render request of the first scene's
+    integrator with the I/Q chain on, the wall filter's degree, nyquist velocity)"""
+    scenes = list(scenes)
+    if len(scenes) < 2:
+        raise ValueError(f"doppler_render needs an ensemble of two scenes at least (one per pulse), got {len(scenes)}")
+    N = _checked_ensemble_length(len(scenes))
+    integs = [s.integrator() for s in scenes]
+    if any(getattr(i, "pulse_model", None) != "gaussian" for i in integs):
+        raise ValueError("doppler_render needs pulse_model='gaussian': the 'impulse' model deposits sin(2 pi f t) at the absolute "
+                         "arrival time t, so its carrier is tied to absolute time and a moving target shifts no phase from pulse to pulse")
+    key = _acquisition_key(integs[0], scenes[0])
+    for n in range(1, N):
+        if _acquisition_key(integs[n], scenes[n]) != key:
+            raise ValueError(f"doppler_render: the integrator of scene {n} differs from that of scene 0 in something an acquisition reads "
+                             "(array, angles, sampling, frequency, sensor, quirks, seed, paths_per_ray or pulse): only the geometry may move")
+    if not (math.isfinite(float(prf)) and float(prf) > 0.0):
+        raise ValueError(f"doppler_render: prf must be finite and > 0, got {prf!r}")
+    d = _wall_degree(wall_filter, degree, N)
+    _checked_smoothing(smoothing, kernel)
+    integ = integs[0]
+    step = step or integ.sound_speed / integ.frequency / 2
+    rq = _us_render_request(integ, x_range, z_range, dynamic_range, step, seed, paths_per_ray, beamformer, True, decimation, "grid", None)
+    return scenes, rq, d, nyquist_velocity(integ.sound_speed, prf, rq.f_demod)
+
+
+def doppler_render(scenes, prf, x_range=(-0.04, 0.04), z_range=(0.001, 0.05), step=None, seed=None, paths_per_ray=None, decimation=1,
+                   beamformer=None, wall_filter="none", degree=1, smoothing="hamming", kernel=(1, 1), dynamic_range=60.0,
+                   on_device=False, buffers=None):
+    """Colour and power Doppler of a moving scene, beside us_render (DESIGN D24).  scenes: N scenes, 2 <= N <= 64, one per pulse at the
+    pulse repetition frequency prf -- a sequence, because geometry cannot be updated in place (only materials can: Scene.device()).
+    Per scene: acquisition -> pulse -> rf2iq (decimated by `decimation`) -> I/Q beamform (`beamformer`: a DelayAndSum or Capon, as
+    us_render(iq=True) takes it) into frame n of the ensemble, every pulse with the SAME seed (common random numbers: between two
+    pulses only the echoes of what moved change) and one first-arrival table; then doppler_autocorr(wall_filter, degree),
+    doppler_maps(smoothing, kernel) with nyquist_velocity(c, prf, f) and the log compression of the amplitude.  Everything is queued
+    on the context's stream; one copy per returned image.  The default step is lambda / 2.
+    -> (velocity [nz, nx] in m/s, negative away from the probe; power display [nz, nx] in [0, 1]; (x, z)).  on_device: the two images
+    come back as DeviceBuffers [nx, nz], still being written.  buffers: a dict that receives "frames" (the ensemble [N, nx, nz]
+    complex64), "acf" and "amplitude" as DeviceBuffers.
+    ValueError, before any device work: fewer than 2 scenes; integrators that differ in anything an acquisition reads; and
+    pulse_model='impulse' -- its carrier is tied to absolute time, so a moving target shifts no phase.  Replaying the chain from a
+    recording, as us_render does, is not built."""
+    scenes, rq, d, nyq = _doppler_render_request(scenes, prf, x_range, z_range, step, seed, paths_per_ray, decimation, beamformer,
+                                                 wall_filter, degree, smoothing, kernel, dynamic_range)
+    integ, N = rq.integ, len(scenes)
+    cx = scenes[0].device().ctx
+    key = (rq.plan_key(cx), N)
+    plan = getattr(integ, "_doppler_plan", None)
+    if plan is None or plan.key != key:
+        plan = integ._doppler_plan = _RenderPlan(cx, rq, key)
+        nx, nz = rq.scan.shape
+        plan.d_frames = _capi.DeviceBuffer(cx, (N, nx, nz), np.complex64)
+        plan.d_acf = _capi.DeviceBuffer(cx, (3, nx, nz))
+        plan.d_vel, plan.d_amp = _capi.DeviceBuffer(cx, (nx, nz)), _capi.DeviceBuffer(cx, (nx, nz))
+    plan.bind(rq)
+    nx, nz = rq.scan.shape
+    sd = int(integ.seed if rq.seed is None else rq.seed)
+    for n, scene in enumerate(scenes):
+        it = scene.integrator()
+        it._acquire(scene, it.quirks, paths_per_ray=rq.paths_per_ray, seed=sd, out_dev=plan.d_channel.ptr, pulse=False, queue=True)
+        plan.refresh_delays(np.asarray(it.transmission_delays_buf, dtype=np.float32).reshape(rq.A, rq.E), integ.sound_speed)
+        data = apply_pulse(plan.d_channel, integ.fs, integ.frequency, integ.pulse_sigma, out=plan.d_rf)
+        rq.bf.automatic_setup(rq.info(plan.d_tx), rq.probe)
+        data = rf2iq(data, rq.f_demod, integ.fs, decimation=rq.D, taps=plan.d_iq_taps, out=plan.d_iq)
+        rq.bf.beamform(data, rq.scan, out=plan.d_frames.view(n * nx * nz, (nx, nz)), table=plan.d_table)
+    doppler_autocorr(plan.d_frames, wall_filter, degree, out=plan.d_acf)
+    doppler_maps(plan.d_acf, nyq, smoothing, kernel, out=(plan.d_vel, plan.d_amp))
+    log_compress(plan.d_amp, rq.dynamic_range, out=plan.d_img)
+    if buffers is not None:
+        buffers.update(frames=plan.d_frames, acf=plan.d_acf, amplitude=plan.d_amp)
+    if on_device:
+        return plan.d_vel, plan.d_img, (rq.x_scan, rq.z_scan)
+    return plan.d_vel.numpy().T, plan.d_img.numpy().T, (rq.x_scan, rq.z_scan)

@@ -7,6 +7,7 @@
 #include "bf_request.h"
 #include "capon_request.h"  // the limits of Capon and the subarray rule: CAPON_MAX_L, CAPON_MAX_E, capon_lm
 #include "img_request.h" // the limits of the image steps: FIR_MAX_K, RF2IQ_MAX_D, ENV_MAX_N, ENV_MAX_BLOCKS, PULSE_MAX_K, env_even_len
+#include "doppler_request.h"  // the limits, the tile and the weights of the Doppler steps: DOPPLER_*, DopplerWeights
 #include "device_math.h"
 
 // ---- delay and sum --------------------------------------------------------------------------------------------------------
@@ -1135,4 +1136,130 @@ __global__ __launch_bounds__(256) void k_apply_pulse(uint32_t T, uint32_t K, flo
         // phase reduced per cycle: sin(2 pi fc t) = sinpi(2 fc t)
         return sinpif(2.0f * fc * t) * expf(-(t * t) / (sigma * sigma));
     });
+}
+
+// ---- colour and power Doppler (DESIGN D24, include/pbrt_hip.h) ----------------------------------------------------------------------
+// Slow-time autocorrelation of an ensemble frames[N][P] of beamformed I/Q pixels (P = nx nz pairs per frame) -> acf[3][P], the planes
+// Re R1, Im R1 and R0.  NC: the coefficients of the polynomial regression (wall) filter, 0 = none, else degree + 1; q [NC][N] is the
+// orthonormal basis the host made, read at one address by every lane (scalar loads).  Per pixel, in the order the header states:
+//   u_n = x_n - x_0 (NC > 0);   c_k = sum_n q[k][n] u_n (n ascending, one fmaf per component);   y_n = u_n - sum_k q[k][n] c_k (k
+//   ascending, fmaf of -q);
+//   r0 = fmaf(y.x, y.x, fmaf(y.y, y.y, r0)) over n, R0 = r0 / N;   R1 += y_n conj(y_{n-1}) for n = 1 .. N - 1, two fmaf per component.
+// The two-pass form: the filtered samples are never kept -- a sweep for the NC complex coefficients, a second one that subtracts and
+// correlates with the previous filtered sample in two registers -- so the registers do not depend on N.  One thread per pixel: a wave
+// reads 512 consecutive bytes of a frame per load; 8 N bytes per pixel in (the second sweep mostly from L2), 12 out.
+template <int NC>
+__global__ __launch_bounds__(256) void k_doppler_autocorr(uint32_t N, uint32_t P, const float2 *__restrict__ frames,
+                                                          const float *__restrict__ q, float *__restrict__ acf) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P) return;
+    const float2 *x = frames + i;
+    float cr[NC ? NC : 1], ci[NC ? NC : 1];
+    const float2 x0 = NC > 0 ? x[0] : make_float2(0.0f, 0.0f);  // the filter works on x_n - x_0: what does not move is gone before anything is summed
+    if constexpr (NC > 0) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) cr[k] = ci[k] = 0.0f;
+        for (uint32_t n = 0; n < N; ++n) {
+            const float2 s = x[(size_t)n * P];
+            const float sx = s.x - x0.x, sy = s.y - x0.y;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                const float w = q[(uint32_t)k * N + n];
+                cr[k] = fma_(w, sx, cr[k]);
+                ci[k] = fma_(w, sy, ci[k]);
+            }
+        }
+    }
+    const auto filtered = [&](uint32_t n) {
+        float2 y = x[(size_t)n * P];
+        if constexpr (NC > 0) {
+            y.x -= x0.x;
+            y.y -= x0.y;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                const float w = q[(uint32_t)k * N + n];
+                y.x = fma_(-w, cr[k], y.x);
+                y.y = fma_(-w, ci[k], y.y);
+            }
+        }
+        return y;
+    };
+    float2 prev = filtered(0);
+    float r0 = fma_(prev.x, prev.x, fma_(prev.y, prev.y, 0.0f)), re = 0.0f, im = 0.0f;
+    for (uint32_t n = 1; n < N; ++n) {
+        const float2 y = filtered(n);
+        r0 = fma_(y.x, y.x, fma_(y.y, y.y, r0));
+        re = fma_(y.x, prev.x, fma_(y.y, prev.y, re));
+        im = fma_(y.y, prev.x, fma_(-y.x, prev.y, im));
+        prev = y;
+    }
+    acf[i] = re;
+    acf[(size_t)P + i] = im;
+    acf[2 * (size_t)P + i] = r0 / (float)N;
+}
+
+// acf[3][nx][nz] -> velocity[nx][nz], amplitude[nx][nz]: every plane smoothed by the separable window W (kx x kz, odd, zero outside the
+// image), along z first and then along x, one fmaf per tap in ascending order; velocity = scale atan2f(Im, Re) (exactly 0 where the
+// smoothed R1 is zero), amplitude = sqrtf(R0).  A workgroup makes a tile of DOPPLER_TILE_X x DOPPLER_TILE_Z pixels (8 rows of 32 along
+// z, a thread per pixel): the three planes of the tile with its halo are staged in LDS, [rows][cols] = [8 + kx - 1][32 + kz - 1], the
+// z-smoothed rows go to a second LDS array [rows][32], and the sum along x reads that.  Dynamic LDS, doppler_maps_lds(kx, kz) bytes:
+// the weights (2 x 16 floats), then the two arrays.  12 bytes per pixel in (times the halo's share), 8 out.
+__global__ __launch_bounds__(256) void k_doppler_maps(uint32_t nx, uint32_t nz, uint32_t kx, uint32_t kz, uint32_t tiles_z, float scale,
+                                                      DopplerWeights W, const float *__restrict__ acf, float *__restrict__ velocity,
+                                                      float *__restrict__ amplitude) {
+    extern __shared__ __attribute__((aligned(16))) float lds_dop[];
+    const uint32_t rows = DOPPLER_TILE_X + (kx - 1u), cols = DOPPLER_TILE_Z + (kz - 1u), hx = kx >> 1, hz = kz >> 1;
+    const uint32_t plane_in = rows * cols, plane_t = rows * DOPPLER_TILE_Z;
+    float *wx = lds_dop, *wz = lds_dop + (DOPPLER_MAX_K + 1u);
+    float *in = lds_dop + 2u * (DOPPLER_MAX_K + 1u);  // [3][rows][cols]
+    float *t = in + 3u * plane_in;                    // [3][rows][DOPPLER_TILE_Z]
+    const uint32_t tile_x = blockIdx.x / tiles_z, tile_z = blockIdx.x - tile_x * tiles_z;
+    const uint32_t x0 = tile_x * DOPPLER_TILE_X, z0 = tile_z * DOPPLER_TILE_Z;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (uint32_t i = 0; i < DOPPLER_MAX_K; ++i) {
+            wx[i] = W.wx[i];
+            wz[i] = W.wz[i];
+        }
+    }
+    const size_t P = (size_t)nx * nz;
+    for (uint32_t i = threadIdx.x; i < plane_in; i += 256u) {
+        const uint32_t r = i / cols, c = i - r * cols;
+        const int64_t gx = (int64_t)x0 + r - hx, gz = (int64_t)z0 + c - hz;
+        const bool inside = gx >= 0 && gx < (int64_t)nx && gz >= 0 && gz < (int64_t)nz;
+        const size_t idx = inside ? (size_t)gx * nz + (size_t)gz : 0;
+        in[i] = inside ? acf[idx] : 0.0f;
+        in[plane_in + i] = inside ? acf[P + idx] : 0.0f;
+        in[2u * plane_in + i] = inside ? acf[2 * P + idx] : 0.0f;
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < plane_t; i += 256u) {
+        const uint32_t r = i / DOPPLER_TILE_Z, c = i - r * DOPPLER_TILE_Z;
+        const float *row = in + r * cols + c;
+        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+        for (uint32_t j = 0; j < kz; ++j) {
+            const float w = wz[j];
+            a0 = fma_(w, row[j], a0);
+            a1 = fma_(w, row[plane_in + j], a1);
+            a2 = fma_(w, row[2u * plane_in + j], a2);
+        }
+        t[i] = a0;
+        t[plane_t + i] = a1;
+        t[2u * plane_t + i] = a2;
+    }
+    __syncthreads();
+    const uint32_t tx = threadIdx.x / DOPPLER_TILE_Z, tz = threadIdx.x - tx * DOPPLER_TILE_Z;
+    const uint32_t gx = x0 + tx, gz = z0 + tz;
+    if (gx >= nx || gz >= nz) return;
+    const float *col = t + tx * DOPPLER_TILE_Z + tz;
+    float re = 0.0f, im = 0.0f, r0 = 0.0f;
+    for (uint32_t i = 0; i < kx; ++i) {
+        const float w = wx[i];
+        re = fma_(w, col[i * DOPPLER_TILE_Z], re);
+        im = fma_(w, col[plane_t + i * DOPPLER_TILE_Z], im);
+        r0 = fma_(w, col[2u * plane_t + i * DOPPLER_TILE_Z], r0);
+    }
+    const size_t o = (size_t)gx * nz + gz;
+    velocity[o] = (re == 0.0f && im == 0.0f) ? 0.0f : scale * atan2f(im, re);
+    amplitude[o] = sqrtf(r0);
 }

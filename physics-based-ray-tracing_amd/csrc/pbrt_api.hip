@@ -2590,6 +2590,7 @@ int pbrt_iq_envelope(pbrt_ctx *ctx, uint32_t n, const float *iq, float *env) {
     auto [din, dout] = S.arrays(stage_in(iq, 2 * (size_t)n), stage_out(env, n));
     STAGED_RUN(S, iq_env_enqueue(ctx, rq, din, dout));
 }
+#include "doppler_driver.h"  // pbrt_doppler_autocorr[_dev], pbrt_doppler_maps[_dev] (DESIGN D24): their launches and entry points
 
 int pbrt_bf_beamform_dev(pbrt_ctx *ctx, const pbrt_bf_params *p, const void *d_data, const void *d_tx_delays, const void *d_elem,
                          const void *d_x, const void *d_z, void *d_out) {
