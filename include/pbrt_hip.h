@@ -855,13 +855,21 @@ int pbrt_capon_beamform_table_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, con
  * pixels (both odd), hx = kx / 2, hz = kz / 2, pixels outside the image zero (a 'same' convolution), in f32:
  *   weights w[0 .. k) of a k-point window, in f64 and rounded once to f32: PBRT_DOPPLER_BOXCAR 1 / k; PBRT_DOPPLER_HAMMING
  *          h_i / (h_0 + h_1 + .. + h_{k-1}) (added in that order) with h_i = 0.54 - 0.46 cos(2 pi i / (k - 1)), and 1 for k = 1
- *   along z first: t[ix][iz] = sum over j = 0 .. kz - 1 ascending of wz[j] * a[ix][iz + j - hz]    (t = fmaf(wz[j], a, t), from 0)
+ *   along z first: t[ix][iz] = sum over j = 0 .. kz - 1 ascending of wz[j] * a[ix][iz + j - hz]    (t = fmaf(wz[j], a, t), from -0.0f)
  *   then along x:  s[ix][iz] = sum over i = 0 .. kx - 1 ascending of wx[i] * t[ix + i - hx][iz],   rows outside the image zero
+ *          Both sums start from -0.0f, not +0.0f: the first fmaf then gives the product itself, the sign of a zero included (+0.0f
+ *          would turn a product of -0.0f into +0.0f), and pixels outside the image, which are +0.0f, still add up to +0.0f.
  *   velocity = (float) (nyquist_velocity / pi) * atan2f(s_Im, s_Re), the factor from the doubles, rounded once; a pixel whose smoothed
  *          R1 compares equal to (0, 0) has velocity exactly 0
  *   amplitude = sqrtf(s_R0): the root of a power, so that pbrt_log_compress of it is the power-Doppler display
  *          (20 log10 of an amplitude = 10 log10 of a power)
- *   A 1 x 1 window (weight 1) leaves every plane as it is, bit for bit.
+ *   A 1 x 1 window (weight 1) leaves every plane as it is, bit for bit, -0.0f included: amplitude = sqrtf(-0.0f) = -0.0f there.
+ * Range and non-finite values: non-finite samples and acf values get no special treatment, and the arithmetic of both steps is plain
+ * f32 without rescaling.  A NaN or an infinity in a pixel's ensemble makes all three acf planes of that pixel non-finite and touches
+ * no other pixel; in an acf plane it reaches the kx x kz pixels whose window holds it, in the map that reads the plane (R1: velocity,
+ * R0: amplitude) and in no other; atan2f of an infinite R1 is finite, sqrtf of a negative or -inf R0 is NaN.  A power of two on the
+ * frames is the square of it on acf, bit for bit, the same velocity and that power of two on the amplitude, while no product leaves
+ * the normal range of f32; products below that range lose bits or vanish, and such pixels read as zero motion and zero power.
  * Sign: pbrt_rf2iq mixes with exp(-i 2 pi f t) and the beamformer turns a pixel back by the phase of its own delay, so a target that
  * moves AWAY from the probe (its echo arrives later from pulse to pulse) gives a NEGATIVE velocity, one that moves towards it a
  * positive one: velocity = -v_z for nyquist_velocity = c prf / (4 f), |v_z| below it.

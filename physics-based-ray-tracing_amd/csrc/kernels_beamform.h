@@ -1199,7 +1199,7 @@ __global__ __launch_bounds__(256) void k_doppler_autocorr(uint32_t N, uint32_t P
 }
 
 // acf[3][nx][nz] -> velocity[nx][nz], amplitude[nx][nz]: every plane smoothed by the separable window W (kx x kz, odd, zero outside the
-// image), along z first and then along x, one fmaf per tap in ascending order; velocity = scale atan2f(Im, Re) (exactly 0 where the
+// image), along z first and then along x, one fmaf per tap in ascending order from -0.0f; velocity = scale atan2f(Im, Re) (exactly 0 where the
 // smoothed R1 is zero), amplitude = sqrtf(R0).  A workgroup makes a tile of DOPPLER_TILE_X x DOPPLER_TILE_Z pixels (8 rows of 32 along
 // z, a thread per pixel): the three planes of the tile with its halo are staged in LDS, [rows][cols] = [8 + kx - 1][32 + kz - 1], the
 // z-smoothed rows go to a second LDS array [rows][32], and the sum along x reads that.  Dynamic LDS, doppler_maps_lds(kx, kz) bytes:
@@ -1236,7 +1236,7 @@ __global__ __launch_bounds__(256) void k_doppler_maps(uint32_t nx, uint32_t nz, 
     for (uint32_t i = threadIdx.x; i < plane_t; i += 256u) {
         const uint32_t r = i / DOPPLER_TILE_Z, c = i - r * DOPPLER_TILE_Z;
         const float *row = in + r * cols + c;
-        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+        float a0 = -0.0f, a1 = -0.0f, a2 = -0.0f;  // (-0: the first fmaf gives the product itself, the sign of a zero included)
         for (uint32_t j = 0; j < kz; ++j) {
             const float w = wz[j];
             a0 = fma_(w, row[j], a0);
@@ -1252,7 +1252,7 @@ __global__ __launch_bounds__(256) void k_doppler_maps(uint32_t nx, uint32_t nz, 
     const uint32_t gx = x0 + tx, gz = z0 + tz;
     if (gx >= nx || gz >= nz) return;
     const float *col = t + tx * DOPPLER_TILE_Z + tz;
-    float re = 0.0f, im = 0.0f, r0 = 0.0f;
+    float re = -0.0f, im = -0.0f, r0 = -0.0f;
     for (uint32_t i = 0; i < kx; ++i) {
         const float w = wx[i];
         re = fma_(w, col[i * DOPPLER_TILE_Z], re);

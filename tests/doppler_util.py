@@ -1,5 +1,5 @@
 """Colour and power Doppler (include/pbrt_hip.h) restated in NumPy for test_doppler_restatement.py (CPU) and
-test_gpu_doppler.py (GPU): the slow-time autocorrelation with its polynomial regression (wall) filter and the maps made of it, written
+test_gpu_doppler.py (GPU), and for their non-finite and rescaled cases (test_doppler_nonfinite_restatement.py, test_gpu_doppler_edges.py): the slow-time autocorrelation with its polynomial regression (wall) filter and the maps made of it, written
 from the header's formulas and sharing no text with the kernels.
 
   basis     the orthonormal polynomial basis on N slow-time points, float64 (Gram-Schmidt; the package's wall_basis is held to it)
@@ -84,12 +84,13 @@ def autocorr(frames, q=None, dtype=np.float64):
 
 
 def _along(a, w, axis, dtype):
-    """sum_j w[j] a[.. i + j - h ..] along `axis`, zero outside, j ascending"""
+    """sum_j w[j] a[.. i + j - h ..] along `axis`, zero outside, j ascending.  The sum starts from -0.0, as the header states: then its
+    first term is the product itself, the sign of a zero included, and a 1-point window is the identity on -0.0 too"""
     k, h = len(w), len(w) // 2
     a = np.moveaxis(np.asarray(a, dtype), axis, -1)
     n = a.shape[-1]
     pad = np.concatenate([np.zeros(a.shape[:-1] + (h,), dtype), a, np.zeros(a.shape[:-1] + (h,), dtype)], axis=-1)
-    acc = np.zeros(a.shape, dtype)
+    acc = np.full(a.shape, -0.0, dtype)
     for j in range(k):
         acc = acc + dtype(w[j]) * pad[..., j:j + n]
     return np.moveaxis(acc, -1, axis)

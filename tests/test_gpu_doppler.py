@@ -5,7 +5,9 @@ is held to (nyquist / pi) (4 floor B_R1 / |R1| + 8 2^-24 pi) on the pixels with 
 and at most 10 % of an image may be left out.  Then the exact statements, the three forms, every rule through the C-ABI, the Python
 layer's ValueErrors and doppler_render end to end on the moving plate of D24.  Shapes are the smallest at which the kernels can go
 wrong: 13 x 37 (no multiple of a tile, a wave or a workgroup; two workgroups of the autocorrelation, four tiles of the maps), 1 x 1,
-70 x 5 (nine rows of tiles), 5 x 9 under a 15 x 15 window (larger than the image)."""
+70 x 5 (nine rows of tiles), 5 x 9 under a 15 x 15 window (larger than the image), 1 x 65, 65 x 1 and 9 x 33 under windows 15 long.
+Every instance of k_doppler_autocorr (no filter, degrees 0 .. 3) runs at N = degree + 2 and above.  Non-finite and rescaled data and
+doppler_render beyond one configuration: tests/test_gpu_doppler_edges.py."""
 import ctypes as C
 import math
 
@@ -33,6 +35,8 @@ def _held(name, dev, f64, f32, B):
 
 
 ACF_CASES = [(N, d, (13, 37)) for N in (2, 3, 8, 17, 64) for d in (None, 0, 1, 3) if d is None or d + 1 < N] + [(8, 3, (70, 5)), (17, None, (70, 5))]
+# degree 2 (k_doppler_autocorr<3>), and the tightest ensemble N = degree + 2 of degrees 2 and 3 (those of 0 and 1 are above)
+ACF_CASES += [(N, 2, (13, 37)) for N in (4, 8, 17, 64)] + [(5, 3, (13, 37))]
 
 
 @pytest.mark.parametrize("N,d,shape", ACF_CASES)
@@ -75,9 +79,12 @@ def test_autocorrelation_of_a_1_x_1_image(mi):
 
 
 @pytest.mark.parametrize("window", ["boxcar", "hamming"])
-@pytest.mark.parametrize("shape,kernel", [((13, 37), (1, 1)), ((13, 37), (3, 5)), ((13, 37), (15, 15)), ((5, 9), (15, 15)), ((70, 5), (5, 3))])
+@pytest.mark.parametrize("shape,kernel", [((13, 37), (1, 1)), ((13, 37), (3, 5)), ((13, 37), (15, 15)), ((5, 9), (15, 15)), ((70, 5), (5, 3))]
+                         + [(s, k) for s in ((1, 65), (65, 1), (9, 33)) for k in ((15, 1), (1, 15), (15, 15))])
 def test_maps_against_the_restatement(mi, window, shape, kernel):
-    """the acf of a pure-tone ensemble plus 10 % noise (float64 restatement, rounded to float32) through pbrt_doppler_maps"""
+    """the acf of a pure-tone ensemble plus 10 % noise (float64 restatement, rounded to float32) through pbrt_doppler_maps.  The thin
+    images: 1 x 65 (every halo row outside the image, three z-tiles of one row), 65 x 1 (every halo column outside, nine x-tiles of
+    one column) and 9 x 33 (one pixel past a tile each way)."""
     acf = du.autocorr(du.tone(np.random.default_rng(7), 8, shape))[0].astype(np.float32)
     m64, m32 = du.maps(acf, NYQ, window, kernel), du.maps(acf, NYQ, window, kernel, dtype=np.float32)
     vel, amp = mi.doppler_maps(acf, NYQ, window, kernel)
@@ -125,7 +132,7 @@ def test_the_host_form_and_the_dev_form_are_bit_equal(mi):
     cx = mi.default_context()
     x = du.ensemble(np.random.default_rng(5), 8, (13, 37), d=1)
     d_x = mi.DeviceBuffer.from_host(cx, x)
-    for wall, degree in (("none", 0), ("mean", 0), ("poly", 3)):
+    for wall, degree in (("none", 0), ("mean", 0), ("poly", 3), ("poly", 1), ("poly", 2)):      # (every instance of the kernel)
         host = mi.doppler_autocorr(x, wall, degree)
         d_acf = mi.doppler_autocorr(d_x, wall, degree)
         assert isinstance(d_acf, mi.DeviceBuffer) and d_acf.shape == (3, 13, 37) and np.array_equal(d_acf.numpy(), host)

@@ -250,15 +250,16 @@ def test_rf2iq_at_every_decimation(mi, D):
 
 
 # ---- F ------------------------------------------------------------------------------------------------------------------------
-def _d12_scene(mi):
+def _d12_scene(mi, **integrator):
     """the scene of test_d12_nan_echoes_reach_the_display_as_in_the_f64_chain: the 0-degree plane wave meets a plate that faces the probe
-    exactly, and every element's trace of that transmission holds NaN echoes from sample 800 (2 x 15 mm at 1500 m/s and 40 MHz) on"""
+    exactly, and every element's trace of that transmission holds NaN echoes from sample 800 (2 x 15 mm at 1500 m/s and 40 MHz) on.
+    `integrator`: entries of the integrator's dict to replace (test_gpu_doppler_edges.py: the pulse model and the 0-degree angle alone)"""
     Tf = mi.ScalarTransform4f
     return mi.load_dict({
         "type": "scene",
         "integrator": {"type": "ultrasound_integrator", "max_depth": 4, "sampling_rate": 40e6, "frequency": 4e6, "sound_speed": 1500,
                        "attenuation": 0.1, "main_beam_angle": 20, "cutoff_angle": 35, "n_elements": 32, "pitch": 2e-4,
-                       "time_samples": 4000, "angles": [-5.0, 0.0, 5.0], "paths_per_ray": 50, "seed": 9},
+                       "time_samples": 4000, "angles": [-5.0, 0.0, 5.0], "paths_per_ray": 50, "seed": 9, **integrator},
         "sensor": {"type": "ultrasound_sensor", "to_world": Tf().look_at([0, 0, 0], [0, 0, 0.03], [0, 1, 0])},
         "p": {"type": "rectangle", "to_world": Tf().translate([0, 0, 0.015]) @ Tf().rotate([1, 0, 0], 180) @ Tf().scale([0.03, 0.03, 1]),
               "bsdf": {"type": "ultrasound_bsdf", "impedance": 7.8, "roughness": 0.9}}})
