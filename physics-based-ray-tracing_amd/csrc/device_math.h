@@ -50,6 +50,8 @@ DEV uint32_t udiv_fast(uint32_t n, FastDiv f) {
     const uint32_t q = (((n - hi) >> 1) + hi) >> f.shift;
     return f.is_one ? n : q;
 }
+// rank of a lane among the lanes of ballot b below it
+DEV uint32_t ballot_rank(unsigned long long b) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u)); }
 
 // ---- short correctly rounded forms -----------------------------------------------------------------------
 // A correctly rounded result is unique, so any sequence that provably returns RN(1/b), RN(a/b) or RN(sqrt x) has the bits of

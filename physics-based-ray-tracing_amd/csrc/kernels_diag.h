@@ -22,6 +22,9 @@
 // (PBRT_PAIR_MERGE=k picks the merge bounce).
 // Host: max_depth <= MAX_CHAIN (every path ends inside the launch: no state goes out), 1 <= merge_at < max_depth,
 // grid = ceil(n_paths / (2 * SEG_BRUTE)).
+// row k of entry r of the wave's strip pk (get / put of STATE_LOAD / STATE_STORE)
+#define PARK_GET(k) __uint_as_float(pk[k][r])
+#define PARK_PUT(k, v) pk[k][r] = __float_as_uint(v)
 template <int ACCEL>
 __global__ __launch_bounds__(SEG_BRUTE, ACCEL == ACCEL_K_BRUTE ? FUSED_WAVES_PER_EU : BIG_WAVES_PER_EU) void k_chain_pair(const RadArgs a) {
     static_assert(ACCEL == ACCEL_K_BRUTE || ACCEL == ACCEL_K_BRUTE_BIG, "k_chain_pair: brute-force kernels");
@@ -53,23 +56,13 @@ __global__ __launch_bounds__(SEG_BRUTE, ACCEL == ACCEL_K_BRUTE ? FUSED_WAVES_PER
             const uint32_t slot = (tile0 + turn) * 64u + lane;
             live = slot < a.n_paths;
             home = slot;
-            if (live) {
-                uint32_t px, py;
-                path_key<true>(a, home, &ka, &kb, &px, &py);
-                F4 uj = rng4(ka, kb, 0, a.seed);
-                float fx = (float)px + uj.x, fy = (float)py + uj.y;
-                camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
-                thr = {1, 1, 1};
-                L = {0, 0, 0};
-                eta = 1.0f;
-                prev_pdf = -1.0f;
-            }
+            if (live) camera_start(a, home, &ka, &kb, &o, &d, &tmax, &thr, &L, &eta, &prev_pdf);
         } else {
             // turn 2: the parked paths go to the idle lanes of tile B, in order; turn 3: those that found none, from lane 0 on
             // (every lane is idle by then)
             if (turn == 3u && n_left == 0u) break;
             const unsigned long long idle = ~__ballot(live);
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            const uint32_t rank = ballot_rank(idle);
             uint32_t n_take;
             if (turn == 2u) {
                 n_take = min(n_park, (uint32_t)__popcll(idle));
@@ -80,15 +73,9 @@ __global__ __launch_bounds__(SEG_BRUTE, ACCEL == ACCEL_K_BRUTE ? FUSED_WAVES_PER
             }
             const uint32_t r = (turn == 2u ? 0u : left0) + rank;
             if (!live && rank < n_take) {
-                o = {__uint_as_float(pk[0][r]), __uint_as_float(pk[1][r]), __uint_as_float(pk[2][r])};
-                d = {__uint_as_float(pk[3][r]), __uint_as_float(pk[4][r]), __uint_as_float(pk[5][r])};
-                thr = {__uint_as_float(pk[6][r]), __uint_as_float(pk[7][r]), __uint_as_float(pk[8][r])};
-                L = {__uint_as_float(pk[9][r]), __uint_as_float(pk[10][r]), __uint_as_float(pk[11][r])};
-                eta = __uint_as_float(pk[12][r]);
-                prev_pdf = __uint_as_float(pk[13][r]);
-                home = pk[14][r];
+                STATE_LOAD(PARK_GET, o, d, thr, L, eta, prev_pdf, home);
                 uint32_t px, py;
-                path_key<true>(a, home, &ka, &kb, &px, &py);
+                path_key(a, home, &ka, &kb, &px, &py);
                 live = true;
             }
             b_first = m;
@@ -113,22 +100,8 @@ __global__ __launch_bounds__(SEG_BRUTE, ACCEL == ACCEL_K_BRUTE ? FUSED_WAVES_PER
             const unsigned long long bal = __ballot(live);
             n_park = (uint32_t)__popcll(bal);
             if (live) {
-                const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                pk[0][k] = __float_as_uint(o.x);
-                pk[1][k] = __float_as_uint(o.y);
-                pk[2][k] = __float_as_uint(o.z);
-                pk[3][k] = __float_as_uint(d.x);
-                pk[4][k] = __float_as_uint(d.y);
-                pk[5][k] = __float_as_uint(d.z);
-                pk[6][k] = __float_as_uint(thr.x);
-                pk[7][k] = __float_as_uint(thr.y);
-                pk[8][k] = __float_as_uint(thr.z);
-                pk[9][k] = __float_as_uint(L.x);
-                pk[10][k] = __float_as_uint(L.y);
-                pk[11][k] = __float_as_uint(L.z);
-                pk[12][k] = __float_as_uint(eta);
-                pk[13][k] = __float_as_uint(prev_pdf);
-                pk[14][k] = home;
+                const uint32_t r = ballot_rank(bal);
+                STATE_STORE(PARK_PUT, o, d, thr, L, eta, prev_pdf, home);
             }
         }
     }
@@ -170,7 +143,7 @@ __global__ __launch_bounds__(SEG_BRUTE, WALK_WAVES_PER_EU) void k_walk(const Rad
     const uint32_t wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u;
     // a wave that leaves has published zero counts in both buffers first; s_barrier does not wait for terminated waves,
     // and it does wait for a wave that has neither arrived nor terminated, so the zeros are in place before anybody scans
-    auto leave_if_idle = [&](uint32_t cnt) {
+    auto leave_wave = [&](uint32_t cnt) {
         if ((tid & 63u) == 0 && wave_first >= cnt) {
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
@@ -180,13 +153,9 @@ __global__ __launch_bounds__(SEG_BRUTE, WALK_WAVES_PER_EU) void k_walk(const Rad
                 wave_mid[b][wid] = 0;
             }
         }
-        asm volatile("s_cmp_lt_u32 %0, %1\n\t"
-                     "s_cbranch_scc1 .Lstay_%=\n\t"
-                     "s_waitcnt lgkmcnt(0)\n\t"
-                     "s_endpgm\n"
-                     ".Lstay_%=:" ::"s"(wave_first), "s"(cnt) : "scc", "memory");
+        leave_if_idle(wave_first, cnt);
     };
-    leave_if_idle(cnt_in);
+    leave_wave(cnt_in);
     const uint32_t live_threads = (min(cnt_in, SEG) + 63u) & ~63u;  // waves present at the first trip
     const LdsScene ls = NO_LDS_SCENE;
     const Tables tb = make_tables<ACCEL>(a.sc, ls, tab_lds);
@@ -207,25 +176,16 @@ __global__ __launch_bounds__(SEG_BRUTE, WALK_WAVES_PER_EU) void k_walk(const Rad
         uint32_t home = slot, ka = 0, kb = 0, px = 0, py = 0;
         if (alive) {
             if (first) {
-                path_key<true>(a, home, &ka, &kb, &px, &py);
-                F4 uj = rng4(ka, kb, 0, a.seed);
-                float fx = (float)px + uj.x, fy = (float)py + uj.y;
-                camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
+                camera_start(a, home, &ka, &kb, &o, &d, &tmax);
             } else {
                 const uint32_t v4 = state_voff(slot);
                 constexpr uint32_t row = STATE_ROW_BYTES;
-                o = {bld(r_in, v4 + 0 * row, 0), bld(r_in, v4 + 1 * row, 0), bld(r_in, v4 + 2 * row, 0)};
-                d = {bld(r_in, v4 + 3 * row, 0), bld(r_in, v4 + 4 * row, 0), bld(r_in, v4 + 5 * row, 0)};
-                thr = {bld(r_in, v4 + 6 * row, 0), bld(r_in, v4 + 7 * row, 0), bld(r_in, v4 + 8 * row, 0)};
-                L = {bld(r_in, v4 + 9 * row, 0), bld(r_in, v4 + 10 * row, 0), bld(r_in, v4 + 11 * row, 0)};
-                eta = bld(r_in, v4 + 12 * row, 0);
-                prev_pdf = bld(r_in, v4 + 13 * row, 0);
-                home = __float_as_uint(bld(r_in, v4 + 14 * row, 0));
+                STATE_LOAD(STATE_BLD, o, d, thr, L, eta, prev_pdf, home);
             }
         }
         // shading tables -> LDS, behind the state loads of the first trip so that the two memory round trips overlap
         if (ACCEL == ACCEL_K_BRUTE && !FIRST && trip == 0) fill_tables_lds(a.sc, tab_lds, live_threads);
-        if (alive && !first) path_key<true>(a, home, &ka, &kb, &px, &py);
+        if (alive && !first) path_key(a, home, &ka, &kb, &px, &py);
         const uint32_t nb = (trip == 0) ? (uint32_t)NB0 : 1u;
         bool live = alive;
         uint32_t nseg_w = 0, nshd_w = 0, nmid_w = 0;
@@ -247,7 +207,7 @@ __global__ __launch_bounds__(SEG_BRUTE, WALK_WAVES_PER_EU) void k_walk(const Rad
         }
         // ---- segment-local stream compaction (as in k_bounce)
         const unsigned long long bal = __ballot(survive);
-        const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        const uint32_t prefix = ballot_rank(bal);
         if ((tid & 63u) == 0) {
             wave_tot[buf][wid] = (uint32_t)__popcll(bal);
             wave_seg[buf][wid] = nseg_w;
@@ -256,34 +216,11 @@ __global__ __launch_bounds__(SEG_BRUTE, WALK_WAVES_PER_EU) void k_walk(const Rad
         }
         __syncthreads();
         uint32_t off = 0, total = 0;
-        {
-            const uint32_t t_lane = wave_tot[buf][tid & (W - 1)];
-            const uint32_t wid_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wid);
-#pragma unroll
-            for (uint32_t w = 0; w < W; ++w) {
-                const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)t_lane, (int)w);
-                off += (w < wid_s) ? t : 0u;
-                total += t;
-            }
-        }
+        WAVE_SCAN(W, wave_tot[buf], tid, wid, off, total);
         if (survive) {
             const uint32_t v4 = state_voff(base + off + prefix);
             constexpr uint32_t row = STATE_ROW_BYTES;
-            bst(r_out, v4 + 0 * row, 0, o.x);
-            bst(r_out, v4 + 1 * row, 0, o.y);
-            bst(r_out, v4 + 2 * row, 0, o.z);
-            bst(r_out, v4 + 3 * row, 0, d.x);
-            bst(r_out, v4 + 4 * row, 0, d.y);
-            bst(r_out, v4 + 5 * row, 0, d.z);
-            bst(r_out, v4 + 6 * row, 0, thr.x);
-            bst(r_out, v4 + 7 * row, 0, thr.y);
-            bst(r_out, v4 + 8 * row, 0, thr.z);
-            bst(r_out, v4 + 9 * row, 0, L.x);
-            bst(r_out, v4 + 10 * row, 0, L.y);
-            bst(r_out, v4 + 11 * row, 0, L.z);
-            bst(r_out, v4 + 12 * row, 0, eta);
-            bst(r_out, v4 + 13 * row, 0, prev_pdf);
-            bst(r_out, v4 + 14 * row, 0, __uint_as_float(home));
+            STATE_STORE(STATE_BST, o, d, thr, L, eta, prev_pdf, home);
         }
         if (tid == 0) {  // wave 0 stays as long as the segment has a live path
             uint32_t mid = 0;
@@ -309,7 +246,7 @@ __global__ __launch_bounds__(SEG_BRUTE, WALK_WAVES_PER_EU) void k_walk(const Rad
         r_out = t_r;
         cnt_in = total;
         ++trip;
-        leave_if_idle(cnt_in);
+        leave_wave(cnt_in);
     }
     if (tid == 0) {
         a.seg_out[seg] = left;
@@ -362,19 +299,11 @@ __global__ __launch_bounds__(REGEN_WG, REGEN_WAVES_PER_EU) void k_regen(const Ra
     for (;;) {
         const unsigned long long need = __ballot(!live);
         if (need) {  // uniform: hand the next homes of the share to the idle lanes
-            const uint32_t v = q + __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+            const uint32_t v = q + ballot_rank(need);
             const uint32_t h0 = ((v >> 6) * GW + gw) * 64u + (v & 63u);
             if (!live && h0 < a.n_paths) {
-                uint32_t px, py;
                 home = h0;
-                path_key<true>(a, home, &ka, &kb, &px, &py);
-                F4 uj = rng4(ka, kb, 0, a.seed);
-                float fx = (float)px + uj.x, fy = (float)py + uj.y;
-                camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
-                thr = {1, 1, 1};
-                L = {0, 0, 0};
-                eta = 1.0f;
-                prev_pdf = -1.0f;
+                camera_start(a, home, &ka, &kb, &o, &d, &tmax, &thr, &L, &eta, &prev_pdf);
                 depth = 0;
                 live = true;
             }

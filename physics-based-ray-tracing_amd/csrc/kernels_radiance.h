@@ -1,11 +1,7 @@
 // kernels_radiance.h -- radiance-mode wavefront kernels (gfx950).
 //
-// Layout in HBM (DESIGN.md "Data layout"): path state is a tiled structure of arrays (state_voff below), 15 dwords
-// per slot
-//   [0..2] ray origin  [3..5] ray direction  [6..8] throughput rgb  [9..11] radiance rgb
-//   [12] eta  [13] pdf of the previous BSDF sample (< 0: previous event was a delta lobe / camera)
-//   [14] home slot (uint32): index of the path's radiance accumulator and of its pixel/sample
-// Slots are grouped in segments of SEG = workgroup size.  One bounce = one launch: workgroup g reads
+// Layout in HBM (DESIGN.md "Data layout"): path state is a tiled structure of arrays, N_STATE dwords per slot (the rows ST_* and
+// state_voff below).  Slots are grouped in segments of SEG = workgroup size.  One bounce = one launch: workgroup g reads
 // the live prefix of region g of the `in` state, advances every path by one bounce (closest hit,
 // emission + MIS, next-event estimation with its shadow ray, BSDF sample, Russian roulette) and
 // writes the survivors, compacted to the front of region g of the `out` state: brute-force scenes with a wave
@@ -138,6 +134,15 @@ struct RadArgs {
 // 15 + 15 state accesses of a bounce need no 64-bit VALU address arithmetic (the kernel is VALU-bound) and no
 // SGPR per row (the kernel sits at the 80-SGPR occupancy limit).  A wave reads one contiguous 3840-byte tile.
 // Requires N_STATE * cap * 4 < 4 GiB (checked by the host) and cap % 64 == 0.
+// The rows of a path's record (the ONE place that says what they are; the wave-private LDS strip of k_chain_pair has the same rows):
+//   ST_O, ST_D    3 rows each: ray origin, ray direction
+//   ST_THR, ST_L  3 rows each: throughput rgb, radiance rgb
+//   ST_ETA        eta.  Key mode 1 (Integrator.sample on caller rays): the record k_init_rays writes carries the ray's tmax here
+//                 instead, and the bounce at depth 0 that reads it takes the row as tmax and starts from eta = 1
+//   ST_PDF        pdf of the previous BSDF sample (< 0: the previous event was a delta lobe / the camera)
+//   ST_HOME       home slot (uint32): index of the path's radiance record and of its pixel / sample
+enum { ST_O = 0, ST_D = 3, ST_THR = 6, ST_L = 9, ST_ETA = 12, ST_PDF = 13, ST_HOME = 14 };
+static_assert(ST_HOME == N_STATE - 1, "the rows of a path record");
 #define STATE_TILE_BYTES (64u * N_STATE * 4u)
 #define STATE_ROW_BYTES 256u
 DEV uint32_t state_voff(uint32_t slot) { return (slot >> 6) * STATE_TILE_BYTES + (slot & 63u) * 4u; }
@@ -151,11 +156,46 @@ DEV float bld(Rsrc r, uint32_t voff, uint32_t soff) {
 DEV void bst(Rsrc r, uint32_t voff, uint32_t soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, voff, soff, 0);
 }
+// A record read or written row by row: get(row) is the row as a float, put(row, v) takes it.  Macros on macros, not functions or
+// callables (as DAS_DELAYED, kernels_beamform.h): the 15 accesses then are the site's own statements on its own variables.  Functions
+// with reference parameters and lambdas as get / put each moved the scalar spills of k_bounce chain instances
+// (profiles/shared_path_start.md).  STATE_BLD / STATE_BST: the rows of a state tile through the site's descriptors r_in / r_out, at
+// its byte offset v4 = state_voff(slot), with its `constexpr uint32_t row = STATE_ROW_BYTES`.
+#define STATE_BLD(k) bld(r_in, v4 + (k) * row, 0)
+#define STATE_BST(k, v) bst(r_out, v4 + (k) * row, 0, v)
+#define STATE_LOAD(get, o, d, thr, L, eta, prev_pdf, home)             \
+    {                                                                  \
+        o = {get(ST_O + 0), get(ST_O + 1), get(ST_O + 2)};             \
+        d = {get(ST_D + 0), get(ST_D + 1), get(ST_D + 2)};             \
+        thr = {get(ST_THR + 0), get(ST_THR + 1), get(ST_THR + 2)};     \
+        L = {get(ST_L + 0), get(ST_L + 1), get(ST_L + 2)};             \
+        eta = get(ST_ETA);                                             \
+        prev_pdf = get(ST_PDF);                                        \
+        home = __float_as_uint(get(ST_HOME));                          \
+    }
+#define STATE_STORE(put, o, d, thr, L, eta, prev_pdf, home)            \
+    {                                                                  \
+        put(ST_O + 0, (o).x);                                          \
+        put(ST_O + 1, (o).y);                                          \
+        put(ST_O + 2, (o).z);                                          \
+        put(ST_D + 0, (d).x);                                          \
+        put(ST_D + 1, (d).y);                                          \
+        put(ST_D + 2, (d).z);                                          \
+        put(ST_THR + 0, (thr).x);                                      \
+        put(ST_THR + 1, (thr).y);                                      \
+        put(ST_THR + 2, (thr).z);                                      \
+        put(ST_L + 0, (L).x);                                          \
+        put(ST_L + 1, (L).y);                                          \
+        put(ST_L + 2, (L).z);                                          \
+        put(ST_ETA, eta);                                              \
+        put(ST_PDF, prev_pdf);                                         \
+        put(ST_HOME, __uint_as_float(home));                           \
+    }
 
 // Pixel order inside the rendered region (index k of a pixel = its slot within one sample's block of `Lhome` and
-// of the first-bounce state).  BVH kernels (TILED): the region is cut into bands of 8 rows and a band is walked
-// column by column, so the 64 consecutive paths of a wave are an 8 x 8 pixel tile, not a 64 x 1 strip -- their
-// primary rays visit fewer distinct nodes (every lane of a wave pays for the union).  The rh % 8 rows below the last
+// of the first-bounce state).  The region is cut into bands of 8 rows and a band is walked column by column, so
+// the 64 consecutive paths of a wave are an 8 x 8 pixel tile, not a 64 x 1 strip -- on a BVH their primary rays
+// visit fewer distinct nodes (every lane of a wave pays for the union; path_key).  The rh % 8 rows below the last
 // full band keep the row-major order; tile_rows = rh & ~7 (0: plain row-major everywhere).
 DEV uint32_t region_index(uint32_t xx, uint32_t yy, uint32_t rw, uint32_t tile_rows) {
     return yy < tile_rows ? (yy >> 3) * (8u * rw) + (xx << 3) + (yy & 7u) : yy * rw + xx;
@@ -176,22 +216,19 @@ DEV uint32_t xcd_swizzle(uint32_t b, uint32_t n) {
     return (b & ~7u) | ((b + rot) & 7u);
 }
 
-// Args: RadArgs, or PathArgs (k_path: key mode 0 as a constant)
-template <bool TILED, class Args>
+// The RNG key (ka, kb) and the pixel of the path whose home slot is `home`.  Key mode 0 inverts region_index (one division either
+// way), in every kernel: 8 x 8 pixel tiles per wave are coherent rays for the BVH kernels; for the brute-force kernels, whose
+// primitive loop does not care, they keep the long paths of a chain launch (the pixels of the glass and the mirror sphere) together
+// in the same waves instead of one or two lanes in every wave of a row: Cornell box, one launch per pass, 6.41 -> 6.25 ms.
+// Args: RadArgs, WfArgs, or PathArgs (k_path: key mode 0 as a constant)
+template <class Args>
 DEV void path_key(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, uint32_t *px, uint32_t *py) {
     if (a.key_mode == 0) {
         uint32_t sl = udiv_fast(home, a.div_npix), pr = home - sl * a.npix_r;
-        uint32_t rx, ry;
-        if (TILED) {  // inverse of region_index: one division either way
-            const bool tiled = pr < a.tile_rows * a.rw;
-            const uint32_t num = tiled ? pr >> 3 : pr;
-            const uint32_t q = udiv_fast(num, a.div_rw);
-            rx = num - q * a.rw;
-            ry = tiled ? (q << 3) + (pr & 7u) : q;
-        } else {
-            ry = udiv_fast(pr, a.div_rw);
-            rx = pr - ry * a.rw;
-        }
+        const bool tiled = pr < a.tile_rows * a.rw;
+        const uint32_t num = tiled ? pr >> 3 : pr;
+        const uint32_t q = udiv_fast(num, a.div_rw);
+        const uint32_t rx = num - q * a.rw, ry = tiled ? (q << 3) + (pr & 7u) : q;
         *px = a.rx0 + rx;
         *py = a.ry0 + ry;
         *ka = *py * a.film_w + *px;
@@ -201,6 +238,66 @@ DEV void path_key(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, uint
         *kb = a.sample_index;
         *px = *py = 0;
     }
+}
+// The camera start of the path at `home`: its key, and the ray through its jittered film position (draw 0 of the key).
+template <class Args>
+DEV void camera_start(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, V3 *o, V3 *d, float *tmax) {
+    uint32_t px, py;
+    path_key(a, home, ka, kb, &px, &py);
+    F4 uj = rng4(*ka, *kb, 0, a.seed);
+    float fx = (float)px + uj.x, fy = (float)py + uj.y;
+    camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), o, d, tmax);
+}
+// ... and the state a path starts with, for the kernels whose lanes start more than one path
+template <class Args>
+DEV void camera_start(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, V3 *o, V3 *d, float *tmax, V3 *thr, V3 *L,
+                  float *eta, float *prev_pdf) {
+    camera_start(a, home, ka, kb, o, d, tmax);
+    *thr = {1, 1, 1};
+    *L = {0, 0, 0};
+    *eta = 1.0f;
+    *prev_pdf = -1.0f;
+}
+// The keep word of a wave's camera tile (RadArgs::tile_keep != nullptr; base: the home of the workgroup's thread 0).  The wave's
+// camera rays are the 8 x 8 tile of one sample (or, on a region whose width is no multiple of 8, a few tiles): the closest-hit walk
+// of bounce 0 leaves out what the keep word of its 64 region indices rules out (one scalar load).
+template <class Args>
+DEV uint32_t camera_keep_word(const Args &a, uint32_t base, uint32_t tid) {
+    const uint32_t home0 = base + ((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u);
+    const uint32_t blk = (home0 - udiv_fast(home0, a.div_npix) * a.npix_r) >> 6;
+    return load_uniform<uint32_t>(a.tile_keep + min(blk, (a.npix_r >> 6) - 1u));
+}
+// One 16-byte radiance record per finished path: three 4-byte row stores at a scattered `home` cost three 32-byte HBM sectors
+// (measured: k_bounce WRITE_SIZE 1.23 x algorithmic), one dwordx4 store costs one.
+DEV void store_record(Rsrc r_L, uint32_t home, V3 L) {
+    typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
+    const u32x4 rec = {__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u};
+    __builtin_amdgcn_raw_buffer_store_b128(rec, r_L, home * 16u, 0, 0);
+}
+// Exclusive scan over the W waves' survivor counts `tot` (LDS, published before a barrier) on the scalar unit: one LDS read per
+// lane, then v_readlane + s_add per wave (the per-lane form cost 40 VALU per wave-bounce).  Adds the counts of the waves below wave
+// `wid` to `off` and all of them to `total` (names of the site's variables).  A macro like STATE_LOAD: as a function -- `tot` by
+// pointer or its element by value, the sums by pointer or by reference -- it moved a VGPR or a scalar spill in k_bounce or k_walk
+// (profiles/shared_path_start.md).
+#define WAVE_SCAN(W, tot, tid, wid, off, total)                                                \
+    {                                                                                          \
+        const uint32_t t_lane = (tot)[(tid) & ((W) - 1)];                                      \
+        const uint32_t wid_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wid));           \
+        _Pragma("unroll") for (uint32_t w = 0; w < (W); ++w) {                                 \
+            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)t_lane, (int)w);       \
+            off += (w < wid_s) ? t : 0u;                                                       \
+            total += t;                                                                        \
+        }                                                                                      \
+    }
+// A wave whose first slot (wave_first, scalar) lies at or beyond the cnt live ones ends here, once its LDS writes have landed:
+// s_barrier does not wait for terminated waves.  s_endpgm behind the compiler's back keeps the kernel single-exit for the
+// structurizer.
+DEV void leave_if_idle(uint32_t wave_first, uint32_t cnt) {
+    asm volatile("s_cmp_lt_u32 %0, %1\n\t"
+                 "s_cbranch_scc1 .Llive_%=\n\t"
+                 "s_waitcnt lgkmcnt(0)\n\t"
+                 "s_endpgm\n"
+                 ".Llive_%=:" ::"s"(wave_first), "s"(cnt) : "scc", "memory");
 }
 
 // LDS image of the BVH scene (device_scene.h TreeLds: node planes | leaf records), and the workgroup's traversal stacks (BvhStack)
@@ -410,13 +507,7 @@ DEV bool bounce_step(const Args &a, const Tables &tb, const LdsScene &ls, Rsrc r
             },
             [&](V3 A, V3 B) { L = {fma_(A.x, B.x, L.x), fma_(A.y, B.y, L.y), fma_(A.z, B.z, L.z)}; });
     }
-    if (STORE && !survive) {
-        // one 16-byte record per finished path: three 4-byte row stores at a scattered `home` cost three
-        // 32-byte HBM sectors (measured: k_bounce WRITE_SIZE 1.23 x algorithmic), one dwordx4 store costs one
-        typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-        const u32x4 rec = {__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u};
-        __builtin_amdgcn_raw_buffer_store_b128(rec, r_L, home * 16u, 0, 0);
-    }
+    if (STORE && !survive) store_record(r_L, home, L);
     return survive;
 }
 
@@ -465,10 +556,6 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
     const uint32_t seg = xcd_swizzle(blockIdx.x, gridDim.x);  // region index
     const uint32_t tid = threadIdx.x;
     constexpr uint32_t REGION = rad_region_segs(ACCEL) * SEG;
-    // 8 x 8 pixel tiles per wave (path_key): coherent rays for the BVH kernels; for the brute-force kernels, whose primitive loop does
-    // not care, it keeps the long paths of a chain launch (the pixels of the glass and the mirror sphere) together in the same
-    // waves instead of one or two lanes in every wave of a row: Cornell box, one launch per pass, 6.41 -> 6.25 ms
-    constexpr bool TILED = true;
     constexpr bool DYN = rad_dynamic(ACCEL);  // chunk queue + slot reservation in LDS (BVH kernels): the waves walk 64-path chunks on their own
     constexpr uint32_t W = SEG / 64;          // waves per workgroup
     constexpr uint32_t CH = DYN ? 64u : SEG;  // paths per chunk of the walk
@@ -510,13 +597,7 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
                 wave_mid_hi[0][tid >> 6] = 0;
             }
         }
-        // s_endpgm behind the compiler's back keeps the kernel single-exit for the structurizer
-        const uint32_t wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u;
-        asm volatile("s_cmp_lt_u32 %0, %1\n\t"
-                     "s_cbranch_scc1 .Llive_%=\n\t"
-                     "s_waitcnt lgkmcnt(0)\n\t"
-                     "s_endpgm\n"
-                     ".Llive_%=:" ::"s"(wave_first), "s"(cnt_in) : "scc", "memory");
+        leave_if_idle((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u, cnt_in);
     }
     const uint32_t live_threads = early_exit ? (min(cnt_in, SEG) + 63u) & ~63u : SEG;  // waves still present
     BVH_STACK_LDS(ACCEL, SEG);
@@ -553,40 +634,21 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
     if (alive) {
         if (FIRST) {
             home = slot;
-            path_key<TILED>(a, home, &ka, &kb, &px, &py);
-            F4 uj = rng4(ka, kb, 0, a.seed);
-            float fx = (float)px + uj.x, fy = (float)py + uj.y;
-            camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
-            thr = {1, 1, 1};
-            L = {0, 0, 0};
-            eta = 1.0f;
-            prev_pdf = -1.0f;
+            camera_start(a, home, &ka, &kb, &o, &d, &tmax, &thr, &L, &eta, &prev_pdf);
         } else {
             const uint32_t v4 = state_voff(slot);
             constexpr uint32_t row = STATE_ROW_BYTES;
-            o = {bld(r_in, v4 + 0 * row, 0), bld(r_in, v4 + 1 * row, 0), bld(r_in, v4 + 2 * row, 0)};
-            d = {bld(r_in, v4 + 3 * row, 0), bld(r_in, v4 + 4 * row, 0), bld(r_in, v4 + 5 * row, 0)};
-            thr = {bld(r_in, v4 + 6 * row, 0), bld(r_in, v4 + 7 * row, 0), bld(r_in, v4 + 8 * row, 0)};
-            L = {bld(r_in, v4 + 9 * row, 0), bld(r_in, v4 + 10 * row, 0), bld(r_in, v4 + 11 * row, 0)};
-            eta = bld(r_in, v4 + 12 * row, 0);
-            prev_pdf = bld(r_in, v4 + 13 * row, 0);
-            home = __float_as_uint(bld(r_in, v4 + 14 * row, 0));
-            tmax = (a.key_mode == 1 && a.depth == 0) ? eta : K_INF;  // caller rays carry tmax in the eta slot
+            STATE_LOAD(STATE_BLD, o, d, thr, L, eta, prev_pdf, home);
+            tmax = (a.key_mode == 1 && a.depth == 0) ? eta : K_INF;  // caller rays: ST_ETA
             if (a.key_mode == 1 && a.depth == 0) eta = 1.0f;
         }
     }
     // shading tables -> LDS, behind the state loads so that the two memory round trips overlap
     if (ACCEL == ACCEL_K_BRUTE && !FIRST && !DYN && it0 == 0) fill_tables_lds(a.sc, tab_lds, live_threads);
-    if (alive && !FIRST) path_key<TILED>(a, home, &ka, &kb, &px, &py);
+    if (alive && !FIRST) path_key(a, home, &ka, &kb, &px, &py);
     bool live = alive;                        // the lane still carries a path
-    // the wave's camera rays are the 8 x 8 tile of one sample (or, on a region whose width is no multiple of 8, a few tiles): the
-    // closest-hit walk of bounce 0 leaves out what the keep word of its 64 region indices rules out (one scalar load)
     uint32_t keep = 0xffffffffu;
-    if (FIRST && ACCEL == ACCEL_K_BRUTE && !DYN && a.tile_keep) {
-        const uint32_t home0 = base + ((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u);
-        const uint32_t blk = (home0 - udiv_fast(home0, a.div_npix) * a.npix_r) >> 6;
-        keep = load_uniform<uint32_t>(a.tile_keep + min(blk, (a.npix_r >> 6) - 1u));
-    }
+    if (FIRST && ACCEL == ACCEL_K_BRUTE && !DYN && a.tile_keep) keep = camera_keep_word(a, base, tid);
     uint32_t nseg_w = 0, nshd_w = 0, nmid_w = 0, nmid_hi_w = 0;  // wave-uniform counts over the launch's bounces
 #pragma unroll 1
     for (uint32_t bounce = 0; bounce < nb_run; ++bounce) {
@@ -623,7 +685,7 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
     // ---- segment-local stream compaction: ballot + mbcnt inside the wave, LDS scan across waves
     const uint32_t wid = tid >> 6;
     const unsigned long long bal = __ballot(survive);
-    const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    const uint32_t prefix = ballot_rank(bal);
     uint32_t off = 0, total = 0;
     if (DYN) {  // reserve the survivors' slots in the region with one returning LDS atomic per wave and chunk
         const uint32_t cnt_w = (uint32_t)__popcll(bal);
@@ -644,35 +706,12 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
         }
     }
     __syncthreads();
-    // exclusive scan over the waves' survivor counts on the scalar unit: one LDS read per lane, then
-    // v_readlane + s_add per wave (the per-lane form cost 40 VALU per wave-bounce)
-        const uint32_t t_lane = wave_tot[buf][tid & (SEG / 64 - 1)];
-        const uint32_t wid_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wid);
-#pragma unroll
-        for (uint32_t w = 0; w < SEG / 64; ++w) {
-            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)t_lane, (int)w);
-            off += (w < wid_s) ? t : 0u;
-            total += t;
-        }
+        WAVE_SCAN(W, wave_tot[buf], tid, wid, off, total);
     }
     if (survive) {
         const uint32_t v4 = state_voff(base + out_off + off + prefix);
         constexpr uint32_t row = STATE_ROW_BYTES;
-        bst(r_out, v4 + 0 * row, 0, o.x);
-        bst(r_out, v4 + 1 * row, 0, o.y);
-        bst(r_out, v4 + 2 * row, 0, o.z);
-        bst(r_out, v4 + 3 * row, 0, d.x);
-        bst(r_out, v4 + 4 * row, 0, d.y);
-        bst(r_out, v4 + 5 * row, 0, d.z);
-        bst(r_out, v4 + 6 * row, 0, thr.x);
-        bst(r_out, v4 + 7 * row, 0, thr.y);
-        bst(r_out, v4 + 8 * row, 0, thr.z);
-        bst(r_out, v4 + 9 * row, 0, L.x);
-        bst(r_out, v4 + 10 * row, 0, L.y);
-        bst(r_out, v4 + 11 * row, 0, L.z);
-        bst(r_out, v4 + 12 * row, 0, eta);
-        bst(r_out, v4 + 13 * row, 0, prev_pdf);
-        bst(r_out, v4 + 14 * row, 0, __uint_as_float(home));
+        STATE_STORE(STATE_BST, o, d, thr, L, eta, prev_pdf, home);
     }
     out_off += total;
     if (!DYN && tid == 0) {
@@ -718,8 +757,8 @@ __global__ __launch_bounds__(seg_threads(accel_base(ACCEL_T)), ACCEL_T == ACCEL_
 
 // ---- k_path: camera paths of an ACCEL_K_BRUTE scene walked to their end in ONE launch --------------------------------------------
 // When the fuse plan walks every bounce of a pass in one launch (max_depth <= MAX_CHAIN) no path outlives the launch: there is
-// nothing to compact, no state to write and no survivor count to publish.  k_path is that launch without the machinery: the same
-// camera start, keep word, bounce_step and RNG keys as k_bounce<true, .., 2> in the same order (same film, bit for bit), but
+// nothing to compact, no state to write and no survivor count to publish.  k_path is that launch without the machinery:
+// camera_start, camera_keep_word and bounce_step as k_bounce<true, .., 2> calls them, in the same order (same film, bit for bit), but
 //   * no barrier after the one that ends the table staging: the waves of a workgroup end on their own, and their slots are free
 //     for the next workgroup's waves at once;
 //   * a lane keeps L when its path ends and the wave stores its 64 records after the bounce loop, 1 KiB contiguous;
@@ -793,19 +832,10 @@ __global__ __launch_bounds__(THREADS, FUSED_WAVES_PER_EU) void k_path(const Path
     const uint32_t home = base + tid;
     V3 o = {0, 0, 0}, d = {0, 0, 1}, thr = {1, 1, 1}, L = {0, 0, 0};
     float eta = 1.0f, prev_pdf = -1.0f, tmax = K_INF;
-    uint32_t ka = 0, kb = 0, px = 0, py = 0;
-    if (alive) {
-        path_key<true>(a, home, &ka, &kb, &px, &py);
-        F4 uj = rng4(ka, kb, 0, a.seed);
-        float fx = (float)px + uj.x, fy = (float)py + uj.y;
-        camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), &o, &d, &tmax);
-    }
-    uint32_t keep = 0xffffffffu;  // as k_bounce: the keep word of the wave's 64 region indices
-    if (a.tile_keep) {
-        const uint32_t home0 = base + ((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u);
-        const uint32_t blk = (home0 - udiv_fast(home0, a.div_npix) * a.npix_r) >> 6;
-        keep = load_uniform<uint32_t>(a.tile_keep + min(blk, (a.npix_r >> 6) - 1u));
-    }
+    uint32_t ka = 0, kb = 0;
+    if (alive) camera_start(a, home, &ka, &kb, &o, &d, &tmax);
+    uint32_t keep = 0xffffffffu;
+    if (a.tile_keep) keep = camera_keep_word(a, base, tid);
     bool live = alive;
     uint32_t nseg_w = 0, nshd_w = 0;
     unsigned long long non_w = 0;  // paths of the wave that went on to bounce k (1 .. MAX_CHAIN - 1): 8 bits each
@@ -829,11 +859,7 @@ __global__ __launch_bounds__(THREADS, FUSED_WAVES_PER_EU) void k_path(const Path
         nshd_w += (uint32_t)__popcll(__ballot(did_shadow));
     }
     // one record per path, 64 consecutive homes per wave
-    if (alive) {
-        typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-        const u32x4 rec = {__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u};
-        __builtin_amdgcn_raw_buffer_store_b128(rec, make_rsrc(a.Lhome, a.cap * 16u), home * 16u, 0, 0);
-    }
+    if (alive) store_record(make_rsrc(a.Lhome, a.cap * 16u), home, L);
     // statistics: every wave adds its counts to the workgroup's, the last one to arrive adds those to the row (LDS atomics of one
     // CU are ordered, as the q_done of k_bounce's chunk queue relies on); nobody waits
     if ((tid & 63u) == 0) {
@@ -881,7 +907,7 @@ __global__ __launch_bounds__(64) void k_tile_keep(const TileKeepArgs a) {
     if (blk >= a.n_blocks) return;
     uint32_t x0 = 0xffffffffu, y0 = 0xffffffffu, x1 = 0, y1 = 0;
     for (uint32_t k = 0; k < 64u; ++k) {
-        const uint32_t pr = blk * 64u + k;  // as path_key<TILED>
+        const uint32_t pr = blk * 64u + k;  // as path_key
         const bool tiled = pr < a.tile_rows * a.rw;
         const uint32_t num = tiled ? pr >> 3 : pr;
         const uint32_t q = udiv_fast(num, a.div_rw);
@@ -1140,19 +1166,19 @@ __global__ __launch_bounds__(256) void k_init_rays(float *st, uint32_t *seg_cnt,
     if (i < n_cnt) seg_cnt[i] = n > i * region ? min(n - i * region, region) : 0u;
     if (i >= n) return;
     float *s = st + (state_voff(i) >> 2);  // tiled SoA: row k at +64 * k floats
-    s[0 * 64] = o[i];
-    s[1 * 64] = o[n + i];
-    s[2 * 64] = o[2 * n + i];
-    s[3 * 64] = d[i];
-    s[4 * 64] = d[n + i];
-    s[5 * 64] = d[2 * n + i];
-    s[6 * 64] = 1.0f;
-    s[7 * 64] = 1.0f;
-    s[8 * 64] = 1.0f;
-    s[9 * 64] = 0.0f;
-    s[10 * 64] = 0.0f;
-    s[11 * 64] = 0.0f;
-    s[12 * 64] = tmax[i];  // consumed as tmax by the first bounce
-    s[13 * 64] = -1.0f;
-    s[14 * 64] = __uint_as_float(i);
+    s[(ST_O + 0) * 64] = o[i];
+    s[(ST_O + 1) * 64] = o[n + i];
+    s[(ST_O + 2) * 64] = o[2 * n + i];
+    s[(ST_D + 0) * 64] = d[i];
+    s[(ST_D + 1) * 64] = d[n + i];
+    s[(ST_D + 2) * 64] = d[2 * n + i];
+    s[(ST_THR + 0) * 64] = 1.0f;
+    s[(ST_THR + 1) * 64] = 1.0f;
+    s[(ST_THR + 2) * 64] = 1.0f;
+    s[(ST_L + 0) * 64] = 0.0f;
+    s[(ST_L + 1) * 64] = 0.0f;
+    s[(ST_L + 2) * 64] = 0.0f;
+    s[ST_ETA * 64] = tmax[i];  // a caller ray: the first bounce takes the row as tmax
+    s[ST_PDF * 64] = -1.0f;
+    s[ST_HOME * 64] = __uint_as_float(i);
 }

@@ -534,7 +534,7 @@ __global__ __launch_bounds__(seg_threads(ACCEL), us_waves_per_eu(ACCEL)) void k_
     }
     const uint32_t wid = tid >> 6;
     const unsigned long long bal = __ballot(survive);
-    const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    const uint32_t prefix = ballot_rank(bal);
     const unsigned long long bseg = __ballot(did_seg);
     uint32_t off = 0, total = 0;
     if (WP) {  // the wave packs its own survivors behind its own cursor

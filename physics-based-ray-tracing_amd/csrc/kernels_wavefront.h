@@ -60,8 +60,6 @@ static_assert(WF_REFILL_MIN + WF_WALK_MIN <= 65u, "k_trace: a wave below WF_WALK
 
 // paths of region r when n paths fill the regions from the first one on
 DEV uint32_t wf_region_fill(uint32_t n, uint32_t r) { return n > r * WF_REGION ? min(n - r * WF_REGION, WF_REGION) : 0u; }
-// rank of a lane among the lanes of ballot b below it
-DEV uint32_t ballot_rank(unsigned long long b) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u)); }
 // one slot per lane of ballot b (b != 0) behind an LDS counter: one atomic of lane 0 for the wave; returns the lane's offset
 DEV uint32_t ballot_reserve(uint32_t *counter, unsigned long long b, uint32_t lane) {
     uint32_t got = 0;
@@ -91,32 +89,6 @@ struct WfArgs {
     uint32_t *guard;             // WF_GUARD_WORDS words of the context: [0] waves that ran into the turn guard, [1..30] state of one of them,
                                  // [WF_GUARD_REHIT] hits whose (t, u, v) the shading kernels could not reproduce
 };
-
-DEV RadArgs wf_key_args(const WfArgs &a) {  // path_key reads these members only
-    RadArgs r;
-    r.key_mode = a.key_mode;
-    r.rx0 = a.rx0;
-    r.ry0 = a.ry0;
-    r.rw = a.rw;
-    r.npix_r = a.npix_r;
-    r.s_first = a.s_first;
-    r.film_w = a.film_w;
-    r.film_h = a.film_h;
-    r.tile_rows = a.tile_rows;
-    r.div_npix = a.div_npix;
-    r.div_rw = a.div_rw;
-    r.index_offset = a.index_offset;
-    r.sample_index = a.sample_index;
-    return r;
-}
-DEV void wf_camera_ray(const WfArgs &a, uint32_t home, V3 *o, V3 *d, float *tmax, uint32_t *ka, uint32_t *kb) {
-    uint32_t px, py;
-    const RadArgs ra = wf_key_args(a);
-    path_key<true>(ra, home, ka, kb, &px, &py);
-    F4 uj = rng4(*ka, *kb, 0, a.seed);
-    float fx = (float)px + uj.x, fy = (float)py + uj.y;
-    camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), o, d, tmax);
-}
 
 // Every loop of the stream has an exit that each wave reaches; the guard below is the net under it: a wave that exceeds
 // WF_GUARD_TURNS turns leaves AS A WHOLE, records its state in the context's guard words (WfArgs::guard) and the host reports
@@ -284,7 +256,7 @@ __global__ __launch_bounds__(1024, WF_TRACE_WAVES_PER_EU) void k_trace(const WfA
                 const uint32_t slot = (first & 0x3fffffffu) + (i - cum[s]);
                 if (FIRST) {
                     uint32_t ka, kb;
-                    wf_camera_ray(a, slot, &o, &d, &best, &ka, &kb);
+                    camera_start(a, slot, &ka, &kb, &o, &d, &best);
                     rslot = slot;
                 } else {
                     const float4 *rec = ((first & WF_SHADOW) ? a.shd_in : a.st_in) + slot;
@@ -394,7 +366,7 @@ __global__ __launch_bounds__(1024, WF_TRACE_WAVES_PER_EU) void k_trace_primary(c
         uint32_t hid = 0xffffffffu;
         if (alive) {
             uint32_t ka, kb;
-            wf_camera_ray(a, slot, &o, &d, &best, &ka, &kb);
+            camera_start(a, slot, &ka, &kb, &o, &d, &best);
         }
         // the representative ray: the middle of the tile (lane = 8 x + y), or the first lane that has a ray
         const unsigned long long ba = __ballot(alive);
@@ -680,7 +652,7 @@ struct RadShade {
         if (FIRST) {
             float tm;
             p.home = slot;
-            wf_camera_ray(a, p.home, &p.o, &p.d, &tm, &ka, &kb);
+            camera_start(a, p.home, &ka, &kb, &p.o, &p.d, &tm);
         } else {
             const float4 *stp = a.st_in + slot;
             const size_t cp = a.cap;
@@ -694,8 +666,7 @@ struct RadShade {
             p.prev_pdf = q1.w;
             p.home = __float_as_uint(lh.w);
             uint32_t px, py;
-            const RadArgs ra = wf_key_args(a);
-            path_key<true>(ra, p.home, &ka, &kb, &px, &py);
+            path_key(a, p.home, &ka, &kb, &px, &py);
         }
         // (t, u, v) of the hit k_trace found: the same test on the same operands (a leaf record is the first nine floats of P).
         // Should the repetition ever disagree (other build flags, another code path for the primitive) the call fails with

@@ -92,7 +92,7 @@ static pbrt_camera look_at(double ox, double oy, double oz, double tx, double ty
     return c;
 }
 
-// the pixel of region index pr: the inverse of region_index (kernels_radiance.h path_key<TILED>), region = the whole film
+// the pixel of region index pr: the inverse of region_index (kernels_radiance.h path_key), region = the whole film
 static void pixel_of(uint32_t pr, uint32_t rw, uint32_t tile_rows, uint32_t *x, uint32_t *y) {
     const bool tiled = pr < tile_rows * rw;
     const uint32_t num = tiled ? pr >> 3 : pr, q = num / rw;

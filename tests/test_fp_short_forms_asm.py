@@ -27,6 +27,10 @@ CEILINGS = {
     # k_us_bounce_convex<true, 0, false> (50 / 3) -- the same code under the one kernel name, so no margin
     "_Z7k_shadeILb1ELb1ELb1ELb1EEv6WfArgs": (23, 0),  # k_shade<true, true, true, true>
     "_Z11k_us_bounceILb1ELi0ELb0ELj4294967295ELin1ELb1EEv6UsArgs": (50, 3),  # k_us_bounce<true, 0, false, 0xffffffff, -1, true>
+    # the ordered chain instances: the first to move when the path-record load / store or the wave scan change form
+    # (profiles/shared_path_start.md); what they spill today, no margin
+    "_Z8k_bounceILb1ELi5ELi2EEv7RadArgs": (28, 1),  # k_bounce<true, ACCEL_K_BRUTE_ORDERED, 2>
+    "_Z8k_bounceILb0ELi5ELi2EEv7RadArgs": (48, 1),  # k_bounce<false, ACCEL_K_BRUTE_ORDERED, 2>
 }
 
 
