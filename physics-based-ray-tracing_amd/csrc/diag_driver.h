@@ -196,10 +196,10 @@ static int diag_render(Render &r) {
     for (PassSchedule p{f->spp, r.ps.per_pass, r.fp.probe}; p.next(); ++r.passes) {
         RadArgs a = r.base;
         a.n_paths = (uint32_t)(r.rq.npix_r * p.sc);
-        a.s_first = f->sample_offset + p.s0;
+        a.key.s_first = f->sample_offset + p.s0;
         if ((rc = diag_pass(r, dg, a, div_up(a.n_paths, r.rq.launch.region))) != 0) return rc;
         if ((rc = r.timer.end()) != 0) return rc;
-        r.fa.s_first = a.s_first;
+        r.fa.key.s_first = a.key.s_first;
         r.fa.s_count = p.sc;
         film_accum(c, r.fa);
         HIPCHK(c, hipGetLastError());

@@ -118,15 +118,18 @@ struct RadArgs {
     uint32_t merge_at;  // k_chain_pair: the bounce from which a wave walks the survivors of its two tiles together (1 .. max_depth - 1)
     // key mode 0 (render): home -> (region pixel, local sample)
     uint32_t key_mode;
-    uint32_t rx0, ry0, rw, npix_r, s_first, film_w, film_h;
-    uint32_t tile_rows;  // rows of the region in 8-row bands (region_index); 0 for the brute-force kernels
-    FastDiv div_npix, div_rw;  // exact home / npix_r and pr / rw without the 20-instruction variable udiv
+    FilmKey key;
     // key mode 1 (Integrator.sample on caller rays): key = (index_offset + home, sample_index)
     uint32_t index_offset, sample_index;
     uint32_t lds_bytes;  // ACCEL_K_BVH_LDS: bytes of nodes + prims + ids staged per workgroup
     // key mode 0, ACCEL_K_BRUTE, npix_r % 64 == 0: the keep words of the camera tiles, [npix_r / 64] (k_tile_keep); nullptr: none
     const uint32_t *tile_keep;
 };
+// kernel-argument layout is part of a kernel's figures: the key stands where its ten members stood, nothing behind it moved
+static_assert(offsetof(RadArgs, repack_mask) == 292 && offsetof(RadArgs, key_mode) == 300 && offsetof(RadArgs, key) == 304 &&
+                  offsetof(RadArgs, index_offset) == 368 && offsetof(RadArgs, sample_index) == 372 && offsetof(RadArgs, tile_keep) == 384 &&
+                  sizeof(RadArgs) == 392,
+              "RadArgs keeps its bytes");
 
 // Path state is tiled SoA: 64 consecutive slots (one wave) form a tile of N_STATE rows x 64 lanes = 3840 contiguous
 // bytes, row k of a slot at byte  tile(slot) + k * 256 + lane * 4.  Accessed through buffer descriptors:
@@ -192,15 +195,6 @@ DEV void bst(Rsrc r, uint32_t voff, uint32_t soff, float v) {
         put(ST_HOME, __uint_as_float(home));                           \
     }
 
-// Pixel order inside the rendered region (index k of a pixel = its slot within one sample's block of `Lhome` and
-// of the first-bounce state).  The region is cut into bands of 8 rows and a band is walked column by column, so
-// the 64 consecutive paths of a wave are an 8 x 8 pixel tile, not a 64 x 1 strip -- on a BVH their primary rays
-// visit fewer distinct nodes (every lane of a wave pays for the union; path_key).  The rh % 8 rows below the last
-// full band keep the row-major order; tile_rows = rh & ~7 (0: plain row-major everywhere).
-DEV uint32_t region_index(uint32_t xx, uint32_t yy, uint32_t rw, uint32_t tile_rows) {
-    return yy < tile_rows ? (yy >> 3) * (8u * rw) + (xx << 3) + (yy & 7u) : yy * rw + xx;
-}
-
 // Workgroup b runs on XCD b % 8 (round-robin dispatch), and consecutive regions are consecutive pixels of a row: on a film
 // that is 8 segments wide (4096 px) XCD k would render column stripe k of EVERY row -- the XCDs with the spheres in their stripe
 // finish last (cbox 4096^2: the later bounces 18-40 % slower than on the 512^2 film with the same paths).  Rotating the regions
@@ -216,23 +210,21 @@ DEV uint32_t xcd_swizzle(uint32_t b, uint32_t n) {
     return (b & ~7u) | ((b + rot) & 7u);
 }
 
-// The RNG key (ka, kb) and the pixel of the path whose home slot is `home`.  Key mode 0 inverts region_index (one division either
-// way), in every kernel: 8 x 8 pixel tiles per wave are coherent rays for the BVH kernels; for the brute-force kernels, whose
+// The RNG key (ka, kb) and the pixel of the path whose home slot is `home`.  Key mode 0 inverts region_index (region_pixel, film_key.h),
+// in every kernel: 8 x 8 pixel tiles per wave are coherent rays for the BVH kernels; for the brute-force kernels, whose
 // primitive loop does not care, they keep the long paths of a chain launch (the pixels of the glass and the mirror sphere) together
 // in the same waves instead of one or two lanes in every wave of a row: Cornell box, one launch per pass, 6.41 -> 6.25 ms.
-// Args: RadArgs, WfArgs, or PathArgs (k_path: key mode 0 as a constant)
+// Args: RadArgs, WfArgs, or PathArgs (k_path: key mode 0 as a constant): key_mode, the film key, index_offset, sample_index
 template <class Args>
 DEV void path_key(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, uint32_t *px, uint32_t *py) {
     if (a.key_mode == 0) {
-        uint32_t sl = udiv_fast(home, a.div_npix), pr = home - sl * a.npix_r;
-        const bool tiled = pr < a.tile_rows * a.rw;
-        const uint32_t num = tiled ? pr >> 3 : pr;
-        const uint32_t q = udiv_fast(num, a.div_rw);
-        const uint32_t rx = num - q * a.rw, ry = tiled ? (q << 3) + (pr & 7u) : q;
-        *px = a.rx0 + rx;
-        *py = a.ry0 + ry;
-        *ka = *py * a.film_w + *px;
-        *kb = a.s_first + sl;
+        const FilmKey &k = a.key;
+        uint32_t sl = udiv_fast(home, k.div_npix), pr = home - sl * k.npix_r, rx, ry;
+        region_pixel(k, pr, &rx, &ry);
+        *px = k.rx0 + rx;
+        *py = k.ry0 + ry;
+        *ka = *py * k.film_w + *px;
+        *kb = k.s_first + sl;
     } else {
         *ka = a.index_offset + home;
         *kb = a.sample_index;
@@ -246,7 +238,7 @@ DEV void camera_start(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, 
     path_key(a, home, ka, kb, &px, &py);
     F4 uj = rng4(*ka, *kb, 0, a.seed);
     float fx = (float)px + uj.x, fy = (float)py + uj.y;
-    camera_ray(a.cam, film_coord(fx, a.film_w), film_coord(fy, a.film_h), o, d, tmax);
+    camera_ray(a.cam, film_coord(fx, a.key.film_w), film_coord(fy, a.key.film_h), o, d, tmax);
 }
 // ... and the state a path starts with, for the kernels whose lanes start more than one path
 template <class Args>
@@ -264,8 +256,8 @@ DEV void camera_start(const Args &a, uint32_t home, uint32_t *ka, uint32_t *kb, 
 template <class Args>
 DEV uint32_t camera_keep_word(const Args &a, uint32_t base, uint32_t tid) {
     const uint32_t home0 = base + ((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u);
-    const uint32_t blk = (home0 - udiv_fast(home0, a.div_npix) * a.npix_r) >> 6;
-    return load_uniform<uint32_t>(a.tile_keep + min(blk, (a.npix_r >> 6) - 1u));
+    const uint32_t blk = (home0 - udiv_fast(home0, a.key.div_npix) * a.key.npix_r) >> 6;
+    return load_uniform<uint32_t>(a.tile_keep + min(blk, (a.key.npix_r >> 6) - 1u));
 }
 // One 16-byte radiance record per finished path: three 4-byte row stores at a scattered `home` cost three 32-byte HBM sectors
 // (measured: k_bounce WRITE_SIZE 1.23 x algorithmic), one dwordx4 store costs one.
@@ -781,10 +773,10 @@ struct PathArgs {
     unsigned long long *stats;  // as RadArgs::stats; one row per workgroup of the launch
     const uint32_t *tile_keep;  // as RadArgs::tile_keep
     uint32_t stat_stride, cap, n_paths, max_depth, rr_depth, seed;
-    uint32_t rx0, ry0, rw, npix_r, s_first, film_w, film_h, tile_rows;
-    FastDiv div_npix, div_rw;
+    FilmKey key;
     static constexpr uint32_t key_mode = 0, index_offset = 0, sample_index = 0;  // (path_key)
 };
+static_assert(offsetof(PathArgs, seed) == 252 && offsetof(PathArgs, key) == 256 && sizeof(PathArgs) == 320, "PathArgs keeps its bytes");
 // what k_path reads of the arguments of a bounce launch (host)
 static inline PathArgs path_args(const RadArgs &a) {
     PathArgs p;
@@ -799,16 +791,7 @@ static inline PathArgs path_args(const RadArgs &a) {
     p.max_depth = a.max_depth;
     p.rr_depth = a.rr_depth;
     p.seed = a.seed;
-    p.rx0 = a.rx0;
-    p.ry0 = a.ry0;
-    p.rw = a.rw;
-    p.npix_r = a.npix_r;
-    p.s_first = a.s_first;
-    p.film_w = a.film_w;
-    p.film_h = a.film_h;
-    p.tile_rows = a.tile_rows;
-    p.div_npix = a.div_npix;
-    p.div_rw = a.div_rw;
+    p.key = a.key;
     return p;
 }
 template <int ACCEL_T, int THREADS>
@@ -892,26 +875,23 @@ __global__ __launch_bounds__(THREADS, FUSED_WAVES_PER_EU) void k_path(const Path
 // The keep table of a radiance render of an ACCEL_K_BRUTE scene (RadArgs::tile_keep): word b = which of the <= 32 primitives the
 // camera rays of region indices [64 b, 64 b + 63] can meet, bit i = primitive i of sc.prims (tile_cull.h decides, in double; a
 // cleared bit is a proof that the float test rejects).  The rectangle of a block is the bounding box of its 64 pixels through
-// the inverse of region_index: one 8 x 8 tile when the region's width is a multiple of 8, a few tiles or a piece of the row-major
-// tail otherwise.  One thread per word; a render runs it once, ahead of its first pass (microseconds).
+// region_pixel, as path_key hands them to a wave: one 8 x 8 tile when the region's width is a multiple of 8, a few tiles or a piece
+// of the row-major tail otherwise.  One thread per word; a render runs it once, ahead of its first pass (microseconds).
 struct TileKeepArgs {
     const pbrt_prim *prims;
     uint32_t n_prims;  // <= 32
     pbrt_camera cam;
-    uint32_t rx0, ry0, rw, tile_rows, n_blocks;
-    FastDiv div_rw;
-    uint32_t *keep;  // [n_blocks]
+    FilmKey key;
+    uint32_t n_blocks;  // key.npix_r / 64
+    uint32_t *keep;     // [n_blocks]
 };
 __global__ __launch_bounds__(64) void k_tile_keep(const TileKeepArgs a) {
     const uint32_t blk = blockIdx.x * 64u + threadIdx.x;
     if (blk >= a.n_blocks) return;
     uint32_t x0 = 0xffffffffu, y0 = 0xffffffffu, x1 = 0, y1 = 0;
     for (uint32_t k = 0; k < 64u; ++k) {
-        const uint32_t pr = blk * 64u + k;  // as path_key
-        const bool tiled = pr < a.tile_rows * a.rw;
-        const uint32_t num = tiled ? pr >> 3 : pr;
-        const uint32_t q = udiv_fast(num, a.div_rw);
-        const uint32_t rx = num - q * a.rw, ry = tiled ? (q << 3) + (pr & 7u) : q;
+        uint32_t rx, ry;
+        region_pixel(a.key, blk * 64u + k, &rx, &ry);
         x0 = min(x0, rx);
         x1 = max(x1, rx);
         y0 = min(y0, ry);
@@ -920,7 +900,7 @@ __global__ __launch_bounds__(64) void k_tile_keep(const TileKeepArgs a) {
     uint32_t word = 0;
     for (uint32_t i = 0; i < a.n_prims && i < 32u; ++i) {
         const pbrt_prim P = load_prim_uniform(a.prims + i);
-        if (tile_cull_keep(a.cam, a.rx0 + x0, a.ry0 + y0, a.rx0 + x1, a.ry0 + y1, P)) word |= 1u << i;
+        if (tile_cull_keep(a.cam, a.key.rx0 + x0, a.key.ry0 + y0, a.key.rx0 + x1, a.key.ry0 + y1, P)) word |= 1u << i;
     }
     word |= a.n_prims < 32u ? ~0u << a.n_prims : 0u;  // bits without a primitive stay set: a full word means "nothing culled"
     a.keep[blk] = word;
@@ -973,9 +953,9 @@ struct FilmArgs {
     float *acc;          // [4][cw*ch] running sums (w*r, w*g, w*b, w)
     uint32_t cap;
     uint32_t cx0, cy0, cw, ch;     // crop
-    uint32_t rx0, ry0, rw, rh;     // rendered region (crop + halo, clipped to the film)
-    uint32_t npix_r, s_first, s_count, film_w, film_h, filter, seed;
-    uint32_t tile_rows;            // pixel order of Lhome (region_index)
+    FilmKey key;                   // the pass's: region, pixel order of Lhome (region_index), first sample
+    uint32_t rh;                   // rows of the region
+    uint32_t s_count, filter, seed;
 };
 
 DEV float filter_1d(uint32_t f, float x) {
@@ -994,19 +974,19 @@ __global__ __launch_bounds__(256) void k_film_accum(const FilmArgs a) {
     const int R = a.filter == PBRT_FILTER_BOX ? 0 : (a.filter == PBRT_FILTER_TENT ? 1 : 2);
     const float ccx = (float)x + 0.5f, ccy = (float)y + 0.5f;
     for (uint32_t sl = 0; sl < a.s_count; ++sl) {
-        const uint32_t s_idx = a.s_first + sl;
-        const float4 *Ls = reinterpret_cast<const float4 *>(a.Lhome) + (size_t)sl * a.npix_r;
+        const uint32_t s_idx = a.key.s_first + sl;
+        const float4 *Ls = reinterpret_cast<const float4 *>(a.Lhome) + (size_t)sl * a.key.npix_r;
         for (int ny = y - R; ny <= y + R; ++ny)
             for (int nx = x - R; nx <= x + R; ++nx) {
-                if (nx < 0 || ny < 0 || nx >= (int)a.film_w || ny >= (int)a.film_h) continue;
+                if (nx < 0 || ny < 0 || nx >= (int)a.key.film_w || ny >= (int)a.key.film_h) continue;
                 float w = 1.0f;
                 if (a.filter != PBRT_FILTER_BOX) {
-                    F4 uj = rng4((uint32_t)ny * a.film_w + (uint32_t)nx, s_idx, 0, a.seed);
+                    F4 uj = rng4((uint32_t)ny * a.key.film_w + (uint32_t)nx, s_idx, 0, a.seed);
                     float px = (float)nx + uj.x, py = (float)ny + uj.y;
                     w = filter_1d(a.filter, ccx - px) * filter_1d(a.filter, ccy - py);
                 }
                 if (w > 0.0f) {
-                    const uint32_t k = region_index((uint32_t)(nx - (int)a.rx0), (uint32_t)(ny - (int)a.ry0), a.rw, a.tile_rows);
+                    const uint32_t k = region_index((uint32_t)(nx - (int)a.key.rx0), (uint32_t)(ny - (int)a.key.ry0), a.key.rw, a.key.tile_rows);
                     const float4 Lk = Ls[k];
                     ar = fma_(w, Lk.x, ar);
                     ag = fma_(w, Lk.y, ag);
@@ -1068,9 +1048,9 @@ __global__ __launch_bounds__(FILM_TILE *FILM_TILE) void k_film_accum_tiled(const
         const int nx = tx0 - R + i % TW, ny = ty0 - R + i / TW;
         st_lds[j] = (i / TW) * LS + i % TW;
         st_in[j] = i < TW * TW;
-        st_valid[j] = st_in[j] && nx >= (int)a.rx0 && ny >= (int)a.ry0 && nx < (int)(a.rx0 + a.rw) && ny < (int)(a.ry0 + a.rh);
-        st_key[j] = (uint32_t)ny * a.film_w + (uint32_t)nx;
-        st_k[j] = st_valid[j] ? region_index((uint32_t)(nx - (int)a.rx0), (uint32_t)(ny - (int)a.ry0), a.rw, a.tile_rows) : 0u;
+        st_valid[j] = st_in[j] && nx >= (int)a.key.rx0 && ny >= (int)a.key.ry0 && nx < (int)(a.key.rx0 + a.key.rw) && ny < (int)(a.key.ry0 + a.rh);
+        st_key[j] = (uint32_t)ny * a.key.film_w + (uint32_t)nx;
+        st_k[j] = st_valid[j] ? region_index((uint32_t)(nx - (int)a.key.rx0), (uint32_t)(ny - (int)a.key.ry0), a.key.rw, a.key.tile_rows) : 0u;
         st_x[j] = (float)nx;
         st_y[j] = (float)ny;
     }
@@ -1087,13 +1067,13 @@ __global__ __launch_bounds__(FILM_TILE *FILM_TILE) void k_film_accum_tiled(const
     for (int u = 0; u < PF; ++u)
 #pragma unroll
         for (int j = 0; j < NST; ++j)
-            Lq[u][j] = (st_valid[j] && (uint32_t)u < a.s_count) ? Lrec[(size_t)u * a.npix_r + st_k[j]] : zero4;
+            Lq[u][j] = (st_valid[j] && (uint32_t)u < a.s_count) ? Lrec[(size_t)u * a.key.npix_r + st_k[j]] : zero4;
     for (uint32_t sl0 = 0; sl0 < a.s_count; sl0 += PF) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
             const uint32_t sl = sl0 + (uint32_t)u;
             if (sl >= a.s_count) break;
-            const uint32_t s_idx = a.s_first + sl;
+            const uint32_t s_idx = a.key.s_first + sl;
             float(*T)[FILM_TW * LS] = tile[sl & 1];
 #pragma unroll
             for (int j = 0; j < NST; ++j) {
@@ -1113,7 +1093,7 @@ __global__ __launch_bounds__(FILM_TILE *FILM_TILE) void k_film_accum_tiled(const
             }
 #pragma unroll
             for (int j = 0; j < NST; ++j)
-                Lq[u][j] = (st_valid[j] && sl + PF < a.s_count) ? Lrec[(size_t)(sl + PF) * a.npix_r + st_k[j]] : zero4;
+                Lq[u][j] = (st_valid[j] && sl + PF < a.s_count) ? Lrec[(size_t)(sl + PF) * a.key.npix_r + st_k[j]] : zero4;
             __syncthreads();
             if (inside) {
                 const int e0 = (int)threadIdx.y * LS + (int)threadIdx.x;

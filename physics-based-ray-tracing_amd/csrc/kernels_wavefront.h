@@ -80,8 +80,8 @@ struct WfArgs {
     uint32_t stat_stride, cap, n_paths, n_regions;  // n_regions: regions of THIS launch, the first one is region0
     uint32_t region0;
     uint32_t depth, max_depth, rr_depth, seed;
-    uint32_t key_mode, rx0, ry0, rw, npix_r, s_first, film_w, film_h, tile_rows;
-    FastDiv div_npix, div_rw;
+    uint32_t key_mode;
+    FilmKey key;
     uint32_t index_offset, sample_index;
     uint32_t lds_bytes;          // ACCEL_K_BVH_LDS: bytes of the staged image
     uint32_t stk_rows, stk_shift;  // traversal stacks behind the image: rows, log2(threads of the workgroup)
@@ -89,6 +89,9 @@ struct WfArgs {
     uint32_t *guard;             // WF_GUARD_WORDS words of the context: [0] waves that ran into the turn guard, [1..30] state of one of them,
                                  // [WF_GUARD_REHIT] hits whose (t, u, v) the shading kernels could not reproduce
 };
+static_assert(offsetof(WfArgs, key_mode) == 332 && offsetof(WfArgs, key) == 336 && offsetof(WfArgs, index_offset) == 400 &&
+                  offsetof(WfArgs, sample_index) == 404 && offsetof(WfArgs, guard) == 424 && sizeof(WfArgs) == 432,
+              "WfArgs keeps its bytes (as RadArgs, kernels_radiance.h)");
 
 // Every loop of the stream has an exit that each wave reaches; the guard below is the net under it: a wave that exceeds
 // WF_GUARD_TURNS turns leaves AS A WHOLE, records its state in the context's guard words (WfArgs::guard) and the host reports

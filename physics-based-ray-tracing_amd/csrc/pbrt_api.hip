@@ -1018,10 +1018,10 @@ static uint64_t default_pass_paths(pbrt_ctx *c, bool streams, uint64_t paths, ui
     return streams ? wf_default_pass_paths(c) : fused_default_pass_paths(paths, bytes_per_path, c->work.limit);
 }
 
-// self-check of a fast divisor (device_math.h make_fastdiv) against `/` at the probe values of its caller
+// self-check of a fast divisor (film_key.h make_fastdiv) against `/` at the probe values of its caller
 static bool fastdiv_exact(const FastDiv &fd, uint32_t d, std::initializer_list<uint32_t> probes) {
     for (uint32_t n : probes)
-        if (udiv_fast_host(n, fd) != n / d) return false;
+        if (udiv_fast(n, fd) != n / d) return false;
     return true;
 }
 
@@ -1041,16 +1041,7 @@ static WfArgs wf_args(const RadArgs &a) {
     w.rr_depth = a.rr_depth;
     w.seed = a.seed;
     w.key_mode = a.key_mode;
-    w.rx0 = a.rx0;
-    w.ry0 = a.ry0;
-    w.rw = a.rw;
-    w.npix_r = a.npix_r;
-    w.s_first = a.s_first;
-    w.film_w = a.film_w;
-    w.film_h = a.film_h;
-    w.tile_rows = a.tile_rows;
-    w.div_npix = a.div_npix;
-    w.div_rw = a.div_rw;
+    w.key = a.key;
     w.index_offset = a.index_offset;
     w.sample_index = a.sample_index;
     return w;
@@ -1244,11 +1235,9 @@ static int render_args(Render &r) {
     base.rr_depth = f->rr_depth;
     base.seed = f->seed;
     base.key_mode = 0;
-    render_film_args(r.rq, &base);
-    base.div_npix = make_fastdiv(base.npix_r);
-    base.div_rw = make_fastdiv(rw);
-    const std::initializer_list<uint32_t> probes = {0u, 1u, rw - 1, rw, rw + 1, base.npix_r - 1, base.npix_r, base.npix_r + 1, cap - 1, cap, 0xffffffffu};
-    NEED(r.c, fastdiv_exact(base.div_npix, base.npix_r, probes) && fastdiv_exact(base.div_rw, rw, probes));
+    const FilmKey &key = base.key = render_film_key(r.rq);  // (s_first: the pass loop's)
+    const std::initializer_list<uint32_t> probes = {0u, 1u, rw - 1, rw, rw + 1, key.npix_r - 1, key.npix_r, key.npix_r + 1, cap - 1, cap, 0xffffffffu};
+    NEED(r.c, fastdiv_exact(key.div_npix, key.npix_r, probes) && fastdiv_exact(key.div_rw, rw, probes));
     base.lds_bytes = s->lds_bytes;
     base.tile_keep = nullptr;
     return PBRT_OK;
@@ -1264,7 +1253,7 @@ static void render_film(Render &r) {
     fa.cy0 = f->crop_y;
     fa.cw = f->crop_w;
     fa.ch = f->crop_h;
-    render_film_args(r.rq, &fa);
+    fa.key = r.base.key;
     fa.rh = r.rq.rh;
     fa.filter = f->filter;
     fa.seed = f->seed;
@@ -1280,9 +1269,8 @@ static int render_tile_keep(Render &r) {
     ta.prims = r.s->ds.prims;
     ta.n_prims = r.s->ds.n_prims;
     ta.cam = *r.cam;
-    render_region_args(r.rq, &ta);
-    ta.n_blocks = r.base.npix_r / 64;
-    ta.div_rw = r.base.div_rw;
+    ta.key = r.base.key;
+    ta.n_blocks = ta.key.npix_r / 64;
     ta.keep = (uint32_t *)c->buf("tile_keep", (size_t)ta.n_blocks * 4);
     if (!ta.keep) return PBRT_E_NOMEM;
     const pbrt_ctx::TileKeepKey key{c->work.generation("tile_keep"), r.s->serial, *r.cam, r.rq.rx0, r.rq.ry0, r.rq.rw, r.rq.rh};
@@ -1363,7 +1351,7 @@ static int render_passes(Render &r) {
     for (PassSchedule p{f->spp, r.ps.per_pass, r.fp.probe}; p.next(); ++r.passes) {
         RadArgs a = r.base;
         a.n_paths = (uint32_t)(r.rq.npix_r * p.sc);
-        a.s_first = f->sample_offset + p.s0;
+        a.key.s_first = f->sample_offset + p.s0;
         const uint32_t nseg_pass = div_up(a.n_paths, r.rq.launch.region);
         if (r.rq.wavefront) {
             if ((rc = r.timer.begin()) != 0) return rc;
@@ -1373,7 +1361,7 @@ static int render_passes(Render &r) {
         }
         if (rc) return rc;
         if ((rc = r.timer.end()) != 0) return rc;
-        r.fa.s_first = a.s_first;
+        r.fa.key.s_first = a.key.s_first;
         r.fa.s_count = p.sc;
         film_accum(c, r.fa);
         HIPCHK(c, hipGetLastError());
@@ -1548,6 +1536,13 @@ static int sample_upload(SampleCall &q) {
     return PBRT_OK;
 }
 
+// the film key of key mode 1, which has no film: path_key does not read it, and the two divisions by 1 stand where a render's are
+static FilmKey sample_key() {
+    FilmKey k{};
+    k.npix_r = k.rw = 1;
+    k.div_npix = k.div_rw = make_fastdiv(1);
+    return k;
+}
 // key_mode 1: key = (index_offset + home, sample_index) for the caller's n rays
 static void sample_args(SampleCall &q) {
     RadArgs &a = q.a;
@@ -1562,9 +1557,7 @@ static void sample_args(SampleCall &q) {
     a.rr_depth = q.rr_depth;
     a.seed = q.seed;
     a.key_mode = 1;
-    a.npix_r = 1;
-    a.rw = 1;
-    a.div_npix = a.div_rw = make_fastdiv(1);
+    a.key = sample_key();
     a.index_offset = q.index_offset;
     a.sample_index = q.sample_index;
     a.lds_bytes = q.s->lds_bytes;

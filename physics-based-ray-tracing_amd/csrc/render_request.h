@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "../../include/pbrt_hip.h"
+#include "film_key.h"
 
 #define N_STATE 15
 #define MAX_DEPTH_STATS 62
@@ -87,21 +88,20 @@ static inline const char *render_request(RenderRequest *rq, const pbrt_camera *c
     return nullptr;
 }
 
-// what an argument block of the kernels (RadArgs, TileKeepArgs, FilmArgs) takes from the request: the region and its pixel order
-template <class Args>
-static inline void render_region_args(const RenderRequest &rq, Args *a) {
-    a->rx0 = rq.rx0;
-    a->ry0 = rq.ry0;
-    a->rw = rq.rw;
-    a->tile_rows = rq.tile_rows;
-}
-// ... and the region's size and the film's, for the two that index whole films (RadArgs, FilmArgs)
-template <class Args>
-static inline void render_film_args(const RenderRequest &rq, Args *a) {
-    render_region_args(rq, a);
-    a->npix_r = (uint32_t)rq.npix_r;
-    a->film_w = rq.cam->film_w;
-    a->film_h = rq.cam->film_h;
+// the film key of the request (film_key.h), as every argument block of the kernels carries it: the region and its pixel order, the
+// sizes and the two fast divisors; s_first is the pass's
+static inline FilmKey render_film_key(const RenderRequest &rq) {
+    FilmKey k{};
+    k.rx0 = rq.rx0;
+    k.ry0 = rq.ry0;
+    k.rw = rq.rw;
+    k.npix_r = (uint32_t)rq.npix_r;
+    k.film_w = rq.cam->film_w;
+    k.film_h = rq.cam->film_h;
+    k.tile_rows = rq.tile_rows;
+    k.div_npix = make_fastdiv(k.npix_r);
+    k.div_rw = make_fastdiv(k.rw);
+    return k;
 }
 
 // ---- the shape of a pass ------------------------------------------------------------------------------------------------------

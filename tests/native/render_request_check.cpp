@@ -1,5 +1,6 @@
 // Host check of csrc/render_request.h (tests/test_render_request_host.py builds and runs it under the sanitizers): the argument rules
-// of a radiance render with their texts and their order, the rendered region against a per-pixel restatement, the shape of a pass
+// of a radiance render with their texts and their order, the rendered region and its film key against a per-pixel restatement, the
+// pixel order against its inverse (csrc/film_key.h region_index / region_pixel) over every small region, the shape of a pass
 // and its halving, the pass schedule, the fuse plan, the default pass size, the stream grids and the byte models of pbrt_stats
 // against literals worked by hand.  Prints one JSON line: {"checks": N, "failures": M}.
 #include <cstdio>
@@ -118,11 +119,38 @@ static void region_of(uint32_t W, uint32_t H, const pbrt_film_desc &f, const Ren
     CHECK(rq.rows_per_region() == (wavefront ? launch.rows_streams : launch.rows_fused));
     CHECK(rq.out_floats == ((flags & PBRT_FILM_RAW_ACCUM) ? 4u : 3u));
     CHECK(rq.tile_keep == (launch.keep && inside % 64 == 0 && !(flags & PBRT_FILM_NO_TILE_CULL)));
-    struct {
-        uint32_t rx0, ry0, rw, tile_rows, npix_r, film_w, film_h;
-    } a;
-    render_film_args(rq, &a);
+    const FilmKey a = render_film_key(rq);
     CHECK(a.rx0 == rq.rx0 && a.ry0 == rq.ry0 && a.rw == rq.rw && a.tile_rows == rq.tile_rows && a.npix_r == inside && a.film_w == W && a.film_h == H);
+    CHECK(a.s_first == 0);  // the pass loop's
+    for (uint32_t n : {0u, 1u, a.rw - 1, a.rw, a.rw + 1, a.npix_r - 1, a.npix_r, a.npix_r + 1, 7u * a.npix_r + 3u, 0xffffffffu})
+        CHECK(udiv_fast(n, a.div_npix) == n / a.npix_r && udiv_fast(n, a.div_rw) == n / a.rw);
+}
+
+// region_pixel is the inverse of region_index: every index of a region gives a pixel inside it, that pixel gives the index back, and
+// every pixel is given exactly once -- bands only, bands with a row-major tail, row-major only, widths that are no multiple of 8
+static void pixel_order() {
+    std::vector<uint32_t> widths;
+    for (uint32_t rw = 1; rw <= 17; ++rw) widths.push_back(rw);
+    widths.push_back(64);
+    for (uint32_t rw : widths)
+        for (uint32_t rh = 1; rh <= 17; ++rh) {
+            FilmKey k{};
+            k.rx0 = 3, k.ry0 = 2;  // (region_pixel and region_index speak of the region's own pixels)
+            k.rw = rw, k.npix_r = rw * rh, k.tile_rows = rh & ~7u;
+            k.div_npix = make_fastdiv(k.npix_r), k.div_rw = make_fastdiv(rw);
+            std::vector<uint32_t> given(k.npix_r, 0);
+            for (uint32_t pr = 0; pr < k.npix_r; ++pr) {
+                uint32_t rx = ~0u, ry = ~0u;
+                region_pixel(k, pr, &rx, &ry);
+                CHECK(rx < rw && ry < rh);
+                if (rx >= rw || ry >= rh) continue;
+                CHECK(region_index(rx, ry, rw, k.tile_rows) == pr);
+                ++given[ry * rw + rx];
+            }
+            bool once = true;
+            for (uint32_t g : given) once = once && g == 1;
+            CHECK(once);
+        }
 }
 static void regions() {
     const std::pair<uint32_t, uint32_t> films[] = {{1, 1}, {13, 7}, {16, 16}, {64, 64}, {45, 9}};
@@ -431,6 +459,7 @@ static void byte_models() {
 int main() {
     rule_table();
     regions();
+    pixel_order();
     pass_shapes();
     schedules();
     plans();

@@ -1,6 +1,6 @@
 // Host program around csrc/tile_cull.h (tests/test_tile_cull_host.py builds it with the address and undefined-behaviour sanitizers
 // and runs it on its own): the keep words of named cases -- a camera, a film cut into blocks of 64 region indices as the first
-// bounce's waves see it (kernels_radiance.h region_index), a primitive list.  Prints one JSON object:
+// bounce's waves see it (film_key.h region_index), a primitive list.  Prints one JSON object:
 //   {"cases": {name: {"cam": [17 numbers], "prims": [[type, 12 numbers], ...], "blocks": [[x0, y0, x1, y1, word], ...]}},
 //    "bits": all (block, primitive) bits, "cleared": how many of them are clear, "cleared_share": their share}
 // The test casts the oracle's camera rays against the oracle's primitive tests and holds every cleared bit to them.
@@ -92,7 +92,7 @@ static pbrt_camera look_at(double ox, double oy, double oz, double tx, double ty
     return c;
 }
 
-// the pixel of region index pr: the inverse of region_index (kernels_radiance.h path_key), region = the whole film
+// the pixel of region index pr: the inverse of region_index restated (film_key.h region_pixel is the library's), region = the whole film
 static void pixel_of(uint32_t pr, uint32_t rw, uint32_t tile_rows, uint32_t *x, uint32_t *y) {
     const bool tiled = pr < tile_rows * rw;
     const uint32_t num = tiled ? pr >> 3 : pr, q = num / rw;

@@ -6,7 +6,7 @@ the same render with PBRT_FILM_NO_PATH_KERNEL (that pass through k_bounce) bit f
 depth, launches.  Where it is cheap the film is held to the CPU oracle as well (bit for bit).
 
 Cases: the Cornell box at 64 x 64, 4 spp, max_depth 6; a 13 x 7 crop at 3 spp (273 paths: a partial last wave, a region whose
-width is no multiple of 8, no keep words); max_depth 1 and 2; max_depth 8 (above MAX_CHAIN: two launches, k_path not selected);
+width is no multiple of 8, no keep words); a 15 x 11 region with a band, a partial last column and a row-major tail; max_depth 1 and 2; max_depth 8 (above MAX_CHAIN: two launches, k_path not selected);
 ordered walk on and off, keep words on and off; a scene whose camera sees nothing (segments == 0); several passes with a non-zero
 sample_offset; the second render of a scene, whose plan is learnt from the first."""
 import numpy as np
@@ -82,6 +82,20 @@ def test_crop_13_by_7_has_a_partial_last_wave(mi, ob, capi):
     assert not mi.default_context().tile_keep()["used"]
     ref, ost = oracle_render(ob, sc, 5, 3, crop=crop)
     assert img.shape == (7, 13, 3) and np.array_equal(_bits(img), _bits(ref)) and img.mean() > 0
+    assert (st["segments"], st["shadow_rays"]) == (ost["segments"], ost["shadow_rays"])
+
+
+def test_crop_with_a_band_a_partial_last_column_and_a_row_major_tail(mi, ob, capi):
+    """film 21 x 13, crop (3, 2, 13, 9), tent filter: the region is 15 x 11 at (2, 1) -- one 8-row band whose last column of tiles
+    is 7 pixels wide, three rows in row-major order behind it, away from the film's origin (csrc/film_key.h region_pixel)"""
+    sc = mi.load_file(scene_path("cbox.xml"), res=32, spp=2, max_depth=3, rfilter="tent")
+    film = sc.sensors()[0].film()
+    film.width, film.height, film.crop = 21, 13, (0, 0, 21, 13)
+    crop = (3, 2, 13, 9)
+    img, st = _both(mi, capi, sc, flags=capi.film_fuse_plan(0x1F), seed=7, spp=2, crop=crop)
+    assert st["live"][0] == 15 * 11 * 2 and st["bounce_launches"] == 1
+    ref, ost = oracle_render(ob, sc, 7, 2, crop=crop)
+    assert img.shape == (9, 13, 3) and np.array_equal(_bits(img), _bits(ref)) and img.mean() > 0
     assert (st["segments"], st["shadow_rays"]) == (ost["segments"], ost["shadow_rays"])
 
 

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 # box-filter crops of the Cornell box, every one away from the film's origin: the region is the crop.  128 x 1 does not fit the
 # 64 x 64 film of the others: its film is 160 x 8
 BOX_CROPS = {"16x12": (40, 8, 16, 12), "32x10": (24, 50, 32, 10), "64x9": (0, 30, 64, 9), "48x4": (10, 33, 48, 4), "128x1": (20, 3, 128, 1),
-             "20x16": (31, 40, 20, 16), "4x16": (57, 5, 4, 16)}
+             "20x16": (31, 40, 20, 16), "4x16": (57, 5, 4, 16), "12x16": (45, 21, 12, 16)}
 RANDOM = {"random_2": (2, 5, 10, 12), "random_8": (8, 6, 3, 9)}
 VIEWS = (["cbox_64_tent"] + ["cbox_box_" + k for k in BOX_CROPS] +
          ["cbox_tent_corner", "cbox_gaussian_corner", "cbox_96x64", "in_plane", "near_plane", "prims_32"] + list(RANDOM))

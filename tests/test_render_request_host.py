@@ -2,7 +2,8 @@
 device -- the argument rules and their order, the rendered region, the shape of a pass and its halving, the state-addressing rules,
 the default pass size, the fuse plan, the pass schedule, the grids of the trace / shade streams and the byte models of pbrt_stats.
 No GPU: tests/native/render_request_check.cpp holds the rule table to the texts the driver always gave, the region to a per-pixel
-restatement over every filter and crops at every film edge, the pass shape and the schedule to their properties over drawn and
+restatement over every filter and crops at every film edge (its film key, csrc/film_key.h, with it), the pixel order of a region to its
+inverse over every region of 1..17 and 64 by 1..17 pixels, the pass shape and the schedule to their properties over drawn and
 swept inputs and to literal pass lists, the plan, the default pass size, the grids and the models to literals worked by hand.  The
 program is built with the address and undefined-behaviour sanitizers and run on its own.  The structure test holds what the header
 is for: the rules and the pass arithmetic are written once, and pbrt_integrator_sample has no bounce loop of its own."""
@@ -37,8 +38,12 @@ def test_the_request_keeps_its_rules_and_its_arithmetic(report):
 def test_the_header_includes_nothing_of_hip():
     text = open(os.path.join(CSRC, "render_request.h")).read()
     assert [line.split()[1] for line in text.splitlines() if line.startswith("#include")] == \
-        ["<algorithm>", "<cstddef>", "<cstdint>", '"../../include/pbrt_hip.h"']
+        ["<algorithm>", "<cstddef>", "<cstdint>", '"../../include/pbrt_hip.h"', '"film_key.h"']
     assert "__host__" not in text and "__device__" not in text and "__global__" not in text and "hip_runtime" not in text
+    # ... and the film key it makes (csrc/film_key.h) includes nothing at all of the project's, and names HIP only under hipcc
+    key = open(os.path.join(CSRC, "film_key.h")).read()
+    assert [line.split()[1] for line in key.splitlines() if line.startswith("#include")] == ["<cstddef>", "<cstdint>"]
+    assert "__global__" not in key and "hip_runtime" not in key and key.count("__device__") == 1 and "#if defined(__HIPCC__)" in key
 
 
 def _function(text, head):

@@ -138,7 +138,7 @@ def tile_cull_check_exe(tmp_path_factory):
 
 
 def region_indices(rw, rh):
-    """[rh, rw] the region index of every pixel (xx, yy) of a region: kernels_radiance.h region_index, as the film kernel reads it"""
+    """[rh, rw] the region index of every pixel (xx, yy) of a region: film_key.h region_index, as the film kernel reads it"""
     yy, xx = np.mgrid[0:rh, 0:rw].astype(np.int64)
     tile_rows = rh & ~7
     return np.where(yy < tile_rows, (yy >> 3) * 8 * rw + (xx << 3) + (yy & 7), yy * rw + xx)
