@@ -577,23 +577,48 @@ class Scene(Object):
             ctx = _capi.default_context()
             self._dev = _capi.DeviceScene(ctx, f["prims"], f["materials"], f["emitters"], f["light_prims"],
                                           f["light_cdf"], self.accel, f["vertex_normals"])
+            self._dirty_materials.clear()   # (created from the records _material_changed wrote)
         if self._dirty_materials:
             f = self.flatten()
             for i in sorted(self._dirty_materials):
-                t, p = f["material_objects"][i].to_material()
-                f["materials"]["type"][i] = t
-                f["materials"]["p"][i] = 0
-                f["materials"]["p"][i, :len(p)] = p
-                self._dev.update_material(i, _capi.make_material(t, p))
+                self._dev.update_material(i, _capi.make_material(*f["material_objects"][i].to_material()))
             self._dirty_materials.clear()
         return self._dev
 
     def _material_changed(self, bsdf):
+        """a BSDF has new values: its record of the flattened arrays is written now (flatten() is what an oracle is built from), the
+        device's copy by the next device()"""
         if self._flat is None:
             return
-        for i, b in enumerate(self._flat["material_objects"]):
+        f = self._flat
+        for i, b in enumerate(f["material_objects"]):
             if b is bsdf:
+                t, p = b.to_material()
+                f["materials"]["type"][i] = t
+                f["materials"]["p"][i] = 0
+                f["materials"]["p"][i, :len(p)] = p
                 self._dirty_materials.add(i)
+
+    def _lights_changed(self):
+        """A light of the radiance scene (an area emitter of a shape, a point light) has new values.  Its record is one of many things
+        made from it when the device scene is created -- the light list and its CDF, the occluder lists -- so nothing is patched: the
+        flattened arrays and the device scene are dropped, and the next flatten() / device() makes both again as creation does.  A
+        recording of us_render stands for the old handle, whose address the new one may be given: it goes too."""
+        self._flat = None
+        self._dirty_materials.clear()   # (flatten() reads every material from its object again)
+        if self._dev is not None:
+            self._dev.close()
+            self._dev = None
+        plan = getattr(self._integrator, "_render_plan", None)
+        if plan is not None:
+            plan.graph = plan.graph_key = plan.warm_key = None
+
+    def _check_parameters(self):
+        """what the acquisition's parameter block refuses (an emitter and an integrator that describe different arrays, ...) is
+        refused when the parameters are updated, not at the next acquisition"""
+        us_params = getattr(self._integrator, "us_params", None)
+        if us_params is not None:
+            us_params(self)
 
     # -- batched scene queries (scene.ray_intersect, CustomIntegrator.py:309,324) ------------------
     def ray_intersect(self, o, d, tmax=None):
@@ -812,16 +837,39 @@ class SceneParameters:
             self._pending[k] = value
 
     def update(self):
-        changed = {}
-        for k, v in self._pending.items():
-            owner, name, _ = self._table[k]
-            setattr(owner, _attr_name(owner, name), v)
-            changed.setdefault(id(owner), (owner, []))[1].append(name)
-        self._pending.clear()
+        """Hand the pending values to their owners ("What params.update() does"): a BSDF's record is written in
+        place (flatten()'s array now, the device's copy at the next device()), a light's change drops the flattened arrays and the
+        device scene, everything else is read again by the next request.  What an owner or the acquisition's parameter block refuses
+        raises, names the keys of the update, and leaves every owner as it was."""
+        pending, self._pending = self._pending, {}
+        changed, before = {}, []
+        request = lights = False   # an owner whose values go into a request's parameter block / a light of the radiance scene
+        try:
+            for k, v in pending.items():
+                owner, name, _ = self._table[k]
+                attr = _attr_name(owner, name)
+                before.append((owner, attr, getattr(owner, attr)))
+                setattr(owner, attr, v)
+                changed.setdefault(id(owner), (owner, []))[1].append(name)
+            for owner, names in changed.values():
+                owner.parameters_changed(names)
+                if not isinstance(owner, BSDFBase):
+                    request = True
+                    lights = lights or (isinstance(owner, EmitterBase) and not getattr(owner, "is_transducer", False))
+            if request:   # (no material is part of the acquisition's block)
+                self._scene._check_parameters()
+        except Exception as e:
+            for owner, attr, old in reversed(before):
+                setattr(owner, attr, old)
+            for owner, names in changed.values():
+                owner.parameters_changed(names)   # (the values the owner had: what it derives from them is made again)
+            e.args = (f"{e.args[0] if e.args else ''} [params.update() of {', '.join(pending)}: nothing was changed]",) + e.args[1:]
+            raise
         for owner, names in changed.values():
-            owner.parameters_changed(names)
             if isinstance(owner, BSDFBase):
                 self._scene._material_changed(owner)
+        if lights:
+            self._scene._lights_changed()
         return list(changed)
 
     def __repr__(self):

@@ -279,8 +279,8 @@ def test_full_size_linearity_in_emitted_radiance(mi, cbox_full):
     sc, img, _ = cbox_full
     sc2 = mi.load_file(scene_path("cbox.xml"), res=512, spp=256)
     p = mi.traverse(sc2)
-    sc2.shapes()[0].emitter().radiance = np.array([2.0, 2.0, 2.0])   # x2: exact in binary floating point
-    sc2._flat = None
+    p["luminaire.emitter.radiance"] = np.array([2.0, 2.0, 2.0])   # x2: exact in binary floating point
+    p.update()
     img2 = mi.render(sc2, seed=0)
     assert np.array_equal(img2, 2.0 * img)
 
