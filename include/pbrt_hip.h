@@ -830,6 +830,51 @@ int pbrt_capon_beamform_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const voi
 int pbrt_capon_beamform_table_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const void *d_iq, const void *d_table, const void *d_elem,
                                   const void *d_px, const void *d_pz, void *d_out);
 
+/* ---- non-finite and out-of-range geometry in the beamformers ---------------------------------------------------------
+ * Covers pbrt_das_beamform*, pbrt_bf_*, pbrt_iq_beamform*, pbrt_apod_beamform*, pbrt_scan_beamform*, pbrt_capon_beamform* and the
+ * first-arrival table calls, in every form.  The tables that decide WHICH SAMPLE a pixel reads -- the transmit delays tx[a][e], the
+ * element positions or the element table (x_e, z_e, nx_e, nz_e), the pixel axes or pixel tables, and a first-arrival table ttx[a][pixel]
+ * handed to a _table_dev form -- are not checked by any call (in the _dev forms they live in device memory).  A NaN, an infinity or a
+ * position beyond 2^31 samples in them is not an error.  What happens instead, from the code as built, the same in the host, _dev and
+ * _table_dev forms bit for bit (tests/geom_util.py, tests/test_gpu_geometry_nonfinite.py):
+ *   No read leaves a trace or a table, and no pixel other than those named below changes by a bit.
+ *   First arrival.  t_tx(a; pixel) is the f64 minimum (fmin, which drops a NaN operand) over the elements whose tx[a][e] + d_e / c is not
+ *     NaN, started from 1e300: a NaN or +inf delay or distance leaves the minimum to the other elements, a transmission without any such
+ *     element has the first arrival 1e300 (so does its entry in a table the library makes), and a -inf delay makes it -inf.
+ *   A term (a, e) is taken only if the aperture comparison holds and the position lies in the trace; both are comparisons, false for NaN.
+ *     A line of elements: an element whose position is NaN or infinite receives nothing (|x - x_e| <= half width is false) and gives no
+ *     first arrival.  A NaN position bounds nothing; an infinite one widens the span the tile test uses (tiles are left early only when
+ *     no pixel's aperture reaches into [min x_e, max x_e], taken with fminf / fmaxf, which skip NaN), which costs time and changes no bit.
+ *     An element table with f_number > 0: a row with a NaN in its position or in its normal receives nothing (d_n > 0 is false); with the
+ *     position finite and only the normal NaN it still takes part in the first arrival.  With f_number <= 0 the normal is not read and every
+ *     element receives every pixel: an element whose POSITION is NaN then has a NaN receive part -- nearest interpolation takes nothing;
+ *     linear interpolation indexes the trace by the transmit part alone and, where that lies in the trace, takes a sample with a NaN
+ *     weight: a NaN pixel.  (The one arm in which a bad element does not simply drop out.)
+ *   A pixel whose x or z is NaN or infinite takes no term and is exactly (+0) [(+0, +0)] in every family; with axes that is the whole
+ *     column or row.  So is a finite pixel so far away that its positions leave the trace (x = 3e5 m).
+ *   Positions beyond 2^31 samples.  Nearest interpolation decides on the f64 sum (t_tx + d_e / c - t0) fs: rint, two comparisons with 0 and
+ *     T - 1, then the conversion.  Linear interpolation keeps the two parts (t_tx - t0) fs and d_e fs as whole samples (int32, converted with
+ *     saturation, NaN -> 0) plus an f32 fraction, adds the whole parts and the carry of the fractions in wrapping 32-bit arithmetic and
+ *     compares the sum AS AN UNSIGNED number with T - 1.  The receive part is never negative (a square root times fs > 0).  With it in
+ *     [0, 2^31) and the transmit part inside +-2^31 the result is the f64 rule's; a part at or beyond +-2^31 saturates and the sum is
+ *     refused: 2^31 - 1 plus anything non-negative, and -2^31 plus anything up to 2^31 - 1, are >= 2^31 > T - 1 as unsigned numbers.  One
+ *     corner remains: a finite transmit part at or below -2^31 AND a receive part at or above 2^31 - 1 whose f32 fractions carry sum to
+ *     0 and read samples 0 and 1 -- inside the trace, not the f64 rule's (a pixel 10^5 m away under t0 = +100 s).  (das.t0 = -200 s at
+ *     20 MHz: every position is beyond 2^31, every image exactly zero.)
+ *   What a transmission with a non-finite first arrival (all delays NaN: 1e300; a -inf delay; a NaN or +-inf table entry) adds:
+ *     delay-and-sum, p-DAS, F-DMAS, their windowed forms and Capon add nothing for +-inf and 1e300 (no position lies in the trace; Capon:
+ *       N = 0), and the image is that of the other transmissions.  A NaN table entry: nearest interpolation takes nothing; linear
+ *       interpolation indexes the trace by the receive part alone with a NaN weight -- a NaN pixel (Capon: both components) wherever an
+ *       element of the aperture has floor(d_e fs) in [0, T - 2].
+ *     I/Q and windowed I/Q (the walk): wave 0 turns the transmission's sum by rot_a = exp(2 pi i frac(f_d t_tx)) whether or not a term
+ *       was taken.  For t_tx = 1e300 that is (1, 0) and the zero sum stays (+0, +0).  For t_tx = -inf, +inf or NaN it is NaN: the pixel is
+ *       NaN in both components -- at EVERY pixel of every 8 x 8 tile that is walked, whether the pixel itself sees an element or not.  A
+ *       line of elements: the tiles in which some pixel's aperture reaches into the span of the elements; the other tiles are left early
+ *       with exact zeros.  An element table: every tile.  A table entry reaches its own pixel only.
+ *       So "Capon with L = 1 is I/Q delay-and-sum" does not hold on such input: Capon skips the transmission (N = 0), the walk gives NaN.
+ *   The same delays, elements and pixels give the same bits whether the first arrivals come from the walk's own pass or from
+ *     pbrt_das_first_arrival*_dev / pbrt_scan_first_arrival_dev on the same tables. */
+
 /* ---- colour and power Doppler on an ensemble of beamformed I/Q frames ----------------------------------------------
  * replaces: ultraspy's Doppler module (apply_wall_filter, get_color_doppler_map, get_power_doppler_map; absent here as above, so this
  * is the build's own definition, the lag-one autocorrelation estimator of Kasai et al. 1985).  frames [n_frames][nx][nz] are (re, im)
