@@ -2,7 +2,8 @@
 """The reference's ultrasound driver flow on this library: scene dict -> acquisition -> delay-and-sum -> envelope ->
 log compression -> finite-difference roughness loop (what USMain.py does at :26-90, :93-224, :257-289), without the
 plotting.  Writes the B-mode image and the channel buffer as .npy.
-    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas,capon}] [--p P] [--l-prop X] [--delta-l D]
+    python examples/us_bmode.py [--convex] [--beamformer {das,pdas,fdmas,capon,slsc,cf}] [--p P] [--l-prop X] [--delta-l D]
+                                  [--lag-prop Q] [--half-kernel H] [--gamma G]
                                   [--iq [--decimation D]] [--polar] [--apodization {boxcar,tukey,hann,hamming} [--alpha A]] [out_dir]
 --convex: the same flow under a curved (abdominal) array -- 64 elements on a 40 mm arc of 40 degrees (DESIGN D18); the sensor
 transform puts the apex where the linear array sits, and the scan is given in the sensor's frame, whose origin is the centre of
@@ -13,6 +14,11 @@ frequency AT the carrier, so the example picks lambda / 8 for p-DAS and lambda /
 --beamformer capon: the minimum-variance beamformer (DESIGN D23) with subarrays of --l-prop (default 0.5) of the elements a pixel uses
 and a diagonal loading of --delta-l (default 0.01).  It works on I/Q data, so it implies --iq, and it makes its own weights: no
 --apodization.
+--beamformer slsc / cf: the spatial-coherence beamformers (DESIGN D26; not ultraspy's).  slsc is the short-lag spatial coherence -- the
+image is the correlation between neighbouring elements, summed over the lags up to --lag-prop (default 0.3) of the elements a pixel uses,
+over an axial kernel of 2 x --half-kernel + 1 samples (default 1; 0 .. 4); it is a detection image already, so there is no envelope step.
+cf is delay-and-sum weighted by the coherence factor to the power --gamma (default 1; 0 is delay-and-sum).  Like capon both work on I/Q
+data, so they imply --iq and a lambda / 2 step, and take no --apodization.
 --iq: the I/Q chain (DESIGN D20) -- the channel data are demodulated at the carrier and decimated by --decimation (default 4: 50 MHz ->
 12.5 MHz), delay-and-sum runs on complex samples and the envelope is the modulus of each pixel, which needs no carrier on the grid: the
 example then scans at lambda / 2 axially.  Delay-and-sum only.
@@ -35,10 +41,13 @@ import pbrt_amd.drjit_compat as dr          # was: import drjit as dr
 mi.set_variant("llvm_ad_mono")              # accepted; the one backend is HIP on gfx950
 ap = argparse.ArgumentParser()
 ap.add_argument("--convex", action="store_true")
-ap.add_argument("--beamformer", choices=("das", "pdas", "fdmas", "capon"), default="das")
+ap.add_argument("--beamformer", choices=("das", "pdas", "fdmas", "capon", "slsc", "cf"), default="das")
 ap.add_argument("--p", type=float, default=2.0)
 ap.add_argument("--l-prop", type=float, default=0.5)
 ap.add_argument("--delta-l", type=float, default=0.01)
+ap.add_argument("--lag-prop", type=float, default=0.3)
+ap.add_argument("--half-kernel", type=int, default=1)
+ap.add_argument("--gamma", type=float, default=1.0)
 ap.add_argument("--iq", action="store_true")
 ap.add_argument("--decimation", type=int, default=4)
 ap.add_argument("--polar", action="store_true")
@@ -51,8 +60,12 @@ if args.beamformer == "capon":
     if args.apodization != "boxcar":
         ap.error("--beamformer capon makes its own weights: no --apodization (DESIGN D23)")
     args.iq = True
-if args.iq and args.beamformer not in ("das", "capon"):
-    ap.error("--iq takes delay-and-sum or Capon: the non-linear beamformers are defined on RF data (DESIGN D19)")
+if args.beamformer in ("slsc", "cf"):
+    if args.apodization != "boxcar":
+        ap.error(f"--beamformer {args.beamformer} takes no receive window: no --apodization (DESIGN D26)")
+    args.iq = True
+if args.iq and args.beamformer not in ("das", "capon", "slsc", "cf"):
+    ap.error("--iq takes delay-and-sum, Capon, SLSC or CF: the non-linear beamformers are defined on RF data (DESIGN D19)")
 convex, out_dir = args.convex, args.out_dir
 T = mi.ScalarTransform4f
 RADIUS = 0.04 if convex else 0.0            # centre of curvature RADIUS behind the apex; the scan's z is measured from it
@@ -80,8 +93,10 @@ lam = integ.sound_speed / integ.frequency
 window = dict(rx_apodization=args.apodization, rx_apodization_alpha=args.alpha)
 beamformer = {"das": lambda: mi.DelayAndSum(**window), "pdas": lambda: mi.PDelayAndSum(p=args.p, **window),
               "fdmas": lambda: mi.FilteredDelayMultiplyAndSum(**window),
-              "capon": lambda: mi.Capon(l_prop=args.l_prop, delta_l=args.delta_l)}[args.beamformer]()
-step = {"das": lam / 4, "pdas": lam / 8, "fdmas": lam / 16, "capon": lam / 2}[args.beamformer]
+              "capon": lambda: mi.Capon(l_prop=args.l_prop, delta_l=args.delta_l),
+              "slsc": lambda: mi.ShortLagSpatialCoherence(lag_prop=args.lag_prop, half_kernel=args.half_kernel),
+              "cf": lambda: mi.CoherenceFactor(gamma=args.gamma)}[args.beamformer]()
+step = {"das": lam / 4, "pdas": lam / 8, "fdmas": lam / 16, "capon": lam / 2, "slsc": lam / 2, "cf": lam / 2}[args.beamformer]
 RENDER = dict(x_range=(-0.02, 0.02), z_range=Z_RANGE, step=step, beamformer=beamformer)
 if args.iq:
     RENDER.update(iq=True, decimation=args.decimation, step=lam / 2)

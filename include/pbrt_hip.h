@@ -830,8 +830,72 @@ int pbrt_capon_beamform_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const voi
 int pbrt_capon_beamform_table_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, const void *d_iq, const void *d_table, const void *d_elem,
                                   const void *d_px, const void *d_pz, void *d_out);
 
+/* ---- spatial coherence: SLSC and the coherence factor on I/Q data ------------------------------------------------------
+ * The calls above weigh or solve for AMPLITUDES; these two image the COHERENCE of the aperture.  `ultraspy` has neither, so this is the
+ * build's own definition, after Lediju, Trahey, Byram and Dahl, "Short-lag spatial coherence of backscattered echoes", 2011 (SLSC) and
+ * Mallart and Fink 1994 / Hollman, Rigby and O'Donnell 1999 (the coherence factor, CF).  data [n_angles][n_elements][time_samples] PAIRS
+ * at the rate das.fs, demodulated at demod_freq, exactly as pbrt_iq_beamform takes them.  Per pixel and transmission a, all in f32:
+ *   U(a)   the elements whose centre sample pbrt_iq_beamform would take -- the same first arrival, f64 position, aperture rule and range
+ *          rule -- ranked k = 0 .. N - 1 in element order, as Capon ranks them
+ *   s_k[h] (h = -H .. H, H = half_kernel, 0 <= H <= 4) the trace at the delayed position plus h whole samples, by the interpolation rule
+ *          and with the SAME weight w as the centre.  Linear (i0 the whole part of the position, w its fraction): das_lerp(w, trace[i0 + h],
+ *          trace[i0 + h + 1]) = fmaf(w, t1 - t0, t0) per component if 0 <= i0 + h < T - 1; trace[T - 1] if i0 + h == T - 1 and w == 0;
+ *          (0, 0) otherwise.  Nearest (r the rounded position): trace[r + h] if 0 <= r + h <= T - 1, else (0, 0).
+ *   v_k[h] = rot_e * s_k[h] with the centre's rot_e = exp(2 pi i frac(f_d d_e / c)) and the complex product as in pbrt_iq_beamform: v_k[0]
+ *          is bit for bit the v_k of Capon and of pbrt_iq_beamform.
+ * PBRT_COH_SLSC (half_kernel H, lag_prop): the image is FLOAT32 [nx][nz].
+ *   1. every row v_k[.] is multiplied by the power of two 2^(127 - e), e the biased exponent of max_h max(|Re v_k[h]|, |Im v_k[h]|) (a
+ *      NaN is no maximum) clamped to [1, 253]: exact, Capon's device for the aperture, here per row
+ *   2. P_k = sum over h ascending of fmaf(re, re, fmaf(im, im, P))
+ *   3. u_k[h] = v_k[h] / sqrtf(P_k) (one IEEE square root per row, an IEEE division per component); the row is all zeros when the
+ *      comparison P_k == 0 is true
+ *   4. C(i, j) = Re sum_h u_i[h] conj(u_j[h]): over h ascending, c = fmaf(a.x, b.x, fmaf(a.y, b.y, c))
+ *   5. R_a(m) = (sum_{i = 0}^{N - m - 1} C(i, i + m)) / (N - m)
+ *   6. M = min(max(1, (uint32) floorf(lag_prop * (float) N)), N - 1, 64); M = 0 for N < 2
+ *   7. y_a = sum_{m = 1}^{M} R_a(m), over m ascending.  As built (one wave per pixel, lane l holds the ranks l, l + 64, ...): for a lag m
+ *      a lane adds the C(i, i + m) of its ranks i ascending (those with i + m < N), the 64 lanes' sums meet in a butterfly (lane l with
+ *      lane l ^ 32, ^ 16, .. ^ 1), and that sum is divided by (float)(N - m) (an IEEE division): traces that are +-1 give R_a(m) exactly
+ *   8. out = clamp(sum_a y_a), added in order of a and divided by n_angles when compound_mean is set (before the clamp); clamp(v) is v if
+ *      v > 0, v if v is NaN, else +0.  No rot_a is applied: it cancels.
+ *   A pixel that uses no element is exactly +0.  SLSC is homogeneous of degree 0 in every trace: a trace times a power of two changes no bit.
+ * PBRT_COH_CF (gamma; half_kernel must be 0): the image is COMPLEX [nx][nz] pairs.
+ *   1. the v_k = v_k[0] of the aperture are brought to order 1 by ONE power of two (Capon's rule: e of the maximum over k), undone on S_a
+ *   2. S_a = sum_k v_k, 3. Q_a = sum_k fmaf(re, re, fmaf(im, im, .)): a lane adds its ranks ascending, the lanes meet in the butterfly
+ *   4. CF_a = |S_a|^2 / ((float) N * Q_a) with |S|^2 = fmaf(S.x, S.x, S.y * S.y); 0 when the comparison Q_a == 0 is true
+ *   5. w_a = 1 when gamma == 0, CF_a when gamma == 1, powf(CF_a, gamma) otherwise
+ *   6. out = sum_a rot_a * (w_a * S_a * 2^(e - 127)), rot_a as in pbrt_iq_beamform, in order of a, divided by n_angles for compound_mean.
+ *      A transmission with N = 0 is skipped, as in Capon.
+ *   With gamma = 0 it is pbrt_iq_beamform's image in another order of operations.  A pixel that uses no element is exactly (+0, +0).  CF
+ *   is homogeneous of degree 1: data times a power of two give the image times that power, bit for bit.
+ * Non-finite samples propagate as this arithmetic carries them.  `tables` as in pbrt_apod_params; there is no receive window.
+ * Refused with PBRT_E_INVALID: everything pbrt_scan_params refuses, scan.method != PBRT_SCAN_IQ, tables > 1, a kind other than the two
+ * (a zeroed block is refused), das.n_elements > 256; SLSC: lag_prop not finite or outside (0, 1], half_kernel > 4; CF: gamma not finite or
+ * outside [0, 4], half_kernel != 0.  A refused call leaves `out` untouched.
+ * `out` holds nx * nz floats (SLSC) or nx * nz pairs (CF); pbrt_coherence_beamform takes host pointers and stages the width that `kind`
+ * implies; the _dev forms take device pointers, are queued on the context's stream and recordable; the table is the one
+ * pbrt_das_first_arrival[_probe]_dev / pbrt_scan_first_arrival_dev write, the table form is bit-equal to the direct form, so is tables = 1
+ * on the tables of a separable scan to tables = 0, and the host form to _dev. */
+#define PBRT_COH_SLSC 1u
+#define PBRT_COH_CF 2u
+typedef struct pbrt_coherence_params {
+    pbrt_scan_params scan; /* das, method (PBRT_SCAN_IQ only), demod_freq, probe: every rule of pbrt_scan_params */
+    uint32_t tables;       /* 0: the axes x[nx], z[nz]; 1: two pixel tables [nx][nz] */
+    uint32_t kind;         /* PBRT_COH_SLSC or PBRT_COH_CF */
+    uint32_t half_kernel;  /* SLSC: H <= 4, the axial kernel is 2 H + 1 samples; CF: 0 */
+    float lag_prop;        /* SLSC: the lags summed over the aperture's element count: finite, 0 < lag_prop <= 1 */
+    float gamma;           /* CF: the exponent of the weight: finite, 0 <= gamma <= 4 */
+} pbrt_coherence_params;
+int pbrt_coherence_beamform(pbrt_ctx *ctx, const pbrt_coherence_params *p, const float *iq, const float *tx_delays, const float *elem,
+                            const float *px, const float *pz, float *out);
+int pbrt_coherence_beamform_dev(pbrt_ctx *ctx, const pbrt_coherence_params *p, const void *d_iq, const void *d_tx_delays,
+                                const void *d_elem, const void *d_px, const void *d_pz, void *d_out);
+int pbrt_coherence_beamform_table_dev(pbrt_ctx *ctx, const pbrt_coherence_params *p, const void *d_iq, const void *d_table,
+                                      const void *d_elem, const void *d_px, const void *d_pz, void *d_out);
+
 /* ---- non-finite and out-of-range geometry in the beamformers ---------------------------------------------------------
- * Covers pbrt_das_beamform*, pbrt_bf_*, pbrt_iq_beamform*, pbrt_apod_beamform*, pbrt_scan_beamform*, pbrt_capon_beamform* and the
+ * Covers pbrt_das_beamform*, pbrt_bf_*, pbrt_iq_beamform*, pbrt_apod_beamform*, pbrt_scan_beamform*, pbrt_capon_beamform*,
+ * pbrt_coherence_beamform* (which behave as Capon does wherever Capon is named below: a transmission whose first arrival is +-inf or
+ * 1e300 adds nothing because N = 0, a NaN table entry with linear interpolation gives a NaN pixel) and the
  * first-arrival table calls, in every form.  The tables that decide WHICH SAMPLE a pixel reads -- the transmit delays tx[a][e], the
  * element positions or the element table (x_e, z_e, nx_e, nz_e), the pixel axes or pixel tables, and a first-arrival table ttx[a][pixel]
  * handed to a _table_dev form -- are not checked by any call (in the _dev forms they live in device memory).  A NaN, an infinity or a
@@ -985,6 +1049,7 @@ int pbrt_ctx_tile_keep(pbrt_ctx *ctx, pbrt_tile_keep_info *info, uint32_t *words
  * pbrt_rf2iq_dev, pbrt_iq_beamform_dev, pbrt_iq_beamform_table_dev, pbrt_iq_envelope_dev,
  * pbrt_scan_beamform_dev, pbrt_scan_beamform_table_dev, pbrt_scan_first_arrival_dev, pbrt_scan_convert_dev,
  * pbrt_apod_beamform_dev, pbrt_apod_beamform_table_dev, pbrt_capon_beamform_dev, pbrt_capon_beamform_table_dev,
+ * pbrt_coherence_beamform_dev, pbrt_coherence_beamform_table_dev,
  * pbrt_doppler_autocorr_dev, pbrt_doppler_maps_dev, pbrt_envelope_dev, pbrt_log_compress_dev) are RECORDED on the context's
  * stream instead of run; pbrt_graph_launch replays the recording in one submission and returns without waiting, exactly as if
  * the recorded calls had just been made: same kernels, same arguments, same results bit for bit, the acquisition's statistics

@@ -27,8 +27,9 @@ from .scene import (Film, Object, ParamFlags, ReconstructionFilter, Sampler, Sce
                     load_file, register_bsdf, register_emitter, register_film, register_integrator, register_rfilter,
                     register_sampler, register_sensor, register_shape, traverse)
 from .transforms import Properties, ScalarTransform4f, Transform4f
-from .beamform import (Capon, DelayAndSum, FilteredDelayMultiplyAndSum, GridScan, PDelayAndSum, PolarScan, apply_pulse, axial_fir,
-                       bandpass_taps, build_probe, capon_beamform, das_beamform, das_first_arrival, envelope, iq_beamform, iq_envelope, log_compress,
+from .beamform import (Capon, CoherenceFactor, DelayAndSum, FilteredDelayMultiplyAndSum, GridScan, PDelayAndSum, PolarScan,
+                       ShortLagSpatialCoherence, apply_pulse, axial_fir,
+                       bandpass_taps, build_probe, capon_beamform, coherence_beamform, das_beamform, das_first_arrival, envelope, iq_beamform, iq_envelope, log_compress,
                        lowpass_taps, nonlinear_beamform, polar_n_theta, rf2iq, scan_beamform, scan_convert, scan_first_arrival,
                        us_render)
 from .beamform import (doppler_autocorr, doppler_maps, doppler_render, get_color_doppler_map, get_power_doppler_map,

@@ -176,6 +176,16 @@ class CaponParams(C.Structure):
 CAPON_MAX_L, CAPON_MAX_E = 32, 256
 
 
+class CoherenceParams(C.Structure):
+    """pbrt_coherence_params: a whole spatial-coherence request on I/Q data, SLSC or the coherence factor (DESIGN D26)"""
+    _fields_ = [("scan", ScanParams), ("tables", C.c_uint32), ("kind", C.c_uint32), ("half_kernel", C.c_uint32),
+                ("lag_prop", C.c_float), ("gamma", C.c_float)]
+
+
+COH_SLSC, COH_CF = 1, 2
+COH_MAX_E, COH_MAX_H, COH_MAX_LAG = 256, 4, 64
+
+
 class DopplerParams(C.Structure):
     """pbrt_doppler_params: the one block of the two Doppler steps (DESIGN D24)"""
     _fields_ = [("n_frames", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32), ("wall_degree", C.c_uint32), ("kx", C.c_uint32),
@@ -288,6 +298,10 @@ SIGNATURES = {
     "pbrt_capon_beamform": (C.c_int, [_P, C.POINTER(CaponParams), _F, _F, _F, _F, _F, _F]),
     "pbrt_capon_beamform_dev": (C.c_int, [_P, C.POINTER(CaponParams), _P, _P, _P, _P, _P, _P]),
     "pbrt_capon_beamform_table_dev": (C.c_int, [_P, C.POINTER(CaponParams), _P, _P, _P, _P, _P, _P]),
+    # spatial coherence on I/Q data: SLSC and the coherence factor (DESIGN D26)
+    "pbrt_coherence_beamform": (C.c_int, [_P, C.POINTER(CoherenceParams), _F, _F, _F, _F, _F, _F]),
+    "pbrt_coherence_beamform_dev": (C.c_int, [_P, C.POINTER(CoherenceParams), _P, _P, _P, _P, _P, _P]),
+    "pbrt_coherence_beamform_table_dev": (C.c_int, [_P, C.POINTER(CoherenceParams), _P, _P, _P, _P, _P, _P]),
     # colour and power Doppler on an ensemble of I/Q frames (DESIGN D24)
     "pbrt_doppler_autocorr": (C.c_int, [_P, C.POINTER(DopplerParams), _F, _F, _F]),
     "pbrt_doppler_autocorr_dev": (C.c_int, [_P, C.POINTER(DopplerParams), _P, _P, _P]),

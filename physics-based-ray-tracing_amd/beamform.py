@@ -20,6 +20,8 @@ scan_convert from the sector onto a Cartesian grid, us_render(scan="polar").
 
 Capon: ultraspy's fourth beamformer, minimum-variance weights per pixel and transmission on I/Q data -- capon_beamform
 and the class Capon, on both kinds of scan; us_render(beamformer=Capon()) runs the I/Q chain with it.
+Spatial coherence (not ultraspy's): short-lag spatial coherence and the coherence factor on I/Q data -- coherence_beamform
+and the classes ShortLagSpatialCoherence (a float32 detection image: no envelope step) and CoherenceFactor, on both kinds of scan and in us_render.
 
 All work runs on the GPU through libpbrt_hip.so (no CPU fallback; `on_gpu` is accepted for compatibility)."""
 from __future__ import annotations
@@ -114,11 +116,19 @@ def _checked_window(rx_apodization, rx_apodization_alpha, f_number):
     return _WINDOWS[rx_apodization], alpha
 
 
-def _block(das, tables, method, p, demod_freq, probe, window=_capi.APOD_BOXCAR, alpha=1.0, capon=None):
+def _block(das, tables, method, p, demod_freq, probe, window=_capi.APOD_BOXCAR, alpha=1.0, capon=None, coherence=None):
     """the parameter block of a request and the family of entry points that takes it: pbrt_scan_* for pixel tables (one block for
     every method); on axes pbrt_das_* (the element table is in the NAME: *_probe), pbrt_bf_* or pbrt_iq_* (a probe flag in the block);
     with a receive window other than boxcar pbrt_apod_* (one block for every method, probe and scan kind, DESIGN D22); capon =
-    (l_prop, delta_l): pbrt_capon_* (I/Q data, every probe and scan kind, DESIGN D23)"""
+    (l_prop, delta_l): pbrt_capon_* (I/Q data, every probe and scan kind, DESIGN D23); coherence = (kind, half_kernel, lag_prop, gamma):
+    pbrt_coherence_* (likewise, DESIGN D26)"""
+    if coherence is not None:
+        par = _capi.CoherenceParams()
+        par.scan.das, par.scan.probe, par.scan.method, par.scan.p = das, int(bool(probe)), _METHODS[method], float(p)
+        par.scan.demod_freq = float(demod_freq or 0.0)
+        par.tables, par.kind, par.half_kernel = int(bool(tables)), int(coherence[0]), int(coherence[1])
+        par.lag_prop, par.gamma = float(coherence[2]), float(coherence[3])
+        return par, "coherence"
     if capon is not None:
         par = _capi.CaponParams()
         par.scan.das, par.scan.probe, par.scan.method, par.scan.p = das, int(bool(probe)), _METHODS[method], float(p)
@@ -175,7 +185,7 @@ def das_first_arrival(tx_delays, elem_x, x, z, sound_speed, out=None):
 
 
 def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method, p=2.0, demod_freq=None, t0, f_number, interpolation,
-              compound, out, table, rx_apodization="boxcar", rx_apodization_alpha=0.5, capon=None):
+              compound, out, table, rx_apodization="boxcar", rx_apodization_alpha=0.5, capon=None, coherence=None):
     """One beamform request, from every public call to its entry point: `data` by `method` ("das", "pdas" with p, "fdmas", or "iq"
     with demod_freq: data and result complex64) on the pixels gx, gz -- the axes x, z, or (`tables`) two pixel tables.  Shapes the
     arguments, holds RF against I/Q, uploads the small tables where the data is a DeviceBuffer, validates `out` and `table`, selects
@@ -183,13 +193,18 @@ def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method,
     what a queued kernel reads alive with its result.  Host arrays in: a host array out, `out` and `table` are not read.
     rx_apodization: the receive window on the f-number aperture, "boxcar" (today's entry points), "tukey" (with rx_apodization_alpha),
     "hann" or "hamming" (pbrt_apod_*, DESIGN D22); validated before a context is made.
-    capon: (l_prop, delta_l) -- the I/Q data go through pbrt_capon_* (DESIGN D23), which has no receive window."""
+    capon: (l_prop, delta_l) -- the I/Q data go through pbrt_capon_* (DESIGN D23), which has no receive window.
+    coherence: (kind, half_kernel, lag_prop, gamma) -- the I/Q data go through pbrt_coherence_* (DESIGN D26), likewise; the image of
+    SLSC is float32."""
     window, alpha = _checked_window(rx_apodization, rx_apodization_alpha, f_number)
+    if coherence is not None and (method != "iq" or window != _capi.APOD_BOXCAR or capon is not None):
+        raise ValueError("SLSC and the coherence factor take I/Q data and no receive window: method 'iq' and rx_apodization='boxcar'")
     if capon is not None and (method != "iq" or window != _capi.APOD_BOXCAR):
         raise ValueError("Capon beamforms I/Q data and makes its own weights: method 'iq' and rx_apodization='boxcar'")
     dev = _is_dev(data)
     iq = method == "iq"
     dtype = np.dtype(np.complex64 if iq else np.float32)
+    out_dtype = np.dtype(np.float32) if coherence is not None and coherence[0] == _capi.COH_SLSC else dtype
     cx = data.ctx if dev else _capi.default_context()
     if not dev:
         data, out, table = np.ascontiguousarray(data, dtype=dtype), None, None
@@ -202,11 +217,11 @@ def _beamform(data, tx_delays, elem, gx, gz, tables, fs, sound_speed, *, method,
     tx, ex = _arg(cx, tx_delays, (A, E), dev), _arg(cx, elem, eshape, dev)
     gx, gz, (n0, n1) = _pixels(cx, gx, gz, tables, dev)
     par, family = _block(_das_params(A, E, T, n0, n1, fs, sound_speed, t0, f_number, interpolation, compound), tables, method, p,
-                         demod_freq, probe, window, alpha, capon)
+                         demod_freq, probe, window, alpha, capon, coherence)
     d0, d1 = ("n0", "n1") if tables else ("nx", "nz")
-    res = out if out is not None else _capi.DeviceBuffer(cx, (n0, n1), dtype) if dev else np.empty((n0, n1), dtype)
-    if res.nbytes != n0 * n1 * dtype.itemsize:
-        raise ValueError(f"out must hold {d0} * {d1} {dtype.name}")
+    res = out if out is not None else _capi.DeviceBuffer(cx, (n0, n1), out_dtype) if dev else np.empty((n0, n1), out_dtype)
+    if res.nbytes != n0 * n1 * out_dtype.itemsize:
+        raise ValueError(f"out must hold {d0} * {d1} {out_dtype.name}")
     if table is not None and table.nbytes != A * n0 * n1 * 8:   # the first-arrival times of this scan, made once
         raise ValueError(f"table must be the [n_angles, {d0}, {d1}] float64 buffer of {'scan' if tables else 'das'}_first_arrival for this scan")
     name = (f"pbrt_{family}_beamform" + ("_table" if table is not None else "") + ("_probe" if probe and family == "das" else "")
@@ -295,6 +310,54 @@ def capon_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, l_
     return _beamform(iq, tx_delays, elem, x, z, bool(tables), fs_iq, sound_speed, method="iq",
                      demod_freq=_checked_demod_freq(float(demod_freq)), t0=t0, f_number=f_number, interpolation=interpolation,
                      compound=compound, out=out, table=table, capon=_checked_capon(l_prop, delta_l, int(E)))
+
+
+_COH_KINDS = {"slsc": _capi.COH_SLSC, "cf": _capi.COH_CF}
+
+
+def _checked_coherence(kind, lag_prop, half_kernel, gamma, E):
+    """(kind, half_kernel, lag_prop, gamma) as the library takes them; ValueError for what it would refuse (include/pbrt_hip.h
+    "spatial coherence").  lag_prop and half_kernel are SLSC's, gamma is the coherence factor's: the other kind's are not read (the
+    block carries half_kernel 0 for "cf")."""
+    if not isinstance(kind, str) or kind not in _COH_KINDS:
+        raise ValueError(f"kind must be one of {tuple(_COH_KINDS)}, got {kind!r}")
+    if E > _capi.COH_MAX_E:
+        raise ValueError(f"{kind.upper()} takes at most {_capi.COH_MAX_E} elements, got {E}")
+    if kind == "slsc":
+        try:
+            lp = float(lag_prop)
+        except (TypeError, ValueError):
+            lp = float("nan")
+        if not (math.isfinite(lp) and 0.0 < lp <= 1.0):
+            raise ValueError(f"lag_prop must lie in (0, 1], got {lag_prop!r}")
+        if isinstance(half_kernel, bool) or not isinstance(half_kernel, (int, np.integer)) or not 0 <= int(half_kernel) <= _capi.COH_MAX_H:
+            raise ValueError(f"half_kernel must be an integer in [0, {_capi.COH_MAX_H}], got {half_kernel!r}")
+        return _capi.COH_SLSC, int(half_kernel), lp, 1.0
+    try:
+        gm = float(gamma)
+    except (TypeError, ValueError):
+        gm = float("nan")
+    if not (math.isfinite(gm) and 0.0 <= gm <= 4.0):
+        raise ValueError(f"gamma must lie in [0, 4], got {gamma!r}")
+    return _capi.COH_CF, 0, 0.3, gm
+
+
+def coherence_beamform(iq, tx_delays, elem, x, z, fs_iq, sound_speed, demod_freq, kind="slsc", lag_prop=0.3, half_kernel=1, gamma=1.0,
+                       t0=0.0, f_number=1.0, interpolation="linear", compound="sum", out=None, table=None, tables=False):
+    """Spatial-coherence beamforming of I/Q channel data (DESIGN D26, include/pbrt_hip.h): the delayed and turned samples of
+    iq_beamform -- same delays, aperture and interpolation -- are not added up as amplitudes; the image is the coherence of the aperture.
+    kind="slsc": short-lag spatial coherence (Lediju et al. 2011) -- the normalised correlation between the elements m ranks apart over
+    an axial kernel of 2 half_kernel + 1 samples (0 <= half_kernel <= 4), averaged over the pairs and summed over the lags m = 1 ..
+    floor(lag_prop N) (0 < lag_prop <= 1, at most 64 lags); a float32 image, clamped at 0.  kind="cf": the coherence factor (Mallart and
+    Fink 1994) -- coherent over incoherent power of the aperture, raised to gamma (0 <= gamma <= 4) and multiplied onto delay-and-sum; a
+    complex64 image, gamma=0 is iq_beamform's image in another order of operations.  At most 256 elements.  Arguments and the host /
+    DeviceBuffer rule as capon_beamform: host arrays in -> pbrt_coherence_beamform and a host array out; `iq` a complex DeviceBuffer ->
+    pbrt_coherence_beamform_dev (or _table_dev with `table`), queued, a DeviceBuffer out.  There is no receive window."""
+    shape = tuple(iq.shape) if _is_dev(iq) else np.shape(iq)
+    E = shape[1] if len(shape) == 3 else 0   # (any other shape is _beamform's ValueError)
+    return _beamform(iq, tx_delays, elem, x, z, bool(tables), fs_iq, sound_speed, method="iq",
+                     demod_freq=_checked_demod_freq(float(demod_freq)), t0=t0, f_number=f_number, interpolation=interpolation,
+                     compound=compound, out=out, table=table, coherence=_checked_coherence(kind, lag_prop, half_kernel, gamma, int(E)))
 
 
 _SCAN_METHODS = ("das", "pdas", "fdmas", "iq")
@@ -692,6 +755,7 @@ class DelayAndSum:
     and parity with it is unpinned, as everywhere in this file.  A setup that cannot be beamformed (an unknown window, an alpha outside
     (0, 1], a window with f_number 0) is a ValueError of beamform()."""
     _method = "das"
+    real_image = False   # the image of beamform() is what compute_envelope detects (True: it is a detection image already, D26)
 
     def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", is_iq=False, rx_apodization="boxcar",
                  rx_apodization_alpha=0.5):
@@ -932,6 +996,75 @@ class Capon(DelayAndSum):
         return f"Capon(MI355X, {self.setups})"
 
 
+class _CoherenceBeamformer(DelayAndSum):
+    """what ShortLagSpatialCoherence and CoherenceFactor share (DESIGN D26): always I/Q, no receive window, a GridScan or a PolarScan,
+    and the request through coherence_beamform by the class's kind"""
+    _kind = None
+
+    def set_is_iq(self, flag):
+        if not flag:
+            raise NotImplementedError(f"{type(self).__name__}: RF (real) data are not built -- the coherence is defined on I/Q samples "
+                                      "(DESIGN D26); demodulate them first (rf2iq)")
+        self.setups["is_iq"] = True
+
+    def _request(self, data, scan, out, table):
+        ai, su, dev = self.acquisition_info, self.setups, _is_dev(data)
+        if su["rx_apodization"] != "boxcar":
+            raise ValueError(f"{type(self).__name__} takes no receive window: rx_apodization must be 'boxcar', got {su['rx_apodization']!r}")
+        ex = self.probe_dev if dev and self.probe_dev is not None else self.probe.das_elements
+        polar, gx, gz = _scan_tables(scan, dev)
+        return coherence_beamform(data, ai["delays"], ex, gx, gz, ai["sampling_freq"], ai["sound_speed"], self.demod_freq(),
+                                  kind=self._kind, lag_prop=su.get("lag_prop", 0.3), half_kernel=su.get("half_kernel", 0),
+                                  gamma=su.get("gamma", 1.0), t0=ai.get("t0", 0.0) or 0.0, f_number=su["f_number"],
+                                  interpolation=su["interpolation"], compound=su["compound"], out=out, table=table, tables=polar)
+
+    def __str__(self):
+        return f"{type(self).__name__}(MI355X, {self.setups})"
+
+
+class ShortLagSpatialCoherence(_CoherenceBeamformer):
+    """Short-lag spatial coherence (Lediju, Trahey, Byram, Dahl 2011) in the shape of DelayAndSum (DESIGN D26).  NOT one of ultraspy's
+    beamformers: the class, its setup names and the arithmetic are this build's own (include/pbrt_hip.h "spatial coherence").  Setups:
+    DelayAndSum's, `lag_prop` (the lags summed over the number of elements a pixel uses, (0, 1]) and `half_kernel` (the axial kernel is
+    2 half_kernel + 1 samples, 0 .. 4).  Always I/Q; no receive window; a GridScan or a PolarScan.  The image is float32 and already a
+    detection image: compute_envelope returns it as it is, and beamform_packet (whose ensemble is complex) is a ValueError."""
+    _kind = "slsc"
+    real_image = True   # (us_render: the image goes straight into the envelope buffer)
+
+    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", lag_prop=0.3, half_kernel=1, is_iq=True,
+                 rx_apodization="boxcar", rx_apodization_alpha=0.5):
+        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound, is_iq=is_iq,
+                         rx_apodization=rx_apodization, rx_apodization_alpha=rx_apodization_alpha)
+        self.setups.update(lag_prop=lag_prop, half_kernel=half_kernel)
+
+    def beamform_packet(self, d_data, scan, out=None):
+        raise ValueError("ShortLagSpatialCoherence.beamform_packet: the ensemble buffer is complex and an SLSC image is real -- "
+                         "beamform the frames one by one")
+
+    def compute_envelope(self, d_output, scan=None, out=None):
+        """the image itself: SLSC is a detection image already (`out`: the image is copied there)"""
+        if out is None or out is d_output:
+            return d_output
+        if _is_dev(out):
+            raise ValueError("ShortLagSpatialCoherence.compute_envelope: beamform(..., out=) writes the image where it is wanted")
+        np.copyto(out, d_output.numpy() if _is_dev(d_output) else d_output)
+        return out
+
+
+class CoherenceFactor(_CoherenceBeamformer):
+    """Delay-and-sum weighted by the coherence factor (Mallart and Fink 1994; Hollman, Rigby, O'Donnell 1999) in the shape of DelayAndSum
+    (DESIGN D26).  NOT one of ultraspy's beamformers: the class, its setup name and the arithmetic are this build's own
+    (include/pbrt_hip.h "spatial coherence").  Setups: DelayAndSum's and `gamma` (the exponent of the weight, [0, 4]; 0 is delay-and-sum).
+    Always I/Q; no receive window; a GridScan or a PolarScan; compute_envelope is the modulus."""
+    _kind = "cf"
+
+    def __init__(self, on_gpu=True, f_number=1.0, interpolation="linear", compound="sum", gamma=1.0, is_iq=True,
+                 rx_apodization="boxcar", rx_apodization_alpha=0.5):
+        super().__init__(on_gpu=on_gpu, f_number=f_number, interpolation=interpolation, compound=compound, is_iq=is_iq,
+                         rx_apodization=rx_apodization, rx_apodization_alpha=rx_apodization_alpha)
+        self.setups.update(gamma=gamma)
+
+
 class PDelayAndSum(_NonlinearBeamformer):
     """p-DAS (Polichetti et al. 2018): per transmission the signed p-th roots of the delayed samples are summed and the sum is raised
     back to the p-th power, sign kept; band-pass around the carrier.  1 <= p <= 8; p = 1 is DelayAndSum."""
@@ -991,6 +1124,7 @@ class _UsRenderRequest:
                 self.probe.geometry_type, self.probe.radius, self.probe.opening_angle,   # d_ex: positions, or an arc's element table
                 None if self.taps is None else self.taps.tobytes(),      # d_taps, and d_nl exists
                 self.iq, self.D if self.iq else 1,                       # d_iq, d_bf_iq exist; the decimated length of d_iq
+                self.bf.real_image,                                      # d_bf_iq does not exist: the image goes to d_env (D26)
                 None if self.lp is None else self.lp.tobytes(),          # d_iq_taps
                 self.theta_range if self.polar else None,                # d_px, d_pz: the sector's angles ...
                 len(self.scan.thetas) if self.polar else None)           # ... and their count: the shapes of d_bf, d_env_sec
@@ -1092,8 +1226,11 @@ def _form_image(rq, data, delays, b):
     bf.automatic_setup(rq.info(delays), rq.probe)                                                      # :175
     if rq.iq:                                                                                          # D20: baseband, then complex DAS
         data = rf2iq(data, rq.f_demod, integ.fs, decimation=rq.D, taps=b.d_iq_taps if dev else rq.lp, out=b.d_iq)
-    img = bf.beamform(data if dev else data[np.newaxis], scan, out=b.d_bf_iq if rq.iq else b.d_bf, table=b.d_table)      # :204
-    env = bf.compute_envelope(img, scan, out=b.d_env_sec if rq.polar else b.d_env)                     # :205 (I/Q: the modulus)
+    d_env = b.d_env_sec if rq.polar else b.d_env
+    # (D26: a beamformer with a real image -- SLSC -- writes its detection image where the envelope goes, and there is no envelope step)
+    img = bf.beamform(data if dev else data[np.newaxis], scan, out=d_env if bf.real_image else b.d_bf_iq if rq.iq else b.d_bf,
+                      table=b.d_table)                                                                 # :204
+    env = img if bf.real_image else bf.compute_envelope(img, scan, out=d_env)                          # :205 (I/Q: the modulus)
     if not dev:
         env = env.astype(np.float32)                                                                   # :207
     if rq.polar:                                                                                       # D21: sector -> the grid
@@ -1154,7 +1291,7 @@ class _RenderPlan:
         if rq.iq:
             self.d_iq_taps = _capi.DeviceBuffer.from_host(cx, rq.lp)
             self.d_iq = _capi.DeviceBuffer(cx, (A, E, -(-T // rq.D)), np.complex64)
-            self.d_bf_iq = _capi.DeviceBuffer(cx, (nx, nz), np.complex64)
+            self.d_bf_iq = None if rq.bf.real_image else _capi.DeviceBuffer(cx, (nx, nz), np.complex64)   # (D26: a real image goes to d_env)
         self.graph = self.graph_key = self.warm_key = self.no_graph_key = None
 
     @classmethod

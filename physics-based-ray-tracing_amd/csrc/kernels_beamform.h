@@ -6,6 +6,7 @@
 #include "../../include/pbrt_hip.h"
 #include "bf_request.h"
 #include "capon_request.h"  // the limits of Capon and the subarray rule: CAPON_MAX_L, CAPON_MAX_E, capon_lm
+#include "coherence_request.h"  // the limits of SLSC / CF and the lag rule: COH_MAX_E, COH_MAX_H, COH_MAX_LAG, coherence_lags
 #include "img_request.h" // the limits of the image steps: FIR_MAX_K, RF2IQ_MAX_D, ENV_MAX_N, ENV_MAX_BLOCKS, PULSE_MAX_K, env_even_len
 #include "doppler_request.h"  // the limits, the tile and the weights of the Doppler steps: DOPPLER_*, DopplerWeights
 #include "device_math.h"
@@ -715,6 +716,237 @@ __global__ __launch_bounds__(64 * DAS_SPLIT) void k_capon_beamform(pbrt_das_para
             acc_im += y_a.y;
         }
         if (lane == 0) out[pix] = p.compound_mean ? make_float2(acc / (float)A, acc_im / (float)A) : make_float2(acc, acc_im);
+    }
+}
+
+// ---- spatial coherence: SLSC and the coherence factor on I/Q data (DESIGN D26; the definition and the order of the sums: include/pbrt_hip.h) ----
+// Capon's gather with other arithmetic behind it: a WAVE owns a pixel, its lanes are elements in blocks of 64 and the delayed, turned
+// samples land at their rank in U(a) in the wave's part of LDS.  Called, as Capon calls them: das_tile_of, das_tile_pixel, das_flight /
+// das_first, das_aperture_of / das_in_aperture, DAS_DELAYED (which decides whether an element is in U(a) and hands over the centre sample)
+// and iq_rot / iq_turn; capon_wave_sync between a wave's LDS writes and its reads.  Four waves on one tile, wave w takes the pixels w,
+// w + 4, ...; no s_barrier, every loop bound is wave-uniform.
+//   SLSC  the gathering lane holds the 2 H + 1 kernel samples of its element in registers: it turns them, brings the row to order 1,
+//         sums P_k and divides, and only the unit row goes to LDS -- planes [h][k] of E pairs each, so that lane i's read of rank i + m is
+//         contiguous across the wave.  Then lanes are ranks: for every lag m the lanes' C(i, i + m) meet in a butterfly BEFORE the
+//         division by N - m (so that R(m) of traces that are +-1 is exact), rank i < 64 keeps its own row in registers.
+//   CF    H = 0: one plane; the aperture is brought to order 1 by one power of two as in Capon, S and Q are one pass and one butterfly.
+// LDS: dynamic, 4 waves x E x (2 H + 1) pairs from the request (coherence_request.h) -- 6 KB at 64 elements and H = 1, 72 KB at the limits.
+// out: floats [nx][nz] for SLSC, pairs for CF (the launch hands every family the pixel type of its samples: SLSC narrows it here).
+template <uint32_t INTERP>
+DEV float2 coh_sample(const float2 *__restrict__ trace, uint32_t T, int64_t j, float w) {
+    if (INTERP == PBRT_DAS_NEAREST) return (j >= 0 && j <= (int64_t)T - 1) ? trace[j] : float2{};
+    if (j >= 0 && j < (int64_t)T - 1) return das_lerp(w, trace[j], trace[j + 1]);
+    if (j == (int64_t)T - 1 && w == 0.0f) return trace[j];
+    return float2{};
+}
+// the power of two that brings `big` to order 1, and its inverse (Capon's rule: a NaN is no maximum; an infinity stays one)
+DEV void coh_scale(float big, float *down, float *up) {
+    const uint32_t ex = min(max((__float_as_uint(big) >> 23) & 0xffu, 1u), 253u);
+    *down = __uint_as_float((254u - ex) << 23);
+    *up = __uint_as_float(ex << 23);
+}
+DEV float coh_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+#define COH_MAX_K (2u * COH_MAX_H + 1u)
+// host: a launch may ask for 64 KB of dynamic LDS as it is; one that needs more (beyond 227 elements at H = 4) first raises its kernel
+// instance's limit to the worst case of the request's limits, 72 KB.  The limit belongs to the function, not to a context, and is never
+// lowered: nothing is cached, and the call is made on those rare launches only.
+template <class Kernel>
+static hipError_t coh_allow_lds(Kernel kernel, size_t lds) {
+    if (lds <= 64u * 1024u) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(DAS_SPLIT * COH_MAX_E * COH_MAX_K * 8u));
+}
+template <uint32_t INTERP, bool TABLE, bool CONVEX, uint32_t KIND>
+__global__ __launch_bounds__(64 * DAS_SPLIT) void k_coherence_beamform(pbrt_das_params p, DasGrid grid, const float2 *__restrict__ data,
+                                                                       const float *__restrict__ tx, const float *__restrict__ elem_x,
+                                                                       const float *__restrict__ gx, const float *__restrict__ gz,
+                                                                       const double *__restrict__ ttx, float2 *__restrict__ out, float f_d,
+                                                                       float prm, uint32_t H) {  // prm: lag_prop (SLSC), gamma (CF)
+    extern __shared__ __attribute__((aligned(16))) float2 s_coh[];  // [DAS_SPLIT][2 H + 1][E]
+    constexpr bool SLSC = KIND == PBRT_COH_SLSC;
+    uint32_t tile_x, tile_z;
+    if (!das_tile_of(grid, blockIdx.x, &tile_x, &tile_z)) return;
+    const uint32_t A = p.n_angles, E = p.n_elements, T = p.time_samples;
+    if (E > COH_MAX_E || H > COH_MAX_H || (!SLSC && H != 0u)) return;  // (coherence_request refuses them: a rank never leaves its plane)
+    const uint32_t K = 2u * H + 1u;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    float2 *sv = s_coh + (size_t)wave * K * E;
+    float *outf = reinterpret_cast<float *>(out);
+    const auto zero = [&](size_t pix) {
+        if (SLSC)
+            outf[pix] = 0.0f;
+        else
+            out[pix] = float2{};
+    };
+    const double inv_c = 1.0 / (double)p.sound_speed, fs = (double)p.fs, t0 = (double)p.t0;
+    DasPixel lp;
+    const uint64_t seen = das_tile_pixel<CONVEX>(p, grid.tab, tile_x, tile_z, lane, elem_x, gx, gz, &lp);
+    if (seen == 0ull) {  // exact zeros
+        if (lp.valid && wave == 0) zero((size_t)lp.ix * p.nz + lp.iz);
+        return;
+    }
+    const double x_l = lp.x, z_l = lp.z;
+    for (uint32_t px = wave; px < DAS_TILE * DAS_TILE; px += DAS_SPLIT) {
+        const uint32_t ix = tile_x * DAS_TILE + (px >> 3), iz = tile_z * DAS_TILE + (px & 7u);
+        if (ix >= p.nx || iz >= p.nz) continue;
+        const size_t pix = (size_t)ix * p.nz + iz;
+        if (!((seen >> px) & 1ull)) {  // no element of the line reaches it
+            if (lane == 0) zero(pix);
+            continue;
+        }
+        const double x = das_lane_f64(x_l, px), z = das_lane_f64(z_l, px), zz = z * z;
+        const DasAperture ap = das_aperture_of<false>(p.f_number, das_half_ap(p.f_number, z));
+        float acc = 0.0f, acc_im = 0.0f;
+        for (uint32_t a = 0; a < A; ++a) {
+            // first arrival of the emitted wavefront at the pixel (Capon's: the table, or the wave-wide f64 minimum)
+            double tmin = 1e300;
+            if (TABLE) {
+                tmin = ttx[(size_t)a * p.nx * p.nz + pix];
+            } else {
+                for (uint32_t eb = 0; eb < E; eb += 64u) {
+                    const uint32_t e = min(eb + lane, E - 1u);
+                    const double dx = x - (double)elem_x[CONVEX ? 4u * e : e];
+                    const double dz = CONVEX ? z - (double)elem_x[4u * e + 1u] : 0.0;
+                    tmin = das_first(tmin, (double)tx[(size_t)a * E + e], das_flight<CONVEX>(dx, zz, dz, inv_c));
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) tmin = fmin(tmin, __shfl_xor(tmin, off));
+            }
+            const DasPos tp = INTERP == PBRT_DAS_LINEAR ? das_split((tmin - t0) * fs) : DasPos{0, 0.0f};
+            capon_wave_sync();  // the reads of the transmission before are behind the writes below
+            // gather: v_k[h] = rot_e s_k[h] at the rank k of e in U(a); SLSC: as the unit row u_k[h]
+            uint32_t N = 0;
+            for (uint32_t eb = 0; eb < E; eb += 64u) {
+                const uint32_t e = eb + lane, ec = min(e, E - 1u);
+                const double dx = x - (double)elem_x[CONVEX ? 4u * ec : ec];
+                const double dz = CONVEX ? z - (double)elem_x[4u * ec + 1u] : 0.0;
+                const double enx = CONVEX ? (double)elem_x[4u * ec + 2u] : 0.0, enz = CONVEX ? (double)elem_x[4u * ec + 3u] : 0.0;
+                const bool in_ap = e < E && das_in_aperture<CONVEX, false>(ap, dx, dz, enx, enz, nullptr);
+                const double d = das_flight<CONVEX>(dx, zz, dz, inv_c);
+                const DasPos dp = INTERP == PBRT_DAS_LINEAR ? das_split(d * fs) : DasPos{0, 0.0f};
+                bool use = false;
+                float2 s0 = float2{};
+                const float2 *trace = data + ((size_t)a * E + ec) * T;
+                const auto take = [&](float2 v) {
+                    s0 = v;
+                    use = true;
+                };
+                DAS_DELAYED(INTERP, trace, T, in_ap, tmin, d, t0, fs, tp, dp, take);
+                const uint64_t users = __ballot(use);
+                const uint32_t rank = N + (uint32_t)__popcll(users & ((1ull << lane) - 1ull));
+                N += (uint32_t)__popcll(users);
+                if (!use) continue;
+                const float2 rot_e = iq_rot((double)f_d * d);
+                if (!SLSC) {
+                    sv[rank] = iq_turn(rot_e, s0);
+                    continue;
+                }
+                // where the centre lies, as DAS_DELAYED found it (in the trace: `use`), and the weight every kernel sample shares
+                int64_t ctr;
+                float w = 0.0f;
+                if (INTERP == PBRT_DAS_NEAREST) {
+                    ctr = (int64_t)rint((tmin + d - t0) * fs);
+                } else {
+                    const float fr = tp.f + dp.f, fl = floorf(fr);
+                    w = fr - fl;
+                    ctr = (int64_t)(uint32_t)(tp.i + dp.i + (int32_t)fl);
+                }
+                float2 row[COH_MAX_K];
+                float big = 0.0f;
+#pragma unroll
+                for (uint32_t h = 0; h < COH_MAX_K; ++h) {
+                    row[h] = float2{};
+                    if (h < K) {
+                        row[h] = iq_turn(rot_e, h == H ? s0 : coh_sample<INTERP>(trace, T, ctr + (int64_t)h - (int64_t)H, w));
+                        big = fmaxf(big, fmaxf(__builtin_fabsf(row[h].x), __builtin_fabsf(row[h].y)));
+                    }
+                }
+                float down, up, P = 0.0f;
+                coh_scale(big, &down, &up);
+#pragma unroll
+                for (uint32_t h = 0; h < COH_MAX_K; ++h) {
+                    if (h < K) {
+                        row[h] = make_float2(row[h].x * down, row[h].y * down);
+                        P = fma_(row[h].x, row[h].x, fma_(row[h].y, row[h].y, P));
+                    }
+                }
+                const float nrm = sqrtf(P);
+#pragma unroll
+                for (uint32_t h = 0; h < COH_MAX_K; ++h)
+                    if (h < K) sv[h * E + rank] = P == 0.0f ? float2{} : make_float2(row[h].x / nrm, row[h].y / nrm);
+            }
+            if (N == 0u) continue;  // y_a = 0
+            capon_wave_sync();
+            if constexpr (SLSC) {
+                const uint32_t M = coherence_lags(N, prm);
+                float2 own[COH_MAX_K];  // the row of rank `lane`
+#pragma unroll
+                for (uint32_t h = 0; h < COH_MAX_K; ++h) own[h] = (h < K && lane < N) ? sv[h * E + lane] : float2{};
+                float y = 0.0f;
+                for (uint32_t m = 1; m <= M; ++m) {
+                    float c = 0.0f;
+                    if (lane + m < N) {
+                        float t = 0.0f;
+#pragma unroll
+                        for (uint32_t h = 0; h < COH_MAX_K; ++h) {
+                            if (h < K) {
+                                const float2 b = sv[h * E + lane + m];
+                                t = fma_(own[h].x, b.x, fma_(own[h].y, b.y, t));
+                            }
+                        }
+                        c += t;
+                    }
+                    for (uint32_t ib = 64u; ib + m < N; ib += 64u) {
+                        const uint32_t i = ib + lane;
+                        if (i + m < N) {
+                            float t = 0.0f;
+                            for (uint32_t h = 0; h < K; ++h) {
+                                const float2 u = sv[h * E + i], b = sv[h * E + i + m];
+                                t = fma_(u.x, b.x, fma_(u.y, b.y, t));
+                            }
+                            c += t;
+                        }
+                    }
+                    y += coh_wave_sum(c) / (float)(N - m);
+                }
+                acc += y;
+            } else {
+                float big = 0.0f;
+                for (uint32_t kb = 0; kb < N; kb += 64u)
+                    if (kb + lane < N) big = fmaxf(big, fmaxf(__builtin_fabsf(sv[kb + lane].x), __builtin_fabsf(sv[kb + lane].y)));
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) big = fmaxf(big, __shfl_xor(big, off));
+                float down, up, sx = 0.0f, sy = 0.0f, q = 0.0f;
+                coh_scale(big, &down, &up);
+                for (uint32_t kb = 0; kb < N; kb += 64u) {
+                    if (kb + lane < N) {
+                        const float2 v = make_float2(sv[kb + lane].x * down, sv[kb + lane].y * down);
+                        sx += v.x;
+                        sy += v.y;
+                        q = fma_(v.x, v.x, fma_(v.y, v.y, q));
+                    }
+                }
+                sx = coh_wave_sum(sx);
+                sy = coh_wave_sum(sy);
+                q = coh_wave_sum(q);
+                const float cf = q == 0.0f ? 0.0f : fma_(sx, sx, sy * sy) / ((float)N * q);
+                const float wgt = prm == 0.0f ? 1.0f : prm == 1.0f ? cf : powf(cf, prm);
+                const float2 y_a = iq_turn(iq_rot((double)f_d * tmin), make_float2(wgt * sx * up, wgt * sy * up));
+                acc += y_a.x;
+                acc_im += y_a.y;
+            }
+        }
+        if (lane != 0) continue;
+        if constexpr (SLSC) {
+            const float v = p.compound_mean ? acc / (float)A : acc;
+            outf[pix] = (v > 0.0f || v != v) ? v : 0.0f;
+        } else {
+            out[pix] = p.compound_mean ? make_float2(acc / (float)A, acc_im / (float)A) : make_float2(acc, acc_im);
+        }
     }
 }
 

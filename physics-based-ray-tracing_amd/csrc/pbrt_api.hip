@@ -2342,8 +2342,9 @@ static int launched(pbrt_ctx *c) {  // the end of every function that queues ker
         return &__VA_ARGS__;                                                             \
     }
 static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const float *dt, const float *de, const float *dx, const float *dz,
-                       float *dout, const double *ttx, const CaponRequest *capon = nullptr) {
+                       float *dout, const double *ttx, const CaponRequest *capon = nullptr, const CoherenceRequest *coh = nullptr) {
     const pbrt_das_params *p = rq.das;
+    int rc = PBRT_OK;
     ImgTimer tm(c, IMG_DAS);
     DasGrid g;
     const uint32_t blocks = das_grid(&g, p->nx, p->nz, rq.tab);
@@ -2352,13 +2353,19 @@ static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const 
     const auto family = [&](auto method) {
         constexpr uint32_t M = decltype(method)::value;
         typedef typename DasSample<M>::type Sample;
-        const auto launch = [&](auto pick, auto... own) {
-            hipLaunchKernelGGL(with_flags(pick, p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe), dim3(blocks), dim3(64 * DAS_SPLIT),
-                               0, c->stream, *p, g, reinterpret_cast<const Sample *>(dd), dt, de, dx, dz, ttx, reinterpret_cast<Sample *>(dout), own...);
+        const auto launch_lds = [&](size_t lds, auto pick, auto... own) {  // lds: the dynamic LDS of the launch
+            const auto kernel = with_flags(pick, p->interpolation != PBRT_DAS_NEAREST, ttx != nullptr, rq.probe);
+            if (const hipError_t e = coh_allow_lds(kernel, lds); e != hipSuccess)
+                return (void)(rc = c->fail(PBRT_E_DEVICE, "hipFuncSetAttribute(k_coherence_beamform, %zu bytes of LDS): %s", lds, hipGetErrorString(e)));
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * DAS_SPLIT), lds, c->stream, *p, g, reinterpret_cast<const Sample *>(dd), dt, de, dx,
+                               dz, ttx, reinterpret_cast<Sample *>(dout), own...);
         };
+        const auto launch = [&](auto pick, auto... own) { launch_lds(0, pick, own...); };
         //  the request                                    its kernel                              the kernel's own arguments
         if constexpr (M == BF_IQ) {  // (Capon's samples are I/Q pairs: the switch below sends every Capon request here)
             if (capon)                              return launch(DAS_PICK(k_capon_beamform<I, T, X>),    rq.pw, capon->l_prop, capon->delta_l);  // (D23)
+            if (coh && coh->kind == PBRT_COH_SLSC)  return launch_lds(coh->lds_bytes, DAS_PICK(k_coherence_beamform<I, T, X, PBRT_COH_SLSC>), rq.pw, coh->lag_prop, coh->half_kernel);  // (D26)
+            if (coh)                                return launch_lds(coh->lds_bytes, DAS_PICK(k_coherence_beamform<I, T, X, PBRT_COH_CF>),   rq.pw, coh->gamma, coh->half_kernel);
         }
         if (rq.window != PBRT_APOD_BOXCAR)          return launch(DAS_PICK(k_apod_beamform<I, T, X, M>),  rq.pw, rq.a0, rq.alpha);                // (D22)
         if constexpr (M == BF_IQ)                   return launch(DAS_PICK(k_iq_beamform<I, T, X>),       rq.pw);  // pw: the demodulation frequency
@@ -2367,12 +2374,13 @@ static int das_enqueue(pbrt_ctx *c, const BfRequest &rq, const float *dd, const 
     };
     // (bf_request admits four methods and capon_request I/Q alone; what they would refuse goes where it went before this table was one:
     // a Capon request to Capon whatever its method, an unknown method to p-DAS)
-    switch (capon ? (uint32_t)PBRT_SCAN_IQ : rq.method) {
+    switch (capon || coh ? (uint32_t)PBRT_SCAN_IQ : rq.method) {
         case PBRT_SCAN_IQ: family(std::integral_constant<uint32_t, BF_IQ>{}); break;
         case PBRT_BF_FDMAS: family(std::integral_constant<uint32_t, PBRT_BF_FDMAS>{}); break;
         default: family(std::integral_constant<uint32_t, PBRT_BF_PDAS>{}); break;
         case PBRT_SCAN_DAS: family(std::integral_constant<uint32_t, BF_DAS>{}); break;
     }
+    if (rc != PBRT_OK) return rc;
     c->img_das_bytes = ((uint64_t)p->n_angles * p->n_elements * p->time_samples + (uint64_t)p->nx * p->nz) * (rq.method == PBRT_SCAN_IQ ? 8 : 4);
     return launched(c);
 }
@@ -2431,15 +2439,15 @@ static int iq_env_enqueue(pbrt_ctx *c, const IqEnvRequest &rq, const float *din,
     return launched(c);
 }
 
-// The three bodies behind the 23 beamform and first-arrival entry points (capon: the request of pbrt_capon_*, else null).  Each entry point makes its request first (BF_REQUEST below):
+// The three bodies behind the 26 beamform and first-arrival entry points (capon / coh: the request of pbrt_capon_* / pbrt_coherence_*, else null).  Each entry point makes its request first (BF_REQUEST below):
 // a null context is PBRT_E_INVALID and touches nothing, a refused block is PBRT_E_INVALID with the text of the rule.
 // (d_tx_delays or d_table: the plain form passes its delays, the table form its first-arrival table, and the other one null)
 static int beamform_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_data, const void *d_elem, const void *d_x, const void *d_z,
-                        void *d_out, const void *d_tx_delays, const void *d_table, const CaponRequest *capon = nullptr) {
+                        void *d_out, const void *d_tx_delays, const void *d_table, const CaponRequest *capon = nullptr, const CoherenceRequest *coh = nullptr) {
     NEED(ctx, d_data && (d_tx_delays || d_table) && d_elem && d_x && d_z && d_out);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return das_enqueue(ctx, rq, (const float *)d_data, (const float *)d_tx_delays, (const float *)d_elem, (const float *)d_x,
-                       (const float *)d_z, (float *)d_out, (const double *)d_table, capon);
+                       (const float *)d_z, (float *)d_out, (const double *)d_table, capon, coh);
 }
 
 static int first_arrival_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_tx_delays, const void *d_elem, const void *d_x, const void *d_z,
@@ -2454,18 +2462,18 @@ static int first_arrival_dev(pbrt_ctx *ctx, const BfRequest &rq, const void *d_t
 }
 
 static int beamform_host(pbrt_ctx *ctx, const BfRequest &rq, const float *data, const float *tx_delays, const float *elem, const float *x,
-                         const float *z, float *out, const CaponRequest *capon = nullptr) {
+                         const float *z, float *out, const CaponRequest *capon = nullptr, const CoherenceRequest *coh = nullptr) {
     NEED(ctx, data && tx_delays && elem && x && z && out);
     const pbrt_das_params *p = rq.das;
-    const size_t width = rq.method == PBRT_SCAN_IQ ? 2u : 1u;  // floats per sample and per pixel
+    const size_t width = rq.method == PBRT_SCAN_IQ ? 2u : 1u, out_width = coh ? coh->width : width;  // floats per sample, and per pixel (an SLSC image is real)
     const size_t nd = (size_t)p->n_angles * p->n_elements * p->time_samples * width, ne = (size_t)p->n_angles * p->n_elements;
     const uint32_t n = p->nx * p->nz;
     const size_t nel = (size_t)p->n_elements * (rq.probe ? 4u : 1u);
     const size_t ngx = rq.tab ? (size_t)n : p->nx, ngz = rq.tab ? (size_t)n : p->nz;  // axes, or the two pixel tables
     STAGED_BEGIN(ctx, n == 0);
     auto [dd, dt, de, dx, dz, dout] =
-        S.arrays(stage_in(data, nd), stage_in(tx_delays, ne), stage_in(elem, nel), stage_in(x, ngx), stage_in(z, ngz), stage_out(out, n * width));
-    STAGED_RUN(S, das_enqueue(ctx, rq, dd, dt, de, dx, dz, dout, nullptr, capon));
+        S.arrays(stage_in(data, nd), stage_in(tx_delays, ne), stage_in(elem, nel), stage_in(x, ngx), stage_in(z, ngz), stage_out(out, n * out_width));
+    STAGED_RUN(S, das_enqueue(ctx, rq, dd, dt, de, dx, dz, dout, nullptr, capon, coh));
 }
 // entering an entry point of the image chain: declares rq, the request its maker fills (bf_request.h, img_request.h)
 #define MAKE_REQUEST(ctx, Request, maker, ...) \
@@ -2530,6 +2538,18 @@ int pbrt_capon_beamform_table_dev(pbrt_ctx *ctx, const pbrt_capon_params *p, con
                                   const void *d_px, const void *d_pz, void *d_out) {
     MAKE_REQUEST(ctx, CaponRequest, capon_request, p);
     return beamform_dev(ctx, rq.bf, d_iq, d_elem, d_px, d_pz, d_out, nullptr, d_table, &rq);
+}
+int pbrt_coherence_beamform(pbrt_ctx *ctx, const pbrt_coherence_params *p, const float *iq, const float *tx_delays, const float *elem, const float *px, const float *pz, float *out) {
+    MAKE_REQUEST(ctx, CoherenceRequest, coherence_request, p);
+    return beamform_host(ctx, rq.bf, iq, tx_delays, elem, px, pz, out, nullptr, &rq);
+}
+int pbrt_coherence_beamform_dev(pbrt_ctx *ctx, const pbrt_coherence_params *p, const void *d_iq, const void *d_tx_delays, const void *d_elem, const void *d_px, const void *d_pz, void *d_out) {
+    MAKE_REQUEST(ctx, CoherenceRequest, coherence_request, p);
+    return beamform_dev(ctx, rq.bf, d_iq, d_elem, d_px, d_pz, d_out, d_tx_delays, nullptr, nullptr, &rq);
+}
+int pbrt_coherence_beamform_table_dev(pbrt_ctx *ctx, const pbrt_coherence_params *p, const void *d_iq, const void *d_table, const void *d_elem, const void *d_px, const void *d_pz, void *d_out) {
+    MAKE_REQUEST(ctx, CoherenceRequest, coherence_request, p);
+    return beamform_dev(ctx, rq.bf, d_iq, d_elem, d_px, d_pz, d_out, nullptr, d_table, nullptr, &rq);
 }
 int pbrt_scan_first_arrival_dev(pbrt_ctx *ctx, const pbrt_scan_params *p, const void *d_tx_delays, const void *d_elem, const void *d_px,
                                 const void *d_pz, void *d_table) {
